@@ -5,8 +5,13 @@ Metric (BASELINE.json): DoFs/s for the fp64 Laplace matvec + V-cycle of poisson_
 One *step* = the two operator applications one PCG iteration of the reference performs on the
 finest level (multigrid_solver.h:483-510): one fp64 `LaplaceOperator::vmult` (matrix_dp) followed
 by one fp64 V-cycle (`MultigridSolver::vmult`: Chebyshev(3) pre/post smoothing, residual,
-restriction, coarse solve, prolongation).  `value` = global DoFs / time per step; the matvec-only
-and V-cycle-only rates are reported next to it (`matvec_dofs_per_s`, `vcycle_dofs_per_s`).
+restriction, coarse solve, prolongation).  `value` = global DoFs / time per step, `ms_per_step` the
+milliseconds one of the --steps timed steps took.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs if given and prints the JSON line.
+--full adds, after the timed region: the matvec-only and V-cycle-only rates (`matvec_dofs_per_s`,
+`vcycle_dofs_per_s`), the per-kernel roofline figures (a profiled pass of its own), the end-to-end
+verification, the CPU baseline and, for the default workload on one GPU, the secondary configurations.
 
 N = 1: BASELINE config 1 -- 128^3 cells, 135 005 697 DoFs, one MI355X, inputs resident in HBM.
 N > 1: domain decomposition, one process per GPU over RCCL (torch.distributed "nccl"), interface
@@ -20,7 +25,7 @@ N > 1: domain decomposition, one process per GPU over RCCL (torch.distributed "n
 WORLD_SIZE / MASTER_ADDR / MASTER_PORT set) and relays rank 0's JSON line; under
 torch.distributed.run the ranks are already there and --gpus must equal WORLD_SIZE.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--cells 128] [--degree 4]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--cells 128] [--degree 4] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -42,8 +47,17 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achiev
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="number of timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: matvec-only and V-cycle-only rates, "
+                         "per-kernel roofline figures (a profiled pass of --steps steps of its own), the end-to-end "
+                         "verification, the CPU baseline and the secondary configurations.  Without it a run sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: the matvec result "
+                         "(matvec_y) and the V-cycle result (vcycle_z), each a fixed seeded sample of at most 2^21 "
+                         "entries (per rank: 2^21 / N, files <name>_rank<r>.npy for N > 1)")
     ap.add_argument("--cells", type=int, default=128, help="cells per direction of the finest level")
     ap.add_argument("--degree", type=int, default=4)
     ap.add_argument("--smoother-degree", type=int, default=3)
@@ -54,13 +68,13 @@ def parse():
                          "fourth_kind for MultigridSolver<dim,p,double,double> (:951-952), first_kind for fp32; the work "
                          "per V-cycle is the same")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the end-to-end check after the timed region (PCG iteration count and L2 error of the "
-                         "manufactured problem, README.md:135-159)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the end-to-end check after the timed region (PCG iteration count and L2 error of "
+                         "the manufactured problem, README.md:135-159)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary configurations measured after the headline (N = 1, default workload only): "
-                         "BASELINE configs 3-5 and the reference's default fp32 V-cycle, each with its own time, roofline "
-                         "fraction and check")
+                    help="--full: skip the secondary configurations measured after the headline (N = 1, default workload "
+                         "only): BASELINE configs 3-5 and the reference's default fp32 V-cycle, each with its own time, "
+                         "roofline fraction and check")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="context option for A/B timings of numerically equivalent code paths (include/mgx.h, "
                          "mgx_context_set_option); recorded in the JSON line")
@@ -75,7 +89,10 @@ def parse():
     ap.add_argument("--cpu-cells", type=int, default=0,
                     help="finest level of the CPU baseline sample (0: the bench mesh itself if the host has the memory "
                          "and the cores for it, else 64)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def split_size(cells):
@@ -162,6 +179,26 @@ def verify(args, solver, cube, world, decomposed, transport, native):
     if not ok:
         sys.stderr.write("bench.py: verification FAILED: %s\n" % json.dumps(res))
     return res
+
+
+DUMP_ENTRIES = 1 << 21   # per output array, over all ranks: 2 arrays x 2^21 x 8 B = 32 MiB in all
+DUMP_SEED = 20251016
+
+
+def dump_outputs(directory, rank, world, vectors):
+    """--dump-outputs: the device vectors the timed path handed back in its last step, downloaded and written as
+    directory/<name>.npy in their own number type.  A vector longer than its share of DUMP_ENTRIES is written as the
+    sample at sorted indices drawn without replacement by a generator seeded with DUMP_SEED + rank: the same entries
+    for the same arguments, so that two builds compare output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    cap = max(1, DUMP_ENTRIES // world)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, vec in vectors.items():
+        a = vec.download()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED + rank).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(directory, name + suffix + ".npy"), a)
 
 
 
@@ -401,8 +438,8 @@ def dry_run(args, rank, world, dist):
         print(json.dumps({"metric": "DoFs/s for Laplace matvec + V-cycle, poisson_cube p=%d fp64" % args.degree,
                           "value": None, "unit": "DoFs/s", "n_gpus": world, "dry_run": True, "exchange_ok": ok,
                           "scaling": args.scaling if world > 1 else "weak",
-                          # what the real run checks after its timed region (verify()), unless --no-verify
-                          "verify": None if args.no_verify else
+                          # what the real run checks after its timed region (verify()): with --full, unless --no-verify
+                          "verify": None if args.no_verify or not args.full else
                           {"expected": ({"cg_its": README_P4[args.cells][0], "l2_error": README_P4[args.cells][1]}
                                         if args.degree == 4 and args.cells in README_P4 and
                                         (world == 1 or args.scaling == "strong") else None), "ok": None},
@@ -515,22 +552,34 @@ def main():
     for _ in range(args.warmup):
         step()
     # ---- the timed region: exactly K steps, bracketed by barrier + synchronize ----
-    A.set_profiled(True)
-    solver.matrix(lmax).set_profiled(True)
-    ctx.profile_enable(True)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    prof = {form: ctx.profile_read(form) for form in range(10)}
-    ctx.profile_enable(False)
     if dist is not None:
         import torch
         t = torch.tensor([elapsed], device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        # every step recomputes y = A x and z = V-cycle(rhs) from the same inputs: this is what the last one left
+        dump_outputs(args.dump_outputs, rank, world, {"matvec_y": y, "vcycle_z": z})
+
+    prof = {}
+    if args.full:
+        # per-kernel figures: a profiled pass of its own (HIP events around every finest-level cell loop), after the
+        # timed region so that the headline is measured without the events
+        A.set_profiled(True)
+        solver.matrix(lmax).set_profiled(True)
+        ctx.profile_enable(True)
+        barrier()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        prof = {form: ctx.profile_read(form) for form in range(10)}
+        ctx.profile_enable(False)
 
     # secondary figures (outside the timed region): matvec-only and V-cycle-only
     def timed(fn, reps):
@@ -542,8 +591,9 @@ def main():
         ctx.sync()
         return (time.perf_counter() - t0) / reps
 
-    t_mv = timed(lambda: A.vmult(y, x), 20)
-    t_vc = timed(lambda: solver.vmult(z, rhs), 5)
+    if args.full:
+        t_mv = timed(lambda: A.vmult(y, x), 20)
+        t_vc = timed(lambda: solver.vmult(z, rhs), 5)
 
     ms_per_step = 1e3 * elapsed / args.steps
     total_dofs = global_dofs
@@ -624,31 +674,35 @@ def main():
                                "one %d^3-cell cube per GPU") % args.cells, transport)) if decomposed
                     else "%d independent replicas" % world),
                    "transport": transport if decomposed else None},
-        "matvec_dofs_per_s": total_dofs / t_mv, "vcycle_dofs_per_s": total_dofs / t_vc,
-        "matvec_ms": 1e3 * t_mv, "vcycle_ms": 1e3 * t_vc, "setup_s": t_setup,
-        "rhs_assembly": "host" if args.host_rhs else "device", "options": args.option or None,
-        "roofline": roof(2) or roof(0),
-        "roofline_matvec": roof(0),
-        # the other finest-level forms of the step (HIP events around every application, as above)
-        "roofline_forms": {NAMES[f]: {k: r[k] for k in ("achieved", "frac", "avg_launch_ms", "launches",
-                                                         "algorithmic_bytes_per_dof", "traffic")}
-                           for f in (1, 3, 5, 6, 7, 9) for r in [roof(f)] if r},
-        # the V-cycle as a whole against the fully fused model of SURVEY.md 8d: (10 n + 4.25) accesses per level DoF
-        # x 8/7 (level sum) = 313 B per fine DoF at n = 3 in fp64
-        "roofline_vcycle": (lambda b: {"bound": "hbm", "algorithmic_bytes_per_fine_dof": b,
-                                       "achieved": b * n_dofs / t_vc / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                       "frac": b * n_dofs / t_vc / 1e9 / HBM_PEAK_GBS})(
-            (10.0 * args.smoother_degree + 4.25) * (8.0 if vnum == mg.F64 else 4.0) * 8.0 / 7.0),
+        "setup_s": t_setup, "rhs_assembly": "host" if args.host_rhs else "device", "options": args.option or None,
+        "full": args.full,
     }
-    if not args.no_verify:
+    if args.full:
+        out.update({
+            "matvec_dofs_per_s": total_dofs / t_mv, "vcycle_dofs_per_s": total_dofs / t_vc,
+            "matvec_ms": 1e3 * t_mv, "vcycle_ms": 1e3 * t_vc,
+            "roofline": roof(2) or roof(0),
+            "roofline_matvec": roof(0),
+            # the other finest-level forms of the step (HIP events around every application, as above)
+            "roofline_forms": {NAMES[f]: {k: r[k] for k in ("achieved", "frac", "avg_launch_ms", "launches",
+                                                             "algorithmic_bytes_per_dof", "traffic")}
+                               for f in (1, 3, 5, 6, 7, 9) for r in [roof(f)] if r},
+            # the V-cycle as a whole against the fully fused model of SURVEY.md 8d: (10 n + 4.25) accesses per level
+            # DoF x 8/7 (level sum) = 313 B per fine DoF at n = 3 in fp64
+            "roofline_vcycle": (lambda b: {"bound": "hbm", "algorithmic_bytes_per_fine_dof": b,
+                                           "achieved": b * n_dofs / t_vc / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                           "frac": b * n_dofs / t_vc / 1e9 / HBM_PEAK_GBS})(
+                (10.0 * args.smoother_degree + 4.25) * (8.0 if vnum == mg.F64 else 4.0) * 8.0 / 7.0),
+        })
+    if args.full and not args.no_verify:
         out["verify"] = verify(args, solver, cube, world, decomposed, transport, native)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     failed = "verify" in out and not out["verify"]["ok"]
     solver.close()
     default_workload = (world == 1 and args.degree == 4 and args.cells == 128 and vnum == mg.F64 and not args.option and
                         polynomial == "first_kind" and args.smoother_degree == 3)
-    if default_workload and not args.no_secondary:
+    if args.full and default_workload and not args.no_secondary:
         for v in (x, y, z):
             v.free()
         t_sec = time.time()

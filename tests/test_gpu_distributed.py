@@ -126,7 +126,7 @@ def test_bench_launches_two_ranks_on_one_gpu():
     env = dict(os.environ, MGX_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--cells", "32", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, timeout=600)
+                          "--warmup", "1", "--full", "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.decode().strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["value"] > 0

@@ -10,11 +10,11 @@ stages=${@:-bench trace forms pmc sq p8 dg shell}
 for s in $stages; do
 case $s in
 bench)
-  python3 $R/bench.py > $O/bench_128cube_p4.json 2> $O/bench_128cube_p4.err
+  python3 $R/bench.py --full > $O/bench_128cube_p4.json 2> $O/bench_128cube_p4.err
   tail -1 $O/bench_128cube_p4.json | cut -c1-400 ;;
 trace)
   rm -rf $O/kt
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o t -- python3 $R/bench.py --no-cpu-baseline > $O/bench_profiled.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o t -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_profiled.log 2>&1
   cp $(find $O/kt -name "*kernel_stats.csv" | head -1) $O/kernel_stats_bench_128cube_p4.csv
   python3 $R/tools/summarize_trace.py $(find $O/kt -name "*kernel_trace.csv" | head -1) 2.0 > $O/kernel_trace_by_grid_128cube_p4.txt
   rm -rf $O/kt
@@ -47,10 +47,10 @@ p8)
   python3 $R/tools/make_traffic_json.py $(find $O/pmc8_FETCH_SIZE -name "*counter_collection.csv" | head -1) \
       $(find $O/pmc8_WRITE_SIZE -name "*counter_collection.csv" | head -1) 64 $O/pmc_traffic_64cube_p8.json 8
   rm -rf $O/pmc8_FETCH_SIZE $O/pmc8_WRITE_SIZE
-  python3 $R/bench.py --degree 8 --cells 64 --no-cpu-baseline > $O/bench_64cube_p8.json 2> $O/bench_64cube_p8.err
+  python3 $R/bench.py --full --degree 8 --cells 64 --no-cpu-baseline > $O/bench_64cube_p8.json 2> $O/bench_64cube_p8.err
   tail -1 $O/bench_64cube_p8.json | cut -c1-400
   rm -rf $O/kt8
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt8 -o t -- python3 $R/bench.py --degree 8 --cells 64 --no-cpu-baseline --steps 5 > $O/bench_p8_profiled.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt8 -o t -- python3 $R/bench.py --full --degree 8 --cells 64 --no-cpu-baseline --steps 5 > $O/bench_p8_profiled.log 2>&1
   python3 $R/tools/summarize_trace.py $(find $O/kt8 -name "*kernel_trace.csv" | head -1) 2.0 > $O/kernel_trace_by_grid_64cube_p8.txt
   rm -rf $O/kt8 ;;
 dg)

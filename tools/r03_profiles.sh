@@ -8,11 +8,11 @@ stages=${@:-bench trace pmc levels p8 f32 shell dg rank}
 for s in $stages; do
 case $s in
 bench)
-  python3 $R/bench.py > $O/bench_128cube_p4.json 2> $O/bench_128cube_p4.err
+  python3 $R/bench.py --full > $O/bench_128cube_p4.json 2> $O/bench_128cube_p4.err
   tail -1 $O/bench_128cube_p4.json | cut -c1-300 ;;
 trace)
   rm -rf $O/kt
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o t -- python3 $R/bench.py --no-cpu-baseline --no-verify > $O/bench_profiled.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o t -- python3 $R/bench.py --full --no-cpu-baseline --no-verify > $O/bench_profiled.log 2>&1
   cp $(find $O/kt -name "*kernel_stats.csv" | head -1) $O/kernel_stats_bench_128cube_p4.csv
   python3 $R/tools/summarize_trace.py $(find $O/kt -name "*kernel_trace.csv" | head -1) 1.0 > $O/kernel_trace_by_grid_128cube_p4.txt
   rm -rf $O/kt
@@ -29,10 +29,10 @@ levels)
   python3 $R/tools/vcycle_levels.py 128 4 > $O/vcycle_levels_128cube_p4.txt 2>&1
   cat $O/vcycle_levels_128cube_p4.txt ;;
 p8)
-  python3 $R/bench.py --degree 8 --cells 64 --no-cpu-baseline > $O/bench_64cube_p8.json 2> $O/bench_64cube_p8.err
+  python3 $R/bench.py --full --degree 8 --cells 64 --no-cpu-baseline > $O/bench_64cube_p8.json 2> $O/bench_64cube_p8.err
   tail -1 $O/bench_64cube_p8.json | cut -c1-300 ;;
 f32)
-  python3 $R/bench.py --vcycle-number f32 --no-cpu-baseline > $O/bench_128cube_p4_f32vcycle.json 2> $O/bench_f32.err
+  python3 $R/bench.py --full --vcycle-number f32 --no-cpu-baseline > $O/bench_128cube_p4_f32vcycle.json 2> $O/bench_f32.err
   tail -1 $O/bench_128cube_p4_f32vcycle.json | cut -c1-300 ;;
 shell)
   python3 $R/tools/shell_bench.py 4 5 6 > $O/hyper_shell6_matvec_p4.txt 2>&1
