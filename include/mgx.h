@@ -314,7 +314,14 @@ typedef struct
   /* children[8*parent + c] = fine-level cell index of child c (c = x + 2y + 4z) of coarse cell
    * `parent` (deal.II: cell->child(c)); host pointer, copied */
   const uint32_t *children;
-  /* prolong_1d[a*(p+1)+i], a in [0,2p]: coarse 1D basis i at the fine patch point a */
+  /* prolong_1d[a*(p+1)+i], a in [0,2p]: coarse 1D basis i at the fine patch point a.  The pipelined
+   * kernels and the fused residual + restriction / prolongation forms apply it in even-odd form, which
+   * holds only for an embedding symmetric under reversal (prolong_1d[(2p-a)(p+1)+p-i] equal to
+   * prolong_1d[a(p+1)+i], as for every mirror-symmetric node set: Gauss-Lobatto, equidistant).  Any other
+   * embedding -- a Lagrange basis on nodes that are not mirror-symmetric -- is applied by the first-version
+   * dense kernels instead, correct for every embedding and slower (no patch table, no fused forms).  Not
+   * where the restriction needs owner weights (see weight_shift below): those only the pipelined kernels
+   * apply, and there such an embedding is refused with MGX_ERR_UNSUPPORTED. */
   const double *prolong_1d;
   /* optional, may be NULL: weight_shift[27*parent + e] = log2(multiplicity) of patch entity e
    * (deal.II's weights_on_refined, 3^dim per cell), counting the parents of other ranks as well.

@@ -2674,6 +2674,50 @@ static int build_interface_transfer(mgx_transfer_s *tr, const mgx_transfer_desc 
   return MGX_OK;
 }
 
+// Whether the V-cycle (v_cycle_eager) forms the residual and its restriction in one pass of the fine level's cell
+// loop, and whether its first post-smoothing step forms x + P x_coarse on the fly: nullptr where it does, else why
+// not.  mgx_transfer_create traces the same answers (the smoother degree is known there only as "at least 1").
+// Levels on the one-launch schedule run the residual as one launch and the transfers as kernels of their own: the
+// fused forms need the eight colour launches, each as long as a brick's whole latency chain on such a level (2 M
+// DoFs: 63 instead of 147 us, 52 instead of 180 us) -- except the scratch form of the restriction, one launch itself.
+static const char *fused_restrict_blocker(const mgx_transfer_s *tr, const Tunables &tun)
+{
+  const BrickData &fb         = tr->fine->d.bricks;
+  const bool       one_launch = fb.fr.available() && fb.fr.n_classes == 1;
+  if (!tr->d.coarse_blocks)
+    return "no block table of the coarse level";
+  if (one_launch && !tr->d.coarse_scratch)
+    return "fine level on the one-launch schedule without the scratch form";
+  if (tun.no_fused_residual)
+    return "option no_fused_residual";
+  return nullptr;
+}
+
+// (p <= 4 on the two-class schedule: only from fused_prolong_min_bricks bricks on -- there the two launches + finish of
+// a Chebyshev step are each as long as a brick's latency chain; at p = 8 the prolongation kernel costs 0.18 ms on the
+// 17 M-DoF level and the fused form wins, 0.945 against 1.004 ms)
+static const char *fused_prolong_blocker(const mgx_transfer_s *tr, const Tunables &tun, int smoother_degree)
+{
+  const mgx_operator_t Af         = tr->fine;
+  const BrickData     &fb         = Af->d.bricks;
+  const bool           one_launch = fb.fr.available() && fb.fr.n_classes == 1;
+  if (!tr->d.coarse_blocks)
+    return "no block table of the coarse level";
+  if (!fb.item_map || Af->d.cells_form || !Af->d.separable)
+    return "fine level not on the macro-element kernel";
+  if (tun.no_fused_prolong)
+    return "option no_fused_prolong";
+  if (smoother_degree < 1)
+    return "smoother of degree 0";
+  if (one_launch)
+    return "fine level on the one-launch schedule";
+  if ((uint64_t)Af->d.n_dofs * number_size(Af->d.number) >= 0xFFFFFFF0ull)
+    return "fine vector of 4 GB or more";
+  if (fb.fr.available() && Af->d.p <= 4 && fb.n_bricks < tun.fused_prolong_min_bricks)
+    return "p <= 4 on the two-class schedule below fused_prolong_min_bricks";
+  return nullptr;
+}
+
 int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_transfer_desc *desc,
                         mgx_transfer_t *out)
 {
@@ -2691,6 +2735,20 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
     if (desc->children[i] >= fine->d.n_cells)
       return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: child index out of range");
   MGX_TRACE("transfer_create: parents=%u", npar);
+  // Is the 1D embedding symmetric under reversal of both indices (P1[2p-a][p-j] == P1[a][j])?  Every mirror-symmetric
+  // node set gives one that is.  The pipelined kernels and the fused forms apply it in its even-odd form (Basis1D::P1eo),
+  // which holds only what the symmetry leaves of P1: any other embedding runs the first-version kernels, which read P1.
+  bool p1_symmetric = true;
+  {
+    const double *P1    = desc->prolong_1d;
+    double        scale = 0;
+    for (size_t i = 0; i < (size_t)(2 * p + 1) * n; ++i)
+      scale = std::max(scale, std::fabs(P1[i]));
+    for (int a = 0; a <= 2 * p; ++a)
+      for (int j = 0; j <= p; ++j)
+        if (std::fabs(P1[a * n + j] - P1[(2 * p - a) * n + (p - j)]) > 1e-12 * scale)
+          p1_symmetric = false;
+  }
   auto tr    = std::make_unique<mgx_transfer_s>();
   tr->coarse = coarse;
   tr->fine   = fine;
@@ -2778,7 +2836,13 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
     // patch table of the pipelined kernels (mgx_transfer.hip): the 5^3 mesh entities of the
     // children patch of every parent.  Patch entity layer 0..4 along a direction = (child 0:
     // codes 0,1,2 ; child 1: codes 0,1,2) with child 0's code 2 and child 1's code 0 coinciding.
-    if (fine->d.n_dofs < (1u << 29) && !coarse->ctx->tun.transfer_v1)
+    if (coarse->ctx->tun.transfer_v1)
+      MGX_TRACE("transfer_create: no patch table, first-version kernels (option transfer_v1)");
+    else if (!p1_symmetric)
+      MGX_TRACE("transfer_create: no patch table, first-version kernels (1D embedding not symmetric under reversal)");
+    else if (fine->d.n_dofs >= (1u << 29))
+      MGX_TRACE("transfer_create: no patch table, first-version kernels (%u fine DoFs: 29-bit index)", fine->d.n_dofs);
+    else
       {
         std::vector<uint32_t> patch(125 * (size_t)npar);
         bool                  consistent = true;
@@ -2859,9 +2923,25 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
                     }
                 tr->d.coarse_coloured = ok;
               }
+            MGX_TRACE("transfer_create: patch table built, pipelined kernels");
+            if (tr->d.coarse_coloured)
+              MGX_TRACE("transfer_create: coarse colouring yes (parent index mod 8)");
+            else if (npar % 8 != 0)
+              MGX_TRACE("transfer_create: coarse colouring no (%u parents, not a multiple of 8)", npar);
+            else if (coarse->ctx->tun.restrict_atomic)
+              MGX_TRACE("transfer_create: coarse colouring no (option restrict_atomic)");
+            else
+              MGX_TRACE("transfer_create: coarse colouring no (two parents of one colour share an entity)");
+            // the restriction route of launch_t (mgx_transfer.hip)
+            if (tr->d.coarse_coloured && npar >= tr->d.colour_min)
+              MGX_TRACE("transfer_create: restriction in 8 colour launches");
+            else if (coarse->d.asm_start)
+              MGX_TRACE("transfer_create: restriction in one launch, ordered assembly with constraints, atomic adds without");
+            else
+              MGX_TRACE("transfer_create: restriction in one launch, atomic adds");
           }
         else
-          MGX_TRACE("transfer_create: children patches inconsistent, first-version kernels used");
+          MGX_TRACE("transfer_create: no patch table, first-version kernels (children patches inconsistent)");
       }
   }
   // 1D prolongation matrix into the basis blocks of both operators (the transfer kernels read the
@@ -2870,17 +2950,9 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
   // ... and its even-odd form for the line products of the fused forms (Basis1D::P1eo): the embedding of a parent
   // into its two children is symmetric under reversal of both indices for every node set that is
   std::vector<double> p1eo;
-  bool                p1_symmetric = true;
   {
     const double *P1 = desc->prolong_1d;
     const int     nh = (p + 1) / 2;
-    double        scale = 0;
-    for (size_t i = 0; i < np1; ++i)
-      scale = std::max(scale, std::fabs(P1[i]));
-    for (int a = 0; a <= 2 * p; ++a)
-      for (int j = 0; j <= p; ++j)
-        if (std::fabs(P1[a * n + j] - P1[(2 * p - a) * n + (p - j)]) > 1e-12 * scale)
-          p1_symmetric = false;
     p1eo.assign((size_t)(2 * p + 1) * nh + (p + 1), 0.);
     for (int a = 0; a <= p; ++a)
       for (int j = 0; j < nh; ++j)
@@ -2892,8 +2964,6 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
     if (p % 2 == 0)
       for (int a = 0; a <= p; ++a)
         p1eo[(size_t)(2 * p + 1) * nh + a] = P1[a * n + p / 2];
-    if (!p1_symmetric)
-      MGX_TRACE("transfer_create: 1D embedding not symmetric under reversal, no fused transfer forms");
   }
   for (mgx_operator_t o : {coarse, fine})
     {
@@ -3038,10 +3108,32 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
             }
         }
     }
+  if (trace_on())
+    {
+      // why the block table of the fused forms is missing (the tables' own conditions are checked above)
+      const char *no_blocks = !p1_symmetric                        ? "1D embedding not symmetric under reversal"
+                              : coarse->ctx->tun.no_fused_restrict ? "option no_fused_restrict"
+                              : !fine->d.bricks.available()        ? "fine level without bricks"
+                                                                   : "fine level not separable, not in forest order or decomposed differently";
+      const char *r = fused_restrict_blocker(tr.get(), coarse->ctx->tun), *q = fused_prolong_blocker(tr.get(), coarse->ctx->tun, 1);
+      if (r)
+        MGX_TRACE("transfer_create: fused residual + restriction no (%s)", tr->d.coarse_blocks ? r : no_blocks);
+      else
+        MGX_TRACE("transfer_create: fused residual + restriction yes (%s)", tr->d.coarse_scratch ? "scratch form" : "colour launches");
+      if (q)
+        MGX_TRACE("transfer_create: fused prolongation no (%s)", tr->d.coarse_blocks ? q : no_blocks);
+      else
+        MGX_TRACE("transfer_create: fused prolongation yes (with a smoother of degree >= 1)");
+    }
   if (tr->d.owner_weights && !tr->d.patch)
     {
       std::unique_ptr<mgx_transfer_s, int (*)(mgx_transfer_t)> guard(tr.release(), mgx_transfer_destroy);
-      return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: owner weights need the pipelined transfer kernels (fine level below 2^29 DoFs)");
+      return fail(MGX_ERR_UNSUPPORTED,
+                  !p1_symmetric ? "mgx_transfer_create: owner weights need the pipelined transfer kernels, which need a 1D embedding "
+                                  "symmetric under reversal"
+                  : coarse->ctx->tun.transfer_v1
+                    ? "mgx_transfer_create: owner weights need the pipelined transfer kernels (option transfer_v1 is set)"
+                    : "mgx_transfer_create: owner weights need the pipelined transfer kernels (fine level below 2^29 DoFs)");
     }
   *out = tr.release();
   return MGX_OK;
@@ -3481,13 +3573,9 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
         else
           MGX_TRY(smoother_apply(S->smooth[level], S->solution_update[level], S->defect[level], true));
       }
-      // Levels on the one-launch schedule run the residual as one launch and the transfers as kernels of
-      // their own: the fused forms below need the eight colour launches, each as long as a brick's
-      // whole latency chain on such a level (2 M DoFs: 63 instead of 147 us, 52 instead of 180 us)
-      const bool one_launch = S->matrix[level]->d.bricks.fr.available() && S->matrix[level]->d.bricks.fr.n_classes == 1;
-      // (with the scratch form of the restriction also on the one-launch schedule: it is one launch itself)
-      if (S->transfer[level]->d.coarse_blocks && (!one_launch || S->transfer[level]->d.coarse_scratch) &&
-          !S->ctx->tun.no_fused_residual)
+      // (which of the fused transfer forms run: fused_restrict_blocker / fused_prolong_blocker, which
+      // mgx_transfer_create traces)
+      if (!fused_restrict_blocker(S->transfer[level], S->ctx->tun))
         {
           // residual and restriction in one pass of the cell loop: t only carries the partial sums
           // of brick-surface DoFs between the colour launches, the residual is never stored
@@ -3534,16 +3622,7 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
       MGX_TRY(v_cycle(S, level - 1, 1)); // :671
       // :674 + :678.  On one rank with the macro-element brick loop the prolongation is not a kernel of
       // its own: the first post-smoothing iteration forms x + P x_coarse while it gathers x
-      mgx_operator_t Af = S->matrix[level];
-      const bool     fused_prolong = S->transfer[level]->d.coarse_blocks && Af->d.bricks.item_map && !Af->d.cells_form &&
-                                 Af->d.separable && !S->ctx->tun.no_fused_prolong && S->smooth[level]->info.degree >= 1 && !one_launch &&
-                                 (uint64_t)Af->d.n_dofs * number_size(Af->d.number) < 0xFFFFFFF0ull &&
-                                 // (a level on the two-class schedule -- decomposed or not -- runs its Chebyshev steps in two launches + finish; the fused
-                                 // prolongation form needs the eight colours, each as long as a brick's latency chain there.  p <= 4
-                                 // only: at p = 8 the prolongation kernel costs 0.18 ms on the 17 M-DoF level and the fused form wins,
-                                 // 0.945 against 1.004 ms)
-                                 (!Af->d.bricks.fr.available() || Af->d.p > 4 || Af->d.bricks.n_bricks >= S->ctx->tun.fused_prolong_min_bricks);
-      if (fused_prolong)
+      if (!fused_prolong_blocker(S->transfer[level], S->ctx->tun, S->smooth[level]->info.degree))
         {
           Stopwatch sw(S, level, 5);
           MGX_TRY(smoother_apply(S->smooth[level], S->solution_update[level], S->defect[level], true,
