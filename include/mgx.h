@@ -284,6 +284,35 @@ int mgx_vmult_with_cg_update(mgx_operator_t op, double alpha, double beta, const
 int mgx_compute_diagonal(mgx_operator_t op);
 int mgx_get_inverse_diagonal(mgx_operator_t op, const void **dptr);
 
+/* ---- solution-dependent coefficient of the general branch: MinimalSurfaceOperator<dim,p,number>
+ * (minimal_surface/program.cc:103-200), a LaplaceOperator whose merged_coefficient follows a state vector.
+ * Geometry: affine cells, one metric M = J^-1 J^-T (J^-1 the inverse Jacobian of the cell map) and one det J per
+ * level, handed in by the caller.  With g the reference-space gradient of the state at a quadrature point,
+ * s = g^T M g (= |grad u|^2) and JxW_q = w_q det J, the laws are
+ *   MGX_LAW_UNIT             coef_q = JxW_q M                                         (first_time, :133-134)
+ *   MGX_LAW_MINIMAL_SURFACE  coef_q = JxW_q (M - (M g)(M g)^T / (1 + s)) / sqrt(1 + s)     (:135-139, 144-155)
+ * and the residual  dst_i = - sum_q grad_ref phi_i(q) . a(s) JxW_q M g,  a = 1 / a = 1 / sqrt(1 + s)  (:187-192).
+ * Single rank; square root and division correctly rounded. ---- */
+#define MGX_LAW_UNIT 0
+#define MGX_LAW_MINIMAL_SURFACE 1
+/* Tells an operator of the general branch (created with mgx_operator_desc::coef_q, e.g. the unit-law tensor) the affine
+ * geometry of its level: metric = M as [xx,yy,zz,xy,xz,yz] (what MatrixFree's mapping info holds as `jacobians` and
+ * `JxW_values`, :144-152).  An operator without a per-point coefficient: MGX_ERR_UNSUPPORTED.  (A per-point metric
+ * for curved cells is not implemented; the entry points below keep their meaning when it is added.) */
+int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metric[6], double det_jacobian);
+/* MinimalSurfaceOperator::evaluate_coefficient(first_time, solution) :120-165: rewrites the operator's coef_q on the
+ * device from `state` (device vector of the operator's number type, boundary values in place, read through
+ * idx27_plain).  The inverse diagonal becomes stale: mgx_compute_diagonal before it is used again (a smoother created
+ * afterwards recomputes it itself). */
+int mgx_evaluate_coefficient(mgx_operator_t op, int law, const void *state);
+/* MinimalSurfaceOperator::compute_residual(dst, src, first_time) :169-197: state through idx27_plain (boundary values
+ * contribute), result through idx27, rows of constrained DoFs zero.  No atomics: bitwise reproducible. */
+int mgx_compute_nonlinear_residual(mgx_operator_t op, int law, void *dst, const void *state);
+/* device pointer and length (entries of the operator's number type) of merged_coefficient, layout as
+ * mgx_operator_desc::coef_q -- for tests and for callers that evaluate a law of their own with a kernel of theirs
+ * (then mgx_compute_diagonal and new smoothers are the caller's business as well) */
+int mgx_operator_get_coefficient(mgx_operator_t op, const void **dptr, size_t *n);
+
 /* ---- PreconditionChebyshev (deal.II; configured at multigrid_solver.h:269-289) ---- */
 /* SmootherType::initialize(matrix, additional_data) + estimate_eigenvalues.
  * degree < 0 == numbers::invalid_unsigned_int (determine from smoothing_range, level 0) */
@@ -340,6 +369,11 @@ int mgx_transfer_destroy(mgx_transfer_t transfer);
 int mgx_prolongate(mgx_transfer_t transfer, void *fine, const void *coarse, int add, int with_constraints);
 /* restrict_and_add (multigrid_solver.h:668) */
 int mgx_restrict_and_add(mgx_transfer_t transfer, void *coarse, const void *fine, int with_constraints);
+/* LaplaceProblem::solve, minimal_surface/program.cc:425-457: a state vector on the next coarser level -- every coarse
+ * DoF (boundary DoFs included) = the fine polynomial of the child that contains the coarse Gauss-Lobatto node,
+ * evaluated there (FE_Q::get_restriction_matrix: interpolation, not the transpose of the prolongation).  Vectors of
+ * the transfer's number type; every coarse entry is written, by one designated cell: bitwise reproducible. */
+int mgx_interpolate_to_coarse(mgx_transfer_t transfer, void *coarse, const void *fine);
 
 /* ---- MultigridSolver ---- */
 typedef struct
@@ -377,6 +411,13 @@ int mgx_solver_v_cycle(mgx_solver_t solver);
  * its FE_Q hierarchy differently from multigrid_solver.h:269-289); degree < 0: from the tolerance */
 int mgx_solver_reset_smoother(mgx_solver_t solver, int level, double smoothing_range, int degree,
                               int eig_cg_n_iterations);
+/* LaplaceProblem::solve, minimal_surface/program.cc:425-488: the fp64 state (device, finest level, boundary values in
+ * place) is interpolated down the hierarchy; on every level the law is evaluated on matrix_dp and on matrix (an fp32
+ * V-cycle operator receives the fp64 tensor of its level rounded to fp32), the diagonal is recomputed and the smoother re-created with the parameters
+ * it was created with (new eigenvalue estimate); a captured HIP graph is dropped.  Every level operator must have
+ * been enabled with mgx_operator_enable_coefficient_update.  MGX_ERR_UNSUPPORTED on a context with a communicator and
+ * on an agglomerated solver. */
+int mgx_solver_update_coefficient(mgx_solver_t solver, int law, const double *state_fine);
 int mgx_solver_n_levels(mgx_solver_t solver);
 int mgx_solver_get_operator(mgx_solver_t solver, int level, int fp64, mgx_operator_t *op);
 /* device pointer to an operator's compressed index table [n_cells][27] and its sizes */
@@ -405,6 +446,11 @@ int mgx_solver_solve_hooked(mgx_solver_t solver, int do_analyze, double *reducti
                             mgx_level_hook hook, void *user);
 /* MultigridSolver::solve_cg() :483-493: SolverCG with ReductionControl(1000,1e-16,1e-9) */
 int mgx_solver_solve_cg(mgx_solver_t solver, unsigned int *iterations, double *reduction_rate);
+/* The same with the caller's ReductionControl(max_iterations, abs_tol, reduction), e.g. (m, 1e-13, 1e-4) of the Newton
+ * steps of minimal_surface/program.cc:514-528: right-hand side rhs[maxlevel] (mgx_solver_get_vector id 0), zero start,
+ * result in solution[maxlevel] (mgx_solver_get_solution) */
+int mgx_solver_solve_cg_control(mgx_solver_t solver, unsigned int max_iterations, double abs_tol, double reduction,
+                                unsigned int *iterations, double *reduction_rate);
 /* The residual norms SolverCG handed to its ReductionControl (:486) during the last
  * mgx_solver_solve_cg / mgx_solver_solve_cg_fused: history[0] at the start, history[k] after
  * iteration k.  *count receives their number (iterations + 1); at most `capacity` are written. */

@@ -196,6 +196,17 @@ int mgx_cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vcycle_number
  * LaplaceOperator::compute_residual laplace_operator.h:804-845) from mgx_cube_rhs_quadrature instead of on the host */
 int mgx_cube_solver_create_opt(mgx_context_t ctx, mgx_cube_t cube, int vcycle_number, int degree_pre, int n_cycles,
                                int device_rhs, mgx_cube_solver *out);
+/* The hierarchy in the GENERAL branch of the operator, for solution-dependent coefficients (mgx_solver_update_coefficient,
+ * include/mgx.h; LaplaceProblem::setup_system of minimal_surface/program.cc): Cartesian cube / box meshes on one rank.
+ * jacobian (3 x 3 row-major, may be NULL: identity): the constant matrix A of an affine map x = x0 + A X of the whole
+ * box, so that the cells of level l have the Jacobian h_l A -- an anisotropic or sheared box; the index tables do not
+ * depend on it.  Every level operator is created with coef_q[l] ([n_cells][6][(p+1)^3], may be NULL as may coef_q:
+ * the unit-law tensor JxW_q J^-1 J^-T) and told its metric (mgx_operator_enable_coefficient_update).  Right-hand
+ * sides are zero and boundary values homogeneous: the solver solves for an update, rhs[maxlevel] is the caller's. */
+int mgx_cube_solver_create_general(mgx_context_t ctx, mgx_cube_t cube, int vcycle_number, int degree_pre, int n_cycles,
+                                   const double *jacobian, const double *const *coef_q, mgx_cube_solver *out);
+/* metric J^-1 J^-T [xx,yy,zz,xy,xz,yz] and det J of the cells of a level under that map (J = h_level A) */
+int mgx_cube_affine_metric(mgx_cube_t cube, int level, const double *jacobian, double metric[6], double *det_jacobian);
 int mgx_cube_solver_destroy(mgx_cube_solver *s);
 
 #ifdef __cplusplus

@@ -577,6 +577,39 @@ class Cube:
         check(self.lib.mgx_cube_seeded_vector(self.h, l, seed, out.ctypes.data_as(_lib.f64p)))
         return out
 
+    # ---- affine geometry of the Cartesian cube / box for the general branch (mgx_cube_solver_create_general) ----
+    def affine_metric(self, l, jacobian=None):
+        """(M = J^-1 J^-T as [xx,yy,zz,xy,xz,yz], det J) of the cells of level l, J = h_l A with the constant 3 x 3 matrix
+        A = jacobian (None: identity) of an affine map of the whole box"""
+        m, det = np.zeros(6), C.c_double()
+        a = None if jacobian is None else np.ascontiguousarray(jacobian, dtype=np.float64).ravel()
+        check(self.lib.mgx_cube_affine_metric(self.h, l, None if a is None else a.ctypes.data_as(_lib.f64p),
+                                              m.ctypes.data_as(_lib.f64p), C.byref(det)))
+        return m, det.value
+
+    def unit_law_coefficient(self, l, jacobian=None):
+        """[n_cells, 6, (p+1)^3] merged coefficient JxW_q M of the unit law (LAW_UNIT): what puts a level of the
+        Cartesian mesh into the general branch of the operator"""
+        m, det = self.affine_metric(l, jacobian)
+        w = self.qweights()
+        jxw = (w[:, None, None] * w[None, :, None] * w[None, None, :]).ravel() * det
+        return np.ascontiguousarray(np.broadcast_to(m[None, :, None] * jxw[None, None, :],
+                                                    (self.n_cells(l), 6, jxw.size)))
+
+    def dof_coordinates(self, l, jacobian=None):
+        """[n_dofs, 3] physical coordinates of the Gauss-Lobatto node of every DoF of level l (Cartesian cube / box;
+        jacobian: the affine map x = x0 + A X of the box about its lower corner x0)"""
+        assert self.shell is None and self.size == 1
+        p, g = self.degree, self.dof_grid(l).astype(np.int64)
+        n = np.array(self.cells_per_dim3(l)[1], dtype=np.int64)
+        G = n * p + 1
+        ijk = np.stack([g % G[0], (g // G[0]) % G[1], g // (G[0] * G[1])], axis=1)
+        cell = np.minimum(ijk // p, n[None, :] - 1)
+        X = (cell + self.gll()[ijk - cell * p]) * self.cell_size(l)
+        if jacobian is not None:
+            X = X @ np.asarray(jacobian, dtype=np.float64).T
+        return (-0.9 if self.box_desc is None else self.box_desc["origin"]) + X
+
 
 class LaplaceOperator:
     """multigrid::LaplaceOperator<3,p,number> of one level (laplace_operator.h:56-164)."""
@@ -593,8 +626,15 @@ class LaplaceOperator:
         self.number = self.lib.mgx_operator_number(self.h)
 
     @classmethod
-    def from_cube(cls, ctx, cube, level, number=F64):
-        return cls(ctx, cube.operator_desc(level, number))
+    def from_cube(cls, ctx, cube, level, number=F64, coef_q=None):
+        """coef_q: [n_cells, 6, (p+1)^3] merged coefficient of the general branch instead of the cube's own
+        (e.g. cube.unit_law_coefficient(level))"""
+        d = cube.operator_desc(level, number)
+        if coef_q is not None:
+            coef_q = np.ascontiguousarray(coef_q, dtype=np.float64)
+            assert coef_q.size == cube.n_cells(level) * 6 * (cube.degree + 1) ** 3
+            d.coef_q = coef_q.ctypes.data_as(_lib.f64p)  # (copied by mgx_operator_create)
+        return cls(ctx, d)
 
     def m(self):
         return self.lib.mgx_operator_n_dofs(self.h)
@@ -626,6 +666,33 @@ class LaplaceOperator:
 
     def compute_diagonal(self):
         check(self.lib.mgx_compute_diagonal(self.h))
+
+    # ---- MinimalSurfaceOperator (minimal_surface/program.cc:103-200) ----
+    def enable_coefficient_update(self, metric, det_jacobian):
+        """affine geometry of the level: M = J^-1 J^-T as [xx,yy,zz,xy,xz,yz] and det J (Cube.affine_metric)"""
+        m = np.ascontiguousarray(metric, dtype=np.float64)
+        assert m.size == 6
+        check(self.lib.mgx_operator_enable_coefficient_update(self.h, m.ctypes.data_as(_lib.f64p), float(det_jacobian)))
+
+    def evaluate_coefficient(self, law, state):
+        """evaluate_coefficient(first_time, solution) :120-165: coef_q from the state (operator's number type, boundary
+        values in place); law = LAW_UNIT (first_time) | LAW_MINIMAL_SURFACE"""
+        check(self.lib.mgx_evaluate_coefficient(self.h, int(law), state.ptr))
+
+    def compute_nonlinear_residual(self, law, dst, state):
+        """compute_residual(dst, src, first_time) :169-197"""
+        check(self.lib.mgx_compute_nonlinear_residual(self.h, int(law), dst.ptr, state.ptr))
+
+    def get_coefficient(self):
+        """the operator's merged coefficient on the device, [n_cells * 6 * (p+1)^3] entries of its number type"""
+        p, n = C.c_void_p(), C.c_size_t()
+        check(self.lib.mgx_operator_get_coefficient(self.h, C.byref(p), C.byref(n)))
+        return DeviceVector(self.ctx, n.value, self.number, ptr=p)
+
+    def l2_norm(self, x):
+        r = C.c_double()
+        check(self.lib.mgx_operator_l2_norm(self.h, x.ptr, C.byref(r)))
+        return r.value
 
     def get_matrix_diagonal_inverse(self):
         p = C.c_void_p()
@@ -680,8 +747,11 @@ class Chebyshev:
 class Transfer:
     """One level pair of dealii::MGTransferMatrixFree (multigrid_solver.h:209-222)."""
 
-    def __init__(self, coarse, fine, children, prolong_1d):
-        self.lib = coarse.lib
+    def __init__(self, coarse, fine, children, prolong_1d, handle=None):
+        if handle is not None:  # a transfer of a solver, not owned
+            self.lib, self.h, self.owned = coarse.lib, C.c_void_p(handle), False
+            return
+        self.lib, self.owned = coarse.lib, True
         self._children = np.ascontiguousarray(children, dtype=np.uint32)
         self._p1 = np.ascontiguousarray(prolong_1d, dtype=np.float64)
         d = _lib.TransferDesc(self._children.ctypes.data_as(_lib.u32p), self._p1.ctypes.data_as(_lib.f64p))
@@ -698,8 +768,13 @@ class Transfer:
     def restrict_and_add(self, coarse, fine, with_constraints=True):
         check(self.lib.mgx_restrict_and_add(self.h, coarse.ptr, fine.ptr, int(with_constraints)))
 
+    def interpolate_to_coarse(self, coarse, fine):
+        """the state on the next coarser level (minimal_surface/program.cc:425-457): nodal interpolation, boundary DoFs
+        included"""
+        check(self.lib.mgx_interpolate_to_coarse(self.h, coarse.ptr, fine.ptr))
+
     def clear(self):
-        if self.h:
+        if self.h and self.owned:
             self.lib.mgx_transfer_destroy(self.h)
             self.h = None
 
@@ -711,8 +786,12 @@ class MultigridSolver:
     `vcycle_number` is the template parameter Number (program.cc:76: float; BASELINE: double)."""
 
     def __init__(self, ctx, cube, degree_pre=3, degree_post=3, n_cycles=1, vcycle_number=F64, comm=None,
-                 polynomial="first_kind", agglomerate=True, device_rhs=False):
+                 polynomial="first_kind", agglomerate=True, device_rhs=False, general=False, jacobian=None, coef_q=None):
         """device_rhs: the right-hand sides are assembled on the GPU (mgx_solver_compute_rhs) instead of on the host.
+        general: the hierarchy in the general branch of the operator for solution-dependent coefficients
+        (mgx_cube_solver_create_general: Cartesian cube / box on one rank; zero right-hand sides, homogeneous boundary
+        values), with the constant matrix `jacobian` of an affine map of the box (None: identity) and, per level, the
+        merged coefficient coef_q[l] ([n_cells, 6, (p+1)^3]; None: the unit-law tensor).
         polynomial: Chebyshev polynomial type of the level smoothers: "first_kind" is what
         MultigridSolver<dim,p,Number,Number2> sets (multigrid_solver.h:277-278), "fourth_kind" what
         the Number == Number2 specialisation sets (:951-952)"""
@@ -724,8 +803,18 @@ class MultigridSolver:
         if cube.size > 1:
             if comm is None:
                 raise ValueError("a decomposed cube needs a Communicator")
-        check(self.lib.mgx_cube_solver_create_opt(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles, int(bool(device_rhs)),
-                                                  C.byref(self.s)))
+        self.jacobian = None if jacobian is None else np.ascontiguousarray(jacobian, dtype=np.float64).reshape(3, 3)
+        if general:
+            jac = None if self.jacobian is None else self.jacobian.ctypes.data_as(_lib.f64p)
+            cq = None
+            if coef_q is not None:
+                keep = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in coef_q]
+                cq = (_lib.f64p * len(keep))(*[None if a is None else a.ctypes.data_as(_lib.f64p) for a in keep])
+            check(self.lib.mgx_cube_solver_create_general(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles, jac, cq,
+                                                          C.byref(self.s)))
+        else:
+            check(self.lib.mgx_cube_solver_create_opt(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles,
+                                                      int(bool(device_rhs)), C.byref(self.s)))
         self.n_levels = self.s.n_levels
         self.max_level = self.n_levels - 1
         self.h = C.c_void_p(self.s.solver)
@@ -825,11 +914,28 @@ class MultigridSolver:
         check(self.lib.mgx_solver_solve_hooked(self.h, 1, C.byref(rate), trace.ctypes.data_as(_lib.f64p), cb, None))
         return rate.value, trace.reshape(-1, 2), errors
 
-    def solve_cg(self):
+    def solve_cg(self, control=None):
+        """control: (max_iterations, abs_tol, reduction) of the ReductionControl (mgx_solver_solve_cg_control) instead of
+        the reference's (1000, 1e-16, 1e-9) of MultigridSolver::solve_cg"""
         its = C.c_uint()
         red = C.c_double()
-        check(self.lib.mgx_solver_solve_cg(self.h, C.byref(its), C.byref(red)))
+        if control is None:
+            check(self.lib.mgx_solver_solve_cg(self.h, C.byref(its), C.byref(red)))
+        else:
+            check(self.lib.mgx_solver_solve_cg_control(self.h, int(control[0]), float(control[1]), float(control[2]),
+                                                       C.byref(its), C.byref(red)))
         return its.value, red.value
+
+    def update_coefficient(self, law, state):
+        """LaplaceProblem::solve, minimal_surface/program.cc:425-488: the fp64 state of the finest level down the hierarchy,
+        coefficient, diagonal and smoother of every level from it"""
+        check(self.lib.mgx_solver_update_coefficient(self.h, int(law), state.ptr))
+
+    def transfer_dp(self, level):
+        return Transfer(self.matrix_dp(level - 1), None, None, None, handle=self.s.transfer_dp[level])
+
+    def transfer(self, level):
+        return Transfer(self.matrix(level - 1), None, None, None, handle=self.s.transfer[level])
 
     def cg_history(self):
         """residual norms of the last solve_cg / solve_cg_fused: [0] at the start, [k] after iteration k"""
@@ -899,6 +1005,93 @@ class MultigridSolver:
             c.close()
             c.cube.close()
             c.ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# minimal_surface: solution-dependent coefficient, Newton iteration
+LAW_UNIT, LAW_MINIMAL_SURFACE = 0, 1
+
+
+class MinimalSurfaceProblem:
+    """LaplaceProblem<dim> of minimal_surface/program.cc in 3D on the Cartesian cube / box: -div(grad u / sqrt(1 + |grad u|^2))
+    = 0 with Dirichlet values, Newton's method with a V-cycle-preconditioned CG per step and the reference's
+    step-halving line search.  Vectors, norms and updates stay on the device; scalars cross to the host.
+
+    boundary: function of the node coordinates [n, 3] -> values [n] (the reference's Solution, :97-99)."""
+
+    def __init__(self, ctx, cube, boundary, vcycle_number=F32, smoother_degree=2, jacobian=None):
+        # (:470-476: Chebyshev degree 2, range 20, 15 CG iterations above the coarsest level)
+        self.ctx, self.cube, self.lib = ctx, cube, ctx.lib
+        self.solver = MultigridSolver(ctx, cube, smoother_degree, smoother_degree, 1, vcycle_number, general=True,
+                                      jacobian=jacobian)
+        l = self.level = cube.max_level
+        self.op = self.solver.matrix_dp(l)
+        n = self.n = cube.n_dofs(l)
+        # interpolate_boundary_values(): zero in the interior, the boundary function on the Dirichlet DoFs
+        u = np.zeros(n)
+        c = cube.constrained(l)
+        u[c] = boundary(cube.dof_coordinates(l, jacobian)[c])
+        self.solution = ctx.vector(n, F64, u)
+        self.tentative = ctx.vector(n, F64)
+        self.system_rhs = self.solver.get_vector(l, "rhs")
+        self.n_residual = self.linear_iterations = 0
+        self.time_solve = self.time_residual = self.time_coefficient = 0.0
+        self.history = []  # per step: (initial residual norm, halvings, final residual norm, CG iterations)
+
+    def _residual(self, law, state):
+        self.op.compute_nonlinear_residual(law, self.system_rhs, state)
+        self.n_residual += 1
+        return self.op.l2_norm(self.system_rhs)
+
+    def solve(self, first_time, log=None):
+        """LaplaceProblem::solve(first_time) :414-573; returns (initial, final) residual norm"""
+        import time
+        law = LAW_UNIT if first_time else LAW_MINIMAL_SURFACE
+        t0 = time.perf_counter()
+        self.solver.update_coefficient(law, self.solution)  # :425-488
+        self.ctx.sync()
+        self.time_coefficient += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        initial = self._residual(law, self.solution)  # :519-523
+        self.time_residual += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        its = 0
+        if initial > 0.0:
+            its, _ = self.solver.solve_cg(control=(self.n, 1e-13, 1e-4))  # :514, 537-541
+        direction = self.solver.get_solution(self.level, insert_bc=False)  # zero in the Dirichlet rows (:548)
+        self.ctx.sync()
+        self.time_solve += time.perf_counter() - t0
+        self.linear_iterations += its
+        t0 = time.perf_counter()
+        final, alpha, n_steps, nbytes = initial, 1.0, 0, 8 * self.n
+        while n_steps < 100:  # :552-568
+            check(self.lib.mgx_copy_device(self.ctx.h, self.tentative.ptr, self.solution.ptr, nbytes))
+            check(self.lib.mgx_sadd(self.ctx.h, F64, self.tentative.ptr, 1.0, alpha, direction.ptr, self.n))
+            final = self._residual(LAW_MINIMAL_SURFACE, self.tentative)
+            if final < initial:
+                break
+            alpha /= 2.0
+            n_steps += 1
+        self.time_residual += time.perf_counter() - t0
+        if log is not None:
+            log("Time solve (%d iterations)" % its)
+            log("Residual norm: %.6g in %d steps to %.6g" % (initial, n_steps, final))
+        check(self.lib.mgx_copy_device(self.ctx.h, self.solution.ptr, self.tentative.ptr, nbytes))
+        self.history.append((initial, n_steps, final, its))
+        return initial, final
+
+    def run(self, n_inner_iterations=100, tolerance=1e-12, log=None):
+        """the inner loop of run() :656-662; returns the number of Newton steps taken"""
+        for it in range(n_inner_iterations):
+            _, final = self.solve(it == 0, log)
+            if final < tolerance:
+                break
+        return len(self.history)
+
+    def close(self):
+        for v in (self.solution, self.tentative):
+            v.free()
+        self.solver.close()
 
 
 # ---------------------------------------------------------------------------------------------

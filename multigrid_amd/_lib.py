@@ -225,6 +225,17 @@ SIGNATURES = {
     "mgx_solver_get_operator": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp)]),
     "mgx_operator_device_indices": (C.c_int, [vp, C.POINTER(u32p), u32p, u32p, C.POINTER(C.c_int)]),
     "mgx_solver_set_agglomeration": (C.c_int, [vp, C.c_int, vp, u32p, C.POINTER(C.c_uint8), C.c_uint32]),
+    # solution-dependent coefficient (minimal_surface)
+    "mgx_operator_enable_coefficient_update": (C.c_int, [vp, f64p, C.c_double]),
+    "mgx_evaluate_coefficient": (C.c_int, [vp, C.c_int, vp]),
+    "mgx_compute_nonlinear_residual": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mgx_operator_get_coefficient": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+    "mgx_interpolate_to_coarse": (C.c_int, [vp, vp, vp]),
+    "mgx_solver_update_coefficient": (C.c_int, [vp, C.c_int, vp]),
+    "mgx_solver_solve_cg_control": (C.c_int, [vp, C.c_uint, C.c_double, C.c_double, C.POINTER(C.c_uint), f64p]),
+    "mgx_cube_solver_create_general": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f64p, C.POINTER(f64p),
+                                                 C.POINTER(CubeSolver)]),
+    "mgx_cube_affine_metric": (C.c_int, [vp, C.c_int, f64p, f64p, f64p]),
     # include/mgx_dg.h
     "mgx_dg_operator_create": (C.c_int, [vp, C.POINTER(DGOperatorDesc), C.POINTER(vp)]),
     "mgx_dg_operator_destroy": (C.c_int, [vp]),

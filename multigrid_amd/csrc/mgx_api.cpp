@@ -294,6 +294,11 @@ struct mgx_operator_s
   double  *cg_partials = nullptr, *cg_result = nullptr;
   void    *cg_carrier  = nullptr;
   bool     constrained_last = false; // the constrained DoFs are exactly [n_dofs - n_constrained, n_dofs)
+  // solution-dependent coefficient (mgx_operator_enable_coefficient_update): affine geometry of the level,
+  // M = J^-1 J^-T [xx,yy,zz,xy,xz,yz] and det J
+  bool     coef_update  = false;
+  double   metric[6]    = {0, 0, 0, 0, 0, 0};
+  double   det_jacobian = 0;
 };
 
 struct mgx_smoother_s
@@ -305,6 +310,9 @@ struct mgx_smoother_s
   // AdditionalData::PolynomialType::fourth_kind (multigrid_solver.h:951-952): info.delta = lambda_max
   bool              fourth_kind = false;
   double            range_a     = 0; // lower end of the smoothing range (first-kind delta / theta)
+  // the arguments of mgx_smoother_create, for mgx_solver_update_coefficient which re-creates the smoother with them
+  double            req_range  = 0;
+  int               req_degree = 0, req_eig_its = 0;
   // factor of the first step, and factor1 / factor2 of iteration k = 0, 1, ... of the recurrence
   double first_factor() const { return fourth_kind ? 4. / (3. * info.delta) : 1. / info.theta; }
   void   next_factors(int k, double &rhok, double &f1, double &f2) const
@@ -327,6 +335,10 @@ struct mgx_transfer_s
   mgx_operator_t coarse = nullptr, fine = nullptr;
   TransferData   d;
   void          *scratch = nullptr; // decomposed mesh: coarse-level scratch of restrict_and_add
+  // mgx_interpolate_to_coarse (built at its first call): 1D interpolation matrix [(2p+1)(p+1)] in the number type and
+  // the coarse cells' entity ownership (bit e: first cell in cell order that contains entity e)
+  void          *interp_1d  = nullptr;
+  uint32_t      *own_coarse = nullptr;
 };
 
 struct mgx_solver_s
@@ -361,6 +373,8 @@ struct mgx_solver_s
   hipEvent_t      agg_in = nullptr, agg_out = nullptr;
   std::vector<double> agg_host;         // callback transport: staging of the allreduce
   std::vector<double> cg_history;       // residual norms of the last solve_cg: start, then one per iteration
+  // mgx_solver_update_coefficient: the fp64 state on every level (the finest entry is unused), allocated at the first call
+  std::vector<double *> nl_state;
 };
 
 namespace
@@ -2095,6 +2109,84 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
   return exchange_add(op, dst); // dst.compress(add), laplace_operator.h:843
 }
 
+/* ------------------------------------------------------------------------------------------
+ * Solution-dependent coefficient of the general branch (MinimalSurfaceOperator, minimal_surface/program.cc:103-200)
+ * ------------------------------------------------------------------------------------------ */
+int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metric[6], double det_jacobian)
+{
+  MGX_REQUIRE(op && metric, "mgx_operator_enable_coefficient_update: null argument");
+  if (!op->d.coef_q)
+    return fail(MGX_ERR_UNSUPPORTED,
+                "mgx_operator_enable_coefficient_update: the operator has no per-point coefficient (separable or "
+                "one-tensor-per-mesh branch); create it with mgx_operator_desc::coef_q set, e.g. to the unit-law tensor "
+                "JxW_q J^-1 J^-T");
+  // M = J^-1 J^-T is symmetric positive definite (leading minors), det J > 0
+  const double m0 = metric[0], m1 = metric[1], m2 = metric[2], m3 = metric[3], m4 = metric[4], m5 = metric[5];
+  const double det_m = m0 * (m1 * m2 - m5 * m5) - m3 * (m3 * m2 - m5 * m4) + m4 * (m3 * m5 - m1 * m4);
+  MGX_REQUIRE(det_jacobian > 0. && m0 > 0. && m0 * m1 - m3 * m3 > 0. && det_m > 0.,
+              "mgx_operator_enable_coefficient_update: the metric must be positive definite and det J > 0");
+  std::copy(metric, metric + 6, op->metric);
+  op->det_jacobian = det_jacobian;
+  op->coef_update  = true;
+  return MGX_OK;
+}
+
+static int require_coefficient_update(mgx_operator_t op, int law, const char *who)
+{
+  const std::string w(who);
+  MGX_REQUIRE(law == MGX_LAW_UNIT || law == MGX_LAW_MINIMAL_SURFACE, w + ": unknown law");
+  if (op->ctx->has_comm || op->plan)
+    return fail(MGX_ERR_UNSUPPORTED, w + ": not on a decomposed mesh (single rank only)");
+  MGX_REQUIRE(op->coef_update, w + ": call mgx_operator_enable_coefficient_update first (affine geometry of the level)");
+  MGX_REQUIRE(op->d.idx27_plain, w + ": the operator was created without idx27_plain (the state is read with its boundary values)");
+  return MGX_OK;
+}
+
+int mgx_evaluate_coefficient(mgx_operator_t op, int law, const void *state)
+{
+  MGX_REQUIRE(op && state, "mgx_evaluate_coefficient: null argument");
+  MGX_TRY(require_coefficient_update(op, law, "mgx_evaluate_coefficient"));
+  launch_evaluate_coefficient(op->ctx->stream, op->d, op->d.coef_q, op->d.number, law == MGX_LAW_MINIMAL_SURFACE, op->metric,
+                              op->det_jacobian, nullptr, state);
+  MGX_HIP(hipGetLastError());
+  op->has_diag = false; // the inverse diagonal belongs to the previous coefficient
+  return MGX_OK;
+}
+
+int mgx_operator_get_coefficient(mgx_operator_t op, const void **dptr, size_t *n)
+{
+  MGX_REQUIRE(op && dptr && n, "mgx_operator_get_coefficient: null argument");
+  if (!op->d.coef_q)
+    return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_get_coefficient: the operator has no per-point coefficient");
+  const size_t np = (size_t)op->d.p + 1;
+  *dptr           = op->d.coef_q;
+  *n              = (size_t)op->d.n_cells * 6 * np * np * np;
+  return MGX_OK;
+}
+
+int mgx_compute_nonlinear_residual(mgx_operator_t op, int law, void *dst, const void *state)
+{
+  MGX_REQUIRE(op && dst && state, "mgx_compute_nonlinear_residual: null argument");
+  MGX_REQUIRE(dst != state, "mgx_compute_nonlinear_residual: dst and state must not alias");
+  MGX_TRY(require_coefficient_update(op, law, "mgx_compute_nonlinear_residual"));
+  hipStream_t s  = op->ctx->stream;
+  const bool  ms = law == MGX_LAW_MINIMAL_SURFACE;
+  // atomic-free assembly as in mgx_compute_residual: colour by colour where the level has cell colours, else ordered
+  if (op->d.asm_start)
+    launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, dst, state);
+  else if (op->d.cell_order)
+    {
+      MGX_HIP(hipMemsetAsync(dst, 0, number_size(op->d.number) * op->d.n_dofs, s));
+      launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, dst, state, op->d.cell_order, op->d.cell_colour_start,
+                              op->d.n_cell_colours);
+    }
+  else
+    return fail(MGX_ERR_UNSUPPORTED, "mgx_compute_nonlinear_residual: the level has neither cell colours nor the ordered-assembly "
+                                     "tables (more than 32 colours): no reproducible assembly");
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
 int mgx_compute_diagonal(mgx_operator_t op)
 {
   MGX_REQUIRE(op, "mgx_compute_diagonal: null argument");
@@ -2203,6 +2295,9 @@ int mgx_smoother_create(mgx_operator_t op, double smoothing_range, int degree, i
   const size_t  n   = op->d.n_dofs, bytes = number_size(num) * n;
   std::unique_ptr<mgx_smoother_s, int (*)(mgx_smoother_t)> sm(new mgx_smoother_s, mgx_smoother_destroy);
   sm->op            = op;
+  sm->req_range     = smoothing_range;
+  sm->req_degree    = degree;
+  sm->req_eig_its   = eig_cg_n_iterations;
   MGX_HIP(hipMalloc(&sm->x_old, bytes));
   MGX_HIP(hipMalloc(&sm->tmp, bytes));
   // estimate_eigenvalues: PCG(D^-1) on v_i = (i mod 11) - mean; Lanczos tridiagonal
@@ -3147,6 +3242,8 @@ int mgx_transfer_destroy(mgx_transfer_t tr)
   (void)hipFree(tr->d.children);
   (void)hipFree(tr->d.weight_shift);
   (void)hipFree(tr->d.own27);
+  (void)hipFree(tr->interp_1d);
+  (void)hipFree(tr->own_coarse);
   (void)hipFree(tr->d.patch);
   (void)hipFree(tr->d.coarse_blocks);
   (void)hipFree(tr->d.coarse_scratch);
@@ -3189,6 +3286,104 @@ int mgx_restrict_and_add(mgx_transfer_t tr, void *coarse, const void *fine, int 
   launch_restrict_add(s, tr->d, tr->scratch, fine, with_constraints != 0);
   MGX_TRY(exchange_add(cop, tr->scratch));
   launch_add_cast(s, coarse, cop->d.number, tr->scratch, cop->d.number, cop->d.n_dofs);
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+// 1D matrix of the state interpolation to the coarser level (minimal_surface/program.cc:425-457, FE_Q's
+// get_restriction_matrix): r[a (p+1) + i] = value at the coarse Gauss-Lobatto node i of the Lagrange polynomial of the
+// fine patch point a (child 0: a = 0..p, child 1: a = p..2p; the children's node sets on [0,1/2] and [1/2,1]); the
+// child that contains the node is used (a node on the common face: either gives the same value, child 0 is taken).
+static std::vector<double> interpolation_matrix_1d(int p)
+{
+  using ld = long double;
+  const int       n = p + 1, m = 2 * p + 1;
+  std::vector<ld> x(n);
+  x[0] = 0, x[p] = 1;
+  const ld pi = 3.141592653589793238462643383279502884L;
+  for (int i = 1; i < p; ++i) // Gauss-Lobatto interior nodes: Newton on P_p'
+    {
+      ld t = -std::cos(pi * i / p);
+      for (int it = 0; it < 100; ++it)
+        {
+          ld p0 = 1, p1 = t; // Legendre recurrence: P_p(t) and its first two derivatives
+          for (int k = 2; k <= p; ++k)
+            {
+              const ld pk = ((2 * k - 1) * t * p1 - (k - 1) * p0) / k;
+              p0 = p1, p1 = pk;
+            }
+          const ld dP  = p * (p0 - t * p1) / (1 - t * t); // p1 = P_p, p0 = P_{p-1}
+          const ld d2P = (2 * t * dP - (ld)p * (p + 1) * p1) / (1 - t * t);
+          const ld dt  = dP / d2P;
+          t -= dt;
+          if (std::fabs(dt) < 1e-19L)
+            break;
+        }
+      x[i] = (t + 1) / 2;
+    }
+  for (int i = 0; i < n / 2; ++i) // mirror symmetry to the last bit
+    x[p - i] = 1 - x[i];
+  std::vector<double> r((size_t)m * n, 0.);
+  for (int i = 0; i < n; ++i)
+    {
+      const int child = x[i] > 0.5L ? 1 : 0;
+      const ld  xi    = 2 * x[i] - child; // coordinate of the coarse node in the child
+      for (int a = 0; a < n; ++a)
+        {
+          ld v = 1;
+          for (int b = 0; b < n; ++b)
+            if (b != a)
+              v *= (xi - x[b]) / (x[a] - x[b]);
+          r[(size_t)(child * p + a) * n + i] = (double)v;
+        }
+    }
+  return r;
+}
+
+/* LaplaceProblem::solve, minimal_surface/program.cc:425-457 */
+int mgx_interpolate_to_coarse(mgx_transfer_t tr, void *coarse, const void *fine)
+{
+  MGX_REQUIRE(tr && coarse && fine, "mgx_interpolate_to_coarse: null argument");
+  mgx_operator_t cop = tr->coarse, fop = tr->fine;
+  if (cop->plan || fop->plan || cop->ctx->has_comm)
+    return fail(MGX_ERR_UNSUPPORTED, "mgx_interpolate_to_coarse: not on a decomposed mesh (single rank only)");
+  MGX_REQUIRE(cop->d.idx27_plain && fop->d.idx27_plain, "mgx_interpolate_to_coarse: the level operators need idx27_plain");
+  hipStream_t s = cop->ctx->stream;
+  const int   p = cop->d.p;
+  if (!tr->interp_1d)
+    {
+      // (the Gauss-Lobatto nodes mgx_operator_desc::shape_values is defined on)
+      const std::vector<double> r = interpolation_matrix_1d(p);
+      std::vector<uint32_t>     idxc((size_t)cop->d.n_cells * 27), own(cop->d.n_cells, 0u);
+      MGX_HIP(hipMemcpy(idxc.data(), cop->d.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
+      std::vector<uint8_t> seen(cop->d.n_dofs, 0);
+      for (uint32_t c = 0; c < cop->d.n_cells; ++c)
+        for (int e = 0; e < 27; ++e)
+          {
+            const int size = (e % 3 == 1 ? p - 1 : 1) * ((e / 3) % 3 == 1 ? p - 1 : 1) * (e / 9 == 1 ? p - 1 : 1);
+            if (size == 0)
+              continue;
+            const uint32_t base = idxc[27 * (size_t)c + e];
+            MGX_REQUIRE(base < cop->d.n_dofs, "mgx_interpolate_to_coarse: index table out of range");
+            if (!seen[base])
+              {
+                seen[base] = 1;
+                own[c] |= 1u << e;
+              }
+          }
+      const size_t bytes = number_size(cop->d.number) * r.size();
+      MGX_HIP(hipMalloc(&tr->interp_1d, bytes));
+      if (cop->d.number == MGX_F64)
+        MGX_HIP(hipMemcpy(tr->interp_1d, r.data(), bytes, hipMemcpyHostToDevice));
+      else
+        {
+          const std::vector<float> rf(r.begin(), r.end());
+          MGX_HIP(hipMemcpy(tr->interp_1d, rf.data(), bytes, hipMemcpyHostToDevice));
+        }
+      MGX_HIP(hipMalloc((void **)&tr->own_coarse, sizeof(uint32_t) * own.size()));
+      MGX_HIP(hipMemcpy(tr->own_coarse, own.data(), sizeof(uint32_t) * own.size(), hipMemcpyHostToDevice));
+    }
+  launch_interpolate_to_coarse(s, tr->d, tr->interp_1d, tr->own_coarse, coarse, fine);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -3251,6 +3446,8 @@ int mgx_solver_destroy(mgx_solver_t S)
     (void)hipEventDestroy(S->agg_in);
   if (S->agg_out)
     (void)hipEventDestroy(S->agg_out);
+  for (auto p : S->nl_state)
+    (void)hipFree(p);
   (void)hipFree(S->cg_r);
   (void)hipFree(S->cg_z);
   (void)hipFree(S->cg_d);
@@ -3785,9 +3982,10 @@ int mgx_solver_vmult(mgx_solver_t S, double *dst, const double *src)
   return MGX_OK;
 }
 
-int mgx_solver_solve_cg(mgx_solver_t S, unsigned int *iterations, double *reduction_rate)
+// SolverCG preconditioned by the V-cycle with ReductionControl(max_iterations, abs_tol, reduction)
+static int solve_cg_control(mgx_solver_t S, unsigned int max_iterations, double abs_tol, double reduction,
+                            unsigned int *iterations, double *reduction_rate, const char *not_converged)
 {
-  MGX_REQUIRE(S, "mgx_solver_solve_cg: null solver");
   const int      lmax = S->n_levels - 1;
   const size_t   n    = S->matrix[lmax]->d.n_dofs;
   mgx_context_t  ctx  = S->ctx;
@@ -3808,8 +4006,7 @@ int mgx_solver_solve_cg(mgx_solver_t S, unsigned int *iterations, double *reduct
   float     *r32 = (float *)S->defect[lmax];
   if (mixed)
     launch_copy_cast(s, r32, MGX_F32, r, MGX_F64, n);
-  // SolverCG with ReductionControl(1000, 1e-16, 1e-9) (:486)
-  while (res > 1e-16 && res > 1e-9 * res0 && it < 1000)
+  while (res > abs_tol && res > reduction * res0 && it < max_iterations)
     {
       ++it;
       rz_old = rz;
@@ -3851,9 +4048,27 @@ int mgx_solver_solve_cg(mgx_solver_t S, unsigned int *iterations, double *reduct
     *iterations = it;
   if (reduction_rate)
     *reduction_rate = it > 0 ? std::pow(res / res0, 1. / it) : 1.; // :491-492
-  if (it >= 1000)
-    return fail(MGX_ERR_NOT_CONVERGED, "mgx_solver_solve_cg: no convergence in 1000 iterations");
+  if (it >= max_iterations)
+    return fail(MGX_ERR_NOT_CONVERGED, not_converged);
   return MGX_OK;
+}
+
+int mgx_solver_solve_cg(mgx_solver_t S, unsigned int *iterations, double *reduction_rate)
+{
+  MGX_REQUIRE(S, "mgx_solver_solve_cg: null solver");
+  // SolverCG with ReductionControl(1000, 1e-16, 1e-9) (:486)
+  return solve_cg_control(S, 1000, 1e-16, 1e-9, iterations, reduction_rate,
+                          "mgx_solver_solve_cg: no convergence in 1000 iterations");
+}
+
+/* minimal_surface/program.cc:514-528: the same solver with the caller's ReductionControl */
+int mgx_solver_solve_cg_control(mgx_solver_t S, unsigned int max_iterations, double abs_tol, double reduction,
+                                unsigned int *iterations, double *reduction_rate)
+{
+  MGX_REQUIRE(S, "mgx_solver_solve_cg_control: null solver");
+  MGX_REQUIRE(max_iterations >= 1 && abs_tol >= 0. && reduction >= 0., "mgx_solver_solve_cg_control: bad control values");
+  return solve_cg_control(S, max_iterations, abs_tol, reduction, iterations, reduction_rate,
+                          "mgx_solver_solve_cg_control: no convergence within max_iterations");
 }
 
 /* MultigridSolver::vmult_with_residual_update (multigrid_solver.h:516-619); out3 (may be NULL)
@@ -4029,6 +4244,73 @@ int mgx_solver_reset_smoother(mgx_solver_t S, int level, double smoothing_range,
       S->graph       = nullptr;
       S->graph_calls = 0;
     }
+  return MGX_OK;
+}
+
+/* LaplaceProblem::solve, minimal_surface/program.cc:425-488: the state on every level, the coefficient of every level
+ * operator from it, diagonals, smoothers */
+int mgx_solver_update_coefficient(mgx_solver_t S, int law, const double *state_fine)
+{
+  MGX_REQUIRE(S && state_fine, "mgx_solver_update_coefficient: null argument");
+  if (S->ctx->has_comm)
+    return fail(MGX_ERR_UNSUPPORTED, "mgx_solver_update_coefficient: not on a context with a communicator (single rank only)");
+  if (S->agg_solver)
+    return fail(MGX_ERR_UNSUPPORTED, "mgx_solver_update_coefficient: not on an agglomerated hierarchy");
+  const int nl = S->n_levels, lmax = nl - 1;
+  for (int l = 0; l < nl; ++l) // everything that can be refused is refused before the first level changes
+    {
+      MGX_TRY(require_coefficient_update(S->matrix_dp[l], law, "mgx_solver_update_coefficient"));
+      MGX_TRY(require_coefficient_update(S->matrix[l], law, "mgx_solver_update_coefficient"));
+    }
+  hipStream_t s = S->ctx->stream;
+  if (S->nl_state.empty())
+    {
+      S->nl_state.assign(nl, nullptr);
+      for (int l = 0; l < nl; ++l)
+        {
+          const size_t n = S->matrix_dp[l]->d.n_dofs;
+          if (l < lmax)
+            MGX_HIP(hipMalloc((void **)&S->nl_state[l], 8 * n));
+        }
+    }
+  // :425-457 (the reference interpolates in the level number type; here in fp64)
+  for (int l = lmax; l > 0; --l)
+    MGX_TRY(mgx_interpolate_to_coarse(S->transfer_dp[l], S->nl_state[l - 1], l == lmax ? state_fine : S->nl_state[l]));
+  for (int l = 0; l < nl; ++l)
+    {
+      const double *state = l == lmax ? state_fine : S->nl_state[l];
+      MGX_TRY(mgx_evaluate_coefficient(S->matrix_dp[l], law, state)); // :458 / :469
+      if (S->matrix[l] != S->matrix_dp[l])
+        {
+          // The fp32 operator of the level receives the fp64 tensor, rounded: evaluated with the tables of matrix_dp
+          // from the fp64 state.  (The reference evaluates in level_number from the state cast to it, :469; the fp32
+          // tensor would then sit about 1e-7 from the fp64 one instead of at its rounding, and the level operators of
+          // the two precisions would no longer be the same operator up to storage.)
+          mgx_operator_t A = S->matrix_dp[l], V = S->matrix[l];
+          MGX_REQUIRE(V->d.n_cells == A->d.n_cells && V->d.p == A->d.p, "mgx_solver_update_coefficient: level operators differ");
+          launch_evaluate_coefficient(s, A->d, V->d.coef_q, V->d.number, law == MGX_LAW_MINIMAL_SURFACE, A->metric,
+                                      A->det_jacobian, nullptr, state);
+          MGX_HIP(hipGetLastError());
+          V->has_diag = false;
+        }
+      // :484, and the smoother with the parameters it was created with (:470-487: a new eigenvalue estimate)
+      MGX_TRY(mgx_compute_diagonal(S->matrix[l]));
+      mgx_smoother_t old = S->smooth[l], sm = nullptr;
+      MGX_TRY(mgx_smoother_create(S->matrix[l], old->req_range, old->req_degree, old->req_eig_its, &sm));
+      if (old->fourth_kind)
+        MGX_TRY(mgx_smoother_set_polynomial_type(sm, MGX_CHEBYSHEV_FOURTH_KIND));
+      MGX_TRY(mgx_smoother_destroy(old));
+      S->smooth[l] = sm;
+    }
+  if (S->graph_exec) // the captured launches carry the old smoothers' buffers and factors
+    {
+      MGX_HIP(hipStreamSynchronize(s));
+      (void)hipGraphExecDestroy(S->graph_exec);
+      (void)hipGraphDestroy(S->graph);
+      S->graph_exec = nullptr;
+      S->graph      = nullptr;
+    }
+  S->graph_calls = 0;
   return MGX_OK;
 }
 

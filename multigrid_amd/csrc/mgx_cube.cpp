@@ -1314,12 +1314,60 @@ int mgx_cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vnumber, int 
   return mgx_cube_solver_create_opt(ctx, cube, vnumber, degree_pre, n_cycles, 0, out);
 }
 
+} // extern "C"
+
+// general != nullptr: the hierarchy of mgx_cube_solver_create_general
+struct GeneralHierarchy
+{
+  const double        *jacobian; // 3 x 3 row-major or nullptr (identity)
+  const double *const *coef_q;   // per level or nullptr
+};
+static int cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vnumber, int degree_pre, int n_cycles, int device_rhs,
+                              const GeneralHierarchy *general, mgx_cube_solver *out);
+
+extern "C" {
+int mgx_cube_affine_metric(mgx_cube_t cube, int level, const double *jacobian, double metric[6], double *det_jacobian)
+{
+  if (!cube || level < 0 || level >= (int)cube->levels.size() || !metric || !det_jacobian)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_cube_affine_metric: bad argument");
+  static const double identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  const double       *A           = jacobian ? jacobian : identity;
+  const double        h           = cube->levels[level].h;
+  const double det = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
+  if (!(det > 0.))
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_cube_affine_metric: the Jacobian must have a positive determinant");
+  // inverse of h A by cofactors
+  const double inv[9] = {(A[4] * A[8] - A[5] * A[7]) / det, (A[2] * A[7] - A[1] * A[8]) / det, (A[1] * A[5] - A[2] * A[4]) / det,
+                         (A[5] * A[6] - A[3] * A[8]) / det, (A[0] * A[8] - A[2] * A[6]) / det, (A[2] * A[3] - A[0] * A[5]) / det,
+                         (A[3] * A[7] - A[4] * A[6]) / det, (A[1] * A[6] - A[0] * A[7]) / det, (A[0] * A[4] - A[1] * A[3]) / det};
+  auto mm = [&](int i, int j) { return (inv[3 * i] * inv[3 * j] + inv[3 * i + 1] * inv[3 * j + 1] + inv[3 * i + 2] * inv[3 * j + 2]) / (h * h); };
+  metric[0] = mm(0, 0), metric[1] = mm(1, 1), metric[2] = mm(2, 2), metric[3] = mm(0, 1), metric[4] = mm(0, 2), metric[5] = mm(1, 2);
+  *det_jacobian = det * h * h * h;
+  return MGX_OK;
+}
+
+int mgx_cube_solver_create_general(mgx_context_t ctx, mgx_cube_t cube, int vnumber, int degree_pre, int n_cycles,
+                                   const double *jacobian, const double *const *coef_q, mgx_cube_solver *out)
+{
+  const GeneralHierarchy g{jacobian, coef_q};
+  return cube_solver_create(ctx, cube, vnumber, degree_pre, n_cycles, 1, &g, out);
+}
+
 int mgx_cube_solver_create_opt(mgx_context_t ctx, mgx_cube_t cube, int vnumber, int degree_pre, int n_cycles, int device_rhs,
                            mgx_cube_solver *out)
+{
+  return cube_solver_create(ctx, cube, vnumber, degree_pre, n_cycles, device_rhs, nullptr, out);
+}
+} // extern "C"
+
+static int cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vnumber, int degree_pre, int n_cycles, int device_rhs,
+                              const GeneralHierarchy *general, mgx_cube_solver *out)
 {
   if (!ctx || !cube || !out || (vnumber != MGX_F32 && vnumber != MGX_F64))
     return MGX_ERR_INVALID_ARGUMENT;
   const int nl = (int)cube->levels.size();
+  if (general && (cube->size > 1 || !cube->levels[0].coef_q.empty()))
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_cube_solver_create_general: Cartesian cube / box meshes on one rank only");
   std::memset(out, 0, sizeof(*out));
   out->n_levels    = nl;
   out->matrix      = new mgx_operator_t[nl]();
@@ -1331,6 +1379,32 @@ int mgx_cube_solver_create_opt(mgx_context_t ctx, mgx_cube_t cube, int vnumber, 
     {
       mgx_operator_desc d;
       mgx_cube_operator_desc(cube, l, MGX_F64, &d);
+      // general branch on the Cartesian mesh: the unit-law tensor JxW_q M (or the caller's) as merged coefficient
+      std::vector<double> unit;
+      double              metric[6] = {0, 0, 0, 0, 0, 0}, det = 0;
+      if (general)
+        {
+          status = mgx_cube_affine_metric(cube, l, general->jacobian, metric, &det);
+          if (status != MGX_OK)
+            break;
+          if (general->coef_q && general->coef_q[l])
+            d.coef_q = general->coef_q[l];
+          else
+            {
+              const int    n  = cube->p + 1;
+              const size_t n3 = (size_t)n * n * n;
+              unit.resize((size_t)d.n_cells * 6 * n3);
+              for (size_t q = 0; q < n3; ++q)
+                {
+                  const double jxw = cube->basis.gw[q % n] * cube->basis.gw[(q / n) % n] * cube->basis.gw[q / (n * n)] * det;
+                  for (int c = 0; c < 6; ++c)
+                    unit[c * n3 + q] = jxw * metric[c];
+                }
+              for (size_t cell = 1; cell < d.n_cells; ++cell)
+                std::copy(unit.begin(), unit.begin() + 6 * n3, unit.begin() + cell * 6 * n3);
+              d.coef_q = unit.data();
+            }
+        }
       // decomposed mesh: plan ids 2*level (fp64 operator) and 2*level+1 (V-cycle operator)
       mgx_exchange_desc ex;
       const uint32_t   *idx[27];
@@ -1352,6 +1426,10 @@ int mgx_cube_solver_create_opt(mgx_context_t ctx, mgx_cube_t cube, int vnumber, 
           ex.plan_id = 2 * l + 1;
           status     = mgx_operator_create(ctx, &d, &out->matrix[l]);
         }
+      if (general && status == MGX_OK)
+        status = mgx_operator_enable_coefficient_update(out->matrix_dp[l], metric, det);
+      if (general && status == MGX_OK && out->matrix[l] != out->matrix_dp[l])
+        status = mgx_operator_enable_coefficient_update(out->matrix[l], metric, det);
     }
   for (int l = 1; l < nl && status == MGX_OK; ++l)
     {
@@ -1377,7 +1455,8 @@ int mgx_cube_solver_create_opt(mgx_context_t ctx, mgx_cube_t cube, int vnumber, 
           rhs[l] = device_rhs ? nullptr : mgx_cube_rhs(cube, l);
           bci[l] = cube->levels[l].bc_index.data();
           bcv[l] = cube->levels[l].bc_value.data();
-          bcn[l] = (uint32_t)cube->levels[l].bc_index.size();
+          // (general hierarchy: the Newton update has homogeneous boundary values, the right-hand side is the caller's)
+          bcn[l] = general ? 0u : (uint32_t)cube->levels[l].bc_index.size();
         }
       mgx_solver_desc sd;
       sd.n_levels    = nl;
@@ -1394,7 +1473,7 @@ int mgx_cube_solver_create_opt(mgx_context_t ctx, mgx_cube_t cube, int vnumber, 
       status         = mgx_solver_create(ctx, &sd, &out->solver);
       // the right-hand sides on the device (laplace_operator.h:804-845): the host only evaluates f JxW at the
       // quadrature points
-      for (int l = 0; l < nl && status == MGX_OK && device_rhs; ++l)
+      for (int l = 0; l < nl && status == MGX_OK && device_rhs && !general; ++l)
         {
           const size_t        n3 = (size_t)(cube->p + 1) * (cube->p + 1) * (cube->p + 1), count = n3 * cube->levels[l].n_cells;
           std::vector<double> fq(count);
@@ -1424,5 +1503,3 @@ int mgx_cube_solver_create_opt(mgx_context_t ctx, mgx_cube_t cube, int vnumber, 
     }
   return status;
 }
-
-} // extern "C"

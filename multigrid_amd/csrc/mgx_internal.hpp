@@ -279,6 +279,28 @@ namespace mgx
   // launch_cell_diagonal (lists of cells that share no DoF / ordered assembly / atomics).  dst zeroed by the caller.
   void launch_cell_residual(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *rhs_q,
                             const uint32_t *lists = nullptr, const uint32_t *list_start = nullptr, int n_lists = 0);
+  // MinimalSurfaceOperator::compute_residual (minimal_surface/program.cc:169-197) on affine cells with the metric
+  // M = J^-1 J^-T [xx,yy,zz,xy,xz,yz] and det J: dst = - sum over the cells of grad phi_i . a JxW M grad u, a = 1 or
+  // 1 / sqrt(1 + |grad u|^2); src through idx27_plain, dst through idx27.  n_lists > 0: launches over cell lists that share
+  // no DoF (dst zeroed by the caller); n_lists == 0: the operator's ordered assembly (required then, dst written)
+  void launch_cell_nl_residual(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,
+                               void *dst, const void *src, const uint32_t *lists = nullptr, const uint32_t *list_start = nullptr,
+                               int n_lists = 0);
+  // ---- solution-dependent coefficients (mgx_nonlinear.hip) ----
+  // MinimalSurfaceOperator::evaluate_coefficient (minimal_surface/program.cc:120-165) on affine cells: op.coef_q =
+  // JxW_q M (first_time) or JxW_q (M - (M g)(M g)^T / (1 + s)) / sqrt(1 + s), s = g^T M g, g the reference-space
+  // gradient of `state` (operator's number type, read through idx27_plain) at the quadrature points.
+  // op: index table, 1D tables and number type of the state and of the arithmetic; coef_q / coef_number: the tensor
+  // array written and its number type (that of op, or fp32 from an fp64 op: the rounded fp64 tensor).
+  // metric_q: reserved for a per-point metric (curved cells); must be nullptr.
+  void launch_evaluate_coefficient(hipStream_t s, const OperatorData &op, void *coef_q, int coef_number, bool minimal_surface,
+                                   const double *metric, double det, const void *metric_q, const void *state);
+  // state interpolation to the coarser level (minimal_surface/program.cc:425-457): every coarse DoF = the polynomial of
+  // the child that contains the coarse node, evaluated there.  r1d: device [(2p+1)(p+1)], r1d[a (p+1) + i] = weight of
+  // fine patch point a for coarse node i; own_c: device [n_coarse_cells], bit e set iff the cell is the first (in cell
+  // order) that contains its entity e -- the one writer of the entity's DoFs
+  void launch_interpolate_to_coarse(hipStream_t s, const TransferData &t, const void *r1d, const uint32_t *own_c, void *coarse,
+                                    const void *fine);
   // free_schedule (modes 0..6, op.bricks.fr.available()): the launch groups are those of the reduced-colour
   // schedule; the caller completes the private DoFs with launch_surf_finish: DoFs [first, first + count)
   // of op.bricks.fr.surf_dof; those below n_surf_shared: carrier[d] = sum only

@@ -17,146 +17,12 @@
 // the x-line {left vertex/edge/face entry, p-1 contiguous interior entries, right entry}.
 #include "mgx_macro_device.hpp" // buffer-descriptor access (brick_general_kernel)
 #include "mgx_internal.hpp"
+#include "mgx_cell_device.hpp"
 
 #include <hip/hip_runtime.h>
 
 namespace mgx
 {
-#ifndef MGX_GENERAL_WG_THREADS
-#define MGX_GENERAL_WG_THREADS 256 // 128 measured: no gain
-#endif
-  template <int P, int WG = 256>
-  struct Cfg
-  {
-    static constexpr int N        = P + 1;
-    static constexpr int LN       = N | 1; // x-line pitch, odd => conflict-free ds_read_b64
-    static constexpr int TPC      = N * N; // threads per cell
-    static constexpr int CPB      = (WG / TPC) < 1 ? 1 : (WG / TPC);
-    static constexpr int THREADS  = ((CPB * TPC + 63) / 64) * 64;
-    static constexpr int CELL_LDS = N * N * LN;
-  };
-
-  // out[a] = sum_b M[a*N+b] in[b]
-  template <int N, typename T>
-  __device__ __forceinline__ void mv(const T *__restrict__ M, const T (&in)[N], T (&out)[N])
-  {
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-      {
-        T s = M[a * N] * in[0];
-#pragma unroll
-        for (int b = 1; b < N; ++b)
-          s = fma(M[a * N + b], in[b], s);
-        out[a] = s;
-      }
-  }
-
-  // out[a] = sum_b M[b*N+a] in[b]
-  template <int N, typename T>
-  __device__ __forceinline__ void mvT(const T *__restrict__ M, const T (&in)[N], T (&out)[N])
-  {
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-      {
-        T s = M[a] * in[0];
-#pragma unroll
-        for (int b = 1; b < N; ++b)
-          s = fma(M[b * N + a], in[b], s);
-        out[a] = s;
-      }
-  }
-
-  // entity code (0 = low vertex plane, 1 = interior, 2 = high) and offset inside the entity of
-  // the 1D node index j (vector_access_reduced.h:232-247)
-  template <int P>
-  __device__ __forceinline__ void node_code(int j, int &code, int &offs)
-  {
-    code = (j == 0) ? 0 : (j == P ? 2 : 1);
-    offs = (code == 1) ? j - 1 : 0;
-  }
-
-  template <int P>
-  struct LineIndex
-  {
-    uint32_t b0, b1, b2; // first DoF of the left / interior / right entity of this x-line
-    uint32_t off;        // offset of the line inside those entities
-  };
-
-  // address computation of read_dof_values_compressed for the x-line (j,k) of `cell`
-  // (vector_access_reduced.h:153-229)
-  template <int P>
-  __device__ __forceinline__ LineIndex<P> line_index(const uint32_t *__restrict__ idx27, uint32_t cell, int j,
-                                                     int k)
-  {
-    int cy, oy, cz, oz;
-    node_code<P>(j, cy, oy);
-    node_code<P>(k, cz, oz);
-    LineIndex<P>    L;
-    const uint32_t *ind = idx27 + 27u * (size_t)cell + 3 * (3 * cz + cy);
-    L.b0                = ind[0];
-    L.b1                = ind[1];
-    L.b2                = ind[2];
-    L.off               = (uint32_t)((cy == 1 ? P - 1 : 1) * oz + oy);
-    return L;
-  }
-
-  template <int P, typename T>
-  __device__ __forceinline__ void gather_line(const T *__restrict__ src, const LineIndex<P> &L, T (&r)[P + 1])
-  {
-    r[0] = L.b0 != kInvalid ? src[L.b0 + L.off] : T(0);
-#pragma unroll
-    for (int i = 0; i < P - 1; ++i)
-      r[1 + i] = L.b1 != kInvalid ? src[L.b1 + L.off * (uint32_t)(P - 1) + (uint32_t)i] : T(0);
-    r[P] = L.b2 != kInvalid ? src[L.b2 + L.off] : T(0);
-  }
-
-  template <int P, typename T>
-  __device__ __forceinline__ void scatter_add_line(T *__restrict__ dst, const LineIndex<P> &L,
-                                                   const T (&r)[P + 1])
-  {
-    if (L.b0 != kInvalid)
-      unsafeAtomicAdd(&dst[L.b0 + L.off], r[0]);
-    if (L.b1 != kInvalid)
-      {
-#pragma unroll
-        for (int i = 0; i < P - 1; ++i)
-          unsafeAtomicAdd(&dst[L.b1 + L.off * (uint32_t)(P - 1) + (uint32_t)i], r[1 + i]);
-      }
-    if (L.b2 != kInvalid)
-      unsafeAtomicAdd(&dst[L.b2 + L.off], r[P]);
-  }
-
-  // the same without atomics: for launches over cells of one colour (no two of them share a DoF)
-  template <int P, typename T>
-  __device__ __forceinline__ void scatter_add_line_plain(T *__restrict__ dst, const LineIndex<P> &L,
-                                                         const T (&r)[P + 1])
-  {
-    if (L.b0 != kInvalid)
-      dst[L.b0 + L.off] += r[0];
-    if (L.b1 != kInvalid)
-      {
-#pragma unroll
-        for (int i = 0; i < P - 1; ++i)
-          dst[L.b1 + L.off * (uint32_t)(P - 1) + (uint32_t)i] += r[1 + i];
-      }
-    if (L.b2 != kInvalid)
-      dst[L.b2 + L.off] += r[P];
-  }
-
-  // Ordered assembly (levels without a brick schedule): instead of adding into the vector, a cell
-  // stores its (p+1)^3 local results at scratch[cell (p+1)^3 + (k n + j) n + i]; assemble_kernel
-  // below then adds, for every DoF, its contributions in ascending cell order -- no atomics, the
-  // sum does not depend on the order in which the workgroups happen to run
-  template <int P, typename T>
-  __device__ __forceinline__ void store_line_local(T *__restrict__ scratch, uint32_t cell, int j, int k,
-                                                   const T (&r)[P + 1])
-  {
-    constexpr int N = P + 1;
-    T            *o = scratch + (size_t)cell * (N * N * N) + (size_t)((k * N + j) * N);
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-      o[i] = r[i];
-  }
 
   // mode 0: dst[d] = sum of the contributions of DoF d (DoFs without contributions, i.e. the
   //         constrained ones, get 0 -- or tail_src[d] for d >= n_head: the identity rows of
@@ -374,12 +240,16 @@ namespace mgx
   // unconstrained index table idx_gather (boundary values in the constrained entries) and negated (:823-824),
   // rhs_q[cell][q] = f(x_q) JxW_q is added to the integrand of the test function values (:839); the rows of
   // constrained DoFs are still skipped on the way out.
-  template <int P, typename T, bool PERQ, bool RESID = false>
+  // MINSURF (with RESID, not PERQ; MinimalSurfaceOperator::compute_residual, minimal_surface/program.cc:169-197): affine
+  // cells with c0..c5 = M = J^-1 J^-T and det = det J; the flux of a point is M g w_q det J / sqrt(1 + |grad u|^2),
+  // |grad u|^2 = g^T M g of the reference-space gradient g (:187-192).
+  template <int P, typename T, bool PERQ, bool RESID = false, bool MINSURF = false>
   __global__ void __launch_bounds__((Cfg<P, MGX_GENERAL_WG_THREADS>::THREADS))
     cell_loop_general_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *__restrict__ idx27,
                              uint32_t n_cells, const Basis1D<T> *__restrict__ B, const T *__restrict__ coef_q, T c0,
                              T c1, T c2, T c3, T c4, T c5, const uint32_t *__restrict__ cell_list, T *__restrict__ scratch,
-                             const uint32_t *__restrict__ idx_gather = nullptr, const T *__restrict__ rhs_q = nullptr)
+                             const uint32_t *__restrict__ idx_gather = nullptr, const T *__restrict__ rhs_q = nullptr,
+                             T det = T(0))
   {
     using C           = Cfg<P, MGX_GENERAL_WG_THREADS>;
     constexpr int N   = C::N;
@@ -484,6 +354,13 @@ namespace mgx
                 t0 = c0 * w, t1 = c1 * w, t2 = c2 * w, t3 = c3 * w, t4 = c4 * w, t5 = c5 * w;
               }
             const T gx = Xc[zl + k * PL], gy = Yc[zl + k * PL], g = gz[k];
+            if (MINSURF)
+              {
+                const T s = gx * (c0 * gx + c3 * gy + c4 * g) + gy * (c3 * gx + c1 * gy + c5 * g) +
+                            g * (c4 * gx + c5 * gy + c2 * g);
+                const T a = det / sqrt(T(1) + s);
+                t0 *= a, t1 *= a, t2 *= a, t3 *= a, t4 *= a, t5 *= a;
+              }
             Xc[zl + k * PL] = t0 * gx + t3 * gy + t4 * g; // :473-486 / :505-518
             Yc[zl + k * PL] = t3 * gx + t1 * gy + t5 * g;
             gz[k]           = t4 * gx + t5 * gy + t2 * g;
@@ -1480,6 +1357,51 @@ namespace mgx
     else
       {
         MGX_DISPATCH_P(op.p, cell_residual_t<P, float>(s, op, dst, src, rhs_q, lists, list_start, n_lists));
+      }
+  }
+
+  // MinimalSurfaceOperator::compute_residual (minimal_surface/program.cc:169-197) on affine cells: the residual form of
+  // the general per-cell kernel with the tensor of the law -- det J M per mesh (first_time) or that divided by
+  // sqrt(1 + |grad u|^2) at every point -- and the assembly variants of cell_residual_t (never atomics: the caller
+  // passes cell lists or the operator has the ordered-assembly tables)
+  template <int P, typename T>
+  static void cell_nl_residual_t(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *M, double det,
+                                 void *dst, const void *src, const uint32_t *lists, const uint32_t *list_start, int n_lists)
+  {
+    using C            = Cfg<P, MGX_GENERAL_WG_THREADS>;
+    T        *scratch  = n_lists == 0 ? (T *)op.cell_scratch : nullptr;
+    const int n_launch = n_lists > 0 ? n_lists : 1;
+    for (int k = 0; k < n_launch; ++k)
+      {
+        const uint32_t  count = n_lists > 0 ? list_start[k + 1] - list_start[k] : op.n_cells;
+        const uint32_t *list  = n_lists > 0 ? lists + list_start[k] : nullptr;
+        if (count == 0)
+          continue;
+        const uint32_t nb = (count + C::CPB - 1) / C::CPB;
+        if (minimal_surface)
+          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, false, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst,
+                             (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)nullptr, (T)M[0], (T)M[1],
+                             (T)M[2], (T)M[3], (T)M[4], (T)M[5], list, scratch, op.idx27_plain, (const T *)nullptr, (T)det);
+        else
+          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, false, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst,
+                             (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)nullptr, (T)(det * M[0]),
+                             (T)(det * M[1]), (T)(det * M[2]), (T)(det * M[3]), (T)(det * M[4]), (T)(det * M[5]), list, scratch,
+                             op.idx27_plain, (const T *)nullptr);
+      }
+    if (scratch)
+      assemble_t<T>(s, op, 0, dst, nullptr, 0u);
+  }
+
+  void launch_cell_nl_residual(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,
+                               void *dst, const void *src, const uint32_t *lists, const uint32_t *list_start, int n_lists)
+  {
+    if (op.number == 1)
+      {
+        MGX_DISPATCH_P(op.p, cell_nl_residual_t<P, double>(s, op, minimal_surface, metric, det, dst, src, lists, list_start, n_lists));
+      }
+    else
+      {
+        MGX_DISPATCH_P(op.p, cell_nl_residual_t<P, float>(s, op, minimal_surface, metric, det, dst, src, lists, list_start, n_lists));
       }
   }
 

@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""minimal_surface/program.cc in 3D on the cube [-0.9, 1]^3: -div(grad u / sqrt(1 + |grad u|^2)) = 0 with the boundary
+values A sin(2 pi (x + y)) of the reference's Solution (:97-99; independent of z, so the problem keeps the character of
+the 2D one), Newton's method with V-cycle-preconditioned CG at ReductionControl(m, 1e-13, 1e-4) per step and the
+step-halving line search (:414-573), at most 100 steps or until the residual norm is below --tolerance (:656-662).
+Prints the reference's lines: "Residual norm: ... in ... steps to ...", "Computing times: nl iterations: ...".
+
+Usage: python tools/minimal_surface.py [degree] [n_refine] [--amplitude A] [--vcycle f32|f64] [--tolerance T]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import multigrid_amd as mg  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("degree", type=int, nargs="?", default=2)
+    ap.add_argument("n_refine", type=int, nargs="?", default=3)
+    ap.add_argument("--amplitude", type=float, default=1.0)
+    ap.add_argument("--vcycle", choices=["f32", "f64"], default="f32", help="number type of the V-cycle (level_number)")
+    ap.add_argument("--tolerance", type=float, default=1e-12, help="stop when the residual norm is below (:660)")
+    ap.add_argument("--max-steps", type=int, default=100, help="n_inner_iterations (:620)")
+    args = ap.parse_args()
+
+    ctx = mg.Context(0)
+    cube = mg.Cube(args.degree, 1, args.n_refine)
+    print("Testing FE_Q<3>(%d)" % args.degree)
+    print("Number of degrees of freedom: %d (%d^3 cells, %d levels)"
+          % (cube.n_dofs(cube.max_level), cube.cells_per_dim(cube.max_level), cube.n_levels), flush=True)
+    t0 = time.perf_counter()
+    amplitude = args.amplitude
+    problem = mg.MinimalSurfaceProblem(ctx, cube, lambda x: amplitude * np.sin(2 * np.pi * (x[:, 0] + x[:, 1])),
+                                       mg.F32 if args.vcycle == "f32" else mg.F64)
+    ctx.sync()
+    print("Setup time                            %g s" % (time.perf_counter() - t0))
+    log = lambda line: print(line, flush=True)
+    t0 = time.perf_counter()
+    steps = problem.run(args.max_steps, args.tolerance, log)
+    ctx.sync()
+    total = time.perf_counter() - t0
+    print("Computing times: nl iterations: %d residuals %d %g  linear solver %d %g  coefficients %d %g  total %g"
+          % (steps, problem.n_residual, problem.time_residual, problem.linear_iterations, problem.time_solve, steps,
+             problem.time_coefficient, total))
+    print("CG iterations per Newton step: %s" % " ".join(str(h[3]) for h in problem.history))
+    first, last = problem.history[0][0], problem.history[-1][2]
+    problem.close()
+    cube.close()
+    ctx.close()
+    return 0 if last < 1e-10 * first else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
