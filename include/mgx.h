@@ -297,9 +297,19 @@ int mgx_get_inverse_diagonal(mgx_operator_t op, const void **dptr);
 #define MGX_LAW_MINIMAL_SURFACE 1
 /* Tells an operator of the general branch (created with mgx_operator_desc::coef_q, e.g. the unit-law tensor) the affine
  * geometry of its level: metric = M as [xx,yy,zz,xy,xz,yz] (what MatrixFree's mapping info holds as `jacobians` and
- * `JxW_values`, :144-152).  An operator without a per-point coefficient: MGX_ERR_UNSUPPORTED.  (A per-point metric
- * for curved cells is not implemented; the entry points below keep their meaning when it is added.) */
+ * `JxW_values`, :144-152).  An operator without a per-point coefficient: MGX_ERR_UNSUPPORTED. */
 int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metric[6], double det_jacobian);
+/* per-point geometry of a level with curved cells: unit_q[cell][6][(p+1)^3] = JxW_q J^-1 J^-T (the unit-law tensor,
+ * layout of mgx_operator_desc::coef_q) and jxw_q[cell][(p+1)^3] = JxW_q; host pointers, copied (to the device, in the
+ * operator's number type).  With U = unit_q, w = jxw_q, v = U g / w (= M g), s = g . v the laws above read
+ *   MGX_LAW_UNIT             coef_q = U
+ *   MGX_LAW_MINIMAL_SURFACE  coef_q = (U - (U g)(U g)^T / (w (1 + s))) / sqrt(1 + s)
+ *   residual                 dst_i = - sum_q grad_ref phi_i(q) . a (U g),  a = 1 / a = 1 / sqrt(1 + s)
+ * i.e. M = U / w per point.  A deal.II caller merges mapping_info's `JxW_values` and `jacobians` of every point this
+ * way.  w > 0 and a positive diagonal of U at every point, or MGX_ERR_INVALID_ARGUMENT; an operator without a per-point
+ * coefficient: MGX_ERR_UNSUPPORTED.  Either enable call replaces what the other set; the entry points below mean the
+ * same with both. */
+int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *unit_q, const double *jxw_q);
 /* MinimalSurfaceOperator::evaluate_coefficient(first_time, solution) :120-165: rewrites the operator's coef_q on the
  * device from `state` (device vector of the operator's number type, boundary values in place, read through
  * idx27_plain).  The inverse diagonal becomes stale: mgx_compute_diagonal before it is used again (a smoother created

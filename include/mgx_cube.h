@@ -103,13 +103,15 @@ int mgx_cube_create_shell(int degree, int n_coarse, int n_refine, int problem, m
 int mgx_cube_create_shell_ranks(int degree, int n_coarse, int n_refine, int problem, int n_ranks, int rank, mgx_cube_t *cube);
 /* level of the whole mesh that level 0 of this object is (0 except for the level-1 partition above) */
 int mgx_cube_level_offset(mgx_cube_t cube);
-/* multi-block meshes: the physical Gauss-Lobatto points of every cell of a level,
- * out[cell][3][(p+1)^3], and the number of cells around each of the 27 entities of every cell
- * (what deal.II's mesh would tell a caller) */
+/* the physical Gauss-Lobatto points of every cell of a level, out[cell][3][(p+1)^3] (box meshes: the map of the
+ * geometry at the points of the reference box), and, on multi-block meshes, the number of cells around each of the 27
+ * entities of every cell (what deal.II's mesh would tell a caller) */
 int            mgx_cube_cell_nodes(mgx_cube_t cube, int level, double *out);
 const uint8_t *mgx_cube_entity_multiplicity(mgx_cube_t cube, int level);
 /* [n_cells][6][(p+1)^3] merged coefficient of a mapped level (NULL on the Cartesian cube) */
 const double *mgx_cube_coef_q(mgx_cube_t cube, int level);
+/* [n_cells][(p+1)^3] JxW_q of a mapped level (NULL on the Cartesian cube) */
+const double *mgx_cube_jxw_q(mgx_cube_t cube, int level);
 int mgx_cube_rank(mgx_cube_t cube);
 int mgx_cube_size(mgx_cube_t cube);
 void mgx_cube_cells_per_dim3(mgx_cube_t cube, int level, uint32_t local[3], uint32_t global[3]);
@@ -197,11 +199,15 @@ int mgx_cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vcycle_number
 int mgx_cube_solver_create_opt(mgx_context_t ctx, mgx_cube_t cube, int vcycle_number, int degree_pre, int n_cycles,
                                int device_rhs, mgx_cube_solver *out);
 /* The hierarchy in the GENERAL branch of the operator, for solution-dependent coefficients (mgx_solver_update_coefficient,
- * include/mgx.h; LaplaceProblem::setup_system of minimal_surface/program.cc): Cartesian cube / box meshes on one rank.
+ * include/mgx.h; LaplaceProblem::setup_system of minimal_surface/program.cc), on one rank.  Cartesian cube / box meshes:
  * jacobian (3 x 3 row-major, may be NULL: identity): the constant matrix A of an affine map x = x0 + A X of the whole
  * box, so that the cells of level l have the Jacobian h_l A -- an anisotropic or sheared box; the index tables do not
  * depend on it.  Every level operator is created with coef_q[l] ([n_cells][6][(p+1)^3], may be NULL as may coef_q:
- * the unit-law tensor JxW_q J^-1 J^-T) and told its metric (mgx_operator_enable_coefficient_update).  Right-hand
+ * the unit-law tensor JxW_q J^-1 J^-T) and told its metric (mgx_operator_enable_coefficient_update).  Mapped cubes
+ * with MGX_CUBE_PROBLEM_CUBE (SHEARED and SHELL_SECTOR boxes, the hyper_shell meshes): jacobian must be NULL; the level
+ * operators are created with mgx_cube_coef_q (or coef_q[l]) and the fp64 ones are told the per-point geometry
+ * (mgx_operator_enable_coefficient_update_q with mgx_cube_coef_q, mgx_cube_jxw_q), which the refresh of an fp32 V-cycle
+ * operator reads too.  MGX_CUBE_PROBLEM_SHELL (the tensor contains a(x)): MGX_ERR_UNSUPPORTED.  Right-hand
  * sides are zero and boundary values homogeneous: the solver solves for an update, rhs[maxlevel] is the caller's. */
 int mgx_cube_solver_create_general(mgx_context_t ctx, mgx_cube_t cube, int vcycle_number, int degree_pre, int n_cycles,
                                    const double *jacobian, const double *const *coef_q, mgx_cube_solver *out);

@@ -480,11 +480,18 @@ class Cube:
             return None
         return np.ctypeslib.as_array(ptr, shape=(self.n_cells(l), 6, (self.degree + 1) ** 3)).copy()
 
+    def jxw_q(self, l):
+        """[n_cells, (p+1)^3] JxW at the quadrature points of a mapped level (None on the Cartesian cube)"""
+        ptr = self.lib.mgx_cube_jxw_q(self.h, l)
+        if not ptr:
+            return None
+        return np.ctypeslib.as_array(ptr, shape=(self.n_cells(l), (self.degree + 1) ** 3)).copy()
+
     def children(self, l):
         return self._arr("mgx_cube_children", (self.n_cells(l - 1), 8), l)
 
     def cell_nodes(self, l):
-        """multi-block meshes: physical Gauss-Lobatto points of every cell, [n_cells, 3, (p+1)^3]"""
+        """physical Gauss-Lobatto points of every cell, [n_cells, 3, (p+1)^3] (x fastest)"""
         out = np.empty((self.n_cells(l), 3, (self.degree + 1) ** 3))
         check(self.lib.mgx_cube_cell_nodes(self.h, l, out.ctypes.data_as(_lib.f64p)))
         return out
@@ -598,8 +605,15 @@ class Cube:
 
     def dof_coordinates(self, l, jacobian=None):
         """[n_dofs, 3] physical coordinates of the Gauss-Lobatto node of every DoF of level l (Cartesian cube / box;
-        jacobian: the affine map x = x0 + A X of the box about its lower corner x0)"""
-        assert self.shell is None and self.size == 1
+        jacobian: the affine map x = x0 + A X of the box about its lower corner x0).  Mapped cubes (sheared and
+        shell_sector boxes, hyper_shell): the cell nodes, through the unconstrained index table."""
+        assert self.size == 1
+        if self.shell is not None or (self.box_desc is not None and self.box_desc["geometry"] != "cartesian"):
+            assert jacobian is None
+            dofs = _cell_dofs(self.idx27_plain(l), self.degree)
+            X = np.empty((self.n_dofs(l), 3))
+            X[dofs.ravel()] = self.cell_nodes(l).transpose(0, 2, 1).reshape(-1, 3)
+            return X
         p, g = self.degree, self.dof_grid(l).astype(np.int64)
         n = np.array(self.cells_per_dim3(l)[1], dtype=np.int64)
         G = n * p + 1
@@ -609,6 +623,23 @@ class Cube:
         if jacobian is not None:
             X = X @ np.asarray(jacobian, dtype=np.float64).T
         return (-0.9 if self.box_desc is None else self.box_desc["origin"]) + X
+
+
+def _cell_dofs(idx27, p):
+    """[n_cells, (p+1)^3] DoF of every node of every cell (x fastest) from a compressed index table without constrained
+    entries (the addressing of read_dof_values_compressed, vector_access_reduced.h:153-229)"""
+    n = p + 1
+    idx27 = np.asarray(idx27, dtype=np.int64).reshape(-1, 27)
+    out = np.empty((idx27.shape[0], n, n, n), dtype=np.int64)
+    code = [0 if a == 0 else (2 if a == p else 1) for a in range(n)]
+    for k in range(n):
+        for j in range(n):
+            oz, oy = (k - 1 if code[k] == 1 else 0), (j - 1 if code[j] == 1 else 0)
+            off = (p - 1 if code[j] == 1 else 1) * oz + oy
+            for i in range(n):
+                base = idx27[:, 9 * code[k] + 3 * code[j] + code[i]]
+                out[:, k, j, i] = base + (off * (p - 1) + i - 1 if code[i] == 1 else off)
+    return out.reshape(idx27.shape[0], n ** 3)
 
 
 class LaplaceOperator:
@@ -673,6 +704,17 @@ class LaplaceOperator:
         m = np.ascontiguousarray(metric, dtype=np.float64)
         assert m.size == 6
         check(self.lib.mgx_operator_enable_coefficient_update(self.h, m.ctypes.data_as(_lib.f64p), float(det_jacobian)))
+
+    def enable_coefficient_update_q(self, unit_q, jxw_q):
+        """per-point geometry of a level with curved cells: unit_q [n_cells, 6, (p+1)^3] = JxW_q J^-1 J^-T and jxw_q
+        [n_cells, (p+1)^3] = JxW_q (Cube.coef_q, Cube.jxw_q of a mapped cube with problem "cube")"""
+        u = np.ascontiguousarray(unit_q, dtype=np.float64)
+        w = np.ascontiguousarray(jxw_q, dtype=np.float64)
+        p, n = C.c_void_p(), C.c_size_t()
+        check(self.lib.mgx_operator_get_coefficient(self.h, C.byref(p), C.byref(n)))  # (refuses an operator without coef_q)
+        assert u.size == n.value and 6 * w.size == n.value
+        check(self.lib.mgx_operator_enable_coefficient_update_q(self.h, u.ctypes.data_as(_lib.f64p),
+                                                                w.ctypes.data_as(_lib.f64p)))
 
     def evaluate_coefficient(self, law, state):
         """evaluate_coefficient(first_time, solution) :120-165: coef_q from the state (operator's number type, boundary
@@ -789,8 +831,9 @@ class MultigridSolver:
                  polynomial="first_kind", agglomerate=True, device_rhs=False, general=False, jacobian=None, coef_q=None):
         """device_rhs: the right-hand sides are assembled on the GPU (mgx_solver_compute_rhs) instead of on the host.
         general: the hierarchy in the general branch of the operator for solution-dependent coefficients
-        (mgx_cube_solver_create_general: Cartesian cube / box on one rank; zero right-hand sides, homogeneous boundary
-        values), with the constant matrix `jacobian` of an affine map of the box (None: identity) and, per level, the
+        (mgx_cube_solver_create_general: one rank; zero right-hand sides, homogeneous boundary values), on a Cartesian
+        cube / box with the constant matrix `jacobian` of an affine map of the box (None: identity), or on a mapped cube
+        with problem "cube" (sheared, shell_sector, shell=6|12; per-point geometry, jacobian None); per level, the
         merged coefficient coef_q[l] ([n_cells, 6, (p+1)^3]; None: the unit-law tensor).
         polynomial: Chebyshev polynomial type of the level smoothers: "first_kind" is what
         MultigridSolver<dim,p,Number,Number2> sets (multigrid_solver.h:277-278), "fourth_kind" what
@@ -1013,7 +1056,8 @@ LAW_UNIT, LAW_MINIMAL_SURFACE = 0, 1
 
 
 class MinimalSurfaceProblem:
-    """LaplaceProblem<dim> of minimal_surface/program.cc in 3D on the Cartesian cube / box: -div(grad u / sqrt(1 + |grad u|^2))
+    """LaplaceProblem<dim> of minimal_surface/program.cc in 3D on the Cartesian cube / box or a mapped cube (curved cells,
+    boundary function at the mapped node coordinates): -div(grad u / sqrt(1 + |grad u|^2))
     = 0 with Dirichlet values, Newton's method with a V-cycle-preconditioned CG per step and the reference's
     step-halving line search.  Vectors, norms and updates stay on the device; scalars cross to the host.
 

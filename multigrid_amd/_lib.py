@@ -205,6 +205,7 @@ SIGNATURES = {
     "mgx_cube_prolong_1d": (f64p, [vp]),
     "mgx_cube_rhs": (f64p, [vp, C.c_int]),
     "mgx_cube_coef_q": (f64p, [vp, C.c_int]),
+    "mgx_cube_jxw_q": (f64p, [vp, C.c_int]),
     "mgx_cube_bc_count": (C.c_uint32, [vp, C.c_int]),
     "mgx_cube_bc_index": (u32p, [vp, C.c_int]),
     "mgx_cube_bc_value": (f64p, [vp, C.c_int]),
@@ -227,6 +228,7 @@ SIGNATURES = {
     "mgx_solver_set_agglomeration": (C.c_int, [vp, C.c_int, vp, u32p, C.POINTER(C.c_uint8), C.c_uint32]),
     # solution-dependent coefficient (minimal_surface)
     "mgx_operator_enable_coefficient_update": (C.c_int, [vp, f64p, C.c_double]),
+    "mgx_operator_enable_coefficient_update_q": (C.c_int, [vp, f64p, f64p]),
     "mgx_evaluate_coefficient": (C.c_int, [vp, C.c_int, vp]),
     "mgx_compute_nonlinear_residual": (C.c_int, [vp, C.c_int, vp, vp]),
     "mgx_operator_get_coefficient": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),

@@ -299,6 +299,9 @@ struct mgx_operator_s
   bool     coef_update  = false;
   double   metric[6]    = {0, 0, 0, 0, 0, 0};
   double   det_jacobian = 0;
+  // ... or (mgx_operator_enable_coefficient_update_q) the per-point geometry of curved cells in the operator's number
+  // type: unit_q [n_cells][6][n^3] = JxW_q J^-1 J^-T, jxw_q [n_cells][n^3] = JxW_q; nullptr: affine geometry
+  void    *unit_q = nullptr, *jxw_q = nullptr;
 };
 
 struct mgx_smoother_s
@@ -1886,6 +1889,8 @@ int mgx_operator_destroy(mgx_operator_t op)
   (void)hipFree(op->cg_partials);
   (void)hipFree(op->cg_result);
   (void)hipFree(op->cg_carrier);
+  (void)hipFree(op->unit_q);
+  (void)hipFree(op->jxw_q);
   (void)hipFree(op->global_index_dev);
   if (op->plan)
     {
@@ -2125,9 +2130,67 @@ int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metri
   const double det_m = m0 * (m1 * m2 - m5 * m5) - m3 * (m3 * m2 - m5 * m4) + m4 * (m3 * m5 - m1 * m4);
   MGX_REQUIRE(det_jacobian > 0. && m0 > 0. && m0 * m1 - m3 * m3 > 0. && det_m > 0.,
               "mgx_operator_enable_coefficient_update: the metric must be positive definite and det J > 0");
+  if (op->unit_q) // replaces a per-point geometry, which a kernel in flight may read
+    {
+      MGX_HIP(hipStreamSynchronize(op->ctx->stream));
+      (void)hipFree(op->unit_q);
+      (void)hipFree(op->jxw_q);
+      op->unit_q = op->jxw_q = nullptr;
+    }
   std::copy(metric, metric + 6, op->metric);
   op->det_jacobian = det_jacobian;
   op->coef_update  = true;
+  return MGX_OK;
+}
+
+// host doubles to a new device array of the number type
+static int upload_as(int number, void **dev, const double *host, size_t n)
+{
+  MGX_HIP(hipMalloc(dev, number_size(number) * n));
+  if (number == MGX_F64)
+    MGX_HIP(hipMemcpy(*dev, host, sizeof(double) * n, hipMemcpyHostToDevice));
+  else
+    {
+      std::vector<float> tmp(host, host + n);
+      MGX_HIP(hipMemcpy(*dev, tmp.data(), sizeof(float) * n, hipMemcpyHostToDevice));
+    }
+  return MGX_OK;
+}
+
+int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *unit_q, const double *jxw_q)
+{
+  MGX_REQUIRE(op && unit_q && jxw_q, "mgx_operator_enable_coefficient_update_q: null argument");
+  if (!op->d.coef_q)
+    return fail(MGX_ERR_UNSUPPORTED,
+                "mgx_operator_enable_coefficient_update_q: the operator has no per-point coefficient (separable or "
+                "one-tensor-per-mesh branch); create it with mgx_operator_desc::coef_q set, e.g. to the unit-law tensor "
+                "JxW_q J^-1 J^-T");
+  const size_t n3 = (size_t)(op->d.p + 1) * (op->d.p + 1) * (op->d.p + 1), nc = op->d.n_cells;
+  bool         ok = true;
+  for (size_t c = 0; c < nc && ok; ++c)
+    for (size_t q = 0; q < n3 && ok; ++q)
+      {
+        const double *u = unit_q + c * 6 * n3 + q;
+        ok              = jxw_q[c * n3 + q] > 0. && u[0] > 0. && u[n3] > 0. && u[2 * n3] > 0.; // (false for NaN)
+      }
+  MGX_REQUIRE(ok, "mgx_operator_enable_coefficient_update_q: JxW_q and the diagonal of JxW_q J^-1 J^-T must be positive at every "
+                  "quadrature point");
+  void *u_dev = nullptr, *w_dev = nullptr;
+  int   status = upload_as(op->d.number, &u_dev, unit_q, nc * 6 * n3);
+  if (status == MGX_OK)
+    status = upload_as(op->d.number, &w_dev, jxw_q, nc * n3);
+  if (status != MGX_OK)
+    {
+      (void)hipFree(u_dev);
+      (void)hipFree(w_dev);
+      return status;
+    }
+  MGX_HIP(hipStreamSynchronize(op->ctx->stream)); // a kernel in flight may read the geometry this call replaces
+  (void)hipFree(op->unit_q);
+  (void)hipFree(op->jxw_q);
+  op->unit_q      = u_dev;
+  op->jxw_q       = w_dev;
+  op->coef_update = true;
   return MGX_OK;
 }
 
@@ -2137,7 +2200,8 @@ static int require_coefficient_update(mgx_operator_t op, int law, const char *wh
   MGX_REQUIRE(law == MGX_LAW_UNIT || law == MGX_LAW_MINIMAL_SURFACE, w + ": unknown law");
   if (op->ctx->has_comm || op->plan)
     return fail(MGX_ERR_UNSUPPORTED, w + ": not on a decomposed mesh (single rank only)");
-  MGX_REQUIRE(op->coef_update, w + ": call mgx_operator_enable_coefficient_update first (affine geometry of the level)");
+  MGX_REQUIRE(op->coef_update, w + ": call mgx_operator_enable_coefficient_update (affine geometry of the level) or "
+                                   "mgx_operator_enable_coefficient_update_q (curved cells) first");
   MGX_REQUIRE(op->d.idx27_plain, w + ": the operator was created without idx27_plain (the state is read with its boundary values)");
   return MGX_OK;
 }
@@ -2147,7 +2211,7 @@ int mgx_evaluate_coefficient(mgx_operator_t op, int law, const void *state)
   MGX_REQUIRE(op && state, "mgx_evaluate_coefficient: null argument");
   MGX_TRY(require_coefficient_update(op, law, "mgx_evaluate_coefficient"));
   launch_evaluate_coefficient(op->ctx->stream, op->d, op->d.coef_q, op->d.number, law == MGX_LAW_MINIMAL_SURFACE, op->metric,
-                              op->det_jacobian, nullptr, state);
+                              op->det_jacobian, op->unit_q, op->jxw_q, state);
   MGX_HIP(hipGetLastError());
   op->has_diag = false; // the inverse diagonal belongs to the previous coefficient
   return MGX_OK;
@@ -2173,11 +2237,11 @@ int mgx_compute_nonlinear_residual(mgx_operator_t op, int law, void *dst, const 
   const bool  ms = law == MGX_LAW_MINIMAL_SURFACE;
   // atomic-free assembly as in mgx_compute_residual: colour by colour where the level has cell colours, else ordered
   if (op->d.asm_start)
-    launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, dst, state);
+    launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state);
   else if (op->d.cell_order)
     {
       MGX_HIP(hipMemsetAsync(dst, 0, number_size(op->d.number) * op->d.n_dofs, s));
-      launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, dst, state, op->d.cell_order, op->d.cell_colour_start,
+      launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state, op->d.cell_order, op->d.cell_colour_start,
                               op->d.n_cell_colours);
     }
   else
@@ -4260,7 +4324,13 @@ int mgx_solver_update_coefficient(mgx_solver_t S, int law, const double *state_f
   for (int l = 0; l < nl; ++l) // everything that can be refused is refused before the first level changes
     {
       MGX_TRY(require_coefficient_update(S->matrix_dp[l], law, "mgx_solver_update_coefficient"));
-      MGX_TRY(require_coefficient_update(S->matrix[l], law, "mgx_solver_update_coefficient"));
+      // curved cells: a V-cycle operator of another precision that was told no geometry of its own is written below
+      // with the tables, state and geometry of matrix_dp[l]; only its coef_q is needed
+      const bool written_from_dp = S->matrix[l] != S->matrix_dp[l] && S->matrix_dp[l]->unit_q && !S->matrix[l]->coef_update;
+      if (!written_from_dp)
+        MGX_TRY(require_coefficient_update(S->matrix[l], law, "mgx_solver_update_coefficient"));
+      else if (!S->matrix[l]->d.coef_q)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_solver_update_coefficient: a V-cycle operator has no per-point coefficient");
     }
   hipStream_t s = S->ctx->stream;
   if (S->nl_state.empty())
@@ -4289,7 +4359,7 @@ int mgx_solver_update_coefficient(mgx_solver_t S, int law, const double *state_f
           mgx_operator_t A = S->matrix_dp[l], V = S->matrix[l];
           MGX_REQUIRE(V->d.n_cells == A->d.n_cells && V->d.p == A->d.p, "mgx_solver_update_coefficient: level operators differ");
           launch_evaluate_coefficient(s, A->d, V->d.coef_q, V->d.number, law == MGX_LAW_MINIMAL_SURFACE, A->metric,
-                                      A->det_jacobian, nullptr, state);
+                                      A->det_jacobian, A->unit_q, A->jxw_q, state);
           MGX_HIP(hipGetLastError());
           V->has_diag = false;
         }

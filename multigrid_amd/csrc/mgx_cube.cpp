@@ -626,6 +626,27 @@ namespace
   // evaluate_coefficient, general branch (laplace_operator.h:388-430) for a mapped mesh: the cell
   // geometry is the degree-p interpolant of the map at the GLL support points (MappingQ of
   // multigrid_solver.h:139); per quadrature point JxW = det J w_q and coef = a(x_q) JxW J^-1 J^-T
+  // support points of a cell of a box mesh: the map at the GLL points of the reference box, nodes[3][(p+1)^3]
+  void box_cell_nodes(const mgx_cube_s &C, const Level &L, uint32_t c, double *nodes)
+  {
+    const int    n = C.p + 1, n3 = n * n * n;
+    const Basis &B = C.basis;
+    const double X0[3] = {C.origin + L.h * (L.off[0] + L.coords[3 * (size_t)c]),
+                          C.origin + L.h * (L.off[1] + L.coords[3 * (size_t)c + 1]),
+                          C.origin + L.h * (L.off[2] + L.coords[3 * (size_t)c + 2])};
+    for (int k = 0, i3 = 0; k < n; ++k)
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i, ++i3)
+          {
+            const double Xr[3] = {X0[0] + L.h * B.gll[i], X0[1] + L.h * B.gll[j], X0[2] + L.h * B.gll[k]};
+            double       xp[3];
+            C.map(Xr, xp);
+            nodes[i3] = xp[0];
+            nodes[n3 + i3] = xp[1];
+            nodes[2 * n3 + i3] = xp[2];
+          }
+  }
+
   void build_geometry(const mgx_cube_s &C, Level &L)
   {
     const int    p = C.p, n = p + 1, n3 = n * n * n;
@@ -640,23 +661,10 @@ namespace
 #pragma omp for schedule(static)
       for (uint32_t c = 0; c < L.n_cells; ++c)
         {
-          const double X0[3] = {C.origin + L.h * (L.off[0] + L.coords[3 * (size_t)c]),
-                                C.origin + L.h * (L.off[1] + L.coords[3 * (size_t)c + 1]),
-                                C.origin + L.h * (L.off[2] + L.coords[3 * (size_t)c + 2])};
           if (C.geometry == MGX_CUBE_GEOMETRY_HYPER_SHELL)
             shell_cell_nodes(C, L, c, nodes);
           else
-          for (int k = 0, i3 = 0; k < n; ++k)
-            for (int j = 0; j < n; ++j)
-              for (int i = 0; i < n; ++i, ++i3)
-                {
-                  const double Xr[3] = {X0[0] + L.h * B.gll[i], X0[1] + L.h * B.gll[j], X0[2] + L.h * B.gll[k]};
-                  double       xp[3];
-                  C.map(Xr, xp);
-                  nodes[i3] = xp[0];
-                  nodes[n3 + i3] = xp[1];
-                  nodes[2 * n3 + i3] = xp[2];
-                }
+            box_cell_nodes(C, L, c, nodes);
           for (int a = 0; a < 3; ++a)
             {
               apply_1d(n, 0, B.S, false, nodes + a * n3, val, false);
@@ -1073,13 +1081,16 @@ int mgx_cube_cell_nodes(mgx_cube_t c, int l, double *out)
 {
   if (!c || !out || l < 0 || l >= (int)c->levels.size())
     return MGX_ERR_INVALID_ARGUMENT;
-  if (c->geometry != MGX_CUBE_GEOMETRY_HYPER_SHELL)
-    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_cube_cell_nodes: multi-block meshes only");
   const Level &L  = c->levels[l];
   const size_t n3 = (size_t)(c->p + 1) * (c->p + 1) * (c->p + 1);
 #pragma omp parallel for schedule(static)
   for (uint32_t cell = 0; cell < L.n_cells; ++cell)
-    shell_cell_nodes(*c, L, cell, out + 3 * n3 * cell);
+    {
+      if (c->geometry == MGX_CUBE_GEOMETRY_HYPER_SHELL)
+        shell_cell_nodes(*c, L, cell, out + 3 * n3 * cell);
+      else
+        box_cell_nodes(*c, L, cell, out + 3 * n3 * cell);
+    }
   return MGX_OK;
 }
 
@@ -1155,6 +1166,11 @@ int mgx_cube_rhs_quadrature(mgx_cube_t c, int l, double *out)
 uint32_t        mgx_cube_bc_count(mgx_cube_t c, int l) { return (uint32_t)c->levels[l].bc_index.size(); }
 const uint32_t *mgx_cube_bc_index(mgx_cube_t c, int l) { return c->levels[l].bc_index.data(); }
 const double   *mgx_cube_bc_value(mgx_cube_t c, int l) { return c->levels[l].bc_value.data(); }
+
+const double *mgx_cube_jxw_q(mgx_cube_t c, int l)
+{
+  return (c && l >= 0 && l < (int)c->levels.size() && !c->levels[l].jxw.empty()) ? c->levels[l].jxw.data() : nullptr;
+}
 
 const double *mgx_cube_coef_q(mgx_cube_t c, int l)
 {
@@ -1366,8 +1382,18 @@ static int cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vnumber, i
   if (!ctx || !cube || !out || (vnumber != MGX_F32 && vnumber != MGX_F64))
     return MGX_ERR_INVALID_ARGUMENT;
   const int nl = (int)cube->levels.size();
-  if (general && (cube->size > 1 || !cube->levels[0].coef_q.empty()))
-    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_cube_solver_create_general: Cartesian cube / box meshes on one rank only");
+  // general hierarchy on a cube with a per-point tensor (mapped geometry or variable coefficient): the tensor has to be
+  // the unit law JxW_q J^-1 J^-T
+  const bool per_point = general && !cube->levels[0].coef_q.empty();
+  if (general && cube->size > 1)
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_cube_solver_create_general: one rank only");
+  if (per_point && cube->problem.id != MGX_CUBE_PROBLEM_CUBE)
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_cube_solver_create_general: the per-point tensor of this cube contains the "
+                                                  "variable coefficient a(x) of MGX_CUBE_PROBLEM_SHELL, it is not the unit law; "
+                                                  "create the cube with MGX_CUBE_PROBLEM_CUBE");
+  if (per_point && general->jacobian)
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_cube_solver_create_general: a jacobian on a mapped cube (the geometry of a "
+                                                  "mapped cube is the per-point one of its own map; jacobian must be NULL)");
   std::memset(out, 0, sizeof(*out));
   out->n_levels    = nl;
   out->matrix      = new mgx_operator_t[nl]();
@@ -1382,7 +1408,12 @@ static int cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vnumber, i
       // general branch on the Cartesian mesh: the unit-law tensor JxW_q M (or the caller's) as merged coefficient
       std::vector<double> unit;
       double              metric[6] = {0, 0, 0, 0, 0, 0}, det = 0;
-      if (general)
+      if (per_point) // the provider's JxW_q J^-1 J^-T (mgx_cube_operator_desc set it), or the caller's tensor
+        {
+          if (general->coef_q && general->coef_q[l])
+            d.coef_q = general->coef_q[l];
+        }
+      else if (general)
         {
           status = mgx_cube_affine_metric(cube, l, general->jacobian, metric, &det);
           if (status != MGX_OK)
@@ -1426,9 +1457,13 @@ static int cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vnumber, i
           ex.plan_id = 2 * l + 1;
           status     = mgx_operator_create(ctx, &d, &out->matrix[l]);
         }
-      if (general && status == MGX_OK)
+      // per_point cells: the geometry is kept once, in fp64 with matrix_dp[l]; mgx_solver_update_coefficient writes the
+      // tensor of an fp32 V-cycle operator from it
+      if (per_point && status == MGX_OK)
+        status = mgx_operator_enable_coefficient_update_q(out->matrix_dp[l], cube->levels[l].coef_q.data(), cube->levels[l].jxw.data());
+      if (general && !per_point && status == MGX_OK)
         status = mgx_operator_enable_coefficient_update(out->matrix_dp[l], metric, det);
-      if (general && status == MGX_OK && out->matrix[l] != out->matrix_dp[l])
+      if (general && !per_point && status == MGX_OK && out->matrix[l] != out->matrix_dp[l])
         status = mgx_operator_enable_coefficient_update(out->matrix[l], metric, det);
     }
   for (int l = 1; l < nl && status == MGX_OK; ++l)

@@ -283,18 +283,21 @@ namespace mgx
   // M = J^-1 J^-T [xx,yy,zz,xy,xz,yz] and det J: dst = - sum over the cells of grad phi_i . a JxW M grad u, a = 1 or
   // 1 / sqrt(1 + |grad u|^2); src through idx27_plain, dst through idx27.  n_lists > 0: launches over cell lists that share
   // no DoF (dst zeroed by the caller); n_lists == 0: the operator's ordered assembly (required then, dst written)
+  // unit_q / jxw_q (device, number type of op; nullptr: affine cells): per-point geometry of curved cells as in
+  // launch_evaluate_coefficient -- the flux of a point is a U g, a = 1 or 1 / sqrt(1 + g . U g / JxW_q)
   void launch_cell_nl_residual(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,
-                               void *dst, const void *src, const uint32_t *lists = nullptr, const uint32_t *list_start = nullptr,
-                               int n_lists = 0);
+                               const void *unit_q, const void *jxw_q, void *dst, const void *src, const uint32_t *lists = nullptr,
+                               const uint32_t *list_start = nullptr, int n_lists = 0);
   // ---- solution-dependent coefficients (mgx_nonlinear.hip) ----
   // MinimalSurfaceOperator::evaluate_coefficient (minimal_surface/program.cc:120-165) on affine cells: op.coef_q =
   // JxW_q M (first_time) or JxW_q (M - (M g)(M g)^T / (1 + s)) / sqrt(1 + s), s = g^T M g, g the reference-space
   // gradient of `state` (operator's number type, read through idx27_plain) at the quadrature points.
   // op: index table, 1D tables and number type of the state and of the arithmetic; coef_q / coef_number: the tensor
   // array written and its number type (that of op, or fp32 from an fp64 op: the rounded fp64 tensor).
-  // metric_q: reserved for a per-point metric (curved cells); must be nullptr.
+  // unit_q / jxw_q: per-point geometry of curved cells, device [n_cells][6][n^3] = JxW_q J^-1 J^-T and [n_cells][n^3] = JxW_q
+  // in the number type of op (metric and det are not read then); nullptr: affine cells.
   void launch_evaluate_coefficient(hipStream_t s, const OperatorData &op, void *coef_q, int coef_number, bool minimal_surface,
-                                   const double *metric, double det, const void *metric_q, const void *state);
+                                   const double *metric, double det, const void *unit_q, const void *jxw_q, const void *state);
   // state interpolation to the coarser level (minimal_surface/program.cc:425-457): every coarse DoF = the polynomial of
   // the child that contains the coarse node, evaluated there.  r1d: device [(2p+1)(p+1)], r1d[a (p+1) + i] = weight of
   // fine patch point a for coarse node i; own_c: device [n_coarse_cells], bit e set iff the cell is the first (in cell

@@ -243,13 +243,15 @@ namespace mgx
   // MINSURF (with RESID, not PERQ; MinimalSurfaceOperator::compute_residual, minimal_surface/program.cc:169-197): affine
   // cells with c0..c5 = M = J^-1 J^-T and det = det J; the flux of a point is M g w_q det J / sqrt(1 + |grad u|^2),
   // |grad u|^2 = g^T M g of the reference-space gradient g (:187-192).
+  // MINSURF with PERQ (curved cells): coef_q = U = JxW_q J^-1 J^-T and jxw_q = JxW_q of
+  // every point; the flux is U g / sqrt(1 + g . U g / JxW_q).
   template <int P, typename T, bool PERQ, bool RESID = false, bool MINSURF = false>
   __global__ void __launch_bounds__((Cfg<P, MGX_GENERAL_WG_THREADS>::THREADS))
     cell_loop_general_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *__restrict__ idx27,
                              uint32_t n_cells, const Basis1D<T> *__restrict__ B, const T *__restrict__ coef_q, T c0,
                              T c1, T c2, T c3, T c4, T c5, const uint32_t *__restrict__ cell_list, T *__restrict__ scratch,
                              const uint32_t *__restrict__ idx_gather = nullptr, const T *__restrict__ rhs_q = nullptr,
-                             T det = T(0))
+                             T det = T(0), const T *__restrict__ jxw_q = nullptr)
   {
     using C           = Cfg<P, MGX_GENERAL_WG_THREADS>;
     constexpr int N   = C::N;
@@ -354,6 +356,16 @@ namespace mgx
                 t0 = c0 * w, t1 = c1 * w, t2 = c2 * w, t3 = c3 * w, t4 = c4 * w, t5 = c5 * w;
               }
             const T gx = Xc[zl + k * PL], gy = Yc[zl + k * PL], g = gz[k];
+            if (MINSURF && PERQ)
+              {
+                const T fx = t0 * gx + t3 * gy + t4 * g, fy = t3 * gx + t1 * gy + t5 * g, fz = t4 * gx + t5 * gy + t2 * g;
+                const T w   = jxw_q[(size_t)cell * N3 + (size_t)((k * N + b) * N + a)];
+                const T fac = T(1) / sqrt(T(1) + (gx * fx + gy * fy + g * fz) / w);
+                Xc[zl + k * PL] = fac * fx;
+                Yc[zl + k * PL] = fac * fy;
+                gz[k]           = fac * fz;
+                continue;
+              }
             if (MINSURF)
               {
                 const T s = gx * (c0 * gx + c3 * gy + c4 * g) + gy * (c3 * gx + c1 * gy + c5 * g) +
@@ -1366,7 +1378,8 @@ namespace mgx
   // passes cell lists or the operator has the ordered-assembly tables)
   template <int P, typename T>
   static void cell_nl_residual_t(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *M, double det,
-                                 void *dst, const void *src, const uint32_t *lists, const uint32_t *list_start, int n_lists)
+                                 const void *unit_q, const void *jxw_q, void *dst, const void *src, const uint32_t *lists,
+                                 const uint32_t *list_start, int n_lists)
   {
     using C            = Cfg<P, MGX_GENERAL_WG_THREADS>;
     T        *scratch  = n_lists == 0 ? (T *)op.cell_scratch : nullptr;
@@ -1378,7 +1391,15 @@ namespace mgx
         if (count == 0)
           continue;
         const uint32_t nb = (count + C::CPB - 1) / C::CPB;
-        if (minimal_surface)
+        if (unit_q && minimal_surface) // curved cells
+          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, true, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst,
+                             (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)unit_q, (T)0, (T)0, (T)0, (T)0,
+                             (T)0, (T)0, list, scratch, op.idx27_plain, (const T *)nullptr, (T)0, (const T *)jxw_q);
+        else if (unit_q) // ... unit law: the per-point residual form with coef_q = U
+          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst, (const T *)src,
+                             op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)unit_q, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0,
+                             list, scratch, op.idx27_plain, (const T *)nullptr);
+        else if (minimal_surface)
           hipLaunchKernelGGL((cell_loop_general_kernel<P, T, false, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst,
                              (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)nullptr, (T)M[0], (T)M[1],
                              (T)M[2], (T)M[3], (T)M[4], (T)M[5], list, scratch, op.idx27_plain, (const T *)nullptr, (T)det);
@@ -1393,15 +1414,16 @@ namespace mgx
   }
 
   void launch_cell_nl_residual(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,
-                               void *dst, const void *src, const uint32_t *lists, const uint32_t *list_start, int n_lists)
+                               const void *unit_q, const void *jxw_q, void *dst, const void *src, const uint32_t *lists,
+                               const uint32_t *list_start, int n_lists)
   {
     if (op.number == 1)
       {
-        MGX_DISPATCH_P(op.p, cell_nl_residual_t<P, double>(s, op, minimal_surface, metric, det, dst, src, lists, list_start, n_lists));
+        MGX_DISPATCH_P(op.p, cell_nl_residual_t<P, double>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists, list_start, n_lists));
       }
     else
       {
-        MGX_DISPATCH_P(op.p, cell_nl_residual_t<P, float>(s, op, minimal_surface, metric, det, dst, src, lists, list_start, n_lists));
+        MGX_DISPATCH_P(op.p, cell_nl_residual_t<P, float>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists, list_start, n_lists));
       }
   }
 

@@ -1,4 +1,4 @@
-// mgx_nonlinear.hip -- solution-dependent coefficients of the general tensor branch on affine cells
+// mgx_nonlinear.hip -- solution-dependent coefficients of the general tensor branch
 // (MinimalSurfaceOperator and LaplaceProblem::solve of minimal_surface/program.cc):
 //   evaluate_coefficient_kernel   :120-165  merged_coefficient from the gradient of a state vector
 //   interpolate_to_coarse_kernel  :425-457  the state on the next coarser level
@@ -9,6 +9,7 @@
 //   first_time:  coef_q = JxW_q M
 //   otherwise:   coef_q = JxW_q (M - v v^T / (1 + s)) / sqrt(1 + s)
 // which is J^-1 (I - G G^T / (1 + |G|^2)) / sqrt(1 + |G|^2) J^-T JxW of :133-155 with G = J^-T g.
+// Curved cells: JxW_q M and JxW_q of every point instead (evaluate_coefficient_kernel, PERQ).
 #include "mgx_cell_device.hpp"
 #include "mgx_internal.hpp"
 
@@ -43,10 +44,16 @@ namespace mgx
   // T: number type of the state, the 1D tables and the arithmetic; TO: number type of coef_q (TO = float with
   // T = double: the fp32 operator of a level receives the rounded fp64 tensor, mgx_solver_update_coefficient).
   // ------------------------------------------------------------------------------------------
-  template <int P, typename T, typename TO, bool MINSURF>
+  // PERQ: per-point geometry of curved cells instead of m0 .. m5 and det -- unit_q[cell][6][n^3] = U = JxW_q J^-1 J^-T
+  // and jxw_q[cell][n^3] = w = JxW_q in the number type T.  The thread reads the seven values of a point of its z-line
+  // where it needs them (lane (a, b) at offset b n + a of plane k: consecutive lanes on consecutive addresses, as the
+  // stores are), and with u = U g, s = g . u / w:  coef_q = U (first_time) or (U - u u^T / (w (1 + s))) / sqrt(1 + s),
+  // the law above with M = U / w.
+  template <int P, typename T, typename TO, bool MINSURF, bool PERQ = false>
   __global__ void __launch_bounds__(Cfg<P>::THREADS)
     evaluate_coefficient_kernel(TO *__restrict__ coef_q, const T *__restrict__ state, const uint32_t *__restrict__ idx_plain,
-                                uint32_t n_cells, const Basis1D<T> *__restrict__ B, T m0, T m1, T m2, T m3, T m4, T m5, T det)
+                                uint32_t n_cells, const Basis1D<T> *__restrict__ B, T m0, T m1, T m2, T m3, T m4, T m5, T det,
+                                const T *__restrict__ unit_q = nullptr, const T *__restrict__ jxw_q = nullptr)
   {
     using C          = Cfg<P>;
     constexpr int N  = C::N;
@@ -135,13 +142,32 @@ namespace mgx
     const int sp    = b * N + a;
     if (active)
       {
-        const T wab = B->w[a] * B->w[b];
+        const T  wab = PERQ ? T(0) : B->w[a] * B->w[b];
+        const T *uq  = PERQ ? unit_q + (size_t)cell * 6 * N3 + (size_t)sp : nullptr;
+        const T *wq  = PERQ ? jxw_q + (size_t)cell * N3 + (size_t)sp : nullptr;
 #pragma unroll
         for (int k = 0; k < N; ++k)
           {
             const T jxw = wab * B->w[k] * det;
             T       c0, c1, c2, c3, c4, c5;
-            if (MINSURF) // :133-139
+            if (PERQ)
+              {
+                const T *up = uq + k * N * N;
+                c0 = up[0], c1 = up[N3], c2 = up[2 * N3], c3 = up[3 * N3], c4 = up[4 * N3], c5 = up[5 * N3];
+                if (MINSURF)
+                  {
+                    const T w  = wq[k * N * N];
+                    const T u0 = c0 * gx[k] + c3 * gy[k] + c4 * gz[k];
+                    const T u1 = c3 * gx[k] + c1 * gy[k] + c5 * gz[k];
+                    const T u2 = c4 * gx[k] + c5 * gy[k] + c2 * gz[k];
+                    const T d  = T(1) + (gx[k] * u0 + gy[k] * u1 + gz[k] * u2) / w;
+                    const T f  = T(1) / sqrt(d);
+                    const T wd = w * d;
+                    c0 = f * (c0 - u0 * u0 / wd), c1 = f * (c1 - u1 * u1 / wd), c2 = f * (c2 - u2 * u2 / wd);
+                    c3 = f * (c3 - u0 * u1 / wd), c4 = f * (c4 - u0 * u2 / wd), c5 = f * (c5 - u1 * u2 / wd);
+                  }
+              }
+            else if (MINSURF) // :133-139
               {
                 const T v0 = m0 * gx[k] + m3 * gy[k] + m4 * gz[k];
                 const T v1 = m3 * gx[k] + m1 * gy[k] + m5 * gz[k];
@@ -319,11 +345,22 @@ namespace mgx
 
   template <int P, typename T, typename TO>
   static void evaluate_coefficient_t(hipStream_t s, const OperatorData &op, void *coef_q, bool minimal_surface, const double *M,
-                                     double det, const void *state)
+                                     double det, const void *unit_q, const void *jxw_q, const void *state)
   {
     using C           = Cfg<P>;
     const uint32_t nb = (op.n_cells + C::CPB - 1) / C::CPB;
-    if (minimal_surface)
+    if (unit_q) // curved cells
+      {
+        if (minimal_surface)
+          hipLaunchKernelGGL((evaluate_coefficient_kernel<P, T, TO, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (TO *)coef_q,
+                             (const T *)state, op.idx27_plain, op.n_cells, (const Basis1D<T> *)op.basis, (T)0, (T)0, (T)0, (T)0, (T)0,
+                             (T)0, (T)0, (const T *)unit_q, (const T *)jxw_q);
+        else
+          hipLaunchKernelGGL((evaluate_coefficient_kernel<P, T, TO, false, true>), dim3(nb), dim3(C::THREADS), 0, s, (TO *)coef_q,
+                             (const T *)state, op.idx27_plain, op.n_cells, (const Basis1D<T> *)op.basis, (T)0, (T)0, (T)0, (T)0, (T)0,
+                             (T)0, (T)0, (const T *)unit_q, (const T *)jxw_q);
+      }
+    else if (minimal_surface)
       hipLaunchKernelGGL((evaluate_coefficient_kernel<P, T, TO, true>), dim3(nb), dim3(C::THREADS), 0, s, (TO *)coef_q,
                          (const T *)state, op.idx27_plain, op.n_cells, (const Basis1D<T> *)op.basis, (T)M[0], (T)M[1], (T)M[2],
                          (T)M[3], (T)M[4], (T)M[5], (T)det);
@@ -334,20 +371,19 @@ namespace mgx
   }
 
   void launch_evaluate_coefficient(hipStream_t s, const OperatorData &op, void *coef_q, int coef_number, bool minimal_surface,
-                                   const double *metric, double det, const void *metric_q, const void *state)
+                                   const double *metric, double det, const void *unit_q, const void *jxw_q, const void *state)
   {
-    (void)metric_q; // per-point geometry: not implemented, refused by the caller
     if (op.number == 1 && coef_number == 1)
       {
-        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, double, double>(s, op, coef_q, minimal_surface, metric, det, state));
+        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, double, double>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state));
       }
     else if (op.number == 1)
       {
-        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, double, float>(s, op, coef_q, minimal_surface, metric, det, state));
+        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, double, float>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state));
       }
     else // (fp32 tables: fp32 tensor)
       {
-        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, float, float>(s, op, coef_q, minimal_surface, metric, det, state));
+        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, float, float>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state));
       }
   }
 

@@ -5,7 +5,11 @@ the 2D one), Newton's method with V-cycle-preconditioned CG at ReductionControl(
 step-halving line search (:414-573), at most 100 steps or until the residual norm is below --tolerance (:656-662).
 Prints the reference's lines: "Residual norm: ... in ... steps to ...", "Computing times: nl iterations: ...".
 
-Usage: python tools/minimal_surface.py [degree] [n_refine] [--amplitude A] [--vcycle f32|f64] [--tolerance T]"""
+--geometry: the same on a mapped mesh with curved cells (per-point geometry): the sheared box, one equiangular sector of
+the shell (a box of one coarse cell, n_refine times refined) or the whole hyper_shell(0, 0.5, 1, 6 | 12).
+
+Usage: python tools/minimal_surface.py [degree] [n_refine] [--amplitude A] [--vcycle f32|f64] [--tolerance T]
+                                       [--geometry cube|sheared|shell_sector|shell6|shell12]"""
 import argparse
 import os
 import sys
@@ -25,13 +29,23 @@ def main():
     ap.add_argument("--vcycle", choices=["f32", "f64"], default="f32", help="number type of the V-cycle (level_number)")
     ap.add_argument("--tolerance", type=float, default=1e-12, help="stop when the residual norm is below (:660)")
     ap.add_argument("--max-steps", type=int, default=100, help="n_inner_iterations (:620)")
+    ap.add_argument("--geometry", choices=["cube", "sheared", "shell_sector", "shell6", "shell12"], default="cube")
     args = ap.parse_args()
 
     ctx = mg.Context(0)
-    cube = mg.Cube(args.degree, 1, args.n_refine)
+    if args.geometry == "cube":
+        cube = mg.Cube(args.degree, 1, args.n_refine)
+    elif args.geometry in ("sheared", "shell_sector"):
+        cube = mg.Cube(args.degree, n_refine=args.n_refine, box=(1, 1, 1), origin=-0.9, h0=1.9, geometry=args.geometry)
+    else:
+        cube = mg.Cube(args.degree, n_refine=args.n_refine, shell=int(args.geometry[5:]), problem="cube")
     print("Testing FE_Q<3>(%d)" % args.degree)
-    print("Number of degrees of freedom: %d (%d^3 cells, %d levels)"
-          % (cube.n_dofs(cube.max_level), cube.cells_per_dim(cube.max_level), cube.n_levels), flush=True)
+    if args.geometry == "cube":
+        print("Number of degrees of freedom: %d (%d^3 cells, %d levels)"
+              % (cube.n_dofs(cube.max_level), cube.cells_per_dim(cube.max_level), cube.n_levels), flush=True)
+    else:
+        print("Number of degrees of freedom: %d (%s, %d cells, %d levels)"
+              % (cube.n_dofs(cube.max_level), args.geometry, cube.n_cells(cube.max_level), cube.n_levels), flush=True)
     t0 = time.perf_counter()
     amplitude = args.amplitude
     problem = mg.MinimalSurfaceProblem(ctx, cube, lambda x: amplitude * np.sin(2 * np.pi * (x[:, 0] + x[:, 1])),

@@ -9,7 +9,13 @@
   update   one whole MultigridSolver.update_coefficient of a hierarchy, against the route without it: download the state,
            evaluate the tensors of every level in numpy, create operators / transfers / solver anew through desc.coef_q
 
+  mapped   the per-point kernels of curved cells (mgx_operator_enable_coefficient_update_q) on a shell_sector box of
+           2^N_REFINE cells per direction NEXT TO the affine kernels on the Cartesian cube of the same size, alternating
+           in one run: evaluation (both laws) and nonlinear residual.  Byte model of an evaluation: the affine one stores
+           6 values per point, the per-point one loads 7 and stores 6 (+ one gathered state value per point each)
+
 Usage: python tools/minimal_surface_profile.py kernel DEGREE N_REFINE [--number f64|f32]
+       python tools/minimal_surface_profile.py mapped DEGREE N_REFINE [--number f64|f32]
        python tools/minimal_surface_profile.py update DEGREE N_REFINE [--vcycle f32|f64] [--no-host]"""
 import argparse
 import os
@@ -72,6 +78,47 @@ def kernel(args):
     print("%-38s %8.1f us (min %.1f max %.1f)" % ("nonlinear residual minimal_surface", t.mean() * 1e6, t.min() * 1e6, t.max() * 1e6))
 
 
+def mapped(args):
+    number, dt, size = (mg.F64, np.float64, 8) if args.number == "f64" else (mg.F32, np.float32, 4)
+    ctx = mg.Context(0)
+    p, n3 = args.degree, (args.degree + 1) ** 3
+    flat = mg.Cube(p, 1, args.n_refine)
+    curved = mg.Cube(p, n_refine=args.n_refine, box=(1, 1, 1), origin=-0.9, h0=1.9, geometry="shell_sector")
+    l = flat.max_level
+    assert curved.n_cells(l) == flat.n_cells(l) and curved.n_dofs(l) == flat.n_dofs(l)
+    n_cells, n_dofs = flat.n_cells(l), flat.n_dofs(l)
+    a = mg.LaplaceOperator.from_cube(ctx, flat, l, number, coef_q=flat.unit_law_coefficient(l))
+    a.enable_coefficient_update(*flat.affine_metric(l))
+    q = mg.LaplaceOperator.from_cube(ctx, curved, l, number)
+    q.enable_coefficient_update_q(curved.coef_q(l), curved.jxw_q(l))
+    ua, uq = smooth_state(flat, l), smooth_state(curved, l)
+    sa, sq = ctx.vector(n_dofs, number, ua.astype(dt)), ctx.vector(n_dofs, number, uq.astype(dt))
+    da, dq = ctx.vector(n_dofs, number), ctx.vector(n_dofs, number)
+    print("FE_Q(%d), %d^3 cells, %d DoFs, %s; coef_q %.1f MB, per-point geometry %.1f MB"
+          % (p, flat.cells_per_dim(l), n_dofs, args.number, n_cells * 6 * n3 * size / 1e6, n_cells * 7 * n3 * size / 1e6))
+    rows = []
+    for name, law in (("evaluate unit", mg.LAW_UNIT), ("evaluate minimal_surface", mg.LAW_MINIMAL_SURFACE)):
+        rows.append((name, lambda law=law: a.evaluate_coefficient(law, sa), lambda law=law: q.evaluate_coefficient(law, sq),
+                     n_cells * 7 * n3 * size, n_cells * 14 * n3 * size))
+    # residual: the affine form streams no tensor; the per-point form loads 6 (unit law) / 7 values per point; both
+    # gather the state, store (p+1)^3 local values per cell and read them again in the ordered assembly
+    base = n_cells * 2 * n3 * size + 2 * size * n_dofs
+    rows.append(("residual unit", lambda: a.compute_nonlinear_residual(mg.LAW_UNIT, da, sa),
+                 lambda: q.compute_nonlinear_residual(mg.LAW_UNIT, dq, sq), base, base + n_cells * 6 * n3 * size))
+    rows.append(("residual minimal_surface", lambda: a.compute_nonlinear_residual(mg.LAW_MINIMAL_SURFACE, da, sa),
+                 lambda: q.compute_nonlinear_residual(mg.LAW_MINIMAL_SURFACE, dq, sq), base, base + n_cells * 7 * n3 * size))
+    print("%-26s %-42s %-42s ratio" % ("", "affine (one metric per level)", "per point (curved cells)"))
+    for name, fa, fq, ba, bq in rows:
+        ta, tq = [], []
+        for _ in range(2):  # alternate the two forms
+            ta.append(timed(ctx, fa, args.reps, args.groups))
+            tq.append(timed(ctx, fq, args.reps, args.groups))
+        ta, tq = np.concatenate(ta), np.concatenate(tq)
+        cell = lambda t, b: "%7.1f us (%.1f..%.1f) %.3f of peak" % (t.mean() * 1e6, t.min() * 1e6, t.max() * 1e6,
+                                                                   b / t.mean() / HBM_PEAK)
+        print("%-26s %-42s %-42s %.2f (bytes: %.2f)" % (name, cell(ta, ba), cell(tq, bq), tq.mean() / ta.mean(), bq / ba))
+
+
 def update(args):
     import nonlinear_reference as nr
     vnumber = mg.F32 if args.vcycle == "f32" else mg.F64
@@ -112,7 +159,7 @@ def update(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["kernel", "update"])
+    ap.add_argument("what", choices=["kernel", "mapped", "update"])
     ap.add_argument("degree", type=int)
     ap.add_argument("n_refine", type=int)
     ap.add_argument("--number", choices=["f64", "f32"], default="f64")
@@ -121,7 +168,7 @@ def main():
     ap.add_argument("--groups", type=int, default=5)
     ap.add_argument("--no-host", action="store_true")
     args = ap.parse_args()
-    (kernel if args.what == "kernel" else update)(args)
+    {"kernel": kernel, "mapped": mapped, "update": update}[args.what](args)
 
 
 if __name__ == "__main__":
