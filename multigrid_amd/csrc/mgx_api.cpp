@@ -454,7 +454,7 @@ namespace
   // sharers' entries, added in ascending rank order on every rank (bitwise identical copies).
   // post (fused exchange plans only; returns with *post_done = true): the Chebyshev update of the interface DoFs and
   // of the constrained rows inside the unpack launch
-  int exchange_add(mgx_operator_t op, void *vec, hipStream_t on = nullptr, const ChebList *post = nullptr,
+  int exchange_add(mgx_operator_t op, void *vec, hipStream_t on = nullptr, const BrickLaunch *post = nullptr,
                    bool *post_done = nullptr)
   {
     ExchangePlan *P = op->plan.get();
@@ -504,7 +504,7 @@ namespace
     if (P->fused && post && post_done)
       {
         launch_unpack_ordered_cheb(s, num, P->recv.data(), (int)P->rank.size(), vec, P->shared_dev, P->csr_start_dev,
-                                   P->csr_k_dev, P->csr_pos_dev, P->n_shared, *post);
+                                   P->csr_k_dev, P->csr_pos_dev, P->n_shared, *post, op->d.constrained, op->d.n_constrained);
         *post_done = true;
       }
     else if (P->fused)
@@ -533,6 +533,14 @@ namespace
     MGX_HIP(hipEventCreateWithFlags(&ctx->ev_iface, hipEventDisableTiming));
     MGX_HIP(hipEventCreateWithFlags(&ctx->ev_side, hipEventDisableTiming));
     return MGX_OK;
+  }
+
+  // compute units of the context's device: what the persistent grids are sized by
+  uint32_t context_cus(mgx_context_t ctx)
+  {
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    return (uint32_t)std::max(1, cus);
   }
 
   // HIP-event bracket around the cell loop of a profiled operator
@@ -589,7 +597,7 @@ namespace
   // post / post_done: the fix as the post-operation of the unpack launch where the exchange plan allows (exchange_add)
   template <typename Launch, typename Fix, typename Finish>
   int brick_loop_with_exchange(mgx_operator_t op, int form, void *carrier, Launch launch, Fix fix, bool free_schedule,
-                               Finish finish, const ChebList *post = nullptr, bool *post_done = nullptr)
+                               Finish finish, const BrickLaunch *post = nullptr, bool *post_done = nullptr)
   {
     mgx_context_t    ctx = op->ctx;
     hipStream_t      s   = ctx->stream;
@@ -655,24 +663,28 @@ namespace
     hipStream_t s = op->ctx->stream;
     if (op->d.bricks.available())
       {
-        const bool fr = op->d.bricks.fr.available();
+        BrickLaunch l; // dst = A src, the partial sums travel in dst itself
+        l.mode          = kPlain;
+        l.src           = src;
+        l.out           = dst;
+        l.carrier       = dst;
+        l.free_schedule = op->d.bricks.fr.available();
         return brick_loop_with_exchange(
-          op, 0, dst,
-          [&](hipStream_t st, int g0, int g1) {
-            launch_brick_loop(st, op->d, 0, src, nullptr, nullptr, dst, dst, 0., 0., nullptr, 0., nullptr, nullptr, g0, g1, fr);
-          },
-          [](hipStream_t) {}, fr,
-          [&](hipStream_t st, uint32_t first, uint32_t count) {
-            launch_surf_finish(st, op->d, 0, first, count, dst, src, dst, nullptr, nullptr, nullptr, 0., 0., 0.);
-          });
+          op, kPlain, dst, [&](hipStream_t st, int g0, int g1) { launch_brick_loop(st, op->d, l.groups(g0, g1)); },
+          [](hipStream_t) {}, l.free_schedule,
+          [&](hipStream_t st, uint32_t first, uint32_t count) { launch_surf_finish(st, op->d, l, first, count); });
       }
-    ProfileBracket pb(op, 0);
+    ProfileBracket pb(op, kPlain);
     if (op->d.gbricks.fr.available() && !op->plan)
       {
         // general operator on its brick schedule: one launch over the bricks, one over the DoFs on brick surfaces
+        BrickLaunch l;
+        l.mode    = kPlain;
+        l.src     = src;
+        l.out     = dst;
+        l.carrier = dst;
         launch_general_bricks(s, op->d, dst, src);
-        launch_surf_finish(s, op->d, 0, 0, op->d.gbricks.fr.n_surf_dofs, dst, src, dst, nullptr, nullptr, nullptr, 0., 0., 0.,
-                           nullptr, 0, &op->d.gbricks.fr);
+        launch_surf_finish(s, op->d, l, 0, op->d.gbricks.fr.n_surf_dofs, nullptr, 0, &op->d.gbricks.fr);
         return MGX_OK;
       }
     if (op->d.asm_start)
@@ -1353,6 +1365,7 @@ int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_op
   d.cells_form       = tun.cells_form;
   d.wide_max         = tun.wide_max;
   d.macro_wg_x16     = tun.macro_wg_x16;
+  d.n_cus            = context_cus(ctx);
   d.macro_v2         = !tun.no_macro_v2;
   for (int a = 0; a < n && d.separable; ++a)
     for (int bb = 0; bb < n; ++bb)
@@ -1953,19 +1966,20 @@ int mgx_vmult_residual(mgx_operator_t op, const void *rhs, const void *lhs, void
     {
       // zeroing (:617-623) and rhs - A lhs (:624-631) are fused into the brick loop; interface
       // DoFs hold partial sums of A lhs: complete them, then rhs - (.)
-      const bool fr = op->d.bricks.fr.available();
+      BrickLaunch l; // res = rhs - A lhs, the partial sums travel in res itself
+      l.mode          = kResidual;
+      l.src           = lhs;
+      l.rhs           = rhs;
+      l.out           = res;
+      l.carrier       = res;
+      l.free_schedule = op->d.bricks.fr.available();
       MGX_TRY(brick_loop_with_exchange(
-        op, 1, res,
-        [&](hipStream_t st, int g0, int g1) {
-          launch_brick_loop(st, op->d, 1, lhs, rhs, nullptr, res, res, 0., 0., nullptr, 0., nullptr, nullptr, g0, g1, fr);
-        },
+        op, kResidual, res, [&](hipStream_t st, int g0, int g1) { launch_brick_loop(st, op->d, l.groups(g0, g1)); },
         [&](hipStream_t st) {
           launch_list_residual(st, op->d.number, res, rhs, op->plan->shared_dev, op->plan->n_shared);
         },
-        fr,
-        [&](hipStream_t st, uint32_t first, uint32_t count) {
-          launch_surf_finish(st, op->d, 1, first, count, res, lhs, res, rhs, nullptr, nullptr, 0., 0., 0.);
-        }));
+        l.free_schedule,
+        [&](hipStream_t st, uint32_t first, uint32_t count) { launch_surf_finish(st, op->d, l, first, count); }));
     }
   else
     {
@@ -2008,7 +2022,7 @@ int mgx_vmult_with_cg_update(mgx_operator_t op, double alpha, double beta, const
         }
       uint32_t used = 0;
       {
-        ProfileBracket pb(op, 8);
+        ProfileBracket pb(op, kCgUpdate);
         fused = num == MGX_F64 ? launch_macro_cg_update_f64(s, op->d, alpha, beta, r, q, p, x, carrier, op->cg_partials,
                                                             kCapacity - 2048, &used)
                                : launch_macro_cg_update_f32(s, op->d, alpha, beta, r, q, p, x, carrier, op->cg_partials,
@@ -2497,7 +2511,7 @@ static bool cheb_in_assembly(mgx_operator_t op)
 static void cheb_assembly_iteration(mgx_smoother_t sm, void *x, const void *b, double f1, double f2, bool three_term)
 {
   mgx_operator_t op = sm->op;
-  ProfileBracket pb(op, three_term ? 2 : 3);
+  ProfileBracket pb(op, three_term ? kCheb : kChebFirst);
   const ChebPost post{sm->x_old, b, op->d.inv_diag, f1, f2, three_term};
   launch_cell_loop(op->ctx->stream, op->d, x, x, nullptr, op->d.n_dofs - op->d.n_constrained, &post);
 }
@@ -2521,7 +2535,7 @@ static int cheb_loop(mgx_smoother_t sm, void *x, const void *b)
           continue;
         }
       MGX_TRY(mgx_vmult(op, sm->tmp, x));
-      launch_cheb_update(s, op->d.number, 2, x, sm->x_old, b, sm->tmp, op->d.inv_diag, f1, f2, op->d.n_dofs);
+      launch_cheb_update(s, op->d.number, kUpdateThreeTerm, x, sm->x_old, b, sm->tmp, op->d.inv_diag, f1, f2, op->d.n_dofs);
     }
   MGX_HIP(hipGetLastError());
   return MGX_OK;
@@ -2530,42 +2544,49 @@ static int cheb_loop(mgx_smoother_t sm, void *x, const void *b)
 // One fused Chebyshev iteration on a brick-scheduled level (the counterpart of
 // LaplaceOperator::vmult(dst, src, before, after), laplace_operator.h:723-741, with
 // PreconditionChebyshev's update as the after-operation):
-//   out <- cur + f1 (cur - out) + f2 D^-1 (b - A cur);  mode 2 general, 3 without the f1 term,
-//   4 with out == 0 on entry.  sm->tmp carries the partial sums of brick-surface DoFs.
-static int cheb_fused_iteration(mgx_smoother_t sm, int mode, const void *cur, const void *old, void *out,
+//   out <- cur + f1 (cur - out) + f2 D^-1 (b - A cur);  kCheb general, kChebFirst without the f1 term,
+//   kChebZeroOld with out == 0 on entry.  sm->tmp carries the partial sums of brick-surface DoFs.
+static int cheb_fused_iteration(mgx_smoother_t sm, BrickMode mode, const void *cur, const void *old, void *out,
                                 const void *b, double f1, double f2, double f0 = 0., const void *coarse = nullptr,
                                 const uint32_t *coarse_blocks = nullptr, const TransferData *prolong_tr = nullptr)
 {
   mgx_operator_t op = sm->op;
   hipStream_t    s  = op->ctx->stream;
-  // the interface DoFs' partial sums of A cur sit in sm->tmp: complete them and apply the update there
-  const bool fr = op->d.bricks.fr.available() && mode >= 2 && mode <= 6;
+  BrickLaunch l;
+  l.mode          = mode;
+  l.src           = cur;
+  l.rhs           = b;
+  l.dinv          = op->d.inv_diag;
+  l.old           = old;
+  l.out           = out;
+  l.carrier       = sm->tmp;
+  l.f0            = f0;
+  l.f1            = f1;
+  l.f2            = f2;
+  l.coarse        = const_cast<void *>(coarse);
+  l.coarse_blocks = coarse_blocks;
+  l.free_schedule = op->d.bricks.fr.available() && on_free_schedule(mode);
   // (reduced-colour schedule on one rank: the update of the constrained rows rides on the finish kernel)
-  const bool folded = fr && !op->plan;
-  // decomposed: interface DoFs and constrained rows are updated by the unpack launch of the exchange
-  const ChebList post{mode, cur, b, op->d.inv_diag, old, out, f1, f2, f0, op->d.constrained, op->d.n_constrained};
-  bool           post_done = false;
+  const bool folded = l.free_schedule && !op->plan;
+  // the interface DoFs' partial sums of A cur sit in sm->tmp: complete them and apply the update there.  Decomposed:
+  // interface DoFs and constrained rows are updated by the unpack launch of the exchange where the plan allows (post)
+  bool post_done = false;
   MGX_TRY(brick_loop_with_exchange(
-    op, mode, sm->tmp,
-    [&](hipStream_t st, int g0, int g1) {
-      launch_brick_loop(st, op->d, mode, cur, b, op->d.inv_diag, out, sm->tmp, f1, f2, old, f0, const_cast<void *>(coarse),
-                        coarse_blocks, g0, g1, fr);
-    },
+    op, mode, sm->tmp, [&](hipStream_t st, int g0, int g1) { launch_brick_loop(st, op->d, l.groups(g0, g1)); },
     [&](hipStream_t st) {
-      if (mode == 9) // the shared DoFs start from x + P x_coarse as well (and store it: x_old of the next iteration)
+      if (mode == kChebFirstProlong) // the shared DoFs start from x + P x_coarse as well (and store it: x_old of the next iteration)
         launch_interface_prolong_cheb(st, op->d.number, *prolong_tr, op->plan->shared_dev, coarse, const_cast<void *>(cur), out, b,
                                       op->d.inv_diag, f2, sm->tmp);
       else
         launch_cheb_constrained(st, op->d.number, mode, cur, out, b, op->d.inv_diag, f1, f2, op->plan->shared_dev,
                                 op->plan->n_shared, sm->tmp, old, f0);
     },
-    fr,
+    l.free_schedule,
     [&](hipStream_t st, uint32_t first, uint32_t count) {
       // one rank: one call for the whole surface list, which takes the constrained rows along
-      launch_surf_finish(st, op->d, mode, first, count, sm->tmp, cur, out, b, op->d.inv_diag, old, f1, f2, f0,
-                         folded ? op->d.constrained : nullptr, folded ? op->d.n_constrained : 0u);
+      launch_surf_finish(st, op->d, l, first, count, folded ? op->d.constrained : nullptr, folded ? op->d.n_constrained : 0u);
     },
-    (op->plan && mode != 9 && !op->ctx->tun.exchange_unfused) ? &post : nullptr, &post_done));
+    (op->plan && mode != kChebFirstProlong && !op->ctx->tun.exchange_unfused) ? &l : nullptr, &post_done));
   if (!folded && !post_done)
     launch_cheb_constrained(s, op->d.number, mode, cur, out, b, op->d.inv_diag, f1, f2, op->d.constrained,
                             op->d.n_constrained, nullptr, old, f0);
@@ -2581,7 +2602,7 @@ static int cheb_fused_iteration(mgx_smoother_t sm, int mode, const void *cur, co
 // all pointers stay fixed from call to call (which lets the coarse part of the V-cycle be
 // replayed as a HIP graph).
 // prolong_coarse / prolong_blocks (step only): the coarse-grid correction P x_coarse is added to x on
-// the fly by the first iteration (mode 9) instead of by a prolongation kernel before the call
+// the fly by the first iteration (kChebFirstProlong) instead of by a prolongation kernel before the call
 static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_step, const void *prolong_coarse = nullptr,
                           const uint32_t *prolong_blocks = nullptr, const TransferData *prolong_tr = nullptr)
 {
@@ -2598,10 +2619,10 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
       else if (is_step)
         {
           MGX_TRY(mgx_vmult(op, sm->tmp, x));
-          launch_cheb_update(s, num, 1, x, sm->x_old, b, sm->tmp, op->d.inv_diag, 0., sm->first_factor(), n);
+          launch_cheb_update(s, num, kUpdateFirst, x, sm->x_old, b, sm->tmp, op->d.inv_diag, 0., sm->first_factor(), n);
         }
       else
-        launch_cheb_update(s, num, 0, x, sm->x_old, b, nullptr, op->d.inv_diag, 0., sm->first_factor(), n);
+        launch_cheb_update(s, num, kUpdateStart, x, sm->x_old, b, nullptr, op->d.inv_diag, 0., sm->first_factor(), n);
       return cheb_loop(sm, x, b);
     }
   const bool three_term = I.degree >= 2 && std::fabs(I.delta) >= 1e-40;
@@ -2610,7 +2631,7 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
   if (!is_step && n_loop >= 1 && op->d.separable && !op->ctx->tun.no_fused_init)
     {
       // Zero initial guess: x_1 = (1/theta) D^-1 b is not stored.  The first loop iteration
-      // evaluates it while gathering (mode 5), the second one again as its x_old (mode 6); from the
+      // evaluates it while gathering (kChebInit), the second one again as its x_old (kChebOldInit); from the
       // third on both operands are stored iterates.  Targets alternate so that the last is X.
       const double f0   = sm->first_factor();
       double       rhok = I.delta / I.theta;
@@ -2620,7 +2641,7 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
           double f1, f2;
           sm->next_factors(k, rhok, f1, f2);
           void *out = ((n_loop - 1 - k) % 2 == 0) ? X : Y;
-          MGX_TRY(cheb_fused_iteration(sm, k == 0 ? 5 : (k == 1 ? 6 : 2), cur, old, out, b, f1, f2, f0));
+          MGX_TRY(cheb_fused_iteration(sm, k == 0 ? kChebInit : (k == 1 ? kChebOldInit : kCheb), cur, old, out, b, f1, f2, f0));
           old = cur;
           cur = out;
         }
@@ -2637,7 +2658,7 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
           double f1, f2;
           sm->next_factors(k, rhok, f1, f2);
           void *out = (cur == X) ? Y : X;
-          MGX_TRY(cheb_fused_iteration(sm, k == 0 ? 4 : 2, cur, old, out, b, f1, f2)); // k = 0: x_0 = 0
+          MGX_TRY(cheb_fused_iteration(sm, k == 0 ? kChebZeroOld : kCheb, cur, old, out, b, f1, f2)); // k = 0: x_0 = 0
           old = cur;
           cur = out;
         }
@@ -2659,13 +2680,13 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
       else
         out = k == 1 ? Y : (k == 2 ? Z : (k == 3 ? X : ((cur == X) ? Y : X)));
       if (k == 1)
-        MGX_TRY(cheb_fused_iteration(sm, prolong_blocks ? 9 : 3, cur, nullptr, out, b, 0., sm->first_factor(), 0.,
+        MGX_TRY(cheb_fused_iteration(sm, prolong_blocks ? kChebFirstProlong : kChebFirst, cur, nullptr, out, b, 0., sm->first_factor(), 0.,
                                      prolong_coarse, prolong_blocks, prolong_tr));
       else
         {
           double f1, f2;
           sm->next_factors(k - 2, rhok, f1, f2);
-          MGX_TRY(cheb_fused_iteration(sm, 2, cur, old, out, b, f1, f2));
+          MGX_TRY(cheb_fused_iteration(sm, kCheb, cur, old, out, b, f1, f2));
         }
       old = cur;
       cur = out;
@@ -3057,9 +3078,7 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
           {
             MGX_HIP(hipMalloc((void **)&tr->d.patch, sizeof(uint32_t) * patch.size()));
             MGX_HIP(hipMemcpy(tr->d.patch, patch.data(), sizeof(uint32_t) * patch.size(), hipMemcpyHostToDevice));
-            int cus = 256;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, coarse->ctx->device);
-            tr->d.n_cus = (uint32_t)std::max(1, cus);
+            tr->d.n_cus = context_cus(coarse->ctx);
             // colouring of the coarse cells by index mod 8 (the parity colouring of a Morton-ordered
             // mesh): valid if no two cells of one colour share a mesh entity
             if (npar % 8 == 0 && !coarse->ctx->tun.restrict_atomic)
@@ -3143,7 +3162,7 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
                             hipMemcpyHostToDevice));
         }
     }
-  // Fused residual + restriction (mgx_brick.hip, mode 7): needs the fine level on the brick
+  // Fused residual + restriction (BrickMode kResidualRestrict): needs the fine level on the brick
   // schedule in its separable form, children in forest order (cell c is child c % 8 of parent
   // c / 8, so that a brick's cells are the children of PB^3 sibling parents) and a single rank.
   // (Degree 7 ran the separate kernels until the line products of the embedding took their even-odd form in round 4:
@@ -3845,16 +3864,22 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
           const TransferData &T = S->transfer[level]->d;
           // scratch form: the bricks store their restricted values block by block (one launch for the level), the
           // coarse defect is assembled from the blocks; otherwise they add into the zeroed coarse defect colour by
-          // colour.  (The form carries no partial sums: its `partial` argument names the scratch array.)
+          // colour
           void *scratch = (T.coarse_scratch && !A->d.cells_form) ? T.coarse_scratch : nullptr;
           if (!scratch)
             MGX_HIP(hipMemsetAsync(S->defect[level - 1], 0, number_size(S->vnumber) * nc, s)); // :667
           {
-            ProfileBracket pb(A, 7);
-            // (the cell-by-cell form of a cross-check build still hands partial sums over through t)
-            launch_brick_loop(s, A->d, 7, S->solution_update[level], S->defect[level], nullptr, S->t[level],
-                              scratch ? scratch : (A->d.cells_form ? S->t[level] : nullptr), 0., 0., nullptr, 0.,
-                              S->defect[level - 1], T.coarse_blocks);
+            ProfileBracket pb(A, kResidualRestrict);
+            BrickLaunch    l;
+            l.mode           = kResidualRestrict;
+            l.src            = S->solution_update[level];
+            l.rhs            = S->defect[level];
+            l.out            = S->t[level];
+            l.carrier        = A->d.cells_form ? S->t[level] : nullptr; // (only the cell-by-cell form of a cross-check build hands partial sums over)
+            l.coarse         = S->defect[level - 1];
+            l.coarse_blocks  = T.coarse_blocks;
+            l.coarse_scratch = scratch;
+            launch_brick_loop(s, A->d, l);
             if (scratch)
               launch_coarse_assemble(s, A->d.number, T, S->defect[level - 1]);
           }

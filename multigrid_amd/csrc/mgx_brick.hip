@@ -857,83 +857,39 @@ namespace mgx
   }
 
   template <typename T>
-  static void brick_dispatch(hipStream_t s, const OperatorData &op, int mode, const void *src, const void *a,
-                             const void *b, void *out, void *partial, double f1, double f2, const void *old, double f0,
-                             void *coarse, const uint32_t *coarse_blocks, int g0, int g1)
+  static bool brick_dispatch(hipStream_t s, const OperatorData &op, const BrickLaunch &l)
   {
-    BrickPost<T> post;
-    post.f0      = (T)f0;
-    post.coarse  = (T *)coarse;
-    post.coarse_blocks = coarse_blocks;
-    post.a       = (const T *)a;
-    post.b       = (const T *)b;
-    post.old     = (const T *)old;
-    post.out     = (T *)out;
-    post.partial = (T *)partial;
-    post.f1      = (T)f1;
-    post.f2      = (T)f2;
-#define MGX_BRICK_CASE(PP)                                                         \
-  case PP:                                                                         \
-    switch (mode)                                                                  \
-      {                                                                            \
-        case kPlain: brick_launch<PP, T, kPlain>(s, op, (const T *)src, post, g0, g1); break; \
-        case kResidual: brick_launch<PP, T, kResidual>(s, op, (const T *)src, post, g0, g1); break; \
-        case kCheb: brick_launch<PP, T, kCheb>(s, op, (const T *)src, post, g0, g1); break; \
-        case kChebFirst: brick_launch<PP, T, kChebFirst>(s, op, (const T *)src, post, g0, g1); break; \
-        case kChebInit: brick_launch<PP, T, kChebInit>(s, op, (const T *)src, post, g0, g1); break; \
-        case kChebOldInit: brick_launch<PP, T, kChebOldInit>(s, op, (const T *)src, post, g0, g1); break; \
-        case kResidualRestrict: brick_launch<PP, T, kResidualRestrict>(s, op, (const T *)src, post, g0, g1); break; \
-        default: brick_launch<PP, T, kChebZeroOld>(s, op, (const T *)src, post, g0, g1); break; \
-      }                                                                            \
-    break;
-    switch (op.p)
-      {
-        MGX_BRICK_CASE(1)
-        MGX_BRICK_CASE(2)
-        MGX_BRICK_CASE(3)
-        MGX_BRICK_CASE(4)
-        MGX_BRICK_CASE(5)
-        MGX_BRICK_CASE(6)
-        MGX_BRICK_CASE(7)
-        MGX_BRICK_CASE(8)
-        MGX_BRICK_CASE(9)
-        default: break;
-      }
-#undef MGX_BRICK_CASE
+    const BrickPost<T> post     = make_post<T>(l);
+    bool               launched = false;
+    dispatch_degree(op.p, [&](auto degree) {
+      constexpr int P = decltype(degree)::value;
+      launched = dispatch_mode<kPlain, kResidual, kCheb, kChebFirst, kChebZeroOld, kChebInit, kChebOldInit, kResidualRestrict>(
+        l.mode, [&](auto form) {
+          brick_launch<P, T, decltype(form)::value>(s, op, (const T *)l.src, post, l.group_begin, l.group_end);
+        });
+    });
+    return launched;
   }
 #endif // MGX_CELLS_FORM
 
-  void launch_brick_loop(hipStream_t s, const OperatorData &op, int mode, const void *src, const void *a,
-                         const void *b, void *out, void *partial, double f1, double f2, const void *old, double f0,
-                         void *coarse, const uint32_t *coarse_blocks, int g0, int g1, bool free_schedule)
+  void launch_brick_loop(hipStream_t s, const OperatorData &op, const BrickLaunch &launch)
   {
-    if (g1 < 0)
-      g1 = op.bricks.n_colours;
-    if (!old)
-      old = out;
-    if (!src)
-      src = (const void *)a; // kChebInit: never dereferenced, but keep the pointer valid
+    const BrickLaunch l = launch.resolved(op.bricks.n_colours);
     // separable operator: macro-element form (mgx_macro.hip); Tunables::cells_form keeps the
     // cell-by-cell form below (A/B measurements, and the reference point of the consistency tests)
     if (op.separable && op.bricks.item_map && !op.cells_form)
       {
-        const bool done = op.number == 1
-                            ? launch_macro_loop_f64(s, op, mode, src, a, b, out, partial, f1, f2, old, f0, coarse, coarse_blocks, g0, g1, free_schedule)
-                            : launch_macro_loop_f32(s, op, mode, src, a, b, out, partial, f1, f2, old, f0, coarse, coarse_blocks, g0, g1, free_schedule);
-        if (done)
+        if (op.number == 1 ? launch_macro_loop_f64(s, op, l) : launch_macro_loop_f32(s, op, l))
           return;
       }
     // (the caller asks for the reduced-colour schedules only where the macro-element kernel runs)
 #if MGX_CELLS_FORM
-    if (op.number == 1)
-      brick_dispatch<double>(s, op, mode, src, a, b, out, partial, f1, f2, old, f0, coarse, coarse_blocks, g0, g1);
-    else
-      brick_dispatch<float>(s, op, mode, src, a, b, out, partial, f1, f2, old, f0, coarse, coarse_blocks, g0, g1);
-#else
-    // unreachable: mgx_operator_create builds a brick schedule only for operators the macro-element
-    // kernel covers; fail loudly rather than return without having computed anything
-    fprintf(stderr, "mgx: brick loop requested for an operator the macro-element kernel does not cover (mode %d)\n", mode);
-    abort();
+    if (op.number == 1 ? brick_dispatch<double>(s, op, l) : brick_dispatch<float>(s, op, l))
+      return;
 #endif
+    // unreachable in the production library: mgx_operator_create builds a brick schedule only for operators the
+    // macro-element kernel covers; fail loudly rather than return without having computed anything
+    fprintf(stderr, "mgx: brick loop requested for an operator or a form no kernel covers (mode %d)\n", (int)l.mode);
+    abort();
   }
 } // namespace mgx

@@ -38,36 +38,7 @@ namespace mgx
     static constexpr int  CELL_LDS   = N * N * LN;
   };
 
-  // fused post-operations (what the reference passes as operation_after_loop)
-  enum BrickMode
-  {
-    kPlain    = 0, // out = A src                                   (vmult, laplace_operator.h:573)
-    kResidual = 1, // out = a - A src                               (vmult_residual, :605)
-    kCheb     = 2, // out = x + f1 (x - out) + f2 b (a - A x)       (PreconditionChebyshev update)
-    kChebFirst = 3, // out = x + f2 b (a - A x)                     (first step: no x_old term)
-    kChebZeroOld = 4, // out = x + f1 x + f2 b (a - A x)             (x_old known to be zero)
-    // start of PreconditionChebyshev::vmult (zero initial guess): the first iterate x_1 = f0 b a is
-    // never stored -- the first loop iteration computes it while gathering (kChebInit, x_old = 0),
-    // the second one recomputes it as its x_old (kChebOldInit); separable kernel only
-    kChebInit    = 5, // x := f0 b a ; out = x + f1 x + f2 b (a - A x)
-    kChebOldInit = 6, // out = x + f1 (x - f0 b a) + f2 b (a - A x)
-    // V-cycle: the residual a - A x is only needed restricted to the next coarser level
-    // (multigrid_solver.h:663-668).  Every brick restricts the residual values it completes (its
-    // LAST points, everything else masked to zero) with the transposed embedding and adds the
-    // (PB p + 1)^3 coarse values to the coarse vector; the residual itself is never stored.
-    kResidualRestrict = 7,
-    // fused PCG step (vmult_with_cg_update, laplace_operator.h:638-719; macro-element kernel only):
-    // the gather forms p_new = f2 p + q (f1 == 0: p_new = q); at completion x += f1 p_old,
-    // p = p_new, q = A p_new, and q.p, r.r, q.r, q.q are accumulated per workgroup
-    kCgUpdate = 8,
-    // first post-smoothing iteration of the V-cycle with the coarse-grid correction formed on the
-    // fly (multigrid_solver.h:674-678; macro-element kernel only): the gather adds the prolongated
-    // coarse values to x (prolong_brick), the iteration is kChebFirst on the corrected x, which is
-    // also written back at completion (it is x_old of the next iteration).  coarse / coarse_blocks
-    // as for kResidualRestrict.
-    kChebFirstProlong = 9
-  };
-
+  // (BrickMode, the fused post-operations: mgx_internal.hpp)
   template <typename T>
   struct BrickPost
   {
@@ -91,6 +62,25 @@ namespace mgx
     const uint32_t *surf_off;
     uint32_t        n_surf, priv_bytes;
   };
+
+  // the kernel argument of a launch; a pipeline that takes an operand from elsewhere overrides that field
+  template <typename T>
+  BrickPost<T> make_post(const BrickLaunch &l)
+  {
+    BrickPost<T> post{};
+    post.a              = (const T *)l.rhs;
+    post.b              = (const T *)l.dinv;
+    post.old            = (const T *)l.old;
+    post.out            = (T *)l.out;
+    post.partial        = (T *)l.carrier;
+    post.f1             = (T)l.f1;
+    post.f2             = (T)l.f2;
+    post.f0             = (T)l.f0;
+    post.coarse         = (T *)l.coarse;
+    post.coarse_blocks  = l.coarse_blocks;
+    post.coarse_scratch = (T *)l.coarse_scratch;
+    return post;
+  }
 
   // Entity table word: bits 0..29 first DoF of the entity, bit 30 FIRST, bit 31 LAST;
   // 0xFFFFFFFF = constrained / empty entity (the host refuses levels with >= 2^30 - 1 DoFs)

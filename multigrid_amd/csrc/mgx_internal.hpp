@@ -4,9 +4,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 struct mgx_context_s;
@@ -171,6 +173,7 @@ namespace mgx
     bool      cells_form    = false; // Tunables::cells_form of the context the operator was created on
     uint32_t  wide_max      = 1024;  // Tunables::wide_max
     uint32_t  macro_wg_x16  = 0;     // Tunables::macro_wg_x16
+    uint32_t  n_cus         = 256;   // compute units of the device of the operator's context
     bool      separable     = true; // Cartesian constant-coefficient fast path of the brick loop
     // inverse diagonal per brick item ((NB p + 1)^3 values in item order) if it is the same for
     // every brick (uniform mesh), else nullptr: the macro-element kernel then reads it from
@@ -191,7 +194,7 @@ namespace mgx
     // children patch: first fine DoF | log2(multiplicity) << 29 | owned-by-this-parent << 31;
     // nullptr if the fine level has 2^29 DoFs or more (first-version kernels are used then)
     uint32_t           *patch = nullptr;
-    // fused residual + restriction (mgx_brick.hip, mode 7): per fine brick, in the fine level's
+    // fused residual + restriction (BrickMode kResidualRestrict): per fine brick, in the fine level's
     // colour-sorted brick order, the first coarse DoF (constrained: invalid) of the (2 PB + 1)^3 mesh
     // entities of the PB^3 parents the brick's cells belong to (PB = 2 for p <= 4, 1 for p >= 5)
     uint32_t           *coarse_blocks = nullptr;
@@ -263,17 +266,128 @@ namespace mgx
   void launch_general_bricks(hipStream_t s, const OperatorData &op, void *dst, const void *src);
   // mode 0: dst = ordered sums of op.cell_scratch (tail as above), mode 1: dst += them
   void launch_assemble(hipStream_t s, const OperatorData &op, int mode, void *dst, const void *tail_src, uint32_t n_head);
-  // brick cell loop with fused post-operation (mgx_brick.hip); mode = BrickMode
-  //   0: out = A src          1: out = a - A src
-  //   2: out = src + f1 (src - out) + f2 b (a - A src)      3: same without the f1 term
-  // `partial` carries partial sums of brick-surface DoFs between the colour launches
-  //   old: previous iterate of mode 2 (nullptr: it is `out`, which is then read before written)
-  // group_begin / group_end: launch groups to run (default: all; the interface / interior halves of
-  // a split schedule are launched separately, BrickData::n_iface_groups)
-  void launch_brick_loop(hipStream_t s, const OperatorData &op, int mode, const void *src, const void *a,
-                         const void *b, void *out, void *partial, double f1, double f2, const void *old = nullptr,
-                         double f0 = 0., void *coarse = nullptr, const uint32_t *coarse_blocks = nullptr,
-                         int group_begin = 0, int group_end = -1, bool free_schedule = false);
+  // ---- brick loop (mgx_macro.hip, mgx_macro2.hip; cross-check builds: mgx_brick.hip) ----
+  // fused post-operations (what the reference passes as operation_after_loop).  The values are public: they are the
+  // form numbers of mgx_profile_read
+  enum BrickMode
+  {
+    kPlain    = 0, // out = A src                                   (vmult, laplace_operator.h:573)
+    kResidual = 1, // out = a - A src                               (vmult_residual, :605)
+    kCheb     = 2, // out = x + f1 (x - out) + f2 b (a - A x)       (PreconditionChebyshev update)
+    kChebFirst = 3, // out = x + f2 b (a - A x)                     (first step: no x_old term)
+    kChebZeroOld = 4, // out = x + f1 x + f2 b (a - A x)             (x_old known to be zero)
+    // start of PreconditionChebyshev::vmult (zero initial guess): the first iterate x_1 = f0 b a is
+    // never stored -- the first loop iteration computes it while gathering (kChebInit, x_old = 0),
+    // the second one recomputes it as its x_old (kChebOldInit); separable kernel only
+    kChebInit    = 5, // x := f0 b a ; out = x + f1 x + f2 b (a - A x)
+    kChebOldInit = 6, // out = x + f1 (x - f0 b a) + f2 b (a - A x)
+    // V-cycle: the residual a - A x is only needed restricted to the next coarser level
+    // (multigrid_solver.h:663-668).  Every brick restricts the residual values it completes (its
+    // LAST points, everything else masked to zero) with the transposed embedding and adds the
+    // (PB p + 1)^3 coarse values to the coarse vector; the residual itself is never stored.
+    kResidualRestrict = 7,
+    // fused PCG step (vmult_with_cg_update, laplace_operator.h:638-719; macro-element kernel only):
+    // the gather forms p_new = f2 p + q (f1 == 0: p_new = q); at completion x += f1 p_old,
+    // p = p_new, q = A p_new, and q.p, r.r, q.r, q.q are accumulated per workgroup
+    kCgUpdate = 8,
+    // first post-smoothing iteration of the V-cycle with the coarse-grid correction formed on the
+    // fly (multigrid_solver.h:674-678; macro-element kernel only): the gather adds the prolongated
+    // coarse values to x (prolong_brick), the iteration is kChebFirst on the corrected x, which is
+    // also written back at completion (it is x_old of the next iteration).  coarse / coarse_blocks
+    // as for kResidualRestrict.
+    kChebFirstProlong = 9
+  };
+  // the fused Chebyshev forms (they use the inverse diagonal and keep the source value)
+  __host__ __device__ constexpr bool is_cheb_mode(int mode)
+  {
+    return (mode >= kCheb && mode <= kChebOldInit) || mode == kChebFirstProlong;
+  }
+  // the forms that run on the reduced-colour schedules (FreeSchedule) where a level has one
+  constexpr bool on_free_schedule(int mode) { return mode >= kPlain && mode <= kChebOldInit; }
+
+  // One launch of the brick loop over the launch groups [group_begin, group_end) of a level, and the operands of the
+  // list kernels that complete it (launch_surf_finish, launch_unpack_ordered_cheb).  In the notation of BrickMode:
+  // a = rhs, b = dinv, x = src.
+  struct BrickLaunch
+  {
+    BrickMode       mode    = kPlain;
+    const void     *src     = nullptr; // vector the loop gathers (kChebInit: not read)
+    const void     *rhs     = nullptr; // residual forms: right-hand side; Chebyshev forms: rhs of the smoother
+    const void     *dinv    = nullptr; // Chebyshev forms: inverse diagonal
+    const void     *old     = nullptr; // kCheb: previous iterate (nullptr: it is `out`, which is then read before written)
+    void           *out     = nullptr; // result vector
+    void           *carrier = nullptr; // partial sums of brick-surface DoFs between the launches of a level (may be `out`)
+    double          f0 = 0., f1 = 0., f2 = 0.;
+    void           *coarse         = nullptr; // kResidualRestrict / kChebFirstProlong: vector of the next coarser level
+    const uint32_t *coarse_blocks  = nullptr; // ... TransferData::coarse_blocks
+    void           *coarse_scratch = nullptr; // kResidualRestrict: TransferData::coarse_scratch (nullptr: added into `coarse` colour by colour)
+    int             group_begin = 0, group_end = -1; // default: all groups of the eight-colour schedule (the interface /
+                                                     // interior halves of a split schedule are launched separately)
+    // on_free_schedule(mode), op.bricks.fr.available(): the launch groups are those of the reduced-colour schedule; the
+    // caller completes the private DoFs with launch_surf_finish
+    bool            free_schedule = false;
+
+    BrickLaunch groups(int g0, int g1) const
+    {
+      BrickLaunch l = *this;
+      l.group_begin = g0;
+      l.group_end   = g1;
+      return l;
+    }
+    // what the launchers work with: every pointer a kernel may form an address from is valid
+    BrickLaunch resolved(int n_groups = 0) const
+    {
+      BrickLaunch l = *this;
+      if (l.group_end < 0)
+        l.group_end = n_groups;
+      if (!l.old)
+        l.old = l.out;
+      if (!l.src)
+        l.src = l.rhs; // kChebInit: never dereferenced
+      return l;
+    }
+  };
+  void launch_brick_loop(hipStream_t s, const OperatorData &op, const BrickLaunch &launch);
+
+  // f(std::integral_constant<int, P>()) for P = p; false: no kernel is built for this degree.  (MGX_MACRO_ONLY_P: A/B
+  // builds of the macro-element translation units with one degree.)
+  template <typename F>
+  static bool dispatch_degree(int p, F &&f)
+  {
+    switch (p)
+      {
+#define MGX_DEGREE_CASE(P) \
+  case P: f(std::integral_constant<int, P>()); return true;
+#ifdef MGX_MACRO_ONLY_P
+        MGX_DEGREE_CASE(MGX_MACRO_ONLY_P)
+#else
+        MGX_DEGREE_CASE(1)
+        MGX_DEGREE_CASE(2)
+        MGX_DEGREE_CASE(3)
+        MGX_DEGREE_CASE(4)
+        MGX_DEGREE_CASE(5)
+        MGX_DEGREE_CASE(6)
+        MGX_DEGREE_CASE(7)
+        MGX_DEGREE_CASE(8)
+        MGX_DEGREE_CASE(9)
+#endif
+#undef MGX_DEGREE_CASE
+        default: return false;
+      }
+  }
+  // f(std::integral_constant<int, MODE>()) for the one of MODES that equals mode; false: none does
+  template <int... MODES, typename F>
+  static bool dispatch_mode(int mode, F &&f)
+  {
+    return ((mode == MODES ? (f(std::integral_constant<int, MODES>()), true) : false) || ...);
+  }
+  // workgroups of a persistent launch over `count` bricks: as many as are resident at once (wgs_per_cu on every CU of
+  // the operator's device); Tunables::macro_wg_x16 sets the number per CU instead (tuning aid)
+  inline uint32_t persistent_grid(const OperatorData &op, int wgs_per_cu, uint32_t count)
+  {
+    const uint32_t resident = op.macro_wg_x16 ? std::max<uint32_t>(1u, op.n_cus * op.macro_wg_x16 / 16u) : (uint32_t)wgs_per_cu * op.n_cus;
+    return std::min(count, resident);
+  }
   // LaplaceOperator::compute_residual (laplace_operator.h:804-845) through the general per-cell kernel:
   // dst += sum over the cells of  S^T [ rhs_q - D^T (K D S (-src)) ], src read through idx27_plain; assembly as in
   // launch_cell_diagonal (lists of cells that share no DoF / ordered assembly / atomics).  dst zeroed by the caller.
@@ -304,24 +418,16 @@ namespace mgx
   // order) that contains its entity e -- the one writer of the entity's DoFs
   void launch_interpolate_to_coarse(hipStream_t s, const TransferData &t, const void *r1d, const uint32_t *own_c, void *coarse,
                                     const void *fine);
-  // free_schedule (modes 0..6, op.bricks.fr.available()): the launch groups are those of the reduced-colour
-  // schedule; the caller completes the private DoFs with launch_surf_finish: DoFs [first, first + count)
-  // of op.bricks.fr.surf_dof; those below n_surf_shared: carrier[d] = sum only
+  // completes the private DoFs of a launch on a reduced-colour schedule: DoFs [first, first + count) of
+  // op.bricks.fr.surf_dof; those below n_surf_shared: carrier[d] = sum only
   // constrained / n_constrained (Chebyshev forms): rows where A x = x, updated by the same launch
-  void launch_surf_finish(hipStream_t s, const OperatorData &op, int mode, uint32_t first, uint32_t count, void *carrier,
-                          const void *x, void *out, const void *a, const void *dinv, const void *old, double f1, double f2,
-                          double f0, const uint32_t *constrained = nullptr, uint32_t n_constrained = 0,
+  void launch_surf_finish(hipStream_t s, const OperatorData &op, const BrickLaunch &launch, uint32_t first, uint32_t count,
+                          const uint32_t *constrained = nullptr, uint32_t n_constrained = 0,
                           const FreeSchedule *schedule = nullptr); // schedule: another one than op.bricks.fr
   // macro-element form of the separable brick loop (mgx_macro.hip), one translation unit per number
   // type; false: mode / degree not covered (the caller falls back to the cell-by-cell form)
-  bool launch_macro_loop_f64(hipStream_t s, const OperatorData &op, int mode, const void *src, const void *a,
-                             const void *b, void *out, void *partial, double f1, double f2, const void *old,
-                             double f0, void *coarse, const uint32_t *coarse_blocks, int group_begin, int group_end,
-                             bool free_schedule);
-  bool launch_macro_loop_f32(hipStream_t s, const OperatorData &op, int mode, const void *src, const void *a,
-                             const void *b, void *out, void *partial, double f1, double f2, const void *old,
-                             double f0, void *coarse, const uint32_t *coarse_blocks, int group_begin, int group_end,
-                             bool free_schedule);
+  bool launch_macro_loop_f64(hipStream_t s, const OperatorData &op, const BrickLaunch &launch);
+  bool launch_macro_loop_f32(hipStream_t s, const OperatorData &op, const BrickLaunch &launch);
   // fused PCG step on a brick-scheduled level (mgx_macro.hip, kCgUpdate)
   bool launch_macro_cg_update_f64(hipStream_t s, const OperatorData &op, double alpha, double beta, const void *r, void *q,
                                   void *p, void *x, void *carrier, double *partials, uint32_t capacity,
@@ -332,13 +438,9 @@ namespace mgx
   void launch_reduce4(hipStream_t s, const double *partials, uint32_t n, const double *extra, double *sums);
   void macro_diag_table_f64(hipStream_t s, const OperatorData &op, const uint32_t *item_map, void *table, uint32_t *flag_dev);
   void macro_diag_table_f32(hipStream_t s, const OperatorData &op, const uint32_t *item_map, void *table, uint32_t *flag_dev);
-  // second pipeline (mgx_macro2.hip: plain, residual, residual + restriction); false: form / degree not covered, use the first
-  bool launch_macro2_loop_f64(hipStream_t s, const OperatorData &op, int mode, const void *src, const void *a, void *out,
-                              void *partial, void *coarse, const uint32_t *coarse_blocks, int group_begin, int group_end,
-                              double f1, double f2, double f0, const void *old);
-  bool launch_macro2_loop_f32(hipStream_t s, const OperatorData &op, int mode, const void *src, const void *a, void *out,
-                              void *partial, void *coarse, const uint32_t *coarse_blocks, int group_begin, int group_end,
-                              double f1, double f2, double f0, const void *old);
+  // second pipeline (mgx_macro2.hip, macro2_covers); false: form / degree not covered, use the first
+  bool launch_macro2_loop_f64(hipStream_t s, const OperatorData &op, const BrickLaunch &launch);
+  bool launch_macro2_loop_f32(hipStream_t s, const OperatorData &op, const BrickLaunch &launch);
   // true: the brick loop evaluates the separable form (7 sweeps); false: the general
   // quadrature-point form of laplace_operator.h:436-523 (12 sweeps)
   // diag += diagonal of the cell matrices (local_compute_diagonal, laplace_operator.h:770-800)
@@ -370,15 +472,18 @@ namespace mgx
   void launch_invert(hipStream_t s, int number, void *v, size_t n);
   void launch_scatter_values(hipStream_t s, int number, void *v, const uint32_t *idx_dev, const double *val_dev,
                              uint32_t count);
-  // Chebyshev updates (PreconditionChebyshev internal::vector_updates):
-  //   mode 0: x = f2 * dinv * b, x_old = 0
-  //   mode 1: x_new = x + f2 * dinv * (b - t)                       (x_old <- x)
-  //   mode 2: x_new = x + f1 * (x - x_old) + f2 * dinv * (b - t)     (x_old <- x)
-  void launch_cheb_update(hipStream_t s, int number, int mode, void *x, void *x_old, const void *b,
+  // Chebyshev updates (PreconditionChebyshev internal::vector_updates); not the numbering of BrickMode
+  enum ChebUpdate
+  {
+    kUpdateStart     = 0, // x = f2 * dinv * b, x_old = 0
+    kUpdateFirst     = 1, // x_new = x + f2 * dinv * (b - t)                       (x_old <- x)
+    kUpdateThreeTerm = 2  // x_new = x + f1 * (x - x_old) + f2 * dinv * (b - t)     (x_old <- x)
+  };
+  void launch_cheb_update(hipStream_t s, int number, ChebUpdate mode, void *x, void *x_old, const void *b,
                           const void *t, const void *dinv, double f1, double f2, size_t n);
   void launch_cheb_init(hipStream_t s, int number, void *x, const void *b, const void *dinv, double f2, size_t n);
   // ax == nullptr: (A x)_c = x_c (constrained rows); otherwise the product is read from ax
-  void launch_cheb_constrained(hipStream_t s, int number, int mode, const void *x, void *out, const void *b,
+  void launch_cheb_constrained(hipStream_t s, int number, BrickMode mode, const void *x, void *out, const void *b,
                                const void *dinv, double f1, double f2, const uint32_t *list, uint32_t count,
                                const void *ax = nullptr, const void *old = nullptr, double f0 = 0.);
   // interface exchange helpers
@@ -398,18 +503,11 @@ namespace mgx
                              const uint32_t *csr_pos, uint32_t n_shared);
   // Chebyshev post-operation of the interface DoFs folded into the ordered unpack (one launch instead of two, and the
   // constrained rows -- A x = x -- ride along): what launch_cheb_constrained would do with ax = the completed sums
-  struct ChebList
-  {
-    int             mode;
-    const void     *x, *b, *dinv, *old;
-    void           *out;
-    double          f1, f2, f0;
-    const uint32_t *constrained;
-    uint32_t        n_constrained;
-  };
+  // (post: the operands of the brick launch the exchange completes)
   void launch_unpack_ordered_cheb(hipStream_t s, int number, void *const *recv, int n_neighbors, void *v,
                                   const uint32_t *shared, const uint32_t *csr_start, const uint8_t *csr_k,
-                                  const uint32_t *csr_pos, uint32_t n_shared, const ChebList &post);
+                                  const uint32_t *csr_pos, uint32_t n_shared, const BrickLaunch &post,
+                                  const uint32_t *constrained, uint32_t n_constrained);
   void launch_unpack_add(hipStream_t s, int number, void *v, const void *buf, const uint32_t *list, uint32_t count);
   void launch_list_residual(hipStream_t s, int number, void *res, const void *rhs, const uint32_t *list,
                             uint32_t count); // res[i] = rhs[i] - res[i]

@@ -1016,21 +1016,6 @@ namespace mgx
   // ------------------------------------------------------------------------------------------
   // launchers
   // ------------------------------------------------------------------------------------------
-#define MGX_DISPATCH_P(p, ...)                 \
-  switch (p)                                   \
-    {                                          \
-      case 1: { constexpr int P = 1; __VA_ARGS__; } break; \
-      case 2: { constexpr int P = 2; __VA_ARGS__; } break; \
-      case 3: { constexpr int P = 3; __VA_ARGS__; } break; \
-      case 4: { constexpr int P = 4; __VA_ARGS__; } break; \
-      case 5: { constexpr int P = 5; __VA_ARGS__; } break; \
-      case 6: { constexpr int P = 6; __VA_ARGS__; } break; \
-      case 7: { constexpr int P = 7; __VA_ARGS__; } break; \
-      case 8: { constexpr int P = 8; __VA_ARGS__; } break; \
-      case 9: { constexpr int P = 9; __VA_ARGS__; } break; \
-      default: break;                          \
-    }
-
   template <typename T>
   static void assemble_t(hipStream_t s, const OperatorData &op, int mode, void *dst, const void *tail_src, uint32_t n_head)
   {
@@ -1234,11 +1219,11 @@ namespace mgx
       return;
     if (number == 1)
       {
-        MGX_DISPATCH_P(p, dg_cg_transfer_t<P, double>(s, to_dg, dst, src, idx27, n_cells, P1, eight_colours));
+        dispatch_degree(p, [&](auto P) { dg_cg_transfer_t<P.value, double>(s, to_dg, dst, src, idx27, n_cells, P1, eight_colours); });
       }
     else
       {
-        MGX_DISPATCH_P(p, dg_cg_transfer_t<P, float>(s, to_dg, dst, src, idx27, n_cells, P1, eight_colours));
+        dispatch_degree(p, [&](auto P) { dg_cg_transfer_t<P.value, float>(s, to_dg, dst, src, idx27, n_cells, P1, eight_colours); });
       }
   }
 
@@ -1247,11 +1232,11 @@ namespace mgx
   {
     if (op.number == 1)
       {
-        MGX_DISPATCH_P(op.p, cell_loop_t<P, double>(s, op, dst, src, tail_src, n_head, post));
+        dispatch_degree(op.p, [&](auto P) { cell_loop_t<P.value, double>(s, op, dst, src, tail_src, n_head, post); });
       }
     else
       {
-        MGX_DISPATCH_P(op.p, cell_loop_t<P, float>(s, op, dst, src, tail_src, n_head, post));
+        dispatch_degree(op.p, [&](auto P) { cell_loop_t<P.value, float>(s, op, dst, src, tail_src, n_head, post); });
       }
   }
 
@@ -1322,11 +1307,11 @@ namespace mgx
   {
     if (op.number == 1)
       {
-        MGX_DISPATCH_P(op.p, cell_diag_t<P, double>(s, op, diag, a, m, lists, list_start, n_lists));
+        dispatch_degree(op.p, [&](auto P) { cell_diag_t<P.value, double>(s, op, diag, a, m, lists, list_start, n_lists); });
       }
     else
       {
-        MGX_DISPATCH_P(op.p, cell_diag_t<P, float>(s, op, diag, a, m, lists, list_start, n_lists));
+        dispatch_degree(op.p, [&](auto P) { cell_diag_t<P.value, float>(s, op, diag, a, m, lists, list_start, n_lists); });
       }
   }
 
@@ -1364,11 +1349,11 @@ namespace mgx
   {
     if (op.number == 1)
       {
-        MGX_DISPATCH_P(op.p, cell_residual_t<P, double>(s, op, dst, src, rhs_q, lists, list_start, n_lists));
+        dispatch_degree(op.p, [&](auto P) { cell_residual_t<P.value, double>(s, op, dst, src, rhs_q, lists, list_start, n_lists); });
       }
     else
       {
-        MGX_DISPATCH_P(op.p, cell_residual_t<P, float>(s, op, dst, src, rhs_q, lists, list_start, n_lists));
+        dispatch_degree(op.p, [&](auto P) { cell_residual_t<P.value, float>(s, op, dst, src, rhs_q, lists, list_start, n_lists); });
       }
   }
 
@@ -1419,11 +1404,11 @@ namespace mgx
   {
     if (op.number == 1)
       {
-        MGX_DISPATCH_P(op.p, cell_nl_residual_t<P, double>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists, list_start, n_lists));
+        dispatch_degree(op.p, [&](auto P) { cell_nl_residual_t<P.value, double>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists, list_start, n_lists); });
       }
     else
       {
-        MGX_DISPATCH_P(op.p, cell_nl_residual_t<P, float>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists, list_start, n_lists));
+        dispatch_degree(op.p, [&](auto P) { cell_nl_residual_t<P.value, float>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists, list_start, n_lists); });
       }
   }
 
@@ -1445,11 +1430,11 @@ namespace mgx
       return launch_prolongate_pipe(s, t, fine, coarse, add, with_constraints);
     if (t.coarse->number == 1)
       {
-        MGX_DISPATCH_P(t.coarse->p, prolongate_t<P, double>(s, t, fine, coarse, add, with_constraints));
+        dispatch_degree(t.coarse->p, [&](auto P) { prolongate_t<P.value, double>(s, t, fine, coarse, add, with_constraints); });
       }
     else
       {
-        MGX_DISPATCH_P(t.coarse->p, prolongate_t<P, float>(s, t, fine, coarse, add, with_constraints));
+        dispatch_degree(t.coarse->p, [&](auto P) { prolongate_t<P.value, float>(s, t, fine, coarse, add, with_constraints); });
       }
   }
 
@@ -1471,11 +1456,11 @@ namespace mgx
       return launch_restrict_add_pipe(s, t, coarse, fine, with_constraints);
     if (t.coarse->number == 1)
       {
-        MGX_DISPATCH_P(t.coarse->p, restrict_t<P, double>(s, t, coarse, fine, with_constraints));
+        dispatch_degree(t.coarse->p, [&](auto P) { restrict_t<P.value, double>(s, t, coarse, fine, with_constraints); });
       }
     else
       {
-        MGX_DISPATCH_P(t.coarse->p, restrict_t<P, float>(s, t, coarse, fine, with_constraints));
+        dispatch_degree(t.coarse->p, [&](auto P) { restrict_t<P.value, float>(s, t, coarse, fine, with_constraints); });
       }
   }
 } // namespace mgx

@@ -787,109 +787,51 @@ namespace mgx
   }
 
   // ------------------------------------------------------------------------------------------
-  // workgroups of a persistent launch per resident slot: the CUs of the device (x WGS per CU);
-  // Tunables::macro_wg_x16 scales it (tuning aid)
-  static uint32_t macro_cus(const OperatorData &op)
+  // The launch groups [g0, g1) of a schedule.  FREE: the reduced-colour schedule hands over its entity table, its group
+  // array and the blocks of private values; otherwise the eight colours of BrickData.
+  template <int P, typename T, int MODE, bool FREE>
+  static void macro_launch(hipStream_t s, const OperatorData &op, const T *src, BrickPost<T> post, int g0, int g1)
   {
-    static const int cus = [] {
-      int dev = 0, n = 256;
-      if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-      return std::max(1, n);
-    }();
-    return op.macro_wg_x16 ? std::max<uint32_t>(1u, (uint32_t)cus * op.macro_wg_x16 / 16u) : (uint32_t)cus;
-  }
-
-  template <int P, typename T, int MODE>
-  static void macro_launch_free(hipStream_t s, const OperatorData &op, const T *src, const BrickPost<T> &post_in, int g0, int g1)
-  {
-    using C             = MCfg<P, T>;
-    const FreeSchedule &fr = op.bricks.fr;
-    BrickPost<T>        post = post_in;
-    post.priv       = (T *)fr.priv;
-    post.surf_off   = fr.surf_off;
-    post.n_surf     = fr.n_surf;
-    post.priv_bytes = (uint32_t)((size_t)op.bricks.n_bricks * fr.n_surf * sizeof(T));
+    using C                     = MCfg<P, T>;
+    const BrickData &bd         = op.bricks;
+    const uint32_t  *ent        = FREE ? bd.fr.ent : bd.ent_base;
+    const uint32_t  *group_start = FREE ? bd.fr.group_start : bd.colour_start;
+    if (FREE)
+      {
+        post.priv       = (T *)bd.fr.priv;
+        post.surf_off   = bd.fr.surf_off;
+        post.n_surf     = bd.fr.n_surf;
+        post.priv_bytes = (uint32_t)((size_t)bd.n_bricks * bd.fr.n_surf * sizeof(T));
+      }
+    // the fused Chebyshev forms read the inverse diagonal from the per-item table where there is one (DTAB)
     constexpr bool kUsesDiag = is_cheb_mode(MODE);
-    if (kUsesDiag && op.diag_items)
+    const bool     dtab      = kUsesDiag && op.diag_items;
+    if (dtab)
       post.b = (const T *)op.diag_items;
-    for (int g = g0; g < g1; ++g)
-      {
-        const uint32_t first = fr.group_start[g], count = fr.group_start[g + 1] - first;
-        if (count == 0)
-          continue;
-        const uint32_t grid = std::min<uint32_t>(count, (uint32_t)(op.macro_wg_x16 ? 1 : C::WGS) * macro_cus(op));
-        if (kUsesDiag && op.diag_items)
-          hipLaunchKernelGGL((brick_macro_kernel<P, T, MODE, kUsesDiag, true>), dim3(grid), dim3(C::THREADS), 0, s, src, first,
-                             count, fr.ent, op.bricks.item_map, (const Basis1D<T> *)op.basis, (T)op.coef[0], (T)op.coef[1],
-                             (T)op.coef[2], post, (uint32_t)(op.n_dofs * sizeof(T)));
-        else
-          hipLaunchKernelGGL((brick_macro_kernel<P, T, MODE, false, true>), dim3(grid), dim3(C::THREADS), 0, s, src, first,
-                             count, fr.ent, op.bricks.item_map, (const Basis1D<T> *)op.basis, (T)op.coef[0], (T)op.coef[1],
-                             (T)op.coef[2], post, (uint32_t)(op.n_dofs * sizeof(T)));
-      }
-  }
-
-  template <int P, typename T, int MODE>
-  static void macro_launch(hipStream_t s, const OperatorData &op, const T *src, const BrickPost<T> &post, int g0, int g1,
-                           bool free_schedule = false)
-  {
-    using C             = MCfg<P, T>;
-    const BrickData &bd = op.bricks;
-    if (free_schedule)
-      {
-        if constexpr (MODE <= kChebOldInit)
-          return macro_launch_free<P, T, MODE>(s, op, src, post, g0, g1);
-      }
     // kResidualRestrict with a coarse scratch array: the bricks hand nothing to each other and write disjoint
     // addresses -- one launch for all of them
     const bool one_launch = MODE == kResidualRestrict && post.coarse_scratch != nullptr;
     for (int c = g0; c < g1; ++c)
       {
-        uint32_t first = bd.colour_start[c], count = bd.colour_start[c + 1] - first;
+        uint32_t first = group_start[c], count = group_start[c + 1] - first;
         if (one_launch)
           {
             if (c != g0)
               break;
-            count = bd.colour_start[g1] - first;
+            count = group_start[g1] - first;
           }
         if (count == 0)
           continue;
-        // persistent workgroups: as many as are resident at once (WGS per CU), each walks over
-        // count / grid bricks
-        const uint32_t grid = std::min<uint32_t>(count, (uint32_t)(op.macro_wg_x16 ? 1 : C::WGS) * macro_cus(op));
-        constexpr bool kUsesDiag = is_cheb_mode(MODE);
-        if (kUsesDiag && op.diag_items)
-          {
-            BrickPost<T> pt = post;
-            pt.b            = (const T *)op.diag_items;
-            hipLaunchKernelGGL((brick_macro_kernel<P, T, MODE, kUsesDiag>), dim3(grid), dim3(C::THREADS), 0, s, src, first,
-                               count, bd.ent_base, bd.item_map, (const Basis1D<T> *)op.basis, (T)op.coef[0],
-                               (T)op.coef[1], (T)op.coef[2], pt, (uint32_t)(op.n_dofs * sizeof(T)));
-          }
+        // persistent workgroups, each walks over count / grid bricks
+        const uint32_t grid = persistent_grid(op, C::WGS, count);
+        if (dtab)
+          hipLaunchKernelGGL((brick_macro_kernel<P, T, MODE, kUsesDiag, FREE>), dim3(grid), dim3(C::THREADS), 0, s, src, first,
+                             count, ent, bd.item_map, (const Basis1D<T> *)op.basis, (T)op.coef[0], (T)op.coef[1],
+                             (T)op.coef[2], post, (uint32_t)(op.n_dofs * sizeof(T)));
         else
-          hipLaunchKernelGGL((brick_macro_kernel<P, T, MODE, false>), dim3(grid), dim3(C::THREADS), 0, s, src, first,
-                             count, bd.ent_base, bd.item_map, (const Basis1D<T> *)op.basis, (T)op.coef[0],
-                             (T)op.coef[1], (T)op.coef[2], post, (uint32_t)(op.n_dofs * sizeof(T)));
-      }
-  }
-
-  template <int P, typename T>
-  static void macro_modes(hipStream_t s, const OperatorData &op, int mode, const T *src, const BrickPost<T> &post, int g0,
-                          int g1, bool fr)
-  {
-    switch (mode)
-      {
-        case kPlain: macro_launch<P, T, kPlain>(s, op, src, post, g0, g1, fr); break;
-        case kResidual: macro_launch<P, T, kResidual>(s, op, src, post, g0, g1, fr); break;
-        case kCheb: macro_launch<P, T, kCheb>(s, op, src, post, g0, g1, fr); break;
-        case kChebFirst: macro_launch<P, T, kChebFirst>(s, op, src, post, g0, g1, fr); break;
-        case kChebZeroOld: macro_launch<P, T, kChebZeroOld>(s, op, src, post, g0, g1, fr); break;
-        case kChebInit: macro_launch<P, T, kChebInit>(s, op, src, post, g0, g1, fr); break;
-        case kChebOldInit: macro_launch<P, T, kChebOldInit>(s, op, src, post, g0, g1, fr); break;
-        case kResidualRestrict: macro_launch<P, T, kResidualRestrict>(s, op, src, post, g0, g1); break;
-        case kChebFirstProlong: macro_launch<P, T, kChebFirstProlong>(s, op, src, post, g0, g1); break;
-        default: break;
+          hipLaunchKernelGGL((brick_macro_kernel<P, T, MODE, false, FREE>), dim3(grid), dim3(C::THREADS), 0, s, src, first,
+                             count, ent, bd.item_map, (const Basis1D<T> *)op.basis, (T)op.coef[0], (T)op.coef[1],
+                             (T)op.coef[2], post, (uint32_t)(op.n_dofs * sizeof(T)));
       }
   }
 
@@ -996,8 +938,7 @@ namespace mgx
       // already updates p, q and x, after which the caller's unfused path would start from half-updated vectors
       uint64_t total = 0;
       for (int c = 0; c < bd.n_colours; ++c)
-        total += std::min<uint32_t>(bd.colour_start[c + 1] - bd.colour_start[c],
-                                    (uint32_t)(op.macro_wg_x16 ? 1 : C::WGS) * macro_cus(op));
+        total += persistent_grid(op, C::WGS, bd.colour_start[c + 1] - bd.colour_start[c]);
       if (total > capacity)
         return false;
       for (int c = 0; c < bd.n_colours; ++c)
@@ -1005,7 +946,7 @@ namespace mgx
           const uint32_t first = bd.colour_start[c], count = bd.colour_start[c + 1] - first;
           if (count == 0)
             continue;
-          const uint32_t grid = std::min<uint32_t>(count, (uint32_t)(op.macro_wg_x16 ? 1 : C::WGS) * macro_cus(op));
+          const uint32_t grid = persistent_grid(op, C::WGS, count);
           post.sums = partials + 4 * (size_t)used;
           used += grid;
           hipLaunchKernelGGL((brick_macro_kernel<C::N - 1, T, kCgUpdate, false>), dim3(grid), dim3(C::THREADS), 0, s,
@@ -1015,23 +956,10 @@ namespace mgx
       return true;
     };
     bool ok = false;
-    switch (op.p)
-      {
-#ifdef MGX_MACRO_ONLY_P
-        case MGX_MACRO_ONLY_P: ok = run(MCfg<MGX_MACRO_ONLY_P, T>()); break;
-#else
-        case 1: ok = run(MCfg<1, T>()); break;
-        case 2: ok = run(MCfg<2, T>()); break;
-        case 3: ok = run(MCfg<3, T>()); break;
-        case 4: ok = run(MCfg<4, T>()); break;
-        case 5: ok = run(MCfg<5, T>()); break;
-        case 6: ok = run(MCfg<6, T>()); break;
-        case 7: ok = run(MCfg<7, T>()); break;
-        case 8: ok = run(MCfg<8, T>()); break;
-        case 9: ok = run(MCfg<9, T>()); break;
-#endif
-        default: break;
-      }
+    dispatch_degree(op.p, [&](auto degree) {
+      if constexpr (!MGX_MACRO_PAIRS) // (kCgUpdate is written for single items: not instantiated in a build with pairs)
+        ok = run(MCfg<decltype(degree)::value, T>());
+    });
     *n_partials = used;
     return ok;
   }
@@ -1044,53 +972,33 @@ namespace mgx
 #endif
 
   // one translation unit per number type (Makefile: -DMGX_MACRO_T=double|float -DMGX_MACRO_SUFFIX=f64|f32)
-  bool MGX_CAT(launch_macro_loop_, MGX_MACRO_SUFFIX)(hipStream_t s, const OperatorData &op, int mode, const void *src,
-                                                     const void *a, const void *b, void *out, void *partial,
-                                                     double f1, double f2, const void *old, double f0, void *coarse,
-                                                     const uint32_t *coarse_blocks, int g0, int g1, bool free_schedule)
+  bool MGX_CAT(launch_macro_loop_, MGX_MACRO_SUFFIX)(hipStream_t s, const OperatorData &op, const BrickLaunch &l)
   {
     using T = MGX_MACRO_T;
-    const bool fr = free_schedule && op.bricks.fr.available() && mode <= kChebOldInit && !MGX_MACRO_PAIRS;
-    if (free_schedule && !fr)
+    const bool fr = l.free_schedule && op.bricks.fr.available() && on_free_schedule(l.mode) && !MGX_MACRO_PAIRS;
+    if (l.free_schedule && !fr)
       return false;
     // the forms the second pipeline covers (mgx_macro2.hip) on the eight-colour schedule
-    if (!free_schedule && op.macro_v2 && !MGX_MACRO_PAIRS &&
-        MGX_CAT(launch_macro2_loop_, MGX_MACRO_SUFFIX)(s, op, mode, src, a, out, partial, coarse, coarse_blocks, g0, g1, f1, f2, f0, old))
+    if (!l.free_schedule && op.macro_v2 && !MGX_MACRO_PAIRS && MGX_CAT(launch_macro2_loop_, MGX_MACRO_SUFFIX)(s, op, l))
       return true;
-    if (mode < kPlain || (mode > kResidualRestrict && mode != kChebFirstProlong) || MGX_MACRO_PAIRS * (mode == kChebFirstProlong) ||
-        (uint64_t)op.n_dofs * sizeof(T) >= 0xFFFFFFF0ull)
+    if (MGX_MACRO_PAIRS * (l.mode == kChebFirstProlong) || (uint64_t)op.n_dofs * sizeof(T) >= 0xFFFFFFF0ull)
       return false;
-    BrickPost<T> post{};
-    post.a             = (const T *)a;
-    post.b             = (const T *)b;
-    post.old           = (const T *)old;
-    post.out           = (T *)out;
-    post.partial       = (T *)partial;
-    post.f1            = (T)f1;
-    post.f2            = (T)f2;
-    post.f0            = (T)f0;
-    post.coarse        = (T *)coarse;
-    post.coarse_blocks = coarse_blocks;
-    // (kResidualRestrict carries no partial sums: its `partial` argument names the coarse scratch array, if any)
-    post.coarse_scratch = mode == kResidualRestrict ? (T *)partial : nullptr;
-    post.src_w         = (T *)const_cast<void *>(src); // kChebFirstProlong writes the corrected x back
-    switch (op.p)
-      {
-#ifdef MGX_MACRO_ONLY_P
-        case MGX_MACRO_ONLY_P: macro_modes<MGX_MACRO_ONLY_P, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-#else
-        case 1: macro_modes<1, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-        case 2: macro_modes<2, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-        case 3: macro_modes<3, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-        case 4: macro_modes<4, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-        case 5: macro_modes<5, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-        case 6: macro_modes<6, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-        case 7: macro_modes<7, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-        case 8: macro_modes<8, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-        case 9: macro_modes<9, T>(s, op, mode, (const T *)src, post, g0, g1, fr); break;
-#endif
-        default: return false;
-      }
-    return true;
+    BrickPost<T> post = make_post<T>(l);
+    post.src_w        = (T *)const_cast<void *>(l.src); // kChebFirstProlong writes the corrected x back
+    const T  *src     = (const T *)l.src;
+    const int g0 = l.group_begin, g1 = l.group_end;
+    bool      launched = false;
+    dispatch_degree(op.p, [&](auto degree) {
+      constexpr int P = decltype(degree)::value;
+      launched        = dispatch_mode<kPlain, kResidual, kCheb, kChebFirst, kChebZeroOld, kChebInit, kChebOldInit, kResidualRestrict,
+                               kChebFirstProlong>(l.mode, [&](auto form) {
+        constexpr int MODE = decltype(form)::value;
+        if constexpr (on_free_schedule(MODE))
+          if (fr)
+            return macro_launch<P, T, MODE, true>(s, op, src, post, g0, g1);
+        macro_launch<P, T, MODE, false>(s, op, src, post, g0, g1);
+      });
+    });
+    return launched;
   }
 } // namespace mgx

@@ -1,6 +1,9 @@
-// mgx_macro2.hip -- second pipeline of the macro-element brick loop for the forms whose write-out loads nothing but
-// partial sums: plain (LaplaceOperator::vmult, laplace_operator.h:527-601) and residual (vmult_residual, :605).  Same
-// operator, same sweeps, same entity tables and the same bits as mgx_macro.hip.
+// mgx_macro2.hip -- second pipeline of the macro-element brick loop.  It runs the forms macro2_covers() names: plain
+// (LaplaceOperator::vmult, laplace_operator.h:527-601) and residual (vmult_residual, :605), whose write-out loads nothing
+// but partial sums; the Chebyshev form that takes x_old from the right-hand side (kChebOldInit); and, at p <= 4, the
+// first Chebyshev iteration from a zero start (kChebInit) and residual + restriction (kResidualRestrict).  The other
+// Chebyshev forms, kCgUpdate and kChebFirstProlong run on the first pipeline only.  Same operator, same sweeps, same
+// entity tables and the same bits as mgx_macro.hip.
 //
 // What round 4 measured on the first pipeline (profiles/r04_*, 135 M DoFs, p = 4):
 //   * phase stamps of the plain form: a brick costs a workgroup 24 100 cycles -- sweeps 10 500, tables parked + gather
@@ -23,8 +26,8 @@
 // Measured: plain 104 -> 95 us per colour launch.  Also measured and not kept (tools/experiments/
 // r04_macro2_wide_early_variants.hip.txt): the gather of the next brick issued before the sweeps (its loads then queue
 // behind the stores of the write-out just before: 99 us); 512-thread workgroups with the sweeps as cell-block tasks
-// (four waves per SIMD: 98 us, the LDS array 63 % busy); the Chebyshev forms on this pipeline (143-148 against 144 us:
-// their write-out waits for its operands either way).
+// (four waves per SIMD: 98 us, the LDS array 63 % busy); the general Chebyshev iteration on this pipeline (143-148
+// against 144 us: its write-out waits for its operands either way).
 // Barriers order LDS traffic only (lds_barrier): global loads stay in flight across them.
 #include "mgx_macro_device.hpp"
 
@@ -264,10 +267,11 @@ namespace mgx
   // side in flight across the sweeps cost more than the wait they remove -- 274 against 257 us per colour launch at p = 8)
   // Of the Chebyshev forms the two that never store the first iterate (kChebInit, kChebOldInit) run here, with the inverse
   // diagonal taken from the per-item table (uniform meshes; where it has to be streamed they stay on the first
-  // pipeline): 119 -> 116 and 133 -> 126 us per colour launch.  The general iteration (kCheb: 144 -> 148 us) and its
+  // pipeline): 119 -> 116 and 133 -> 126 us per colour launch (kChebInit at p <= 4 only; p = 8: 155 against 141 us on
+  // the first pipeline).  The general iteration (kCheb: 144 -> 148 us) and its
   // two special cases gain nothing from the earlier partial sums -- their write-out waits for b and x_old either way --
   // and stay on the first pipeline.
-  __host__ __device__ constexpr bool macro2_covers(int mode, int p = 4)
+  __host__ __device__ constexpr bool macro2_covers(int mode, int p)
   {
     return mode == kPlain || mode == kResidual || ((mode == kResidualRestrict || mode == kChebInit) && p <= 4) || mode == kChebOldInit;
   }
@@ -278,7 +282,7 @@ namespace mgx
                         const uint32_t *__restrict__ ent_base, const uint32_t *__restrict__ item_map,
                         const Basis1D<T> *__restrict__ B, T c0, T c1, T c2, BrickPost<T> post, uint32_t vec_bytes)
   {
-    static_assert(macro2_covers(MODE, (MODE == kResidualRestrict || MODE == kChebInit) ? 4 : P), "form not covered by this pipeline");
+    static_assert(macro2_covers(MODE, P), "form not covered by this pipeline");
     using C            = M2Cfg<P, T>;
     constexpr int NT   = C::THREADS, IT = C::IT, JINT = C::JINT, JSURF = C::JSURF, NE = C::NE;
     constexpr int NEW  = (NE + NT - 1) / NT; // entity words per thread
@@ -603,17 +607,6 @@ namespace mgx
   }
 
   // ------------------------------------------------------------------------------------------
-  static uint32_t macro2_cus(const OperatorData &op)
-  {
-    static const int cus = [] {
-      int dev = 0, n = 256;
-      if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-      return std::max(1, n);
-    }();
-    return op.macro_wg_x16 ? std::max<uint32_t>(1u, (uint32_t)cus * op.macro_wg_x16 / 16u) : (uint32_t)cus;
-  }
-
   template <int P, typename T, int MODE>
   static void macro2_launch(hipStream_t s, const OperatorData &op, const T *src, const BrickPost<T> &post, int g0, int g1)
   {
@@ -633,77 +626,37 @@ namespace mgx
           }
         if (count == 0)
           continue;
-        // persistent workgroups: as many as are resident at once (WGS per CU)
-        const uint32_t grid = std::min<uint32_t>(count, (uint32_t)(op.macro_wg_x16 ? 1 : C::WGS) * macro2_cus(op));
+        const uint32_t grid = persistent_grid(op, C::WGS, count);
         hipLaunchKernelGGL((brick_macro2_kernel<P, T, MODE>), dim3(grid), dim3(C::THREADS), 0, s, src, first, count, bd.ent_base,
                            bd.item_map2, (const Basis1D<T> *)op.basis, (T)op.coef[0], (T)op.coef[1], (T)op.coef[2], post,
                            (uint32_t)(op.n_dofs * sizeof(T)));
       }
   }
 
-  template <int P, typename T>
-  static void macro2_modes(hipStream_t s, const OperatorData &op, int mode, const T *src, const BrickPost<T> &post, int g0, int g1)
-  {
-    switch (mode)
-      {
-        case kPlain: macro2_launch<P, T, kPlain>(s, op, src, post, g0, g1); break;
-        case kResidual: macro2_launch<P, T, kResidual>(s, op, src, post, g0, g1); break;
-        case kChebInit:
-          if constexpr (P <= 4) // (p = 8: 155 against 141 us on the first pipeline)
-            macro2_launch<P, T, kChebInit>(s, op, src, post, g0, g1);
-          break;
-        case kChebOldInit: macro2_launch<P, T, kChebOldInit>(s, op, src, post, g0, g1); break;
-        case kResidualRestrict:
-          if constexpr (P <= 4)
-            macro2_launch<P, T, kResidualRestrict>(s, op, src, post, g0, g1);
-          break;
-        default: break;
-      }
-  }
-
 #define MGX_CAT2(a, b) a##b
 #define MGX_CAT(a, b) MGX_CAT2(a, b)
   // false: form / degree / vector size not covered by this pipeline (the caller uses the first one)
-  // kResidualRestrict: `partial` names the per-brick scratch array of the restricted values (or nullptr: added into
-  // `coarse` colour by colour), coarse_blocks the coarse entity table of the bricks' parents
-  bool MGX_CAT(launch_macro2_loop_, MGX_MACRO_SUFFIX)(hipStream_t s, const OperatorData &op, int mode, const void *src, const void *a,
-                                                      void *out, void *partial, void *coarse, const uint32_t *coarse_blocks, int g0,
-                                                      int g1, double f1, double f2, double f0, const void *old)
+  bool MGX_CAT(launch_macro2_loop_, MGX_MACRO_SUFFIX)(hipStream_t s, const OperatorData &op, const BrickLaunch &l)
   {
     using T = MGX_MACRO_T;
-    if (!macro2_covers(mode, op.p) || !op.bricks.item_map2 || (uint64_t)op.n_dofs * sizeof(T) >= 0xFFFFFFF0ull)
+    if (!macro2_covers(l.mode, op.p) || !op.bricks.item_map2 || (uint64_t)op.n_dofs * sizeof(T) >= 0xFFFFFFF0ull)
       return false;
-    if (is_cheb_mode(mode) && !op.diag_items2) // inverse diagonal not uniform per item: streamed by the first pipeline
+    if (is_cheb_mode(l.mode) && !op.diag_items2) // inverse diagonal not uniform per item: streamed by the first pipeline
       return false;
-    BrickPost<T> post{};
-    post.b   = (const T *)op.diag_items2;
-    post.old = (const T *)old;
-    post.f1  = (T)f1;
-    post.f2  = (T)f2;
-    post.f0  = (T)f0;
-    post.a              = (const T *)a;
-    post.out            = (T *)out;
-    post.partial        = (T *)partial;
-    post.coarse         = (T *)coarse;
-    post.coarse_blocks  = coarse_blocks;
-    post.coarse_scratch = mode == kResidualRestrict ? (T *)partial : nullptr;
-    switch (op.p)
-      {
-#ifdef MGX_MACRO_ONLY_P
-        case MGX_MACRO_ONLY_P: macro2_modes<MGX_MACRO_ONLY_P, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-#else
-        case 1: macro2_modes<1, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-        case 2: macro2_modes<2, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-        case 3: macro2_modes<3, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-        case 4: macro2_modes<4, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-        case 5: macro2_modes<5, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-        case 6: macro2_modes<6, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-        case 7: macro2_modes<7, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-        case 8: macro2_modes<8, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-        case 9: macro2_modes<9, T>(s, op, mode, (const T *)src, post, g0, g1); break;
-#endif
-        default: return false;
-      }
-    return true;
+    BrickPost<T> post = make_post<T>(l);
+    post.b            = (const T *)op.diag_items2; // the per-item table in the order of this pipeline's item map
+    bool launched     = false;
+    dispatch_degree(op.p, [&](auto degree) {
+      constexpr int P = decltype(degree)::value;
+      dispatch_mode<kPlain, kResidual, kChebInit, kChebOldInit, kResidualRestrict>(l.mode, [&](auto form) {
+        constexpr int MODE = decltype(form)::value;
+        if constexpr (macro2_covers(MODE, P))
+          {
+            macro2_launch<P, T, MODE>(s, op, (const T *)l.src, post, l.group_begin, l.group_end);
+            launched = true;
+          }
+      });
+    });
+    return launched;
   }
 } // namespace mgx

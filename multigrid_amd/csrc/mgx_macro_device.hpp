@@ -320,12 +320,6 @@ namespace mgx
   __device__ __forceinline__ uint32_t item_point(uint32_t m) { return (m >> 10) & 8191u; }
   __device__ __forceinline__ uint32_t item_offset(uint32_t m) { return m >> 23; }
 
-  // the fused Chebyshev forms (they use the inverse diagonal and keep the source value)
-  __host__ __device__ constexpr bool is_cheb_mode(int mode)
-  {
-    return (mode >= kCheb && mode <= kChebOldInit) || mode == kChebFirstProlong;
-  }
-
   // Vector access through buffer descriptors: address = (scalar base) + (32-bit byte offset in one
   // VGPR), no 64-bit address arithmetic and no VGPR pair per access in flight; offsets at or beyond
   // the vector's size are out of range: such a load returns zero and such a store is dropped

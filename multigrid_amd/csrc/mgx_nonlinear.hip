@@ -328,21 +328,6 @@ namespace mgx
       }
   }
 
-#define MGX_NL_DISPATCH_P(p, ...)                          \
-  switch (p)                                               \
-    {                                                      \
-      case 1: { constexpr int P = 1; __VA_ARGS__; } break; \
-      case 2: { constexpr int P = 2; __VA_ARGS__; } break; \
-      case 3: { constexpr int P = 3; __VA_ARGS__; } break; \
-      case 4: { constexpr int P = 4; __VA_ARGS__; } break; \
-      case 5: { constexpr int P = 5; __VA_ARGS__; } break; \
-      case 6: { constexpr int P = 6; __VA_ARGS__; } break; \
-      case 7: { constexpr int P = 7; __VA_ARGS__; } break; \
-      case 8: { constexpr int P = 8; __VA_ARGS__; } break; \
-      case 9: { constexpr int P = 9; __VA_ARGS__; } break; \
-      default: break;                                      \
-    }
-
   template <int P, typename T, typename TO>
   static void evaluate_coefficient_t(hipStream_t s, const OperatorData &op, void *coef_q, bool minimal_surface, const double *M,
                                      double det, const void *unit_q, const void *jxw_q, const void *state)
@@ -375,15 +360,15 @@ namespace mgx
   {
     if (op.number == 1 && coef_number == 1)
       {
-        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, double, double>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state));
+        dispatch_degree(op.p, [&](auto P) { evaluate_coefficient_t<P.value, double, double>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state); });
       }
     else if (op.number == 1)
       {
-        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, double, float>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state));
+        dispatch_degree(op.p, [&](auto P) { evaluate_coefficient_t<P.value, double, float>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state); });
       }
     else // (fp32 tables: fp32 tensor)
       {
-        MGX_NL_DISPATCH_P(op.p, evaluate_coefficient_t<P, float, float>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state));
+        dispatch_degree(op.p, [&](auto P) { evaluate_coefficient_t<P.value, float, float>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state); });
       }
   }
 
@@ -401,11 +386,11 @@ namespace mgx
   {
     if (t.coarse->number == 1)
       {
-        MGX_NL_DISPATCH_P(t.coarse->p, interpolate_t<P, double>(s, t, r1d, own_c, coarse, fine));
+        dispatch_degree(t.coarse->p, [&](auto P) { interpolate_t<P.value, double>(s, t, r1d, own_c, coarse, fine); });
       }
     else
       {
-        MGX_NL_DISPATCH_P(t.coarse->p, interpolate_t<P, float>(s, t, r1d, own_c, coarse, fine));
+        dispatch_degree(t.coarse->p, [&](auto P) { interpolate_t<P.value, float>(s, t, r1d, own_c, coarse, fine); });
       }
   }
 } // namespace mgx

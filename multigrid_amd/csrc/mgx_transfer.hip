@@ -535,31 +535,16 @@ namespace mgx
       }
   }
 
-#define MGX_TP_DISPATCH(p, ...)                            \
-  switch (p)                                               \
-    {                                                      \
-      case 1: { constexpr int P = 1; __VA_ARGS__; } break; \
-      case 2: { constexpr int P = 2; __VA_ARGS__; } break; \
-      case 3: { constexpr int P = 3; __VA_ARGS__; } break; \
-      case 4: { constexpr int P = 4; __VA_ARGS__; } break; \
-      case 5: { constexpr int P = 5; __VA_ARGS__; } break; \
-      case 6: { constexpr int P = 6; __VA_ARGS__; } break; \
-      case 7: { constexpr int P = 7; __VA_ARGS__; } break; \
-      case 8: { constexpr int P = 8; __VA_ARGS__; } break; \
-      case 9: { constexpr int P = 9; __VA_ARGS__; } break; \
-      default: break;                                      \
-    }
-
   void launch_prolongate_pipe(hipStream_t s, const TransferData &t, void *fine, const void *coarse, bool add,
                               bool with_constraints)
   {
     if (t.coarse->number == 1)
       {
-        MGX_TP_DISPATCH(t.coarse->p, launch_t<P, double>(s, t, 0, fine, coarse, nullptr, add, with_constraints));
+        dispatch_degree(t.coarse->p, [&](auto P) { launch_t<P.value, double>(s, t, 0, fine, coarse, nullptr, add, with_constraints); });
       }
     else
       {
-        MGX_TP_DISPATCH(t.coarse->p, launch_t<P, float>(s, t, 0, fine, coarse, nullptr, add, with_constraints));
+        dispatch_degree(t.coarse->p, [&](auto P) { launch_t<P.value, float>(s, t, 0, fine, coarse, nullptr, add, with_constraints); });
       }
   }
 
@@ -568,11 +553,11 @@ namespace mgx
   {
     if (t.coarse->number == 1)
       {
-        MGX_TP_DISPATCH(t.coarse->p, launch_t<P, double>(s, t, 1, const_cast<void *>(fine), nullptr, coarse, false, with_constraints));
+        dispatch_degree(t.coarse->p, [&](auto P) { launch_t<P.value, double>(s, t, 1, const_cast<void *>(fine), nullptr, coarse, false, with_constraints); });
       }
     else
       {
-        MGX_TP_DISPATCH(t.coarse->p, launch_t<P, float>(s, t, 1, const_cast<void *>(fine), nullptr, coarse, false, with_constraints));
+        dispatch_degree(t.coarse->p, [&](auto P) { launch_t<P.value, float>(s, t, 1, const_cast<void *>(fine), nullptr, coarse, false, with_constraints); });
       }
   }
 

@@ -97,7 +97,7 @@ namespace mgx
   {
     GRID_STRIDE(i, n)
     {
-      if (MODE == 0)
+      if (MODE == kUpdateStart)
         {
           x_old[i] = T(0);
           x[i]     = f2 * dinv[i] * b[i];
@@ -106,7 +106,7 @@ namespace mgx
         {
           const T xi = x[i];
           T       xn = xi + f2 * dinv[i] * (b[i] - t[i]);
-          if (MODE == 2)
+          if (MODE == kUpdateThreeTerm)
             xn += f1 * (xi - x_old[i]);
           x_old[i] = xi;
           x[i]     = xn;
@@ -122,9 +122,26 @@ namespace mgx
     GRID_STRIDE(i, n) x[i] = f2 * dinv[i] * b[i];
   }
 
-  // Chebyshev update on the constrained rows, where (A x)_c = x_c (laplace_operator.h:736-737);
-  // mode as in mgx_brick.hip: 2 general, 3 first step, 4 x_old == 0, 5 x = f0 D^-1 b computed
-  // here and x_old == 0, 6 x_old = f0 D^-1 b computed here
+  // The Chebyshev update of the fused brick forms (BrickMode, post_finish in mgx_macro_device.hpp) on DoF d, for the
+  // list kernels that complete what the brick loop leaves: ax = (A x)_d, or ident: a constrained row, (A x)_d = x_d
+  // (laplace_operator.h:736-737).  bv = b_d, dv = the inverse diagonal; kChebInit / kChebOldInit evaluate f0 D^-1 b here.
+  // The same expressions in the same order as post_finish: the results agree bit for bit under every schedule.
+  template <typename T>
+  __device__ __forceinline__ T cheb_point(int form, const T *x, const T *old, uint32_t d, bool ident, T ax, T bv, T dv, T f0,
+                                          T f1, T f2)
+  {
+    const T xi = form == kChebInit ? f0 * dv * bv : x[d];
+    T       xn = xi + f2 * dv * (bv - (ident ? xi : ax));
+    if (form == kCheb)
+      xn += f1 * (xi - old[d]);
+    else if (form == kChebOldInit)
+      xn += f1 * (xi - f0 * dv * bv);
+    else if (form == kChebZeroOld || form == kChebInit)
+      xn += f1 * xi;
+    return xn;
+  }
+
+  // Chebyshev update on the rows of a list: the constrained rows (ax == nullptr), or rows whose A x is read from ax
   template <typename T>
   __global__ void __launch_bounds__(256)
     k_cheb_constrained(int mode, const T *__restrict__ x, T *__restrict__ out, const T *__restrict__ b,
@@ -133,16 +150,8 @@ namespace mgx
   {
     GRID_STRIDE(i, count)
     {
-      const uint32_t c  = list[i];
-      const T        xi = mode == 5 ? f0 * dinv[c] * b[c] : x[c];
-      T              xn = xi + f2 * dinv[c] * (b[c] - (ax ? ax[c] : xi));
-      if (mode == 2)
-        xn += f1 * (xi - old[c]);
-      else if (mode == 6)
-        xn += f1 * (xi - f0 * dinv[c] * b[c]);
-      else if (mode == 4 || mode == 5)
-        xn += f1 * xi;
-      out[c] = xn;
+      const uint32_t c = list[i];
+      out[c]           = cheb_point(mode, x, old, c, ax == nullptr, ax ? ax[c] : T(0), b[c], dinv[c], f0, f1, f2);
     }
   }
 
@@ -247,23 +256,12 @@ namespace mgx
               continue;
             }
         }
-      if (mode == 0)
+      if (mode == kPlain)
         out[d] = sum;
-      else if (mode == 1)
+      else if (mode == kResidual)
         out[d] = a[d] - sum;
       else
-        {
-          const T bv = dinv[d], av = a[d];
-          const T xi = mode == 5 ? f0 * bv * av : x[d];
-          T       xn = xi + f2 * bv * (av - (ident ? xi : sum));
-          if (mode == 2)
-            xn += f1 * (xi - old[d]);
-          else if (mode == 6)
-            xn += f1 * (xi - f0 * bv * av);
-          else if (mode == 4 || mode == 5)
-            xn += f1 * xi;
-          out[d] = xn;
-        }
+        out[d] = cheb_point(mode, x, old, d, ident, sum, a[d], dinv[d], f0, f1, f2);
     }
   }
 
@@ -337,15 +335,7 @@ namespace mgx
             }
           v[dof] = sum;
         }
-      const T xi = mode == 5 ? f0 * dinv[dof] * b[dof] : x[dof];
-      T       xn = xi + f2 * dinv[dof] * (b[dof] - (ident ? xi : sum));
-      if (mode == 2)
-        xn += f1 * (xi - old[dof]);
-      else if (mode == 6)
-        xn += f1 * (xi - f0 * dinv[dof] * b[dof]);
-      else if (mode == 4 || mode == 5)
-        xn += f1 * xi;
-      out[dof] = xn;
+      out[dof] = cheb_point(mode, x, old, dof, ident, sum, b[dof], dinv[dof], f0, f1, f2);
     }
   }
 
@@ -624,18 +614,18 @@ namespace mgx
                                          idx_dev, val_dev, count));
   }
 
-  void launch_cheb_update(hipStream_t s, int number, int mode, void *x, void *x_old, const void *b,
+  void launch_cheb_update(hipStream_t s, int number, ChebUpdate mode, void *x, void *x_old, const void *b,
                           const void *t, const void *dinv, double f1, double f2, size_t n)
   {
     if (n == 0)
       return;
     const dim3 g = stream_grid(n);
     BY_NUMBER(
-      number, if (mode == 0) hipLaunchKernelGGL((k_cheb_update<T, 0>), g, dim3(256), 0, s, (T *)x, (T *)x_old,
+      number, if (mode == kUpdateStart) hipLaunchKernelGGL((k_cheb_update<T, kUpdateStart>), g, dim3(256), 0, s, (T *)x, (T *)x_old,
                                                 (const T *)b, (const T *)t, (const T *)dinv, (T)f1, (T)f2, n);
-      else if (mode == 1) hipLaunchKernelGGL((k_cheb_update<T, 1>), g, dim3(256), 0, s, (T *)x, (T *)x_old,
+      else if (mode == kUpdateFirst) hipLaunchKernelGGL((k_cheb_update<T, kUpdateFirst>), g, dim3(256), 0, s, (T *)x, (T *)x_old,
                                              (const T *)b, (const T *)t, (const T *)dinv, (T)f1, (T)f2, n);
-      else hipLaunchKernelGGL((k_cheb_update<T, 2>), g, dim3(256), 0, s, (T *)x, (T *)x_old, (const T *)b,
+      else hipLaunchKernelGGL((k_cheb_update<T, kUpdateThreeTerm>), g, dim3(256), 0, s, (T *)x, (T *)x_old, (const T *)b,
                               (const T *)t, (const T *)dinv, (T)f1, (T)f2, n));
   }
 
@@ -647,7 +637,7 @@ namespace mgx
                                          (const T *)dinv, (T)f2, n));
   }
 
-  void launch_cheb_constrained(hipStream_t s, int number, int mode, const void *x, void *out, const void *b,
+  void launch_cheb_constrained(hipStream_t s, int number, BrickMode mode, const void *x, void *out, const void *b,
                                const void *dinv, double f1, double f2, const uint32_t *list, uint32_t count,
                                const void *ax, const void *old, double f0)
   {
@@ -656,8 +646,8 @@ namespace mgx
     if (!old)
       old = out;
     if (!x)
-      x = b; // mode 5 never reads it
-    BY_NUMBER(number, hipLaunchKernelGGL((k_cheb_constrained<T>), stream_grid(count), dim3(256), 0, s, mode,
+      x = b; // kChebInit never reads it
+    BY_NUMBER(number, hipLaunchKernelGGL((k_cheb_constrained<T>), stream_grid(count), dim3(256), 0, s, (int)mode,
                                          (const T *)x, (T *)out, (const T *)b, (const T *)dinv, (T)f1, (T)f2, list,
                                          count, (const T *)ax, (const T *)old, (T)f0));
   }
@@ -690,23 +680,20 @@ namespace mgx
                                          (T *)out, (const T *)b, (const T *)dinv, (T)f2, (const T *)ax));
   }
 
-  void launch_surf_finish(hipStream_t s, const OperatorData &op, int mode, uint32_t first, uint32_t count, void *carrier,
-                          const void *x, void *out, const void *a, const void *dinv, const void *old, double f1, double f2,
-                          double f0, const uint32_t *constrained, uint32_t n_constrained, const FreeSchedule *schedule)
+  void launch_surf_finish(hipStream_t s, const OperatorData &op, const BrickLaunch &launch, uint32_t first, uint32_t count,
+                          const uint32_t *constrained, uint32_t n_constrained, const FreeSchedule *schedule)
   {
-    if (mode < 2)
+    if (!is_cheb_mode(launch.mode))
       n_constrained = 0; // the identity rows of the plain and residual forms are the caller's
     if (count + n_constrained == 0)
       return;
     const FreeSchedule &bd = schedule ? *schedule : op.bricks.fr;
-    if (!old)
-      old = out;
-    if (!x)
-      x = a; // mode 5 never reads it
-    BY_NUMBER(op.number, hipLaunchKernelGGL((k_surf_finish<T>), stream_grid((size_t)count + n_constrained), dim3(256), 0, s, mode,
-                                            (const T *)bd.priv, bd.surf_dof, bd.surf_start, bd.surf_pos, first, count,
-                                            bd.n_surf_shared, (T *)carrier, (const T *)x, (T *)out, (const T *)a,
-                                            (const T *)dinv, (const T *)old, (T)f1, (T)f2, (T)f0, constrained, n_constrained));
+    const BrickLaunch   l  = launch.resolved();
+    BY_NUMBER(op.number, hipLaunchKernelGGL((k_surf_finish<T>), stream_grid((size_t)count + n_constrained), dim3(256), 0, s,
+                                            (int)l.mode, (const T *)bd.priv, bd.surf_dof, bd.surf_start, bd.surf_pos, first, count,
+                                            bd.n_surf_shared, (T *)l.carrier, (const T *)l.src, (T *)l.out, (const T *)l.rhs,
+                                            (const T *)l.dinv, (const T *)l.old, (T)l.f1, (T)l.f2, (T)l.f0, constrained,
+                                            n_constrained));
   }
 
   // dst[i] = 0 for i < n_head, dst[i] = src[i] behind: the zeroing before a cell loop that scatters
@@ -783,18 +770,19 @@ namespace mgx
 
   void launch_unpack_ordered_cheb(hipStream_t s, int number, void *const *recv, int n_neighbors, void *v,
                                   const uint32_t *shared, const uint32_t *csr_start, const uint8_t *csr_k,
-                                  const uint32_t *csr_pos, uint32_t n_shared, const ChebList &c)
+                                  const uint32_t *csr_pos, uint32_t n_shared, const BrickLaunch &post,
+                                  const uint32_t *constrained, uint32_t n_constrained)
   {
-    if (n_shared + c.n_constrained == 0)
+    if (n_shared + n_constrained == 0)
       return;
     ExchangePtrs p{};
     for (int k = 0; k < n_neighbors; ++k)
       p.buf[k] = recv[k];
-    const void *old = c.old ? c.old : c.out, *x = c.x ? c.x : c.b; // mode 5 never reads x
-    BY_NUMBER(number, hipLaunchKernelGGL((k_unpack_ordered_cheb<T>), stream_grid((size_t)n_shared + c.n_constrained), dim3(256), 0,
-                                         s, p, (T *)v, shared, csr_start, csr_k, csr_pos, n_shared, c.mode, (const T *)x,
-                                         (T *)c.out, (const T *)c.b, (const T *)c.dinv, (const T *)old, (T)c.f1, (T)c.f2,
-                                         (T)c.f0, c.constrained, c.n_constrained));
+    const BrickLaunch c = post.resolved();
+    BY_NUMBER(number, hipLaunchKernelGGL((k_unpack_ordered_cheb<T>), stream_grid((size_t)n_shared + n_constrained), dim3(256), 0,
+                                         s, p, (T *)v, shared, csr_start, csr_k, csr_pos, n_shared, (int)c.mode, (const T *)c.src,
+                                         (T *)c.out, (const T *)c.rhs, (const T *)c.dinv, (const T *)c.old, (T)c.f1, (T)c.f2,
+                                         (T)c.f0, constrained, n_constrained));
   }
 
   void launch_unpack_add(hipStream_t s, int number, void *v, const void *buf, const uint32_t *list, uint32_t count)
