@@ -58,6 +58,10 @@ const char *mgx_version(void);
 /* 1 if the library was built with the round-1 cell-by-cell brick kernels (make crosscheck: the
  * cross-check of the macro-element kernel, context options "cells_form" / "brick_wide_max") */
 int mgx_has_cells_form(void);
+/* diagnostic: device allocations that library objects and the temporaries of running calls hold at the moment, over
+ * all contexts of the process (mgx_malloc buffers are the caller's and are not counted).  Back at its earlier value
+ * once everything created in between has been destroyed. */
+int64_t mgx_live_device_allocations(void);
 
 /* ---- context: device + stream (replaces MPI_InitFinalize / the implicit host execution
  * context, poisson_cube/program.cc:664) ---- */

@@ -96,6 +96,7 @@ SIGNATURES = {
     "mgx_context_create": (C.c_int, [C.POINTER(vp), C.c_int]),
     "mgx_context_set_option": (C.c_int, [vp, C.c_char_p, C.c_double]),
     "mgx_has_cells_form": (C.c_int, []),
+    "mgx_live_device_allocations": (C.c_int64, []),
     "mgx_context_destroy": (C.c_int, [vp]),
     "mgx_sync": (C.c_int, [vp]),
     "mgx_device_memory_info": (C.c_int, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

@@ -4,6 +4,7 @@
 // semantics follow SURVEY.md 8a rows R, S, T and Appendix D.
 #include "../../include/mgx.h"
 #include "mgx_bricks.hpp"
+#include "mgx_device_memory.hpp"
 #include "mgx_internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -35,33 +36,6 @@ namespace
     return code;
   }
 
-#define MGX_HIP(call)                                                                               \
-  do                                                                                                \
-    {                                                                                               \
-      hipError_t e_ = (call);                                                                       \
-      if (e_ != hipSuccess)                                                                         \
-        return fail(MGX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + \
-                                   std::to_string(__LINE__) + ")");                                 \
-    }                                                                                               \
-  while (0)
-
-#define MGX_TRY(call)     \
-  do                      \
-    {                     \
-      int s_ = (call);    \
-      if (s_ != MGX_OK)   \
-        return s_;        \
-    }                     \
-  while (0)
-
-#define MGX_REQUIRE(cond, msg)                        \
-  do                                                  \
-    {                                                 \
-      if (!(cond))                                    \
-        return fail(MGX_ERR_INVALID_ARGUMENT, (msg)); \
-    }                                                 \
-  while (0)
-
   inline size_t number_size(int number) { return number == MGX_F64 ? 8 : 4; }
 
   // MGX_TRACE=1 prints the host-side control flow to stderr (debugging aid); set by the first
@@ -90,6 +64,7 @@ int mgx::report_error(int code, const char *message) { return fail(code, message
 #define MGX_CELLS_FORM 0
 #endif
 extern "C" int mgx_has_cells_form(void) { return MGX_CELLS_FORM; }
+extern "C" int64_t mgx_live_device_allocations(void) { return mgx::live_device_allocations().load(); }
 
 mgx::Tunables mgx::Tunables::from_environment()
 {
@@ -182,7 +157,6 @@ struct ExchangePlan
   std::vector<uint32_t>  count;
   std::vector<uint32_t *> index_dev;
   std::vector<void *>    send, recv;
-  std::vector<uint8_t>   owns_buffers;
   uint32_t              *shared_dev = nullptr, *not_owned_dev = nullptr;
   uint32_t               n_shared = 0, n_not_owned = 0;
   void                  *own_buf = nullptr;
@@ -252,6 +226,7 @@ struct mgx_context_s
 {
   int         device = 0;
   Tunables    tun; // environment switches, read once in mgx_context_create
+  DeviceArena mem{"mgx_context"}; // partial_dev, result_dev, ar_dev
   hipStream_t stream = nullptr;
   bool        borrowed_stream = false; // the stream of the context of the decomposed hierarchy above (agglomerated levels)
   // interface exchange overlapped with the interior bricks: side stream and the two events that
@@ -283,6 +258,7 @@ struct mgx_context_s
 struct mgx_operator_s
 {
   mgx_context_t ctx = nullptr;
+  DeviceArena   mem{"mgx_operator"}; // every device buffer of the operator and of its exchange plan
   OperatorData  d;
   double        S[kMaxN * kMaxN], D[kMaxN * kMaxN], w[kMaxN];
   bool          has_diag = false;
@@ -307,6 +283,7 @@ struct mgx_operator_s
 struct mgx_smoother_s
 {
   mgx_operator_t    op = nullptr;
+  DeviceArena       mem{"mgx_smoother"};
   mgx_smoother_info info{};
   void             *x_old = nullptr, *tmp = nullptr;
   void             *x_old2 = nullptr; // third iterate buffer (odd number of fused iterations in step())
@@ -336,6 +313,7 @@ struct mgx_smoother_s
 struct mgx_transfer_s
 {
   mgx_operator_t coarse = nullptr, fine = nullptr;
+  DeviceArena    mem{"mgx_transfer"};
   TransferData   d;
   void          *scratch = nullptr; // decomposed mesh: coarse-level scratch of restrict_and_add
   // mgx_interpolate_to_coarse (built at its first call): 1D interpolation matrix [(2p+1)(p+1)] in the number type and
@@ -347,6 +325,7 @@ struct mgx_transfer_s
 struct mgx_solver_s
 {
   mgx_context_t               ctx = nullptr;
+  DeviceArena                 mem{"mgx_solver"};
   int                         n_levels = 0, degree = 0, n_cycles = 1, vnumber = MGX_F64;
   std::vector<mgx_operator_t> matrix, matrix_dp;
   std::vector<mgx_transfer_t> transfer, transfer_dp;
@@ -906,15 +885,15 @@ int mgx_context_create(mgx_context_t *out, int device)
     return fail(MGX_ERR_NO_DEVICE, "mgx_context_create: no HIP device available (there is no CPU fallback)");
   MGX_REQUIRE(device >= 0 && device < count, "mgx_context_create: device index out of range");
   MGX_HIP(hipSetDevice(device));
-  auto ctx    = new mgx_context_s;
+  std::unique_ptr<mgx_context_s, int (*)(mgx_context_t)> ctx(new mgx_context_s, mgx_context_destroy);
   ctx->device = device;
   ctx->tun    = Tunables::from_environment();
   g_trace     = g_trace || ctx->tun.trace;
   MGX_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-  MGX_HIP(hipMalloc((void **)&ctx->partial_dev, sizeof(double) * kDotBlocks));
-  MGX_HIP(hipMalloc((void **)&ctx->result_dev, sizeof(double) * 4));
+  MGX_TRY(ctx->mem.alloc(&ctx->partial_dev, kDotBlocks));
+  MGX_TRY(ctx->mem.alloc(&ctx->result_dev, 4));
   MGX_HIP(hipHostMalloc((void **)&ctx->result_host, sizeof(double) * 4));
-  *out = ctx;
+  *out = ctx.release();
   return MGX_OK;
 }
 
@@ -935,10 +914,7 @@ int mgx_context_destroy(mgx_context_t ctx)
     (void)hipDeviceSynchronize(); // the stream's owner may be gone already
   else
     (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(ctx->partial_dev);
-  (void)hipFree(ctx->result_dev);
   (void)hipHostFree(ctx->result_host);
-  (void)hipFree(ctx->ar_dev);
   if (ctx->nccl)
     (void)rccl_api().CommDestroy(ctx->nccl);
   for (auto *pool : {&ctx->ev_pool, &ctx->ev_used})
@@ -1018,7 +994,7 @@ int mgx_context_set_rccl(mgx_context_t ctx, int rank, int size, const void *id12
       ctx->nccl = nullptr;
       return fail(MGX_ERR_HIP, std::string("ncclCommInitRank failed: ") + R.GetErrorString(r));
     }
-  MGX_HIP(hipMalloc((void **)&ctx->ar_dev, 8 * sizeof(double)));
+  MGX_TRY(ctx->mem.alloc(&ctx->ar_dev, 8));
   ctx->rccl_rank = rank;
   ctx->rccl_size = size;
   ctx->has_comm  = size > 1 || ctx->tun.rccl_selftest;
@@ -1205,36 +1181,63 @@ int mgx_set_entries(mgx_context_t ctx, int number, void *v, const uint32_t *idx_
   MGX_REQUIRE(ctx && (count == 0 || (v && idx_host && val_host)), "mgx_set_entries: null argument");
   if (count == 0)
     return MGX_OK;
+  DeviceArena tmp("mgx_set_entries");
   uint32_t *idx_dev = nullptr;
   double   *val_dev = nullptr;
-  MGX_HIP(hipMalloc((void **)&idx_dev, sizeof(uint32_t) * count));
-  MGX_HIP(hipMalloc((void **)&val_dev, sizeof(double) * count));
+  MGX_TRY(tmp.alloc(&idx_dev, count));
+  MGX_TRY(tmp.alloc(&val_dev, count));
   MGX_HIP(hipMemcpyAsync(idx_dev, idx_host, sizeof(uint32_t) * count, hipMemcpyHostToDevice, ctx->stream));
   MGX_HIP(hipMemcpyAsync(val_dev, val_host, sizeof(double) * count, hipMemcpyHostToDevice, ctx->stream));
   launch_scatter_values(ctx->stream, number, v, idx_dev, val_dev, count);
-  MGX_HIP(hipStreamSynchronize(ctx->stream));
-  MGX_HIP(hipFree(idx_dev));
-  MGX_HIP(hipFree(val_dev));
+  MGX_HIP(hipStreamSynchronize(ctx->stream)); // (the host arrays are the caller's, in flight until here)
   return MGX_OK;
 }
 
 /* ------------------------------------------------------------------------------------------
  * LaplaceOperator
  * ------------------------------------------------------------------------------------------ */
-int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_operator_t *out)
+} // extern "C"
+
+// The stages of mgx_operator_create, in the order it calls them.  Every device buffer goes to the operator's arena:
+// a stage that fails leaves nothing behind that mgx_operator_destroy would not free.
+namespace
 {
-  MGX_REQUIRE(ctx && desc && out, "mgx_operator_create: null argument");
-  MGX_REQUIRE(desc->degree >= 1 && desc->degree <= MGX_MAX_DEGREE, "mgx_operator_create: degree must be 1..9");
-  MGX_REQUIRE(desc->number == MGX_F32 || desc->number == MGX_F64, "mgx_operator_create: bad number type");
-  MGX_REQUIRE(desc->n_cells > 0 && desc->n_dofs > 0, "mgx_operator_create: empty level");
-  MGX_REQUIRE(desc->idx27 && desc->shape_values && desc->colloc_grad && desc->qweights,
-              "mgx_operator_create: missing table");
-  MGX_REQUIRE(desc->n_constrained == 0 || desc->constrained, "mgx_operator_create: missing constrained list");
-  const int    p = desc->degree, n = p + 1;
-  const size_t n_entries = 27 * (size_t)desc->n_cells;
-  // host-side validation of operand shapes before any kernel can touch them
+  constexpr size_t kAssemblyMaxEntries = (size_t)1 << 26; // ordered assembly up to this many local values per level
+
+  // DoFs on mesh entity e of a cell of degree p: e = (cz 3 + cy) 3 + cx with the codes 0 low side, 1 inside, 2 high
+  // side per direction (vertex 1, line p - 1, face (p - 1)^2, interior (p - 1)^3)
+  inline int entity_size(int e, int p)
   {
-    const uint32_t sizes[3] = {1u, (uint32_t)(p - 1), (uint32_t)((p - 1) * (p - 1))};
+    return (e % 3 == 1 ? p - 1 : 1) * ((e / 3) % 3 == 1 ? p - 1 : 1) * (e / 9 == 1 ? p - 1 : 1);
+  }
+
+  // G = D S: derivative of the nodal basis at the quadrature points, G[q n + i], accumulated in R
+  template <typename R>
+  void nodal_gradient(const mgx_operator_s &op, R *G)
+  {
+    const int n = op.d.p + 1;
+    for (int q = 0; q < n; ++q)
+      for (int i = 0; i < n; ++i)
+        {
+          R g = 0;
+          for (int r = 0; r < n; ++r)
+            g += (R)op.D[q * n + r] * op.S[r * n + i];
+          G[q * n + i] = g;
+        }
+  }
+
+  // host-side validation of operand shapes before any kernel can touch them
+  int validate_operator_desc(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_operator_t *out)
+  {
+    MGX_REQUIRE(ctx && desc && out, "mgx_operator_create: null argument");
+    MGX_REQUIRE(desc->degree >= 1 && desc->degree <= MGX_MAX_DEGREE, "mgx_operator_create: degree must be 1..9");
+    MGX_REQUIRE(desc->number == MGX_F32 || desc->number == MGX_F64, "mgx_operator_create: bad number type");
+    MGX_REQUIRE(desc->n_cells > 0 && desc->n_dofs > 0, "mgx_operator_create: empty level");
+    MGX_REQUIRE(desc->idx27 && desc->shape_values && desc->colloc_grad && desc->qweights,
+                "mgx_operator_create: missing table");
+    MGX_REQUIRE(desc->n_constrained == 0 || desc->constrained, "mgx_operator_create: missing constrained list");
+    const int    p         = desc->degree;
+    const size_t n_entries = 27 * (size_t)desc->n_cells;
     for (int pass = 0; pass < 2; ++pass)
       {
         const uint32_t *tab = pass == 0 ? desc->idx27 : desc->idx27_plain;
@@ -1245,24 +1248,28 @@ int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_op
             const uint32_t b = tab[i];
             if (b == MGX_INVALID_INDEX)
               continue;
-            const int e = (int)(i % 27), cx = e % 3, cy = (e / 3) % 3, cz = e / 9;
-            const int kind = (cx == 1) + (cy == 1) + (cz == 1);
-            uint32_t  len  = kind == 3 ? sizes[2] * (uint32_t)(p - 1) : sizes[kind];
-            if (kind == 0)
-              len = 1;
-            if ((uint64_t)b + len > desc->n_dofs)
+            if ((uint64_t)b + (uint32_t)entity_size((int)(i % 27), p) > desc->n_dofs)
               return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: compressed index out of range");
           }
       }
     for (uint32_t i = 0; i < desc->n_constrained; ++i)
       if (desc->constrained[i] >= desc->n_dofs)
         return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: constrained index out of range");
+    if (!desc->coef_q)
+      {
+        // the one coefficient tensor of an affine mesh (xx yy zz xy xz yz) must be positive definite
+        const double *c  = desc->coef;
+        const double  m2 = c[0] * c[1] - c[3] * c[3];
+        const double  m3 = c[0] * (c[1] * c[2] - c[5] * c[5]) - c[3] * (c[3] * c[2] - c[5] * c[4]) +
+                          c[4] * (c[3] * c[5] - c[1] * c[4]);
+        MGX_REQUIRE(c[0] > 0 && m2 > 0 && m3 > 0, "mgx_operator_create: the coefficient tensor is not positive definite");
+      }
+    return MGX_OK;
   }
-  // failures below return through the destroy function: device buffers allocated so far are freed
-  std::unique_ptr<mgx_operator_s, int (*)(mgx_operator_t)> op(new mgx_operator_s, mgx_operator_destroy);
-  op->ctx          = ctx;
+
+  // are the constrained DoFs exactly [n_dofs - n_constrained, n_dofs)?  (any order inside the list)
+  bool constrained_are_last(const mgx_operator_desc *desc)
   {
-    // (any order inside the list)
     std::vector<uint8_t> seen(desc->n_constrained, 0);
     bool                 last = true;
     for (uint32_t i = 0; i < desc->n_constrained && last; ++i)
@@ -1272,408 +1279,328 @@ int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_op
         if (last)
           seen[c - (desc->n_dofs - desc->n_constrained)] = 1;
       }
-    op->constrained_last = last;
+    return last;
   }
-  OperatorData &d  = op->d;
-  d.p              = p;
-  d.number         = desc->number;
-  d.n_cells        = desc->n_cells;
-  d.n_dofs         = desc->n_dofs;
-  d.n_constrained  = desc->n_constrained;
-  for (int i = 0; i < 6; ++i)
-    d.coef[i] = desc->coef[i];
-  std::memcpy(op->S, desc->shape_values, sizeof(double) * n * n);
-  std::memcpy(op->D, desc->colloc_grad, sizeof(double) * n * n);
-  std::memcpy(op->w, desc->qweights, sizeof(double) * n);
-  MGX_HIP(hipSetDevice(ctx->device));
-  MGX_HIP(hipMalloc((void **)&d.idx27, sizeof(uint32_t) * n_entries));
-  MGX_HIP(hipMemcpy(d.idx27, desc->idx27, sizeof(uint32_t) * n_entries, hipMemcpyHostToDevice));
-  if (desc->idx27_plain)
-    {
-      MGX_HIP(hipMalloc((void **)&d.idx27_plain, sizeof(uint32_t) * n_entries));
-      MGX_HIP(hipMemcpy(d.idx27_plain, desc->idx27_plain, sizeof(uint32_t) * n_entries, hipMemcpyHostToDevice));
-    }
-  MGX_HIP(hipMalloc((void **)&d.constrained, sizeof(uint32_t) * (desc->n_constrained + 1)));
-  if (desc->n_constrained)
-    MGX_HIP(hipMemcpy(d.constrained, desc->constrained, sizeof(uint32_t) * desc->n_constrained,
-                      hipMemcpyHostToDevice));
-  // 1D mass and stiffness matrices of the separable form, M = S^T W S, K = S^T D^T W D S
-  double M1[kMaxN * kMaxN], K1[kMaxN * kMaxN];
+
+  // 1D tables of the element in the operator's number type (Basis1D<T>); decides d.separable
+  int upload_basis(mgx_operator_s &op)
   {
-    long double G[kMaxN * kMaxN]; // G = D S: derivative of the nodal basis at the quadrature points
-    for (int q = 0; q < n; ++q)
+    OperatorData &d = op.d;
+    const int     n = d.p + 1;
+    // 1D mass and stiffness matrices of the separable form, M = S^T W S, K = S^T D^T W D S
+    double M1[kMaxN * kMaxN], K1[kMaxN * kMaxN];
+    {
+      long double G[kMaxN * kMaxN];
+      nodal_gradient(op, G);
       for (int i = 0; i < n; ++i)
-        {
-          long double g = 0;
-          for (int r = 0; r < n; ++r)
-            g += (long double)op->D[q * n + r] * op->S[r * n + i];
-          G[q * n + i] = g;
-        }
-    for (int i = 0; i < n; ++i)
-      for (int j = 0; j < n; ++j)
-        {
-          long double m = 0, k = 0;
-          for (int q = 0; q < n; ++q)
-            {
-              m += (long double)op->w[q] * op->S[q * n + i] * op->S[q * n + j];
-              k += (long double)op->w[q] * G[q * n + i] * G[q * n + j];
-            }
-          M1[i * n + j] = (double)m;
-          K1[i * n + j] = (double)k;
-        }
-  }
-  auto fill_basis = [&](auto &b) {
-    using T = std::remove_reference_t<decltype(b.S[0])>;
-    for (int i = 0; i < n * n; ++i)
-      {
-        b.S[i] = (T)op->S[i];
-        b.D[i] = (T)op->D[i];
-      }
-    for (int i = 0; i < n; ++i)
-      b.w[i] = (T)op->w[i];
-    const int H = n / 2;
-    auto      eo = [&](auto &E, const double *A) {
-      for (int a = 0; a < H; ++a)
-        {
-          for (int i = 0; i < H; ++i)
-            {
-              E.ee[a * H + i] = (T)(0.5 * (A[a * n + i] + A[a * n + n - 1 - i]));
-              E.eo[a * H + i] = (T)(0.5 * (A[a * n + i] - A[a * n + n - 1 - i]));
-            }
-          E.mc[a] = (n % 2) ? (T)A[a * n + H] : (T)0;
-        }
-      E.mhh = (n % 2) ? (T)A[H * n + H] : (T)0;
-    };
-    eo(b.mass, M1);
-    eo(b.lapl, K1);
-  };
-  // the separable fast path needs the symmetry A[a][b] = A[n-1-a][n-1-b] of M and K (true for
-  // any symmetric node/quadrature set); MGX_GENERAL_KERNEL=1 forces the quadrature-point form
-  const Tunables &tun = ctx->tun;
-  if (!desc->coef_q)
-    {
-      // the one coefficient tensor of an affine mesh (xx yy zz xy xz yz) must be positive definite
-      const double *c  = desc->coef;
-      const double  m2 = c[0] * c[1] - c[3] * c[3];
-      const double  m3 = c[0] * (c[1] * c[2] - c[5] * c[5]) - c[3] * (c[3] * c[2] - c[5] * c[4]) +
-                        c[4] * (c[3] * c[5] - c[1] * c[4]);
-      MGX_REQUIRE(c[0] > 0 && m2 > 0 && m3 > 0, "mgx_operator_create: the coefficient tensor is not positive definite");
-    }
-  d.full_tensor      = !desc->coef_q && (desc->coef[3] != 0. || desc->coef[4] != 0. || desc->coef[5] != 0.);
-  const bool general = d.full_tensor || desc->coef_q; // quadrature-point operation with the full tensor
-  d.separable        = !tun.general_kernel && !general;
-  d.cells_form       = tun.cells_form;
-  d.wide_max         = tun.wide_max;
-  d.macro_wg_x16     = tun.macro_wg_x16;
-  d.n_cus            = context_cus(ctx);
-  d.macro_v2         = !tun.no_macro_v2;
-  for (int a = 0; a < n && d.separable; ++a)
-    for (int bb = 0; bb < n; ++bb)
-      if (std::fabs(M1[a * n + bb] - M1[(n - 1 - a) * n + n - 1 - bb]) > 1e-12 ||
-          std::fabs(K1[a * n + bb] - K1[(n - 1 - a) * n + n - 1 - bb]) > 1e-10 * std::fabs(K1[0]))
-        d.separable = false;
-  if (d.number == MGX_F64)
-    {
-      Basis1D<double> b{};
-      fill_basis(b);
-      MGX_HIP(hipMalloc(&d.basis, sizeof(b)));
-      MGX_HIP(hipMemcpy(d.basis, &b, sizeof(b), hipMemcpyHostToDevice));
-    }
-  else
-    {
-      Basis1D<float> b{};
-      fill_basis(b);
-      MGX_HIP(hipMalloc(&d.basis, sizeof(b)));
-      MGX_HIP(hipMemcpy(d.basis, &b, sizeof(b), hipMemcpyHostToDevice));
-    }
-  MGX_HIP(hipMalloc(&d.inv_diag, number_size(d.number) * d.n_dofs));
-  if (general)
-    {
-      // G = D S for the diagonal of the general cell matrix; the per-point coefficient in the
-      // operator's number type
-      std::vector<double> G((size_t)n * n);
-      for (int q = 0; q < n; ++q)
-        for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j)
           {
-            double g = 0;
-            for (int r = 0; r < n; ++r)
-              g += op->D[q * n + r] * op->S[r * n + i];
-            G[q * n + i] = g;
+            long double m = 0, k = 0;
+            for (int q = 0; q < n; ++q)
+              {
+                m += (long double)op.w[q] * op.S[q * n + i] * op.S[q * n + j];
+                k += (long double)op.w[q] * G[q * n + i] * G[q * n + j];
+              }
+            M1[i * n + j] = (double)m;
+            K1[i * n + j] = (double)k;
           }
-      const size_t nq = desc->coef_q ? (size_t)desc->n_cells * 6 * n * n * n : 0;
-      if (d.number == MGX_F64)
-        {
-          MGX_HIP(hipMalloc(&d.grad_1d, sizeof(double) * n * n));
-          MGX_HIP(hipMemcpy(d.grad_1d, G.data(), sizeof(double) * n * n, hipMemcpyHostToDevice));
-          if (nq)
-            {
-              MGX_HIP(hipMalloc(&d.coef_q, sizeof(double) * nq));
-              MGX_HIP(hipMemcpy(d.coef_q, desc->coef_q, sizeof(double) * nq, hipMemcpyHostToDevice));
-            }
-        }
-      else
-        {
-          std::vector<float> Gf(G.begin(), G.end());
-          MGX_HIP(hipMalloc(&d.grad_1d, sizeof(float) * n * n));
-          MGX_HIP(hipMemcpy(d.grad_1d, Gf.data(), sizeof(float) * n * n, hipMemcpyHostToDevice));
-          if (nq)
-            {
-              std::vector<float> cf(desc->coef_q, desc->coef_q + nq);
-              MGX_HIP(hipMalloc(&d.coef_q, sizeof(float) * nq));
-              MGX_HIP(hipMemcpy(d.coef_q, cf.data(), sizeof(float) * nq, hipMemcpyHostToDevice));
-            }
-        }
     }
-  constexpr size_t kAssemblyMaxEntries = (size_t)1 << 26; // ordered assembly up to this many local values per level
-  if (general && (desc->n_cells >= tun.cell_colour_min || (size_t)n * n * n * desc->n_cells > kAssemblyMaxEntries))
-    {
-      // Cell colouring for the general branch: greedy over the cells in their order, two cells
-      // conflict if they share a mesh entity that carries DoFs (its first DoF is the key).  On the
-      // structured meshes of the provider this gives the 8 parity classes.  More than 32 colours:
-      // keep the single launch with atomics.
-      const int             pm1 = p - 1;
-      std::vector<uint32_t> used(desc->n_dofs, 0u);
-      std::vector<uint8_t>  colour(desc->n_cells, 0);
-      uint32_t              count[33] = {0};
-      int                   n_colours = 0;
-      bool                  ok        = true;
-      for (uint32_t c = 0; c < desc->n_cells && ok; ++c)
+    auto fill_basis = [&](auto &b) {
+      using T = std::remove_reference_t<decltype(b.S[0])>;
+      for (int i = 0; i < n * n; ++i)
         {
-          const uint32_t *ix   = desc->idx27 + 27 * (size_t)c;
-          uint32_t        mask = 0;
-          for (int e = 0; e < 27; ++e)
-            {
-              const int inner = (e % 3 == 1) + ((e / 3) % 3 == 1) + (e / 9 == 1);
-              if (inner == 3 || (inner > 0 && pm1 == 0) || ix[e] == MGX_INVALID_INDEX)
-                continue;
-              mask |= used[ix[e]];
-            }
-          int col = 0;
-          while (col < 32 && (mask >> col) & 1u)
-            ++col;
-          if (col == 32)
-            {
-              ok = false;
-              break;
-            }
-          colour[c] = (uint8_t)col;
-          ++count[col];
-          n_colours = std::max(n_colours, col + 1);
-          for (int e = 0; e < 27; ++e)
-            {
-              const int inner = (e % 3 == 1) + ((e / 3) % 3 == 1) + (e / 9 == 1);
-              if (inner == 3 || (inner > 0 && pm1 == 0) || ix[e] == MGX_INVALID_INDEX)
-                continue;
-              used[ix[e]] |= 1u << col;
-            }
+          b.S[i] = (T)op.S[i];
+          b.D[i] = (T)op.D[i];
         }
-      if (ok)
-        {
-          std::vector<uint32_t> order(desc->n_cells), fill(33, 0);
-          d.cell_colour_start[0] = 0;
-          for (int k = 0; k < n_colours; ++k)
-            d.cell_colour_start[k + 1] = d.cell_colour_start[k] + count[k];
-          for (int k = 0; k < n_colours; ++k)
-            fill[k] = d.cell_colour_start[k];
-          for (uint32_t c = 0; c < desc->n_cells; ++c)
-            order[fill[colour[c]]++] = c;
-          d.n_cell_colours = n_colours;
-          MGX_HIP(hipMalloc((void **)&d.cell_order, sizeof(uint32_t) * (size_t)desc->n_cells));
-          MGX_HIP(hipMemcpy(d.cell_order, order.data(), sizeof(uint32_t) * (size_t)desc->n_cells, hipMemcpyHostToDevice));
-          MGX_TRACE("operator_create: general branch, %u cells in %d colours", desc->n_cells, n_colours);
-        }
-    }
+      for (int i = 0; i < n; ++i)
+        b.w[i] = (T)op.w[i];
+      const int H = n / 2;
+      auto      eo = [&](auto &E, const double *A) {
+        for (int a = 0; a < H; ++a)
+          {
+            for (int i = 0; i < H; ++i)
+              {
+                E.ee[a * H + i] = (T)(0.5 * (A[a * n + i] + A[a * n + n - 1 - i]));
+                E.eo[a * H + i] = (T)(0.5 * (A[a * n + i] - A[a * n + n - 1 - i]));
+              }
+            E.mc[a] = (n % 2) ? (T)A[a * n + H] : (T)0;
+          }
+        E.mhh = (n % 2) ? (T)A[H * n + H] : (T)0;
+      };
+      eo(b.mass, M1);
+      eo(b.lapl, K1);
+    };
+    // the separable fast path needs the symmetry A[a][b] = A[n-1-a][n-1-b] of M and K (true for
+    // any symmetric node/quadrature set); MGX_GENERAL_KERNEL=1 forces the quadrature-point form
+    for (int a = 0; a < n && d.separable; ++a)
+      for (int bb = 0; bb < n; ++bb)
+        if (std::fabs(M1[a * n + bb] - M1[(n - 1 - a) * n + n - 1 - bb]) > 1e-12 ||
+            std::fabs(K1[a * n + bb] - K1[(n - 1 - a) * n + n - 1 - bb]) > 1e-10 * std::fabs(K1[0]))
+          d.separable = false;
+    if (d.number == MGX_F64)
+      {
+        Basis1D<double> b{};
+        fill_basis(b);
+        return op.mem.upload_bytes(&d.basis, &b, sizeof(b));
+      }
+    Basis1D<float> b{};
+    fill_basis(b);
+    return op.mem.upload_bytes(&d.basis, &b, sizeof(b));
+  }
+
+  // general branch: G = D S for the diagonal of the general cell matrix; the per-point coefficient in the
+  // operator's number type
+  int upload_general_tables(mgx_operator_s &op, const mgx_operator_desc *desc)
+  {
+    OperatorData       &d = op.d;
+    const int           n = d.p + 1;
+    std::vector<double> G((size_t)n * n);
+    nodal_gradient(op, G.data());
+    MGX_TRY(op.mem.upload_as(d.number, &d.grad_1d, G.data(), G.size()));
+    if (desc->coef_q)
+      MGX_TRY(op.mem.upload_as(d.number, &d.coef_q, desc->coef_q, (size_t)desc->n_cells * 6 * n * n * n));
+    return MGX_OK;
+  }
+
+  // Cell colouring for the general branch: greedy over the cells in their order, two cells
+  // conflict if they share a mesh entity that carries DoFs (its first DoF is the key).  On the
+  // structured meshes of the provider this gives the 8 parity classes.  More than 32 colours:
+  // keep the single launch with atomics.
+  int colour_cells(mgx_operator_s &op, const mgx_operator_desc *desc)
+  {
+    OperatorData         &d = op.d;
+    const int             p = d.p;
+    std::vector<uint32_t> used(desc->n_dofs, 0u);
+    std::vector<uint8_t>  colour(desc->n_cells, 0);
+    uint32_t              count[33] = {0};
+    int                   n_colours = 0;
+    // the entities whose first DoF is a key: all that carry DoFs but the cell's interior
+    auto is_key = [p](const uint32_t *ix, int e) { return e != 13 && entity_size(e, p) != 0 && ix[e] != MGX_INVALID_INDEX; };
+    for (uint32_t c = 0; c < desc->n_cells; ++c)
+      {
+        const uint32_t *ix   = desc->idx27 + 27 * (size_t)c;
+        uint32_t        mask = 0;
+        for (int e = 0; e < 27; ++e)
+          if (is_key(ix, e))
+            mask |= used[ix[e]];
+        int col = 0;
+        while (col < 32 && (mask >> col) & 1u)
+          ++col;
+        if (col == 32)
+          return MGX_OK;
+        colour[c] = (uint8_t)col;
+        ++count[col];
+        n_colours = std::max(n_colours, col + 1);
+        for (int e = 0; e < 27; ++e)
+          if (is_key(ix, e))
+            used[ix[e]] |= 1u << col;
+      }
+    std::vector<uint32_t> order(desc->n_cells), fill(33, 0);
+    d.cell_colour_start[0] = 0;
+    for (int k = 0; k < n_colours; ++k)
+      d.cell_colour_start[k + 1] = d.cell_colour_start[k] + count[k];
+    for (int k = 0; k < n_colours; ++k)
+      fill[k] = d.cell_colour_start[k];
+    for (uint32_t c = 0; c < desc->n_cells; ++c)
+      order[fill[colour[c]]++] = c;
+    d.n_cell_colours = n_colours;
+    MGX_TRY(op.mem.upload(&d.cell_order, order));
+    MGX_TRACE("operator_create: general branch, %u cells in %d colours", desc->n_cells, n_colours);
+    return MGX_OK;
+  }
+
+  // device tables of a reduced-colour schedule (bricks.fr and gbricks.fr); the counts of `fr` that differ between
+  // the two are the caller's
+  int upload_free_schedule(DeviceArena &mem, FreeSchedule &fr, FreeHost &fh, uint32_t n_bricks, int number)
+  {
+    fr.n_surf      = fh.n_surf;
+    fr.n_surf_dofs = (uint32_t)fh.surf_dof.size();
+    fh.surf_dof.push_back(0);
+    fh.surf_pos.push_back(0);
+    MGX_TRY(mem.upload(&fr.surf_off, fh.surf_off));
+    MGX_TRY(mem.upload(&fr.surf_dof, fh.surf_dof));
+    MGX_TRY(mem.upload(&fr.surf_start, fh.surf_start));
+    MGX_TRY(mem.upload(&fr.surf_pos, fh.surf_pos));
+    MGX_TRY(mem.alloc(&fr.priv, (size_t)n_bricks * fh.n_surf * number_size(number) + 16));
+    return mem.upload(&fr.ent, fh.ent);
+  }
+
   // brick schedule for the atomic-free cell loop (mgx_brick.hip); MGX_NO_BRICKS=1 keeps the
   // per-cell kernel (A/B measurements)
-  // (builds without the cell-by-cell cross-check kernels schedule bricks only where the macro-element
-  // kernel runs: separable operator, vector below the 4 GB of a buffer descriptor)
-  const bool macro_covers = d.separable && (uint64_t)desc->n_dofs * number_size(d.number) < 0xFFFFFFF0ull;
-  if (!tun.no_bricks && !general && (MGX_CELLS_FORM ? (p <= 4 || d.separable) : macro_covers))
-    {
-      BrickHost   bh;
-      std::string why;
-      const mgx_exchange_desc *ex = desc->exchange;
-      // The eight colour launches of a brick loop cost about 80 us however small the level is; below
-      // that the per-cell kernel (all cells of the level in one launch, atomic scatter) is faster.
-      // Measured cross-over with the macro-element kernel on MI355X (tools/time_matvec.py): p = 4 and
-      // p = 8 between 216 and 512 bricks (512: 0.082 vs 0.098 ms, 0.090 vs 0.134 ms), p = 2 between 512
-      // and 1728 bricks (512: 0.042 vs 0.028 ms).  MGX_BRICK_MIN overrides the threshold as given.
-      const uint32_t brick_min   = tun.brick_min_from_env ? tun.brick_min : (p <= 2 ? 2 * tun.brick_min : tun.brick_min);
-      const uint32_t brick_cells = p <= 4 ? 64u : 8u;
-      // Decomposed mesh: from this many bricks per rank on, the bricks on the rank interface are
-      // launched first and the exchange overlaps with the interior bricks.  The split costs one
-      // small (latency-bound) launch per colour; DESIGN.md 6 has the measured break-even.
-      const uint32_t overlap_min = tun.overlap_min;
-      if (desc->n_dofs >= 0x3FFFFFFFu)
+  int build_brick_schedule(mgx_operator_s &op, const mgx_operator_desc *desc, const Tunables &tun)
+  {
+    OperatorData &d = op.d;
+    const int     p = d.p;
+    BrickHost   bh;
+    std::string why;
+    const mgx_exchange_desc *ex = desc->exchange;
+    // The eight colour launches of a brick loop cost about 80 us however small the level is; below
+    // that the per-cell kernel (all cells of the level in one launch, atomic scatter) is faster.
+    // Measured cross-over with the macro-element kernel on MI355X (tools/time_matvec.py): p = 4 and
+    // p = 8 between 216 and 512 bricks (512: 0.082 vs 0.098 ms, 0.090 vs 0.134 ms), p = 2 between 512
+    // and 1728 bricks (512: 0.042 vs 0.028 ms).  MGX_BRICK_MIN overrides the threshold as given.
+    const uint32_t brick_min   = tun.brick_min_from_env ? tun.brick_min : (p <= 2 ? 2 * tun.brick_min : tun.brick_min);
+    const uint32_t brick_cells = p <= 4 ? 64u : 8u;
+    // Decomposed mesh: from this many bricks per rank on, the bricks on the rank interface are
+    // launched first and the exchange overlaps with the interior bricks.  The split costs one
+    // small (latency-bound) launch per colour; DESIGN.md 6 has the measured break-even.
+    const uint32_t overlap_min = tun.overlap_min;
+    if (desc->n_dofs >= 0x3FFFFFFFu)
+      {
         MGX_TRACE("operator_create: per-cell kernel (%u DoFs do not fit the 30-bit entity index)", desc->n_dofs);
-      else if (desc->n_cells / brick_cells < brick_min)
+        return MGX_OK;
+      }
+    if (desc->n_cells / brick_cells < brick_min)
+      {
         MGX_TRACE("operator_create: per-cell kernel (%u bricks < %u)", desc->n_cells / brick_cells, brick_min);
-      else if (build_bricks(p, desc->n_cells, desc->n_dofs, desc->idx27, desc->idx27_plain, desc->brick_colour,
-                            ex ? ex->shared : nullptr, ex ? ex->n_shared : 0,
-                            ex && desc->n_cells / brick_cells >= overlap_min, bh, why))
-        {
-          BrickData &b = d.bricks;
-          b.n_bricks   = bh.n_bricks;
-          b.n_colours  = bh.n_colours;
-          b.n_iface_groups = bh.n_iface_groups;
-          b.order      = bh.order;
-          for (int c = 0; c <= bh.n_colours; ++c)
-            b.colour_start[c] = bh.colour_start[c];
-          // device table word: bits 0..29 first DoF, bit 30 FIRST, bit 31 LAST (mgx_brick.hip)
-          for (size_t i = 0; i < bh.ent_base.size(); ++i)
-            if (bh.ent_base[i] != MGX_INVALID_INDEX)
-              bh.ent_base[i] |= (uint32_t)(bh.ent_flags[i] & 3u) << 30;
-          MGX_HIP(hipMalloc((void **)&b.ent_base, sizeof(uint32_t) * bh.ent_base.size()));
-          MGX_HIP(hipMemcpy(b.ent_base, bh.ent_base.data(), sizeof(uint32_t) * bh.ent_base.size(),
-                            hipMemcpyHostToDevice));
-          b.ent_flags = nullptr;
-          if (d.separable)
-            {
-              // write-out order of the macro-element kernel (mgx_macro.hip)
-              std::vector<uint32_t> map;
-              build_item_map(p, map);
-              MGX_HIP(hipMalloc((void **)&b.item_map, sizeof(uint32_t) * map.size()));
-              MGX_HIP(hipMemcpy(b.item_map, map.data(), sizeof(uint32_t) * map.size(), hipMemcpyHostToDevice));
-              {
-                // ... and of its second pipeline (mgx_macro2.hip): interior of the brick first
-                std::vector<uint32_t> map2;
-                build_item_map2(p, map2);
-                MGX_HIP(hipMalloc((void **)&b.item_map2, sizeof(uint32_t) * map2.size()));
-                MGX_HIP(hipMemcpy(b.item_map2, map2.data(), sizeof(uint32_t) * map2.size(), hipMemcpyHostToDevice));
-              }
-              // Reduced-colour schedule of the plain / residual / Chebyshev forms (mgx_macro.hip, FREE): one
-              // class (one launch per level) on levels with at most free_one_max bricks, two classes up to
-              // free_max_bricks
-              const int n_classes = b.n_bricks <= tun.free_one_max ? 1 : 2;
-              FreeHost  fh;
-              if (!MGX_MACRO_PAIRS && !tun.cells_form && b.n_bricks <= tun.free_max_bricks &&
-                  (uint64_t)desc->n_dofs * number_size(d.number) < 0xFFFFFFF0ull &&
-                  build_free_schedule(p, bh, desc->n_dofs, ex ? ex->shared : nullptr, ex ? ex->n_shared : 0,
-                                      bh.n_iface_groups > 0, n_classes, map, fh) &&
-                  (size_t)b.n_bricks * fh.n_surf * number_size(d.number) < 0xFFFFFFF0ull && fh.n_groups <= 8)
-                {
-                  FreeSchedule &fr  = b.fr;
-                  fr.n_classes      = n_classes;
-                  fr.n_groups       = fh.n_groups;
-                  fr.n_iface_groups = fh.n_iface_groups;
-                  for (int g = 0; g <= fh.n_groups; ++g)
-                    fr.group_start[g] = fh.group_start[g];
-                  fr.n_surf        = fh.n_surf;
-                  fr.n_surf_dofs   = (uint32_t)fh.surf_dof.size();
-                  fr.n_surf_shared = fh.n_surf_shared;
-                  fh.surf_dof.push_back(0);
-                  fh.surf_pos.push_back(0);
-                  auto up = [&](uint32_t *&dev, const std::vector<uint32_t> &v) {
-                    if (hipMalloc((void **)&dev, sizeof(uint32_t) * v.size()) != hipSuccess)
-                      return false;
-                    return hipMemcpy(dev, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice) == hipSuccess;
-                  };
-                  MGX_REQUIRE(up(fr.surf_off, fh.surf_off) && up(fr.surf_dof, fh.surf_dof) && up(fr.surf_start, fh.surf_start) &&
-                                up(fr.surf_pos, fh.surf_pos),
-                              "mgx_operator_create: out of device memory (reduced-colour schedule)");
-                  MGX_HIP(hipMalloc(&fr.priv, (size_t)b.n_bricks * fh.n_surf * number_size(d.number) + 16));
-                  MGX_REQUIRE(up(fr.ent, fh.ent), "mgx_operator_create: out of device memory (reduced-colour schedule)");
-                  MGX_TRACE("operator_create: reduced-colour schedule, %d classes, %d groups, %u private values per brick, %u "
-                            "private DoFs (%u shared)",
-                            n_classes, fr.n_groups, fr.n_surf, fr.n_surf_dofs, fr.n_surf_shared);
-                }
-            }
-          MGX_TRACE("operator_create: %u bricks, %d colours", b.n_bricks, b.n_colours);
-        }
-      else
+        return MGX_OK;
+      }
+    if (!build_bricks(p, desc->n_cells, desc->n_dofs, desc->idx27, desc->idx27_plain, desc->brick_colour,
+                      ex ? ex->shared : nullptr, ex ? ex->n_shared : 0, ex && desc->n_cells / brick_cells >= overlap_min, bh,
+                      why))
+      {
         MGX_TRACE("operator_create: per-cell kernel (%s)", why.c_str());
-    }
+        return MGX_OK;
+      }
+    BrickData &b = d.bricks;
+    b.n_bricks   = bh.n_bricks;
+    b.n_colours  = bh.n_colours;
+    b.n_iface_groups = bh.n_iface_groups;
+    b.order      = bh.order;
+    for (int c = 0; c <= bh.n_colours; ++c)
+      b.colour_start[c] = bh.colour_start[c];
+    // device table word: bits 0..29 first DoF, bit 30 FIRST, bit 31 LAST (mgx_brick.hip)
+    for (size_t i = 0; i < bh.ent_base.size(); ++i)
+      if (bh.ent_base[i] != MGX_INVALID_INDEX)
+        bh.ent_base[i] |= (uint32_t)(bh.ent_flags[i] & 3u) << 30;
+    MGX_TRY(op.mem.upload(&b.ent_base, bh.ent_base));
+    b.ent_flags = nullptr;
+    if (d.separable)
+      {
+        // write-out order of the macro-element kernel (mgx_macro.hip)
+        std::vector<uint32_t> map;
+        build_item_map(p, map);
+        MGX_TRY(op.mem.upload(&b.item_map, map));
+        {
+          // ... and of its second pipeline (mgx_macro2.hip): interior of the brick first
+          std::vector<uint32_t> map2;
+          build_item_map2(p, map2);
+          MGX_TRY(op.mem.upload(&b.item_map2, map2));
+        }
+        // Reduced-colour schedule of the plain / residual / Chebyshev forms (mgx_macro.hip, FREE): one
+        // class (one launch per level) on levels with at most free_one_max bricks, two classes up to
+        // free_max_bricks
+        const int n_classes = b.n_bricks <= tun.free_one_max ? 1 : 2;
+        FreeHost  fh;
+        if (!MGX_MACRO_PAIRS && !tun.cells_form && b.n_bricks <= tun.free_max_bricks &&
+            (uint64_t)desc->n_dofs * number_size(d.number) < 0xFFFFFFF0ull &&
+            build_free_schedule(p, bh, desc->n_dofs, ex ? ex->shared : nullptr, ex ? ex->n_shared : 0,
+                                bh.n_iface_groups > 0, n_classes, map, fh) &&
+            (size_t)b.n_bricks * fh.n_surf * number_size(d.number) < 0xFFFFFFF0ull && fh.n_groups <= 8)
+          {
+            FreeSchedule &fr  = b.fr;
+            fr.n_classes      = n_classes;
+            fr.n_groups       = fh.n_groups;
+            fr.n_iface_groups = fh.n_iface_groups;
+            for (int g = 0; g <= fh.n_groups; ++g)
+              fr.group_start[g] = fh.group_start[g];
+            fr.n_surf_shared = fh.n_surf_shared;
+            MGX_TRY(upload_free_schedule(op.mem, fr, fh, b.n_bricks, d.number));
+            MGX_TRACE("operator_create: reduced-colour schedule, %d classes, %d groups, %u private values per brick, %u "
+                      "private DoFs (%u shared)",
+                      n_classes, fr.n_groups, fr.n_surf, fr.n_surf_dofs, fr.n_surf_shared);
+          }
+      }
+    MGX_TRACE("operator_create: %u bricks, %d colours", b.n_bricks, b.n_colours);
+    return MGX_OK;
+  }
+
   // Brick form of the general tensor branch (mgx_kernels.hip, brick_general_kernel): p = 4, one rank, vectors and
   // coefficient array below the 4 GB of a 32-bit element offset, cells in bricks (hyper_shell and every structured
   // mapped mesh of mgx_cube): the one-launch schedule of the macro-element kernel -- every entity on a brick surface
   // private -- with its finish kernel.  vmult only; the other forms of a general operator keep the per-cell kernel.
-  if (general && p == 4 && !desc->exchange && !tun.no_bricks && !tun.no_general_bricks && desc->n_dofs < 0x3FFFFFFFu &&
-      (uint64_t)desc->n_dofs * number_size(d.number) < 0xFFFFFFF0ull &&
-      desc->n_cells / 64 >= tun.general_brick_min)
-    {
-      BrickHost   bh;
-      std::string why;
-      FreeHost    fh;
-      std::vector<uint32_t> map;
-      build_item_map(p, map);
-      if (build_bricks(p, desc->n_cells, desc->n_dofs, desc->idx27, desc->idx27_plain, nullptr, nullptr, 0, false, bh, why) &&
-          build_free_schedule(p, bh, desc->n_dofs, nullptr, 0, false, 1, map, fh) && fh.n_groups == 1 &&
-          (size_t)bh.n_bricks * fh.n_surf * number_size(d.number) < 0xFFFFFFF0ull)
-        {
-          BrickData &g = d.gbricks;
-          g.n_bricks   = bh.n_bricks;
-          FreeSchedule &fr = g.fr;
-          fr.n_classes = 1;
-          fr.n_groups  = 1;
-          fr.group_start[0] = 0;
-          fr.group_start[1] = bh.n_bricks;
-          fr.n_surf        = fh.n_surf;
-          fr.n_surf_dofs   = (uint32_t)fh.surf_dof.size();
-          fr.n_surf_shared = 0;
-          fh.surf_dof.push_back(0);
-          fh.surf_pos.push_back(0);
-          auto up = [&](uint32_t *&dev, const std::vector<uint32_t> &v) {
-            if (hipMalloc((void **)&dev, sizeof(uint32_t) * v.size()) != hipSuccess)
-              return false;
-            return hipMemcpy(dev, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice) == hipSuccess;
-          };
-          MGX_REQUIRE(up(g.order_dev, bh.order) && up(g.item_map, map) && up(fr.surf_off, fh.surf_off) && up(fr.surf_dof, fh.surf_dof) &&
-                        up(fr.surf_start, fh.surf_start) && up(fr.surf_pos, fh.surf_pos) && up(fr.ent, fh.ent),
-                      "mgx_operator_create: out of device memory (brick schedule of the general operator)");
-          MGX_HIP(hipMalloc(&fr.priv, (size_t)bh.n_bricks * fh.n_surf * number_size(d.number) + 16));
-          MGX_TRACE("operator_create: general branch on %u bricks, %u private values per brick, %u private DoFs", bh.n_bricks,
-                    fr.n_surf, fr.n_surf_dofs);
-        }
-      else
-        MGX_TRACE("operator_create: general branch without bricks (%s)", why.c_str());
-    }
+  int build_general_brick_schedule(mgx_operator_s &op, const mgx_operator_desc *desc)
+  {
+    OperatorData &d = op.d;
+    const int     p = d.p;
+    BrickHost   bh;
+    std::string why;
+    FreeHost    fh;
+    std::vector<uint32_t> map;
+    build_item_map(p, map);
+    if (build_bricks(p, desc->n_cells, desc->n_dofs, desc->idx27, desc->idx27_plain, nullptr, nullptr, 0, false, bh, why) &&
+        build_free_schedule(p, bh, desc->n_dofs, nullptr, 0, false, 1, map, fh) && fh.n_groups == 1 &&
+        (size_t)bh.n_bricks * fh.n_surf * number_size(d.number) < 0xFFFFFFF0ull)
+      {
+        BrickData &g = d.gbricks;
+        g.n_bricks   = bh.n_bricks;
+        FreeSchedule &fr = g.fr;
+        fr.n_classes = 1;
+        fr.n_groups  = 1;
+        fr.group_start[0] = 0;
+        fr.group_start[1] = bh.n_bricks;
+        fr.n_surf_shared = 0;
+        MGX_TRY(op.mem.upload(&g.order_dev, bh.order));
+        MGX_TRY(op.mem.upload(&g.item_map, map));
+        MGX_TRY(upload_free_schedule(op.mem, fr, fh, bh.n_bricks, d.number));
+        MGX_TRACE("operator_create: general branch on %u bricks, %u private values per brick, %u private DoFs", bh.n_bricks,
+                  fr.n_surf, fr.n_surf_dofs);
+      }
+    else
+      MGX_TRACE("operator_create: general branch without bricks (%s)", why.c_str());
+    return MGX_OK;
+  }
+
   // Ordered assembly for the per-cell kernels: levels without a brick schedule and without cell
   // colours.  For every DoF the positions (cell (p+1)^3 + local index) of its contributions in
   // ascending cell order, from the compressed index table (read_dof_values_compressed,
   // vector_access_reduced.h:153-229; constrained entities contribute nothing).  Larger levels than
   // kAssemblyMaxEntries keep the one launch with atomic adds (last bits not reproducible).
+  int build_ordered_assembly(mgx_operator_s &op, const mgx_operator_desc *desc)
   {
-    const size_t     n3 = (size_t)n * n * n, n_local = n3 * desc->n_cells;
-    if (!d.bricks.available() && !d.cell_order && n_local <= kAssemblyMaxEntries)
-      {
-        std::vector<uint32_t> start((size_t)desc->n_dofs + 1, 0), pos;
-        auto for_each_local = [&](auto &&f) {
-          for (uint32_t c = 0; c < desc->n_cells; ++c)
-            {
-              const uint32_t *ix = desc->idx27 + 27 * (size_t)c;
-              for (int k = 0; k < n; ++k)
-                for (int j = 0; j < n; ++j)
-                  {
-                    const int       cz = k == 0 ? 0 : (k == p ? 2 : 1), oz = cz == 1 ? k - 1 : 0;
-                    const int       cy = j == 0 ? 0 : (j == p ? 2 : 1), oy = cy == 1 ? j - 1 : 0;
-                    const uint32_t *e  = ix + 3 * (3 * cz + cy);
-                    const uint32_t  off = (uint32_t)((cy == 1 ? p - 1 : 1) * oz + oy);
-                    const uint32_t  l0  = (uint32_t)(c * n3 + (size_t)(k * n + j) * n);
-                    if (e[0] != MGX_INVALID_INDEX)
-                      f(e[0] + off, l0);
-                    if (e[1] != MGX_INVALID_INDEX)
-                      for (int i = 1; i < p; ++i)
-                        f(e[1] + off * (uint32_t)(p - 1) + (uint32_t)(i - 1), l0 + (uint32_t)i);
-                    if (e[2] != MGX_INVALID_INDEX)
-                      f(e[2] + off, l0 + (uint32_t)p);
-                  }
-            }
-        };
-        for_each_local([&](uint32_t dof, uint32_t) { ++start[dof + 1]; });
-        for (size_t i = 0; i < desc->n_dofs; ++i)
-          start[i + 1] += start[i];
-        pos.resize(start.back() + 1);
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-        for_each_local([&](uint32_t dof, uint32_t l) { pos[fill[dof]++] = l; });
-        MGX_HIP(hipMalloc((void **)&d.asm_start, sizeof(uint32_t) * start.size()));
-        MGX_HIP(hipMalloc((void **)&d.asm_pos, sizeof(uint32_t) * pos.size()));
-        MGX_HIP(hipMalloc(&d.cell_scratch, number_size(d.number) * n_local));
-        MGX_HIP(hipMemcpy(d.asm_start, start.data(), sizeof(uint32_t) * start.size(), hipMemcpyHostToDevice));
-        MGX_HIP(hipMemcpy(d.asm_pos, pos.data(), sizeof(uint32_t) * pos.size(), hipMemcpyHostToDevice));
-        MGX_TRACE("operator_create: ordered assembly of the per-cell kernel (%zu contributions)", pos.size() - 1);
-      }
+    OperatorData &d = op.d;
+    const int     p = d.p, n = p + 1;
+    const size_t  n3 = (size_t)n * n * n, n_local = n3 * desc->n_cells;
+    if (d.bricks.available() || d.cell_order || n_local > kAssemblyMaxEntries)
+      return MGX_OK;
+    std::vector<uint32_t> start((size_t)desc->n_dofs + 1, 0), pos;
+    auto for_each_local = [&](auto &&f) {
+      for (uint32_t c = 0; c < desc->n_cells; ++c)
+        {
+          const uint32_t *ix = desc->idx27 + 27 * (size_t)c;
+          for (int k = 0; k < n; ++k)
+            for (int j = 0; j < n; ++j)
+              {
+                const int       cz = k == 0 ? 0 : (k == p ? 2 : 1), oz = cz == 1 ? k - 1 : 0;
+                const int       cy = j == 0 ? 0 : (j == p ? 2 : 1), oy = cy == 1 ? j - 1 : 0;
+                const uint32_t *e  = ix + 3 * (3 * cz + cy);
+                const uint32_t  off = (uint32_t)((cy == 1 ? p - 1 : 1) * oz + oy);
+                const uint32_t  l0  = (uint32_t)(c * n3 + (size_t)(k * n + j) * n);
+                if (e[0] != MGX_INVALID_INDEX)
+                  f(e[0] + off, l0);
+                if (e[1] != MGX_INVALID_INDEX)
+                  for (int i = 1; i < p; ++i)
+                    f(e[1] + off * (uint32_t)(p - 1) + (uint32_t)(i - 1), l0 + (uint32_t)i);
+                if (e[2] != MGX_INVALID_INDEX)
+                  f(e[2] + off, l0 + (uint32_t)p);
+              }
+        }
+    };
+    for_each_local([&](uint32_t dof, uint32_t) { ++start[dof + 1]; });
+    for (size_t i = 0; i < desc->n_dofs; ++i)
+      start[i + 1] += start[i];
+    pos.resize(start.back() + 1);
+    std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+    for_each_local([&](uint32_t dof, uint32_t l) { pos[fill[dof]++] = l; });
+    MGX_TRY(op.mem.upload(&d.asm_start, start));
+    MGX_TRY(op.mem.upload(&d.asm_pos, pos));
+    MGX_TRY(op.mem.alloc(&d.cell_scratch, number_size(d.number) * n_local));
+    MGX_TRACE("operator_create: ordered assembly of the per-cell kernel (%zu contributions)", pos.size() - 1);
+    return MGX_OK;
   }
+
   // smoother start vector statistics over the DoFs this rank owns
+  void start_vector_statistics(mgx_operator_s &op, const mgx_operator_desc *desc)
   {
     std::vector<uint8_t> skip(desc->n_dofs, 0);
     if (desc->exchange)
@@ -1686,159 +1613,207 @@ int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_op
           sum += (double)((desc->global_index ? desc->global_index[i] : i) % 11u);
           cnt += 1;
         }
-    op->start_sum   = sum;
-    op->start_count = cnt;
+    op.start_sum   = sum;
+    op.start_count = cnt;
   }
-  if (desc->global_index)
-    {
-      MGX_HIP(hipMalloc((void **)&op->global_index_dev, sizeof(uint32_t) * desc->n_dofs));
-      MGX_HIP(hipMemcpy(op->global_index_dev, desc->global_index, sizeof(uint32_t) * desc->n_dofs,
-                        hipMemcpyHostToDevice));
-    }
-  if (desc->exchange)
-    {
-      const mgx_exchange_desc &e = *desc->exchange;
-      MGX_REQUIRE(ctx->has_comm, "mgx_operator_create: exchange plan given but no communicator set on the context");
-      MGX_REQUIRE(e.n_neighbors >= 0 && (e.n_neighbors == 0 || (e.neighbor_rank && e.count && e.index)),
-                  "mgx_operator_create: incomplete exchange plan");
-      auto P     = std::make_unique<ExchangePlan>();
-      P->plan_id = e.plan_id;
-      P->number  = d.number;
-      const size_t es = number_size(d.number);
-      const int    my_rank = (ctx->nccl && !ctx->comm.exchange) ? ctx->rccl_rank : ctx->comm.rank;
-      // MGX_RCCL_SELFTEST: a one-rank communicator may name itself as neighbour (tools/rccl_selftest.py)
-      const bool   selftest = tun.rccl_selftest;
-      for (int k = 0; k < e.n_neighbors; ++k)
-        {
-          MGX_REQUIRE(selftest ||
-                        (e.neighbor_rank[k] != my_rank && (k == 0 || e.neighbor_rank[k] > e.neighbor_rank[k - 1])),
-                      "mgx_operator_create: neighbour ranks must be ascending and differ from the own rank");
-          for (uint32_t i = 0; i < e.count[k]; ++i)
-            if (e.index[k][i] >= desc->n_dofs)
-              return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: exchange index out of range");
-          if (e.neighbor_rank[k] < my_rank)
-            P->self_pos = k + 1;
-          P->rank.push_back(e.neighbor_rank[k]);
-          P->count.push_back(e.count[k]);
-          uint32_t *idx = nullptr;
-          MGX_HIP(hipMalloc((void **)&idx, sizeof(uint32_t) * (e.count[k] + 1)));
-          MGX_HIP(hipMemcpy(idx, e.index[k], sizeof(uint32_t) * e.count[k], hipMemcpyHostToDevice));
-          P->index_dev.push_back(idx);
-          void *sb = e.send_buf ? e.send_buf[k] : nullptr, *rb = e.recv_buf ? e.recv_buf[k] : nullptr;
-          bool own = !(sb && rb);
-          if (own && ctx->comm.alloc_device)
-            {
-              sb  = ctx->comm.alloc_device(ctx->comm.user, es * (e.count[k] + 1));
-              rb  = ctx->comm.alloc_device(ctx->comm.user, es * (e.count[k] + 1));
-              own = false;
-              MGX_REQUIRE(sb && rb, "mgx_operator_create: the communicator's alloc_device failed");
-            }
-          if (own)
-            {
-              MGX_HIP(hipMalloc(&sb, es * (e.count[k] + 1)));
-              MGX_HIP(hipMalloc(&rb, es * (e.count[k] + 1)));
-            }
-          P->send.push_back(sb);
-          P->recv.push_back(rb);
-          P->owns_buffers.push_back(own ? 1 : 0);
-        }
-      for (uint32_t i = 0; i < e.n_shared; ++i)
-        if (e.shared[i] >= desc->n_dofs)
-          return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: shared index out of range");
+
+  // interface exchange of a decomposed mesh: lists, buffers (the operator's arena holds those it allocates itself;
+  // the caller's and the communicator's stay theirs) and the tables of the fused pack / ordered unpack
+  int build_exchange_plan(mgx_operator_s &op, const mgx_operator_desc *desc, const Tunables &tun)
+  {
+    mgx_context_t            ctx = op.ctx;
+    const OperatorData      &d   = op.d;
+    const mgx_exchange_desc &e   = *desc->exchange;
+    MGX_REQUIRE(ctx->has_comm, "mgx_operator_create: exchange plan given but no communicator set on the context");
+    MGX_REQUIRE(e.n_neighbors >= 0 && (e.n_neighbors == 0 || (e.neighbor_rank && e.count && e.index)),
+                "mgx_operator_create: incomplete exchange plan");
+    auto P     = std::make_unique<ExchangePlan>();
+    P->plan_id = e.plan_id;
+    P->number  = d.number;
+    const size_t es = number_size(d.number);
+    const int    my_rank = (ctx->nccl && !ctx->comm.exchange) ? ctx->rccl_rank : ctx->comm.rank;
+    // MGX_RCCL_SELFTEST: a one-rank communicator may name itself as neighbour (tools/rccl_selftest.py)
+    const bool   selftest = tun.rccl_selftest;
+    for (int k = 0; k < e.n_neighbors; ++k)
       {
-        // Dirichlet DoFs are never exchanged: their rows are the identity on every rank, and the
-        // interface post-operations assume the two lists to be disjoint (mgx.h, mgx_exchange_desc)
-        std::vector<uint8_t> is_constrained(desc->n_dofs, 0);
-        for (uint32_t i = 0; i < desc->n_constrained; ++i)
-          is_constrained[desc->constrained[i]] = 1;
-        for (uint32_t i = 0; i < e.n_shared; ++i)
-          if (is_constrained[e.shared[i]])
-            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: a constrained DoF is listed as shared; leave "
-                                                  "Dirichlet DoFs out of the exchange plan");
+        MGX_REQUIRE(selftest ||
+                      (e.neighbor_rank[k] != my_rank && (k == 0 || e.neighbor_rank[k] > e.neighbor_rank[k - 1])),
+                    "mgx_operator_create: neighbour ranks must be ascending and differ from the own rank");
+        for (uint32_t i = 0; i < e.count[k]; ++i)
+          if (e.index[k][i] >= desc->n_dofs)
+            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: exchange index out of range");
+        if (e.neighbor_rank[k] < my_rank)
+          P->self_pos = k + 1;
+        P->rank.push_back(e.neighbor_rank[k]);
+        P->count.push_back(e.count[k]);
+        uint32_t *idx = nullptr;
+        MGX_TRY(op.mem.upload(&idx, e.index[k], e.count[k], 1));
+        P->index_dev.push_back(idx);
+        void *sb = e.send_buf ? e.send_buf[k] : nullptr, *rb = e.recv_buf ? e.recv_buf[k] : nullptr;
+        bool own = !(sb && rb);
+        if (own && ctx->comm.alloc_device)
+          {
+            sb  = ctx->comm.alloc_device(ctx->comm.user, es * (e.count[k] + 1));
+            rb  = ctx->comm.alloc_device(ctx->comm.user, es * (e.count[k] + 1));
+            own = false;
+            MGX_REQUIRE(sb && rb, "mgx_operator_create: the communicator's alloc_device failed");
+          }
+        if (own)
+          {
+            MGX_TRY(op.mem.alloc(&sb, es * (e.count[k] + 1)));
+            MGX_TRY(op.mem.alloc(&rb, es * (e.count[k] + 1)));
+          }
+        P->send.push_back(sb);
+        P->recv.push_back(rb);
+      }
+    for (uint32_t i = 0; i < e.n_shared; ++i)
+      if (e.shared[i] >= desc->n_dofs)
+        return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: shared index out of range");
+    {
+      // Dirichlet DoFs are never exchanged: their rows are the identity on every rank, and the
+      // interface post-operations assume the two lists to be disjoint (mgx.h, mgx_exchange_desc)
+      std::vector<uint8_t> is_constrained(desc->n_dofs, 0);
+      for (uint32_t i = 0; i < desc->n_constrained; ++i)
+        is_constrained[desc->constrained[i]] = 1;
+      for (uint32_t i = 0; i < e.n_shared; ++i)
+        if (is_constrained[e.shared[i]])
+          return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: a constrained DoF is listed as shared; leave "
+                                                "Dirichlet DoFs out of the exchange plan");
+      for (int k = 0; k < e.n_neighbors; ++k)
+        for (uint32_t i = 0; i < e.count[k]; ++i)
+          if (is_constrained[e.index[k][i]])
+            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: a constrained DoF is listed for exchange; "
+                                                  "leave Dirichlet DoFs out of the exchange plan");
+    }
+    P->n_shared    = e.n_shared;
+    P->n_not_owned = e.n_not_owned;
+    P->not_owned_host.assign(e.not_owned, e.not_owned + e.n_not_owned);
+    MGX_TRY(op.mem.upload(&P->shared_dev, e.shared, e.n_shared, 1));
+    MGX_TRY(op.mem.upload(&P->not_owned_dev, e.not_owned, e.n_not_owned, 1));
+    MGX_TRY(op.mem.alloc(&P->own_buf, es * (e.n_shared + 1)));
+    // fused pack / ordered unpack tables
+    if (e.n_neighbors <= 32 && e.n_neighbors < 255 && !tun.exchange_unfused)
+      {
+        P->start.assign(e.n_neighbors + 1, 0);
+        for (int k = 0; k < e.n_neighbors; ++k)
+          P->start[k + 1] = P->start[k] + e.count[k];
+        const uint32_t        total = P->start.back();
+        std::vector<uint32_t> all_index(total + 1, 0);
+        std::vector<uint8_t>  all_seg(total + 1, 0);
         for (int k = 0; k < e.n_neighbors; ++k)
           for (uint32_t i = 0; i < e.count[k]; ++i)
-            if (is_constrained[e.index[k][i]])
-              return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: a constrained DoF is listed for exchange; "
-                                                    "leave Dirichlet DoFs out of the exchange plan");
-      }
-      P->n_shared    = e.n_shared;
-      P->n_not_owned = e.n_not_owned;
-      P->not_owned_host.assign(e.not_owned, e.not_owned + e.n_not_owned);
-      MGX_HIP(hipMalloc((void **)&P->shared_dev, sizeof(uint32_t) * (e.n_shared + 1)));
-      MGX_HIP(hipMalloc((void **)&P->not_owned_dev, sizeof(uint32_t) * (e.n_not_owned + 1)));
-      MGX_HIP(hipMalloc(&P->own_buf, es * (e.n_shared + 1)));
-      if (e.n_shared)
-        MGX_HIP(hipMemcpy(P->shared_dev, e.shared, sizeof(uint32_t) * e.n_shared, hipMemcpyHostToDevice));
-      if (e.n_not_owned)
-        MGX_HIP(hipMemcpy(P->not_owned_dev, e.not_owned, sizeof(uint32_t) * e.n_not_owned, hipMemcpyHostToDevice));
-      // fused pack / ordered unpack tables
-      if (e.n_neighbors <= 32 && e.n_neighbors < 255 && !tun.exchange_unfused)
-        {
-          P->start.assign(e.n_neighbors + 1, 0);
-          for (int k = 0; k < e.n_neighbors; ++k)
-            P->start[k + 1] = P->start[k] + e.count[k];
-          const uint32_t        total = P->start.back();
-          std::vector<uint32_t> all_index(total + 1, 0);
-          std::vector<uint8_t>  all_seg(total + 1, 0);
-          for (int k = 0; k < e.n_neighbors; ++k)
-            for (uint32_t i = 0; i < e.count[k]; ++i)
-              {
-                all_index[P->start[k] + i] = e.index[k][i];
-                all_seg[P->start[k] + i]   = (uint8_t)k;
-              }
-          // contributions per interface DoF in ascending rank order, own sum at self_pos
-          std::vector<uint32_t> slot(desc->n_dofs, MGX_INVALID_INDEX);
-          for (uint32_t j = 0; j < e.n_shared; ++j)
-            slot[e.shared[j]] = j;
-          std::vector<uint32_t> cnt(e.n_shared + 1, 0);
-          bool                  ok = true;
-          for (int k = 0; k < e.n_neighbors && ok; ++k)
-            for (uint32_t i = 0; i < e.count[k]; ++i)
-              {
-                const uint32_t j = slot[e.index[k][i]];
-                if (j == MGX_INVALID_INDEX)
-                  {
-                    ok = false; // an exchanged DoF that is not in the shared list: keep the plain form
-                    break;
-                  }
-                cnt[j]++;
-              }
-          if (ok)
             {
-              std::vector<uint32_t> cs(e.n_shared + 1, 0);
-              for (uint32_t j = 0; j < e.n_shared; ++j)
-                cs[j + 1] = cs[j] + cnt[j] + 1;
-              std::vector<uint8_t>  ck(cs.back() + 1, 0);
-              std::vector<uint32_t> cp(cs.back() + 1, 0), fill(cs.begin(), cs.end() - 1);
-              for (int k = 0; k <= e.n_neighbors; ++k)
-                {
-                  if (k == P->self_pos)
-                    for (uint32_t j = 0; j < e.n_shared; ++j)
-                      ck[fill[j]++] = 255;
-                  if (k < e.n_neighbors)
-                    for (uint32_t i = 0; i < e.count[k]; ++i)
-                      {
-                        const uint32_t j = slot[e.index[k][i]];
-                        ck[fill[j]]   = (uint8_t)k;
-                        cp[fill[j]++] = i;
-                      }
-                }
-              MGX_HIP(hipMalloc((void **)&P->all_index_dev, sizeof(uint32_t) * all_index.size()));
-              MGX_HIP(hipMalloc((void **)&P->all_seg_dev, all_seg.size()));
-              MGX_HIP(hipMalloc((void **)&P->csr_start_dev, sizeof(uint32_t) * cs.size()));
-              MGX_HIP(hipMalloc((void **)&P->csr_k_dev, ck.size()));
-              MGX_HIP(hipMalloc((void **)&P->csr_pos_dev, sizeof(uint32_t) * cp.size()));
-              MGX_HIP(hipMemcpy(P->all_index_dev, all_index.data(), sizeof(uint32_t) * all_index.size(), hipMemcpyHostToDevice));
-              MGX_HIP(hipMemcpy(P->all_seg_dev, all_seg.data(), all_seg.size(), hipMemcpyHostToDevice));
-              MGX_HIP(hipMemcpy(P->csr_start_dev, cs.data(), sizeof(uint32_t) * cs.size(), hipMemcpyHostToDevice));
-              MGX_HIP(hipMemcpy(P->csr_k_dev, ck.data(), ck.size(), hipMemcpyHostToDevice));
-              MGX_HIP(hipMemcpy(P->csr_pos_dev, cp.data(), sizeof(uint32_t) * cp.size(), hipMemcpyHostToDevice));
-              P->fused = true;
+              all_index[P->start[k] + i] = e.index[k][i];
+              all_seg[P->start[k] + i]   = (uint8_t)k;
             }
-        }
-      ctx->plans.push_back({(size_t)desc->n_dofs, P.get()});
-      op->plan = std::move(P);
-    }
+        // contributions per interface DoF in ascending rank order, own sum at self_pos
+        std::vector<uint32_t> slot(desc->n_dofs, MGX_INVALID_INDEX);
+        for (uint32_t j = 0; j < e.n_shared; ++j)
+          slot[e.shared[j]] = j;
+        std::vector<uint32_t> cnt(e.n_shared + 1, 0);
+        bool                  ok = true;
+        for (int k = 0; k < e.n_neighbors && ok; ++k)
+          for (uint32_t i = 0; i < e.count[k]; ++i)
+            {
+              const uint32_t j = slot[e.index[k][i]];
+              if (j == MGX_INVALID_INDEX)
+                {
+                  ok = false; // an exchanged DoF that is not in the shared list: keep the plain form
+                  break;
+                }
+              cnt[j]++;
+            }
+        if (ok)
+          {
+            std::vector<uint32_t> cs(e.n_shared + 1, 0);
+            for (uint32_t j = 0; j < e.n_shared; ++j)
+              cs[j + 1] = cs[j] + cnt[j] + 1;
+            std::vector<uint8_t>  ck(cs.back() + 1, 0);
+            std::vector<uint32_t> cp(cs.back() + 1, 0), fill(cs.begin(), cs.end() - 1);
+            for (int k = 0; k <= e.n_neighbors; ++k)
+              {
+                if (k == P->self_pos)
+                  for (uint32_t j = 0; j < e.n_shared; ++j)
+                    ck[fill[j]++] = 255;
+                if (k < e.n_neighbors)
+                  for (uint32_t i = 0; i < e.count[k]; ++i)
+                    {
+                      const uint32_t j = slot[e.index[k][i]];
+                      ck[fill[j]]   = (uint8_t)k;
+                      cp[fill[j]++] = i;
+                    }
+              }
+            MGX_TRY(op.mem.upload(&P->all_index_dev, all_index));
+            MGX_TRY(op.mem.upload(&P->all_seg_dev, all_seg));
+            MGX_TRY(op.mem.upload(&P->csr_start_dev, cs));
+            MGX_TRY(op.mem.upload(&P->csr_k_dev, ck));
+            MGX_TRY(op.mem.upload(&P->csr_pos_dev, cp));
+            P->fused = true;
+          }
+      }
+    ctx->plans.push_back({(size_t)desc->n_dofs, P.get()});
+    op.plan = std::move(P);
+    return MGX_OK;
+  }
+} // namespace
+
+extern "C" {
+
+int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_operator_t *out)
+{
+  MGX_TRY(validate_operator_desc(ctx, desc, out));
+  // failures below return through the destroy function, which frees what the operator's arena holds by then
+  std::unique_ptr<mgx_operator_s, int (*)(mgx_operator_t)> op(new mgx_operator_s, mgx_operator_destroy);
+  op->ctx              = ctx;
+  op->constrained_last = constrained_are_last(desc);
+  const Tunables &tun  = ctx->tun;
+  const int       p = desc->degree, n = p + 1;
+  const size_t    n_entries = 27 * (size_t)desc->n_cells;
+  OperatorData   &d  = op->d;
+  d.p              = p;
+  d.number         = desc->number;
+  d.n_cells        = desc->n_cells;
+  d.n_dofs         = desc->n_dofs;
+  d.n_constrained  = desc->n_constrained;
+  for (int i = 0; i < 6; ++i)
+    d.coef[i] = desc->coef[i];
+  std::memcpy(op->S, desc->shape_values, sizeof(double) * n * n);
+  std::memcpy(op->D, desc->colloc_grad, sizeof(double) * n * n);
+  std::memcpy(op->w, desc->qweights, sizeof(double) * n);
+  d.full_tensor      = !desc->coef_q && (desc->coef[3] != 0. || desc->coef[4] != 0. || desc->coef[5] != 0.);
+  const bool general = d.full_tensor || desc->coef_q; // quadrature-point operation with the full tensor
+  d.separable        = !tun.general_kernel && !general;
+  d.cells_form       = tun.cells_form;
+  d.wide_max         = tun.wide_max;
+  d.macro_wg_x16     = tun.macro_wg_x16;
+  d.n_cus            = context_cus(ctx);
+  d.macro_v2         = !tun.no_macro_v2;
+  MGX_HIP(hipSetDevice(ctx->device));
+  MGX_TRY(op->mem.upload(&d.idx27, desc->idx27, n_entries));
+  if (desc->idx27_plain)
+    MGX_TRY(op->mem.upload(&d.idx27_plain, desc->idx27_plain, n_entries));
+  MGX_TRY(op->mem.upload(&d.constrained, desc->constrained, desc->n_constrained, 1));
+  MGX_TRY(upload_basis(*op));
+  MGX_TRY(op->mem.alloc(&d.inv_diag, number_size(d.number) * d.n_dofs));
+  if (general)
+    MGX_TRY(upload_general_tables(*op, desc));
+  if (general && (desc->n_cells >= tun.cell_colour_min || (size_t)n * n * n * desc->n_cells > kAssemblyMaxEntries))
+    MGX_TRY(colour_cells(*op, desc));
+  // (builds without the cell-by-cell cross-check kernels schedule bricks only where the macro-element
+  // kernel runs: separable operator, vector below the 4 GB of a buffer descriptor)
+  const bool macro_covers = d.separable && (uint64_t)desc->n_dofs * number_size(d.number) < 0xFFFFFFF0ull;
+  if (!tun.no_bricks && !general && (MGX_CELLS_FORM ? (p <= 4 || d.separable) : macro_covers))
+    MGX_TRY(build_brick_schedule(*op, desc, tun));
+  if (general && p == 4 && !desc->exchange && !tun.no_bricks && !tun.no_general_bricks && desc->n_dofs < 0x3FFFFFFFu &&
+      (uint64_t)desc->n_dofs * number_size(d.number) < 0xFFFFFFF0ull &&
+      desc->n_cells / 64 >= tun.general_brick_min)
+    MGX_TRY(build_general_brick_schedule(*op, desc));
+  MGX_TRY(build_ordered_assembly(*op, desc));
+  start_vector_statistics(*op, desc);
+  if (desc->global_index)
+    MGX_TRY(op->mem.upload(&op->global_index_dev, desc->global_index, desc->n_dofs));
+  if (desc->exchange)
+    MGX_TRY(build_exchange_plan(*op, desc, tun));
   *out = op.release();
   return MGX_OK;
 }
@@ -1868,66 +1843,12 @@ int mgx_operator_destroy(mgx_operator_t op)
   if (!op)
     return MGX_OK;
   (void)hipStreamSynchronize(op->ctx->stream);
-  (void)hipFree(op->d.idx27);
-  (void)hipFree(op->d.idx27_plain);
-  (void)hipFree(op->d.constrained);
-  (void)hipFree(op->d.basis);
-  (void)hipFree(op->d.inv_diag);
-  (void)hipFree(op->d.coef_q);
-  (void)hipFree(op->d.grad_1d);
-  (void)hipFree(op->d.cell_order);
-  (void)hipFree(op->d.asm_start);
-  (void)hipFree(op->d.asm_pos);
-  (void)hipFree(op->d.cell_scratch);
-  (void)hipFree(op->d.bricks.ent_base);
-  (void)hipFree(op->d.bricks.ent_flags);
-  (void)hipFree(op->d.bricks.item_map);
-  (void)hipFree(op->d.bricks.item_map2);
-  (void)hipFree(op->d.bricks.fr.ent);
-  (void)hipFree(op->d.bricks.fr.surf_off);
-  (void)hipFree(op->d.bricks.fr.priv);
-  (void)hipFree(op->d.bricks.fr.surf_dof);
-  (void)hipFree(op->d.bricks.fr.surf_start);
-  (void)hipFree(op->d.bricks.fr.surf_pos);
-  (void)hipFree(op->d.gbricks.item_map);
-  (void)hipFree(op->d.gbricks.order_dev);
-  (void)hipFree(op->d.gbricks.fr.ent);
-  (void)hipFree(op->d.gbricks.fr.surf_off);
-  (void)hipFree(op->d.gbricks.fr.priv);
-  (void)hipFree(op->d.gbricks.fr.surf_dof);
-  (void)hipFree(op->d.gbricks.fr.surf_start);
-  (void)hipFree(op->d.gbricks.fr.surf_pos);
-  (void)hipFree(op->d.diag_items);
-  (void)hipFree(op->d.diag_items2);
-  (void)hipFree(op->cg_partials);
-  (void)hipFree(op->cg_result);
-  (void)hipFree(op->cg_carrier);
-  (void)hipFree(op->unit_q);
-  (void)hipFree(op->jxw_q);
-  (void)hipFree(op->global_index_dev);
   if (op->plan)
     {
       ExchangePlan *P = op->plan.get();
       auto         &v = op->ctx->plans;
       v.erase(std::remove_if(v.begin(), v.end(), [P](const std::pair<size_t, ExchangePlan *> &x) { return x.second == P; }),
               v.end());
-      for (size_t k = 0; k < P->rank.size(); ++k)
-        {
-          (void)hipFree(P->index_dev[k]);
-          if (P->owns_buffers[k])
-            {
-              (void)hipFree(P->send[k]);
-              (void)hipFree(P->recv[k]);
-            }
-        }
-      (void)hipFree(P->shared_dev);
-      (void)hipFree(P->not_owned_dev);
-      (void)hipFree(P->own_buf);
-      (void)hipFree(P->all_index_dev);
-      (void)hipFree(P->all_seg_dev);
-      (void)hipFree(P->csr_start_dev);
-      (void)hipFree(P->csr_k_dev);
-      (void)hipFree(P->csr_pos_dev);
     }
   delete op;
   return MGX_OK;
@@ -2005,8 +1926,8 @@ int mgx_vmult_with_cg_update(mgx_operator_t op, double alpha, double beta, const
   constexpr uint32_t kCapacity = 1u << 16; // quadruples
   if (!op->cg_partials)
     {
-      MGX_HIP(hipMalloc((void **)&op->cg_partials, sizeof(double) * 4 * kCapacity));
-      MGX_HIP(hipMalloc((void **)&op->cg_result, sizeof(double) * 4));
+      MGX_TRY(op->mem.alloc(&op->cg_partials, 4 * (size_t)kCapacity));
+      MGX_TRY(op->mem.alloc(&op->cg_result, 4));
     }
   bool fused = op->d.bricks.available() && op->d.separable && op->d.bricks.item_map && !op->plan;
   if (fused)
@@ -2017,7 +1938,7 @@ int mgx_vmult_with_cg_update(mgx_operator_t op, double alpha, double beta, const
       if (!carrier)
         {
           if (!op->cg_carrier)
-            MGX_HIP(hipMalloc(&op->cg_carrier, number_size(num) * n));
+            MGX_TRY(op->mem.alloc(&op->cg_carrier, number_size(num) * n));
           carrier = op->cg_carrier;
         }
       uint32_t used = 0;
@@ -2090,24 +2011,13 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
   hipStream_t  s     = op->ctx->stream;
   const size_t bytes = number_size(op->d.number) * op->d.n_dofs;
   // temporaries of this call, released on every path out of it (after the stream has drained)
-  struct Scratch
-  {
-    hipStream_t s;
-    void       *zero      = nullptr;
-    uint32_t   *lists_dev = nullptr;
-    ~Scratch()
-    {
-      if (zero || lists_dev)
-        (void)hipStreamSynchronize(s);
-      (void)hipFree(zero);
-      (void)hipFree(lists_dev);
-    }
-  } tmp{s};
+  DeviceArena tmp("mgx_compute_residual");
+  tmp.drain_before_release(s);
   if (!src) // homogeneous boundary values
     {
-      MGX_HIP(hipMalloc(&tmp.zero, bytes));
-      MGX_HIP(hipMemsetAsync(tmp.zero, 0, bytes, s));
-      src = tmp.zero;
+      void *zero = nullptr;
+      MGX_TRY(tmp.zeros(&zero, bytes, s));
+      src = zero;
     }
   MGX_HIP(hipMemsetAsync(dst, 0, bytes, s));
   // assembly without atomics, as for the diagonal (mgx_compute_diagonal)
@@ -2115,9 +2025,10 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
     {
       std::vector<uint32_t> lists, list_start;
       brick_cell_lists(op, lists, list_start);
-      MGX_HIP(hipMalloc((void **)&tmp.lists_dev, sizeof(uint32_t) * (lists.size() + 1)));
-      MGX_HIP(hipMemcpyAsync(tmp.lists_dev, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice, s));
-      launch_cell_residual(s, op->d, dst, src, rhs_q, tmp.lists_dev, list_start.data(), (int)list_start.size() - 1);
+      uint32_t *lists_dev = nullptr;
+      MGX_TRY(tmp.alloc(&lists_dev, lists.size() + 1));
+      MGX_HIP(hipMemcpyAsync(lists_dev, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice, s));
+      launch_cell_residual(s, op->d, dst, src, rhs_q, lists_dev, list_start.data(), (int)list_start.size() - 1);
       MGX_HIP(hipStreamSynchronize(s)); // (`lists` is pageable host memory in flight until here)
     }
   else if (op->d.cell_order && !op->d.asm_start)
@@ -2147,27 +2058,13 @@ int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metri
   if (op->unit_q) // replaces a per-point geometry, which a kernel in flight may read
     {
       MGX_HIP(hipStreamSynchronize(op->ctx->stream));
-      (void)hipFree(op->unit_q);
-      (void)hipFree(op->jxw_q);
+      op->mem.release(op->unit_q);
+      op->mem.release(op->jxw_q);
       op->unit_q = op->jxw_q = nullptr;
     }
   std::copy(metric, metric + 6, op->metric);
   op->det_jacobian = det_jacobian;
   op->coef_update  = true;
-  return MGX_OK;
-}
-
-// host doubles to a new device array of the number type
-static int upload_as(int number, void **dev, const double *host, size_t n)
-{
-  MGX_HIP(hipMalloc(dev, number_size(number) * n));
-  if (number == MGX_F64)
-    MGX_HIP(hipMemcpy(*dev, host, sizeof(double) * n, hipMemcpyHostToDevice));
-  else
-    {
-      std::vector<float> tmp(host, host + n);
-      MGX_HIP(hipMemcpy(*dev, tmp.data(), sizeof(float) * n, hipMemcpyHostToDevice));
-    }
   return MGX_OK;
 }
 
@@ -2189,19 +2086,13 @@ int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *un
       }
   MGX_REQUIRE(ok, "mgx_operator_enable_coefficient_update_q: JxW_q and the diagonal of JxW_q J^-1 J^-T must be positive at every "
                   "quadrature point");
+  // (a failed upload leaves the new arrays to the operator's arena and the present geometry in place)
   void *u_dev = nullptr, *w_dev = nullptr;
-  int   status = upload_as(op->d.number, &u_dev, unit_q, nc * 6 * n3);
-  if (status == MGX_OK)
-    status = upload_as(op->d.number, &w_dev, jxw_q, nc * n3);
-  if (status != MGX_OK)
-    {
-      (void)hipFree(u_dev);
-      (void)hipFree(w_dev);
-      return status;
-    }
+  MGX_TRY(op->mem.upload_as(op->d.number, &u_dev, unit_q, nc * 6 * n3));
+  MGX_TRY(op->mem.upload_as(op->d.number, &w_dev, jxw_q, nc * n3));
   MGX_HIP(hipStreamSynchronize(op->ctx->stream)); // a kernel in flight may read the geometry this call replaces
-  (void)hipFree(op->unit_q);
-  (void)hipFree(op->jxw_q);
+  op->mem.release(op->unit_q);
+  op->mem.release(op->jxw_q);
   op->unit_q      = u_dev;
   op->jxw_q       = w_dev;
   op->coef_update = true;
@@ -2272,14 +2163,14 @@ int mgx_compute_diagonal(mgx_operator_t op)
   const int   n = op->d.p + 1;
   // 1D diagonal factors: G = D*S is the gradient of the nodal basis at the quadrature points
   double a1d[kMaxN], m1d[kMaxN];
+  double G[kMaxN * kMaxN];
+  nodal_gradient(*op, G);
   for (int i = 0; i < n; ++i)
     {
       double a = 0, m = 0;
       for (int q = 0; q < n; ++q)
         {
-          double g = 0;
-          for (int r = 0; r < n; ++r)
-            g += op->D[q * n + r] * op->S[r * n + i];
+          const double g = G[q * n + i];
           a += op->w[q] * g * g;
           m += op->w[q] * op->S[q * n + i] * op->S[q * n + i];
         }
@@ -2295,12 +2186,12 @@ int mgx_compute_diagonal(mgx_operator_t op)
     {
       std::vector<uint32_t> lists, list_start;
       brick_cell_lists(op, lists, list_start);
-      uint32_t *lists_dev = nullptr;
-      MGX_HIP(hipMalloc((void **)&lists_dev, sizeof(uint32_t) * (lists.size() + 1)));
+      DeviceArena tmp("mgx_compute_diagonal");
+      uint32_t   *lists_dev = nullptr;
+      MGX_TRY(tmp.alloc(&lists_dev, lists.size() + 1));
       MGX_HIP(hipMemcpyAsync(lists_dev, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice, s));
       launch_cell_diagonal(s, op->d, op->d.inv_diag, a1d, m1d, lists_dev, list_start.data(), (int)list_start.size() - 1);
       MGX_HIP(hipStreamSynchronize(s));
-      MGX_HIP(hipFree(lists_dev));
     }
   else if (op->d.cell_order)
     launch_cell_diagonal(s, op->d, op->d.inv_diag, a1d, m1d, op->d.cell_order, op->d.cell_colour_start, op->d.n_cell_colours);
@@ -2318,31 +2209,26 @@ int mgx_compute_diagonal(mgx_operator_t op)
     {
       void          *&slot = which == 0 ? op->d.diag_items : op->d.diag_items2;
       const uint32_t *map  = which == 0 ? op->d.bricks.item_map : op->d.bricks.item_map2;
-      if (slot)
-        {
-          MGX_HIP(hipFree(slot));
-          slot = nullptr;
-        }
+      op->mem.release(slot);
+      slot = nullptr;
       if (!map || !op->d.separable || op->ctx->tun.no_diag_table)
         continue;
       const uint32_t nb = op->d.p <= 4 ? 4 : 2, g = nb * op->d.p + 1, npts = g * g * g;
+      DeviceArena    tmp("mgx_compute_diagonal");
       void          *table = nullptr;
       uint32_t      *flag  = nullptr, mismatch = 1;
-      MGX_HIP(hipMalloc(&table, number_size(op->d.number) * npts));
-      MGX_HIP(hipMalloc((void **)&flag, sizeof(uint32_t)));
-      MGX_HIP(hipMemsetAsync(table, 0, number_size(op->d.number) * npts, s));
-      MGX_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), s));
+      MGX_TRY(op->mem.zeros(&table, number_size(op->d.number) * npts, s));
+      MGX_TRY(tmp.zeros(&flag, 1, s));
       if (op->d.number == MGX_F64)
         macro_diag_table_f64(s, op->d, map, table, flag);
       else
         macro_diag_table_f32(s, op->d, map, table, flag);
       MGX_HIP(hipMemcpyAsync(&mismatch, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       MGX_HIP(hipStreamSynchronize(s));
-      MGX_HIP(hipFree(flag));
       if (mismatch == 0)
         slot = table;
       else
-        MGX_HIP(hipFree(table));
+        op->mem.release(table);
       if (which == 0)
         MGX_TRACE("compute_diagonal: diagonal %s per brick item", mismatch == 0 ? "uniform" : "not uniform");
     }
@@ -2376,23 +2262,14 @@ int mgx_smoother_create(mgx_operator_t op, double smoothing_range, int degree, i
   sm->req_range     = smoothing_range;
   sm->req_degree    = degree;
   sm->req_eig_its   = eig_cg_n_iterations;
-  MGX_HIP(hipMalloc(&sm->x_old, bytes));
-  MGX_HIP(hipMalloc(&sm->tmp, bytes));
+  MGX_TRY(sm->mem.alloc(&sm->x_old, bytes));
+  MGX_TRY(sm->mem.alloc(&sm->tmp, bytes));
   // estimate_eigenvalues: PCG(D^-1) on v_i = (i mod 11) - mean; Lanczos tridiagonal
-  void *r = nullptr, *z = nullptr, *d = nullptr, *h = sm->tmp, *x = sm->x_old;
-  struct Scratch
-  {
-    void *&a, *&b, *&c;
-    ~Scratch()
-    {
-      (void)hipFree(a);
-      (void)hipFree(b);
-      (void)hipFree(c);
-    }
-  } scratch{r, z, d};
-  MGX_HIP(hipMalloc(&r, bytes));
-  MGX_HIP(hipMalloc(&z, bytes));
-  MGX_HIP(hipMalloc(&d, bytes));
+  void       *r = nullptr, *z = nullptr, *d = nullptr, *h = sm->tmp, *x = sm->x_old;
+  DeviceArena scratch("mgx_smoother_create");
+  MGX_TRY(scratch.alloc(&r, bytes));
+  MGX_TRY(scratch.alloc(&z, bytes));
+  MGX_TRY(scratch.alloc(&d, bytes));
   {
     // deal.II: v_i = (global index of i) mod 11 minus the global mean
     double sc[2] = {op->start_sum, op->start_count};
@@ -2477,9 +2354,6 @@ int mgx_smoother_destroy(mgx_smoother_t sm)
   if (!sm)
     return MGX_OK;
   (void)hipStreamSynchronize(sm->op->ctx->stream);
-  (void)hipFree(sm->x_old);
-  (void)hipFree(sm->x_old2);
-  (void)hipFree(sm->tmp);
   delete sm;
   return MGX_OK;
 }
@@ -2667,7 +2541,7 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
   // step(): 1 + n_loop iterations starting from X
   const int T = 1 + n_loop;
   if (T % 2 == 1 && T >= 3 && !sm->x_old2)
-    MGX_HIP(hipMalloc(&sm->x_old2, number_size(num) * n));
+    MGX_TRY(sm->mem.alloc(&sm->x_old2, number_size(num) * n));
   void  *Z = sm->x_old2, *cur = X, *old = nullptr;
   double rhok = I.delta / I.theta;
   for (int k = 1; k <= T; ++k)
@@ -2756,8 +2630,7 @@ static int build_interface_transfer(mgx_transfer_s *tr, const mgx_transfer_desc 
         const uint32_t *indf = &idxf[27 * (size_t)desc->children[8 * (size_t)pc + ch]];
         bool            any = false;
         for (int e = 0; e < 27 && !any; ++e)
-          any = indf[e] != kInvalid && indf[e] < fine->d.n_dofs && pos[indf[e]] != kInvalid &&
-                (p > 1 || (e % 3 != 1 && (e / 3) % 3 != 1 && e / 9 != 1));
+          any = indf[e] != kInvalid && indf[e] < fine->d.n_dofs && pos[indf[e]] != kInvalid && entity_size(e, p) != 0;
         if (!any)
           continue;
         for (int iz = 0; iz < n; ++iz)
@@ -2787,24 +2660,11 @@ static int build_interface_transfer(mgx_transfer_s *tr, const mgx_transfer_desc 
   for (uint32_t i = 0; i < nsh; ++i)
     if (!done[i])
       return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: a shared DoF of the fine level lies in no cell");
-  const int    num = fine->d.number;
-  const size_t wsz = number_size(num);
-  auto upload_w = [&](const std::vector<double> &w, void **dev) -> int {
-    MGX_HIP(hipMalloc(dev, wsz * std::max<size_t>(1, w.size())));
-    if (num == MGX_F64)
-      MGX_HIP(hipMemcpy(*dev, w.data(), 8 * w.size(), hipMemcpyHostToDevice));
-    else
-      {
-        std::vector<float> wf(w.begin(), w.end());
-        MGX_HIP(hipMemcpy(*dev, wf.data(), 4 * wf.size(), hipMemcpyHostToDevice));
-      }
-    return MGX_OK;
+  // (an empty list still gets one entry)
+  auto upload_w = [&](const std::vector<double> &w, void **dev) {
+    return tr->mem.upload_as(fine->d.number, dev, w.data(), w.size(), w.empty() ? 1 : 0);
   };
-  auto upload_u = [&](const std::vector<uint32_t> &v, uint32_t **dev) -> int {
-    MGX_HIP(hipMalloc((void **)dev, sizeof(uint32_t) * std::max<size_t>(1, v.size())));
-    MGX_HIP(hipMemcpy(*dev, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice));
-    return MGX_OK;
-  };
+  auto upload_u = [&](const std::vector<uint32_t> &v, uint32_t **dev) { return tr->mem.upload(dev, v, v.empty() ? 1 : 0); };
   // prolongation: rows in the order of the shared list
   {
     std::stable_sort(ent.begin(), ent.end(), [](const Entry &a, const Entry &b) { return a.si < b.si; });
@@ -2898,49 +2758,37 @@ static const char *fused_prolong_blocker(const mgx_transfer_s *tr, const Tunable
   return nullptr;
 }
 
-int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_transfer_desc *desc,
-                        mgx_transfer_t *out)
+} // extern "C"
+
+// The stages of mgx_transfer_create, in the order it calls them; device buffers go to the transfer's arena.
+namespace
 {
-  MGX_REQUIRE(coarse && fine && desc && out && desc->children && desc->prolong_1d,
-              "mgx_transfer_create: null argument");
-  MGX_REQUIRE(coarse->d.p == fine->d.p && coarse->d.number == fine->d.number,
-              "mgx_transfer_create: level operators differ in degree or number type");
-  MGX_REQUIRE(coarse->d.idx27_plain && fine->d.idx27_plain,
-              "mgx_transfer_create: operators were created without idx27_plain");
-  MGX_REQUIRE((uint64_t)coarse->d.n_cells * 8 == fine->d.n_cells,
-              "mgx_transfer_create: fine level must have 8 children per coarse cell (uniform refinement)");
-  const int      p = coarse->d.p, n = p + 1;
-  const uint32_t npar = coarse->d.n_cells;
-  for (size_t i = 0; i < 8 * (size_t)npar; ++i)
-    if (desc->children[i] >= fine->d.n_cells)
-      return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: child index out of range");
-  MGX_TRACE("transfer_create: parents=%u", npar);
   // Is the 1D embedding symmetric under reversal of both indices (P1[2p-a][p-j] == P1[a][j])?  Every mirror-symmetric
   // node set gives one that is.  The pipelined kernels and the fused forms apply it in its even-odd form (Basis1D::P1eo),
   // which holds only what the symmetry leaves of P1: any other embedding runs the first-version kernels, which read P1.
-  bool p1_symmetric = true;
+  bool embedding_is_symmetric(const double *P1, int p)
   {
-    const double *P1    = desc->prolong_1d;
-    double        scale = 0;
+    const int n     = p + 1;
+    double    scale = 0;
     for (size_t i = 0; i < (size_t)(2 * p + 1) * n; ++i)
       scale = std::max(scale, std::fabs(P1[i]));
     for (int a = 0; a <= 2 * p; ++a)
       for (int j = 0; j <= p; ++j)
         if (std::fabs(P1[a * n + j] - P1[(2 * p - a) * n + (p - j)]) > 1e-12 * scale)
-          p1_symmetric = false;
+          return false;
+    return true;
   }
-  auto tr    = std::make_unique<mgx_transfer_s>();
-  tr->coarse = coarse;
-  tr->fine   = fine;
-  tr->d.coarse = &coarse->d;
-  tr->d.colour_min = coarse->ctx->tun.restrict_colour_min;
-  tr->d.fine   = &fine->d;
-  MGX_HIP(hipMalloc((void **)&tr->d.children, sizeof(uint32_t) * 8 * (size_t)npar));
-  MGX_HIP(hipMemcpy(tr->d.children, desc->children, sizeof(uint32_t) * 8 * (size_t)npar, hipMemcpyHostToDevice));
+
   // weights 1/multiplicity (multiplicity = number of parent patches sharing a fine DoF), stored
-  // compressed as 3^3 entries per parent like deal.II does on uniform meshes
+  // compressed as 3^3 entries per parent like deal.II does on uniform meshes, and the ownership of the fine entities.
+  // idxf (the fine level's idx27_plain), shift and own are left on the host for build_patch_table.
+  int build_weights_and_ownership(mgx_transfer_s &tr, const mgx_transfer_desc *desc, std::vector<uint32_t> &idxf,
+                                  std::vector<uint8_t> &shift, std::vector<uint32_t> &own)
   {
-    std::vector<uint32_t> idxf(27 * (size_t)fine->d.n_cells);
+    mgx_operator_t coarse = tr.coarse, fine = tr.fine;
+    const int      p    = coarse->d.p;
+    const uint32_t npar = coarse->d.n_cells;
+    idxf.resize(27 * (size_t)fine->d.n_cells);
     MGX_HIP(hipMemcpy(idxf.data(), fine->d.idx27_plain, sizeof(uint32_t) * idxf.size(), hipMemcpyDeviceToHost));
     std::vector<uint8_t> cnt(fine->d.n_dofs, 0);
     // representative fine DoF of patch entity e = (ca,cb,cc): a child vertex lying in it (low
@@ -2955,7 +2803,7 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
     for (uint32_t pc = 0; pc < npar; ++pc)
       for (int e = 0; e < 27; ++e)
         cnt[rep(pc, e)]++;
-    std::vector<uint8_t> shift(27 * (size_t)npar, 0);
+    shift.assign(27 * (size_t)npar, 0);
     // Multiplicities other than 1/2/4/8 (three blocks of a multi-block mesh around an edge): the
     // restriction then uses OWNER weights -- a shared fine DoF is restricted by the one parent that
     // owns its entity, with weight 1.  Any weights that add up to one over the parents of a fine
@@ -2980,7 +2828,7 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
           return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: fine DoF multiplicities other than 1/2/4/8 together with "
                                            "weight_shift");
         std::fill(shift.begin(), shift.end(), (uint8_t)0);
-        tr->d.owner_weights = true;
+        tr.d.owner_weights = true;
       }
     if (desc->weight_shift) // multiplicities that count the parents of other ranks as well
       {
@@ -2991,17 +2839,15 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
             shift[i] = desc->weight_shift[i];
           }
       }
-    MGX_HIP(hipMalloc((void **)&tr->d.weight_shift, shift.size()));
-    MGX_HIP(hipMemcpy(tr->d.weight_shift, shift.data(), shift.size(), hipMemcpyHostToDevice));
+    MGX_TRY(tr.mem.upload(&tr.d.weight_shift, shift));
     // ownership of the fine entities for the atomic-free prolongation: first cell in cell order
-    std::vector<uint32_t> own(fine->d.n_cells, 0u);
+    own.assign(fine->d.n_cells, 0u);
     {
       std::vector<uint8_t> seen(fine->d.n_dofs, 0);
       for (uint32_t c = 0; c < fine->d.n_cells; ++c)
         for (int e = 0; e < 27; ++e)
           {
-            const int size = (e % 3 == 1 ? p - 1 : 1) * ((e / 3) % 3 == 1 ? p - 1 : 1) * (e / 9 == 1 ? p - 1 : 1);
-            if (size == 0)
+            if (entity_size(e, p) == 0)
               continue;
             const uint32_t base = idxf[27 * (size_t)c + e];
             if (!seen[base])
@@ -3011,308 +2857,367 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
               }
           }
     }
-    MGX_HIP(hipMalloc((void **)&tr->d.own27, sizeof(uint32_t) * own.size()));
-    MGX_HIP(hipMemcpy(tr->d.own27, own.data(), sizeof(uint32_t) * own.size(), hipMemcpyHostToDevice));
-    // patch table of the pipelined kernels (mgx_transfer.hip): the 5^3 mesh entities of the
-    // children patch of every parent.  Patch entity layer 0..4 along a direction = (child 0:
-    // codes 0,1,2 ; child 1: codes 0,1,2) with child 0's code 2 and child 1's code 0 coinciding.
-    if (coarse->ctx->tun.transfer_v1)
-      MGX_TRACE("transfer_create: no patch table, first-version kernels (option transfer_v1)");
-    else if (!p1_symmetric)
-      MGX_TRACE("transfer_create: no patch table, first-version kernels (1D embedding not symmetric under reversal)");
-    else if (fine->d.n_dofs >= (1u << 29))
-      MGX_TRACE("transfer_create: no patch table, first-version kernels (%u fine DoFs: 29-bit index)", fine->d.n_dofs);
-    else
-      {
-        std::vector<uint32_t> patch(125 * (size_t)npar);
-        bool                  consistent = true;
-        // owner weights on a decomposed mesh: a fine entity that a lower rank holds as well is restricted
-        // there; here it enters with weight 0 (the coarse sums are added over the ranks afterwards)
-        std::vector<uint8_t> foreign;
-        if (tr->d.owner_weights && fine->plan)
-          {
-            foreign.assign(fine->d.n_dofs, 0);
-            for (uint32_t i : fine->plan->not_owned_host)
-              foreign[i] = 1;
-          }
-#pragma omp parallel for schedule(static)
-        for (uint32_t pc = 0; pc < npar; ++pc)
-          for (int e = 0; e < 125; ++e)
-            {
-              const int el[3] = {e % 5, (e / 5) % 5, e / 25};
-              int       nopt[3], bit[3][2], code[3][2], cls[3], size = 1;
-              for (int d = 0; d < 3; ++d)
-                {
-                  nopt[d]    = el[d] == 2 ? 2 : 1;
-                  bit[d][0]  = el[d] > 2;
-                  code[d][0] = el[d] - 2 * bit[d][0];
-                  bit[d][1]  = 1; // layer 2 seen from child 1: its code 0
-                  code[d][1] = 0;
-                  cls[d]     = el[d] == 0 ? 0 : (el[d] == 4 ? 2 : 1);
-                  size *= (el[d] % 2 == 1) ? p - 1 : 1;
-                }
-              uint32_t base = 0;
-              bool     owned = false, first = true;
-              for (int oz = 0; oz < nopt[2]; ++oz)
-                for (int oy = 0; oy < nopt[1]; ++oy)
-                  for (int ox = 0; ox < nopt[0]; ++ox)
-                    {
-                      const int      ch = bit[0][ox] | (bit[1][oy] << 1) | (bit[2][oz] << 2);
-                      const int      ce = (code[2][oz] * 3 + code[1][oy]) * 3 + code[0][ox];
-                      const uint32_t fc = desc->children[8 * (size_t)pc + ch];
-                      const uint32_t b  = idxf[27 * (size_t)fc + ce];
-                      if (first)
-                        base = b;
-                      else if (b != base)
-                        consistent = false; // children do not share the entities of the parent's mid planes
-                      first = false;
-                      owned = owned || ((own[fc] >> ce) & 1u);
-                    }
-              uint32_t sh = shift[27 * (size_t)pc + (cls[2] * 3 + cls[1]) * 3 + cls[0]];
-              if (tr->d.owner_weights) // the field then says who restricts the entity: 0 = this parent, 1 = another one
-                sh = (owned && size != 0 && (foreign.empty() || !foreign[base])) ? 0u : 1u;
-              patch[125 * (size_t)pc + e] =
-                size == 0 ? 0u : (base | (sh << 29) | ((owned ? 1u : 0u) << 31));
-            }
-        if (consistent)
-          {
-            MGX_HIP(hipMalloc((void **)&tr->d.patch, sizeof(uint32_t) * patch.size()));
-            MGX_HIP(hipMemcpy(tr->d.patch, patch.data(), sizeof(uint32_t) * patch.size(), hipMemcpyHostToDevice));
-            tr->d.n_cus = context_cus(coarse->ctx);
-            // colouring of the coarse cells by index mod 8 (the parity colouring of a Morton-ordered
-            // mesh): valid if no two cells of one colour share a mesh entity
-            if (npar % 8 == 0 && !coarse->ctx->tun.restrict_atomic)
-              {
-                std::vector<uint32_t> idxc(27 * (size_t)npar);
-                MGX_HIP(hipMemcpy(idxc.data(), coarse->d.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
-                std::vector<uint8_t> mask(coarse->d.n_dofs, 0);
-                bool                 ok = true;
-                for (uint32_t c = 0; c < npar && ok; ++c)
-                  for (int e = 0; e < 27; ++e)
-                    {
-                      const int size = (e % 3 == 1 ? p - 1 : 1) * ((e / 3) % 3 == 1 ? p - 1 : 1) * (e / 9 == 1 ? p - 1 : 1);
-                      if (size == 0 || e == 13)
-                        continue;
-                      uint8_t      &m   = mask[idxc[27 * (size_t)c + e]];
-                      const uint8_t bit = (uint8_t)(1u << (c & 7u));
-                      if (m & bit)
-                        ok = false;
-                      m |= bit;
-                    }
-                tr->d.coarse_coloured = ok;
-              }
-            MGX_TRACE("transfer_create: patch table built, pipelined kernels");
-            if (tr->d.coarse_coloured)
-              MGX_TRACE("transfer_create: coarse colouring yes (parent index mod 8)");
-            else if (npar % 8 != 0)
-              MGX_TRACE("transfer_create: coarse colouring no (%u parents, not a multiple of 8)", npar);
-            else if (coarse->ctx->tun.restrict_atomic)
-              MGX_TRACE("transfer_create: coarse colouring no (option restrict_atomic)");
-            else
-              MGX_TRACE("transfer_create: coarse colouring no (two parents of one colour share an entity)");
-            // the restriction route of launch_t (mgx_transfer.hip)
-            if (tr->d.coarse_coloured && npar >= tr->d.colour_min)
-              MGX_TRACE("transfer_create: restriction in 8 colour launches");
-            else if (coarse->d.asm_start)
-              MGX_TRACE("transfer_create: restriction in one launch, ordered assembly with constraints, atomic adds without");
-            else
-              MGX_TRACE("transfer_create: restriction in one launch, atomic adds");
-          }
-        else
-          MGX_TRACE("transfer_create: no patch table, first-version kernels (children patches inconsistent)");
-      }
+    return tr.mem.upload(&tr.d.own27, own);
   }
+
+  // patch table of the pipelined kernels (mgx_transfer.hip): the 5^3 mesh entities of the
+  // children patch of every parent.  Patch entity layer 0..4 along a direction = (child 0:
+  // codes 0,1,2 ; child 1: codes 0,1,2) with child 0's code 2 and child 1's code 0 coinciding.
+  // With the table: the check of the coarse cells' colouring by index mod 8 and the route of the restriction.
+  int build_patch_table(mgx_transfer_s &tr, const mgx_transfer_desc *desc, bool p1_symmetric, const std::vector<uint32_t> &idxf,
+                        const std::vector<uint8_t> &shift, const std::vector<uint32_t> &own)
+  {
+    mgx_operator_t coarse = tr.coarse, fine = tr.fine;
+    const int      p    = coarse->d.p;
+    const uint32_t npar = coarse->d.n_cells;
+    if (coarse->ctx->tun.transfer_v1)
+      {
+        MGX_TRACE("transfer_create: no patch table, first-version kernels (option transfer_v1)");
+        return MGX_OK;
+      }
+    if (!p1_symmetric)
+      {
+        MGX_TRACE("transfer_create: no patch table, first-version kernels (1D embedding not symmetric under reversal)");
+        return MGX_OK;
+      }
+    if (fine->d.n_dofs >= (1u << 29))
+      {
+        MGX_TRACE("transfer_create: no patch table, first-version kernels (%u fine DoFs: 29-bit index)", fine->d.n_dofs);
+        return MGX_OK;
+      }
+    std::vector<uint32_t> patch(125 * (size_t)npar);
+    bool                  consistent = true;
+    // owner weights on a decomposed mesh: a fine entity that a lower rank holds as well is restricted
+    // there; here it enters with weight 0 (the coarse sums are added over the ranks afterwards)
+    std::vector<uint8_t> foreign;
+    if (tr.d.owner_weights && fine->plan)
+      {
+        foreign.assign(fine->d.n_dofs, 0);
+        for (uint32_t i : fine->plan->not_owned_host)
+          foreign[i] = 1;
+      }
+#pragma omp parallel for schedule(static)
+    for (uint32_t pc = 0; pc < npar; ++pc)
+      for (int e = 0; e < 125; ++e)
+        {
+          const int el[3] = {e % 5, (e / 5) % 5, e / 25};
+          int       nopt[3], bit[3][2], code[3][2], cls[3], size = 1;
+          for (int d = 0; d < 3; ++d)
+            {
+              nopt[d]    = el[d] == 2 ? 2 : 1;
+              bit[d][0]  = el[d] > 2;
+              code[d][0] = el[d] - 2 * bit[d][0];
+              bit[d][1]  = 1; // layer 2 seen from child 1: its code 0
+              code[d][1] = 0;
+              cls[d]     = el[d] == 0 ? 0 : (el[d] == 4 ? 2 : 1);
+              size *= (el[d] % 2 == 1) ? p - 1 : 1;
+            }
+          uint32_t base = 0;
+          bool     owned = false, first = true;
+          for (int oz = 0; oz < nopt[2]; ++oz)
+            for (int oy = 0; oy < nopt[1]; ++oy)
+              for (int ox = 0; ox < nopt[0]; ++ox)
+                {
+                  const int      ch = bit[0][ox] | (bit[1][oy] << 1) | (bit[2][oz] << 2);
+                  const int      ce = (code[2][oz] * 3 + code[1][oy]) * 3 + code[0][ox];
+                  const uint32_t fc = desc->children[8 * (size_t)pc + ch];
+                  const uint32_t b  = idxf[27 * (size_t)fc + ce];
+                  if (first)
+                    base = b;
+                  else if (b != base)
+                    consistent = false; // children do not share the entities of the parent's mid planes
+                  first = false;
+                  owned = owned || ((own[fc] >> ce) & 1u);
+                }
+          uint32_t sh = shift[27 * (size_t)pc + (cls[2] * 3 + cls[1]) * 3 + cls[0]];
+          if (tr.d.owner_weights) // the field then says who restricts the entity: 0 = this parent, 1 = another one
+            sh = (owned && size != 0 && (foreign.empty() || !foreign[base])) ? 0u : 1u;
+          patch[125 * (size_t)pc + e] =
+            size == 0 ? 0u : (base | (sh << 29) | ((owned ? 1u : 0u) << 31));
+        }
+    if (!consistent)
+      {
+        MGX_TRACE("transfer_create: no patch table, first-version kernels (children patches inconsistent)");
+        return MGX_OK;
+      }
+    MGX_TRY(tr.mem.upload(&tr.d.patch, patch));
+    tr.d.n_cus = context_cus(coarse->ctx);
+    // colouring of the coarse cells by index mod 8 (the parity colouring of a Morton-ordered
+    // mesh): valid if no two cells of one colour share a mesh entity
+    if (npar % 8 == 0 && !coarse->ctx->tun.restrict_atomic)
+      {
+        std::vector<uint32_t> idxc(27 * (size_t)npar);
+        MGX_HIP(hipMemcpy(idxc.data(), coarse->d.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
+        std::vector<uint8_t> mask(coarse->d.n_dofs, 0);
+        bool                 ok = true;
+        for (uint32_t c = 0; c < npar && ok; ++c)
+          for (int e = 0; e < 27; ++e)
+            {
+              if (entity_size(e, p) == 0 || e == 13)
+                continue;
+              uint8_t      &m   = mask[idxc[27 * (size_t)c + e]];
+              const uint8_t bit = (uint8_t)(1u << (c & 7u));
+              if (m & bit)
+                ok = false;
+              m |= bit;
+            }
+        tr.d.coarse_coloured = ok;
+      }
+    MGX_TRACE("transfer_create: patch table built, pipelined kernels");
+    if (tr.d.coarse_coloured)
+      MGX_TRACE("transfer_create: coarse colouring yes (parent index mod 8)");
+    else if (npar % 8 != 0)
+      MGX_TRACE("transfer_create: coarse colouring no (%u parents, not a multiple of 8)", npar);
+    else if (coarse->ctx->tun.restrict_atomic)
+      MGX_TRACE("transfer_create: coarse colouring no (option restrict_atomic)");
+    else
+      MGX_TRACE("transfer_create: coarse colouring no (two parents of one colour share an entity)");
+    // the restriction route of launch_t (mgx_transfer.hip)
+    if (tr.d.coarse_coloured && npar >= tr.d.colour_min)
+      MGX_TRACE("transfer_create: restriction in 8 colour launches");
+    else if (coarse->d.asm_start)
+      MGX_TRACE("transfer_create: restriction in one launch, ordered assembly with constraints, atomic adds without");
+    else
+      MGX_TRACE("transfer_create: restriction in one launch, atomic adds");
+    return MGX_OK;
+  }
+
   // 1D prolongation matrix into the basis blocks of both operators (the transfer kernels read the
   // coarse one, the fused residual + restriction of the fine level's cell loop the fine one)
-  const size_t np1 = (size_t)(2 * p + 1) * n;
   // ... and its even-odd form for the line products of the fused forms (Basis1D::P1eo): the embedding of a parent
   // into its two children is symmetric under reversal of both indices for every node set that is
-  std::vector<double> p1eo;
+  int upload_embedding(mgx_transfer_s &tr, const mgx_transfer_desc *desc)
   {
-    const double *P1 = desc->prolong_1d;
-    const int     nh = (p + 1) / 2;
-    p1eo.assign((size_t)(2 * p + 1) * nh + (p + 1), 0.);
-    for (int a = 0; a <= p; ++a)
-      for (int j = 0; j < nh; ++j)
-        {
-          p1eo[(size_t)a * nh + j] = 0.5 * (P1[a * n + j] + P1[a * n + p - j]);
-          if (a < p)
-            p1eo[(size_t)(p + 1 + a) * nh + j] = 0.5 * (P1[a * n + j] - P1[a * n + p - j]);
-        }
-    if (p % 2 == 0)
-      for (int a = 0; a <= p; ++a)
-        p1eo[(size_t)(2 * p + 1) * nh + a] = P1[a * n + p / 2];
-  }
-  for (mgx_operator_t o : {coarse, fine})
+    const int           p = tr.coarse->d.p, n = p + 1;
+    const size_t        np1 = (size_t)(2 * p + 1) * n;
+    std::vector<double> p1eo;
     {
-      if (o->d.number == MGX_F64)
-        {
-          MGX_HIP(hipMemcpy((char *)o->d.basis + offsetof(Basis1D<double>, P1), desc->prolong_1d,
-                            sizeof(double) * np1, hipMemcpyHostToDevice));
-          MGX_HIP(hipMemcpy((char *)o->d.basis + offsetof(Basis1D<double>, P1eo), p1eo.data(), sizeof(double) * p1eo.size(),
-                            hipMemcpyHostToDevice));
-        }
-      else
-        {
-          std::vector<float> pf(desc->prolong_1d, desc->prolong_1d + np1);
-          MGX_HIP(hipMemcpy((char *)o->d.basis + offsetof(Basis1D<float>, P1), pf.data(), sizeof(float) * np1,
-                            hipMemcpyHostToDevice));
-          std::vector<float> pe(p1eo.begin(), p1eo.end());
-          MGX_HIP(hipMemcpy((char *)o->d.basis + offsetof(Basis1D<float>, P1eo), pe.data(), sizeof(float) * pe.size(),
-                            hipMemcpyHostToDevice));
-        }
+      const double *P1 = desc->prolong_1d;
+      const int     nh = (p + 1) / 2;
+      p1eo.assign((size_t)(2 * p + 1) * nh + (p + 1), 0.);
+      for (int a = 0; a <= p; ++a)
+        for (int j = 0; j < nh; ++j)
+          {
+            p1eo[(size_t)a * nh + j] = 0.5 * (P1[a * n + j] + P1[a * n + p - j]);
+            if (a < p)
+              p1eo[(size_t)(p + 1 + a) * nh + j] = 0.5 * (P1[a * n + j] - P1[a * n + p - j]);
+          }
+      if (p % 2 == 0)
+        for (int a = 0; a <= p; ++a)
+          p1eo[(size_t)(2 * p + 1) * nh + a] = P1[a * n + p / 2];
     }
+    for (mgx_operator_t o : {tr.coarse, tr.fine})
+      {
+        const bool   f64 = o->d.number == MGX_F64;
+        const size_t at_p1 = f64 ? offsetof(Basis1D<double>, P1) : offsetof(Basis1D<float>, P1);
+        const size_t at_eo = f64 ? offsetof(Basis1D<double>, P1eo) : offsetof(Basis1D<float>, P1eo);
+        MGX_TRY(tr.mem.copy_as(o->d.number, (char *)o->d.basis + at_p1, desc->prolong_1d, np1));
+        MGX_TRY(tr.mem.copy_as(o->d.number, (char *)o->d.basis + at_eo, p1eo.data(), p1eo.size()));
+      }
+    return MGX_OK;
+  }
+
   // Fused residual + restriction (BrickMode kResidualRestrict): needs the fine level on the brick
   // schedule in its separable form, children in forest order (cell c is child c % 8 of parent
   // c / 8, so that a brick's cells are the children of PB^3 sibling parents) and a single rank.
   // (Degree 7 ran the separate kernels until the line products of the embedding took their even-odd form in round 4:
   // V-cycle at 64^3 cells 10.69 ms separate, 9.70 ms fused; before: 8.86 / 9.36 ms at the clocks of round 2.  Degree 8
   // was in the same position while its fused forms spilled.  The option "force_fused_transfers" is a no-op now.)
-  const bool fused_pays = p1_symmetric;
-  // (decomposed mesh: both levels decomposed alike -- not across an agglomeration -- and interface rows, above)
-  if (fine->d.bricks.available() && fine->d.separable && (!fine->plan == !coarse->plan) && fused_pays &&
-      !coarse->ctx->tun.no_fused_restrict && !(fine->plan && coarse->ctx->tun.no_fused_decomposed))
-    {
-      bool forest = true;
-      for (size_t i = 0; i < 8 * (size_t)npar && forest; ++i)
-        forest = desc->children[i] == (uint32_t)i;
-      const int      PB = p <= 4 ? 2 : 1, CE1 = 2 * PB + 1, CE3 = CE1 * CE1 * CE1;
-      const uint32_t nb = fine->d.bricks.n_bricks, ppb = PB * PB * PB; // parents per brick
-      if (forest && (uint64_t)nb * ppb == npar && fine->d.bricks.order.size() == nb)
-        {
-          std::vector<uint32_t> idxc(27 * (size_t)npar);
-          MGX_HIP(hipMemcpy(idxc.data(), coarse->d.idx27, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
-          std::vector<uint32_t> idxp(27 * (size_t)npar);
-          MGX_HIP(hipMemcpy(idxp.data(), coarse->d.idx27_plain, sizeof(uint32_t) * idxp.size(), hipMemcpyDeviceToHost));
-          std::vector<uint32_t> tab((size_t)nb * CE3);
-          bool                  consistent = true;
-          for (uint32_t sb = 0; sb < nb; ++sb)
-            {
-              const uint32_t b = fine->d.bricks.order[sb]; // brick in cell order: parents ppb*b ...
-              for (int e = 0; e < CE3; ++e)
-                {
-                  const int el[3] = {e % CE1, (e / CE1) % CE1, e / (CE1 * CE1)};
-                  int       nopt[3], bit[3][2], code[3][2];
-                  for (int d = 0; d < 3; ++d)
-                    {
-                      // entity layer el of PB parents in a row: parent el/2 (last layer: the previous
-                      // parent's high side); the layer between two parents is seen from both
-                      nopt[d]    = (PB == 2 && el[d] == 2) ? 2 : 1;
-                      bit[d][0]  = (PB == 2 && el[d] > 2) ? 1 : 0;
-                      code[d][0] = el[d] - 2 * bit[d][0];
-                      bit[d][1]  = 1;
-                      code[d][1] = 0;
-                    }
-                  uint32_t word = 0, key = 0;
-                  bool     first = true;
-                  for (int oz = 0; oz < nopt[2]; ++oz)
-                    for (int oy = 0; oy < nopt[1]; ++oy)
-                      for (int ox = 0; ox < nopt[0]; ++ox)
-                        {
-                          const int      q  = bit[0][ox] | (bit[1][oy] << 1) | (bit[2][oz] << 2);
-                          const int      ce = (code[2][oz] * 3 + code[1][oy]) * 3 + code[0][ox];
-                          const uint32_t pc = ppb * b + (uint32_t)q;
-                          if (first)
-                            {
-                              word = idxc[27 * (size_t)pc + ce];
-                              key  = idxp[27 * (size_t)pc + ce];
-                            }
-                          else if (idxp[27 * (size_t)pc + ce] != key)
-                            consistent = false;
-                          first = false;
-                        }
-                  tab[(size_t)sb * CE3 + e] = word;
-                }
-            }
-          if (consistent && fine->plan)
-            {
-              const int status = build_interface_transfer(tr.get(), desc, idxc);
-              if (status != MGX_OK)
-                {
-                  (void)mgx_transfer_destroy(tr.release());
-                  return status;
-                }
-            }
-          if (consistent)
-            {
-              MGX_HIP(hipMalloc((void **)&tr->d.coarse_blocks, sizeof(uint32_t) * tab.size()));
-              MGX_HIP(hipMemcpy(tr->d.coarse_blocks, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice));
-            }
-          // scratch form of the fused residual + restriction: every brick stores its (PB p + 1)^3 restricted values
-          // in a block of its own; the coarse vector is assembled from the blocks in brick order
-          const uint64_t CN = (uint64_t)PB * p + 1, NC = CN * CN * CN;
-          // (levels on the reduced-colour schedules only: there a colour launch is as long as a brick's latency chain and
-          // one launch instead of eight pays -- 17 M DoFs 179 -> 164 us; on the finest level of C2 the blocks' extra traffic
-          // costs more than the seven launch ramps it saves, 1.184 against 1.138 ms)
-          if (consistent && (uint64_t)nb * NC < 0xFFFFFFF0ull && !coarse->ctx->tun.no_restrict_scratch &&
-              nb <= coarse->ctx->tun.free_max_bricks)
-            {
-              auto layer = [p](int a, int &e, int &o, int &len) {
-                const int q = a / p, rr = a - q * p;
-                e           = 2 * q + (rr != 0);
-                o           = rr ? rr - 1 : 0;
-                len         = rr ? p - 1 : 1;
-              };
-              const uint32_t        ncd = coarse->d.n_dofs;
-              std::vector<uint32_t> start(ncd + 1, 0), dof((size_t)nb * NC, kInvalid);
-#pragma omp parallel for schedule(static)
-              for (uint32_t sb = 0; sb < nb; ++sb)
-                for (uint32_t l = 0; l < NC; ++l)
+  // tab: the block table on the host for build_restrict_scratch, empty where the fused forms have none
+  int build_fused_blocks(mgx_transfer_s &tr, const mgx_transfer_desc *desc, bool p1_symmetric, std::vector<uint32_t> &tab)
+  {
+    mgx_operator_t coarse = tr.coarse, fine = tr.fine;
+    const int      p    = coarse->d.p;
+    const uint32_t npar = coarse->d.n_cells;
+    tab.clear();
+    const bool fused_pays = p1_symmetric;
+    // (decomposed mesh: both levels decomposed alike -- not across an agglomeration -- and interface rows, above)
+    if (!(fine->d.bricks.available() && fine->d.separable && (!fine->plan == !coarse->plan) && fused_pays &&
+          !coarse->ctx->tun.no_fused_restrict && !(fine->plan && coarse->ctx->tun.no_fused_decomposed)))
+      return MGX_OK;
+    bool forest = true;
+    for (size_t i = 0; i < 8 * (size_t)npar && forest; ++i)
+      forest = desc->children[i] == (uint32_t)i;
+    const int      PB = p <= 4 ? 2 : 1, CE1 = 2 * PB + 1, CE3 = CE1 * CE1 * CE1;
+    const uint32_t nb = fine->d.bricks.n_bricks, ppb = PB * PB * PB; // parents per brick
+    if (!(forest && (uint64_t)nb * ppb == npar && fine->d.bricks.order.size() == nb))
+      return MGX_OK;
+    std::vector<uint32_t> idxc(27 * (size_t)npar);
+    MGX_HIP(hipMemcpy(idxc.data(), coarse->d.idx27, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> idxp(27 * (size_t)npar);
+    MGX_HIP(hipMemcpy(idxp.data(), coarse->d.idx27_plain, sizeof(uint32_t) * idxp.size(), hipMemcpyDeviceToHost));
+    tab.resize((size_t)nb * CE3);
+    bool consistent = true;
+    for (uint32_t sb = 0; sb < nb; ++sb)
+      {
+        const uint32_t b = fine->d.bricks.order[sb]; // brick in cell order: parents ppb*b ...
+        for (int e = 0; e < CE3; ++e)
+          {
+            const int el[3] = {e % CE1, (e / CE1) % CE1, e / (CE1 * CE1)};
+            int       nopt[3], bit[3][2], code[3][2];
+            for (int d = 0; d < 3; ++d)
+              {
+                // entity layer el of PB parents in a row: parent el/2 (last layer: the previous
+                // parent's high side); the layer between two parents is seen from both
+                nopt[d]    = (PB == 2 && el[d] == 2) ? 2 : 1;
+                bit[d][0]  = (PB == 2 && el[d] > 2) ? 1 : 0;
+                code[d][0] = el[d] - 2 * bit[d][0];
+                bit[d][1]  = 1;
+                code[d][1] = 0;
+              }
+            uint32_t word = 0, key = 0;
+            bool     first = true;
+            for (int oz = 0; oz < nopt[2]; ++oz)
+              for (int oy = 0; oy < nopt[1]; ++oy)
+                for (int ox = 0; ox < nopt[0]; ++ox)
                   {
-                    const int x = (int)(l % CN), y = (int)((l / CN) % CN), z = (int)(l / (CN * CN));
-                    int       ex, ey, ez, ox, oy, oz, nx, ny, nz;
-                    layer(x, ex, ox, nx);
-                    layer(y, ey, oy, ny);
-                    layer(z, ez, oz, nz);
-                    const uint32_t w = tab[(size_t)sb * CE3 + (size_t)((ez * CE1 + ey) * CE1 + ex)];
-                    if (w != kInvalid)
-                      dof[(size_t)sb * NC + l] = w + (uint32_t)((oz * ny + oy) * nx + ox);
+                    const int      q  = bit[0][ox] | (bit[1][oy] << 1) | (bit[2][oz] << 2);
+                    const int      ce = (code[2][oz] * 3 + code[1][oy]) * 3 + code[0][ox];
+                    const uint32_t pc = ppb * b + (uint32_t)q;
+                    if (first)
+                      {
+                        word = idxc[27 * (size_t)pc + ce];
+                        key  = idxp[27 * (size_t)pc + ce];
+                      }
+                    else if (idxp[27 * (size_t)pc + ce] != key)
+                      consistent = false;
+                    first = false;
                   }
-              for (uint32_t d : dof)
-                if (d != kInvalid)
-                  start[d + 1]++;
-              for (uint32_t d = 0; d < ncd; ++d)
-                start[d + 1] += start[d];
-              std::vector<uint32_t> pos(start[ncd]), fill(start.begin(), start.end() - 1);
-              for (size_t k = 0; k < dof.size(); ++k) // ascending position = ascending brick: the order of the sums
-                if (dof[k] != kInvalid)
-                  pos[fill[dof[k]]++] = (uint32_t)k;
-              MGX_HIP(hipMalloc(&tr->d.coarse_scratch, number_size(fine->d.number) * (size_t)nb * NC));
-              MGX_HIP(hipMemset(tr->d.coarse_scratch, 0, number_size(fine->d.number) * (size_t)nb * NC));
-              MGX_HIP(hipMalloc((void **)&tr->d.cs_start, sizeof(uint32_t) * start.size()));
-              MGX_HIP(hipMemcpy(tr->d.cs_start, start.data(), sizeof(uint32_t) * start.size(), hipMemcpyHostToDevice));
-              MGX_HIP(hipMalloc((void **)&tr->d.cs_pos, sizeof(uint32_t) * std::max<size_t>(1, pos.size())));
-              MGX_HIP(hipMemcpy(tr->d.cs_pos, pos.data(), sizeof(uint32_t) * pos.size(), hipMemcpyHostToDevice));
-            }
+            tab[(size_t)sb * CE3 + e] = word;
+          }
+      }
+    if (!consistent)
+      {
+        tab.clear();
+        return MGX_OK;
+      }
+    if (fine->plan)
+      MGX_TRY(build_interface_transfer(&tr, desc, idxc));
+    return tr.mem.upload(&tr.d.coarse_blocks, tab);
+  }
+
+  // scratch form of the fused residual + restriction: every brick stores its (PB p + 1)^3 restricted values
+  // in a block of its own; the coarse vector is assembled from the blocks in brick order
+  int build_restrict_scratch(mgx_transfer_s &tr, const std::vector<uint32_t> &tab)
+  {
+    mgx_operator_t coarse = tr.coarse, fine = tr.fine;
+    const int      p  = coarse->d.p;
+    const int      PB = p <= 4 ? 2 : 1, CE1 = 2 * PB + 1, CE3 = CE1 * CE1 * CE1;
+    const uint32_t nb = fine->d.bricks.n_bricks;
+    const uint64_t CN = (uint64_t)PB * p + 1, NC = CN * CN * CN;
+    // (levels on the reduced-colour schedules only: there a colour launch is as long as a brick's latency chain and
+    // one launch instead of eight pays -- 17 M DoFs 179 -> 164 us; on the finest level of C2 the blocks' extra traffic
+    // costs more than the seven launch ramps it saves, 1.184 against 1.138 ms)
+    if (tab.empty() || !((uint64_t)nb * NC < 0xFFFFFFF0ull && !coarse->ctx->tun.no_restrict_scratch &&
+                         nb <= coarse->ctx->tun.free_max_bricks))
+      return MGX_OK;
+    auto layer = [p](int a, int &e, int &o, int &len) {
+      const int q = a / p, rr = a - q * p;
+      e           = 2 * q + (rr != 0);
+      o           = rr ? rr - 1 : 0;
+      len         = rr ? p - 1 : 1;
+    };
+    const uint32_t        ncd = coarse->d.n_dofs;
+    std::vector<uint32_t> start(ncd + 1, 0), dof((size_t)nb * NC, kInvalid);
+#pragma omp parallel for schedule(static)
+    for (uint32_t sb = 0; sb < nb; ++sb)
+      for (uint32_t l = 0; l < NC; ++l)
+        {
+          const int x = (int)(l % CN), y = (int)((l / CN) % CN), z = (int)(l / (CN * CN));
+          int       ex, ey, ez, ox, oy, oz, nx, ny, nz;
+          layer(x, ex, ox, nx);
+          layer(y, ey, oy, ny);
+          layer(z, ez, oz, nz);
+          const uint32_t w = tab[(size_t)sb * CE3 + (size_t)((ez * CE1 + ey) * CE1 + ex)];
+          if (w != kInvalid)
+            dof[(size_t)sb * NC + l] = w + (uint32_t)((oz * ny + oy) * nx + ox);
         }
-    }
-  if (trace_on())
-    {
-      // why the block table of the fused forms is missing (the tables' own conditions are checked above)
-      const char *no_blocks = !p1_symmetric                        ? "1D embedding not symmetric under reversal"
-                              : coarse->ctx->tun.no_fused_restrict ? "option no_fused_restrict"
-                              : !fine->d.bricks.available()        ? "fine level without bricks"
-                                                                   : "fine level not separable, not in forest order or decomposed differently";
-      const char *r = fused_restrict_blocker(tr.get(), coarse->ctx->tun), *q = fused_prolong_blocker(tr.get(), coarse->ctx->tun, 1);
-      if (r)
-        MGX_TRACE("transfer_create: fused residual + restriction no (%s)", tr->d.coarse_blocks ? r : no_blocks);
-      else
-        MGX_TRACE("transfer_create: fused residual + restriction yes (%s)", tr->d.coarse_scratch ? "scratch form" : "colour launches");
-      if (q)
-        MGX_TRACE("transfer_create: fused prolongation no (%s)", tr->d.coarse_blocks ? q : no_blocks);
-      else
-        MGX_TRACE("transfer_create: fused prolongation yes (with a smoother of degree >= 1)");
-    }
+    for (uint32_t d : dof)
+      if (d != kInvalid)
+        start[d + 1]++;
+    for (uint32_t d = 0; d < ncd; ++d)
+      start[d + 1] += start[d];
+    std::vector<uint32_t> pos(start[ncd]), fill(start.begin(), start.end() - 1);
+    for (size_t k = 0; k < dof.size(); ++k) // ascending position = ascending brick: the order of the sums
+      if (dof[k] != kInvalid)
+        pos[fill[dof[k]]++] = (uint32_t)k;
+    const size_t scratch_bytes = number_size(fine->d.number) * (size_t)nb * NC;
+    MGX_TRY(tr.mem.alloc(&tr.d.coarse_scratch, scratch_bytes));
+    MGX_HIP(hipMemset(tr.d.coarse_scratch, 0, scratch_bytes));
+    MGX_TRY(tr.mem.upload(&tr.d.cs_start, start));
+    return tr.mem.upload(&tr.d.cs_pos, pos, pos.empty() ? 1 : 0);
+  }
+
+  // which of the fused transfer forms the V-cycle will run on this level pair, and why not
+  void trace_transfer_routes(const mgx_transfer_s &tr, bool p1_symmetric)
+  {
+    if (!trace_on())
+      return;
+    mgx_operator_t coarse = tr.coarse, fine = tr.fine;
+    // why the block table of the fused forms is missing (the tables' own conditions are checked above)
+    const char *no_blocks = !p1_symmetric                        ? "1D embedding not symmetric under reversal"
+                            : coarse->ctx->tun.no_fused_restrict ? "option no_fused_restrict"
+                            : !fine->d.bricks.available()        ? "fine level without bricks"
+                                                                 : "fine level not separable, not in forest order or decomposed differently";
+    const char *r = fused_restrict_blocker(&tr, coarse->ctx->tun), *q = fused_prolong_blocker(&tr, coarse->ctx->tun, 1);
+    if (r)
+      MGX_TRACE("transfer_create: fused residual + restriction no (%s)", tr.d.coarse_blocks ? r : no_blocks);
+    else
+      MGX_TRACE("transfer_create: fused residual + restriction yes (%s)", tr.d.coarse_scratch ? "scratch form" : "colour launches");
+    if (q)
+      MGX_TRACE("transfer_create: fused prolongation no (%s)", tr.d.coarse_blocks ? q : no_blocks);
+    else
+      MGX_TRACE("transfer_create: fused prolongation yes (with a smoother of degree >= 1)");
+  }
+} // namespace
+
+extern "C" {
+
+int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_transfer_desc *desc,
+                        mgx_transfer_t *out)
+{
+  MGX_REQUIRE(coarse && fine && desc && out && desc->children && desc->prolong_1d,
+              "mgx_transfer_create: null argument");
+  MGX_REQUIRE(coarse->d.p == fine->d.p && coarse->d.number == fine->d.number,
+              "mgx_transfer_create: level operators differ in degree or number type");
+  MGX_REQUIRE(coarse->d.idx27_plain && fine->d.idx27_plain,
+              "mgx_transfer_create: operators were created without idx27_plain");
+  MGX_REQUIRE((uint64_t)coarse->d.n_cells * 8 == fine->d.n_cells,
+              "mgx_transfer_create: fine level must have 8 children per coarse cell (uniform refinement)");
+  const uint32_t npar = coarse->d.n_cells;
+  for (size_t i = 0; i < 8 * (size_t)npar; ++i)
+    if (desc->children[i] >= fine->d.n_cells)
+      return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: child index out of range");
+  MGX_TRACE("transfer_create: parents=%u", npar);
+  const bool p1_symmetric = embedding_is_symmetric(desc->prolong_1d, coarse->d.p);
+  // failures below return through the destroy function, which frees what the transfer's arena holds by then
+  std::unique_ptr<mgx_transfer_s, int (*)(mgx_transfer_t)> tr(new mgx_transfer_s, mgx_transfer_destroy);
+  tr->coarse = coarse;
+  tr->fine   = fine;
+  tr->d.coarse = &coarse->d;
+  tr->d.colour_min = coarse->ctx->tun.restrict_colour_min;
+  tr->d.fine   = &fine->d;
+  MGX_TRY(tr->mem.upload(&tr->d.children, desc->children, 8 * (size_t)npar));
+  {
+    std::vector<uint32_t> idxf, own; // fine idx27_plain, entity ownership of the fine cells
+    std::vector<uint8_t>  shift;
+    MGX_TRY(build_weights_and_ownership(*tr, desc, idxf, shift, own));
+    MGX_TRY(build_patch_table(*tr, desc, p1_symmetric, idxf, shift, own));
+  }
+  MGX_TRY(upload_embedding(*tr, desc));
+  {
+    std::vector<uint32_t> tab; // block table of the fused forms
+    MGX_TRY(build_fused_blocks(*tr, desc, p1_symmetric, tab));
+    MGX_TRY(build_restrict_scratch(*tr, tab));
+  }
+  trace_transfer_routes(*tr, p1_symmetric);
   if (tr->d.owner_weights && !tr->d.patch)
-    {
-      std::unique_ptr<mgx_transfer_s, int (*)(mgx_transfer_t)> guard(tr.release(), mgx_transfer_destroy);
-      return fail(MGX_ERR_UNSUPPORTED,
-                  !p1_symmetric ? "mgx_transfer_create: owner weights need the pipelined transfer kernels, which need a 1D embedding "
-                                  "symmetric under reversal"
-                  : coarse->ctx->tun.transfer_v1
-                    ? "mgx_transfer_create: owner weights need the pipelined transfer kernels (option transfer_v1 is set)"
-                    : "mgx_transfer_create: owner weights need the pipelined transfer kernels (fine level below 2^29 DoFs)");
-    }
+    return fail(MGX_ERR_UNSUPPORTED,
+                !p1_symmetric ? "mgx_transfer_create: owner weights need the pipelined transfer kernels, which need a 1D embedding "
+                                "symmetric under reversal"
+                : coarse->ctx->tun.transfer_v1
+                  ? "mgx_transfer_create: owner weights need the pipelined transfer kernels (option transfer_v1 is set)"
+                  : "mgx_transfer_create: owner weights need the pipelined transfer kernels (fine level below 2^29 DoFs)");
   *out = tr.release();
   return MGX_OK;
 }
@@ -3322,20 +3227,6 @@ int mgx_transfer_destroy(mgx_transfer_t tr)
   if (!tr)
     return MGX_OK;
   (void)hipStreamSynchronize(tr->coarse->ctx->stream);
-  (void)hipFree(tr->d.children);
-  (void)hipFree(tr->d.weight_shift);
-  (void)hipFree(tr->d.own27);
-  (void)hipFree(tr->interp_1d);
-  (void)hipFree(tr->own_coarse);
-  (void)hipFree(tr->d.patch);
-  (void)hipFree(tr->d.coarse_blocks);
-  (void)hipFree(tr->d.coarse_scratch);
-  (void)hipFree(tr->d.cs_start);
-  (void)hipFree(tr->d.cs_pos);
-  for (void *q : {(void *)tr->d.ifr_cdof, (void *)tr->d.ifr_start, (void *)tr->d.ifr_fdof, tr->d.ifr_w, (void *)tr->d.ifp_start,
-                  (void *)tr->d.ifp_cdof, tr->d.ifp_w})
-    (void)hipFree(q);
-  (void)hipFree(tr->scratch);
   delete tr;
   return MGX_OK;
 }
@@ -3364,7 +3255,7 @@ int mgx_restrict_and_add(mgx_transfer_t tr, void *coarse, const void *fine, int 
   // per sharing rank)
   const size_t bytes = number_size(cop->d.number) * cop->d.n_dofs;
   if (!tr->scratch)
-    MGX_HIP(hipMalloc(&tr->scratch, bytes));
+    MGX_TRY(tr->mem.alloc(&tr->scratch, bytes));
   MGX_HIP(hipMemsetAsync(tr->scratch, 0, bytes, s));
   launch_restrict_add(s, tr->d, tr->scratch, fine, with_constraints != 0);
   MGX_TRY(exchange_add(cop, tr->scratch));
@@ -3443,8 +3334,7 @@ int mgx_interpolate_to_coarse(mgx_transfer_t tr, void *coarse, const void *fine)
       for (uint32_t c = 0; c < cop->d.n_cells; ++c)
         for (int e = 0; e < 27; ++e)
           {
-            const int size = (e % 3 == 1 ? p - 1 : 1) * ((e / 3) % 3 == 1 ? p - 1 : 1) * (e / 9 == 1 ? p - 1 : 1);
-            if (size == 0)
+            if (entity_size(e, p) == 0)
               continue;
             const uint32_t base = idxc[27 * (size_t)c + e];
             MGX_REQUIRE(base < cop->d.n_dofs, "mgx_interpolate_to_coarse: index table out of range");
@@ -3454,17 +3344,8 @@ int mgx_interpolate_to_coarse(mgx_transfer_t tr, void *coarse, const void *fine)
                 own[c] |= 1u << e;
               }
           }
-      const size_t bytes = number_size(cop->d.number) * r.size();
-      MGX_HIP(hipMalloc(&tr->interp_1d, bytes));
-      if (cop->d.number == MGX_F64)
-        MGX_HIP(hipMemcpy(tr->interp_1d, r.data(), bytes, hipMemcpyHostToDevice));
-      else
-        {
-          const std::vector<float> rf(r.begin(), r.end());
-          MGX_HIP(hipMemcpy(tr->interp_1d, rf.data(), bytes, hipMemcpyHostToDevice));
-        }
-      MGX_HIP(hipMalloc((void **)&tr->own_coarse, sizeof(uint32_t) * own.size()));
-      MGX_HIP(hipMemcpy(tr->own_coarse, own.data(), sizeof(uint32_t) * own.size(), hipMemcpyHostToDevice));
+      MGX_TRY(tr->mem.upload(&tr->own_coarse, own));
+      MGX_TRY(tr->mem.upload_as(cop->d.number, &tr->interp_1d, r.data(), r.size())); // (last: it marks the tables as built)
     }
   launch_interpolate_to_coarse(s, tr->d, tr->interp_1d, tr->own_coarse, coarse, fine);
   MGX_HIP(hipGetLastError());
@@ -3501,40 +3382,14 @@ int mgx_solver_destroy(mgx_solver_t S)
   (void)hipStreamSynchronize(S->ctx->stream);
   for (auto sm : S->smooth)
     mgx_smoother_destroy(sm);
-  for (auto p : S->solution)
-    (void)hipFree(p);
-  for (auto p : S->rhs)
-    (void)hipFree(p);
-  for (auto p : S->residual)
-    (void)hipFree(p);
-  for (auto p : S->defect)
-    (void)hipFree(p);
-  for (auto p : S->t)
-    (void)hipFree(p);
-  for (auto p : S->solution_update)
-    (void)hipFree(p);
-  for (auto p : S->bc_index_dev)
-    (void)hipFree(p);
-  for (auto p : S->bc_value_dev)
-    (void)hipFree(p);
-  for (auto p : S->bc_zero_dev)
-    (void)hipFree(p);
   if (S->graph_exec)
     (void)hipGraphExecDestroy(S->graph_exec);
   if (S->graph)
     (void)hipGraphDestroy(S->graph);
-  (void)hipFree(S->agg_map);
-  (void)hipFree(S->agg_owned);
   if (S->agg_in)
     (void)hipEventDestroy(S->agg_in);
   if (S->agg_out)
     (void)hipEventDestroy(S->agg_out);
-  for (auto p : S->nl_state)
-    (void)hipFree(p);
-  (void)hipFree(S->cg_r);
-  (void)hipFree(S->cg_z);
-  (void)hipFree(S->cg_d);
-  (void)hipFree(S->cg_h);
   delete S;
   return MGX_OK;
 }
@@ -3574,42 +3429,32 @@ int mgx_solver_create(mgx_context_t ctx, const mgx_solver_desc *desc, mgx_solver
       const size_t n = desc->matrix[l]->d.n_dofs;
       double      *p = nullptr;
       void        *q = nullptr;
-      MGX_HIP(hipMalloc((void **)&p, 8 * n));
-      MGX_HIP(hipMemsetAsync(p, 0, 8 * n, ctx->stream));
+      MGX_TRY(S->mem.zeros(&p, n, ctx->stream));
       S->solution.push_back(p);
-      MGX_HIP(hipMalloc((void **)&p, 8 * n));
       if (desc->rhs && desc->rhs[l])
         {
-          MGX_HIP(hipMemcpy(p, desc->rhs[l], 8 * n, hipMemcpyHostToDevice));
+          MGX_TRY(S->mem.upload(&p, desc->rhs[l], n));
           // a rank assembles the rhs over its own cells: complete the interface entries
           // (dst.compress(add) in compute_residual, laplace_operator.h:843)
           MGX_TRY(exchange_add(desc->matrix_dp[l], p));
         }
       else // assembled on the device afterwards: mgx_solver_compute_rhs
-        MGX_HIP(hipMemsetAsync(p, 0, 8 * n, ctx->stream));
+        MGX_TRY(S->mem.zeros(&p, n, ctx->stream));
       S->rhs.push_back(p);
-      MGX_HIP(hipMalloc((void **)&p, 8 * n));
-      MGX_HIP(hipMemsetAsync(p, 0, 8 * n, ctx->stream));
+      MGX_TRY(S->mem.zeros(&p, n, ctx->stream));
       S->residual.push_back(p);
       const size_t vb = number_size(S->vnumber) * n;
-      MGX_HIP(hipMalloc(&q, vb));
-      MGX_HIP(hipMemsetAsync(q, 0, vb, ctx->stream));
+      MGX_TRY(S->mem.zeros(&q, vb, ctx->stream));
       S->defect.push_back(q);
-      MGX_HIP(hipMalloc(&q, vb));
-      MGX_HIP(hipMemsetAsync(q, 0, vb, ctx->stream));
+      MGX_TRY(S->mem.zeros(&q, vb, ctx->stream));
       S->t.push_back(q);
-      MGX_HIP(hipMalloc(&q, vb));
-      MGX_HIP(hipMemsetAsync(q, 0, vb, ctx->stream));
+      MGX_TRY(S->mem.zeros(&q, vb, ctx->stream));
       S->solution_update.push_back(q);
       // inhomogeneous boundary values (multigrid_solver.h:225-253)
       const uint32_t nb = desc->bc_count[l];
       S->bc_count.push_back(nb);
       uint32_t *bi = nullptr;
       double   *bv = nullptr, *bz = nullptr;
-      MGX_HIP(hipMalloc((void **)&bi, sizeof(uint32_t) * (nb + 1)));
-      MGX_HIP(hipMalloc((void **)&bv, sizeof(double) * (nb + 1)));
-      MGX_HIP(hipMalloc((void **)&bz, sizeof(double) * (nb + 1)));
-      MGX_HIP(hipMemsetAsync(bz, 0, sizeof(double) * (nb + 1), ctx->stream));
       if (nb)
         {
           MGX_REQUIRE(desc->bc_index && desc->bc_value && desc->bc_index[l] && desc->bc_value[l],
@@ -3617,9 +3462,10 @@ int mgx_solver_create(mgx_context_t ctx, const mgx_solver_desc *desc, mgx_solver
           for (uint32_t i = 0; i < nb; ++i)
             if (desc->bc_index[l][i] >= n)
               return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_solver_create: boundary index out of range");
-          MGX_HIP(hipMemcpy(bi, desc->bc_index[l], sizeof(uint32_t) * nb, hipMemcpyHostToDevice));
-          MGX_HIP(hipMemcpy(bv, desc->bc_value[l], sizeof(double) * nb, hipMemcpyHostToDevice));
         }
+      MGX_TRY(S->mem.upload(&bi, nb ? desc->bc_index[l] : nullptr, nb, 1));
+      MGX_TRY(S->mem.upload(&bv, nb ? desc->bc_value[l] : nullptr, nb, 1));
+      MGX_TRY(S->mem.zeros(&bz, (size_t)nb + 1, ctx->stream));
       S->bc_index_dev.push_back(bi);
       S->bc_value_dev.push_back(bv);
       S->bc_zero_dev.push_back(bz);
@@ -3644,10 +3490,8 @@ int mgx_solver_create(mgx_context_t ctx, const mgx_solver_desc *desc, mgx_solver
           S->graph_level = l;
     }
   const size_t nmax = S->matrix[nl - 1]->d.n_dofs;
-  MGX_HIP(hipMalloc((void **)&S->cg_r, 8 * nmax));
-  MGX_HIP(hipMalloc((void **)&S->cg_z, 8 * nmax));
-  MGX_HIP(hipMalloc((void **)&S->cg_d, 8 * nmax));
-  MGX_HIP(hipMalloc((void **)&S->cg_h, 8 * nmax));
+  for (double **v : {&S->cg_r, &S->cg_z, &S->cg_d, &S->cg_h})
+    MGX_TRY(S->mem.alloc(v, nmax));
   *out = S.release();
   return MGX_OK;
 }
@@ -3770,10 +3614,8 @@ int mgx_solver_set_agglomeration(mgx_solver_t S, int level, mgx_solver_t coarse,
   for (uint32_t i = 0; i < n_local; ++i)
     if (local_to_global[i] >= ng)
       return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_solver_set_agglomeration: map entry out of range");
-  MGX_HIP(hipMalloc((void **)&S->agg_map, sizeof(uint32_t) * ((size_t)n_local + 1)));
-  MGX_HIP(hipMalloc((void **)&S->agg_owned, (size_t)n_local + 1));
-  MGX_HIP(hipMemcpy(S->agg_map, local_to_global, sizeof(uint32_t) * n_local, hipMemcpyHostToDevice));
-  MGX_HIP(hipMemcpy(S->agg_owned, owned, n_local, hipMemcpyHostToDevice));
+  MGX_TRY(S->mem.upload(&S->agg_map, local_to_global, n_local, 1));
+  MGX_TRY(S->mem.upload(&S->agg_owned, owned, n_local, 1));
   MGX_HIP(hipEventCreateWithFlags(&S->agg_in, hipEventDisableTiming));
   MGX_HIP(hipEventCreateWithFlags(&S->agg_out, hipEventDisableTiming));
   // the copy runs in line with the decomposed levels: on their stream (no event hops around its graph)
@@ -3935,13 +3777,12 @@ int mgx_solver_compute_rhs(mgx_solver_t S, int level, const double *rhs_q)
   MGX_REQUIRE(S && level >= 0 && level < S->n_levels, "mgx_solver_compute_rhs: bad argument");
   // the boundary values in a vector of their own (the level's solution vector is the caller's)
   mgx_operator_t A = S->matrix_dp[level];
+  DeviceArena    tmp("mgx_solver_compute_rhs");
   double        *u = nullptr;
-  MGX_HIP(hipMalloc((void **)&u, 8 * (size_t)A->d.n_dofs));
-  MGX_HIP(hipMemsetAsync(u, 0, 8 * (size_t)A->d.n_dofs, S->ctx->stream));
+  MGX_TRY(tmp.zeros(&u, A->d.n_dofs, S->ctx->stream));
   set_bc(S, level, u, false);
   const int status = mgx_compute_residual(A, S->rhs[level], u, rhs_q);
   (void)hipStreamSynchronize(S->ctx->stream);
-  (void)hipFree(u);
   return status;
 }
 
@@ -4176,8 +4017,8 @@ static int residual_update(mgx_solver_t S, double *residual, double *update, dou
     return fail(MGX_ERR_UNSUPPORTED, "mgx_solver_vmult_with_residual_update: single rank only");
   if (!A->cg_partials)
     {
-      MGX_HIP(hipMalloc((void **)&A->cg_partials, sizeof(double) * 4 * (1u << 16)));
-      MGX_HIP(hipMalloc((void **)&A->cg_result, sizeof(double) * 4));
+      MGX_TRY(A->mem.alloc(&A->cg_partials, 4 * (size_t)(1u << 16)));
+      MGX_TRY(A->mem.alloc(&A->cg_result, 4));
     }
   const size_t n_free = n - A->d.n_constrained;
   launch_residual_pre(s, S->vnumber, S->defect[lmax], residual, update, factor, n); // :527-534
@@ -4365,7 +4206,7 @@ int mgx_solver_update_coefficient(mgx_solver_t S, int law, const double *state_f
         {
           const size_t n = S->matrix_dp[l]->d.n_dofs;
           if (l < lmax)
-            MGX_HIP(hipMalloc((void **)&S->nl_state[l], 8 * n));
+            MGX_TRY(S->mem.alloc(&S->nl_state[l], n));
         }
     }
   // :425-457 (the reference interpolates in the level number type; here in fp64)

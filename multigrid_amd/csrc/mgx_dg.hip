@@ -19,6 +19,7 @@
 // Dirichlet faces: a table of at most 64 x (p+1)^3 values replaces the reference's per-cell
 // stream, so the fused Chebyshev step moves 4 vector accesses per DoF (source, right-hand side,
 // old iterate, new iterate) where the reference's model counts 5 (matvec_dg_cheby/program.cc:178).
+#include "mgx_device_memory.hpp"
 #include "mgx_internal.hpp"
 
 #include "../../include/mgx_dg.h"
@@ -1675,7 +1676,8 @@ namespace
 
 struct mgx_dg_operator_s
 {
-  mgx_context_t ctx    = nullptr;
+  mgx_context_t    ctx = nullptr;
+  mgx::DeviceArena mem{"mgx_dg_operator"};
   int           degree = 0, basis = 0, number = MGX_F32;
   uint32_t      n_cells = 0;
   int32_t      *neigh   = nullptr; // device
@@ -1709,6 +1711,7 @@ struct mgx_dg_operator_s
 struct mgx_dg_solver_s
 {
   mgx_context_t     ctx = nullptr;
+  mgx::DeviceArena  mem{"mgx_dg_solver"};
   mgx_dg_operator_t A = nullptr, A_dp = nullptr;
   mgx_solver_t      cfe = nullptr;
   int               degree = 0, number = MGX_F32;
@@ -1729,24 +1732,6 @@ struct mgx_dg_solver_s
 namespace
 {
   int dg_fail(int code, const std::string &msg) { return mgx::report_error(code, msg.c_str()); }
-
-#define DG_HIP(call)                                                                       \
-  do                                                                                       \
-    {                                                                                      \
-      hipError_t e_ = (call);                                                              \
-      if (e_ != hipSuccess)                                                                \
-        return dg_fail(MGX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));    \
-    }                                                                                      \
-  while (0)
-
-#define MGX_DG_TRY(call) \
-  do                     \
-    {                    \
-      int s_ = (call);   \
-      if (s_ != MGX_OK)  \
-        return s_;       \
-    }                    \
-  while (0)
 
   template <typename T>
   __global__ void __launch_bounds__(256)
@@ -1809,7 +1794,7 @@ namespace
           hipLaunchKernelGGL(k_pack_cells<float>, dim3(grid), dim3(256), 0, s, (float *)op->nb_send[k], (const float *)vec,
                              op->nb_cells_dev[k], op->nb_count[k], n3);
       }
-    DG_HIP(hipGetLastError());
+    MGX_HIP(hipGetLastError());
     return MGX_OK;
   }
 
@@ -1830,7 +1815,7 @@ namespace
   {
     if (op->n_ghost == 0)
       return MGX_OK;
-    MGX_DG_TRY(ghosts_pack(op, vec));
+    MGX_TRY(ghosts_pack(op, vec));
     return ghosts_exchange(op, vec, nullptr);
   }
 
@@ -1874,7 +1859,7 @@ namespace
                         (float)f2, iteration_index, m.cell_stride, m.partials, (float *)m.cg, m.idx27, (const float *)m.P1, m.plain};
         launch_degree<float>(s, op->degree, op->basis, action, a, op->n_ghost > 0);
       }
-    DG_HIP(hipGetLastError());
+    MGX_HIP(hipGetLastError());
     return MGX_OK;
   }
 
@@ -1887,12 +1872,12 @@ namespace
     if (!with_ghosts || op->n_ghost == 0)
       return launch_cells(op, action, dst, rhs, src, f1, f2, iteration_index, nullptr, op->n_cells, nullptr, 0, m);
     void *ghosted = const_cast<void *>(src);
-    MGX_DG_TRY(ghosts_pack(op, src));
+    MGX_TRY(ghosts_pack(op, src));
     hipStream_t side = (op->n_interior > 0 && !mgx::context_tunables(op->ctx).dg_no_overlap) ? mgx::side_stream_begin(op->ctx)
                                                                                                : nullptr;
     if (!side)
       {
-        MGX_DG_TRY(ghosts_exchange(op, ghosted, nullptr));
+        MGX_TRY(ghosts_exchange(op, ghosted, nullptr));
         return launch_cells(op, action, dst, rhs, src, f1, f2, iteration_index, nullptr, op->n_cells, nullptr, 0, m);
       }
     // main stream: interior cells; side stream: exchange, then the cells next to a ghost cell (they
@@ -1967,7 +1952,8 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
         return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: the exchange plan does not fill every ghost cell "
                                                  "exactly once");
     }
-  std::unique_ptr<mgx_dg_operator_s> op(new mgx_dg_operator_s);
+  // failures below return through the destroy function, which frees what the operator's arena holds by then
+  std::unique_ptr<mgx_dg_operator_s, int (*)(mgx_dg_operator_t)> op(new mgx_dg_operator_s, mgx_dg_operator_destroy);
   op->ctx     = ctx;
   op->degree  = desc->degree;
   op->basis   = desc->basis;
@@ -2012,34 +1998,7 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
           table[cat * n3 + i] = 1.0 / diag[i];
         }
     }
-  hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
-  auto        cleanup = [&]() {
-    (void)hipFree(op->neigh);
-    (void)hipFree(op->consts);
-    (void)hipFree(op->inv_diag);
-    (void)hipFree(op->interior_cells);
-    (void)hipFree(op->boundary_cells);
-    for (auto *p : op->nb_cells_dev)
-      (void)hipFree(p);
-    for (auto *p : op->nb_send)
-      (void)hipFree(p);
-    for (auto *p : op->nb_faces_dev)
-      (void)hipFree(p);
-  };
-#define DG_HIP_C(call)                                                                      \
-  do                                                                                        \
-    {                                                                                       \
-      hipError_t e_ = (call);                                                               \
-      if (e_ != hipSuccess)                                                                 \
-        {                                                                                   \
-          cleanup();                                                                        \
-          return dg_fail(MGX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
-        }                                                                                   \
-    }                                                                                       \
-  while (0)
-  DG_HIP_C(hipMalloc((void **)&op->neigh, sizeof(int32_t) * 6 * (size_t)desc->n_cells));
-  DG_HIP_C(hipMemcpyAsync(op->neigh, desc->neighbours, sizeof(int32_t) * 6 * (size_t)desc->n_cells,
-                          hipMemcpyHostToDevice, s));
+  MGX_TRY(op->mem.upload(&op->neigh, desc->neighbours, 6 * (size_t)desc->n_cells));
   if (op->n_ghost > 0)
     {
       const mgx_dg_exchange_desc &e = *desc->exchange;
@@ -2052,10 +2011,9 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
           op->nb_recv_first.push_back(e.recv_first[k]);
           uint32_t *cells = nullptr;
           void     *buf   = nullptr;
-          DG_HIP_C(hipMalloc((void **)&cells, sizeof(uint32_t) * ((size_t)e.count[k] + 1)));
+          MGX_TRY(op->mem.upload(&cells, e.send_cells[k], e.count[k], 1));
           op->nb_cells_dev.push_back(cells);
-          DG_HIP_C(hipMemcpyAsync(cells, e.send_cells[k], sizeof(uint32_t) * e.count[k], hipMemcpyHostToDevice, s));
-          DG_HIP_C(hipMalloc(&buf, nsz * ((size_t)e.count[k] * op->ghost_stride + 1)));
+          MGX_TRY(op->mem.alloc(&buf, nsz * ((size_t)e.count[k] * op->ghost_stride + 1)));
           op->nb_send.push_back(buf);
           if (op->basis == MGX_DG_HERMITE)
             {
@@ -2074,17 +2032,13 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
                         }
                     }
                   if (n_found != 1)
-                    {
-                      cleanup();
-                      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: a sent cell must touch the cells of the "
-                                                          "receiving rank through exactly one face");
-                    }
+                    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: a sent cell must touch the cells of the "
+                                                        "receiving rank through exactly one face");
                   face[i] = (uint8_t)found;
                 }
               uint8_t *fd = nullptr;
-              DG_HIP_C(hipMalloc((void **)&fd, face.size() + 1));
+              MGX_TRY(op->mem.upload(&fd, face, 1));
               op->nb_faces_dev.push_back(fd);
-              DG_HIP_C(hipMemcpy(fd, face.data(), face.size(), hipMemcpyHostToDevice));
             }
         }
     }
@@ -2101,32 +2055,22 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
       op->n_interior = (uint32_t)interior.size();
       op->n_boundary = (uint32_t)boundary.size();
       op->interior_is_prefix = interior.empty() || interior.back() + 1 == interior.size();
-      DG_HIP_C(hipMalloc((void **)&op->interior_cells, sizeof(uint32_t) * (interior.size() + 1)));
-      DG_HIP_C(hipMalloc((void **)&op->boundary_cells, sizeof(uint32_t) * (boundary.size() + 1)));
-      DG_HIP_C(hipMemcpy(op->interior_cells, interior.data(), sizeof(uint32_t) * interior.size(), hipMemcpyHostToDevice));
-      DG_HIP_C(hipMemcpy(op->boundary_cells, boundary.data(), sizeof(uint32_t) * boundary.size(), hipMemcpyHostToDevice));
+      MGX_TRY(op->mem.upload(&op->interior_cells, interior, 1));
+      MGX_TRY(op->mem.upload(&op->boundary_cells, boundary, 1));
     }
-  DG_HIP_C(hipMalloc(&op->inv_diag, nsz * table.size()));
+  MGX_TRY(op->mem.upload_as(desc->number, &op->inv_diag, table.data(), table.size()));
   if (desc->number == MGX_F64)
     {
       DGConst<double> c;
       fill_const(op->h, op->g, c);
-      DG_HIP_C(hipMalloc(&op->consts, sizeof(c)));
-      DG_HIP_C(hipMemcpyAsync(op->consts, &c, sizeof(c), hipMemcpyHostToDevice, s));
-      DG_HIP_C(hipMemcpyAsync(op->inv_diag, table.data(), nsz * table.size(), hipMemcpyHostToDevice, s));
-      DG_HIP_C(hipStreamSynchronize(s));
+      MGX_TRY(op->mem.upload_bytes(&op->consts, &c, sizeof(c)));
     }
   else
     {
       DGConst<float> c;
       fill_const(op->h, op->g, c);
-      std::vector<float> tf(table.begin(), table.end());
-      DG_HIP_C(hipMalloc(&op->consts, sizeof(c)));
-      DG_HIP_C(hipMemcpyAsync(op->consts, &c, sizeof(c), hipMemcpyHostToDevice, s));
-      DG_HIP_C(hipMemcpyAsync(op->inv_diag, tf.data(), nsz * tf.size(), hipMemcpyHostToDevice, s));
-      DG_HIP_C(hipStreamSynchronize(s));
+      MGX_TRY(op->mem.upload_bytes(&op->consts, &c, sizeof(c)));
     }
-#undef DG_HIP_C
   *out = op.release();
   return MGX_OK;
 }
@@ -2136,19 +2080,6 @@ int mgx_dg_operator_destroy(mgx_dg_operator_t op)
   if (!op)
     return MGX_OK;
   (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(op->ctx));
-  (void)hipFree(op->neigh);
-  (void)hipFree(op->consts);
-  (void)hipFree(op->inv_diag);
-  (void)hipFree(op->interior_cells);
-  (void)hipFree(op->boundary_cells);
-  (void)hipFree(op->cg_partials);
-  (void)hipFree(op->cg_sums);
-  for (auto *p : op->nb_cells_dev)
-    (void)hipFree(p);
-  for (auto *p : op->nb_send)
-    (void)hipFree(p);
-  for (auto *p : op->nb_faces_dev)
-    (void)hipFree(p);
   delete op;
   return MGX_OK;
 }
@@ -2218,31 +2149,30 @@ int mgx_dg_vmult_with_cg_update(mgx_dg_operator_t op, double alpha, double beta,
                                        : dg_grid<float>(op->degree, op->n_cells));
   if (blocks > op->cg_capacity)
     {
-      if (op->cg_partials)
-        DG_HIP(hipFree(op->cg_partials));
+      op->mem.release(op->cg_partials);
       op->cg_partials = nullptr;
       op->cg_capacity = 0;
-      DG_HIP(hipMalloc(&op->cg_partials, sizeof(double) * 4 * (size_t)blocks));
+      MGX_TRY(op->mem.alloc(&op->cg_partials, 4 * (size_t)blocks));
       op->cg_capacity = blocks;
     }
   if (!op->cg_sums)
-    DG_HIP(hipMalloc(&op->cg_sums, sizeof(double) * 4));
+    MGX_TRY(op->mem.alloc(&op->cg_sums, 4));
   // laplace_operator_dg.h:871-902: x += alpha p ; p = beta p + q (alpha == 0: p = q) on the owned entries
   mgx::launch_cg_pre(s, op->number, x, p, q, alpha, beta, (size_t)mgx_dg_operator_n_dofs(op));
   // :903 q = A p with the sums of the next iteration
   if (op->n_cells == 0)
-    DG_HIP(hipMemsetAsync(op->cg_sums, 0, sizeof(double) * 4, s));
+    MGX_HIP(hipMemsetAsync(op->cg_sums, 0, sizeof(double) * 4, s));
   else
     {
       // without the overlap of the ghost exchange the cells run in one launch: its blocks are not the split's
-      DG_HIP(hipMemsetAsync(op->cg_partials, 0, sizeof(double) * 4 * (size_t)blocks, s));
+      MGX_HIP(hipMemsetAsync(op->cg_partials, 0, sizeof(double) * 4 * (size_t)blocks, s));
       MergedArgs m;
       m.partials = op->cg_partials;
-      MGX_DG_TRY(run(op, kCgSums, q, r, p, 0, 0, 0, true, m));
+      MGX_TRY(run(op, kCgSums, q, r, p, 0, 0, 0, true, m));
       mgx::launch_reduce4(s, op->cg_partials, blocks, nullptr, op->cg_sums);
     }
-  DG_HIP(hipMemcpyAsync(sums, op->cg_sums, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
-  DG_HIP(hipStreamSynchronize(s));
+  MGX_HIP(hipMemcpyAsync(sums, op->cg_sums, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
   return mgx::allreduce_sum(op->ctx, sums, 4); // :904-906
 }
 
@@ -2375,7 +2305,7 @@ namespace
 
   int dg_norm(mgx_dg_solver_t S, int number, const void *x, double *out)
   {
-    MGX_DG_TRY(mgx::dot_owned_prefix(S->ctx, number, x, x, S->n, out));
+    MGX_TRY(mgx::dot_owned_prefix(S->ctx, number, x, x, S->n, out));
     *out = std::sqrt(*out);
     return MGX_OK;
   }
@@ -2388,12 +2318,12 @@ namespace
     int                      index;
     if (!is_step)
       {
-        MGX_DG_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, 0, 0., 1. / I.theta, S->update, S->old));
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, 0, 0., 1. / I.theta, S->update, S->old));
         index = 1;
       }
     else
       {
-        MGX_DG_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, 1, 0., 1. / I.theta, S->update, S->old));
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, 1, 0., 1. / I.theta, S->update, S->old));
         std::swap(S->update, S->old);
         index = 2;
       }
@@ -2406,7 +2336,7 @@ namespace
         const double rhokp = 1. / (2. * sigma - rhok);
         const double f1 = rhokp * rhok, f2 = 2. * rhokp / I.delta;
         rhok = rhokp;
-        MGX_DG_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, (unsigned)index, f1, f2, S->update, S->old));
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, (unsigned)index, f1, f2, S->update, S->old));
         std::swap(S->update, S->old);
       }
     return MGX_OK;
@@ -2419,24 +2349,24 @@ namespace
   {
     hipStream_t       s  = (hipStream_t)mgx_context_stream(S->ctx);
     mgx_dg_operator_t op = S->A;
-    DG_HIP(hipMemsetAsync(cg, 0, dg_nsz(S->number) * S->n_cg, s));
+    MGX_HIP(hipMemsetAsync(cg, 0, dg_nsz(S->number) * S->n_cg, s));
     if (op->n_ghost > 0)
-      MGX_DG_TRY(update_ghosts(op, const_cast<void *>(lhs)));
+      MGX_TRY(update_ghosts(op, const_cast<void *>(lhs)));
     MergedArgs m;
     m.cg    = cg;
     m.idx27 = S->idx27;
     m.P1    = S->P1;
     if (!S->cg_eight_colours)
-      MGX_DG_TRY(launch_cells(op, kRestrict, nullptr, rhs, lhs, 0, 0, 0, nullptr, op->n_cells, nullptr, 0, m));
+      MGX_TRY(launch_cells(op, kRestrict, nullptr, rhs, lhs, 0, 0, 0, nullptr, op->n_cells, nullptr, 0, m));
     else
       {
         m.plain       = 1;
         m.cell_stride = 8;
         for (uint32_t k = 0; k < 8 && k < op->n_cells; ++k)
-          MGX_DG_TRY(launch_cells(op, kRestrict, nullptr, rhs, lhs, 0, 0, 0, nullptr, (op->n_cells - k + 7) / 8, nullptr, k, m));
+          MGX_TRY(launch_cells(op, kRestrict, nullptr, rhs, lhs, 0, 0, 0, nullptr, (op->n_cells - k + 7) / 8, nullptr, k, m));
       }
     if (S->decomposed) // FE_Q DoFs on a rank interface collect the contributions of all sharers
-      MGX_DG_TRY(mgx_exchange_add(S->fe, cg));
+      MGX_TRY(mgx_exchange_add(S->fe, cg));
     return MGX_OK;
   }
 
@@ -2444,23 +2374,23 @@ namespace
   int dg_v_cycle(mgx_dg_solver_t S)
   {
     hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
-    MGX_DG_TRY(dg_smoother_apply(S, false));
+    MGX_TRY(dg_smoother_apply(S, false));
     // vmult_residual_and_restrict_to_cg (:616-618)
     if (!mgx::context_tunables(S->ctx).dg_unmerged_restrict)
-      MGX_DG_TRY(dg_residual_and_restrict(S, S->cg_defect, S->defect, S->update));
+      MGX_TRY(dg_residual_and_restrict(S, S->cg_defect, S->defect, S->update));
     else
       {
-        MGX_DG_TRY(mgx_dg_vmult_residual(S->A, S->t, S->defect, S->update));
-        DG_HIP(hipMemsetAsync(S->cg_defect, 0, dg_nsz(S->number) * S->n_cg, s));
+        MGX_TRY(mgx_dg_vmult_residual(S->A, S->t, S->defect, S->update));
+        MGX_HIP(hipMemsetAsync(S->cg_defect, 0, dg_nsz(S->number) * S->n_cg, s));
         mgx::launch_dg_cg_transfer(s, S->number, S->degree, false, S->cg_defect, S->t, S->idx27, S->n_cells, S->P1,
                                    S->cg_eight_colours);
         if (S->decomposed) // FE_Q DoFs on a rank interface collect the contributions of all sharers
-          MGX_DG_TRY(mgx_exchange_add(S->fe, S->cg_defect));
+          MGX_TRY(mgx_exchange_add(S->fe, S->cg_defect));
       }
-    MGX_DG_TRY(mgx_solver_v_cycle(S->cfe)); // :622
+    MGX_TRY(mgx_solver_v_cycle(S->cfe)); // :622
     // prolongate_add_cg_to_dg (:625; laplace_operator_dg.h:1863-1894)
     mgx::launch_dg_cg_transfer(s, S->number, S->degree, true, S->update, S->cg_update, S->idx27, S->n_cells, S->P1);
-    DG_HIP(hipGetLastError());
+    MGX_HIP(hipGetLastError());
     return dg_smoother_apply(S, true); // :629
   }
 } // namespace
@@ -2478,11 +2408,11 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_create: degree_pre must be at least 1");
   const int      lmax = mgx_solver_n_levels(desc->cfe) - 1;
   mgx_operator_t fe   = nullptr;
-  MGX_DG_TRY(mgx_solver_get_operator(desc->cfe, lmax, 0, &fe));
+  MGX_TRY(mgx_solver_get_operator(desc->cfe, lmax, 0, &fe));
   const uint32_t *idx27 = nullptr;
   uint32_t        nc = 0, ncg = 0;
   int             p = 0;
-  MGX_DG_TRY(mgx_operator_device_indices(fe, &idx27, &nc, &ncg, &p));
+  MGX_TRY(mgx_operator_device_indices(fe, &idx27, &nc, &ncg, &p));
   if (nc != A->n_cells || p != A->degree || mgx_operator_number(fe) != A->number)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_create: the FE_Q hierarchy's finest level must have the DG "
                                              "operator's cells, degree and number type");
@@ -2505,7 +2435,7 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
   {
     // forest order (the same child of every parent in one class): checked, not assumed
     std::vector<uint32_t> h27(27 * (size_t)nc), stamp(ncg, 0xFFFFFFFFu);
-    DG_HIP(hipMemcpy(h27.data(), idx27, sizeof(uint32_t) * h27.size(), hipMemcpyDeviceToHost));
+    MGX_HIP(hipMemcpy(h27.data(), idx27, sizeof(uint32_t) * h27.size(), hipMemcpyDeviceToHost));
     bool ok = nc >= 64;
     for (uint32_t k = 0; k < 8 && ok; ++k)
       for (uint32_t c = k; c < nc && ok; c += 8)
@@ -2527,38 +2457,29 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
   const size_t vb = dg_nsz(S->number) * S->n_vec;
   for (void **v : {&S->defect, &S->t, &S->update, &S->old})
     {
-      DG_HIP(hipMalloc(v, vb));
-      DG_HIP(hipMemsetAsync(*v, 0, vb, s));
+      MGX_TRY(S->mem.zeros(v, vb, s));
     }
   for (double **v : {&S->r, &S->z, &S->d, &S->h})
     {
-      DG_HIP(hipMalloc((void **)v, 8 * S->n_vec));
-      DG_HIP(hipMemsetAsync(*v, 0, 8 * S->n_vec, s));
+      MGX_TRY(S->mem.zeros(v, S->n_vec, s));
     }
   {
     const int n1 = S->degree + 1;
-    DG_HIP(hipMalloc(&S->P1, dg_nsz(S->number) * n1 * n1));
-    if (S->number == MGX_F64)
-      DG_HIP(hipMemcpy(S->P1, A->h.P1.data(), 8 * n1 * n1, hipMemcpyHostToDevice));
-    else
-      {
-        std::vector<float> pf(A->h.P1.begin(), A->h.P1.end());
-        DG_HIP(hipMemcpy(S->P1, pf.data(), 4 * n1 * n1, hipMemcpyHostToDevice));
-      }
+    MGX_TRY(S->mem.upload_as(S->number, &S->P1, A->h.P1.data(), (size_t)n1 * n1));
   }
   // the FE_Q hierarchy under a DG level smooths with degree_pre - 1 on its finest level and solves
   // the coarsest one to 2e-3 (multigrid_solver_dg.h:271-291)
   if (lmax > 0)
-    MGX_DG_TRY(mgx_solver_reset_smoother(desc->cfe, lmax, 20., std::max(1, desc->degree_pre - 1), 15));
+    MGX_TRY(mgx_solver_reset_smoother(desc->cfe, lmax, 20., std::max(1, desc->degree_pre - 1), 15));
   {
     uint32_t n0 = 0;
     mgx_operator_t f0 = nullptr;
-    MGX_DG_TRY(mgx_solver_get_operator(desc->cfe, 0, 0, &f0));
-    MGX_DG_TRY(mgx_operator_device_indices(f0, nullptr, nullptr, &n0, nullptr));
-    MGX_DG_TRY(mgx_solver_reset_smoother(desc->cfe, 0, 2e-3, -1, (int)std::max<uint32_t>(3u, n0)));
+    MGX_TRY(mgx_solver_get_operator(desc->cfe, 0, 0, &f0));
+    MGX_TRY(mgx_operator_device_indices(f0, nullptr, nullptr, &n0, nullptr));
+    MGX_TRY(mgx_solver_reset_smoother(desc->cfe, 0, 2e-3, -1, (int)std::max<uint32_t>(3u, n0)));
   }
-  MGX_DG_TRY(mgx_solver_get_vector(desc->cfe, lmax, 2, &S->cg_defect));
-  MGX_DG_TRY(mgx_solver_get_vector(desc->cfe, lmax, 4, &S->cg_update));
+  MGX_TRY(mgx_solver_get_vector(desc->cfe, lmax, 2, &S->cg_defect));
+  MGX_TRY(mgx_solver_get_vector(desc->cfe, lmax, 4, &S->cg_update));
 
   // smooth_dg.initialize (multigrid_solver_dg.h:293-303): eigenvalue estimate by 15 iterations of
   // CG preconditioned with JacobiTransformed on v_i = (i mod 11) - mean, lambda_max = 1.2 x the
@@ -2567,16 +2488,14 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
     const size_t n  = S->n;
     void        *r = S->t, *z = S->update, *d = S->old, *h = S->defect; // free until the first cycle
     double ng = (double)n; // global number of DoFs
-    MGX_DG_TRY(mgx::allreduce_sum(ctx, &ng, 1));
+    MGX_TRY(mgx::allreduce_sum(ctx, &ng, 1));
     const uint64_t ngl  = (uint64_t)(ng + 0.5);
     const uint64_t full = ngl / 11, rem = ngl % 11;
     const double   mean = (full * 55.0 + rem * (rem - 1) / 2.0) / (double)ngl;
-    uint32_t      *cell_id = nullptr;
+    mgx::DeviceArena tmp("mgx_dg_solver_create");
+    uint32_t        *cell_id = nullptr;
     if (desc->cell_global_id)
-      {
-        DG_HIP(hipMalloc((void **)&cell_id, sizeof(uint32_t) * (size_t)S->n_cells));
-        DG_HIP(hipMemcpy(cell_id, desc->cell_global_id, sizeof(uint32_t) * (size_t)S->n_cells, hipMemcpyHostToDevice));
-      }
+      MGX_TRY(tmp.upload(&cell_id, desc->cell_global_id, S->n_cells));
     {
       const uint32_t n3   = (uint32_t)(n / S->n_cells);
       const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192);
@@ -2584,33 +2503,33 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
         hipLaunchKernelGGL(k_start_vector<double>, dim3(grid), dim3(256), 0, s, (double *)r, cell_id, S->n_cells, n3, mean);
       else
         hipLaunchKernelGGL(k_start_vector<float>, dim3(grid), dim3(256), 0, s, (float *)r, cell_id, S->n_cells, n3, mean);
-      DG_HIP(hipStreamSynchronize(s));
-      (void)hipFree(cell_id);
+      MGX_HIP(hipStreamSynchronize(s));
+      tmp.release(cell_id);
     }
     std::vector<double> diag, off;
     double              res = 0, rz = 0, rz_old = 0, alpha = 0, alpha_old = 0, beta = 0;
-    MGX_DG_TRY(dg_norm(S.get(), S->number, r, &res));
+    MGX_TRY(dg_norm(S.get(), S->number, r, &res));
     int it = 0;
     while (it < 15 && res > 1e-10)
       {
         ++it;
         rz_old = rz;
-        MGX_DG_TRY(mgx_dg_jacobi_vmult(A, z, r));
-        MGX_DG_TRY(dg_dot(S.get(), S->number, r, z, &rz));
+        MGX_TRY(mgx_dg_jacobi_vmult(A, z, r));
+        MGX_TRY(dg_dot(S.get(), S->number, r, z, &rz));
         if (it > 1)
           {
             beta = rz / rz_old;
-            MGX_DG_TRY(mgx_sadd(ctx, S->number, d, beta, 1.0, z, n));
+            MGX_TRY(mgx_sadd(ctx, S->number, d, beta, 1.0, z, n));
           }
         else
-          MGX_DG_TRY(mgx_copy_cast(ctx, d, S->number, z, S->number, n));
+          MGX_TRY(mgx_copy_cast(ctx, d, S->number, z, S->number, n));
         alpha_old = alpha;
-        MGX_DG_TRY(mgx_dg_vmult(A, h, d));
+        MGX_TRY(mgx_dg_vmult(A, h, d));
         double dh = 0;
-        MGX_DG_TRY(dg_dot(S.get(), S->number, d, h, &dh));
+        MGX_TRY(dg_dot(S.get(), S->number, d, h, &dh));
         alpha = rz / dh;
-        MGX_DG_TRY(mgx_sadd(ctx, S->number, r, 1.0, -alpha, h, n));
-        MGX_DG_TRY(dg_norm(S.get(), S->number, r, &res));
+        MGX_TRY(mgx_sadd(ctx, S->number, r, 1.0, -alpha, h, n));
+        MGX_TRY(dg_norm(S.get(), S->number, r, &res));
         if (it == 1)
           diag.push_back(1. / alpha);
         else
@@ -2642,8 +2561,8 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
     I.delta        = (I.lambda_max - a) * 0.5;
     I.theta        = (I.lambda_max + a) * 0.5;
     for (void *v : {S->defect, S->t, S->update, S->old})
-      DG_HIP(hipMemsetAsync(v, 0, vb, s));
-    DG_HIP(hipStreamSynchronize(s));
+      MGX_HIP(hipMemsetAsync(v, 0, vb, s));
+    MGX_HIP(hipStreamSynchronize(s));
   }
   *out = S.release();
   return MGX_OK;
@@ -2655,8 +2574,6 @@ int mgx_dg_solver_destroy(mgx_dg_solver_t S)
     return MGX_OK;
   if (S->ctx)
     (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
-  for (void *v : {S->defect, S->t, S->update, S->old, S->P1, (void *)S->r, (void *)S->z, (void *)S->d, (void *)S->h})
-    (void)hipFree(v);
   delete S;
   return MGX_OK;
 }
@@ -2674,9 +2591,9 @@ int mgx_dg_restrict_to_cg(mgx_dg_solver_t S, void *cg_dst, const void *dg_src)
   if (!S || !cg_dst || !dg_src)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_restrict_to_cg: null argument");
   hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
-  DG_HIP(hipMemsetAsync(cg_dst, 0, dg_nsz(S->number) * S->n_cg, s));
+  MGX_HIP(hipMemsetAsync(cg_dst, 0, dg_nsz(S->number) * S->n_cg, s));
   mgx::launch_dg_cg_transfer(s, S->number, S->degree, false, cg_dst, dg_src, S->idx27, S->n_cells, S->P1, S->cg_eight_colours);
-  DG_HIP(hipGetLastError());
+  MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
 
@@ -2693,7 +2610,7 @@ int mgx_dg_prolongate_add_cg_to_dg(mgx_dg_solver_t S, void *dg_dst, const void *
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_prolongate_add_cg_to_dg: null argument");
   hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
   mgx::launch_dg_cg_transfer(s, S->number, S->degree, true, dg_dst, cg_src, S->idx27, S->n_cells, S->P1);
-  DG_HIP(hipGetLastError());
+  MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
 
@@ -2701,8 +2618,8 @@ int mgx_dg_solver_vmult(mgx_dg_solver_t S, double *dst, const double *src)
 {
   if (!S || !dst || !src)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_vmult: null argument");
-  MGX_DG_TRY(mgx_copy_cast(S->ctx, S->defect, S->number, src, MGX_F64, S->n)); // multigrid_solver_dg.h:433
-  MGX_DG_TRY(dg_v_cycle(S));
+  MGX_TRY(mgx_copy_cast(S->ctx, S->defect, S->number, src, MGX_F64, S->n)); // multigrid_solver_dg.h:433
+  MGX_TRY(dg_v_cycle(S));
   return mgx_copy_cast(S->ctx, dst, MGX_F64, S->update, S->number, S->n);       // :436
 }
 
@@ -2717,29 +2634,29 @@ int mgx_dg_solver_solve_cg(mgx_dg_solver_t S, double tolerance, const double *rh
   const size_t  n   = S->n;
   hipStream_t   s   = (hipStream_t)mgx_context_stream(ctx);
   double       *r = S->r, *z = S->z, *d = S->d, *h = S->h;
-  DG_HIP(hipMemsetAsync(solution, 0, 8 * S->n_vec, s));
-  MGX_DG_TRY(mgx_copy_cast(ctx, r, MGX_F64, rhs, MGX_F64, n));
+  MGX_HIP(hipMemsetAsync(solution, 0, 8 * S->n_vec, s));
+  MGX_TRY(mgx_copy_cast(ctx, r, MGX_F64, rhs, MGX_F64, n));
   double res0 = 0, res = 0, rz = 0, rz_old = 0;
-  MGX_DG_TRY(dg_norm(S, MGX_F64, r, &res0));
+  MGX_TRY(dg_norm(S, MGX_F64, r, &res0));
   res         = res0;
   unsigned it = 0;
   while (res > std::max(1e-16, tolerance * res0) && it < 100)
     {
       ++it;
-      MGX_DG_TRY(mgx_dg_solver_vmult(S, z, r));
+      MGX_TRY(mgx_dg_solver_vmult(S, z, r));
       rz_old = rz;
-      MGX_DG_TRY(dg_dot(S, MGX_F64, r, z, &rz));
+      MGX_TRY(dg_dot(S, MGX_F64, r, z, &rz));
       if (it > 1)
-        MGX_DG_TRY(mgx_sadd(ctx, MGX_F64, d, rz / rz_old, 1.0, z, n));
+        MGX_TRY(mgx_sadd(ctx, MGX_F64, d, rz / rz_old, 1.0, z, n));
       else
-        MGX_DG_TRY(mgx_copy_cast(ctx, d, MGX_F64, z, MGX_F64, n));
-      MGX_DG_TRY(mgx_dg_vmult(S->A_dp, h, d));
+        MGX_TRY(mgx_copy_cast(ctx, d, MGX_F64, z, MGX_F64, n));
+      MGX_TRY(mgx_dg_vmult(S->A_dp, h, d));
       double dh = 0;
-      MGX_DG_TRY(dg_dot(S, MGX_F64, d, h, &dh));
+      MGX_TRY(dg_dot(S, MGX_F64, d, h, &dh));
       const double alpha = rz / dh;
-      MGX_DG_TRY(mgx_sadd(ctx, MGX_F64, solution, 1.0, alpha, d, n));
-      MGX_DG_TRY(mgx_sadd(ctx, MGX_F64, r, 1.0, -alpha, h, n));
-      MGX_DG_TRY(dg_norm(S, MGX_F64, r, &res));
+      MGX_TRY(mgx_sadd(ctx, MGX_F64, solution, 1.0, alpha, d, n));
+      MGX_TRY(mgx_sadd(ctx, MGX_F64, r, 1.0, -alpha, h, n));
+      MGX_TRY(dg_norm(S, MGX_F64, r, &res));
     }
   if (iterations)
     *iterations = it;

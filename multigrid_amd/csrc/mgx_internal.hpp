@@ -239,6 +239,36 @@ namespace mgx
   // records the message mgx_last_error() returns on the calling thread; returns `code` (used by the
   // translation units that implement parts of the C ABI outside mgx_api.cpp)
   int report_error(int code, const char *message);
+  inline int report_error(int code, const std::string &message) { return report_error(code, message.c_str()); }
+
+// status plumbing of the host code behind the C ABI (the codes are those of include/mgx.h): a failed HIP call, a failed
+// callee, a refused argument -- each returns from the calling function with the status
+#define MGX_HIP(call)                                                                                                \
+  do                                                                                                                 \
+    {                                                                                                                \
+      hipError_t e_ = (call);                                                                                        \
+      if (e_ != hipSuccess)                                                                                          \
+        return mgx::report_error(MGX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + \
+                                                std::to_string(__LINE__) + ")");                                     \
+    }                                                                                                                \
+  while (0)
+
+#define MGX_TRY(call)     \
+  do                      \
+    {                     \
+      int s_ = (call);    \
+      if (s_ != MGX_OK)   \
+        return s_;        \
+    }                     \
+  while (0)
+
+#define MGX_REQUIRE(cond, msg)                                      \
+  do                                                                \
+    {                                                               \
+      if (!(cond))                                                  \
+        return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, (msg));  \
+    }                                                               \
+  while (0)
 
   void launch_prolongate_pipe(hipStream_t s, const TransferData &t, void *fine, const void *coarse, bool add,
                               bool with_constraints);
