@@ -170,6 +170,73 @@ int mgx_dg_prolongate_add_cg_to_dg(mgx_dg_solver_t solver, void *dg_dst, const v
  * runs this form unless the context option "dg_unmerged_restrict" is set. */
 int mgx_dg_vmult_residual_and_restrict_to_cg(mgx_dg_solver_t solver, void *cg_dst, const void *rhs, const void *lhs);
 
+/* ---- level transfer between two DG spaces: MGTransferMatrixFree<3,Number> on FE_DGQ* level vectors, as
+ * MultigridSolverDGPlain uses it (common/multigrid_solver_dg_plain.h:150-159 build, :483 restrict_and_add, :489
+ * prolongate_and_add).  Same degree and basis on both levels; every coarse cell has eight children. ---- */
+typedef struct mgx_dg_transfer_s *mgx_dg_transfer_t;
+typedef struct
+{
+  int      degree; /* 1 .. MGX_MAX_DEGREE */
+  int      basis;  /* MGX_DG_* */
+  int      number; /* MGX_F32 or MGX_F64: the type of the vectors */
+  uint32_t n_coarse_cells;
+  /* host [n_coarse_cells][8], copied: fine cell that is child kx + 2 ky + 4 kz of a coarse cell; every fine cell
+   * 0 .. 8 n_coarse_cells - 1 exactly once (checked) */
+  const uint32_t *children;
+} mgx_dg_transfer_desc;
+/* MGTransferMatrixFree::build: the 1D embedding of the parent's basis into the two children's, computed in double
+ * from the operator's own 1D polynomials */
+int mgx_dg_transfer_create(mgx_context_t ctx, const mgx_dg_transfer_desc *desc, mgx_dg_transfer_t *transfer);
+int mgx_dg_transfer_destroy(mgx_dg_transfer_t transfer);
+/* MGTransferMatrixFree::prolongate_and_add: fine[children[c][k]] += (P_kz (x) P_ky (x) P_kx) coarse[c] */
+int mgx_dg_transfer_prolongate_and_add(mgx_dg_transfer_t transfer, void *fine_dst, const void *coarse_src);
+/* MGTransferMatrixFree::restrict_and_add: coarse[c] += sum_k (P_kz (x) P_ky (x) P_kx)^T fine[children[c][k]]; DG has
+ * neither weights nor constrained rows.  Both operations give the same bits in every run. */
+int mgx_dg_transfer_restrict_and_add(mgx_dg_transfer_t transfer, void *coarse_dst, const void *fine_src);
+/* the 1D embedding for inspection (MGTransferMatrixFree's prolongation_matrix_1d, one half at a time):
+ * p1d[h (p+1)^2 + i (p+1) + j] = coefficient i, in the child's basis on [0,1], of phi_j((x + h) / 2) */
+int mgx_dg_transfer_matrix(mgx_dg_transfer_t transfer, double *p1d);
+
+/* ---- MultigridSolverDGPlain<3,p,Number,double> (common/multigrid_solver_dg_plain.h:55-595): the DG-SIP operator on
+ * every level of a globally refined mesh, Chebyshev / JacobiTransformed smoothers, DG-to-DG transfers, level 0 solved
+ * by its Chebyshev iteration; one rank ---- */
+typedef struct mgx_dg_plain_solver_s *mgx_dg_plain_solver_t;
+typedef struct
+{
+  int                      n_levels;
+  const mgx_dg_operator_t *matrix;       /* [n_levels], V-cycle number type (:95-122) */
+  mgx_dg_operator_t        matrix_dg_dp; /* fp64 twin of matrix[n_levels - 1] (:126-146) */
+  const mgx_dg_transfer_t *transfer;     /* [n_levels - 1], transfer[l - 1] between levels l - 1 and l (:150-159) */
+  int                      degree_pre;   /* Chebyshev degree of levels 0 < l < L; max(1, degree_pre - 1) on level L (:195-202) */
+  /* optional [n_levels] (entries may be NULL), host [n_cells of the level]: as in mgx_dg_solver_desc */
+  const uint32_t *const *cell_global_id;
+} mgx_dg_plain_solver_desc;
+/* ctor (:58-215): level vectors and smooth[level].initialize -- levels l > 0: range 20, 15 CG iterations; level 0:
+ * range 1e-5, degree by Varga's rule, at most m() CG iterations (:204-209) */
+int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc *desc, mgx_dg_plain_solver_t *solver);
+int mgx_dg_plain_solver_destroy(mgx_dg_plain_solver_t solver);
+int mgx_dg_plain_solver_smoother_info(mgx_dg_plain_solver_t solver, int level, mgx_smoother_info *info);
+/* MultigridSolverDGPlain::vmult (:322-334): one V-cycle (:456-496); fp64 device vectors of the finest level */
+int mgx_dg_plain_solver_vmult(mgx_dg_plain_solver_t solver, double *dst, const double *src);
+/* MultigridSolverDGPlain::solve_cg(tolerance) (:303-317) on a given right-hand side: zero start, at most 100
+ * iterations; iterations = last_step, reduction_rate = (res/res0)^(1/its) */
+int mgx_dg_plain_solver_solve_cg(mgx_dg_plain_solver_t solver, double tolerance, const double *rhs, double *solution,
+                                 unsigned *iterations, double *reduction_rate);
+/* MultigridSolverDGPlain::vmult_with_residual_update (:340-427): defect = residual + factor update; V-cycle -> mg;
+ * residual += factor update; sums = {mg.residual, mg.(factor update)} (factor == 0: both mg.residual); update = mg.
+ * The sums are added in a fixed order. */
+int mgx_dg_plain_solver_vmult_with_residual_update(mgx_dg_plain_solver_t solver, double *residual, double *update,
+                                                   double factor, double sums[2]);
+/* wall time per level of the V-cycles since the last call (print_wall_times, :264-287), seconds, for diagnosis: the
+ * stream is synchronised around every part while enabled.  times [n_levels][6]: level 0 {coarse solve, calls, 0...},
+ * level l > 0 {mg_mv, restrict, prolongate, 0, 0, smoother} (the columns of `timings[level]`). */
+int mgx_dg_plain_solver_enable_timings(mgx_dg_plain_solver_t solver, int on);
+int mgx_dg_plain_solver_get_timings(mgx_dg_plain_solver_t solver, double *times);
+/* do_matvec / do_matvec_smoother (:432-445): one product with the finest fp64 / V-cycle operator on the solver's
+ * own vectors (timing aids) */
+int mgx_dg_plain_solver_do_matvec(mgx_dg_plain_solver_t solver);
+int mgx_dg_plain_solver_do_matvec_smoother(mgx_dg_plain_solver_t solver);
+
 /* ---- mesh helpers (stand in for GridGenerator + DoFHandler of the harness) ---- */
 
 /* matvec_dg_cheby/program.cc:55-77: cells per direction and the cell Jacobian of the sheared box
@@ -180,6 +247,11 @@ int mgx_dg_cheby_mesh(int n_cell_steps, int cells[3], double jacobian[9]);
  * ordering 0: lexicographic, x fastest; 1: z-order (space-filling curve, as p4est gives the
  * reference).  cell_ijk (optional) receives the (i, j, k) position of every cell. */
 int mgx_dg_box_neighbours(const int cells[3], int ordering, int32_t *neighbours, int32_t *cell_ijk);
+
+/* child table between a box of coarse_cells and its global refinement (2 coarse_cells per direction), the cells of
+ * either numbered as mgx_dg_box_neighbours numbers them in the given ordering (Triangulation::refine_global):
+ * children[c * 8 + kx + 2 ky + 4 kz] = fine cell at position 2 ijk(c) + (kx, ky, kz) */
+int mgx_dg_box_children(const int coarse_cells[3], int coarse_ordering, int fine_ordering, uint32_t *children);
 
 #ifdef __cplusplus
 }

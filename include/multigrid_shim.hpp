@@ -5,6 +5,7 @@
 //     multigrid::LaplaceOperatorCompactCombine<dim,fe_degree,Number,type> + JacobiTransformed
 //                                                                common/laplace_operator_dg.h:350-2256
 //     multigrid::MultigridSolverDG<dim,fe_degree,Number,Number2> common/multigrid_solver_dg.h:55-747
+//     multigrid::MultigridSolverDGPlain<dim,fe_degree,Number,Number2> common/multigrid_solver_dg_plain.h:55-595
 // keeps its call sites (vmult, vmult_residual, vmult_with_cg_update, compute_residual, evaluate_coefficient,
 // compute_diagonal, get_matrix_diagonal_inverse, solve, solve_cg, vmult_with_residual_update, do_matvec,
 // compute_l2_error, get_solution, print_wall_times ...).  Non-zero C status codes become
@@ -638,5 +639,120 @@ namespace multigrid
   private:
     MultigridSolver<dim, fe_degree, Number, Number2> cfe_; // FE_Q hierarchy, re-configured by the DG solver (:271-291)
     mgx_dg_solver_t                                  h_ = nullptr;
+  };
+
+  // multigrid::MultigridSolverDGPlain<dim,fe_degree,Number,Number2> (multigrid_solver_dg_plain.h:55-595): the DG-SIP operator
+  // on every level with DG-to-DG transfers.  The reference's constructor takes a DoFHandler on a globally refined
+  // triangulation; here the mesh arrives as a box of coarse_cells (level 0), its cell Jacobian and the number of levels, the
+  // cells of every level along the space-filling curve (mgx_dg_box_neighbours, ordering 1).
+  template <int dim, int fe_degree, typename Number, typename Number2, int type = 0>
+  class MultigridSolverDGPlain
+  {
+    static_assert(dim == 3, "the MI355X path implements dim = 3");
+    static_assert(std::is_same<Number2, double>::value, "the outer iteration is fp64");
+
+  public:
+    MultigridSolverDGPlain(const Context &ctx, const int (&coarse_cells)[3], const double (&jacobian0)[9], const unsigned int n_levels,
+                           const unsigned int degree_pre)
+      : matrix(n_levels)
+      , transfer_(n_levels > 0 ? n_levels - 1 : 0, nullptr)
+    {
+      try
+        {
+          std::vector<std::vector<std::uint32_t>> gid(n_levels);
+          std::vector<const std::uint32_t *>      gid_ptr(n_levels);
+          for (unsigned int l = 0; l < n_levels; ++l)
+            {
+              const int    cells[3] = {coarse_cells[0] << l, coarse_cells[1] << l, coarse_cells[2] << l};
+              const size_t nc       = (size_t)cells[0] * cells[1] * cells[2];
+              std::vector<std::int32_t> nb(6 * nc), ijk(3 * nc);
+              check(mgx_dg_box_neighbours(cells, 1, nb.data(), ijk.data()));
+              double jac[9];
+              for (int i = 0; i < 9; ++i)
+                jac[i] = jacobian0[i] / (double)(1u << l);
+              matrix[l].reinit(ctx, nb, jac);
+              if (l + 1 == n_levels)
+                matrix_dg_dp.reinit(ctx, nb, jac);
+              gid[l].resize(nc);
+              for (size_t c = 0; c < nc; ++c)
+                gid[l][c] = (std::uint32_t)(ijk[3 * c] + cells[0] * (ijk[3 * c + 1] + (size_t)cells[1] * ijk[3 * c + 2]));
+              gid_ptr[l] = gid[l].data();
+              if (l > 0)
+                {
+                  const int coarse[3] = {cells[0] / 2, cells[1] / 2, cells[2] / 2};
+                  std::vector<std::uint32_t> children(nc);
+                  check(mgx_dg_box_children(coarse, 1, 1, children.data()));
+                  mgx_dg_transfer_desc t{};
+                  t.degree         = fe_degree;
+                  t.basis          = type;
+                  t.number         = number_id<Number>::value;
+                  t.n_coarse_cells = (std::uint32_t)(nc / 8);
+                  t.children       = children.data();
+                  check(mgx_dg_transfer_create(ctx.handle(), &t, &transfer_[l - 1]));
+                }
+            }
+          std::vector<mgx_dg_operator_t> ops(n_levels);
+          for (unsigned int l = 0; l < n_levels; ++l)
+            ops[l] = matrix[l].handle();
+          mgx_dg_plain_solver_desc d{};
+          d.n_levels       = (int)n_levels;
+          d.matrix         = ops.data();
+          d.matrix_dg_dp   = matrix_dg_dp.handle();
+          d.transfer       = transfer_.data();
+          d.degree_pre     = (int)degree_pre;
+          d.cell_global_id = gid_ptr.data();
+          check(mgx_dg_plain_solver_create(ctx.handle(), &d, &h_));
+        }
+      catch (...)
+        {
+          release();
+          throw;
+        }
+    }
+    ~MultigridSolverDGPlain() { release(); }
+    MultigridSolverDGPlain(const MultigridSolverDGPlain &) = delete;
+    MultigridSolverDGPlain &operator=(const MultigridSolverDGPlain &) = delete;
+    // solve_cg(tolerance) (:303-317) on a given right-hand side: (iterations, reduction per iteration)
+    std::pair<unsigned int, double> solve_cg(const Vector<Number2> &rhs, Vector<Number2> &solution, const double tolerance = 1e-9)
+    {
+      unsigned int its = 0;
+      double       red = 1.;
+      check(mgx_dg_plain_solver_solve_cg(h_, tolerance, rhs.begin(), solution.begin(), &its, &red));
+      return std::make_pair(its, red);
+    }
+    // vmult (:322-334): one V-cycle
+    void vmult(Vector<Number2> &dst, const Vector<Number2> &src) const { check(mgx_dg_plain_solver_vmult(h_, dst.begin(), src.begin())); }
+    // vmult_with_residual_update(residual, update, factor) (:340-427)
+    std::array<Number2, 2> vmult_with_residual_update(Vector<Number2> &residual, Vector<Number2> &update, const Number2 factor) const
+    {
+      double out[2];
+      check(mgx_dg_plain_solver_vmult_with_residual_update(h_, residual.begin(), update.begin(), (double)factor, out));
+      return {{(Number2)out[0], (Number2)out[1]}};
+    }
+    void do_matvec() { check(mgx_dg_plain_solver_do_matvec(h_)); }                   // :432-436
+    void do_matvec_smoother() { check(mgx_dg_plain_solver_do_matvec_smoother(h_)); } // :441-445
+    mgx_smoother_info smoother_info(const unsigned int level) const
+    {
+      mgx_smoother_info i{};
+      check(mgx_dg_plain_solver_smoother_info(h_, (int)level, &i));
+      return i;
+    }
+    std::vector<LaplaceOperatorCompactCombine<dim, fe_degree, Number, type>> matrix;       // :550
+    LaplaceOperatorCompactCombine<dim, fe_degree, Number2, type>             matrix_dg_dp; // :551
+    mgx_dg_plain_solver_t handle() const { return h_; }
+
+  private:
+    void release()
+    {
+      mgx_dg_plain_solver_destroy(h_);
+      h_ = nullptr;
+      for (mgx_dg_transfer_t &t : transfer_)
+        {
+          mgx_dg_transfer_destroy(t);
+          t = nullptr;
+        }
+    }
+    std::vector<mgx_dg_transfer_t> transfer_;
+    mgx_dg_plain_solver_t          h_ = nullptr;
   };
 } // namespace multigrid

@@ -1162,6 +1162,16 @@ def dg_box_neighbours(cells, ordering="z"):
     return nb, ijk
 
 
+def dg_box_children(coarse_cells, coarse_ordering="z", fine_ordering="z"):
+    """child table [n_coarse, 8] between a box of cells and its global refinement, both numbered as
+    dg_box_neighbours numbers them: entry kx + 2 ky + 4 kz is the fine cell at 2 ijk + (kx, ky, kz)"""
+    c = (C.c_int * 3)(*coarse_cells)
+    ch = np.empty((int(np.prod(coarse_cells)), 8), dtype=np.uint32)
+    check(_lib.load().mgx_dg_box_children(C.byref(c), 1 if coarse_ordering == "z" else 0, 1 if fine_ordering == "z" else 0,
+                                          ch.ctypes.data_as(_lib.u32p)))
+    return ch
+
+
 def dg_partition(ijk, cells, procs, rank):
     """Ghost cells and exchange lists of a block decomposition, for the owned cells `ijk` ([n, 3] global
     positions, in the local cell order) of the rank whose block of the process grid they fill.
@@ -1404,3 +1414,133 @@ class DGMultigridSolver:
             self.matrix_dg.clear()
             self.matrix_dg_dp.clear()
             self.cfe.close()
+
+
+class DGLevelTransfer:
+    """MGTransferMatrixFree between two DG levels of the same degree and basis (include/mgx_dg.h): a cell and
+    its eight children, `children` [n_coarse, 8] as dg_box_children() gives it."""
+
+    def __init__(self, ctx, degree, basis, children, number=F32):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.degree, self.basis, self.number = degree, basis, number
+        ch = np.ascontiguousarray(children, dtype=np.uint32).reshape(-1, 8)
+        d = _lib.DGTransferDesc(degree, basis, number, ch.shape[0], ch.ctypes.data_as(_lib.u32p))
+        h = C.c_void_p()
+        check(self.lib.mgx_dg_transfer_create(ctx.h, C.byref(d), C.byref(h)))
+        self.h = h
+
+    def prolongate_and_add(self, fine, coarse):
+        check(self.lib.mgx_dg_transfer_prolongate_and_add(self.h, fine.ptr, coarse.ptr))
+
+    def restrict_and_add(self, coarse, fine):
+        check(self.lib.mgx_dg_transfer_restrict_and_add(self.h, coarse.ptr, fine.ptr))
+
+    def matrix(self):
+        """P[h, i, j]: coefficient i, in the child's basis, of the parent's function j on the half h of [0, 1]"""
+        n = self.degree + 1
+        P = np.empty((2, n, n))
+        check(self.lib.mgx_dg_transfer_matrix(self.h, P.ctypes.data_as(_lib.f64p)))
+        return P
+
+    def clear(self):
+        if getattr(self, "h", None):
+            self.lib.mgx_dg_transfer_destroy(self.h)
+            self.h = None
+
+
+class DGPlainMultigridSolver:
+    """multigrid::MultigridSolverDGPlain<3,p,Number,double> (common/multigrid_solver_dg_plain.h:55-595) on a box of
+    coarse_cells refined n_levels - 1 times: the DG-SIP operator on every level (cells 2^l per coarse cell and
+    direction, Jacobian jacobian0 / 2^l), Chebyshev smoothers with the JacobiTransformed preconditioner, DG-to-DG
+    transfers, level 0 solved by its Chebyshev iteration; V-cycle in `vcycle_number`, outer CG in fp64."""
+
+    def __init__(self, ctx, degree, basis, coarse_cells, jacobian0, n_levels, degree_pre=3, vcycle_number=F32, ordering="z"):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.degree, self.basis, self.n_levels, self.vnumber = degree, basis, n_levels, vcycle_number
+        jac0 = np.asarray(jacobian0, dtype=float).reshape(3, 3)
+        self.cells, self.cell_ijk, self.cell_gid, self.matrix, self.transfer = [], [], [], [], []
+        self.matrix_dg_dp = self.h = None
+        try:
+            for l in range(n_levels):
+                cells = tuple(int(c) << l for c in coarse_cells)
+                nb, ijk = dg_box_neighbours(cells, ordering)
+                self.cells.append(cells)
+                self.cell_ijk.append(ijk)
+                i64 = ijk.astype(np.int64)
+                self.cell_gid.append(np.ascontiguousarray(i64[:, 0] + cells[0] * (i64[:, 1] + cells[1] * i64[:, 2]), dtype=np.uint32))
+                self.matrix.append(DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, vcycle_number))
+                if l == n_levels - 1:
+                    self.matrix_dg_dp = DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, F64)
+                if l > 0:
+                    self.transfer.append(DGLevelTransfer(ctx, degree, basis, dg_box_children(self.cells[l - 1], ordering, ordering),
+                                                         vcycle_number))
+            d = _lib.DGPlainSolverDesc()
+            d.n_levels = n_levels
+            d.matrix = (_lib.vp * n_levels)(*[m.h for m in self.matrix])
+            d.matrix_dg_dp = self.matrix_dg_dp.h
+            d.transfer = (_lib.vp * max(1, n_levels - 1))(*[t.h for t in self.transfer])
+            d.degree_pre = degree_pre
+            d.cell_global_id = (_lib.u32p * n_levels)(*[g.ctypes.data_as(_lib.u32p) for g in self.cell_gid])
+            h = C.c_void_p()
+            check(self.lib.mgx_dg_plain_solver_create(ctx.h, C.byref(d), C.byref(h)))
+            self.h = h
+        except Exception:
+            self.close()
+            raise
+
+    def m(self):
+        return self.matrix[-1].m()
+
+    def initialize_dof_vector(self, data=None):
+        """fp64 vector of the finest level"""
+        return self.matrix_dg_dp.initialize_dof_vector(data)
+
+    def smoother_info(self, level):
+        i = _lib.SmootherInfo()
+        check(self.lib.mgx_dg_plain_solver_smoother_info(self.h, level, C.byref(i)))
+        return dict(lambda_min=i.lambda_min, lambda_max=i.lambda_max, theta=i.theta, delta=i.delta,
+                    degree=i.degree, cg_its=i.cg_iterations)
+
+    def vmult(self, dst, src):
+        """one V-cycle (multigrid_solver_dg_plain.h:322-334); fp64 vectors"""
+        check(self.lib.mgx_dg_plain_solver_vmult(self.h, dst.ptr, src.ptr))
+
+    def solve_cg(self, rhs, solution, tolerance=1e-9):
+        """(iterations, reduction rate per iteration) of the V-cycle-preconditioned CG (:303-317)"""
+        its, red = C.c_uint(), C.c_double()
+        check(self.lib.mgx_dg_plain_solver_solve_cg(self.h, tolerance, rhs.ptr, solution.ptr, C.byref(its), C.byref(red)))
+        return its.value, red.value
+
+    def vmult_with_residual_update(self, residual, update, factor):
+        """(:340-427) residual += factor update, update = V-cycle(residual); returns (mg.residual, mg.(factor update))"""
+        out = np.empty(2)
+        check(self.lib.mgx_dg_plain_solver_vmult_with_residual_update(self.h, residual.ptr, update.ptr, factor,
+                                                                       out.ctypes.data_as(_lib.f64p)))
+        return out
+
+    def enable_timings(self, on=True):
+        check(self.lib.mgx_dg_plain_solver_enable_timings(self.h, 1 if on else 0))
+
+    def wall_times(self):
+        """[n_levels, 6] seconds since the last call, the columns of the reference's timings[level] (print_wall_times)"""
+        t = np.zeros((self.n_levels, 6))
+        check(self.lib.mgx_dg_plain_solver_get_timings(self.h, t.ctypes.data_as(_lib.f64p)))
+        return t
+
+    def do_matvec(self):
+        check(self.lib.mgx_dg_plain_solver_do_matvec(self.h))
+
+    def do_matvec_smoother(self):
+        check(self.lib.mgx_dg_plain_solver_do_matvec_smoother(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mgx_dg_plain_solver_destroy(self.h)
+            self.h = None
+        for t in self.transfer:
+            t.clear()
+        for m in self.matrix:
+            m.clear()
+        if self.matrix_dg_dp is not None:
+            self.matrix_dg_dp.clear()
+        self.transfer, self.matrix, self.matrix_dg_dp = [], [], None

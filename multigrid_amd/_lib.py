@@ -67,6 +67,16 @@ class DGSolverDesc(C.Structure):
                 ("cell_global_id", u32p)]
 
 
+class DGTransferDesc(C.Structure):
+    _fields_ = [("degree", C.c_int), ("basis", C.c_int), ("number", C.c_int), ("n_coarse_cells", C.c_uint32),
+                ("children", u32p)]
+
+
+class DGPlainSolverDesc(C.Structure):
+    _fields_ = [("n_levels", C.c_int), ("matrix", C.POINTER(vp)), ("matrix_dg_dp", vp), ("transfer", C.POINTER(vp)),
+                ("degree_pre", C.c_int), ("cell_global_id", C.POINTER(u32p))]
+
+
 class SmootherInfo(C.Structure):
     _fields_ = [("lambda_min", C.c_double), ("lambda_max", C.c_double), ("theta", C.c_double),
                 ("delta", C.c_double), ("degree", C.c_int), ("cg_iterations", C.c_int)]
@@ -260,6 +270,22 @@ SIGNATURES = {
     "mgx_dg_restrict_to_cg": (C.c_int, [vp, vp, vp]),
     "mgx_dg_prolongate_add_cg_to_dg": (C.c_int, [vp, vp, vp]),
     "mgx_dg_vmult_residual_and_restrict_to_cg": (C.c_int, [vp, vp, vp, vp]),
+    "mgx_dg_transfer_create": (C.c_int, [vp, C.POINTER(DGTransferDesc), C.POINTER(vp)]),
+    "mgx_dg_transfer_destroy": (C.c_int, [vp]),
+    "mgx_dg_transfer_prolongate_and_add": (C.c_int, [vp, vp, vp]),
+    "mgx_dg_transfer_restrict_and_add": (C.c_int, [vp, vp, vp]),
+    "mgx_dg_transfer_matrix": (C.c_int, [vp, f64p]),
+    "mgx_dg_plain_solver_create": (C.c_int, [vp, C.POINTER(DGPlainSolverDesc), C.POINTER(vp)]),
+    "mgx_dg_plain_solver_destroy": (C.c_int, [vp]),
+    "mgx_dg_plain_solver_smoother_info": (C.c_int, [vp, C.c_int, C.POINTER(SmootherInfo)]),
+    "mgx_dg_plain_solver_vmult": (C.c_int, [vp, vp, vp]),
+    "mgx_dg_plain_solver_solve_cg": (C.c_int, [vp, C.c_double, vp, vp, C.POINTER(C.c_uint), f64p]),
+    "mgx_dg_plain_solver_vmult_with_residual_update": (C.c_int, [vp, vp, vp, C.c_double, f64p]),
+    "mgx_dg_plain_solver_enable_timings": (C.c_int, [vp, C.c_int]),
+    "mgx_dg_plain_solver_get_timings": (C.c_int, [vp, f64p]),
+    "mgx_dg_plain_solver_do_matvec": (C.c_int, [vp]),
+    "mgx_dg_plain_solver_do_matvec_smoother": (C.c_int, [vp]),
+    "mgx_dg_box_children": (C.c_int, [C.POINTER(C.c_int * 3), C.c_int, C.c_int, u32p]),
     "mgx_dg_cheby_mesh": (C.c_int, [C.c_int, C.POINTER(C.c_int * 3), C.POINTER(C.c_double * 9)]),
     "mgx_dg_box_neighbours": (C.c_int, [C.POINTER(C.c_int * 3), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

@@ -811,6 +811,11 @@ namespace
   }
 } // namespace
 
+void mgx::tridiag_extreme_eigenvalues(int n, const double *d, const double *e, double &lo, double &hi)
+{
+  tridiag_extreme(n, d, e, lo, hi);
+}
+
 // Point-to-point exchange of packed device buffers with the context's transport (native RCCL group
 // on the stream, or the blocking callback), for the parts of the ABI implemented in other
 // translation units (the DG ghost-cell update); allreduce of a few host doubles likewise

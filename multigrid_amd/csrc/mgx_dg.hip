@@ -25,6 +25,7 @@
 #include "../../include/mgx_dg.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -1206,6 +1207,45 @@ namespace
     return out;
   }
 
+  // inverse of a dense n x n matrix (row-major), Gauss-Jordan with partial pivoting; false: singular
+  bool invert(int n, std::vector<double> Bm, std::vector<double> &inv)
+  {
+    inv.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i)
+      inv[i * n + i] = 1;
+    for (int col = 0; col < n; ++col)
+      {
+        int piv = col;
+        for (int r = col + 1; r < n; ++r)
+          if (std::abs(Bm[r * n + col]) > std::abs(Bm[piv * n + col]))
+            piv = r;
+        if (std::abs(Bm[piv * n + col]) < 1e-14)
+          return false;
+        for (int k = 0; k < n; ++k)
+          {
+            std::swap(Bm[piv * n + k], Bm[col * n + k]);
+            std::swap(inv[piv * n + k], inv[col * n + k]);
+          }
+        const double dinv = 1.0 / Bm[col * n + col];
+        for (int k = 0; k < n; ++k)
+          {
+            Bm[col * n + k] *= dinv;
+            inv[col * n + k] *= dinv;
+          }
+        for (int r = 0; r < n; ++r)
+          if (r != col)
+            {
+              const double f = Bm[r * n + col];
+              for (int k = 0; k < n; ++k)
+                {
+                  Bm[r * n + k] -= f * Bm[col * n + k];
+                  inv[r * n + k] -= f * inv[col * n + k];
+                }
+            }
+      }
+    return true;
+  }
+
   struct Host1D
   {
     int                 n = 0;
@@ -1214,6 +1254,9 @@ namespace
     double              b[2][kMaxN], g[2][kMaxN], fb[2][kMaxN], fg[2][kMaxN];
     double              hderiv = 0;
     std::vector<double> P1; // [i*n+q]: values in the Gauss-Lobatto nodes -> coefficients of the element basis
+    // [h*n*n + i*n+j], h = 0, 1: coefficient i, in this basis on [0,1], of phi_j((x + h) / 2) -- the embedding of a
+    // cell's space into the spaces of its two halves (level transfer between DG spaces)
+    std::vector<double> embed;
     // eigenfunctions: Laplace form, first-derivative form, values and derivatives at the two ends
     std::vector<double> lt, ct, beta[2], gamma[2];
   };
@@ -1266,46 +1309,35 @@ namespace
       nodes.push_back(1.0);
       if (n == 1)
         nodes = {0.5};
-      std::vector<double> Bm(n * n), inv(n * n, 0.0);
+      std::vector<double> Bm(n * n);
       for (int q = 0; q < n; ++q)
         for (int i = 0; i < n; ++i)
           Bm[q * n + i] = fe[i].val(nodes[q]);
-      for (int i = 0; i < n; ++i)
-        inv[i * n + i] = 1;
-      for (int col = 0; col < n; ++col) // Gauss-Jordan with partial pivoting
+      if (!invert(n, Bm, h.P1))
         {
-          int piv = col;
-          for (int r = col + 1; r < n; ++r)
-            if (std::abs(Bm[r * n + col]) > std::abs(Bm[piv * n + col]))
-              piv = r;
-          if (std::abs(Bm[piv * n + col]) < 1e-14)
-            {
-              why = "element basis is not unisolvent in the Gauss-Lobatto nodes";
-              return MGX_ERR_UNSUPPORTED;
-            }
-          for (int k = 0; k < n; ++k)
-            {
-              std::swap(Bm[piv * n + k], Bm[col * n + k]);
-              std::swap(inv[piv * n + k], inv[col * n + k]);
-            }
-          const double dinv = 1.0 / Bm[col * n + col];
-          for (int k = 0; k < n; ++k)
-            {
-              Bm[col * n + k] *= dinv;
-              inv[col * n + k] *= dinv;
-            }
-          for (int r = 0; r < n; ++r)
-            if (r != col)
-              {
-                const double f = Bm[r * n + col];
-                for (int k = 0; k < n; ++k)
-                  {
-                    Bm[r * n + k] -= f * Bm[col * n + k];
-                    inv[r * n + k] -= f * inv[col * n + k];
-                  }
-              }
+          why = "element basis is not unisolvent in the Gauss-Lobatto nodes";
+          return MGX_ERR_UNSUPPORTED;
         }
-      h.P1 = inv;
+    }
+    {
+      // embedding into the two halves of the cell: sum_i P_h[i][j] phi_i(x_q) = phi_j((x_q + h) / 2) in the Gauss
+      // points x_q, i.e. P_h = S^-1 V_h (the spaces are nested: any unisolvent set of points gives the same matrix)
+      std::vector<double> Sinv;
+      if (!invert(n, h.S, Sinv))
+        {
+          why = "element basis is not unisolvent in the Gauss points";
+          return MGX_ERR_UNSUPPORTED;
+        }
+      h.embed.assign(2 * n * n, 0.0);
+      for (int half = 0; half < 2; ++half)
+        for (int i = 0; i < n; ++i)
+          for (int j = 0; j < n; ++j)
+            {
+              double v = 0;
+              for (int q = 0; q < n; ++q)
+                v += Sinv[i * n + q] * fe[j].val(0.5 * (h.xq[q] + half));
+              h.embed[(half * n + i) * n + j] = v;
+            }
     }
 
     // generalised eigenproblem lapl v = lambda mass v (laplace_operator_dg.h:179-215)
@@ -1727,6 +1759,41 @@ struct mgx_dg_solver_s
   bool              cg_eight_colours = false; // cells c, c + 8, ... of the FE_Q level share no DoF
   void             *cg_defect = nullptr, *cg_update = nullptr; // the FE_Q solver's finest-level vectors
   double           *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr; // PCG, fp64
+};
+
+// MGTransferMatrixFree between two DG levels (mgx_dg_transfer.hip)
+struct mgx_dg_transfer_s
+{
+  mgx_context_t       ctx = nullptr;
+  mgx::DeviceArena    mem{"mgx_dg_transfer"};
+  int                 degree = 0, basis = 0, number = MGX_F32;
+  uint32_t            n_coarse = 0;
+  uint32_t           *children = nullptr; // device [n_coarse][8]
+  bool                identity = false;   // children[c][k] == 8 c + k (checked at creation): the table is not read
+  void               *p1d      = nullptr; // device [2][(p+1)^2], number type
+  std::vector<double> p1d_host;
+};
+
+// MultigridSolverDGPlain (common/multigrid_solver_dg_plain.h:55-595)
+struct mgx_dg_plain_solver_s
+{
+  struct Level
+  {
+    mgx_dg_operator_t A = nullptr;
+    mgx_dg_transfer_t transfer = nullptr; // from the level below (null on level 0)
+    size_t            n = 0;
+    mgx_smoother_info info{};
+    void             *defect = nullptr, *t = nullptr, *update = nullptr, *old = nullptr; // V-cycle number type
+    double            times[6] = {0, 0, 0, 0, 0, 0};                                     // timings[level] of the reference
+  };
+  mgx_context_t      ctx = nullptr;
+  mgx::DeviceArena   mem{"mgx_dg_plain_solver"};
+  std::vector<Level> level;
+  mgx_dg_operator_t  A_dp = nullptr;
+  int                number = MGX_F32;
+  double            *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr; // PCG, fp64
+  double            *partials = nullptr, *sums = nullptr;                   // vmult_with_residual_update
+  bool               timed = false;
 };
 
 namespace
@@ -2298,33 +2365,35 @@ namespace
       }
   }
 
-  int dg_dot(mgx_dg_solver_t S, int number, const void *x, const void *y, double *out)
+  // over the first n (owned) entries
+  int dg_dot(mgx_context_t ctx, size_t n, int number, const void *x, const void *y, double *out)
   {
-    return mgx::dot_owned_prefix(S->ctx, number, x, y, S->n, out);
+    return mgx::dot_owned_prefix(ctx, number, x, y, n, out);
   }
 
-  int dg_norm(mgx_dg_solver_t S, int number, const void *x, double *out)
+  int dg_norm(mgx_context_t ctx, size_t n, int number, const void *x, double *out)
   {
-    MGX_TRY(mgx::dot_owned_prefix(S->ctx, number, x, x, S->n, out));
+    MGX_TRY(mgx::dot_owned_prefix(ctx, number, x, x, n, out));
     *out = std::sqrt(*out);
     return MGX_OK;
   }
 
   // PreconditionChebyshev<LaplaceOperatorCompactCombine, Vector, JacobiTransformed>: vmult (zero start) and
   // step, through the merged operation (deal.II hands iteration index 0 / 1, then k + 1 / k + 2)
-  int dg_smoother_apply(mgx_dg_solver_t S, bool is_step)
+  // (update and old trade places with every step, as the reference swaps its two vectors)
+  int dg_smoother_apply(mgx_dg_operator_t A, const mgx_smoother_info &I, const void *defect, void *&update, void *&old,
+                        bool is_step)
   {
-    const mgx_smoother_info &I = S->info;
-    int                      index;
+    int index;
     if (!is_step)
       {
-        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, 0, 0., 1. / I.theta, S->update, S->old));
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, 0, 0., 1. / I.theta, update, old));
         index = 1;
       }
     else
       {
-        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, 1, 0., 1. / I.theta, S->update, S->old));
-        std::swap(S->update, S->old);
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, 1, 0., 1. / I.theta, update, old));
+        std::swap(update, old);
         index = 2;
       }
     if (I.degree < 2 || std::fabs(I.delta) < 1e-40)
@@ -2336,9 +2405,121 @@ namespace
         const double rhokp = 1. / (2. * sigma - rhok);
         const double f1 = rhokp * rhok, f2 = 2. * rhokp / I.delta;
         rhok = rhokp;
-        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(S->A, S->defect, (unsigned)index, f1, f2, S->update, S->old));
-        std::swap(S->update, S->old);
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, (unsigned)index, f1, f2, update, old));
+        std::swap(update, old);
       }
+    return MGX_OK;
+  }
+
+  int dg_smoother_apply(mgx_dg_solver_t S, bool is_step) { return dg_smoother_apply(S->A, S->info, S->defect, S->update, S->old, is_step); }
+
+  // PreconditionChebyshev::initialize -> estimate_eigenvalues for a DG operator with JacobiTransformed
+  // (multigrid_solver_dg.h:293-303, multigrid_solver_dg_plain.h:192-213): at most max_its iterations of CG
+  // preconditioned with JacobiTransformed on v_i = (global index of i mod 11) - mean, stopped at a residual of 1e-10;
+  // lambda_max = 1.2 x the largest Ritz value.  smoothing_range > 1: [lambda_max / range, lambda_max]; otherwise
+  // [min(0.9 lambda_max, lambda_min), lambda_max].  degree < 0 (numbers::invalid_unsigned_int): Varga's estimate of the
+  // degree that reduces the error by smoothing_range.  r, z, d, h: four vectors of the operator, overwritten;
+  // cell_global_id: host, may be null.  A step whose d.A d or r.z is not a positive finite number ends the estimate
+  // with the Ritz values collected so far (fp32 on a level that CG has already solved to rounding).
+  int dg_smoother_initialize(mgx_context_t ctx, mgx_dg_operator_t A, const uint32_t *cell_global_id, void *r, void *z, void *d,
+                             void *h, int max_its, double smoothing_range, int degree, mgx_smoother_info &I)
+  {
+    hipStream_t  s      = (hipStream_t)mgx_context_stream(ctx);
+    const size_t n      = (size_t)mgx_dg_operator_n_dofs(A);
+    const int    number = A->number;
+    double       ng     = (double)n; // global number of DoFs
+    MGX_TRY(mgx::allreduce_sum(ctx, &ng, 1));
+    const uint64_t ngl  = (uint64_t)(ng + 0.5);
+    const uint64_t full = ngl / 11, rem = ngl % 11;
+    const double   mean = (full * 55.0 + rem * (rem - 1) / 2.0) / (double)ngl;
+    {
+      mgx::DeviceArena tmp("DG smoother set-up");
+      uint32_t        *cell_id = nullptr;
+      if (cell_global_id)
+        MGX_TRY(tmp.upload(&cell_id, cell_global_id, A->n_cells));
+      const uint32_t n3   = (uint32_t)(n / A->n_cells);
+      const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192);
+      if (number == MGX_F64)
+        hipLaunchKernelGGL(k_start_vector<double>, dim3(grid), dim3(256), 0, s, (double *)r, cell_id, A->n_cells, n3, mean);
+      else
+        hipLaunchKernelGGL(k_start_vector<float>, dim3(grid), dim3(256), 0, s, (float *)r, cell_id, A->n_cells, n3, mean);
+      MGX_HIP(hipStreamSynchronize(s));
+    }
+    std::vector<double> diag, off;
+    double              res = 0, rz = 0, rz_old = 0, alpha = 0, alpha_old = 0, beta = 0;
+    MGX_TRY(dg_norm(ctx, n, number, r, &res));
+    int it = 0;
+    while (it < max_its && res > 1e-10)
+      {
+        rz_old = rz;
+        MGX_TRY(mgx_dg_jacobi_vmult(A, z, r));
+        MGX_TRY(dg_dot(ctx, n, number, r, z, &rz));
+        if (!(rz > 0.) || !std::isfinite(rz))
+          break;
+        ++it;
+        if (it > 1)
+          {
+            beta = rz / rz_old;
+            MGX_TRY(mgx_sadd(ctx, number, d, beta, 1.0, z, n));
+          }
+        else
+          MGX_TRY(mgx_copy_cast(ctx, d, number, z, number, n));
+        MGX_TRY(mgx_dg_vmult(A, h, d));
+        double dh = 0;
+        MGX_TRY(dg_dot(ctx, n, number, d, h, &dh));
+        if (!(dh > 0.) || !std::isfinite(dh))
+          {
+            --it;
+            break;
+          }
+        alpha_old = alpha;
+        alpha     = rz / dh;
+        MGX_TRY(mgx_sadd(ctx, number, r, 1.0, -alpha, h, n));
+        MGX_TRY(dg_norm(ctx, n, number, r, &res));
+        if (it == 1)
+          diag.push_back(1. / alpha);
+        else
+          {
+            off.push_back(std::sqrt(beta) / alpha_old);
+            diag.push_back(1. / alpha + beta / alpha_old);
+          }
+      }
+    I.cg_iterations = it;
+    if (diag.empty())
+      I.lambda_min = I.lambda_max = 1.;
+    else if (diag.size() <= 64)
+      {
+        const int           m = (int)diag.size();
+        std::vector<double> Tm((size_t)m * m, 0.0), lam, V;
+        for (int i = 0; i < m; ++i)
+          {
+            Tm[i * m + i] = diag[i];
+            if (i + 1 < m)
+              Tm[i * m + i + 1] = Tm[(i + 1) * m + i] = off[i];
+          }
+        sym_eig(m, Tm, lam, V);
+        I.lambda_min = lam.front();
+        I.lambda_max = 1.2 * lam.back();
+      }
+    else // (the Jacobi sweeps above cost m^3 each: bisection on the tridiagonal matrix for a long Lanczos run)
+      {
+        double lo = 0, hi = 0;
+        off.push_back(0.);
+        mgx::tridiag_extreme_eigenvalues((int)diag.size(), diag.data(), off.data(), lo, hi);
+        I.lambda_min = lo;
+        I.lambda_max = 1.2 * hi;
+      }
+    const double a = smoothing_range > 1. ? I.lambda_max / smoothing_range : std::min(0.9 * I.lambda_max, I.lambda_min);
+    if (degree < 0)
+      {
+        const double actual_range = I.lambda_max / a;
+        const double sigma        = (1. - std::sqrt(1. / actual_range)) / (1. + std::sqrt(1. / actual_range));
+        const double eps          = smoothing_range;
+        degree = 1 + (int)(std::log(1. / eps + std::sqrt(1. / eps / eps - 1.)) / std::log(1. / sigma));
+      }
+    I.degree = degree;
+    I.delta  = (I.lambda_max - a) * 0.5;
+    I.theta  = (I.lambda_max + a) * 0.5;
     return MGX_OK;
   }
 
@@ -2485,81 +2666,9 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
   // CG preconditioned with JacobiTransformed on v_i = (i mod 11) - mean, lambda_max = 1.2 x the
   // largest Ritz value, range 20
   {
-    const size_t n  = S->n;
-    void        *r = S->t, *z = S->update, *d = S->old, *h = S->defect; // free until the first cycle
-    double ng = (double)n; // global number of DoFs
-    MGX_TRY(mgx::allreduce_sum(ctx, &ng, 1));
-    const uint64_t ngl  = (uint64_t)(ng + 0.5);
-    const uint64_t full = ngl / 11, rem = ngl % 11;
-    const double   mean = (full * 55.0 + rem * (rem - 1) / 2.0) / (double)ngl;
-    mgx::DeviceArena tmp("mgx_dg_solver_create");
-    uint32_t        *cell_id = nullptr;
-    if (desc->cell_global_id)
-      MGX_TRY(tmp.upload(&cell_id, desc->cell_global_id, S->n_cells));
-    {
-      const uint32_t n3   = (uint32_t)(n / S->n_cells);
-      const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192);
-      if (S->number == MGX_F64)
-        hipLaunchKernelGGL(k_start_vector<double>, dim3(grid), dim3(256), 0, s, (double *)r, cell_id, S->n_cells, n3, mean);
-      else
-        hipLaunchKernelGGL(k_start_vector<float>, dim3(grid), dim3(256), 0, s, (float *)r, cell_id, S->n_cells, n3, mean);
-      MGX_HIP(hipStreamSynchronize(s));
-      tmp.release(cell_id);
-    }
-    std::vector<double> diag, off;
-    double              res = 0, rz = 0, rz_old = 0, alpha = 0, alpha_old = 0, beta = 0;
-    MGX_TRY(dg_norm(S.get(), S->number, r, &res));
-    int it = 0;
-    while (it < 15 && res > 1e-10)
-      {
-        ++it;
-        rz_old = rz;
-        MGX_TRY(mgx_dg_jacobi_vmult(A, z, r));
-        MGX_TRY(dg_dot(S.get(), S->number, r, z, &rz));
-        if (it > 1)
-          {
-            beta = rz / rz_old;
-            MGX_TRY(mgx_sadd(ctx, S->number, d, beta, 1.0, z, n));
-          }
-        else
-          MGX_TRY(mgx_copy_cast(ctx, d, S->number, z, S->number, n));
-        alpha_old = alpha;
-        MGX_TRY(mgx_dg_vmult(A, h, d));
-        double dh = 0;
-        MGX_TRY(dg_dot(S.get(), S->number, d, h, &dh));
-        alpha = rz / dh;
-        MGX_TRY(mgx_sadd(ctx, S->number, r, 1.0, -alpha, h, n));
-        MGX_TRY(dg_norm(S.get(), S->number, r, &res));
-        if (it == 1)
-          diag.push_back(1. / alpha);
-        else
-          {
-            off.push_back(std::sqrt(beta) / alpha_old);
-            diag.push_back(1. / alpha + beta / alpha_old);
-          }
-      }
-    mgx_smoother_info &I = S->info;
-    I.cg_iterations      = it;
-    if (diag.empty())
-      I.lambda_min = I.lambda_max = 1.;
-    else
-      {
-        const int           m = (int)diag.size();
-        std::vector<double> Tm((size_t)m * m, 0.0), lam, V;
-        for (int i = 0; i < m; ++i)
-          {
-            Tm[i * m + i] = diag[i];
-            if (i + 1 < m)
-              Tm[i * m + i + 1] = Tm[(i + 1) * m + i] = off[i];
-          }
-        sym_eig(m, Tm, lam, V);
-        I.lambda_min = lam.front();
-        I.lambda_max = 1.2 * lam.back();
-      }
-    const double a = I.lambda_max / 20.;
-    I.degree       = desc->degree_pre;
-    I.delta        = (I.lambda_max - a) * 0.5;
-    I.theta        = (I.lambda_max + a) * 0.5;
+    // (the level vectors are free until the first cycle)
+    MGX_TRY(dg_smoother_initialize(ctx, A, desc->cell_global_id, S->t, S->update, S->old, S->defect, 15, 20., desc->degree_pre,
+                                   S->info));
     for (void *v : {S->defect, S->t, S->update, S->old})
       MGX_HIP(hipMemsetAsync(v, 0, vb, s));
     MGX_HIP(hipStreamSynchronize(s));
@@ -2637,7 +2746,7 @@ int mgx_dg_solver_solve_cg(mgx_dg_solver_t S, double tolerance, const double *rh
   MGX_HIP(hipMemsetAsync(solution, 0, 8 * S->n_vec, s));
   MGX_TRY(mgx_copy_cast(ctx, r, MGX_F64, rhs, MGX_F64, n));
   double res0 = 0, res = 0, rz = 0, rz_old = 0;
-  MGX_TRY(dg_norm(S, MGX_F64, r, &res0));
+  MGX_TRY(dg_norm(ctx, n, MGX_F64, r, &res0));
   res         = res0;
   unsigned it = 0;
   while (res > std::max(1e-16, tolerance * res0) && it < 100)
@@ -2645,18 +2754,18 @@ int mgx_dg_solver_solve_cg(mgx_dg_solver_t S, double tolerance, const double *rh
       ++it;
       MGX_TRY(mgx_dg_solver_vmult(S, z, r));
       rz_old = rz;
-      MGX_TRY(dg_dot(S, MGX_F64, r, z, &rz));
+      MGX_TRY(dg_dot(ctx, n, MGX_F64, r, z, &rz));
       if (it > 1)
         MGX_TRY(mgx_sadd(ctx, MGX_F64, d, rz / rz_old, 1.0, z, n));
       else
         MGX_TRY(mgx_copy_cast(ctx, d, MGX_F64, z, MGX_F64, n));
       MGX_TRY(mgx_dg_vmult(S->A_dp, h, d));
       double dh = 0;
-      MGX_TRY(dg_dot(S, MGX_F64, d, h, &dh));
+      MGX_TRY(dg_dot(ctx, n, MGX_F64, d, h, &dh));
       const double alpha = rz / dh;
       MGX_TRY(mgx_sadd(ctx, MGX_F64, solution, 1.0, alpha, d, n));
       MGX_TRY(mgx_sadd(ctx, MGX_F64, r, 1.0, -alpha, h, n));
-      MGX_TRY(dg_norm(S, MGX_F64, r, &res));
+      MGX_TRY(dg_norm(ctx, n, MGX_F64, r, &res));
     }
   if (iterations)
     *iterations = it;
@@ -2664,6 +2773,394 @@ int mgx_dg_solver_solve_cg(mgx_dg_solver_t S, double tolerance, const double *rh
     *reduction_rate = it ? std::pow(res / res0, 1.0 / it) : 1.0;
   return res > std::max(1e-16, tolerance * res0) ? dg_fail(MGX_ERR_NOT_CONVERGED, "mgx_dg_solver_solve_cg: 100 iterations")
                                                  : MGX_OK;
+}
+
+} // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * DG-to-DG level transfer and MultigridSolverDGPlain
+ * --------------------------------------------------------------------------------------------- */
+namespace
+{
+  // one part of a V-cycle, timed when the solver's timings are on (print_wall_times of the reference: host timers
+  // around synchronised parts -- for diagnosis, the parts no longer overlap their launches)
+  struct PlainTimer
+  {
+    mgx_dg_plain_solver_t S;
+    double               *slot;
+    std::chrono::steady_clock::time_point t0;
+    PlainTimer(mgx_dg_plain_solver_t solver, double *where)
+      : S(solver)
+      , slot(where)
+    {
+      if (S->timed)
+        {
+          (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
+          t0 = std::chrono::steady_clock::now();
+        }
+    }
+    ~PlainTimer()
+    {
+      if (S->timed)
+        {
+          (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
+          *slot += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+    }
+  };
+
+  // v_cycle(level, 1) (multigrid_solver_dg_plain.h:456-496): defect[level] in, update[level] out
+  int plain_v_cycle(mgx_dg_plain_solver_t S, int l)
+  {
+    hipStream_t                   s = (hipStream_t)mgx_context_stream(S->ctx);
+    mgx_dg_plain_solver_s::Level &L = S->level[l];
+    if (l == 0) // coarse = the level-0 smoother's vmult (:462)
+      {
+        PlainTimer timer(S, &L.times[0]);
+        L.times[1] += 1;
+        return dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, false);
+      }
+    mgx_dg_plain_solver_s::Level &C = S->level[l - 1];
+    {
+      PlainTimer timer(S, &L.times[5]);
+      MGX_TRY(dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, false)); // :472
+    }
+    {
+      PlainTimer timer(S, &L.times[0]);
+      MGX_TRY(mgx_dg_vmult_residual(L.A, L.t, L.defect, L.update)); // :478
+    }
+    {
+      PlainTimer timer(S, &L.times[1]);
+      MGX_HIP(hipMemsetAsync(C.defect, 0, dg_nsz(S->number) * C.n, s)); // :482
+      MGX_TRY(mgx_dg_transfer_restrict_and_add(L.transfer, C.defect, L.t)); // :483
+    }
+    MGX_TRY(plain_v_cycle(S, l - 1));
+    {
+      PlainTimer timer(S, &L.times[2]);
+      MGX_TRY(mgx_dg_transfer_prolongate_and_add(L.transfer, L.update, C.update)); // :489
+    }
+    PlainTimer timer(S, &L.times[5]);
+    return dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, true); // :493
+  }
+} // namespace
+
+extern "C" {
+
+int mgx_dg_box_children(const int coarse_cells[3], int coarse_ordering, int fine_ordering, uint32_t *children)
+{
+  if (!coarse_cells || !children || coarse_cells[0] < 1 || coarse_cells[1] < 1 || coarse_cells[2] < 1)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_box_children: invalid argument");
+  const uint64_t nc = (uint64_t)coarse_cells[0] * coarse_cells[1] * coarse_cells[2];
+  if (8 * nc >= (1ull << 31))
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_box_children: more than 2^31 fine cells");
+  const int fine_cells[3] = {2 * coarse_cells[0], 2 * coarse_cells[1], 2 * coarse_cells[2]};
+  std::vector<int32_t> nb(6 * (size_t)8 * nc), cijk(3 * (size_t)nc), fijk(3 * (size_t)8 * nc);
+  MGX_TRY(mgx_dg_box_neighbours(coarse_cells, coarse_ordering, nb.data(), cijk.data()));
+  MGX_TRY(mgx_dg_box_neighbours(fine_cells, fine_ordering, nb.data(), fijk.data()));
+  std::vector<uint32_t> at(8 * (size_t)nc); // lexicographic position of a fine cell -> its number
+  for (uint32_t f = 0; f < 8 * nc; ++f)
+    at[fijk[3 * (size_t)f] + (size_t)fine_cells[0] * (fijk[3 * (size_t)f + 1] + (size_t)fine_cells[1] * fijk[3 * (size_t)f + 2])] = f;
+  for (uint32_t c = 0; c < nc; ++c)
+    for (int k = 0; k < 8; ++k)
+      {
+        const size_t x = 2 * (size_t)cijk[3 * (size_t)c] + (k & 1), y = 2 * (size_t)cijk[3 * (size_t)c + 1] + ((k >> 1) & 1),
+                     z = 2 * (size_t)cijk[3 * (size_t)c + 2] + (k >> 2);
+        children[8 * (size_t)c + k] = at[x + fine_cells[0] * (y + fine_cells[1] * z)];
+      }
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_create(mgx_context_t ctx, const mgx_dg_transfer_desc *desc, mgx_dg_transfer_t *out)
+{
+  if (!ctx || !desc || !out || !desc->children)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: null argument");
+  if (desc->degree < 1 || desc->degree > MGX_MAX_DEGREE)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_transfer_create: degree must be in 1.." + std::to_string(MGX_MAX_DEGREE));
+  if (desc->basis < MGX_DG_HERMITE || desc->basis > MGX_DG_GAUSS)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_transfer_create: basis must be MGX_DG_HERMITE, _GAUSS_LOBATTO or _GAUSS");
+  if (desc->number != MGX_F32 && desc->number != MGX_F64)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: number must be MGX_F32 or MGX_F64");
+  if (desc->n_coarse_cells == 0 || desc->n_coarse_cells >= (1u << 28))
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: n_coarse_cells must be in 1 .. 2^28 - 1");
+  // every fine cell is the child of exactly one coarse cell: what lets the kernels write without atomics, and what
+  // keeps every access inside the fine vector
+  const size_t      n_fine = 8 * (size_t)desc->n_coarse_cells;
+  std::vector<bool> seen(n_fine, false);
+  bool              identity = true;
+  for (size_t i = 0; i < n_fine; ++i)
+    {
+      const uint32_t f = desc->children[i];
+      if (f >= n_fine || seen[f])
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: children must name every fine cell 0 .. 8 n_coarse_cells - 1 "
+                                                 "exactly once (entry " + std::to_string(i) + " = " + std::to_string(f) + ")");
+      seen[f]  = true;
+      identity = identity && f == i;
+    }
+  Host1D      h;
+  std::string why;
+  const int   status = build_1d(desc->degree, desc->basis, h, why);
+  if (status != MGX_OK)
+    return dg_fail(status, "mgx_dg_transfer_create: " + why);
+  std::unique_ptr<mgx_dg_transfer_s, int (*)(mgx_dg_transfer_t)> T(new mgx_dg_transfer_s, mgx_dg_transfer_destroy);
+  T->ctx      = ctx;
+  T->degree   = desc->degree;
+  T->basis    = desc->basis;
+  T->number   = desc->number;
+  T->n_coarse = desc->n_coarse_cells;
+  T->identity = identity;
+  T->p1d_host = h.embed;
+  MGX_TRY(T->mem.upload(&T->children, desc->children, n_fine));
+  MGX_TRY(T->mem.upload_as(T->number, &T->p1d, h.embed.data(), h.embed.size()));
+  *out = T.release();
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_destroy(mgx_dg_transfer_t T)
+{
+  if (!T)
+    return MGX_OK;
+  if (T->ctx)
+    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(T->ctx));
+  delete T;
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_prolongate_and_add(mgx_dg_transfer_t T, void *fine_dst, const void *coarse_src)
+{
+  if (!T || !fine_dst || !coarse_src || fine_dst == coarse_src)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_prolongate_and_add: null or aliased vectors");
+  mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->degree, true, fine_dst, coarse_src, T->children,
+                          T->n_coarse, T->p1d, T->identity);
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_restrict_and_add(mgx_dg_transfer_t T, void *coarse_dst, const void *fine_src)
+{
+  if (!T || !coarse_dst || !fine_src || coarse_dst == fine_src)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_restrict_and_add: null or aliased vectors");
+  mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->degree, false, coarse_dst, fine_src, T->children,
+                          T->n_coarse, T->p1d, T->identity);
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_matrix(mgx_dg_transfer_t T, double *p1d)
+{
+  if (!T || !p1d)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_matrix: null argument");
+  std::copy(T->p1d_host.begin(), T->p1d_host.end(), p1d);
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc *desc, mgx_dg_plain_solver_t *out)
+{
+  if (!ctx || !desc || !out || !desc->matrix || !desc->matrix_dg_dp || (desc->n_levels > 1 && !desc->transfer))
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: null argument");
+  if (desc->n_levels < 1 || desc->n_levels > 32)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: n_levels must be in 1..32");
+  if (desc->degree_pre < 1)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: degree_pre must be at least 1");
+  const int         L   = desc->n_levels - 1;
+  mgx_dg_operator_t top = desc->matrix[L], Ad = desc->matrix_dg_dp;
+  for (int l = 0; l <= L; ++l)
+    {
+      mgx_dg_operator_t A = desc->matrix[l];
+      if (!A)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) + "] is null");
+      if (A->ctx != ctx)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: operators of another context");
+      if (A->n_ghost > 0)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
+                                                   "] has ghost cells; the plain DG multigrid runs on one rank");
+      if (A->degree != top->degree || A->basis != top->basis || A->number != top->number)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
+                                                   "] differs from the finest level in degree, basis or number type");
+      if (l == 0)
+        continue;
+      mgx_dg_transfer_t T = desc->transfer[l - 1];
+      if (!T)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) + "] is null");
+      if (T->degree != top->degree || T->basis != top->basis || T->number != top->number || T->ctx != ctx)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) +
+                                                   "] differs from the operators in degree, basis, number type or context");
+      if (T->n_coarse != desc->matrix[l - 1]->n_cells || 8 * (uint64_t)desc->matrix[l - 1]->n_cells != A->n_cells)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: level " + std::to_string(l) + " has " +
+                                                   std::to_string(A->n_cells) + " cells, level " + std::to_string(l - 1) + " " +
+                                                   std::to_string(desc->matrix[l - 1]->n_cells) + " and the transfer between them " +
+                                                   std::to_string(T->n_coarse) + " coarse cells (8 x coarse = fine required)");
+    }
+  if (Ad->number != MGX_F64 || Ad->n_cells != top->n_cells || Ad->degree != top->degree || Ad->basis != top->basis || Ad->n_ghost > 0 ||
+      Ad->ctx != ctx)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix_dg_dp must be the fp64 twin of the finest matrix");
+
+  std::unique_ptr<mgx_dg_plain_solver_s, int (*)(mgx_dg_plain_solver_t)> S(new mgx_dg_plain_solver_s, mgx_dg_plain_solver_destroy);
+  S->ctx    = ctx;
+  S->A_dp   = Ad;
+  S->number = top->number;
+  S->level.resize(L + 1);
+  hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
+  for (int l = 0; l <= L; ++l)
+    {
+      mgx_dg_plain_solver_s::Level &lv = S->level[l];
+      lv.A        = desc->matrix[l];
+      lv.transfer = l > 0 ? desc->transfer[l - 1] : nullptr;
+      lv.n        = (size_t)mgx_dg_operator_n_dofs(lv.A);
+      for (void **v : {&lv.defect, &lv.t, &lv.update, &lv.old})
+        {
+          MGX_TRY(S->mem.zeros(v, dg_nsz(S->number) * lv.n, s));
+        }
+    }
+  for (double **v : {&S->r, &S->z, &S->d, &S->h})
+    {
+      MGX_TRY(S->mem.zeros(v, S->level[L].n, s));
+    }
+  MGX_TRY(S->mem.alloc(&S->partials, 4 * (size_t)mgx::kDotBlocks));
+  MGX_TRY(S->mem.alloc(&S->sums, 4));
+  // smooth[level].initialize (:192-213)
+  for (int l = 0; l <= L; ++l)
+    {
+      mgx_dg_plain_solver_s::Level &lv  = S->level[l];
+      const uint32_t               *ids = desc->cell_global_id ? desc->cell_global_id[l] : nullptr;
+      if (l > 0)
+        MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect, 15, 20.,
+                                       l < L ? desc->degree_pre : std::max(1, desc->degree_pre - 1), lv.info));
+      else
+        MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect,
+                                       (int)std::min<size_t>(lv.n, 0x7FFFFFFF), 1e-5, -1, lv.info));
+      for (void *v : {lv.defect, lv.t, lv.update, lv.old})
+        MGX_HIP(hipMemsetAsync(v, 0, dg_nsz(S->number) * lv.n, s));
+    }
+  MGX_HIP(hipStreamSynchronize(s));
+  *out = S.release();
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_destroy(mgx_dg_plain_solver_t S)
+{
+  if (!S)
+    return MGX_OK;
+  if (S->ctx)
+    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
+  delete S;
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_smoother_info(mgx_dg_plain_solver_t S, int level, mgx_smoother_info *info)
+{
+  if (!S || !info || level < 0 || level >= (int)S->level.size())
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_smoother_info: null argument or no such level");
+  *info = S->level[level].info;
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_vmult(mgx_dg_plain_solver_t S, double *dst, const double *src)
+{
+  if (!S || !dst || !src)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_vmult: null argument");
+  mgx_dg_plain_solver_s::Level &top = S->level.back();
+  MGX_TRY(mgx_copy_cast(S->ctx, top.defect, S->number, src, MGX_F64, top.n)); // multigrid_solver_dg_plain.h:327
+  MGX_TRY(plain_v_cycle(S, (int)S->level.size() - 1));
+  return mgx_copy_cast(S->ctx, dst, MGX_F64, top.update, S->number, top.n);   // :331
+}
+
+int mgx_dg_plain_solver_solve_cg(mgx_dg_plain_solver_t S, double tolerance, const double *rhs, double *solution,
+                                 unsigned *iterations, double *reduction_rate)
+{
+  if (!S || !rhs || !solution)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_solve_cg: null argument");
+  // SolverCG with ReductionControl(100, 1e-16, tolerance), zero start, preconditioner = one V-cycle (:303-317)
+  mgx_context_t ctx = S->ctx;
+  const size_t  n   = S->level.back().n;
+  hipStream_t   s   = (hipStream_t)mgx_context_stream(ctx);
+  double       *r = S->r, *z = S->z, *d = S->d, *h = S->h;
+  MGX_HIP(hipMemsetAsync(solution, 0, 8 * n, s));
+  MGX_TRY(mgx_copy_cast(ctx, r, MGX_F64, rhs, MGX_F64, n));
+  double res0 = 0, res = 0, rz = 0, rz_old = 0;
+  MGX_TRY(dg_norm(ctx, n, MGX_F64, r, &res0));
+  res         = res0;
+  unsigned it = 0;
+  while (res > std::max(1e-16, tolerance * res0) && it < 100)
+    {
+      ++it;
+      MGX_TRY(mgx_dg_plain_solver_vmult(S, z, r));
+      rz_old = rz;
+      MGX_TRY(dg_dot(ctx, n, MGX_F64, r, z, &rz));
+      if (it > 1)
+        MGX_TRY(mgx_sadd(ctx, MGX_F64, d, rz / rz_old, 1.0, z, n));
+      else
+        MGX_TRY(mgx_copy_cast(ctx, d, MGX_F64, z, MGX_F64, n));
+      MGX_TRY(mgx_dg_vmult(S->A_dp, h, d));
+      double dh = 0;
+      MGX_TRY(dg_dot(ctx, n, MGX_F64, d, h, &dh));
+      const double alpha = rz / dh;
+      MGX_TRY(mgx_sadd(ctx, MGX_F64, solution, 1.0, alpha, d, n));
+      MGX_TRY(mgx_sadd(ctx, MGX_F64, r, 1.0, -alpha, h, n));
+      MGX_TRY(dg_norm(ctx, n, MGX_F64, r, &res));
+    }
+  if (iterations)
+    *iterations = it;
+  if (reduction_rate)
+    *reduction_rate = it ? std::pow(res / res0, 1.0 / it) : 1.0;
+  return res > std::max(1e-16, tolerance * res0) ? dg_fail(MGX_ERR_NOT_CONVERGED, "mgx_dg_plain_solver_solve_cg: 100 iterations")
+                                                 : MGX_OK;
+}
+
+int mgx_dg_plain_solver_vmult_with_residual_update(mgx_dg_plain_solver_t S, double *residual, double *update, double factor,
+                                                   double sums[2])
+{
+  if (!S || !residual || !update || !sums || residual == update)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_vmult_with_residual_update: null or aliased argument");
+  hipStream_t                   s   = (hipStream_t)mgx_context_stream(S->ctx);
+  mgx_dg_plain_solver_s::Level &top = S->level.back();
+  mgx::launch_residual_pre(s, S->number, top.defect, residual, update, factor, top.n); // :353-358
+  MGX_TRY(plain_v_cycle(S, (int)S->level.size() - 1));                                 // :362
+  // :365-413 (no constrained rows in DG: every entry takes the V-cycle's value); block sums added in a fixed order
+  const uint32_t used = mgx::launch_residual_post(s, S->number, top.update, residual, update, factor, top.n, top.n, S->partials);
+  mgx::launch_reduce4(s, S->partials, used, nullptr, S->sums);
+  MGX_HIP(hipGetLastError());
+  double h[4];
+  MGX_HIP(hipMemcpyAsync(h, S->sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
+  sums[0] = h[0];
+  sums[1] = h[1];
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_enable_timings(mgx_dg_plain_solver_t S, int on)
+{
+  if (!S)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_enable_timings: null solver");
+  S->timed = on != 0;
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_get_timings(mgx_dg_plain_solver_t S, double *times)
+{
+  if (!S || !times)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_get_timings: null argument");
+  for (size_t l = 0; l < S->level.size(); ++l)
+    for (int j = 0; j < 6; ++j)
+      {
+        times[6 * l + j]       = S->level[l].times[j];
+        S->level[l].times[j] = 0.;
+      }
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_do_matvec(mgx_dg_plain_solver_t S)
+{
+  if (!S)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_do_matvec: null solver");
+  return mgx_dg_vmult(S->A_dp, S->h, S->d); // matrix_dg_dp.vmult(residual, solution), :435
+}
+
+int mgx_dg_plain_solver_do_matvec_smoother(mgx_dg_plain_solver_t S)
+{
+  if (!S)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_do_matvec_smoother: null solver");
+  mgx_dg_plain_solver_s::Level &top = S->level.back();
+  return mgx_dg_vmult(top.A, top.t, top.defect); // matrix[maxlevel].vmult, :444
 }
 
 } // extern "C"

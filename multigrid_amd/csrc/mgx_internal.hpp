@@ -235,6 +235,9 @@ namespace mgx
   int  dot_owned_prefix(struct ::mgx_context_s *ctx, int number, const void *x, const void *y, size_t n, double *out);
   bool context_has_comm(struct ::mgx_context_s *ctx);
   const Tunables &context_tunables(struct ::mgx_context_s *ctx);
+  // smallest and largest eigenvalue of the symmetric tridiagonal matrix (diagonal d[n], off-diagonal e[n], e[n-1]
+  // unused), by bisection -- the Lanczos matrix of an eigenvalue estimate
+  void tridiag_extreme_eigenvalues(int n, const double *d, const double *e, double &lo, double &hi);
 
   // records the message mgx_last_error() returns on the calling thread; returns `code` (used by the
   // translation units that implement parts of the C ABI outside mgx_api.cpp)
@@ -523,6 +526,11 @@ namespace mgx
   // plain read-modify-writes instead of one with atomics
   void launch_dg_cg_transfer(hipStream_t s, int number, int p, bool to_dg, void *dst, const void *src,
                              const uint32_t *idx27, uint32_t n_cells, const void *P1, bool eight_colours = false);
+  // DG <-> DG transfer between a level and its refinement (mgx_dg_transfer.hip): prolong: fine += P coarse, else
+  // coarse += P^T fine; children [n_coarse][8] names every fine cell exactly once (the caller has checked it);
+  // p1d [2][(p+1)^2] in the number type; identity: children[c][k] == 8 c + k, the table is not read
+  void launch_dg_transfer(hipStream_t s, int number, int p, bool prolong, void *dst, const void *src, const uint32_t *children,
+                          uint32_t n_coarse, const void *p1d, bool identity);
   void launch_zero_head_copy_tail(hipStream_t s, int number, void *dst, const void *src, uint32_t n_head, uint32_t n);
   void launch_scatter_map(hipStream_t s, int number, void *dst, const void *src, const uint32_t *map,
                           const uint8_t *mask, uint32_t n);

@@ -1,0 +1,115 @@
+"""Harness of the plain DG multigrid, mirroring poisson_dg_plain/program.cc in 3D: FE_DGQHermite(p) on the cube
+[-0.9, 1]^3 (one cell refined n_refine times, as hyper_cube + refine_global gives), rhs 3 (3 pi)^2 prod sin(3 pi x_d),
+CG preconditioned with one V-cycle of MultigridSolverDGPlain -- the DG-SIP operator on every level, DG-to-DG level
+transfers, level 0 (the single cell) solved by its Chebyshev iteration; fp32 V-cycle inside the fp64 outer iteration.
+The same problem, printed lines and table row as tools/poisson_dg.py, whose solver it is the A/B partner of.
+
+    python tools/poisson_dg_plain.py [degree=3] [n_refine=5] [n_pre_smooth=3] [tolerance=1e-9] [--vcycle f32|f64]
+                                     [--basis 0|1|2] [--solution reference|vanishing] [--levels]
+
+One line per level gives the smoother's degree, lambda_max and the CG iterations of its eigenvalue estimate.
+--levels: one more solve with the solver's per-level timers on, and the table of the reference's print_wall_times
+(multigrid_solver_dg_plain.h:264-287).  The timers synchronise the stream around every part: for diagnosis, the
+solve they time is slower than the solves reported above it.
+
+--solution as in tools/poisson_dg.py: the benchmark's own solution does not vanish on the boundary, `vanishing` does
+and shows the discretisation error (tests/test_gpu_dg_plain.py)."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import multigrid_amd as mg  # noqa: E402
+
+WAVE = 3.0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("degree", nargs="?", type=int, default=3)
+    ap.add_argument("n_refine", nargs="?", type=int, default=5)
+    ap.add_argument("n_pre_smooth", nargs="?", type=int, default=3)
+    ap.add_argument("tolerance", nargs="?", type=float, default=1e-9)
+    ap.add_argument("--vcycle", choices=["f32", "f64"], default="f32")
+    ap.add_argument("--basis", type=int, default=0)
+    ap.add_argument("--solution", choices=["reference", "vanishing"], default="reference")
+    ap.add_argument("--levels", action="store_true", help="per-level time table of one more (synchronised) solve")
+    a = ap.parse_args()
+    vnum = mg.F32 if a.vcycle == "f32" else mg.F64
+    t0 = time.time()
+    ctx = mg.Context(0)
+    n_levels = a.n_refine + 1
+    solver = mg.DGPlainMultigridSolver(ctx, a.degree, a.basis, (1, 1, 1), np.eye(3) * 1.9, n_levels, a.n_pre_smooth, vnum)
+    n = solver.m()
+    nc = n // (a.degree + 1) ** 3
+    print("Number of degrees of freedom: %d (%d cells, FE_DGQHermite(%d) on every one of %d levels, V-cycle in %s)"
+          % (n, nc, a.degree, n_levels, a.vcycle))
+    for l in range(n_levels):
+        i = solver.smoother_info(l)
+        print("level %2d  cells %9d  smoother degree %3d  lambda_max %.6f  cg_its %d"
+              % (l, int(np.prod(solver.cells[l])), i["degree"], i["lambda_max"], i["cg_its"]))
+    S, xq, wq = solver.matrix_dg_dp.basis_1d()
+    h = 1.9 / 2 ** a.n_refine
+    S3 = np.kron(S, np.kron(S, S))
+    w3 = np.kron(wq, np.kron(wq, wq)) * h ** 3
+    ref = np.stack(np.meshgrid(xq, xq, xq, indexing="ij"), axis=-1)[..., ::-1].reshape(-1, 3)  # (k, j, i) order
+    x = -0.9 + h * (solver.cell_ijk[-1].astype(float)[:, None, :] + ref[None, :, :])
+    if a.solution == "reference":
+        u = np.prod(np.sin(np.pi * WAVE * x), axis=-1)
+        f = 3 * (np.pi * WAVE) ** 2 * u
+    else:
+        k = np.pi * WAVE / 1.9
+        u = np.prod(np.sin(k * (x + 0.9)), axis=-1)
+        f = 3 * k ** 2 * u
+    rhs = (f * w3) @ S3                                      # multigrid_solver_dg_plain.h:163-185
+    print("Time setup                    %.3f s   rhs_norm = %.6e" % (time.time() - t0, np.sqrt(float(np.sum(rhs ** 2)))))
+    b, sol = solver.initialize_dof_vector(rhs.ravel()), solver.initialize_dof_vector()
+    time_cg = 1e10
+    for _ in range(4):
+        ctx.sync()
+        t = time.perf_counter()
+        its, red = solver.solve_cg(b, sol, a.tolerance)
+        ctx.sync()
+        dt = time.perf_counter() - t
+        time_cg = min(time_cg, dt)
+        print("Time solve CG                 %.6f s   (%d iterations, reduction %.4e)" % (dt, its, red))
+    uh = sol.download()[:n].reshape(nc, -1) @ S3.T
+    l2 = np.sqrt(float(np.sum(w3 * (uh - u) ** 2)) / (nc * h ** 3))
+    if a.levels:
+        solver.enable_timings(True)
+        solver.solve_cg(b, sol, a.tolerance)
+        t = solver.wall_times()
+        solver.enable_timings(False)
+        print("Coarse solver %d times: %.4g tot prec %.4g" % (int(t[0, 1]), t[0, 0], t[0, 0] + t[1:, [0, 1, 2, 5]].sum()))
+        print("level  smoother    mg_mv     mg_vec    restrict  prolongate  inhomBC")
+        for l in range(1, n_levels):
+            print("L%-2d    %-12.4g%-10.4g%-10.4g%-10.4g%-12.4g%-10.4g" % (l, t[l, 5], t[l, 0], t[l, 4], t[l, 1], t[l, 2], t[l, 3]))
+    best = {}
+    for name, A in (("dp", solver.matrix_dg_dp), ("sp", solver.matrix[-1])):
+        v, w = A.initialize_dof_vector(np.ones(n)), A.initialize_dof_vector()
+        n_mv = 200 if n < 10000000 else 50
+        best[name] = 1e10
+        for _ in range(5):
+            ctx.sync()
+            t = time.perf_counter()
+            for _ in range(n_mv):
+                A.vmult(w, v)
+            ctx.sync()
+            dt = (time.perf_counter() - t) / n_mv
+            best[name] = min(best[name], dt)
+            print("matvec time %s %.6e DoFs/s: %.5e" % (name, dt, n / dt))
+        v.free(); w.free()
+    print("Best timings for ndof = %d   mv %.6e    mv smooth %.6e   cg-mg %.6e" % (n, best["dp"], best["sp"], time_cg))
+    print("L2 error with ndof = %d  %.6e" % (n, l2))
+    print("cells dofs mv_outer mv_inner cg_L2error cg_time cg_its cg_reduction")
+    print("%d %d %.4e %.4e %.4e %.4e %d %.4e  | %.3e DoFs/s solved per second of CG"
+          % (nc, n, best["dp"], best["sp"], l2, time_cg, its, red, n / time_cg))
+    solver.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
