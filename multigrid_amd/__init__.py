@@ -182,7 +182,7 @@ class Communicator:
     def _device_tensor(self, ptr, nbytes):
         """torch view of `nbytes` of device memory at `ptr`: the tensor the alloc callback handed out, or -- for
         buffers the library owns (the DG ghost exchange sends from hipMalloc'd pack buffers and receives straight
-        into the ghost part of the vector it was given, mgx_dg.hip) -- a zero-copy wrapper of the raw pointer"""
+        into the ghost part of the vector it was given, mgx_dg_api.cpp) -- a zero-copy wrapper of the raw pointer"""
         import torch
         t = self._tensors.get(ptr)
         if t is not None:

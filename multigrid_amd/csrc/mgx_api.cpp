@@ -816,6 +816,23 @@ void mgx::tridiag_extreme_eigenvalues(int n, const double *d, const double *e, d
   tridiag_extreme(n, d, e, lo, hi);
 }
 
+double mgx::chebyshev_interval(double smoothing_range, int degree, mgx_smoother_info &info)
+{
+  const double a =
+    smoothing_range > 1. ? info.lambda_max / smoothing_range : std::min(0.9 * info.lambda_max, info.lambda_min);
+  if (degree < 0) // numbers::invalid_unsigned_int: Varga's estimate for eps = smoothing_range
+    {
+      const double actual_range = info.lambda_max / a;
+      const double sigma        = (1. - std::sqrt(1. / actual_range)) / (1. + std::sqrt(1. / actual_range));
+      const double eps          = smoothing_range;
+      degree = 1 + (int)(std::log(1. / eps + std::sqrt(1. / eps / eps - 1.)) / std::log(1. / sigma));
+    }
+  info.degree = degree;
+  info.delta  = (info.lambda_max - a) * 0.5;
+  info.theta  = (info.lambda_max + a) * 0.5;
+  return a;
+}
+
 // Point-to-point exchange of packed device buffers with the context's transport (native RCCL group
 // on the stream, or the blocking callback), for the parts of the ABI implemented in other
 // translation units (the DG ghost-cell update); allreduce of a few host doubles likewise
@@ -2336,19 +2353,8 @@ int mgx_smoother_create(mgx_operator_t op, double smoothing_range, int degree, i
       info.lambda_min = lo;
       info.lambda_max = 1.2 * hi; // safety factor
     }
-  const double a =
-    smoothing_range > 1. ? info.lambda_max / smoothing_range : std::min(0.9 * info.lambda_max, info.lambda_min);
-  if (degree < 0) // numbers::invalid_unsigned_int: Varga's estimate for eps = smoothing_range
-    {
-      const double actual_range = info.lambda_max / a;
-      const double sigma        = (1. - std::sqrt(1. / actual_range)) / (1. + std::sqrt(1. / actual_range));
-      const double eps          = smoothing_range;
-      degree = 1 + (int)(std::log(1. / eps + std::sqrt(1. / eps / eps - 1.)) / std::log(1. / sigma));
-    }
-  MGX_TRACE("smoother_create: its=%d lambda=[%g,%g] degree=%d", it, info.lambda_min, info.lambda_max, degree);
-  info.degree = degree;
-  info.delta  = (info.lambda_max - a) * 0.5;
-  info.theta  = (info.lambda_max + a) * 0.5;
+  const double a = chebyshev_interval(smoothing_range, degree, info);
+  MGX_TRACE("smoother_create: its=%d lambda=[%g,%g] degree=%d", it, info.lambda_min, info.lambda_max, info.degree);
   sm->range_a = a;
   *out        = sm.release();
   return MGX_OK;

@@ -1,4 +1,4 @@
-// mgx_device_memory.hpp -- the one owner of device memory on the host side (mgx_api.cpp, host half of mgx_dg.hip).
+// mgx_device_memory.hpp -- the one owner of device memory on the host side (mgx_api.cpp, mgx_dg_api.cpp).
 // Host only: nothing here is used from device code.
 #pragma once
 

@@ -1,0 +1,1260 @@
+// mgx_dg_api.cpp -- host side of the DG objects of include/mgx_dg.h: the operator (set-up, ghost exchange, the
+// applications of the cell kernel), MultigridSolverDG on top of an FE_Q hierarchy, the DG-to-DG level transfer
+// object and MultigridSolverDGPlain.  No kernel lives here: the cell kernel and its launch are mgx_dg_kernels.hip
+// (DG section of mgx_internal.hpp), the level transfer kernels mgx_dg_transfer.hip, the fp64 numerics of the set-up
+// mgx_dg_host.cpp.
+#include "mgx_device_memory.hpp"
+#include "mgx_dg_host.hpp"
+#include "mgx_internal.hpp"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <memory>
+#include <string>
+#include <vector>
+
+using namespace mgx::dg;
+
+struct mgx_dg_operator_s
+{
+  mgx_context_t    ctx = nullptr;
+  mgx::DeviceArena mem{"mgx_dg_operator"};
+  int           degree = 0, basis = 0, number = MGX_F32;
+  uint32_t      n_cells = 0;
+  int32_t      *neigh   = nullptr; // device
+  void         *consts  = nullptr; // device DGConst<T>
+  void         *inv_diag = nullptr; // device [64][(p+1)^3]
+  Host1D        h;
+  Geometry      g;
+  // decomposed mesh: ghost cells behind the owned ones, filled from their owners before every
+  // application (mgx_dg_update_ghost_values)
+  uint32_t                n_ghost = 0;
+  int                     plan_id = 0;
+  std::vector<int>        nb_rank;
+  std::vector<uint32_t>   nb_count, nb_recv_first, nb_entries;
+  std::vector<uint32_t *> nb_cells_dev;
+  std::vector<void *>     nb_send;
+  // cells without / with a ghost neighbour: the former run while the ghost exchange is in flight
+  // (the reference completes its exchange, laplace_operator_dg.h:986-1057, before the cell loop)
+  uint32_t *interior_cells = nullptr, *boundary_cells = nullptr; // device
+  uint32_t  n_interior = 0, n_boundary = 0;
+  bool      interior_is_prefix = false; // the interior cells are cells 0 ... n_interior - 1
+  // entries per ghost: a whole cell, or for the Hermite-like basis two values per face point
+  // (data_per_face of laplace_operator_dg.h:565)
+  uint32_t               ghost_stride = 0;
+  std::vector<uint8_t *> nb_faces_dev; // Hermite-like basis: face of every sent cell towards the neighbour rank
+  // block sums of the merged CG iteration (action 2) and their total, allocated at the first use
+  double  *cg_partials = nullptr, *cg_sums = nullptr;
+  uint32_t cg_capacity = 0;
+};
+
+// MultigridSolverDG (common/multigrid_solver_dg.h:55-747): the DG level on top of an FE_Q hierarchy
+struct mgx_dg_solver_s
+{
+  mgx_context_t     ctx = nullptr;
+  mgx::DeviceArena  mem{"mgx_dg_solver"};
+  mgx_dg_operator_t A = nullptr, A_dp = nullptr;
+  mgx_solver_t      cfe = nullptr;
+  int               degree = 0, number = MGX_F32;
+  size_t            n = 0;      // owned DoFs
+  size_t            n_vec = 0;  // entries of a vector: owned cells, then ghost cells
+  mgx_operator_t    fe = nullptr; // finest FE_Q operator (interface sum of the restricted defect)
+  bool              decomposed = false;
+  mgx_smoother_info info{};
+  void             *defect = nullptr, *t = nullptr, *update = nullptr, *old = nullptr; // V-cycle number type
+  void             *P1 = nullptr;                                                      // device, V-cycle number type
+  const uint32_t   *idx27 = nullptr;
+  uint32_t          n_cells = 0, n_cg = 0;
+  bool              cg_eight_colours = false; // cells c, c + 8, ... of the FE_Q level share no DoF
+  void             *cg_defect = nullptr, *cg_update = nullptr; // the FE_Q solver's finest-level vectors
+  double           *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr; // PCG, fp64
+};
+
+// MGTransferMatrixFree between two DG levels (mgx_dg_transfer.hip)
+struct mgx_dg_transfer_s
+{
+  mgx_context_t       ctx = nullptr;
+  mgx::DeviceArena    mem{"mgx_dg_transfer"};
+  int                 degree = 0, basis = 0, number = MGX_F32;
+  uint32_t            n_coarse = 0;
+  uint32_t           *children = nullptr; // device [n_coarse][8]
+  bool                identity = false;   // children[c][k] == 8 c + k (checked at creation): the table is not read
+  void               *p1d      = nullptr; // device [2][(p+1)^2], number type
+  std::vector<double> p1d_host;
+};
+
+// MultigridSolverDGPlain (common/multigrid_solver_dg_plain.h:55-595)
+struct mgx_dg_plain_solver_s
+{
+  struct Level
+  {
+    mgx_dg_operator_t A = nullptr;
+    mgx_dg_transfer_t transfer = nullptr; // from the level below (null on level 0)
+    size_t            n = 0;
+    mgx_smoother_info info{};
+    void             *defect = nullptr, *t = nullptr, *update = nullptr, *old = nullptr; // V-cycle number type
+    double            times[6] = {0, 0, 0, 0, 0, 0};                                     // timings[level] of the reference
+  };
+  mgx_context_t      ctx = nullptr;
+  mgx::DeviceArena   mem{"mgx_dg_plain_solver"};
+  std::vector<Level> level;
+  mgx_dg_operator_t  A_dp = nullptr;
+  int                number = MGX_F32;
+  double            *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr; // PCG, fp64
+  double            *partials = nullptr, *sums = nullptr;                   // vmult_with_residual_update
+  bool               timed = false;
+};
+
+namespace
+{
+  int dg_fail(int code, const std::string &msg) { return mgx::report_error(code, msg.c_str()); }
+
+  size_t dg_nsz(int number) { return number == MGX_F64 ? 8 : 4; }
+
+  // pack kernels on the context's stream; `overlap`: the exchange itself on the side stream, begun
+  // behind the pack kernels -- the caller enqueues independent work and then calls ghosts_finish
+  int ghosts_pack(mgx_dg_operator_t op, const void *vec)
+  {
+    hipStream_t    s   = (hipStream_t)mgx_context_stream(op->ctx);
+    const uint32_t n3  = (uint32_t)(op->degree + 1) * (op->degree + 1) * (op->degree + 1);
+    const int      nnb = (int)op->nb_rank.size();
+    for (int k = 0; k < nnb; ++k)
+      {
+        if (op->basis == MGX_DG_HERMITE)
+          launch_pack_faces(s, op->number, op->nb_send[k], vec, op->nb_cells_dev[k], op->nb_faces_dev[k], op->nb_count[k],
+                            op->degree + 1, op->h.hderiv);
+        else
+          launch_pack_cells(s, op->number, op->nb_send[k], vec, op->nb_cells_dev[k], op->nb_count[k], n3);
+      }
+    MGX_HIP(hipGetLastError());
+    return MGX_OK;
+  }
+
+  int ghosts_exchange(mgx_dg_operator_t op, void *vec, hipStream_t stream)
+  {
+    const uint32_t n3  = (uint32_t)(op->degree + 1) * (op->degree + 1) * (op->degree + 1);
+    const size_t   es  = dg_nsz(op->number);
+    const int      nnb = (int)op->nb_rank.size();
+    std::vector<void *> recv(nnb);
+    for (int k = 0; k < nnb; ++k)
+      recv[k] = (char *)vec + ((size_t)op->n_cells * n3 + (size_t)(op->nb_recv_first[k] - op->n_cells) * op->ghost_stride) *
+                                es; // straight into the ghosts
+    return mgx::exchange_buffers(op->ctx, op->plan_id, op->number, nnb, op->nb_rank.data(), op->nb_entries.data(),
+                                 op->nb_send.data(), recv.data(), stream);
+  }
+
+  int update_ghosts(mgx_dg_operator_t op, void *vec)
+  {
+    if (op->n_ghost == 0)
+      return MGX_OK;
+    MGX_TRY(ghosts_pack(op, vec));
+    return ghosts_exchange(op, vec, nullptr);
+  }
+
+  int launch_cells(mgx_dg_operator_t op, const DGLaunch &launch, hipStream_t stream = nullptr)
+  {
+    const CellOperands o{op->number, op->degree, op->basis, op->neigh, op->consts, op->inv_diag, op->n_cells, op->n_ghost > 0};
+    return launch_dg_cells(stream ? stream : (hipStream_t)mgx_context_stream(op->ctx), o, launch);
+  }
+
+  // One application over all cells of the operator (the launch names none).  with_ghosts: the action reads neighbour
+  // cells, so the ghost cells of src are refreshed first; the cells without a ghost neighbour run while that exchange
+  // is in flight on the context's side stream (with the blocking callback transport: while the host waits in it).
+  int run(mgx_dg_operator_t op, DGLaunch all, bool with_ghosts = false)
+  {
+    all.n_cells = op->n_cells;
+    if (!with_ghosts || op->n_ghost == 0)
+      return launch_cells(op, all);
+    void *ghosted = const_cast<void *>(all.src);
+    MGX_TRY(ghosts_pack(op, all.src));
+    hipStream_t side = (op->n_interior > 0 && !mgx::context_tunables(op->ctx).dg_no_overlap) ? mgx::side_stream_begin(op->ctx)
+                                                                                               : nullptr;
+    if (!side)
+      {
+        MGX_TRY(ghosts_exchange(op, ghosted, nullptr));
+        return launch_cells(op, all);
+      }
+    // main stream: interior cells; side stream: exchange, then the cells next to a ghost cell (they
+    // write other cells of dst than the interior launch and share its read-only operands)
+    // (interior cells first in the caller's order: two contiguous ranges, no index lists)
+    DGLaunch interior = all, boundary = all;
+    interior.cell_list = op->interior_is_prefix ? nullptr : op->interior_cells;
+    interior.n_cells   = op->n_interior;
+    boundary.cell_list  = op->interior_is_prefix ? nullptr : op->boundary_cells;
+    boundary.cell_first = op->interior_is_prefix ? op->n_interior : 0;
+    boundary.n_cells    = op->n_boundary;
+    if (all.partials) // the block sums of the second launch behind those of the first
+      boundary.partials += 4 * (size_t)cell_grid(op->number, op->degree, op->n_interior);
+    // whatever fails below, the main stream is ordered behind the side stream again before returning:
+    // nothing of this application may still be in flight when the caller reuses src / dst
+    int status = launch_cells(op, interior);
+    if (status == MGX_OK)
+      status = ghosts_exchange(op, ghosted, side);
+    if (status == MGX_OK)
+      status = launch_cells(op, boundary, side);
+    const int joined = mgx::side_stream_end(op->ctx);
+    return status != MGX_OK ? status : joined;
+  }
+
+  // ---- stages of mgx_dg_operator_create ----
+  int validate_dg_operator_desc(mgx_context_t ctx, const mgx_dg_operator_desc *desc, mgx_dg_operator_t *out)
+  {
+    MGX_REQUIRE(ctx && desc && out, "mgx_dg_operator_create: null argument");
+    if (desc->degree < 1 || desc->degree > MGX_MAX_DEGREE)
+      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: degree must be in 1.." + std::to_string(MGX_MAX_DEGREE));
+    if (desc->basis < MGX_DG_HERMITE || desc->basis > MGX_DG_GAUSS)
+      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: basis must be MGX_DG_HERMITE, _GAUSS_LOBATTO or _GAUSS");
+    if (desc->number != MGX_F32 && desc->number != MGX_F64)
+      return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: number must be MGX_F32 or MGX_F64");
+    MGX_REQUIRE(desc->n_cells != 0 && desc->neighbours, "mgx_dg_operator_create: empty mesh");
+    const uint64_t n3 = (uint64_t)(desc->degree + 1) * (desc->degree + 1) * (desc->degree + 1);
+    if ((uint64_t)desc->n_cells * n3 * dg_nsz(desc->number) >= (1ull << 40))
+      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: vector larger than 1 TiB");
+    const uint64_t n_all = (uint64_t)desc->n_cells + desc->n_ghost_cells;
+    if (n_all * n3 >= (1ull << 32))
+      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: more than 2^32 vector entries per rank");
+    for (uint64_t i = 0; i < (uint64_t)desc->n_cells * 6; ++i)
+      if (desc->neighbours[i] != MGX_DG_BOUNDARY && (desc->neighbours[i] < 0 || (uint64_t)desc->neighbours[i] >= n_all))
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: neighbour entry " + std::to_string(i) +
+                                                   " is neither a cell of the mesh, a ghost cell nor MGX_DG_BOUNDARY");
+    if (desc->n_ghost_cells > 0)
+      {
+        if (!desc->exchange || !mgx::context_has_comm(ctx))
+          return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: ghost cells need an exchange plan and a "
+                                                   "communicator on the context");
+        const mgx_dg_exchange_desc &e = *desc->exchange;
+        if (e.n_neighbors < 1 || !e.neighbor_rank || !e.count || !e.send_cells || !e.recv_first)
+          return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: incomplete exchange plan");
+        uint64_t                    covered = 0;
+        for (int k = 0; k < e.n_neighbors; ++k)
+          {
+            if (k > 0 && e.neighbor_rank[k] <= e.neighbor_rank[k - 1])
+              return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: neighbour ranks must be ascending");
+            if (e.recv_first[k] < desc->n_cells || (uint64_t)e.recv_first[k] + e.count[k] > n_all)
+              return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: ghost range outside the ghost cells");
+            if (e.count[k] > 0 && !e.send_cells[k])
+              return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: incomplete exchange plan");
+            for (uint32_t i = 0; i < e.count[k]; ++i)
+              if (e.send_cells[k][i] >= desc->n_cells)
+                return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: only owned cells can be sent");
+            covered += e.count[k];
+          }
+        if (covered != desc->n_ghost_cells)
+          return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: the exchange plan does not fill every ghost cell "
+                                                   "exactly once");
+      }
+    return MGX_OK;
+  }
+
+  // 1D data and geometry factors; the symmetries the cell kernel rests on are checked, not assumed
+  int build_basis_and_geometry(mgx_dg_operator_s &op, const mgx_dg_operator_desc *desc)
+  {
+    std::string why;
+    int         status = build_1d(desc->degree, desc->basis, op.h, why);
+    if (status == MGX_OK)
+      status = build_geometry(desc->jacobian, desc->degree, op.g, why);
+    if (status != MGX_OK)
+      return dg_fail(status, "mgx_dg_operator_create: " + why);
+    // the even-odd line products of the cell kernel (mul_eo) rest on the reversal symmetry of the 1D
+    // matrices: S[q][i] = S[n-1-q][n-1-i], D[q][r] = -D[n-1-q][n-1-r].  All three bases have it.
+    const int n = op.h.n;
+    double    dev = 0, scale = 0;
+    for (int q = 0; q < n; ++q)
+      for (int i = 0; i < n; ++i)
+        {
+          dev   = std::max(dev, std::fabs(op.h.S[q * n + i] - op.h.S[(n - 1 - q) * n + n - 1 - i]));
+          dev   = std::max(dev, std::fabs(op.h.D[q * n + i] + op.h.D[(n - 1 - q) * n + n - 1 - i]));
+          scale = std::max(scale, std::max(std::fabs(op.h.S[q * n + i]), std::fabs(op.h.D[q * n + i])));
+        }
+    if (dev > 1e-11 * scale)
+      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: the 1D basis is not symmetric under x -> 1 - x");
+    if (!op.h.e_parity)
+      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: the eigenvectors of the 1D problem have no definite parity "
+                                          "(degenerate eigenvalues)");
+    return MGX_OK;
+  }
+
+  // table[cat][(p+1)^3]: inverse of the transformed diagonal for every combination of Dirichlet faces (host)
+  int build_inverse_diagonal(const mgx_dg_operator_s &op, uint64_t n3, std::vector<double> &table)
+  {
+    std::vector<double> diag;
+    table.resize(64 * n3);
+    for (unsigned cat = 0; cat < 64; ++cat)
+      {
+        transformed_diagonal(op.h, op.g, cat, diag);
+        for (uint64_t i = 0; i < n3; ++i)
+          {
+            if (!(diag[i] > 0))
+              return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: transformed cell block is not positive");
+            table[cat * n3 + i] = 1.0 / diag[i];
+          }
+      }
+    return MGX_OK;
+  }
+
+  // neighbour ranks, their send lists and buffers, and (Hermite-like basis) the face every sent cell is sent for
+  int upload_exchange_plan(mgx_dg_operator_s &op, const mgx_dg_operator_desc *desc)
+  {
+    const size_t                nsz = dg_nsz(op.number);
+    const mgx_dg_exchange_desc &e = *desc->exchange;
+    op.plan_id                    = e.plan_id;
+    for (int k = 0; k < e.n_neighbors; ++k)
+      {
+        op.nb_rank.push_back(e.neighbor_rank[k]);
+        op.nb_count.push_back(e.count[k]);
+        op.nb_entries.push_back((uint32_t)((uint64_t)e.count[k] * op.ghost_stride));
+        op.nb_recv_first.push_back(e.recv_first[k]);
+        uint32_t *cells = nullptr;
+        void     *buf   = nullptr;
+        MGX_TRY(op.mem.upload(&cells, e.send_cells[k], e.count[k], 1));
+        op.nb_cells_dev.push_back(cells);
+        MGX_TRY(op.mem.alloc(&buf, nsz * ((size_t)e.count[k] * op.ghost_stride + 1)));
+        op.nb_send.push_back(buf);
+        if (op.basis == MGX_DG_HERMITE)
+          {
+            // the face of every sent cell that looks at this neighbour's cells
+            std::vector<uint8_t> face(e.count[k]);
+            for (uint32_t i = 0; i < e.count[k]; ++i)
+              {
+                int found = -1, n_found = 0;
+                for (int f = 0; f < 6; ++f)
+                  {
+                    const int32_t nbr = desc->neighbours[(size_t)e.send_cells[k][i] * 6 + f];
+                    if (nbr >= 0 && (uint32_t)nbr >= e.recv_first[k] && (uint32_t)nbr < e.recv_first[k] + e.count[k])
+                      {
+                        found = f;
+                        ++n_found;
+                      }
+                  }
+                if (n_found != 1)
+                  return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: a sent cell must touch the cells of the "
+                                                      "receiving rank through exactly one face");
+                face[i] = (uint8_t)found;
+              }
+            uint8_t *fd = nullptr;
+            MGX_TRY(op.mem.upload(&fd, face, 1));
+            op.nb_faces_dev.push_back(fd);
+          }
+      }
+    return MGX_OK;
+  }
+
+  // cells without / with a ghost neighbour
+  int split_interior_and_boundary(mgx_dg_operator_s &op, const mgx_dg_operator_desc *desc)
+  {
+    std::vector<uint32_t> interior, boundary;
+    for (uint32_t c = 0; c < desc->n_cells; ++c)
+      {
+        bool ghost = false;
+        for (int f = 0; f < 6; ++f)
+          ghost = ghost || (desc->neighbours[(size_t)c * 6 + f] >= 0 && (uint32_t)desc->neighbours[(size_t)c * 6 + f] >= desc->n_cells);
+        (ghost ? boundary : interior).push_back(c);
+      }
+    op.n_interior = (uint32_t)interior.size();
+    op.n_boundary = (uint32_t)boundary.size();
+    op.interior_is_prefix = interior.empty() || interior.back() + 1 == interior.size();
+    MGX_TRY(op.mem.upload(&op.interior_cells, interior, 1));
+    MGX_TRY(op.mem.upload(&op.boundary_cells, boundary, 1));
+    return MGX_OK;
+  }
+
+  int upload_constants(mgx_dg_operator_s &op)
+  {
+    const std::vector<char> block = const_block(op.number, op.h, op.g);
+    return op.mem.upload_bytes(&op.consts, block.data(), block.size());
+  }
+} // namespace
+
+extern "C" {
+
+int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, mgx_dg_operator_t *out)
+{
+  MGX_TRY(validate_dg_operator_desc(ctx, desc, out));
+  const uint64_t n3 = (uint64_t)(desc->degree + 1) * (desc->degree + 1) * (desc->degree + 1);
+  // failures below return through the destroy function, which frees what the operator's arena holds by then
+  std::unique_ptr<mgx_dg_operator_s, int (*)(mgx_dg_operator_t)> op(new mgx_dg_operator_s, mgx_dg_operator_destroy);
+  op->ctx     = ctx;
+  op->degree  = desc->degree;
+  op->basis   = desc->basis;
+  op->number  = desc->number;
+  op->n_cells = desc->n_cells;
+  op->n_ghost = desc->n_ghost_cells;
+  op->ghost_stride = desc->basis == MGX_DG_HERMITE ? 2u * (desc->degree + 1) * (desc->degree + 1) : (uint32_t)n3;
+  MGX_TRY(build_basis_and_geometry(*op, desc));
+  std::vector<double> table;
+  MGX_TRY(build_inverse_diagonal(*op, n3, table));
+  MGX_TRY(op->mem.upload(&op->neigh, desc->neighbours, 6 * (size_t)desc->n_cells));
+  if (op->n_ghost > 0)
+    {
+      MGX_TRY(upload_exchange_plan(*op, desc));
+      MGX_TRY(split_interior_and_boundary(*op, desc));
+    }
+  MGX_TRY(op->mem.upload_as(desc->number, &op->inv_diag, table.data(), table.size()));
+  MGX_TRY(upload_constants(*op));
+  *out = op.release();
+  return MGX_OK;
+}
+
+int mgx_dg_operator_destroy(mgx_dg_operator_t op)
+{
+  if (!op)
+    return MGX_OK;
+  (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(op->ctx));
+  delete op;
+  return MGX_OK;
+}
+
+uint64_t mgx_dg_operator_vector_size(mgx_dg_operator_t op)
+{
+  return op ? mgx_dg_operator_n_dofs(op) + (uint64_t)op->n_ghost * op->ghost_stride : 0;
+}
+
+int mgx_dg_update_ghost_values(mgx_dg_operator_t op, void *vec)
+{
+  MGX_REQUIRE(op && vec, "mgx_dg_update_ghost_values: null argument");
+  return update_ghosts(op, vec);
+}
+
+uint64_t mgx_dg_operator_n_dofs(mgx_dg_operator_t op)
+{
+  return op ? (uint64_t)op->n_cells * (op->degree + 1) * (op->degree + 1) * (op->degree + 1) : 0;
+}
+
+int mgx_dg_vmult(mgx_dg_operator_t op, void *dst, const void *src)
+{
+  MGX_REQUIRE(op && dst && src && dst != src, "mgx_dg_vmult: null or aliased vectors");
+  return run(op, DGLaunch(kVmult, dst, nullptr, src), true);
+}
+
+int mgx_dg_vmult_residual(mgx_dg_operator_t op, void *dst, const void *rhs, const void *src)
+{
+  MGX_REQUIRE(op && dst && src && rhs && dst != src, "mgx_dg_vmult_residual: null or aliased vectors");
+  return run(op, DGLaunch(kResidual, dst, rhs, src), true);
+}
+
+int mgx_dg_jacobi_vmult(mgx_dg_operator_t op, void *dst, const void *src)
+{
+  MGX_REQUIRE(op && dst && src, "mgx_dg_jacobi_vmult: null vector");
+  DGLaunch l(kJacobi, dst, nullptr, src);
+  l.f2 = 1.0;
+  return run(op, l);
+}
+
+int mgx_dg_vmult_with_chebyshev_update(mgx_dg_operator_t op, const void *rhs, unsigned iteration_index, double factor1,
+                                       double factor2, void *solution, void *solution_old)
+{
+  MGX_REQUIRE(op && rhs && solution, "mgx_dg_vmult_with_chebyshev_update: null vector");
+  if (iteration_index == 0)
+    {
+      DGLaunch l(kJacobi, solution, nullptr, rhs);
+      l.f2 = factor2;
+      return run(op, l);
+    }
+  MGX_REQUIRE(solution_old && solution_old != solution, "mgx_dg_vmult_with_chebyshev_update: solution_old is null or aliases solution");
+  DGLaunch l(kChebyshev, solution_old, rhs, solution);
+  l.f1              = factor1;
+  l.f2              = factor2;
+  l.iteration_index = (int)iteration_index;
+  return run(op, l, true);
+}
+
+int mgx_dg_vmult_with_cg_update(mgx_dg_operator_t op, double alpha, double beta, const void *r, void *q, void *p, void *x,
+                                double sums[4])
+{
+  MGX_REQUIRE(op && r && q && p && x && sums && q != p, "mgx_dg_vmult_with_cg_update: null or aliased vectors");
+  hipStream_t    s      = (hipStream_t)mgx_context_stream(op->ctx);
+  const bool     split  = op->n_ghost > 0 && op->n_interior > 0;
+  const uint32_t blocks = split ? cell_grid(op->number, op->degree, op->n_interior) + cell_grid(op->number, op->degree, op->n_boundary)
+                                : cell_grid(op->number, op->degree, op->n_cells);
+  if (blocks > op->cg_capacity)
+    {
+      op->mem.release(op->cg_partials);
+      op->cg_partials = nullptr;
+      op->cg_capacity = 0;
+      MGX_TRY(op->mem.alloc(&op->cg_partials, 4 * (size_t)blocks));
+      op->cg_capacity = blocks;
+    }
+  if (!op->cg_sums)
+    MGX_TRY(op->mem.alloc(&op->cg_sums, 4));
+  // laplace_operator_dg.h:871-902: x += alpha p ; p = beta p + q (alpha == 0: p = q) on the owned entries
+  mgx::launch_cg_pre(s, op->number, x, p, q, alpha, beta, (size_t)mgx_dg_operator_n_dofs(op));
+  // :903 q = A p with the sums of the next iteration
+  if (op->n_cells == 0)
+    MGX_HIP(hipMemsetAsync(op->cg_sums, 0, sizeof(double) * 4, s));
+  else
+    {
+      // without the overlap of the ghost exchange the cells run in one launch: its blocks are not the split's
+      MGX_HIP(hipMemsetAsync(op->cg_partials, 0, sizeof(double) * 4 * (size_t)blocks, s));
+      DGLaunch l(kCgSums, q, r, p);
+      l.partials = op->cg_partials;
+      MGX_TRY(run(op, l, true));
+      mgx::launch_reduce4(s, op->cg_partials, blocks, nullptr, op->cg_sums);
+    }
+  MGX_HIP(hipMemcpyAsync(sums, op->cg_sums, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
+  return mgx::allreduce_sum(op->ctx, sums, 4); // :904-906
+}
+
+int mgx_dg_operator_info(mgx_dg_operator_t op, double *hderiv, double penalty[3], double eigenvalues_1d[MGX_MAX_DEGREE + 1])
+{
+  MGX_REQUIRE(op, "mgx_dg_operator_info: null operator");
+  if (hderiv)
+    *hderiv = op->h.hderiv;
+  if (penalty)
+    for (int d = 0; d < 3; ++d)
+      penalty[d] = op->g.sigma[d];
+  if (eigenvalues_1d)
+    {
+      std::vector<double> sorted(op->h.lambda.begin(), op->h.lambda.begin() + op->h.n);
+      std::sort(sorted.begin(), sorted.end()); // (held parity by parity internally)
+      for (int i = 0; i <= MGX_MAX_DEGREE; ++i)
+        eigenvalues_1d[i] = i < op->h.n ? sorted[i] : 0.0;
+    }
+  return MGX_OK;
+}
+
+int mgx_dg_operator_basis(mgx_dg_operator_t op, double *shape_values, double *quadrature_points,
+                          double *quadrature_weights)
+{
+  MGX_REQUIRE(op, "mgx_dg_operator_basis: null operator");
+  const int n = op->h.n;
+  if (shape_values)
+    std::copy(op->h.S.begin(), op->h.S.begin() + n * n, shape_values);
+  if (quadrature_points)
+    std::copy(op->h.xq.begin(), op->h.xq.begin() + n, quadrature_points);
+  if (quadrature_weights)
+    std::copy(op->h.wq.begin(), op->h.wq.begin() + n, quadrature_weights);
+  return MGX_OK;
+}
+
+} // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * MultigridSolverDG
+ * --------------------------------------------------------------------------------------------- */
+namespace
+{
+  // over the first n (owned) entries
+  int dg_dot(mgx_context_t ctx, size_t n, int number, const void *x, const void *y, double *out)
+  {
+    return mgx::dot_owned_prefix(ctx, number, x, y, n, out);
+  }
+
+  int dg_norm(mgx_context_t ctx, size_t n, int number, const void *x, double *out)
+  {
+    MGX_TRY(mgx::dot_owned_prefix(ctx, number, x, x, n, out));
+    *out = std::sqrt(*out);
+    return MGX_OK;
+  }
+
+  // SolverCG with ReductionControl(100, 1e-16, tolerance) and zero start on the fp64 operator A_dp, as both multigrid
+  // solvers run it: n owned entries, solution_bytes cleared in the solution, r / z / d / h four fp64 vectors of the
+  // solver, precondition(z, r): z = M^-1 r; `name` heads the message when the iteration does not converge
+  template <typename Preconditioner>
+  int dg_pcg(mgx_context_t ctx, mgx_dg_operator_t A_dp, size_t n, size_t solution_bytes, double *r, double *z, double *d, double *h,
+             Preconditioner precondition, double tolerance, const double *rhs, double *solution, unsigned *iterations,
+             double *reduction_rate, const char *name)
+  {
+    hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
+    MGX_HIP(hipMemsetAsync(solution, 0, solution_bytes, s));
+    MGX_TRY(mgx_copy_cast(ctx, r, MGX_F64, rhs, MGX_F64, n));
+    double res0 = 0, res = 0, rz = 0, rz_old = 0;
+    MGX_TRY(dg_norm(ctx, n, MGX_F64, r, &res0));
+    res         = res0;
+    unsigned it = 0;
+    while (res > std::max(1e-16, tolerance * res0) && it < 100)
+      {
+        ++it;
+        MGX_TRY(precondition(z, r));
+        rz_old = rz;
+        MGX_TRY(dg_dot(ctx, n, MGX_F64, r, z, &rz));
+        if (it > 1)
+          MGX_TRY(mgx_sadd(ctx, MGX_F64, d, rz / rz_old, 1.0, z, n));
+        else
+          MGX_TRY(mgx_copy_cast(ctx, d, MGX_F64, z, MGX_F64, n));
+        MGX_TRY(mgx_dg_vmult(A_dp, h, d));
+        double dh = 0;
+        MGX_TRY(dg_dot(ctx, n, MGX_F64, d, h, &dh));
+        const double alpha = rz / dh;
+        MGX_TRY(mgx_sadd(ctx, MGX_F64, solution, 1.0, alpha, d, n));
+        MGX_TRY(mgx_sadd(ctx, MGX_F64, r, 1.0, -alpha, h, n));
+        MGX_TRY(dg_norm(ctx, n, MGX_F64, r, &res));
+      }
+    if (iterations)
+      *iterations = it;
+    if (reduction_rate)
+      *reduction_rate = it ? std::pow(res / res0, 1.0 / it) : 1.0;
+    return res > std::max(1e-16, tolerance * res0) ? dg_fail(MGX_ERR_NOT_CONVERGED, std::string(name) + ": 100 iterations") : MGX_OK;
+  }
+
+  // PreconditionChebyshev<LaplaceOperatorCompactCombine, Vector, JacobiTransformed>: vmult (zero start) and
+  // step, through the merged operation (deal.II hands iteration index 0 / 1, then k + 1 / k + 2)
+  // (update and old trade places with every step, as the reference swaps its two vectors)
+  int dg_smoother_apply(mgx_dg_operator_t A, const mgx_smoother_info &I, const void *defect, void *&update, void *&old,
+                        bool is_step)
+  {
+    int index;
+    if (!is_step)
+      {
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, 0, 0., 1. / I.theta, update, old));
+        index = 1;
+      }
+    else
+      {
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, 1, 0., 1. / I.theta, update, old));
+        std::swap(update, old);
+        index = 2;
+      }
+    if (I.degree < 2 || std::fabs(I.delta) < 1e-40)
+      return MGX_OK;
+    double rhok = I.delta / I.theta;
+    const double sigma = I.theta / I.delta;
+    for (int k = 0; k < I.degree - 1; ++k, ++index)
+      {
+        const double rhokp = 1. / (2. * sigma - rhok);
+        const double f1 = rhokp * rhok, f2 = 2. * rhokp / I.delta;
+        rhok = rhokp;
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, (unsigned)index, f1, f2, update, old));
+        std::swap(update, old);
+      }
+    return MGX_OK;
+  }
+
+  int dg_smoother_apply(mgx_dg_solver_t S, bool is_step) { return dg_smoother_apply(S->A, S->info, S->defect, S->update, S->old, is_step); }
+
+  // PreconditionChebyshev::initialize -> estimate_eigenvalues for a DG operator with JacobiTransformed
+  // (multigrid_solver_dg.h:293-303, multigrid_solver_dg_plain.h:192-213): at most max_its iterations of CG
+  // preconditioned with JacobiTransformed on v_i = (global index of i mod 11) - mean, stopped at a residual of 1e-10;
+  // lambda_max = 1.2 x the largest Ritz value.  smoothing_range > 1: [lambda_max / range, lambda_max]; otherwise
+  // [min(0.9 lambda_max, lambda_min), lambda_max].  degree < 0 (numbers::invalid_unsigned_int): Varga's estimate of the
+  // degree that reduces the error by smoothing_range.  r, z, d, h: four vectors of the operator, overwritten;
+  // cell_global_id: host, may be null.  A step whose d.A d or r.z is not a positive finite number ends the estimate
+  // with the Ritz values collected so far (fp32 on a level that CG has already solved to rounding).
+  int dg_smoother_initialize(mgx_context_t ctx, mgx_dg_operator_t A, const uint32_t *cell_global_id, void *r, void *z, void *d,
+                             void *h, int max_its, double smoothing_range, int degree, mgx_smoother_info &I)
+  {
+    hipStream_t  s      = (hipStream_t)mgx_context_stream(ctx);
+    const size_t n      = (size_t)mgx_dg_operator_n_dofs(A);
+    const int    number = A->number;
+    double       ng     = (double)n; // global number of DoFs
+    MGX_TRY(mgx::allreduce_sum(ctx, &ng, 1));
+    const uint64_t ngl  = (uint64_t)(ng + 0.5);
+    const uint64_t full = ngl / 11, rem = ngl % 11;
+    const double   mean = (full * 55.0 + rem * (rem - 1) / 2.0) / (double)ngl;
+    {
+      mgx::DeviceArena tmp("DG smoother set-up");
+      uint32_t        *cell_id = nullptr;
+      if (cell_global_id)
+        MGX_TRY(tmp.upload(&cell_id, cell_global_id, A->n_cells));
+      launch_start_vector(s, number, r, cell_id, A->n_cells, (uint32_t)(n / A->n_cells), mean);
+      MGX_HIP(hipStreamSynchronize(s));
+    }
+    std::vector<double> diag, off;
+    double              res = 0, rz = 0, rz_old = 0, alpha = 0, alpha_old = 0, beta = 0;
+    MGX_TRY(dg_norm(ctx, n, number, r, &res));
+    int it = 0;
+    while (it < max_its && res > 1e-10)
+      {
+        rz_old = rz;
+        MGX_TRY(mgx_dg_jacobi_vmult(A, z, r));
+        MGX_TRY(dg_dot(ctx, n, number, r, z, &rz));
+        if (!(rz > 0.) || !std::isfinite(rz))
+          break;
+        ++it;
+        if (it > 1)
+          {
+            beta = rz / rz_old;
+            MGX_TRY(mgx_sadd(ctx, number, d, beta, 1.0, z, n));
+          }
+        else
+          MGX_TRY(mgx_copy_cast(ctx, d, number, z, number, n));
+        MGX_TRY(mgx_dg_vmult(A, h, d));
+        double dh = 0;
+        MGX_TRY(dg_dot(ctx, n, number, d, h, &dh));
+        if (!(dh > 0.) || !std::isfinite(dh))
+          {
+            --it;
+            break;
+          }
+        alpha_old = alpha;
+        alpha     = rz / dh;
+        MGX_TRY(mgx_sadd(ctx, number, r, 1.0, -alpha, h, n));
+        MGX_TRY(dg_norm(ctx, n, number, r, &res));
+        if (it == 1)
+          diag.push_back(1. / alpha);
+        else
+          {
+            off.push_back(std::sqrt(beta) / alpha_old);
+            diag.push_back(1. / alpha + beta / alpha_old);
+          }
+      }
+    I.cg_iterations = it;
+    if (diag.empty())
+      I.lambda_min = I.lambda_max = 1.;
+    else if (diag.size() <= 64)
+      {
+        const int           m = (int)diag.size();
+        std::vector<double> Tm((size_t)m * m, 0.0), lam, V;
+        for (int i = 0; i < m; ++i)
+          {
+            Tm[i * m + i] = diag[i];
+            if (i + 1 < m)
+              Tm[i * m + i + 1] = Tm[(i + 1) * m + i] = off[i];
+          }
+        sym_eig(m, Tm, lam, V);
+        I.lambda_min = lam.front();
+        I.lambda_max = 1.2 * lam.back();
+      }
+    else // (the Jacobi sweeps above cost m^3 each: bisection on the tridiagonal matrix for a long Lanczos run)
+      {
+        double lo = 0, hi = 0;
+        off.push_back(0.);
+        mgx::tridiag_extreme_eigenvalues((int)diag.size(), diag.data(), off.data(), lo, hi);
+        I.lambda_min = lo;
+        I.lambda_max = 1.2 * hi;
+      }
+    mgx::chebyshev_interval(smoothing_range, degree, I);
+    return MGX_OK;
+  }
+
+  // vmult_residual_and_restrict_to_cg (laplace_operator_dg.h:853-861, action 1 :1798-1819): cg = sum over the cells of
+  // P^T (rhs - A lhs), inside the cell kernel.  Cells c, c + 8, ... share no FE_Q DoF when the mesh is in forest order:
+  // eight launches with plain adds (the sum is then the same in every run); one launch with atomics otherwise.
+  int dg_residual_and_restrict(mgx_dg_solver_t S, void *cg, const void *rhs, const void *lhs)
+  {
+    hipStream_t       s  = (hipStream_t)mgx_context_stream(S->ctx);
+    mgx_dg_operator_t op = S->A;
+    MGX_HIP(hipMemsetAsync(cg, 0, dg_nsz(S->number) * S->n_cg, s));
+    if (op->n_ghost > 0)
+      MGX_TRY(update_ghosts(op, const_cast<void *>(lhs)));
+    DGLaunch l(kRestrict, nullptr, rhs, lhs);
+    l.cg      = cg;
+    l.idx27   = S->idx27;
+    l.P1      = S->P1;
+    l.n_cells = op->n_cells;
+    if (!S->cg_eight_colours)
+      MGX_TRY(launch_cells(op, l));
+    else
+      {
+        l.plain       = 1;
+        l.cell_stride = 8;
+        for (uint32_t k = 0; k < 8 && k < op->n_cells; ++k)
+          {
+            l.cell_first = k;
+            l.n_cells    = (op->n_cells - k + 7) / 8;
+            MGX_TRY(launch_cells(op, l));
+          }
+      }
+    if (S->decomposed) // FE_Q DoFs on a rank interface collect the contributions of all sharers
+      MGX_TRY(mgx_exchange_add(S->fe, cg));
+    return MGX_OK;
+  }
+
+  // dg_v_cycle(1) (multigrid_solver_dg.h:605-633): defect in, update out
+  int dg_v_cycle(mgx_dg_solver_t S)
+  {
+    hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
+    MGX_TRY(dg_smoother_apply(S, false));
+    // vmult_residual_and_restrict_to_cg (:616-618)
+    if (!mgx::context_tunables(S->ctx).dg_unmerged_restrict)
+      MGX_TRY(dg_residual_and_restrict(S, S->cg_defect, S->defect, S->update));
+    else
+      {
+        MGX_TRY(mgx_dg_vmult_residual(S->A, S->t, S->defect, S->update));
+        MGX_HIP(hipMemsetAsync(S->cg_defect, 0, dg_nsz(S->number) * S->n_cg, s));
+        mgx::launch_dg_cg_transfer(s, S->number, S->degree, false, S->cg_defect, S->t, S->idx27, S->n_cells, S->P1,
+                                   S->cg_eight_colours);
+        if (S->decomposed) // FE_Q DoFs on a rank interface collect the contributions of all sharers
+          MGX_TRY(mgx_exchange_add(S->fe, S->cg_defect));
+      }
+    MGX_TRY(mgx_solver_v_cycle(S->cfe)); // :622
+    // prolongate_add_cg_to_dg (:625; laplace_operator_dg.h:1863-1894)
+    mgx::launch_dg_cg_transfer(s, S->number, S->degree, true, S->update, S->cg_update, S->idx27, S->n_cells, S->P1);
+    MGX_HIP(hipGetLastError());
+    return dg_smoother_apply(S, true); // :629
+  }
+} // namespace
+
+extern "C" {
+
+int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_dg_solver_t *out)
+{
+  MGX_REQUIRE(ctx && desc && out && desc->matrix_dg && desc->matrix_dg_dp && desc->cfe, "mgx_dg_solver_create: null argument");
+  mgx_dg_operator_t A = desc->matrix_dg, Ad = desc->matrix_dg_dp;
+  if (Ad->number != MGX_F64 || A->n_cells != Ad->n_cells || A->degree != Ad->degree || A->basis != Ad->basis)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_create: matrix_dg_dp must be the fp64 twin of matrix_dg");
+  if (desc->degree_pre < 1)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_create: degree_pre must be at least 1");
+  const int      lmax = mgx_solver_n_levels(desc->cfe) - 1;
+  mgx_operator_t fe   = nullptr;
+  MGX_TRY(mgx_solver_get_operator(desc->cfe, lmax, 0, &fe));
+  const uint32_t *idx27 = nullptr;
+  uint32_t        nc = 0, ncg = 0;
+  int             p = 0;
+  MGX_TRY(mgx_operator_device_indices(fe, &idx27, &nc, &ncg, &p));
+  if (nc != A->n_cells || p != A->degree || mgx_operator_number(fe) != A->number)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_create: the FE_Q hierarchy's finest level must have the DG "
+                                             "operator's cells, degree and number type");
+  std::unique_ptr<mgx_dg_solver_s, int (*)(mgx_dg_solver_t)> S(new mgx_dg_solver_s, mgx_dg_solver_destroy);
+  S->ctx = ctx;
+  S->A = A;
+  S->A_dp = Ad;
+  S->cfe = desc->cfe;
+  S->degree = A->degree;
+  S->number = A->number;
+  S->n = (size_t)mgx_dg_operator_n_dofs(A);
+  S->n_vec = (size_t)mgx_dg_operator_vector_size(A);
+  S->fe = fe;
+  S->decomposed = A->n_ghost > 0;
+  if (A->n_ghost != Ad->n_ghost)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_create: the two DG operators must share the partition");
+  S->idx27 = idx27;
+  S->n_cells = nc;
+  S->n_cg = ncg;
+  {
+    // forest order (the same child of every parent in one class): checked, not assumed
+    std::vector<uint32_t> h27(27 * (size_t)nc), stamp(ncg, 0xFFFFFFFFu);
+    MGX_HIP(hipMemcpy(h27.data(), idx27, sizeof(uint32_t) * h27.size(), hipMemcpyDeviceToHost));
+    bool ok = nc >= 64;
+    for (uint32_t k = 0; k < 8 && ok; ++k)
+      for (uint32_t c = k; c < nc && ok; c += 8)
+        for (int e = 0; e < 27 && ok; ++e)
+          {
+            const uint32_t v = h27[27 * (size_t)c + e];
+            if (v == 0xFFFFFFFFu || v >= ncg)
+              continue;
+            if (S->degree == 1 && (e % 3 == 1 || (e / 3) % 3 == 1 || e / 9 == 1)) // entity without DoFs
+              continue;
+            // an entity's first DoF identifies it; stamp = class * nc + cell would overflow: class and cell apart
+            const uint32_t mark = k * 0x10000000u + (c >> 3);
+            ok                  = stamp[v] == 0xFFFFFFFFu || (stamp[v] >> 28) != k || stamp[v] == mark;
+            stamp[v]            = mark;
+          }
+    S->cg_eight_colours = ok && nc < 0x80000000u;
+  }
+  hipStream_t  s  = (hipStream_t)mgx_context_stream(ctx);
+  const size_t vb = dg_nsz(S->number) * S->n_vec;
+  for (void **v : {&S->defect, &S->t, &S->update, &S->old})
+    {
+      MGX_TRY(S->mem.zeros(v, vb, s));
+    }
+  for (double **v : {&S->r, &S->z, &S->d, &S->h})
+    {
+      MGX_TRY(S->mem.zeros(v, S->n_vec, s));
+    }
+  {
+    const int n1 = S->degree + 1;
+    MGX_TRY(S->mem.upload_as(S->number, &S->P1, A->h.P1.data(), (size_t)n1 * n1));
+  }
+  // the FE_Q hierarchy under a DG level smooths with degree_pre - 1 on its finest level and solves
+  // the coarsest one to 2e-3 (multigrid_solver_dg.h:271-291)
+  if (lmax > 0)
+    MGX_TRY(mgx_solver_reset_smoother(desc->cfe, lmax, 20., std::max(1, desc->degree_pre - 1), 15));
+  {
+    uint32_t n0 = 0;
+    mgx_operator_t f0 = nullptr;
+    MGX_TRY(mgx_solver_get_operator(desc->cfe, 0, 0, &f0));
+    MGX_TRY(mgx_operator_device_indices(f0, nullptr, nullptr, &n0, nullptr));
+    MGX_TRY(mgx_solver_reset_smoother(desc->cfe, 0, 2e-3, -1, (int)std::max<uint32_t>(3u, n0)));
+  }
+  MGX_TRY(mgx_solver_get_vector(desc->cfe, lmax, 2, &S->cg_defect));
+  MGX_TRY(mgx_solver_get_vector(desc->cfe, lmax, 4, &S->cg_update));
+
+  // smooth_dg.initialize (multigrid_solver_dg.h:293-303): eigenvalue estimate by 15 iterations of
+  // CG preconditioned with JacobiTransformed on v_i = (i mod 11) - mean, lambda_max = 1.2 x the
+  // largest Ritz value, range 20
+  {
+    // (the level vectors are free until the first cycle)
+    MGX_TRY(dg_smoother_initialize(ctx, A, desc->cell_global_id, S->t, S->update, S->old, S->defect, 15, 20., desc->degree_pre,
+                                   S->info));
+    for (void *v : {S->defect, S->t, S->update, S->old})
+      MGX_HIP(hipMemsetAsync(v, 0, vb, s));
+    MGX_HIP(hipStreamSynchronize(s));
+  }
+  *out = S.release();
+  return MGX_OK;
+}
+
+int mgx_dg_solver_destroy(mgx_dg_solver_t S)
+{
+  if (!S)
+    return MGX_OK;
+  if (S->ctx)
+    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
+  delete S;
+  return MGX_OK;
+}
+
+int mgx_dg_solver_smoother_info(mgx_dg_solver_t S, mgx_smoother_info *info)
+{
+  MGX_REQUIRE(S && info, "mgx_dg_solver_smoother_info: null argument");
+  *info = S->info;
+  return MGX_OK;
+}
+
+int mgx_dg_restrict_to_cg(mgx_dg_solver_t S, void *cg_dst, const void *dg_src)
+{
+  MGX_REQUIRE(S && cg_dst && dg_src, "mgx_dg_restrict_to_cg: null argument");
+  hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
+  MGX_HIP(hipMemsetAsync(cg_dst, 0, dg_nsz(S->number) * S->n_cg, s));
+  mgx::launch_dg_cg_transfer(s, S->number, S->degree, false, cg_dst, dg_src, S->idx27, S->n_cells, S->P1, S->cg_eight_colours);
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_vmult_residual_and_restrict_to_cg(mgx_dg_solver_t S, void *cg_dst, const void *rhs, const void *lhs)
+{
+  MGX_REQUIRE(S && cg_dst && rhs && lhs, "mgx_dg_vmult_residual_and_restrict_to_cg: null argument");
+  return dg_residual_and_restrict(S, cg_dst, rhs, lhs);
+}
+
+int mgx_dg_prolongate_add_cg_to_dg(mgx_dg_solver_t S, void *dg_dst, const void *cg_src)
+{
+  MGX_REQUIRE(S && dg_dst && cg_src, "mgx_dg_prolongate_add_cg_to_dg: null argument");
+  hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
+  mgx::launch_dg_cg_transfer(s, S->number, S->degree, true, dg_dst, cg_src, S->idx27, S->n_cells, S->P1);
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_solver_vmult(mgx_dg_solver_t S, double *dst, const double *src)
+{
+  MGX_REQUIRE(S && dst && src, "mgx_dg_solver_vmult: null argument");
+  MGX_TRY(mgx_copy_cast(S->ctx, S->defect, S->number, src, MGX_F64, S->n)); // multigrid_solver_dg.h:433
+  MGX_TRY(dg_v_cycle(S));
+  return mgx_copy_cast(S->ctx, dst, MGX_F64, S->update, S->number, S->n);       // :436
+}
+
+int mgx_dg_solver_solve_cg(mgx_dg_solver_t S, double tolerance, const double *rhs, double *solution,
+                           unsigned *iterations, double *reduction_rate)
+{
+  MGX_REQUIRE(S && rhs && solution, "mgx_dg_solver_solve_cg: null argument");
+  // preconditioner = one DG V-cycle (multigrid_solver_dg.h:410-424)
+  return dg_pcg(S->ctx, S->A_dp, S->n, 8 * S->n_vec, S->r, S->z, S->d, S->h, [S](double *z, const double *r) { return mgx_dg_solver_vmult(S, z, r); },
+                tolerance, rhs, solution, iterations, reduction_rate, "mgx_dg_solver_solve_cg");
+}
+
+} // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * DG-to-DG level transfer and MultigridSolverDGPlain
+ * --------------------------------------------------------------------------------------------- */
+namespace
+{
+  // one part of a V-cycle, timed when the solver's timings are on (print_wall_times of the reference: host timers
+  // around synchronised parts -- for diagnosis, the parts no longer overlap their launches)
+  struct PlainTimer
+  {
+    mgx_dg_plain_solver_t S;
+    double               *slot;
+    std::chrono::steady_clock::time_point t0;
+    PlainTimer(mgx_dg_plain_solver_t solver, double *where)
+      : S(solver)
+      , slot(where)
+    {
+      if (S->timed)
+        {
+          (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
+          t0 = std::chrono::steady_clock::now();
+        }
+    }
+    ~PlainTimer()
+    {
+      if (S->timed)
+        {
+          (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
+          *slot += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+    }
+  };
+
+  // v_cycle(level, 1) (multigrid_solver_dg_plain.h:456-496): defect[level] in, update[level] out
+  int plain_v_cycle(mgx_dg_plain_solver_t S, int l)
+  {
+    hipStream_t                   s = (hipStream_t)mgx_context_stream(S->ctx);
+    mgx_dg_plain_solver_s::Level &L = S->level[l];
+    if (l == 0) // coarse = the level-0 smoother's vmult (:462)
+      {
+        PlainTimer timer(S, &L.times[0]);
+        L.times[1] += 1;
+        return dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, false);
+      }
+    mgx_dg_plain_solver_s::Level &C = S->level[l - 1];
+    {
+      PlainTimer timer(S, &L.times[5]);
+      MGX_TRY(dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, false)); // :472
+    }
+    {
+      PlainTimer timer(S, &L.times[0]);
+      MGX_TRY(mgx_dg_vmult_residual(L.A, L.t, L.defect, L.update)); // :478
+    }
+    {
+      PlainTimer timer(S, &L.times[1]);
+      MGX_HIP(hipMemsetAsync(C.defect, 0, dg_nsz(S->number) * C.n, s)); // :482
+      MGX_TRY(mgx_dg_transfer_restrict_and_add(L.transfer, C.defect, L.t)); // :483
+    }
+    MGX_TRY(plain_v_cycle(S, l - 1));
+    {
+      PlainTimer timer(S, &L.times[2]);
+      MGX_TRY(mgx_dg_transfer_prolongate_and_add(L.transfer, L.update, C.update)); // :489
+    }
+    PlainTimer timer(S, &L.times[5]);
+    return dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, true); // :493
+  }
+} // namespace
+
+extern "C" {
+
+int mgx_dg_transfer_create(mgx_context_t ctx, const mgx_dg_transfer_desc *desc, mgx_dg_transfer_t *out)
+{
+  MGX_REQUIRE(ctx && desc && out && desc->children, "mgx_dg_transfer_create: null argument");
+  if (desc->degree < 1 || desc->degree > MGX_MAX_DEGREE)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_transfer_create: degree must be in 1.." + std::to_string(MGX_MAX_DEGREE));
+  if (desc->basis < MGX_DG_HERMITE || desc->basis > MGX_DG_GAUSS)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_transfer_create: basis must be MGX_DG_HERMITE, _GAUSS_LOBATTO or _GAUSS");
+  if (desc->number != MGX_F32 && desc->number != MGX_F64)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: number must be MGX_F32 or MGX_F64");
+  if (desc->n_coarse_cells == 0 || desc->n_coarse_cells >= (1u << 28))
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: n_coarse_cells must be in 1 .. 2^28 - 1");
+  // every fine cell is the child of exactly one coarse cell: what lets the kernels write without atomics, and what
+  // keeps every access inside the fine vector
+  const size_t      n_fine = 8 * (size_t)desc->n_coarse_cells;
+  std::vector<bool> seen(n_fine, false);
+  bool              identity = true;
+  for (size_t i = 0; i < n_fine; ++i)
+    {
+      const uint32_t f = desc->children[i];
+      if (f >= n_fine || seen[f])
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: children must name every fine cell 0 .. 8 n_coarse_cells - 1 "
+                                                 "exactly once (entry " + std::to_string(i) + " = " + std::to_string(f) + ")");
+      seen[f]  = true;
+      identity = identity && f == i;
+    }
+  Host1D      h;
+  std::string why;
+  const int   status = build_1d(desc->degree, desc->basis, h, why);
+  if (status != MGX_OK)
+    return dg_fail(status, "mgx_dg_transfer_create: " + why);
+  std::unique_ptr<mgx_dg_transfer_s, int (*)(mgx_dg_transfer_t)> T(new mgx_dg_transfer_s, mgx_dg_transfer_destroy);
+  T->ctx      = ctx;
+  T->degree   = desc->degree;
+  T->basis    = desc->basis;
+  T->number   = desc->number;
+  T->n_coarse = desc->n_coarse_cells;
+  T->identity = identity;
+  T->p1d_host = h.embed;
+  MGX_TRY(T->mem.upload(&T->children, desc->children, n_fine));
+  MGX_TRY(T->mem.upload_as(T->number, &T->p1d, h.embed.data(), h.embed.size()));
+  *out = T.release();
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_destroy(mgx_dg_transfer_t T)
+{
+  if (!T)
+    return MGX_OK;
+  if (T->ctx)
+    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(T->ctx));
+  delete T;
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_prolongate_and_add(mgx_dg_transfer_t T, void *fine_dst, const void *coarse_src)
+{
+  MGX_REQUIRE(T && fine_dst && coarse_src && fine_dst != coarse_src, "mgx_dg_transfer_prolongate_and_add: null or aliased vectors");
+  mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->degree, true, fine_dst, coarse_src, T->children,
+                          T->n_coarse, T->p1d, T->identity);
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_restrict_and_add(mgx_dg_transfer_t T, void *coarse_dst, const void *fine_src)
+{
+  MGX_REQUIRE(T && coarse_dst && fine_src && coarse_dst != fine_src, "mgx_dg_transfer_restrict_and_add: null or aliased vectors");
+  mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->degree, false, coarse_dst, fine_src, T->children,
+                          T->n_coarse, T->p1d, T->identity);
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_transfer_matrix(mgx_dg_transfer_t T, double *p1d)
+{
+  MGX_REQUIRE(T && p1d, "mgx_dg_transfer_matrix: null argument");
+  std::copy(T->p1d_host.begin(), T->p1d_host.end(), p1d);
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc *desc, mgx_dg_plain_solver_t *out)
+{
+  if (!ctx || !desc || !out || !desc->matrix || !desc->matrix_dg_dp || (desc->n_levels > 1 && !desc->transfer))
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: null argument");
+  if (desc->n_levels < 1 || desc->n_levels > 32)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: n_levels must be in 1..32");
+  if (desc->degree_pre < 1)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: degree_pre must be at least 1");
+  const int         L   = desc->n_levels - 1;
+  mgx_dg_operator_t top = desc->matrix[L], Ad = desc->matrix_dg_dp;
+  for (int l = 0; l <= L; ++l)
+    {
+      mgx_dg_operator_t A = desc->matrix[l];
+      if (!A)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) + "] is null");
+      if (A->ctx != ctx)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: operators of another context");
+      if (A->n_ghost > 0)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
+                                                   "] has ghost cells; the plain DG multigrid runs on one rank");
+      if (A->degree != top->degree || A->basis != top->basis || A->number != top->number)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
+                                                   "] differs from the finest level in degree, basis or number type");
+      if (l == 0)
+        continue;
+      mgx_dg_transfer_t T = desc->transfer[l - 1];
+      if (!T)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) + "] is null");
+      if (T->degree != top->degree || T->basis != top->basis || T->number != top->number || T->ctx != ctx)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) +
+                                                   "] differs from the operators in degree, basis, number type or context");
+      if (T->n_coarse != desc->matrix[l - 1]->n_cells || 8 * (uint64_t)desc->matrix[l - 1]->n_cells != A->n_cells)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: level " + std::to_string(l) + " has " +
+                                                   std::to_string(A->n_cells) + " cells, level " + std::to_string(l - 1) + " " +
+                                                   std::to_string(desc->matrix[l - 1]->n_cells) + " and the transfer between them " +
+                                                   std::to_string(T->n_coarse) + " coarse cells (8 x coarse = fine required)");
+    }
+  if (Ad->number != MGX_F64 || Ad->n_cells != top->n_cells || Ad->degree != top->degree || Ad->basis != top->basis || Ad->n_ghost > 0 ||
+      Ad->ctx != ctx)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix_dg_dp must be the fp64 twin of the finest matrix");
+
+  std::unique_ptr<mgx_dg_plain_solver_s, int (*)(mgx_dg_plain_solver_t)> S(new mgx_dg_plain_solver_s, mgx_dg_plain_solver_destroy);
+  S->ctx    = ctx;
+  S->A_dp   = Ad;
+  S->number = top->number;
+  S->level.resize(L + 1);
+  hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
+  for (int l = 0; l <= L; ++l)
+    {
+      mgx_dg_plain_solver_s::Level &lv = S->level[l];
+      lv.A        = desc->matrix[l];
+      lv.transfer = l > 0 ? desc->transfer[l - 1] : nullptr;
+      lv.n        = (size_t)mgx_dg_operator_n_dofs(lv.A);
+      for (void **v : {&lv.defect, &lv.t, &lv.update, &lv.old})
+        {
+          MGX_TRY(S->mem.zeros(v, dg_nsz(S->number) * lv.n, s));
+        }
+    }
+  for (double **v : {&S->r, &S->z, &S->d, &S->h})
+    {
+      MGX_TRY(S->mem.zeros(v, S->level[L].n, s));
+    }
+  MGX_TRY(S->mem.alloc(&S->partials, 4 * (size_t)mgx::kDotBlocks));
+  MGX_TRY(S->mem.alloc(&S->sums, 4));
+  // smooth[level].initialize (:192-213)
+  for (int l = 0; l <= L; ++l)
+    {
+      mgx_dg_plain_solver_s::Level &lv  = S->level[l];
+      const uint32_t               *ids = desc->cell_global_id ? desc->cell_global_id[l] : nullptr;
+      if (l > 0)
+        MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect, 15, 20.,
+                                       l < L ? desc->degree_pre : std::max(1, desc->degree_pre - 1), lv.info));
+      else
+        MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect,
+                                       (int)std::min<size_t>(lv.n, 0x7FFFFFFF), 1e-5, -1, lv.info));
+      for (void *v : {lv.defect, lv.t, lv.update, lv.old})
+        MGX_HIP(hipMemsetAsync(v, 0, dg_nsz(S->number) * lv.n, s));
+    }
+  MGX_HIP(hipStreamSynchronize(s));
+  *out = S.release();
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_destroy(mgx_dg_plain_solver_t S)
+{
+  if (!S)
+    return MGX_OK;
+  if (S->ctx)
+    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
+  delete S;
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_smoother_info(mgx_dg_plain_solver_t S, int level, mgx_smoother_info *info)
+{
+  if (!S || !info || level < 0 || level >= (int)S->level.size())
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_smoother_info: null argument or no such level");
+  *info = S->level[level].info;
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_vmult(mgx_dg_plain_solver_t S, double *dst, const double *src)
+{
+  MGX_REQUIRE(S && dst && src, "mgx_dg_plain_solver_vmult: null argument");
+  mgx_dg_plain_solver_s::Level &top = S->level.back();
+  MGX_TRY(mgx_copy_cast(S->ctx, top.defect, S->number, src, MGX_F64, top.n)); // multigrid_solver_dg_plain.h:327
+  MGX_TRY(plain_v_cycle(S, (int)S->level.size() - 1));
+  return mgx_copy_cast(S->ctx, dst, MGX_F64, top.update, S->number, top.n);   // :331
+}
+
+int mgx_dg_plain_solver_solve_cg(mgx_dg_plain_solver_t S, double tolerance, const double *rhs, double *solution,
+                                 unsigned *iterations, double *reduction_rate)
+{
+  MGX_REQUIRE(S && rhs && solution, "mgx_dg_plain_solver_solve_cg: null argument");
+  // preconditioner = one V-cycle (multigrid_solver_dg_plain.h:303-317)
+  const size_t n = S->level.back().n;
+  return dg_pcg(S->ctx, S->A_dp, n, 8 * n, S->r, S->z, S->d, S->h, [S](double *z, const double *r) { return mgx_dg_plain_solver_vmult(S, z, r); },
+                tolerance, rhs, solution, iterations, reduction_rate, "mgx_dg_plain_solver_solve_cg");
+}
+
+int mgx_dg_plain_solver_vmult_with_residual_update(mgx_dg_plain_solver_t S, double *residual, double *update, double factor,
+                                                   double sums[2])
+{
+  MGX_REQUIRE(S && residual && update && sums && residual != update, "mgx_dg_plain_solver_vmult_with_residual_update: null or aliased argument");
+  hipStream_t                   s   = (hipStream_t)mgx_context_stream(S->ctx);
+  mgx_dg_plain_solver_s::Level &top = S->level.back();
+  mgx::launch_residual_pre(s, S->number, top.defect, residual, update, factor, top.n); // :353-358
+  MGX_TRY(plain_v_cycle(S, (int)S->level.size() - 1));                                 // :362
+  // :365-413 (no constrained rows in DG: every entry takes the V-cycle's value); block sums added in a fixed order
+  const uint32_t used = mgx::launch_residual_post(s, S->number, top.update, residual, update, factor, top.n, top.n, S->partials);
+  mgx::launch_reduce4(s, S->partials, used, nullptr, S->sums);
+  MGX_HIP(hipGetLastError());
+  double h[4];
+  MGX_HIP(hipMemcpyAsync(h, S->sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
+  sums[0] = h[0];
+  sums[1] = h[1];
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_enable_timings(mgx_dg_plain_solver_t S, int on)
+{
+  MGX_REQUIRE(S, "mgx_dg_plain_solver_enable_timings: null solver");
+  S->timed = on != 0;
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_get_timings(mgx_dg_plain_solver_t S, double *times)
+{
+  MGX_REQUIRE(S && times, "mgx_dg_plain_solver_get_timings: null argument");
+  for (size_t l = 0; l < S->level.size(); ++l)
+    for (int j = 0; j < 6; ++j)
+      {
+        times[6 * l + j]       = S->level[l].times[j];
+        S->level[l].times[j] = 0.;
+      }
+  return MGX_OK;
+}
+
+int mgx_dg_plain_solver_do_matvec(mgx_dg_plain_solver_t S)
+{
+  MGX_REQUIRE(S, "mgx_dg_plain_solver_do_matvec: null solver");
+  return mgx_dg_vmult(S->A_dp, S->h, S->d); // matrix_dg_dp.vmult(residual, solution), :435
+}
+
+int mgx_dg_plain_solver_do_matvec_smoother(mgx_dg_plain_solver_t S)
+{
+  MGX_REQUIRE(S, "mgx_dg_plain_solver_do_matvec_smoother: null solver");
+  mgx_dg_plain_solver_s::Level &top = S->level.back();
+  return mgx_dg_vmult(top.A, top.t, top.defect); // matrix[maxlevel].vmult, :444
+}
+
+} // extern "C"

@@ -1,0 +1,48 @@
+// mgx_dg_host.hpp -- host numerics of the DG (symmetric interior penalty) operator, in fp64 and without the device:
+// the 1D data of an element basis (quadrature, shape values, the generalised eigenproblem of the block-Jacobi
+// preconditioner, the embedding into the two halves of a cell), the geometry factors of an affine cell and the
+// transformed diagonal.  Implemented in mgx_dg_host.cpp; read by mgx_dg_api.cpp (set-up of the objects) and
+// mgx_dg_kernels.hip (which turns them into the constant block of the cell kernel).
+#pragma once
+
+#include "../../include/mgx_dg.h"
+
+#include <string>
+#include <vector>
+
+namespace mgx::dg
+{
+  constexpr int kMaxN = MGX_MAX_DEGREE + 1;
+
+  // eigenvalues (ascending) and eigenvectors (columns of V) of a symmetric matrix, cyclic Jacobi
+  void sym_eig(int n, std::vector<double> A, std::vector<double> &lambda, std::vector<double> &V);
+
+  struct Host1D
+  {
+    int                 n = 0;
+    std::vector<double> xq, wq, S, SD, D, E, lambda;
+    bool                e_parity = false; // eigenvectors sorted even first / odd behind (see build_1d)
+    double              b[2][kMaxN], g[2][kMaxN], fb[2][kMaxN], fg[2][kMaxN];
+    double              hderiv = 0;
+    std::vector<double> P1; // [i*n+q]: values in the Gauss-Lobatto nodes -> coefficients of the element basis
+    // [h*n*n + i*n+j], h = 0, 1: coefficient i, in this basis on [0,1], of phi_j((x + h) / 2) -- the embedding of a
+    // cell's space into the spaces of its two halves (level transfer between DG spaces)
+    std::vector<double> embed;
+    // eigenfunctions: Laplace form, first-derivative form, values and derivatives at the two ends
+    std::vector<double> lt, ct, beta[2], gamma[2];
+  };
+
+  // 1D data of degree p in the basis MGX_DG_*; a status of include/mgx.h, with the reason in `why` on failure
+  int build_1d(int p, int basis, Host1D &h, std::string &why);
+
+  struct Geometry
+  {
+    double K[6], cn[3][3], fw[3], sigma[3];
+  };
+
+  int build_geometry(const double J[9], int p, Geometry &g, std::string &why);
+
+  // diagonal of T^T A_KK T for one combination of Dirichlet faces (bit f of cat): Kronecker
+  // products of 1D forms in the eigenvector basis, in which the mass matrix is the identity
+  void transformed_diagonal(const Host1D &h, const Geometry &g, unsigned cat, std::vector<double> &diag);
+} // namespace mgx::dg

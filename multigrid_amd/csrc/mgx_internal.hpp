@@ -2,6 +2,8 @@
 // (mgx_kernels.hip).  Not installed; the public boundary is include/mgx.h.
 #pragma once
 
+#include "../../include/mgx.h"
+
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,7 +17,7 @@ struct mgx_context_s;
 
 namespace mgx
 {
-  constexpr int      kMaxN    = 10; // p <= 9
+  constexpr int      kMaxN    = MGX_MAX_DEGREE + 1;
   constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 
   // Options of a context, carried by the objects built on it (two contexts of one process can differ:
@@ -414,6 +416,15 @@ namespace mgx
   {
     return ((mode == MODES ? (f(std::integral_constant<int, MODES>()), true) : false) || ...);
   }
+  // f(T()) with T the number type: double for MGX_F64, float otherwise
+  template <typename F>
+  static void dispatch_number(int number, F &&f)
+  {
+    if (number == MGX_F64)
+      f(double());
+    else
+      f(float());
+  }
   // workgroups of a persistent launch over `count` bricks: as many as are resident at once (wgs_per_cu on every CU of
   // the operator's device); Tunables::macro_wg_x16 sets the number per CU instead (tuning aid)
   inline uint32_t persistent_grid(const OperatorData &op, int wgs_per_cu, uint32_t count)
@@ -531,6 +542,71 @@ namespace mgx
   // p1d [2][(p+1)^2] in the number type; identity: children[c][k] == 8 c + k, the table is not read
   void launch_dg_transfer(hipStream_t s, int number, int p, bool prolong, void *dst, const void *src, const uint32_t *children,
                           uint32_t n_coarse, const void *p1d, bool identity);
+  // ---- DG cell kernel (mgx_dg_kernels.hip): what it offers the host code of mgx_dg_api.cpp ----
+  namespace dg
+  {
+    struct Host1D;   // mgx_dg_host.hpp
+    struct Geometry;
+
+    enum Action
+    {
+      kVmult     = 0,
+      kRestrict  = 1, // residual, changed to the FE_Q basis and added into the FE_Q vector
+      kCgSums    = 2, // product stored, the four sums of the merged CG iteration
+      kChebyshev = 3, // numbering of laplace_operator_dg.h:957-962
+      kResidual  = 4,
+      kJacobi    = 5  // P^-1 only (scaled by f2)
+    };
+
+    // what every launch of one operator shares (device pointers; consts: a copy of const_block)
+    struct CellOperands
+    {
+      int            number = 0, degree = 0, basis = 0;
+      const int32_t *neigh    = nullptr;
+      const void    *consts   = nullptr;
+      const void    *inv_diag = nullptr; // [64][(p+1)^3]
+      uint32_t       n_owned  = 0;       // owned cells of the operator: neighbour entries >= n_owned are ghosts
+      bool           has_ghosts = false;
+    };
+
+    // one launch of the cell kernel; vectors and P1 in the operator's number type
+    struct DGLaunch
+    {
+      DGLaunch(int action_, void *dst_, const void *rhs_, const void *src_) : action(action_), dst(dst_), rhs(rhs_), src(src_) {}
+      int             action;
+      void           *dst;
+      const void     *rhs, *src;
+      double          f1 = 0, f2 = 0;
+      int             iteration_index = 0;
+      const uint32_t *cell_list       = nullptr; // cells of this launch (nullptr: cell_first + cell_stride * i)
+      uint32_t        cell_first = 0, cell_stride = 1, n_cells = 0;
+      // kCgSums: [workgroups][4] block sums.  kRestrict: the FE_Q vector the transformed residual is added into, the
+      // compressed index table of the FE_Q cells (in the order of the DG cells), the 1D change of basis [n][n] and
+      // whether the cells of the launch share no FE_Q DoF (plain adds instead of atomics)
+      double         *partials = nullptr;
+      void           *cg       = nullptr;
+      const uint32_t *idx27    = nullptr;
+      const void     *P1       = nullptr;
+      int             plain    = 0;
+    };
+    // a status of include/mgx.h: MGX_ERR_UNSUPPORTED for a degree, basis or action no kernel is built for
+    int      launch_dg_cells(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
+    uint32_t cell_grid(int number, int p, uint32_t n_cells); // workgroups of a launch over n_cells cells
+    // the constant block of the cell kernel in the number type, from the host data
+    std::vector<char> const_block(int number, const Host1D &h, const Geometry &g);
+    // ghost exchange: whole cells / (Hermite-like basis) value and normal derivative on face faces[c] of cells[c]
+    void launch_pack_cells(hipStream_t s, int number, void *buf, const void *vec, const uint32_t *cells, uint32_t count,
+                           uint32_t n3);
+    void launch_pack_faces(hipStream_t s, int number, void *buf, const void *vec, const uint32_t *cells, const uint8_t *faces,
+                           uint32_t count, int N, double hderiv);
+    // v[i] = (global index of i mod 11) - mean over n_cells cells of n3 entries; cell_id: global cell numbers or null
+    void launch_start_vector(hipStream_t s, int number, void *v, const uint32_t *cell_id, uint32_t n_cells, uint32_t n3,
+                             double mean);
+  } // namespace dg
+  // Ritz values -> Chebyshev interval (PreconditionChebyshev::estimate_eigenvalues): given info.lambda_min / lambda_max,
+  // sets degree (degree < 0: Varga's estimate for eps = smoothing_range), delta and theta; returns the lower end a =
+  // lambda_max / smoothing_range (smoothing_range > 1) or min(0.9 lambda_max, lambda_min)
+  double chebyshev_interval(double smoothing_range, int degree, mgx_smoother_info &info);
   void launch_zero_head_copy_tail(hipStream_t s, int number, void *dst, const void *src, uint32_t n_head, uint32_t n);
   void launch_scatter_map(hipStream_t s, int number, void *dst, const void *src, const uint32_t *map,
                           const uint8_t *mask, uint32_t n);

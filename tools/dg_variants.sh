@@ -1,6 +1,6 @@
 #!/bin/bash
 # Merged DG Chebyshev step (tools/matvec_dg_cheby.py, Hermite-like basis) for several degrees and library
-# variants (tools/build_variant_of.sh mgx_dg <tag> ...): DoFs/s per (variant, degree, number type).
+# variants (tools/build_variant_of.sh mgx_dg_kernels <tag> ...): DoFs/s per (variant, degree, number type).
 # usage: tools/dg_variants.sh "<tags>" "<degrees>" [f32|f64] [steps]     (tag prod = the production library)
 tags=$1; degs=$2; num=${3:-f32}; steps=${4:-18}
 for tag in $tags; do
