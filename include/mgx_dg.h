@@ -69,16 +69,24 @@ typedef struct
    * mgx_dg_operator_vector_size() entries, owned cells first, like deal.II's owned | ghost layout */
   uint32_t                    n_ghost_cells;
   const mgx_dg_exchange_desc *exchange;
+  /* space dimension of the cells: 0 or 3: three (everything above), 2: two -- LaplaceOperatorCompactCombine<2,...>
+   * (the dim == 2 branches, laplace_operator_dg.h:418, 1028, 1147, 1675) as poisson_dg_plain/program.cc:65 sets it.
+   * Then neighbours is [n_cells][4] (face 2d+s, d = 0, 1), jacobian holds a row-major 2 x 2 in its first four entries
+   * (the rest is ignored), vectors hold (p+1)^2 coefficients per cell, x fastest, and n_ghost_cells must be 0 (one
+   * rank only).  Any other value: MGX_ERR_INVALID_ARGUMENT. */
+  int dim;
 } mgx_dg_operator_desc;
 
 /* LaplaceOperatorCompactCombine::reinit (:361-771) + JacobiTransformed::JacobiTransformed
  * (:2031-2038, local_compute_diagonals :2099-2233): 1D basis data, penalty and normal factors,
  * eigenvector basis and the inverse transformed diagonals (one set per combination of Dirichlet
  * faces -- at most 64 -- instead of one per cell). */
+/* desc->dim == 2: the same with the dim == 2 branches (:418 data per face, :749-771 geometry; JacobiTransformed
+ * :2162): 16 combinations of Dirichlet faces. */
 int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, mgx_dg_operator_t *op);
 int mgx_dg_operator_destroy(mgx_dg_operator_t op);
 
-/* LaplaceOperatorCompactCombine::m (:796-800) */
+/* LaplaceOperatorCompactCombine::m (:796-800): n_cells (p+1)^dim */
 uint64_t mgx_dg_operator_n_dofs(mgx_dg_operator_t op);
 
 /* entries of a vector including the ghost cells (== mgx_dg_operator_n_dofs on a single rank) */
@@ -86,9 +94,11 @@ uint64_t mgx_dg_operator_vector_size(mgx_dg_operator_t op);
 /* Vector::update_ghost_values (the import of laplace_operator_dg.h:986-1057): fills the ghost cells
  * of vec from their owners.  Every operator application below does this for its source vector
  * (whose ghost part is therefore written although the argument is const). */
+/* A 2D operator lives on one rank (the exchange of :1028 is not built): MGX_ERR_UNSUPPORTED. */
 int mgx_dg_update_ghost_values(mgx_dg_operator_t op, void *vec);
 
-/* LaplaceOperatorCompactCombine::vmult (:802-806, action 0).  dst must not alias src. */
+/* LaplaceOperatorCompactCombine::vmult (:802-806, action 0).  dst must not alias src.  2D operators: the cell loop
+ * of :1147 with the dim == 2 cell term (:1675) and faces (:1418), as the three entry points below. */
 int mgx_dg_vmult(mgx_dg_operator_t op, void *dst, const void *src);
 
 /* vmult_with_merged_ops<4> (:962-966, epilogue :1812-1818): dst = rhs - A src */
@@ -112,12 +122,13 @@ int mgx_dg_vmult_with_chebyshev_update(mgx_dg_operator_t op, const void *rhs, un
  *   alpha != 0:  x += alpha p ;  p = beta p + q      alpha == 0:  p = q
  *   q = A p ;  sums = { q.p, r.r, q.r, q.q }  summed over all ranks (host array)
  * The four sums come out of the cell kernel's epilogue (block sums added in a fixed order). */
+/* Not built for 2D operators (the plain solver does not run it): MGX_ERR_UNSUPPORTED. */
 int mgx_dg_vmult_with_cg_update(mgx_dg_operator_t op, double alpha, double beta, const void *r, void *q, void *p, void *x,
                                 double sums[4]);
 
 /* 1D data of the operator for inspection: hermite_derivative_on_face (:408-409), the penalty
  * parameters get_penalty(face 2d) (:789-793) and the 1D generalised eigenvalues (:207-208).
- * Any pointer may be NULL. */
+ * Any pointer may be NULL.  A 2D operator fills penalty[0..1] and leaves penalty[2] untouched. */
 int mgx_dg_operator_info(mgx_dg_operator_t op, double *hermite_derivative_on_face, double penalty[3],
                          double eigenvalues_1d[MGX_MAX_DEGREE + 1]);
 
@@ -148,7 +159,8 @@ typedef struct
    * entries), cfe is the decomposed FE_Q solver of the same partition, not agglomerated. */
   const uint32_t   *cell_global_id;
 } mgx_dg_solver_desc;
-/* ctor (:58-323), incl. smooth_dg.initialize: eigenvalue estimate with JacobiTransformed */
+/* ctor (:58-323), incl. smooth_dg.initialize: eigenvalue estimate with JacobiTransformed.  2D operators are refused
+ * with MGX_ERR_UNSUPPORTED: there is no FE_Q hierarchy in two dimensions (include/mgx.h). */
 int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_dg_solver_t *solver);
 int mgx_dg_solver_destroy(mgx_dg_solver_t solver);
 int mgx_dg_solver_smoother_info(mgx_dg_solver_t solver, mgx_smoother_info *info);
@@ -183,12 +195,16 @@ typedef struct
   /* host [n_coarse_cells][8], copied: fine cell that is child kx + 2 ky + 4 kz of a coarse cell; every fine cell
    * 0 .. 8 n_coarse_cells - 1 exactly once (checked) */
   const uint32_t *children;
+  /* 0 or 3: as above; 2: MGTransferMatrixFree<2,Number> -- children is [n_coarse_cells][4], child kx + 2 ky, every
+   * fine cell 0 .. 4 n_coarse_cells - 1 exactly once (checked).  Any other value: MGX_ERR_INVALID_ARGUMENT. */
+  int dim;
 } mgx_dg_transfer_desc;
 /* MGTransferMatrixFree::build: the 1D embedding of the parent's basis into the two children's, computed in double
- * from the operator's own 1D polynomials */
+ * from the operator's own 1D polynomials (the same matrix in two and three dimensions) */
 int mgx_dg_transfer_create(mgx_context_t ctx, const mgx_dg_transfer_desc *desc, mgx_dg_transfer_t *transfer);
 int mgx_dg_transfer_destroy(mgx_dg_transfer_t transfer);
-/* MGTransferMatrixFree::prolongate_and_add: fine[children[c][k]] += (P_kz (x) P_ky (x) P_kx) coarse[c] */
+/* MGTransferMatrixFree::prolongate_and_add: fine[children[c][k]] += (P_kz (x) P_ky (x) P_kx) coarse[c]; dim == 2:
+ * (P_ky (x) P_kx), here and below */
 int mgx_dg_transfer_prolongate_and_add(mgx_dg_transfer_t transfer, void *fine_dst, const void *coarse_src);
 /* MGTransferMatrixFree::restrict_and_add: coarse[c] += sum_k (P_kz (x) P_ky (x) P_kx)^T fine[children[c][k]]; DG has
  * neither weights nor constrained rows.  Both operations give the same bits in every run. */
@@ -212,7 +228,9 @@ typedef struct
   const uint32_t *const *cell_global_id;
 } mgx_dg_plain_solver_desc;
 /* ctor (:58-215): level vectors and smooth[level].initialize -- levels l > 0: range 20, 15 CG iterations; level 0:
- * range 1e-5, degree by Varga's rule, at most m() CG iterations (:204-209) */
+ * range 1e-5, degree by Varga's rule, at most m() CG iterations (:204-209).  The dimension is that of the operators
+ * (poisson_dg_plain/program.cc:65 runs dimension 2): all operators and transfers must share it, and a level has 2^dim
+ * times the cells of the one below. */
 int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc *desc, mgx_dg_plain_solver_t *solver);
 int mgx_dg_plain_solver_destroy(mgx_dg_plain_solver_t solver);
 int mgx_dg_plain_solver_smoother_info(mgx_dg_plain_solver_t solver, int level, mgx_smoother_info *info);
@@ -252,6 +270,12 @@ int mgx_dg_box_neighbours(const int cells[3], int ordering, int32_t *neighbours,
  * either numbered as mgx_dg_box_neighbours numbers them in the given ordering (Triangulation::refine_global):
  * children[c * 8 + kx + 2 ky + 4 kz] = fine cell at position 2 ijk(c) + (kx, ky, kz) */
 int mgx_dg_box_children(const int coarse_cells[3], int coarse_ordering, int fine_ordering, uint32_t *children);
+
+/* the same two tables for a box of cells[0] x cells[1] quadrilaterals: neighbours [n][4] (face 2d+s, d = 0, 1),
+ * cell_ij [n][2] (optional); ordering 0: lexicographic, 1: z-order over the two coordinates;
+ * children[c * 4 + kx + 2 ky] = fine cell at position 2 ij(c) + (kx, ky) */
+int mgx_dg_box_neighbours_2d(const int cells[2], int ordering, int32_t *neighbours, int32_t *cell_ij);
+int mgx_dg_box_children_2d(const int coarse_cells[2], int coarse_ordering, int fine_ordering, uint32_t *children);
 
 #ifdef __cplusplus
 }

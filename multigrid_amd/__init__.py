@@ -1151,24 +1151,28 @@ def dg_cheby_mesh(n_cell_steps):
 
 
 def dg_box_neighbours(cells, ordering="z"):
-    """(neighbour table [n, 6], cell positions [n, 3]) of a box of cells, all outer faces Dirichlet"""
-    c = (C.c_int * 3)(*cells)
+    """(neighbour table [n, 6], cell positions [n, 3]) of a box of cells, all outer faces Dirichlet; a 2-tuple of
+    cells gives the tables of a box of quadrilaterals, [n, 4] and [n, 2]"""
+    dim = len(cells)
+    c = (C.c_int * dim)(*cells)
     n = int(np.prod(cells))
-    nb = np.empty((n, 6), dtype=np.int32)
-    ijk = np.empty((n, 3), dtype=np.int32)
+    nb = np.empty((n, 2 * dim), dtype=np.int32)
+    ijk = np.empty((n, dim), dtype=np.int32)
     i32p = C.POINTER(C.c_int32)
-    check(_lib.load().mgx_dg_box_neighbours(C.byref(c), 1 if ordering == "z" else 0, nb.ctypes.data_as(i32p),
-                                            ijk.ctypes.data_as(i32p)))
+    fn = _lib.load().mgx_dg_box_neighbours_2d if dim == 2 else _lib.load().mgx_dg_box_neighbours
+    check(fn(C.byref(c), 1 if ordering == "z" else 0, nb.ctypes.data_as(i32p), ijk.ctypes.data_as(i32p)))
     return nb, ijk
 
 
 def dg_box_children(coarse_cells, coarse_ordering="z", fine_ordering="z"):
     """child table [n_coarse, 8] between a box of cells and its global refinement, both numbered as
-    dg_box_neighbours numbers them: entry kx + 2 ky + 4 kz is the fine cell at 2 ijk + (kx, ky, kz)"""
-    c = (C.c_int * 3)(*coarse_cells)
-    ch = np.empty((int(np.prod(coarse_cells)), 8), dtype=np.uint32)
-    check(_lib.load().mgx_dg_box_children(C.byref(c), 1 if coarse_ordering == "z" else 0, 1 if fine_ordering == "z" else 0,
-                                          ch.ctypes.data_as(_lib.u32p)))
+    dg_box_neighbours numbers them: entry kx + 2 ky + 4 kz is the fine cell at 2 ijk + (kx, ky, kz); a 2-tuple of
+    cells gives [n_coarse, 4], entry kx + 2 ky"""
+    dim = len(coarse_cells)
+    c = (C.c_int * dim)(*coarse_cells)
+    ch = np.empty((int(np.prod(coarse_cells)), 1 << dim), dtype=np.uint32)
+    fn = _lib.load().mgx_dg_box_children_2d if dim == 2 else _lib.load().mgx_dg_box_children
+    check(fn(C.byref(c), 1 if coarse_ordering == "z" else 0, 1 if fine_ordering == "z" else 0, ch.ctypes.data_as(_lib.u32p)))
     return ch
 
 
@@ -1249,18 +1253,22 @@ def dg_box_partition(cells, procs, rank, ordering="z"):
 
 class DGLaplaceOperator:
     """multigrid::LaplaceOperatorCompactCombine<3,p,Number,type> with its JacobiTransformed
-    preconditioner (common/laplace_operator_dg.h:350-2256) on an affine mesh."""
+    preconditioner (common/laplace_operator_dg.h:350-2256) on an affine mesh; dim=2: <2,p,Number,type> on
+    quadrilaterals (one rank)."""
 
-    def __init__(self, ctx, degree, basis, neighbours, jacobian, number=F32, n_ghost=0, exchange=None, plan_id=77):
+    def __init__(self, ctx, degree, basis, neighbours, jacobian, number=F32, n_ghost=0, exchange=None, plan_id=77, dim=3):
         """n_ghost / exchange: decomposed mesh as dg_box_partition() describes it (the context then
-        needs a Communicator)"""
+        needs a Communicator); dim: neighbours is [n, 2 dim], jacobian dim x dim"""
         self.ctx, self.lib = ctx, ctx.lib
-        self.degree, self.basis, self.number = degree, basis, number
-        nb = np.ascontiguousarray(neighbours, dtype=np.int32).reshape(-1, 6)
+        self.degree, self.basis, self.number, self.dim = degree, basis, number, dim
+        nb = np.ascontiguousarray(neighbours, dtype=np.int32).reshape(-1, 2 * dim)
         d = _lib.DGOperatorDesc()
         d.degree, d.basis, d.number, d.n_cells = degree, basis, number, nb.shape[0]
         d.neighbours = nb.ctypes.data_as(C.POINTER(C.c_int32))
-        d.jacobian = (C.c_double * 9)(*np.asarray(jacobian, dtype=float).ravel())
+        jac = np.zeros(9)
+        jac[:dim * dim] = np.asarray(jacobian, dtype=float).reshape(dim, dim).ravel()
+        d.jacobian = (C.c_double * 9)(*jac)
+        d.dim = 0 if dim == 3 else dim
         d.n_ghost_cells = n_ghost
         if n_ghost:
             k = len(exchange)
@@ -1335,7 +1343,7 @@ class DGLaplaceOperator:
         pen = (C.c_double * 3)()
         ev = (C.c_double * 10)()
         check(self.lib.mgx_dg_operator_info(self.h, C.byref(hd), pen, ev))
-        return dict(hermite_derivative_on_face=hd.value, penalty=np.array(pen),
+        return dict(hermite_derivative_on_face=hd.value, penalty=np.array(pen)[:self.dim],
                     eigenvalues_1d=np.array(ev)[:self.degree + 1])
 
     def clear(self):
@@ -1418,13 +1426,16 @@ class DGMultigridSolver:
 
 class DGLevelTransfer:
     """MGTransferMatrixFree between two DG levels of the same degree and basis (include/mgx_dg.h): a cell and
-    its eight children, `children` [n_coarse, 8] as dg_box_children() gives it."""
+    its eight children, `children` [n_coarse, 8] as dg_box_children() gives it; [n_coarse, 4]: a quadrilateral and its
+    four children."""
 
     def __init__(self, ctx, degree, basis, children, number=F32):
         self.ctx, self.lib = ctx, ctx.lib
         self.degree, self.basis, self.number = degree, basis, number
-        ch = np.ascontiguousarray(children, dtype=np.uint32).reshape(-1, 8)
-        d = _lib.DGTransferDesc(degree, basis, number, ch.shape[0], ch.ctypes.data_as(_lib.u32p))
+        ch = np.asarray(children)
+        self.dim = 2 if ch.ndim == 2 and ch.shape[1] == 4 else 3
+        ch = np.ascontiguousarray(ch, dtype=np.uint32).reshape(-1, 1 << self.dim)
+        d = _lib.DGTransferDesc(degree, basis, number, ch.shape[0], ch.ctypes.data_as(_lib.u32p), 0 if self.dim == 3 else self.dim)
         h = C.c_void_p()
         check(self.lib.mgx_dg_transfer_create(ctx.h, C.byref(d), C.byref(h)))
         self.h = h
@@ -1452,12 +1463,14 @@ class DGPlainMultigridSolver:
     """multigrid::MultigridSolverDGPlain<3,p,Number,double> (common/multigrid_solver_dg_plain.h:55-595) on a box of
     coarse_cells refined n_levels - 1 times: the DG-SIP operator on every level (cells 2^l per coarse cell and
     direction, Jacobian jacobian0 / 2^l), Chebyshev smoothers with the JacobiTransformed preconditioner, DG-to-DG
-    transfers, level 0 solved by its Chebyshev iteration; V-cycle in `vcycle_number`, outer CG in fp64."""
+    transfers, level 0 solved by its Chebyshev iteration; V-cycle in `vcycle_number`, outer CG in fp64.  A 2-tuple of
+    coarse_cells (and a 2 x 2 jacobian0) gives <2,p,Number,double>, the dimension poisson_dg_plain/program.cc:65 runs."""
 
     def __init__(self, ctx, degree, basis, coarse_cells, jacobian0, n_levels, degree_pre=3, vcycle_number=F32, ordering="z"):
         self.ctx, self.lib = ctx, ctx.lib
         self.degree, self.basis, self.n_levels, self.vnumber = degree, basis, n_levels, vcycle_number
-        jac0 = np.asarray(jacobian0, dtype=float).reshape(3, 3)
+        self.dim = dim = len(coarse_cells)
+        jac0 = np.asarray(jacobian0, dtype=float).reshape(dim, dim)
         self.cells, self.cell_ijk, self.cell_gid, self.matrix, self.transfer = [], [], [], [], []
         self.matrix_dg_dp = self.h = None
         try:
@@ -1467,10 +1480,11 @@ class DGPlainMultigridSolver:
                 self.cells.append(cells)
                 self.cell_ijk.append(ijk)
                 i64 = ijk.astype(np.int64)
-                self.cell_gid.append(np.ascontiguousarray(i64[:, 0] + cells[0] * (i64[:, 1] + cells[1] * i64[:, 2]), dtype=np.uint32))
-                self.matrix.append(DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, vcycle_number))
+                lex = i64[:, 0] + cells[0] * (i64[:, 1] + (cells[1] * i64[:, 2] if dim == 3 else 0))
+                self.cell_gid.append(np.ascontiguousarray(lex, dtype=np.uint32))
+                self.matrix.append(DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, vcycle_number, dim=dim))
                 if l == n_levels - 1:
-                    self.matrix_dg_dp = DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, F64)
+                    self.matrix_dg_dp = DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, F64, dim=dim)
                 if l > 0:
                     self.transfer.append(DGLevelTransfer(ctx, degree, basis, dg_box_children(self.cells[l - 1], ordering, ordering),
                                                          vcycle_number))

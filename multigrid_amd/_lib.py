@@ -59,7 +59,7 @@ class DGExchangeDesc(C.Structure):
 class DGOperatorDesc(C.Structure):
     _fields_ = [("degree", C.c_int), ("basis", C.c_int), ("number", C.c_int), ("n_cells", C.c_uint32),
                 ("neighbours", C.POINTER(C.c_int32)), ("jacobian", C.c_double * 9),
-                ("n_ghost_cells", C.c_uint32), ("exchange", C.POINTER(DGExchangeDesc))]
+                ("n_ghost_cells", C.c_uint32), ("exchange", C.POINTER(DGExchangeDesc)), ("dim", C.c_int)]
 
 
 class DGSolverDesc(C.Structure):
@@ -69,7 +69,7 @@ class DGSolverDesc(C.Structure):
 
 class DGTransferDesc(C.Structure):
     _fields_ = [("degree", C.c_int), ("basis", C.c_int), ("number", C.c_int), ("n_coarse_cells", C.c_uint32),
-                ("children", u32p)]
+                ("children", u32p), ("dim", C.c_int)]
 
 
 class DGPlainSolverDesc(C.Structure):
@@ -288,6 +288,8 @@ SIGNATURES = {
     "mgx_dg_box_children": (C.c_int, [C.POINTER(C.c_int * 3), C.c_int, C.c_int, u32p]),
     "mgx_dg_cheby_mesh": (C.c_int, [C.c_int, C.POINTER(C.c_int * 3), C.POINTER(C.c_double * 9)]),
     "mgx_dg_box_neighbours": (C.c_int, [C.POINTER(C.c_int * 3), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mgx_dg_box_neighbours_2d": (C.c_int, [C.POINTER(C.c_int * 2), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mgx_dg_box_children_2d": (C.c_int, [C.POINTER(C.c_int * 2), C.c_int, C.c_int, u32p]),
 }
 
 _lib = None

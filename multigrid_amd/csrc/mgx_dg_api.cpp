@@ -21,10 +21,11 @@ struct mgx_dg_operator_s
   mgx_context_t    ctx = nullptr;
   mgx::DeviceArena mem{"mgx_dg_operator"};
   int           degree = 0, basis = 0, number = MGX_F32;
+  int           dim = 3; // 2: quadrilaterals -- 4 faces, (p+1)^2 entries per cell, one rank
   uint32_t      n_cells = 0;
-  int32_t      *neigh   = nullptr; // device
+  int32_t      *neigh   = nullptr; // device [n_cells][2 dim]
   void         *consts  = nullptr; // device DGConst<T>
-  void         *inv_diag = nullptr; // device [64][(p+1)^3]
+  void         *inv_diag = nullptr; // device [4^dim][(p+1)^dim]
   Host1D        h;
   Geometry      g;
   // decomposed mesh: ghost cells behind the owned ones, filled from their owners before every
@@ -77,9 +78,10 @@ struct mgx_dg_transfer_s
   mgx_context_t       ctx = nullptr;
   mgx::DeviceArena    mem{"mgx_dg_transfer"};
   int                 degree = 0, basis = 0, number = MGX_F32;
+  int                 dim = 3;
   uint32_t            n_coarse = 0;
-  uint32_t           *children = nullptr; // device [n_coarse][8]
-  bool                identity = false;   // children[c][k] == 8 c + k (checked at creation): the table is not read
+  uint32_t           *children = nullptr; // device [n_coarse][2^dim]
+  bool                identity = false;   // children[c][k] == 2^dim c + k (checked at creation): the table is not read
   void               *p1d      = nullptr; // device [2][(p+1)^2], number type
   std::vector<double> p1d_host;
 };
@@ -111,6 +113,12 @@ namespace
   int dg_fail(int code, const std::string &msg) { return mgx::report_error(code, msg.c_str()); }
 
   size_t dg_nsz(int number) { return number == MGX_F64 ? 8 : 4; }
+
+  // entries of a cell: (p+1)^dim
+  uint64_t dg_cell_entries(int degree, int dim) { return dim == 2 ? (uint64_t)(degree + 1) * (degree + 1) : (uint64_t)(degree + 1) * (degree + 1) * (degree + 1); }
+
+  // the `dim` field of the descriptors: 0 and 3 mean three dimensions; -1: neither 0, 2 nor 3
+  int dg_desc_dim(int dim) { return dim == 0 || dim == 3 ? 3 : (dim == 2 ? 2 : -1); }
 
   // pack kernels on the context's stream; `overlap`: the exchange itself on the side stream, begun
   // behind the pack kernels -- the caller enqueues independent work and then calls ghosts_finish
@@ -154,7 +162,7 @@ namespace
 
   int launch_cells(mgx_dg_operator_t op, const DGLaunch &launch, hipStream_t stream = nullptr)
   {
-    const CellOperands o{op->number, op->degree, op->basis, op->neigh, op->consts, op->inv_diag, op->n_cells, op->n_ghost > 0};
+    const CellOperands o{op->number, op->degree, op->basis, op->neigh, op->consts, op->inv_diag, op->n_cells, op->n_ghost > 0, op->dim};
     return launch_dg_cells(stream ? stream : (hipStream_t)mgx_context_stream(op->ctx), o, launch);
   }
 
@@ -208,13 +216,18 @@ namespace
     if (desc->number != MGX_F32 && desc->number != MGX_F64)
       return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: number must be MGX_F32 or MGX_F64");
     MGX_REQUIRE(desc->n_cells != 0 && desc->neighbours, "mgx_dg_operator_create: empty mesh");
-    const uint64_t n3 = (uint64_t)(desc->degree + 1) * (desc->degree + 1) * (desc->degree + 1);
+    const int dim = dg_desc_dim(desc->dim);
+    if (dim < 0)
+      return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: dim must be 0 or 3 (three dimensions) or 2");
+    if (dim == 2 && desc->n_ghost_cells > 0)
+      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: 2D DG operator on one rank only");
+    const uint64_t n3 = dg_cell_entries(desc->degree, dim);
     if ((uint64_t)desc->n_cells * n3 * dg_nsz(desc->number) >= (1ull << 40))
       return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: vector larger than 1 TiB");
     const uint64_t n_all = (uint64_t)desc->n_cells + desc->n_ghost_cells;
     if (n_all * n3 >= (1ull << 32))
       return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: more than 2^32 vector entries per rank");
-    for (uint64_t i = 0; i < (uint64_t)desc->n_cells * 6; ++i)
+    for (uint64_t i = 0; i < (uint64_t)desc->n_cells * 2 * dim; ++i)
       if (desc->neighbours[i] != MGX_DG_BOUNDARY && (desc->neighbours[i] < 0 || (uint64_t)desc->neighbours[i] >= n_all))
         return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: neighbour entry " + std::to_string(i) +
                                                    " is neither a cell of the mesh, a ghost cell nor MGX_DG_BOUNDARY");
@@ -253,7 +266,8 @@ namespace
     std::string why;
     int         status = build_1d(desc->degree, desc->basis, op.h, why);
     if (status == MGX_OK)
-      status = build_geometry(desc->jacobian, desc->degree, op.g, why);
+      status = op.dim == 2 ? build_geometry_2d(desc->jacobian, desc->degree, op.g, why) // laplace_operator_dg.h:749-771, dim == 2
+                           : build_geometry(desc->jacobian, desc->degree, op.g, why);
     if (status != MGX_OK)
       return dg_fail(status, "mgx_dg_operator_create: " + why);
     // the even-odd line products of the cell kernel (mul_eo) rest on the reversal symmetry of the 1D
@@ -275,12 +289,14 @@ namespace
     return MGX_OK;
   }
 
-  // table[cat][(p+1)^3]: inverse of the transformed diagonal for every combination of Dirichlet faces (host)
+  // table[cat][(p+1)^dim]: inverse of the transformed diagonal for every combination of Dirichlet faces (host);
+  // 64 combinations of 6 faces, 16 of the 4 faces of a quadrilateral (JacobiTransformed, laplace_operator_dg.h:2162)
   int build_inverse_diagonal(const mgx_dg_operator_s &op, uint64_t n3, std::vector<double> &table)
   {
     std::vector<double> diag;
-    table.resize(64 * n3);
-    for (unsigned cat = 0; cat < 64; ++cat)
+    const unsigned      n_cat = 1u << (2 * op.dim);
+    table.resize(n_cat * n3);
+    for (unsigned cat = 0; cat < n_cat; ++cat)
       {
         transformed_diagonal(op.h, op.g, cat, diag);
         for (uint64_t i = 0; i < n3; ++i)
@@ -371,10 +387,12 @@ extern "C" {
 int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, mgx_dg_operator_t *out)
 {
   MGX_TRY(validate_dg_operator_desc(ctx, desc, out));
-  const uint64_t n3 = (uint64_t)(desc->degree + 1) * (desc->degree + 1) * (desc->degree + 1);
+  const int      dim = dg_desc_dim(desc->dim);
+  const uint64_t n3  = dg_cell_entries(desc->degree, dim);
   // failures below return through the destroy function, which frees what the operator's arena holds by then
   std::unique_ptr<mgx_dg_operator_s, int (*)(mgx_dg_operator_t)> op(new mgx_dg_operator_s, mgx_dg_operator_destroy);
   op->ctx     = ctx;
+  op->dim     = dim;
   op->degree  = desc->degree;
   op->basis   = desc->basis;
   op->number  = desc->number;
@@ -384,7 +402,7 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
   MGX_TRY(build_basis_and_geometry(*op, desc));
   std::vector<double> table;
   MGX_TRY(build_inverse_diagonal(*op, n3, table));
-  MGX_TRY(op->mem.upload(&op->neigh, desc->neighbours, 6 * (size_t)desc->n_cells));
+  MGX_TRY(op->mem.upload(&op->neigh, desc->neighbours, 2 * (size_t)dim * desc->n_cells));
   if (op->n_ghost > 0)
     {
       MGX_TRY(upload_exchange_plan(*op, desc));
@@ -413,12 +431,14 @@ uint64_t mgx_dg_operator_vector_size(mgx_dg_operator_t op)
 int mgx_dg_update_ghost_values(mgx_dg_operator_t op, void *vec)
 {
   MGX_REQUIRE(op && vec, "mgx_dg_update_ghost_values: null argument");
+  if (op->dim == 2)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_update_ghost_values: 2D DG operator on one rank only, there are no ghost cells");
   return update_ghosts(op, vec);
 }
 
 uint64_t mgx_dg_operator_n_dofs(mgx_dg_operator_t op)
 {
-  return op ? (uint64_t)op->n_cells * (op->degree + 1) * (op->degree + 1) * (op->degree + 1) : 0;
+  return op ? (uint64_t)op->n_cells * dg_cell_entries(op->degree, op->dim) : 0;
 }
 
 int mgx_dg_vmult(mgx_dg_operator_t op, void *dst, const void *src)
@@ -463,6 +483,9 @@ int mgx_dg_vmult_with_cg_update(mgx_dg_operator_t op, double alpha, double beta,
                                 double sums[4])
 {
   MGX_REQUIRE(op && r && q && p && x && sums && q != p, "mgx_dg_vmult_with_cg_update: null or aliased vectors");
+  if (op->dim == 2)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_vmult_with_cg_update: the merged CG iteration is not built for 2D DG operators "
+                                        "(the 2D cell kernel has no epilogue with the four sums)");
   hipStream_t    s      = (hipStream_t)mgx_context_stream(op->ctx);
   const bool     split  = op->n_ghost > 0 && op->n_interior > 0;
   const uint32_t blocks = split ? cell_grid(op->number, op->degree, op->n_interior) + cell_grid(op->number, op->degree, op->n_boundary)
@@ -502,7 +525,7 @@ int mgx_dg_operator_info(mgx_dg_operator_t op, double *hderiv, double penalty[3]
   if (hderiv)
     *hderiv = op->h.hderiv;
   if (penalty)
-    for (int d = 0; d < 3; ++d)
+    for (int d = 0; d < op->dim; ++d)
       penalty[d] = op->g.sigma[d];
   if (eigenvalues_1d)
     {
@@ -780,8 +803,12 @@ extern "C" {
 
 int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_dg_solver_t *out)
 {
-  MGX_REQUIRE(ctx && desc && out && desc->matrix_dg && desc->matrix_dg_dp && desc->cfe, "mgx_dg_solver_create: null argument");
+  MGX_REQUIRE(ctx && desc && out && desc->matrix_dg && desc->matrix_dg_dp, "mgx_dg_solver_create: null argument");
   mgx_dg_operator_t A = desc->matrix_dg, Ad = desc->matrix_dg_dp;
+  if (A->dim == 2 || Ad->dim == 2) // (before the FE_Q solver is looked at: none can exist for these operators)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: 2D DG operator -- there is no FE_Q hierarchy in two dimensions; "
+                                        "use mgx_dg_plain_solver_create");
+  MGX_REQUIRE(desc->cfe, "mgx_dg_solver_create: null argument");
   if (Ad->number != MGX_F64 || A->n_cells != Ad->n_cells || A->degree != Ad->degree || A->basis != Ad->basis)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_create: matrix_dg_dp must be the fp64 twin of matrix_dg");
   if (desc->degree_pre < 1)
@@ -1017,17 +1044,22 @@ int mgx_dg_transfer_create(mgx_context_t ctx, const mgx_dg_transfer_desc *desc, 
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: number must be MGX_F32 or MGX_F64");
   if (desc->n_coarse_cells == 0 || desc->n_coarse_cells >= (1u << 28))
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: n_coarse_cells must be in 1 .. 2^28 - 1");
+  const int dim = dg_desc_dim(desc->dim);
+  if (dim < 0)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: dim must be 0 or 3 (three dimensions) or 2");
   // every fine cell is the child of exactly one coarse cell: what lets the kernels write without atomics, and what
   // keeps every access inside the fine vector
-  const size_t      n_fine = 8 * (size_t)desc->n_coarse_cells;
+  const size_t      n_kids = (size_t)1 << dim;
+  const size_t      n_fine = n_kids * (size_t)desc->n_coarse_cells;
   std::vector<bool> seen(n_fine, false);
   bool              identity = true;
   for (size_t i = 0; i < n_fine; ++i)
     {
       const uint32_t f = desc->children[i];
       if (f >= n_fine || seen[f])
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: children must name every fine cell 0 .. 8 n_coarse_cells - 1 "
-                                                 "exactly once (entry " + std::to_string(i) + " = " + std::to_string(f) + ")");
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_transfer_create: children must name every fine cell 0 .. " +
+                                                   std::to_string(n_kids) + " n_coarse_cells - 1 exactly once (entry " +
+                                                   std::to_string(i) + " = " + std::to_string(f) + ")");
       seen[f]  = true;
       identity = identity && f == i;
     }
@@ -1038,6 +1070,7 @@ int mgx_dg_transfer_create(mgx_context_t ctx, const mgx_dg_transfer_desc *desc, 
     return dg_fail(status, "mgx_dg_transfer_create: " + why);
   std::unique_ptr<mgx_dg_transfer_s, int (*)(mgx_dg_transfer_t)> T(new mgx_dg_transfer_s, mgx_dg_transfer_destroy);
   T->ctx      = ctx;
+  T->dim      = dim;
   T->degree   = desc->degree;
   T->basis    = desc->basis;
   T->number   = desc->number;
@@ -1064,7 +1097,7 @@ int mgx_dg_transfer_prolongate_and_add(mgx_dg_transfer_t T, void *fine_dst, cons
 {
   MGX_REQUIRE(T && fine_dst && coarse_src && fine_dst != coarse_src, "mgx_dg_transfer_prolongate_and_add: null or aliased vectors");
   mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->degree, true, fine_dst, coarse_src, T->children,
-                          T->n_coarse, T->p1d, T->identity);
+                          T->n_coarse, T->p1d, T->identity, T->dim);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -1073,7 +1106,7 @@ int mgx_dg_transfer_restrict_and_add(mgx_dg_transfer_t T, void *coarse_dst, cons
 {
   MGX_REQUIRE(T && coarse_dst && fine_src && coarse_dst != fine_src, "mgx_dg_transfer_restrict_and_add: null or aliased vectors");
   mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->degree, false, coarse_dst, fine_src, T->children,
-                          T->n_coarse, T->p1d, T->identity);
+                          T->n_coarse, T->p1d, T->identity, T->dim);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -1108,6 +1141,9 @@ int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc
       if (A->degree != top->degree || A->basis != top->basis || A->number != top->number)
         return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
                                                    "] differs from the finest level in degree, basis or number type");
+      if (A->dim != top->dim)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) + "] has dimension " +
+                                                   std::to_string(A->dim) + ", the finest level " + std::to_string(top->dim));
       if (l == 0)
         continue;
       mgx_dg_transfer_t T = desc->transfer[l - 1];
@@ -1116,14 +1152,18 @@ int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc
       if (T->degree != top->degree || T->basis != top->basis || T->number != top->number || T->ctx != ctx)
         return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) +
                                                    "] differs from the operators in degree, basis, number type or context");
-      if (T->n_coarse != desc->matrix[l - 1]->n_cells || 8 * (uint64_t)desc->matrix[l - 1]->n_cells != A->n_cells)
+      if (T->dim != top->dim)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) + "] has dimension " +
+                                                   std::to_string(T->dim) + ", the operators " + std::to_string(top->dim));
+      if (T->n_coarse != desc->matrix[l - 1]->n_cells || ((uint64_t)desc->matrix[l - 1]->n_cells << top->dim) != A->n_cells)
         return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: level " + std::to_string(l) + " has " +
                                                    std::to_string(A->n_cells) + " cells, level " + std::to_string(l - 1) + " " +
                                                    std::to_string(desc->matrix[l - 1]->n_cells) + " and the transfer between them " +
-                                                   std::to_string(T->n_coarse) + " coarse cells (8 x coarse = fine required)");
+                                                   std::to_string(T->n_coarse) + " coarse cells (" + (top->dim == 2 ? "4" : "8") +
+                                                   " x coarse = fine required)");
     }
   if (Ad->number != MGX_F64 || Ad->n_cells != top->n_cells || Ad->degree != top->degree || Ad->basis != top->basis || Ad->n_ghost > 0 ||
-      Ad->ctx != ctx)
+      Ad->ctx != ctx || Ad->dim != top->dim)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix_dg_dp must be the fp64 twin of the finest matrix");
 
   std::unique_ptr<mgx_dg_plain_solver_s, int (*)(mgx_dg_plain_solver_t)> S(new mgx_dg_plain_solver_s, mgx_dg_plain_solver_destroy);

@@ -525,6 +525,7 @@ namespace mgx::dg
       for (int c = 0; c < 3; ++c)
         G[a][c] = inv[a][0] * inv[c][0] + inv[a][1] * inv[c][1] + inv[a][2] * inv[c][2];
     const double ad = std::abs(det);
+    g.dim  = 3;
     g.K[0] = ad * G[0][0];
     g.K[1] = ad * G[1][1];
     g.K[2] = ad * G[2][2];
@@ -542,8 +543,71 @@ namespace mgx::dg
     return MGX_OK;
   }
 
+  int build_geometry_2d(const double J[4], int p, Geometry &g, std::string &why)
+  {
+    g = Geometry{};
+    g.dim = 2;
+    for (int i = 0; i < 4; ++i)
+      if (!std::isfinite(J[i]))
+        {
+          why = "cell Jacobian with an entry that is not finite";
+          return MGX_ERR_INVALID_ARGUMENT;
+        }
+    const double det = J[0] * J[3] - J[1] * J[2];
+    if (!(det > 0) || !std::isfinite(det))
+      {
+        why = "cell Jacobian with a determinant that is not positive";
+        return MGX_ERR_INVALID_ARGUMENT;
+      }
+    // inv[a][i] = d xi_a / d x_i
+    const double inv[2][2] = {{J[3] / det, -J[1] / det}, {-J[2] / det, J[0] / det}};
+    double       G[2][2];
+    for (int a = 0; a < 2; ++a)
+      for (int c = 0; c < 2; ++c)
+        G[a][c] = inv[a][0] * inv[c][0] + inv[a][1] * inv[c][1];
+    g.K[0] = det * G[0][0];
+    g.K[1] = det * G[1][1];
+    g.K[2] = det * G[0][1];
+    for (int d = 0; d < 2; ++d)
+      {
+        const double nrm = std::sqrt(G[d][d]);
+        for (int a = 0; a < 2; ++a)
+          g.cn[d][a] = G[d][a] / nrm;
+        g.fw[d]    = det * nrm;
+        g.sigma[d] = double(p + 1) * (p + 1) * std::abs(g.cn[d][d]); // penalty_factor = 1 (:47)
+      }
+    return MGX_OK;
+  }
+
+  namespace
+  {
+    void transformed_diagonal_2d(const Host1D &h, const Geometry &g, unsigned cat, std::vector<double> &diag)
+    {
+      const int n = h.n;
+      diag.assign((size_t)n * n, 0.0);
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i)
+          {
+            const int e[2] = {i, j};
+            double    v    = g.K[0] * h.lt[i] + g.K[1] * h.lt[j] + 2 * g.K[2] * h.ct[i] * h.ct[j];
+            for (int f = 0; f < 4; ++f)
+              {
+                const int    d = f / 2, s = f % 2;
+                const double fbnd = (cat >> f) & 1u ? 1.0 : 0.5;
+                const double sgn  = s ? 1.0 : -1.0;
+                const double be = h.beta[s][e[d]], ga = h.gamma[s][e[d]];
+                const double vn = g.cn[d][d] * be * ga + g.cn[d][1 - d] * be * be * h.ct[e[1 - d]];
+                v += g.fw[d] * (2 * fbnd * g.sigma[d] * be * be - 2 * fbnd * sgn * vn);
+              }
+            diag[j * n + i] = v;
+          }
+    }
+  } // namespace
+
   void transformed_diagonal(const Host1D &h, const Geometry &g, unsigned cat, std::vector<double> &diag)
   {
+    if (g.dim == 2)
+      return transformed_diagonal_2d(h, g, cat, diag);
     const int n = h.n;
     diag.assign((size_t)n * n * n, 0.0);
     for (int k = 0; k < n; ++k)
@@ -660,6 +724,79 @@ int mgx_dg_box_children(const int coarse_cells[3], int coarse_ordering, int fine
         const size_t x = 2 * (size_t)cijk[3 * (size_t)c] + (k & 1), y = 2 * (size_t)cijk[3 * (size_t)c + 1] + ((k >> 1) & 1),
                      z = 2 * (size_t)cijk[3 * (size_t)c + 2] + (k >> 2);
         children[8 * (size_t)c + k] = at[x + fine_cells[0] * (y + fine_cells[1] * z)];
+      }
+  return MGX_OK;
+}
+
+namespace
+{
+  // numbering of a box of two dimensions: order[c] = lexicographic position of cell c (x fastest)
+  std::vector<uint32_t> box_order_2d(const int cells[2], int ordering)
+  {
+    const uint64_t        n = (uint64_t)cells[0] * cells[1];
+    std::vector<uint32_t> order(n);
+    std::iota(order.begin(), order.end(), 0u);
+    if (ordering == 1)
+      {
+        auto spread = [](uint64_t v) { // bits of v to every second position
+          uint64_t r = 0;
+          for (int bit = 0; bit < 31; ++bit)
+            r |= ((v >> bit) & 1ull) << (2 * bit);
+          return r;
+        };
+        std::vector<uint64_t> key(n);
+        for (uint32_t c = 0; c < n; ++c)
+          key[c] = spread(c % cells[0]) | (spread(c / cells[0]) << 1);
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
+      }
+    return order;
+  }
+} // namespace
+
+int mgx_dg_box_neighbours_2d(const int cells[2], int ordering, int32_t *neighbours, int32_t *cell_ij)
+{
+  if (!cells || !neighbours || cells[0] < 1 || cells[1] < 1)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_box_neighbours_2d: invalid argument");
+  const uint64_t n = (uint64_t)cells[0] * cells[1];
+  if (n >= (1ull << 31))
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_dg_box_neighbours_2d: more than 2^31 cells");
+  const std::vector<uint32_t> order = box_order_2d(cells, ordering);
+  std::vector<uint32_t>       position(n);
+  for (uint32_t c = 0; c < n; ++c)
+    position[order[c]] = c;
+  const uint64_t stride[2] = {1, (uint64_t)cells[0]};
+  for (uint32_t c = 0; c < n; ++c)
+    {
+      const int p[2] = {(int)(order[c] % cells[0]), (int)(order[c] / cells[0])};
+      for (int d = 0; d < 2; ++d)
+        {
+          if (cell_ij)
+            cell_ij[(size_t)c * 2 + d] = p[d];
+          neighbours[(size_t)c * 4 + 2 * d] = p[d] > 0 ? (int32_t)position[order[c] - stride[d]] : MGX_DG_BOUNDARY;
+          neighbours[(size_t)c * 4 + 2 * d + 1] =
+            p[d] + 1 < cells[d] ? (int32_t)position[order[c] + stride[d]] : MGX_DG_BOUNDARY;
+        }
+    }
+  return MGX_OK;
+}
+
+int mgx_dg_box_children_2d(const int coarse_cells[2], int coarse_ordering, int fine_ordering, uint32_t *children)
+{
+  if (!coarse_cells || !children || coarse_cells[0] < 1 || coarse_cells[1] < 1)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_box_children_2d: invalid argument");
+  const uint64_t nc = (uint64_t)coarse_cells[0] * coarse_cells[1];
+  if (4 * nc >= (1ull << 31))
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_dg_box_children_2d: more than 2^31 fine cells");
+  const int                   fine_cells[2] = {2 * coarse_cells[0], 2 * coarse_cells[1]};
+  const std::vector<uint32_t> corder = box_order_2d(coarse_cells, coarse_ordering), forder = box_order_2d(fine_cells, fine_ordering);
+  std::vector<uint32_t>       at(4 * (size_t)nc); // lexicographic position of a fine cell -> its number
+  for (uint32_t f = 0; f < 4 * nc; ++f)
+    at[forder[f]] = f;
+  for (uint32_t c = 0; c < nc; ++c)
+    for (int k = 0; k < 4; ++k)
+      {
+        const size_t x = 2 * (size_t)(corder[c] % coarse_cells[0]) + (k & 1), y = 2 * (size_t)(corder[c] / coarse_cells[0]) + (k >> 1);
+        children[4 * (size_t)c + k] = at[x + fine_cells[0] * y];
       }
   return MGX_OK;
 }

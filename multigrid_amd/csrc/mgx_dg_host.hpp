@@ -35,14 +35,22 @@ namespace mgx::dg
   // 1D data of degree p in the basis MGX_DG_*; a status of include/mgx.h, with the reason in `why` on failure
   int build_1d(int p, int basis, Host1D &h, std::string &why);
 
+  // K = det J * J^-1 J^-T (dim 3: xx yy zz xy xz yz; dim 2: xx yy xy), cn[d][a] = n_d . grad xi_a with n_d the unit
+  // normal towards +xi_d, fw[d] the face JxW without the quadrature weight, sigma[d] the penalty; entries of
+  // directions >= dim are zero
   struct Geometry
   {
     double K[6], cn[3][3], fw[3], sigma[3];
+    int    dim = 3;
   };
 
   int build_geometry(const double J[9], int p, Geometry &g, std::string &why);
+  // the same for a cell of two dimensions, J row-major 2 x 2 (laplace_operator_dg.h:749-771 with dim == 2); refused
+  // unless every entry is finite and the determinant positive
+  int build_geometry_2d(const double J[4], int p, Geometry &g, std::string &why);
 
   // diagonal of T^T A_KK T for one combination of Dirichlet faces (bit f of cat): Kronecker
-  // products of 1D forms in the eigenvector basis, in which the mass matrix is the identity
+  // products of 1D forms in the eigenvector basis, in which the mass matrix is the identity.
+  // g.dim == 2: 16 categories of (p+1)^2 entries (JacobiTransformed, laplace_operator_dg.h:2162)
   void transformed_diagonal(const Host1D &h, const Geometry &g, unsigned cat, std::vector<double> &diag);
 } // namespace mgx::dg

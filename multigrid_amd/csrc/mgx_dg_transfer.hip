@@ -12,6 +12,11 @@
 // cell is a child of exactly one parent (checked by the host when the transfer is created): no atomics, no colours,
 // the same bits in every run.  The two matrices sit in LDS: they are wave-uniform, but 2 (p+1)^2 entries do not fit the
 // scalar registers from p = 7 on, and a thread addresses them with compile-time offsets.
+//
+// Two dimensions (MGTransferMatrixFree<2,Number>, as poisson_dg_plain/program.cc:65 runs it): the sibling kernel
+// dg_transfer_kernel_2d with a 2 x 2 tile of (2(p+1))^2 values per parent, two sweeps, four children.  A parent has
+// only p+1 lines in the first sweep, so a workgroup takes as many parents as 4096 tile values admit, at most 64:
+// 64 parents for p = 1 ... 3 (256 x-lines at p = 3), then 40, 28, 20, 16, 12, 10 for p = 4 ... 9.
 #include "mgx_internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -170,6 +175,118 @@ namespace mgx
         }
     }
 
+    // ---- two dimensions ----
+    template <int P, typename T>
+    struct DGTransferCfg2
+    {
+      static constexpr int N = P + 1, M = 2 * N;
+      static constexpr int MP      = M + 1; // row pitch, odd: y-lines of neighbouring columns on different banks
+      static constexpr int TILE    = M * MP;
+      static constexpr int NN      = N * N;
+      static constexpr int THREADS = 256;
+      // parents per workgroup: tiles of at most 4096 values together, at most 64 (36 KiB of LDS at p = 3 in fp64, the largest)
+      static constexpr int PPB = 4096 / (M * M) > 64 ? 64 : 4096 / (M * M);
+    };
+
+    // the lines of one sweep direction over the parents of the workgroup.  DIR 0: x lines (j < N), 1: y lines (i' < M)
+    template <int P, typename T, bool PROLONG, int DIR>
+    __device__ __forceinline__ void transfer_sweep_2d(T *__restrict__ tile, const T *__restrict__ mat, const int n_parents)
+    {
+      using C              = DGTransferCfg2<P, T>;
+      constexpr int N      = C::N, M = C::M, MP = C::MP;
+      constexpr int count  = DIR == 0 ? N : M;
+      constexpr int stride = DIR == 0 ? 1 : MP;
+      for (int it = threadIdx.x; it < n_parents * count; it += C::THREADS)
+        {
+          const int pp = it / count, l = it - pp * count;
+          const int base = DIR == 0 ? l * MP : l;
+          int       mat_offset = 0; // (see transfer_sweep)
+          asm volatile("" : "+v"(mat_offset));
+          transfer_line<N, T, PROLONG>(tile + pp * C::TILE + base, stride, mat + mat_offset);
+        }
+    }
+
+    template <int P, typename T, bool PROLONG>
+    __global__ void __launch_bounds__((DGTransferCfg2<P, T>::THREADS), 2)
+      dg_transfer_kernel_2d(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *__restrict__ children,
+                            const uint32_t n_coarse, const T *__restrict__ p1d, const int identity)
+    {
+      using C         = DGTransferCfg2<P, T>;
+      constexpr int N = C::N, MP = C::MP, NN = C::NN;
+      __shared__ T  tile[C::PPB * C::TILE];
+      __shared__ T  mat[2 * N * N];
+      const int      tid       = threadIdx.x;
+      const uint32_t first     = blockIdx.x * (uint32_t)C::PPB;
+      const int      n_parents = (int)min((uint32_t)C::PPB, n_coarse - first); // >= 1: the grid covers n_coarse
+
+      for (int i = tid; i < 2 * N * N; i += C::THREADS)
+        mat[i] = p1d[i];
+
+      // tile position of entry `local` of child k (x fastest in both)
+      auto fine_slot = [](const int k, const int local) {
+        const int lx = local % N, ly = local / N;
+        return ((k >> 1) * N + ly) * MP + (k & 1) * N + lx;
+      };
+      auto child_cell = [&](const uint32_t parent, const int k) {
+        return identity ? 4u * parent + (uint32_t)k : children[4 * (size_t)parent + k];
+      };
+
+      if (PROLONG)
+        {
+#pragma unroll 4
+          for (int it = tid; it < n_parents * NN; it += C::THREADS)
+            {
+              const int pp = it / NN, local = it - pp * NN;
+              tile[pp * C::TILE + fine_slot(0, local)] = src[(size_t)(first + pp) * NN + local];
+            }
+          __syncthreads();
+          transfer_sweep_2d<P, T, true, 0>(tile, mat, n_parents);
+          __syncthreads();
+          transfer_sweep_2d<P, T, true, 1>(tile, mat, n_parents);
+          __syncthreads();
+#pragma unroll 4
+          for (int it = tid; it < n_parents * 4 * NN; it += C::THREADS)
+            {
+              const int pp = it / (4 * NN), rem = it - pp * 4 * NN, k = rem / NN, local = rem - k * NN;
+              dst[(size_t)child_cell(first + pp, k) * NN + local] += tile[pp * C::TILE + fine_slot(k, local)];
+            }
+        }
+      else
+        {
+#pragma unroll 4
+          for (int it = tid; it < n_parents * 4 * NN; it += C::THREADS)
+            {
+              const int pp = it / (4 * NN), rem = it - pp * 4 * NN, k = rem / NN, local = rem - k * NN;
+              tile[pp * C::TILE + fine_slot(k, local)] = src[(size_t)child_cell(first + pp, k) * NN + local];
+            }
+          __syncthreads();
+          transfer_sweep_2d<P, T, false, 1>(tile, mat, n_parents);
+          __syncthreads();
+          transfer_sweep_2d<P, T, false, 0>(tile, mat, n_parents);
+          __syncthreads();
+#pragma unroll 4
+          for (int it = tid; it < n_parents * NN; it += C::THREADS)
+            {
+              const int pp = it / NN, local = it - pp * NN;
+              dst[(size_t)(first + pp) * NN + local] += tile[pp * C::TILE + fine_slot(0, local)];
+            }
+        }
+    }
+
+    template <int P, typename T>
+    void dg_transfer_2d_t(hipStream_t s, bool prolong, void *dst, const void *src, const uint32_t *children, uint32_t n_coarse,
+                          const void *p1d, bool identity)
+    {
+      using C           = DGTransferCfg2<P, T>;
+      const uint32_t nb = (n_coarse + C::PPB - 1) / C::PPB;
+      if (prolong)
+        hipLaunchKernelGGL((dg_transfer_kernel_2d<P, T, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst, (const T *)src, children,
+                           n_coarse, (const T *)p1d, identity ? 1 : 0);
+      else
+        hipLaunchKernelGGL((dg_transfer_kernel_2d<P, T, false>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst, (const T *)src, children,
+                           n_coarse, (const T *)p1d, identity ? 1 : 0);
+    }
+
     template <int P, typename T>
     void dg_transfer_t(hipStream_t s, bool prolong, void *dst, const void *src, const uint32_t *children, uint32_t n_coarse,
                        const void *p1d, bool identity)
@@ -186,10 +303,18 @@ namespace mgx
   } // namespace
 
   void launch_dg_transfer(hipStream_t s, int number, int p, bool prolong, void *dst, const void *src, const uint32_t *children,
-                          uint32_t n_coarse, const void *p1d, bool identity)
+                          uint32_t n_coarse, const void *p1d, bool identity, int dim)
   {
     if (n_coarse == 0)
       return;
+    if (dim == 2)
+      {
+        if (number == 1)
+          dispatch_degree(p, [&](auto P) { dg_transfer_2d_t<P.value, double>(s, prolong, dst, src, children, n_coarse, p1d, identity); });
+        else
+          dispatch_degree(p, [&](auto P) { dg_transfer_2d_t<P.value, float>(s, prolong, dst, src, children, n_coarse, p1d, identity); });
+        return;
+      }
     if (number == 1)
       {
         dispatch_degree(p, [&](auto P) { dg_transfer_t<P.value, double>(s, prolong, dst, src, children, n_coarse, p1d, identity); });

@@ -539,9 +539,10 @@ namespace mgx
                              const uint32_t *idx27, uint32_t n_cells, const void *P1, bool eight_colours = false);
   // DG <-> DG transfer between a level and its refinement (mgx_dg_transfer.hip): prolong: fine += P coarse, else
   // coarse += P^T fine; children [n_coarse][8] names every fine cell exactly once (the caller has checked it);
-  // p1d [2][(p+1)^2] in the number type; identity: children[c][k] == 8 c + k, the table is not read
+  // p1d [2][(p+1)^2] in the number type; identity: children[c][k] == 8 c + k, the table is not read.  dim == 2: a cell
+  // and its four children, children [n_coarse][4], identity: children[c][k] == 4 c + k
   void launch_dg_transfer(hipStream_t s, int number, int p, bool prolong, void *dst, const void *src, const uint32_t *children,
-                          uint32_t n_coarse, const void *p1d, bool identity);
+                          uint32_t n_coarse, const void *p1d, bool identity, int dim = 3);
   // ---- DG cell kernel (mgx_dg_kernels.hip): what it offers the host code of mgx_dg_api.cpp ----
   namespace dg
   {
@@ -564,9 +565,10 @@ namespace mgx
       int            number = 0, degree = 0, basis = 0;
       const int32_t *neigh    = nullptr;
       const void    *consts   = nullptr;
-      const void    *inv_diag = nullptr; // [64][(p+1)^3]
+      const void    *inv_diag = nullptr; // [4^dim][(p+1)^dim]
       uint32_t       n_owned  = 0;       // owned cells of the operator: neighbour entries >= n_owned are ghosts
       bool           has_ghosts = false;
+      int            dim        = 3;     // 2: quadrilaterals, neigh [n_cells][4] (mgx_dg_kernels_2d.hip)
     };
 
     // one launch of the cell kernel; vectors and P1 in the operator's number type
@@ -591,7 +593,11 @@ namespace mgx
     };
     // a status of include/mgx.h: MGX_ERR_UNSUPPORTED for a degree, basis or action no kernel is built for
     int      launch_dg_cells(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
-    uint32_t cell_grid(int number, int p, uint32_t n_cells); // workgroups of a launch over n_cells cells
+    uint32_t cell_grid(int number, int p, uint32_t n_cells, int dim = 3); // workgroups of a launch over n_cells cells
+    // the cell kernel of two dimensions (mgx_dg_kernels_2d.hip), reached through the two functions above: actions
+    // kVmult, kResidual, kChebyshev and kJacobi; false: no kernel for this degree, basis or action
+    bool     launch_dg_cells_2d(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
+    uint32_t cell_grid_2d(int number, int p, uint32_t n_cells);
     // the constant block of the cell kernel in the number type, from the host data
     std::vector<char> const_block(int number, const Host1D &h, const Geometry &g);
     // ghost exchange: whole cells / (Hermite-like basis) value and normal derivative on face faces[c] of cells[c]

@@ -2,7 +2,10 @@
 warm, against the DG <-> FE_Q transfers of MultigridSolverDG (mgx_dg_prolongate_add_cg_to_dg / mgx_dg_restrict_to_cg)
 on the same fine cells in the same process, and as a fraction of a streaming ceiling.
 
-    python tools/dg_transfer_time.py [degree=4] [n_refine=6] [--number f32|f64] [--repeat 20] [--ceiling 4.9e12]
+    python tools/dg_transfer_time.py [degree=4] [n_refine=6] [--number f32|f64] [--repeat 20] [--ceiling 4.9e12] [--dim 2]
+
+--dim 2: the 2D transfers alone, on 4^n_refine fine cells in forest order (there is no FE_Q partner in 2D): 2 1/4
+accesses per fine DoF for the prolongation, 1 1/2 for the restriction.
 
 Fine mesh: 2^n_refine cells per direction (the cube provider's finest level, forest order: children[c][k] = 8 c + k).
 Bytes per call: prolongation reads and writes the fine vector and reads the coarse one (2 1/8 accesses per fine DoF),
@@ -43,9 +46,27 @@ def main():
     ap.add_argument("--number", choices=["f32", "f64"], default="f64")
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--ceiling", type=float, default=4.9e12)
+    ap.add_argument("--dim", type=int, choices=[2, 3], default=3)
     a = ap.parse_args()
     number, es = (mg.F32, 4) if a.number == "f32" else (mg.F64, 8)
     ctx = mg.Context(0)
+    if a.dim == 2:
+        p, n2 = a.degree, (a.degree + 1) ** 2
+        n_fine_cells = 4 ** a.n_refine
+        n_fine, n_coarse = n_fine_cells * n2, n_fine_cells // 4 * n2
+        T = mg.DGLevelTransfer(ctx, p, mg.DG_HERMITE, np.arange(n_fine_cells, dtype=np.uint32).reshape(-1, 4), number)
+        rng = np.random.default_rng(0)
+        fine = ctx.vector(n_fine, number, rng.standard_normal(n_fine))
+        coarse = ctx.vector(n_coarse, number, rng.standard_normal(n_coarse))
+        print("FE_DGQHermite(%d) in 2D, %d fine cells, %d fine DoFs, %s" % (p, n_fine_cells, n_fine, a.number))
+        for name, fn, nbytes in (("dg->dg prolongate_and_add 2D", lambda: T.prolongate_and_add(fine, coarse), es * (2 * n_fine + n_coarse)),
+                                 ("dg->dg restrict_and_add 2D", lambda: T.restrict_and_add(coarse, fine), es * (n_fine + 2 * n_coarse))):
+            best, med = timed(ctx, fn, a.repeat)
+            print("%-34s best %9.2f us  median %9.2f us  %7.3f TB/s  %5.1f %% of the %.1f TB/s copy ceiling"
+                  % (name, best * 1e6, med * 1e6, nbytes / best * 1e-12, 100 * nbytes / best / a.ceiling, a.ceiling * 1e-12))
+        T.clear()
+        ctx.close()
+        return
     p, n3 = a.degree, (a.degree + 1) ** 3
     cube = mg.Cube(p, 1, a.n_refine)
     hybrid = mg.DGMultigridSolver(ctx, cube, mg.DG_HERMITE, 3, number)

@@ -5,7 +5,10 @@ transfers, level 0 (the single cell) solved by its Chebyshev iteration; fp32 V-c
 The same problem, printed lines and table row as tools/poisson_dg.py, whose solver it is the A/B partner of.
 
     python tools/poisson_dg_plain.py [degree=3] [n_refine=5] [n_pre_smooth=3] [tolerance=1e-9] [--vcycle f32|f64]
-                                     [--basis 0|1|2] [--solution reference|vanishing] [--levels]
+                                     [--basis 0|1|2] [--solution reference|vanishing] [--levels] [--dim 2|3]
+
+--dim 2: the dimension the reference's driver is compiled for (poisson_dg_plain/program.cc:65): the square [-0.9, 1]^2,
+rhs dim (3 pi)^2 prod sin(3 pi x_d) (program.cc:140), the same printed lines and table row.
 
 One line per level gives the smoother's degree, lambda_max and the CG iterations of its eigenvalue estimate.
 --levels: one more solve with the solver's per-level timers on, and the table of the reference's print_wall_times
@@ -37,14 +40,16 @@ def main():
     ap.add_argument("--basis", type=int, default=0)
     ap.add_argument("--solution", choices=["reference", "vanishing"], default="reference")
     ap.add_argument("--levels", action="store_true", help="per-level time table of one more (synchronised) solve")
+    ap.add_argument("--dim", type=int, choices=[2, 3], default=3)
     a = ap.parse_args()
     vnum = mg.F32 if a.vcycle == "f32" else mg.F64
     t0 = time.time()
     ctx = mg.Context(0)
     n_levels = a.n_refine + 1
-    solver = mg.DGPlainMultigridSolver(ctx, a.degree, a.basis, (1, 1, 1), np.eye(3) * 1.9, n_levels, a.n_pre_smooth, vnum)
+    dim = a.dim
+    solver = mg.DGPlainMultigridSolver(ctx, a.degree, a.basis, (1,) * dim, np.eye(dim) * 1.9, n_levels, a.n_pre_smooth, vnum)
     n = solver.m()
-    nc = n // (a.degree + 1) ** 3
+    nc = n // (a.degree + 1) ** dim
     print("Number of degrees of freedom: %d (%d cells, FE_DGQHermite(%d) on every one of %d levels, V-cycle in %s)"
           % (n, nc, a.degree, n_levels, a.vcycle))
     for l in range(n_levels):
@@ -53,17 +58,19 @@ def main():
               % (l, int(np.prod(solver.cells[l])), i["degree"], i["lambda_max"], i["cg_its"]))
     S, xq, wq = solver.matrix_dg_dp.basis_1d()
     h = 1.9 / 2 ** a.n_refine
-    S3 = np.kron(S, np.kron(S, S))
-    w3 = np.kron(wq, np.kron(wq, wq)) * h ** 3
-    ref = np.stack(np.meshgrid(xq, xq, xq, indexing="ij"), axis=-1)[..., ::-1].reshape(-1, 3)  # (k, j, i) order
+    S3, w3 = S, wq                                           # tensor products over the dim directions, x fastest
+    for _ in range(dim - 1):
+        S3, w3 = np.kron(S, S3), np.kron(wq, w3)
+    w3 = w3 * h ** dim
+    ref = np.stack(np.meshgrid(*([xq] * dim), indexing="ij"), axis=-1)[..., ::-1].reshape(-1, dim)  # (k, j, i) order
     x = -0.9 + h * (solver.cell_ijk[-1].astype(float)[:, None, :] + ref[None, :, :])
     if a.solution == "reference":
         u = np.prod(np.sin(np.pi * WAVE * x), axis=-1)
-        f = 3 * (np.pi * WAVE) ** 2 * u
+        f = dim * (np.pi * WAVE) ** 2 * u
     else:
         k = np.pi * WAVE / 1.9
         u = np.prod(np.sin(k * (x + 0.9)), axis=-1)
-        f = 3 * k ** 2 * u
+        f = dim * k ** 2 * u
     rhs = (f * w3) @ S3                                      # multigrid_solver_dg_plain.h:163-185
     print("Time setup                    %.3f s   rhs_norm = %.6e" % (time.time() - t0, np.sqrt(float(np.sum(rhs ** 2)))))
     b, sol = solver.initialize_dof_vector(rhs.ravel()), solver.initialize_dof_vector()
@@ -77,7 +84,7 @@ def main():
         time_cg = min(time_cg, dt)
         print("Time solve CG                 %.6f s   (%d iterations, reduction %.4e)" % (dt, its, red))
     uh = sol.download()[:n].reshape(nc, -1) @ S3.T
-    l2 = np.sqrt(float(np.sum(w3 * (uh - u) ** 2)) / (nc * h ** 3))
+    l2 = np.sqrt(float(np.sum(w3 * (uh - u) ** 2)) / (nc * h ** dim))
     if a.levels:
         solver.enable_timings(True)
         solver.solve_cg(b, sol, a.tolerance)
