@@ -126,6 +126,22 @@ int mgx_dg_vmult_with_chebyshev_update(mgx_dg_operator_t op, const void *rhs, un
 int mgx_dg_vmult_with_cg_update(mgx_dg_operator_t op, double alpha, double beta, const void *r, void *q, void *p, void *x,
                                 double sums[4]);
 
+/* The preconditioner of solver_dg/program.cc:134-148, the inverse of the lumped mass matrix: the mesh has one cell
+ * Jacobian, so it is one table of (p+1)^dim numbers,
+ *   1 / lumped[i],  lumped[i] = |det J| prod_d sum_q w_q phi_{i_d}(x_q)   ((p+1)-point Gauss rule, x fastest),
+ * computed in double when the operator is created and kept on the device in the operator's number type.  `table`: host
+ * array of (p+1)^dim entries.  An entry is not positive and finite where the lumped mass is not (none of the three
+ * bases at p = 1 .. 9); mgx_dg_pcg_solver_create then refuses the operator.  Works in 3D and 2D. */
+int mgx_dg_operator_lumped_mass_inverse(mgx_dg_operator_t op, double *table);
+
+/* The operator's part of one merged iteration of that preconditioned CG (solver_dg/program.cc:222-263; action
+ * kPcgSums of both cell kernels):
+ *   q = A p ;  sums = { q.p, r.(m r), q.(m r), q.(m q) }  summed over all ranks (host array)
+ * with m the table above at every entry's local index.  The sums are formed in double in the cell kernel's epilogue
+ * and added in a fixed order: the same bits in every run.  r and p are not written (but for p's ghost part, as in
+ * every application); q must alias neither.  3D, decomposed or not, and 2D. */
+int mgx_dg_vmult_with_pcg_sums(mgx_dg_operator_t op, const void *r, void *q, const void *p, double sums[4]);
+
 /* 1D data of the operator for inspection: hermite_derivative_on_face (:408-409), the penalty
  * parameters get_penalty(face 2d) (:789-793) and the 1D generalised eigenvalues (:207-208).
  * Any pointer may be NULL.  A 2D operator fills penalty[0..1] and leaves penalty[2] untouched. */
@@ -254,6 +270,50 @@ int mgx_dg_plain_solver_get_timings(mgx_dg_plain_solver_t solver, double *times)
  * own vectors (timing aids) */
 int mgx_dg_plain_solver_do_matvec(mgx_dg_plain_solver_t solver);
 int mgx_dg_plain_solver_do_matvec_smoother(mgx_dg_plain_solver_t solver);
+
+/* ---- conjugate gradients on the DG operator alone, preconditioned by the inverse lumped mass matrix: the solver of
+ * solver_dg/program.cc (SolverCG with IterationNumberControl, :177-178; DiagonalMatrix of the lumped mass, :134-148),
+ * in the program's two forms, "cell-based loops" (:222-241) and "interleaved loops" (:243-263); 3D and 2D, one rank ----
+ *
+ * MGX_DG_PCG_MERGED: the whole iteration stays on the device.  Per iteration three plain launches on the context's
+ * stream -- the cell kernel (q = A p with the four block sums of mgx_dg_vmult_with_pcg_sums), one workgroup that adds
+ * them and writes
+ *   alpha = s1 / s0 ;  rho_next = s1 - 2 alpha s2 + alpha^2 s3 ;  beta = rho_next / s1 ;  rho[k] = s1, rho[k+1] = rho_next
+ * and one pass  x += alpha p ; r -= alpha q ; p = m r + beta p  that loads alpha and beta from device memory.  If s0 or s1
+ * is not a positive finite number or rho_next is not finite, alpha = beta = 0 and the iteration index k is recorded
+ * once: x and r stay as they are from then on, the history stays flat, no NaN is produced.  If only rho_next fails,
+ * finite but not positive -- the residual has reached rounding level, where the recurrence cancels -- the step is still
+ * taken, beta = 0, rho[k+1] = 0 and k + 1 is recorded: the number of steps taken, either way.
+ * MGX_DG_PCG_SEPARATE: the yardstick, textbook PCG from mgx_dg_vmult, separate dot-product and update kernels and
+ * scalars on the host (two to three host round trips per iteration); same interface, history and stopping rule. */
+#define MGX_DG_PCG_MERGED 0
+#define MGX_DG_PCG_SEPARATE 1
+typedef struct mgx_dg_pcg_solver_s *mgx_dg_pcg_solver_t;
+typedef struct
+{
+  mgx_dg_operator_t matrix;         /* without ghost cells (else MGX_ERR_UNSUPPORTED); vectors are in its number type */
+  int               form;           /* MGX_DG_PCG_* */
+  unsigned          max_iterations; /* n_tests of IterationNumberControl (:177) */
+  double            tolerance;      /* 0: run max_iterations (the reference's 1e-20); > 0: stop at sqrt(rho_k / rho_0) <= tolerance */
+  unsigned          check_every;    /* >= 1: with a tolerance, the host looks at the history every so many iterations */
+} mgx_dg_pcg_solver_desc;
+/* solver_dg/program.cc:134-148, 177-178: owns r, p, q, the block sums, the scalars and the history.  Refused with
+ * MGX_ERR_UNSUPPORTED (and a reason) if an entry of the preconditioner table is not positive and finite. */
+int mgx_dg_pcg_solver_create(mgx_context_t ctx, const mgx_dg_pcg_solver_desc *desc, mgx_dg_pcg_solver_t *solver);
+int mgx_dg_pcg_solver_destroy(mgx_dg_pcg_solver_t solver);
+/* solver.solve(laplace_operator, output, input, diagonal) (solver_dg/program.cc:222-263): zero start, `solution` is
+ * overwritten (:225 output = 0) and must not alias rhs; device vectors of mgx_dg_operator_n_dofs entries.  The operator
+ * and the update are applied k times each, so x_k and r_k are formed.  With a tolerance the solve stops at the first
+ * checked k (multiples of check_every, and max_iterations) with sqrt(rho_k / rho_0) <= tolerance.  iterations = that k,
+ * max_iterations if the tolerance was not met, or the iteration of the breakdown if one came first;
+ * reduction_rate = sqrt(rho_k / rho_0)^(1/k).  max_iterations == 0 or rhs == 0: x = 0, 0 iterations, rate 0.
+ * iterations and reduction_rate may be NULL. */
+int mgx_dg_pcg_solver_solve(mgx_dg_pcg_solver_t solver, const void *rhs, void *solution, unsigned *iterations,
+                            double *reduction_rate);
+/* the history rho_k = r_k . M^-1 r_k of the last solve (solver_dg/program.cc:134-148 the preconditioner, :222-263 the
+ * loops): rho[0] at the start, rho[k] after iteration k, for every iteration that ran; *count = their number (at most
+ * max_iterations + 1).  rho may be NULL to ask for the count only. */
+int mgx_dg_pcg_solver_history(mgx_dg_pcg_solver_t solver, double *rho, unsigned *count);
 
 /* ---- mesh helpers (stand in for GridGenerator + DoFHandler of the harness) ---- */
 

@@ -549,6 +549,24 @@ namespace multigrid
       check(mgx_dg_vmult_with_cg_update(h_, (double)alpha, (double)beta, r.begin(), q.begin(), p.begin(), x.begin(), sums));
       return {{(Number)sums[0], (Number)sums[1], (Number)sums[2], (Number)sums[3]}};
     }
+    // the operator's part of one merged iteration of the lumped-mass PCG (solver_dg/program.cc:222-263):
+    // q = A p, {q.p, r.(m r), q.(m r), q.(m q)} with m = lumped_mass_inverse() at every entry's local index
+    std::array<double, 4> vmult_with_pcg_sums(const Vector<Number> &r, Vector<Number> &q, const Vector<Number> &p) const
+    {
+      std::array<double, 4> sums;
+      check(mgx_dg_vmult_with_pcg_sums(h_, r.begin(), q.begin(), p.begin(), sums.data()));
+      return sums;
+    }
+    // inverse of the lumped mass matrix of a cell (solver_dg/program.cc:134-148), (fe_degree+1)^dim entries, x fastest
+    std::vector<double> lumped_mass_inverse() const
+    {
+      std::size_t n = 1;
+      for (int d = 0; d < dim; ++d)
+        n *= fe_degree + 1;
+      std::vector<double> table(n);
+      check(mgx_dg_operator_lumped_mass_inverse(h_, table.data()));
+      return table;
+    }
     // :910-955; the two vectors trade their storage for iteration_index >= 1, as the reference's swap does (:931)
     void vmult_with_chebyshev_update(const Vector<Number> &rhs, const unsigned int iteration_index, const Number factor1,
                                      const Number factor2, Vector<Number> &solution, Vector<Number> &solution_old) const
@@ -582,6 +600,49 @@ namespace multigrid
 
   private:
     const LaplaceOperatorCompactCombine<dim, fe_degree, Number, type> &laplace_;
+  };
+
+  // SolverCG<Vector<Number>> with IterationNumberControl and the inverse lumped mass matrix as preconditioner, as
+  // solver_dg/program.cc sets it up (:134-148, 177-178) and runs it in two forms (:222-263): interleaved = true keeps the
+  // whole iteration on the device (MGX_DG_PCG_MERGED), false is textbook PCG from separate kernels (MGX_DG_PCG_SEPARATE)
+  template <int dim, int fe_degree, typename Number, int type = 0>
+  class SolverCGLumpedMass
+  {
+  public:
+    SolverCGLumpedMass(const LaplaceOperatorCompactCombine<dim, fe_degree, Number, type> &laplace, const unsigned int n_iterations,
+                       const bool interleaved = true, const double tolerance = 0., const unsigned int check_every = 1)
+    {
+      mgx_dg_pcg_solver_desc d{};
+      d.matrix         = laplace.handle();
+      d.form           = interleaved ? MGX_DG_PCG_MERGED : MGX_DG_PCG_SEPARATE;
+      d.max_iterations = n_iterations;
+      d.tolerance      = tolerance;
+      d.check_every    = check_every;
+      check(mgx_dg_pcg_solver_create(laplace.context().handle(), &d, &h_));
+    }
+    ~SolverCGLumpedMass() { mgx_dg_pcg_solver_destroy(h_); }
+    SolverCGLumpedMass(const SolverCGLumpedMass &) = delete;
+    SolverCGLumpedMass &operator=(const SolverCGLumpedMass &) = delete;
+    // solver.solve(laplace_operator, output, input, diagonal): zero start; returns {last_step, reduction rate per iteration}
+    std::pair<unsigned int, double> solve(Vector<Number> &solution, const Vector<Number> &rhs) const
+    {
+      unsigned int its = 0;
+      double       red = 0;
+      check(mgx_dg_pcg_solver_solve(h_, rhs.begin(), solution.begin(), &its, &red));
+      return {its, red};
+    }
+    // r_k . M^-1 r_k of the last solve, k = 0 ... iterations run
+    std::vector<double> history() const
+    {
+      unsigned int n = 0;
+      check(mgx_dg_pcg_solver_history(h_, nullptr, &n));
+      std::vector<double> rho(n);
+      check(mgx_dg_pcg_solver_history(h_, rho.data(), &n));
+      return rho;
+    }
+
+  private:
+    mgx_dg_pcg_solver_t h_ = nullptr;
   };
 
   // multigrid::MultigridSolverDG<dim,fe_degree,Number,Number2> (multigrid_solver_dg.h:55-747): the DG level on top of the

@@ -22,7 +22,7 @@ from ._lib import F32, F64, INVALID_INDEX, MgxError, check
 __all__ = ["Context", "DeviceVector", "Cube", "LaplaceOperator", "Chebyshev", "Transfer", "MultigridSolver",
            "Communicator", "process_grid", "F32", "F64", "INVALID_INDEX", "MgxError", "DGLaplaceOperator", "dg_cheby_mesh",
            "dg_box_neighbours", "dg_box_partition", "dg_partition", "DG_HERMITE", "DG_GAUSS_LOBATTO", "DG_GAUSS", "DGMultigridSolver",
-           "spawn_ranks"]
+           "DGConjugateGradient", "DG_PCG_MERGED", "DG_PCG_SEPARATE", "spawn_ranks"]
 
 
 def spawn_ranks(script, argv, n, one_gpu=False, grace=30.0):
@@ -1330,6 +1330,19 @@ class DGLaplaceOperator:
                                                    sums.ctypes.data_as(_lib.f64p)))
         return sums
 
+    def lumped_mass_inverse(self):
+        """inverse of the lumped mass matrix of a cell (solver_dg/program.cc:134-148), (p+1)^dim entries, x fastest, fp64"""
+        t = np.empty((self.degree + 1) ** self.dim)
+        check(self.lib.mgx_dg_operator_lumped_mass_inverse(self.h, t.ctypes.data_as(_lib.f64p)))
+        return t
+
+    def vmult_with_pcg_sums(self, r, q, p):
+        """q = A p; returns (q.p, r.(m r), q.(m r), q.(m q)) with m = lumped_mass_inverse() at every entry's local index,
+        summed over the ranks: the operator's part of one merged iteration of the lumped-mass PCG"""
+        sums = np.empty(4)
+        check(self.lib.mgx_dg_vmult_with_pcg_sums(self.h, r.ptr, q.ptr, p.ptr, sums.ctypes.data_as(_lib.f64p)))
+        return sums
+
     def basis_1d(self):
         """(shape values [q, i] in the Gauss points, Gauss points, Gauss weights) on [0, 1]"""
         n = self.degree + 1
@@ -1349,6 +1362,40 @@ class DGLaplaceOperator:
     def clear(self):
         if getattr(self, "h", None):
             self.lib.mgx_dg_operator_destroy(self.h)
+            self.h = None
+
+
+DG_PCG_MERGED, DG_PCG_SEPARATE = 0, 1
+
+
+class DGConjugateGradient:
+    """Conjugate gradients on a DGLaplaceOperator alone, preconditioned by the inverse lumped mass matrix: the solver of
+    solver_dg/program.cc (:134-148 preconditioner, :177-178 control, :222-263 the two loops).  form DG_PCG_MERGED keeps the
+    whole iteration on the device (three launches, no host round trip); DG_PCG_SEPARATE is textbook PCG from separate
+    kernels with the scalars on the host, the yardstick.  Vectors are in the operator's number type; one rank."""
+
+    def __init__(self, op, form=DG_PCG_MERGED, max_iterations=100, tolerance=0.0, check_every=1):
+        self.op, self.lib, self.h = op, op.lib, None
+        d = _lib.DGPcgSolverDesc(op.h, form, max_iterations, tolerance, check_every)
+        h = C.c_void_p()
+        check(self.lib.mgx_dg_pcg_solver_create(op.ctx.h, C.byref(d), C.byref(h)))
+        self.h, self.max_iterations = h, max_iterations
+
+    def solve(self, rhs, solution):
+        """zero start, `solution` is overwritten; returns (iterations, reduction rate per iteration)"""
+        its, red = C.c_uint(), C.c_double()
+        check(self.lib.mgx_dg_pcg_solver_solve(self.h, rhs.ptr, solution.ptr, C.byref(its), C.byref(red)))
+        return its.value, red.value
+
+    def history(self):
+        """rho_k = r_k . M^-1 r_k of the last solve: [0] at the start, [k] after iteration k"""
+        rho, n = np.zeros(self.max_iterations + 1), C.c_uint()
+        check(self.lib.mgx_dg_pcg_solver_history(self.h, rho.ctypes.data_as(_lib.f64p), C.byref(n)))
+        return rho[:n.value].copy()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mgx_dg_pcg_solver_destroy(self.h)
             self.h = None
 
 

@@ -77,6 +77,11 @@ class DGPlainSolverDesc(C.Structure):
                 ("degree_pre", C.c_int), ("cell_global_id", C.POINTER(u32p))]
 
 
+class DGPcgSolverDesc(C.Structure):
+    _fields_ = [("matrix", vp), ("form", C.c_int), ("max_iterations", C.c_uint), ("tolerance", C.c_double),
+                ("check_every", C.c_uint)]
+
+
 class SmootherInfo(C.Structure):
     _fields_ = [("lambda_min", C.c_double), ("lambda_max", C.c_double), ("theta", C.c_double),
                 ("delta", C.c_double), ("degree", C.c_int), ("cg_iterations", C.c_int)]
@@ -260,6 +265,12 @@ SIGNATURES = {
     "mgx_dg_jacobi_vmult": (C.c_int, [vp, vp, vp]),
     "mgx_dg_vmult_with_chebyshev_update": (C.c_int, [vp, vp, C.c_uint, C.c_double, C.c_double, vp, vp]),
     "mgx_dg_vmult_with_cg_update": (C.c_int, [vp, C.c_double, C.c_double, vp, vp, vp, vp, f64p]),
+    "mgx_dg_operator_lumped_mass_inverse": (C.c_int, [vp, f64p]),
+    "mgx_dg_vmult_with_pcg_sums": (C.c_int, [vp, vp, vp, vp, f64p]),
+    "mgx_dg_pcg_solver_create": (C.c_int, [vp, C.POINTER(DGPcgSolverDesc), C.POINTER(vp)]),
+    "mgx_dg_pcg_solver_destroy": (C.c_int, [vp]),
+    "mgx_dg_pcg_solver_solve": (C.c_int, [vp, vp, vp, C.POINTER(C.c_uint), f64p]),
+    "mgx_dg_pcg_solver_history": (C.c_int, [vp, f64p, C.POINTER(C.c_uint)]),
     "mgx_dg_operator_info": (C.c_int, [vp, f64p, f64p, f64p]),
     "mgx_dg_operator_basis": (C.c_int, [vp, f64p, f64p, f64p]),
     "mgx_dg_solver_create": (C.c_int, [vp, C.POINTER(DGSolverDesc), C.POINTER(vp)]),

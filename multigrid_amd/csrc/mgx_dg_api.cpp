@@ -26,6 +26,10 @@ struct mgx_dg_operator_s
   int32_t      *neigh   = nullptr; // device [n_cells][2 dim]
   void         *consts  = nullptr; // device DGConst<T>
   void         *inv_diag = nullptr; // device [4^dim][(p+1)^dim]
+  // inverse of the lumped mass matrix of a cell (solver_dg/program.cc:134-148): host fp64 and device in the number type,
+  // [(p+1)^dim]; an entry is not positive and finite where the lumped mass is not (mgx_dg_pcg_solver_create refuses)
+  std::vector<double> lumped_inv_host;
+  void               *lumped_inv = nullptr;
   Host1D        h;
   Geometry      g;
   // decomposed mesh: ghost cells behind the owned ones, filled from their owners before every
@@ -106,6 +110,27 @@ struct mgx_dg_plain_solver_s
   double            *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr; // PCG, fp64
   double            *partials = nullptr, *sums = nullptr;                   // vmult_with_residual_update
   bool               timed = false;
+};
+
+// conjugate gradients on the DG operator alone, preconditioned by the inverse lumped mass (solver_dg/program.cc:134-148,
+// 177-178, 222-263)
+struct mgx_dg_pcg_solver_s
+{
+  mgx_context_t     ctx = nullptr;
+  mgx::DeviceArena  mem{"mgx_dg_pcg_solver"};
+  mgx_dg_operator_t A = nullptr;
+  int               form = MGX_DG_PCG_MERGED;
+  unsigned          max_iterations = 0, check_every = 1;
+  double            tolerance = 0;
+  size_t            n = 0;
+  uint32_t          n3 = 0, blocks = 0;
+  void             *r = nullptr, *p = nullptr, *q = nullptr; // the operator's number type
+  void             *z = nullptr, *dinv = nullptr;            // separate form: M^-1 r and the diagonal as a vector
+  double           *partials = nullptr;                      // merged: [blocks][4]; separate: kDotBlocks
+  double           *presums  = nullptr;                      // merged: [kPcgPresums][4], the first stage of many block sums
+  double           *scalars = nullptr, *rho_dev = nullptr;   // merged: alpha, beta, stalled_at, - ; [max_iterations + 1]
+  double           *result  = nullptr;                       // separate: a dot product
+  std::vector<double> rho;                                   // history of the last solve
 };
 
 namespace
@@ -309,6 +334,30 @@ namespace
     return MGX_OK;
   }
 
+  // lumped[i] = |det J| prod_d sum_q w_q phi_{i_d}(x_q) on the (p+1)-point Gauss rule, x fastest; the table holds 1 / lumped
+  void build_lumped_mass_inverse(const mgx_dg_operator_s &op, const double *J, std::vector<double> &table)
+  {
+    const int    n   = op.h.n;
+    const double det = op.dim == 2 ? J[0] * J[3] - J[1] * J[2]
+                                   : J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) +
+                                       J[2] * (J[3] * J[7] - J[4] * J[6]);
+    std::vector<double> sum(n, 0.0), line(n);
+    for (int i = 0; i < n; ++i)
+      for (int q = 0; q < n; ++q)
+        sum[i] += op.h.wq[q] * op.h.S[q * n + i];
+    // the basis is symmetric under x -> 1 - x (build_basis_and_geometry has checked it): the mean of the two mirror
+    // entries keeps the table exactly symmetric and sheds the part of the rounding error that is not.  The sums cancel
+    // from terms of 0.1 to 0.011 at p = 9 (Gauss-Lobatto): against numpy 6.0e-14 becomes 2.7e-14 there, 8.0e-14 in 3D
+    for (int i = 0; i < n; ++i)
+      line[i] = 0.5 * (sum[i] + sum[n - 1 - i]);
+    const int nz = op.dim == 2 ? 1 : n;
+    table.resize((size_t)n * n * nz);
+    for (int k = 0; k < nz; ++k)
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i)
+          table[((size_t)k * n + j) * n + i] = 1.0 / (std::fabs(det) * line[i] * line[j] * (op.dim == 2 ? 1.0 : line[k]));
+  }
+
   // neighbour ranks, their send lists and buffers, and (Hermite-like basis) the face every sent cell is sent for
   int upload_exchange_plan(mgx_dg_operator_s &op, const mgx_dg_operator_desc *desc)
   {
@@ -409,6 +458,8 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
       MGX_TRY(split_interior_and_boundary(*op, desc));
     }
   MGX_TRY(op->mem.upload_as(desc->number, &op->inv_diag, table.data(), table.size()));
+  build_lumped_mass_inverse(*op, desc->jacobian, op->lumped_inv_host);
+  MGX_TRY(op->mem.upload_as(desc->number, &op->lumped_inv, op->lumped_inv_host.data(), op->lumped_inv_host.size()));
   MGX_TRY(upload_constants(*op));
   *out = op.release();
   return MGX_OK;
@@ -517,6 +568,43 @@ int mgx_dg_vmult_with_cg_update(mgx_dg_operator_t op, double alpha, double beta,
   MGX_HIP(hipMemcpyAsync(sums, op->cg_sums, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
   MGX_HIP(hipStreamSynchronize(s));
   return mgx::allreduce_sum(op->ctx, sums, 4); // :904-906
+}
+
+int mgx_dg_operator_lumped_mass_inverse(mgx_dg_operator_t op, double *table)
+{
+  MGX_REQUIRE(op && table, "mgx_dg_operator_lumped_mass_inverse: null argument");
+  std::copy(op->lumped_inv_host.begin(), op->lumped_inv_host.end(), table);
+  return MGX_OK;
+}
+
+int mgx_dg_vmult_with_pcg_sums(mgx_dg_operator_t op, const void *r, void *q, const void *p, double sums[4])
+{
+  MGX_REQUIRE(op && r && q && p && sums && q != p && q != r, "mgx_dg_vmult_with_pcg_sums: null or aliased vectors");
+  hipStream_t    s      = (hipStream_t)mgx_context_stream(op->ctx);
+  const bool     split  = op->n_ghost > 0 && op->n_interior > 0;
+  const uint32_t blocks = split ? cell_grid(op->number, op->degree, op->n_interior, op->dim) +
+                                    cell_grid(op->number, op->degree, op->n_boundary, op->dim)
+                                : cell_grid(op->number, op->degree, op->n_cells, op->dim);
+  if (blocks > op->cg_capacity)
+    {
+      op->mem.release(op->cg_partials);
+      op->cg_partials = nullptr;
+      op->cg_capacity = 0;
+      MGX_TRY(op->mem.alloc(&op->cg_partials, 4 * (size_t)blocks));
+      op->cg_capacity = blocks;
+    }
+  if (!op->cg_sums)
+    MGX_TRY(op->mem.alloc(&op->cg_sums, 4));
+  // without the overlap of the ghost exchange the cells run in one launch: its blocks are not the split's
+  MGX_HIP(hipMemsetAsync(op->cg_partials, 0, sizeof(double) * 4 * (size_t)blocks, s));
+  DGLaunch l(kPcgSums, q, r, p);
+  l.partials = op->cg_partials;
+  l.lumped   = op->lumped_inv;
+  MGX_TRY(run(op, l, true));
+  mgx::launch_reduce4(s, op->cg_partials, blocks, nullptr, op->cg_sums);
+  MGX_HIP(hipMemcpyAsync(sums, op->cg_sums, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
+  return mgx::allreduce_sum(op->ctx, sums, 4);
 }
 
 int mgx_dg_operator_info(mgx_dg_operator_t op, double *hderiv, double penalty[3], double eigenvalues_1d[MGX_MAX_DEGREE + 1])
@@ -1295,6 +1383,243 @@ int mgx_dg_plain_solver_do_matvec_smoother(mgx_dg_plain_solver_t S)
   MGX_REQUIRE(S, "mgx_dg_plain_solver_do_matvec_smoother: null solver");
   mgx_dg_plain_solver_s::Level &top = S->level.back();
   return mgx_dg_vmult(top.A, top.t, top.defect); // matrix[maxlevel].vmult, :444
+}
+
+} // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * lumped-mass PCG on the DG operator (solver_dg/program.cc:134-148, 177-178, 222-263)
+ * --------------------------------------------------------------------------------------------- */
+namespace
+{
+  bool pcg_positive_finite(double v) { return v > 0. && std::isfinite(v); }
+
+  // what both forms report from the history rho[0 .. k]
+  void pcg_report(const std::vector<double> &rho, unsigned k, unsigned *iterations, double *reduction_rate)
+  {
+    if (iterations)
+      *iterations = k;
+    if (reduction_rate)
+      *reduction_rate = k > 0 && rho[0] > 0. ? std::pow(std::sqrt(rho[k] / rho[0]), 1.0 / k) : 0.;
+  }
+
+  // The merged form: per iteration the cell kernel (q = A p and the block sums), one workgroup that adds them and writes
+  // alpha, beta and the history, and the update kernel.  Nothing returns to the host inside the loop; the host looks at
+  // the history every check_every iterations if there is a tolerance, once at the end otherwise.
+  int pcg_solve_merged(mgx_dg_pcg_solver_t S, const void *rhs, void *x, unsigned *k_stop)
+  {
+    hipStream_t       s  = (hipStream_t)mgx_context_stream(S->ctx);
+    mgx_dg_operator_t A  = S->A;
+    const unsigned    nk = S->max_iterations;
+    mgx::launch_pcg_start(s, A->number, x, S->r, S->p, rhs, A->lumped_inv, S->n3, S->n);
+    DGLaunch l(kPcgSums, S->q, S->r, S->p);
+    l.partials = S->partials;
+    l.lumped   = A->lumped_inv;
+    l.n_cells  = A->n_cells;
+    double   head[4]; // scalars
+    unsigned done = 0;
+    *k_stop       = nk;
+    while (done < nk)
+      {
+        MGX_TRY(launch_cells(A, l));
+        mgx::launch_pcg_scalars(s, S->partials, S->blocks, done, S->scalars, S->rho_dev, S->presums);
+        mgx::launch_pcg_update(s, A->number, x, S->r, S->p, S->q, A->lumped_inv, S->n3, S->scalars, S->n);
+        ++done;
+        if (S->tolerance > 0. && (done % S->check_every == 0 || done == nk))
+          {
+            MGX_HIP(hipMemcpyAsync(head, S->scalars, sizeof(head), hipMemcpyDeviceToHost, s));
+            MGX_HIP(hipMemcpyAsync(S->rho.data(), S->rho_dev, sizeof(double) * (done + 1), hipMemcpyDeviceToHost, s));
+            MGX_HIP(hipStreamSynchronize(s));
+            if (head[2] >= 0.)
+              {
+                *k_stop = (unsigned)head[2];
+                break;
+              }
+            if (std::sqrt(S->rho[done] / S->rho[0]) <= S->tolerance)
+              {
+                *k_stop = done;
+                break;
+              }
+          }
+      }
+    MGX_HIP(hipGetLastError());
+    if (S->tolerance > 0.)
+      {
+        S->rho.resize(done + 1);
+        return MGX_OK;
+      }
+    MGX_HIP(hipMemcpyAsync(head, S->scalars, sizeof(head), hipMemcpyDeviceToHost, s));
+    MGX_HIP(hipMemcpyAsync(S->rho.data(), S->rho_dev, sizeof(double) * (nk + 1), hipMemcpyDeviceToHost, s));
+    MGX_HIP(hipStreamSynchronize(s));
+    if (head[2] >= 0.)
+      *k_stop = (unsigned)head[2];
+    return MGX_OK;
+  }
+
+  // The separate form, the yardstick: textbook PCG (deal.II's SolverCG around the cell-based operator, :222-241) from
+  // mgx_dg_vmult and the dot / update kernels of the FE_Q solver, the scalars on the host.  Same history, same stopping
+  // rule, same breakdown rule as the merged form.
+  int pcg_solve_separate(mgx_dg_pcg_solver_t S, const void *rhs, void *x, unsigned *k_stop)
+  {
+    hipStream_t       s   = (hipStream_t)mgx_context_stream(S->ctx);
+    mgx_dg_operator_t A   = S->A;
+    const int         num = A->number;
+    const unsigned    nk  = S->max_iterations;
+    auto              fetch = [&](double *v) {
+      MGX_HIP(hipMemcpyAsync(v, S->result, sizeof(double), hipMemcpyDeviceToHost, s));
+      MGX_HIP(hipStreamSynchronize(s));
+      return (int)MGX_OK;
+    };
+    MGX_HIP(hipMemsetAsync(x, 0, dg_nsz(num) * S->n, s));
+    MGX_HIP(hipMemcpyAsync(S->r, rhs, dg_nsz(num) * S->n, hipMemcpyDeviceToDevice, s));
+    mgx::launch_jacobi_dot(s, num, S->z, S->dinv, S->r, S->n, S->partials, S->result); // z = M^-1 r ; r.z
+    MGX_HIP(hipMemcpyAsync(S->p, S->z, dg_nsz(num) * S->n, hipMemcpyDeviceToDevice, s));
+    double rho = 0, pq = 0;
+    MGX_TRY(fetch(&rho));
+    S->rho[0] = rho >= 0. && std::isfinite(rho) ? rho : 0.;
+    unsigned done = 0;
+    *k_stop       = nk;
+    bool stalled  = false;
+    while (done < nk)
+      {
+        if (!stalled)
+          {
+            MGX_TRY(mgx_dg_vmult(A, S->q, S->p));
+            mgx::launch_dot(s, num, S->p, S->q, S->n, S->partials, S->result);
+            MGX_TRY(fetch(&pq));
+            stalled = !(pcg_positive_finite(pq) && pcg_positive_finite(rho));
+          }
+        double rho_next = S->rho[done];
+        if (!stalled)
+          {
+            const double alpha = rho / pq;
+            mgx::launch_cg_update(s, num, x, S->r, S->p, S->q, alpha, S->n, S->partials, S->result); // x += alpha p ; r -= alpha q
+            mgx::launch_jacobi_dot(s, num, S->z, S->dinv, S->r, S->n, S->partials, S->result);
+            MGX_TRY(fetch(&rho_next));
+            // (a residual that has reached zero is a breakdown of the next iteration, not of this one)
+            if (!(rho_next >= 0.) || !std::isfinite(rho_next))
+              return dg_fail(MGX_ERR_NOT_CONVERGED, "mgx_dg_pcg_solver_solve: r.M^-1 r is not a number");
+            mgx::launch_xpby(s, num, S->p, S->z, rho_next / rho, S->n);
+            rho = rho_next;
+          }
+        else if (*k_stop == nk)
+          *k_stop = done;
+        ++done;
+        S->rho[done] = rho_next;
+        if (S->tolerance > 0. && (done % S->check_every == 0 || done == nk))
+          {
+            if (stalled)
+              break;
+            if (std::sqrt(S->rho[done] / S->rho[0]) <= S->tolerance)
+              {
+                *k_stop = done;
+                break;
+              }
+          }
+      }
+    MGX_HIP(hipGetLastError());
+    S->rho.resize(done + 1);
+    return MGX_OK;
+  }
+} // namespace
+
+extern "C" {
+
+int mgx_dg_pcg_solver_create(mgx_context_t ctx, const mgx_dg_pcg_solver_desc *desc, mgx_dg_pcg_solver_t *out)
+{
+  MGX_REQUIRE(ctx && desc && out && desc->matrix, "mgx_dg_pcg_solver_create: null argument");
+  mgx_dg_operator_t A = desc->matrix;
+  if (A->ctx != ctx)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_pcg_solver_create: operator of another context");
+  if (desc->form != MGX_DG_PCG_MERGED && desc->form != MGX_DG_PCG_SEPARATE)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_pcg_solver_create: form must be MGX_DG_PCG_MERGED or MGX_DG_PCG_SEPARATE");
+  if (!(desc->tolerance >= 0.) || !std::isfinite(desc->tolerance))
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_pcg_solver_create: tolerance must be a finite number >= 0");
+  if (desc->check_every < 1)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_pcg_solver_create: check_every must be at least 1");
+  if (desc->max_iterations >= (1u << 24))
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_pcg_solver_create: max_iterations must be below 2^24");
+  if (A->n_ghost > 0)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_pcg_solver_create: the operator has ghost cells; the lumped-mass PCG runs on one "
+                                        "rank (its scalars stay on the device, there is no allreduce)");
+  for (size_t i = 0; i < A->lumped_inv_host.size(); ++i)
+    if (!pcg_positive_finite(A->lumped_inv_host[i]))
+      return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_pcg_solver_create: the lumped mass of local index " + std::to_string(i) +
+                                            " is not positive: no preconditioner for this basis");
+  std::unique_ptr<mgx_dg_pcg_solver_s, int (*)(mgx_dg_pcg_solver_t)> S(new mgx_dg_pcg_solver_s, mgx_dg_pcg_solver_destroy);
+  S->ctx            = ctx;
+  S->A              = A;
+  S->form           = desc->form;
+  S->max_iterations = desc->max_iterations;
+  S->check_every    = desc->check_every;
+  S->tolerance      = desc->tolerance;
+  S->n              = (size_t)mgx_dg_operator_n_dofs(A);
+  S->n3             = (uint32_t)dg_cell_entries(A->degree, A->dim);
+  if (S->n3 > mgx::kPcgTableMax)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_pcg_solver_create: more entries per cell than the update kernel's table holds");
+  S->rho.assign((size_t)S->max_iterations + 1, 0.);
+  hipStream_t  s   = (hipStream_t)mgx_context_stream(ctx);
+  const size_t vec = dg_nsz(A->number) * S->n;
+  for (void **v : {&S->r, &S->p, &S->q})
+    {
+      MGX_TRY(S->mem.zeros(v, vec, s));
+    }
+  if (S->form == MGX_DG_PCG_MERGED)
+    {
+      S->blocks = cell_grid(A->number, A->degree, A->n_cells, A->dim);
+      MGX_TRY(S->mem.zeros(&S->partials, 4 * (size_t)S->blocks, s));
+      MGX_TRY(S->mem.zeros(&S->presums, 4 * (size_t)mgx::kPcgPresums, s));
+      MGX_TRY(S->mem.zeros(&S->scalars, 4, s));
+      MGX_TRY(S->mem.zeros(&S->rho_dev, (size_t)S->max_iterations + 1, s));
+    }
+  else
+    {
+      MGX_TRY(S->mem.zeros(&S->z, vec, s));
+      MGX_TRY(S->mem.alloc(&S->dinv, vec));
+      mgx::launch_tile_table(s, A->number, S->dinv, A->lumped_inv, S->n3, S->n);
+      MGX_TRY(S->mem.zeros(&S->partials, (size_t)mgx::kDotBlocks, s));
+      MGX_TRY(S->mem.zeros(&S->result, 1, s));
+    }
+  MGX_HIP(hipGetLastError());
+  MGX_HIP(hipStreamSynchronize(s));
+  *out = S.release();
+  return MGX_OK;
+}
+
+int mgx_dg_pcg_solver_destroy(mgx_dg_pcg_solver_t S)
+{
+  if (!S)
+    return MGX_OK;
+  if (S->ctx)
+    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
+  delete S;
+  return MGX_OK;
+}
+
+int mgx_dg_pcg_solver_solve(mgx_dg_pcg_solver_t S, const void *rhs, void *solution, unsigned *iterations, double *reduction_rate)
+{
+  MGX_REQUIRE(S && rhs && solution && rhs != solution, "mgx_dg_pcg_solver_solve: null or aliased vectors");
+  S->rho.assign((size_t)S->max_iterations + 1, 0.);
+  unsigned k = 0;
+  if (S->max_iterations == 0)
+    {
+      hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
+      MGX_HIP(hipMemsetAsync(solution, 0, dg_nsz(S->A->number) * S->n, s)); // :225 output = 0
+      MGX_HIP(hipStreamSynchronize(s));
+    }
+  else
+    MGX_TRY(S->form == MGX_DG_PCG_MERGED ? pcg_solve_merged(S, rhs, solution, &k) : pcg_solve_separate(S, rhs, solution, &k));
+  pcg_report(S->rho, k, iterations, reduction_rate);
+  return MGX_OK;
+}
+
+int mgx_dg_pcg_solver_history(mgx_dg_pcg_solver_t S, double *rho, unsigned *count)
+{
+  MGX_REQUIRE(S && count, "mgx_dg_pcg_solver_history: null argument");
+  *count = (unsigned)S->rho.size();
+  if (rho)
+    std::copy(S->rho.begin(), S->rho.end(), rho);
+  return MGX_OK;
 }
 
 } // extern "C"

@@ -60,7 +60,7 @@ namespace mgx::dg::device
     T                *dst;
     const int32_t    *neigh;
     const DGConst<T> *c;
-    const T          *inv_diag; // [4^dim][(p+1)^dim]
+    const T          *inv_diag; // [4^dim][(p+1)^dim]; kPcgSums: the inverse lumped mass of a cell instead, [(p+1)^dim]
     const uint32_t   *cell_list; // cells of this launch (nullptr: cells cell_first ... in order)
     uint32_t          cell_first;
     uint32_t          n_cells;   // cells of this launch
@@ -69,7 +69,7 @@ namespace mgx::dg::device
     int               iteration_index;
     // cells of a launch without a list: cell_first + cell_stride * i
     uint32_t          cell_stride;
-    // kCgSums: [gridDim.x][4] block sums.  kRestrict: the FE_Q vector the transformed residual is added into,
+    // kCgSums, kPcgSums: [gridDim.x][4] block sums.  kRestrict: the FE_Q vector the transformed residual is added into,
     // the compressed index table of the FE_Q cells (in the order of the DG cells), the 1D change of basis
     // [n][n] and whether the cells of the launch share no FE_Q DoF (plain adds instead of atomics)
     double           *partials;
@@ -233,6 +233,46 @@ namespace mgx::dg::device
 #pragma unroll
     for (int i = 0; i < N; ++i)
       out[i] = in[i];
+  }
+
+  // kPcgSums, one entry: q = (A p)_i, p, r and the inverse lumped mass m of the entry's local index.  As in kCgSums the
+  // products are formed in the number type and summed in double; m r is the product the update kernel of the solver forms.
+  template <typename T>
+  __device__ __forceinline__ void pcg_sums_add(double (&sum)[4], T q, T p, T r, T m)
+  {
+    const T mr = m * r;
+    sum[0] += (double)(q * p);
+    sum[1] += (double)(r * mr);
+    sum[2] += (double)(q * mr);
+    sum[3] += (double)(q * (m * q));
+  }
+
+  // the four sums of a workgroup of THREADS threads -> partials[blockIdx.x][4]: shuffles within a wave, then the waves'
+  // sums through `red` (4 doubles per wave, LDS the caller no longer reads) in the order of the waves.  Every thread of
+  // the workgroup calls it.
+  template <int THREADS>
+  __device__ __forceinline__ void block_sum4_cells(double (&sum)[4], double *red, int tid, double *__restrict__ partials)
+  {
+    constexpr int WAVES = THREADS / 64;
+    static_assert(THREADS % 64 == 0, "whole waves");
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+          sum[k] += __shfl_down(sum[k], o);
+        if ((tid & 63) == 0)
+          red[(tid >> 6) * 4 + k] = sum[k];
+      }
+    __syncthreads();
+    if (tid < 4)
+      {
+        double t4 = red[tid];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w)
+          t4 += red[w * 4 + tid];
+        partials[(size_t)blockIdx.x * 4 + tid] = t4;
+      }
   }
 
   // q[e] = sum_i E[i][e] r[i] (to the eigenvector basis) and r[i] = sum_e E[i][e] q[e] (back): every

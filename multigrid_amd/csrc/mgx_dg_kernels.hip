@@ -657,6 +657,24 @@ namespace
             A.partials[(size_t)blockIdx.x * 4 + tid] = t4;
           }
       }
+    else if constexpr (ACTION == kPcgSums)
+      {
+        // kCgSums with the inverse lumped mass m of the DoF's local index (A.inv_diag carries the table here; the
+        // preconditioner of solver_dg/program.cc:134-148): dst.src, rhs.(m rhs), dst.(m rhs), dst.(m dst)
+        double sum[4] = {0., 0., 0., 0.};
+        if (store)
+          {
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+              {
+                const T m = A.inv_diag[(b * N + a) * N + i], r = A.rhs[lbase + i];
+                A.dst[lbase + i] = y[i];
+                pcg_sums_add(sum, y[i], xs[i], r, m);
+              }
+          }
+        __syncthreads(); // the x-lines above were read from U
+        block_sum4_cells<C::THREADS>(sum, reinterpret_cast<double *>(lds), tid, A.partials);
+      }
     else
       {
         // laplace_operator_dg.h:1839-1860
@@ -832,13 +850,14 @@ namespace
   template <typename T>
   bool launch_cells_t(hipStream_t s, const CellOperands &op, const DGLaunch &l)
   {
-    const DGArgs<T> a{(const T *)l.src, (const T *)l.rhs, (T *)l.dst, op.neigh, (const DGConst<T> *)op.consts, (const T *)op.inv_diag,
+    const DGArgs<T> a{(const T *)l.src, (const T *)l.rhs, (T *)l.dst, op.neigh, (const DGConst<T> *)op.consts,
+                      (const T *)(l.action == kPcgSums ? l.lumped : op.inv_diag),
                       l.cell_list, l.cell_first, l.n_cells, op.n_owned, (T)l.f1, (T)l.f2, l.iteration_index, l.cell_stride,
                       l.partials, (T *)l.cg, l.idx27, (const T *)l.P1, l.plain};
     bool launched = false;
     mgx::dispatch_degree(op.degree, [&](auto P) {
       mgx::dispatch_mode<MGX_DG_HERMITE, MGX_DG_GAUSS_LOBATTO, MGX_DG_GAUSS>(op.basis, [&](auto TYPE) {
-        launched = mgx::dispatch_mode<kVmult, kRestrict, kCgSums, kChebyshev, kResidual, kJacobi>(l.action, [&](auto ACTION) {
+        launched = mgx::dispatch_mode<kVmult, kRestrict, kCgSums, kChebyshev, kResidual, kJacobi, kPcgSums>(l.action, [&](auto ACTION) {
           launch_one<decltype(P)::value, T, decltype(TYPE)::value, decltype(ACTION)::value>(s, a, op.has_ghosts);
         });
       });

@@ -1,5 +1,5 @@
 // mgx_dg_kernels_2d.hip -- the gfx950 cell kernel of the DG (symmetric interior penalty) Laplace operator on an affine
-// mesh of quadrilaterals, with the merged Chebyshev update: LaplaceOperatorCompactCombine<2,p,Number,type> and
+// mesh of quadrilaterals, with the merged Chebyshev update and the sums of the merged CG iteration: LaplaceOperatorCompactCombine<2,p,Number,type> and
 // JacobiTransformed<2,p,Number,type>.  The line products, the constant block and the argument block are those of the
 // 3D kernel (mgx_dg_device.hpp); this file holds what depends on the dimension.
 //
@@ -375,6 +375,25 @@ namespace
               A.dst[lbase + i] = A.rhs[lbase + i] - y[i];
           }
       }
+    else if constexpr (ACTION == kPcgSums)
+      {
+        // the product stored and the four sums of the merged CG iteration, weighted by the inverse lumped mass m of the
+        // DoF's local index (A.inv_diag carries the table here; solver_dg/program.cc:134-148):
+        // dst.src, rhs.(m rhs), dst.(m rhs), dst.(m dst) over the cells of the launch
+        double sum[4] = {0., 0., 0., 0.};
+        if (store)
+          {
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+              {
+                const T m = A.inv_diag[a * N + i], r = A.rhs[lbase + i];
+                A.dst[lbase + i] = y[i];
+                pcg_sums_add(sum, y[i], xs[i], r, m);
+              }
+          }
+        __syncthreads(); // the x-lines above were read from U
+        block_sum4_cells<C::THREADS>(sum, reinterpret_cast<double *>(lds), tid, A.partials);
+      }
     else
       {
         // laplace_operator_dg.h:1839-1860
@@ -416,13 +435,14 @@ namespace
   template <typename T>
   bool launch_cells_2d_t(hipStream_t s, const CellOperands &op, const DGLaunch &l)
   {
-    const DGArgs<T> a{(const T *)l.src, (const T *)l.rhs, (T *)l.dst, op.neigh, (const DGConst<T> *)op.consts, (const T *)op.inv_diag,
+    const DGArgs<T> a{(const T *)l.src, (const T *)l.rhs, (T *)l.dst, op.neigh, (const DGConst<T> *)op.consts,
+                      (const T *)(l.action == kPcgSums ? l.lumped : op.inv_diag),
                       l.cell_list, l.cell_first, l.n_cells, op.n_owned, (T)l.f1, (T)l.f2, l.iteration_index, l.cell_stride,
-                      nullptr, nullptr, nullptr, nullptr, 0};
+                      l.partials, nullptr, nullptr, nullptr, 0};
     bool launched = false;
     mgx::dispatch_degree(op.degree, [&](auto P) {
       mgx::dispatch_mode<MGX_DG_HERMITE, MGX_DG_GAUSS_LOBATTO, MGX_DG_GAUSS>(op.basis, [&](auto TYPE) {
-        launched = mgx::dispatch_mode<kVmult, kChebyshev, kResidual, kJacobi>(l.action, [&](auto ACTION) {
+        launched = mgx::dispatch_mode<kVmult, kChebyshev, kResidual, kJacobi, kPcgSums>(l.action, [&](auto ACTION) {
           launch_one_2d<decltype(P)::value, T, decltype(TYPE)::value, decltype(ACTION)::value>(s, a);
         });
       });

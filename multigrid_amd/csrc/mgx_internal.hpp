@@ -556,7 +556,8 @@ namespace mgx
       kCgSums    = 2, // product stored, the four sums of the merged CG iteration
       kChebyshev = 3, // numbering of laplace_operator_dg.h:957-962
       kResidual  = 4,
-      kJacobi    = 5  // P^-1 only (scaled by f2)
+      kJacobi    = 5, // P^-1 only (scaled by f2)
+      kPcgSums   = 6  // product stored, the four sums of the merged CG iteration weighted by the inverse lumped mass
     };
 
     // what every launch of one operator shares (device pointers; consts: a copy of const_block)
@@ -590,12 +591,14 @@ namespace mgx
       const uint32_t *idx27    = nullptr;
       const void     *P1       = nullptr;
       int             plain    = 0;
+      // kPcgSums: the inverse lumped mass of a cell, [(p+1)^dim] in the number type (device); block sums in `partials`
+      const void     *lumped   = nullptr;
     };
     // a status of include/mgx.h: MGX_ERR_UNSUPPORTED for a degree, basis or action no kernel is built for
     int      launch_dg_cells(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
     uint32_t cell_grid(int number, int p, uint32_t n_cells, int dim = 3); // workgroups of a launch over n_cells cells
     // the cell kernel of two dimensions (mgx_dg_kernels_2d.hip), reached through the two functions above: actions
-    // kVmult, kResidual, kChebyshev and kJacobi; false: no kernel for this degree, basis or action
+    // kVmult, kResidual, kChebyshev, kJacobi and kPcgSums; false: no kernel for this degree, basis or action
     bool     launch_dg_cells_2d(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
     uint32_t cell_grid_2d(int number, int p, uint32_t n_cells);
     // the constant block of the cell kernel in the number type, from the host data
@@ -667,6 +670,31 @@ namespace mgx
   uint32_t launch_axpy_norm(hipStream_t s, int number, void *r, const void *q, double factor, size_t n, double *partials);
   void     launch_cg_pre(hipStream_t s, int number, void *x, void *p, void *q, double alpha, double beta, size_t n);
   uint32_t launch_dot4(hipStream_t s, int number, const void *q, const void *p, const void *r, size_t n, double *partials);
+  // ---- lumped-mass PCG on the DG operator (mgx_dg_pcg_solver_*, solver_dg/program.cc:134-148, 222-263) ----
+  // `table`: the inverse lumped mass of a cell, n3 <= kPcgTableMax entries in the number type (device); entry i of a
+  // vector belongs to local index i mod n3.
+  // Device scalars of the merged form, written by launch_pcg_scalars and read by launch_pcg_update:
+  //   scalars[0] = alpha, [1] = beta, [2] = stalled_at (-1: no breakdown so far), [3] unused
+  constexpr uint32_t kPcgTableMax = 1000; // (MGX_MAX_DEGREE + 1)^3
+  //   x = 0 ; r = b ; p = m r
+  void launch_pcg_start(hipStream_t s, int number, void *x, void *r, void *p, const void *b, const void *table, uint32_t n3,
+                        size_t n);
+  // the block sums {q.p, r.mr, q.mr, q.mq} of iteration k added in a fixed order, then
+  //   alpha = s1 / s0 ; rho_next = s1 - 2 alpha s2 + alpha^2 s3 ; beta = rho_next / s1 ; rho_hist[k] = s1 ; rho_hist[k + 1] = rho_next
+  // unless s0 or s1 is not a positive finite number, rho_next is not finite, or a breakdown is on record: then
+  // alpha = beta = 0, rho_hist[k + 1] = rho_hist[k] (k == 0: s1 if it is finite and not negative, else 0) and
+  // stalled_at = k, once.  rho_next finite but not positive: the step is taken, beta = 0, rho_hist[k + 1] = 0 and
+  // stalled_at = k + 1 (the steps taken, either way)
+  // More than kPcgPresumFrom block sums: kPcgPresums workgroups add a contiguous share each into presums
+  // [kPcgPresums][4] first (a fourth launch; the order of the additions stays fixed), the one workgroup adds those.
+  constexpr uint32_t kPcgPresumFrom = 4096, kPcgPresums = 256;
+  void launch_pcg_scalars(hipStream_t s, const double *partials, uint32_t n_partials, uint32_t k, double *scalars, double *rho_hist,
+                          double *presums);
+  //   x += alpha p ; r -= alpha q ; p = m r + beta p      (alpha, beta from `scalars`)
+  void launch_pcg_update(hipStream_t s, int number, void *x, void *r, void *p, const void *q, const void *table, uint32_t n3,
+                         const double *scalars, size_t n);
+  //   v[i] = table[i mod n3]  (the separate form's diagonal vector)
+  void launch_tile_table(hipStream_t s, int number, void *v, const void *table, uint32_t n3, size_t n);
   void     launch_residual_pre(hipStream_t s, int defect_number, void *defect, const double *residual, const double *update,
                                double factor, size_t n);
   uint32_t launch_residual_post(hipStream_t s, int z_number, const void *z, double *residual, double *update, double factor,

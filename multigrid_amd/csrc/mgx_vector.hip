@@ -1046,4 +1046,196 @@ namespace mgx
                                            n_free, n, partials));
     return g.x;
   }
+
+  // ------------------------------------------------------------------------------------------
+  // lumped-mass PCG on the DG operator, merged form (mgx_dg_pcg_solver_*; the preconditioner and the interleaved loop of
+  // solver_dg/program.cc:134-148, 222-263).  The preconditioner is one table of n3 = (p+1)^dim numbers, the same in
+  // every cell: it sits in the LDS, and a thread follows its entry's local index from one grid stride to the next
+  // without a division.
+  // ------------------------------------------------------------------------------------------
+  template <typename T>
+  struct PcgTable
+  {
+    // every thread of the workgroup calls the constructor
+    __device__ PcgTable(T *lds, const T *__restrict__ table, uint32_t n3_) : tab(lds), n3(n3_)
+    {
+      for (uint32_t j = threadIdx.x; j < n3; j += blockDim.x)
+        lds[j] = table[j];
+      __syncthreads();
+      const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+      local = (uint32_t)(first % n3);
+      step  = (uint32_t)(stride % n3);
+    }
+    __device__ T next() // the entry of the current index; moves on by one grid stride
+    {
+      const T m = tab[local];
+      local += step;
+      if (local >= n3)
+        local -= n3;
+      return m;
+    }
+    const T *tab;
+    uint32_t n3, local, step;
+  };
+
+  template <typename T>
+  __global__ void __launch_bounds__(256)
+    k_pcg_start(T *__restrict__ x, T *__restrict__ r, T *__restrict__ p, const T *__restrict__ b, const T *__restrict__ table,
+                uint32_t n3, size_t n)
+  {
+    __shared__ T tab[kPcgTableMax];
+    PcgTable<T>  m(tab, table, n3);
+    GRID_STRIDE(i, n)
+    {
+      const T bi = b[i];
+      x[i]       = T(0);
+      r[i]       = bi;
+      p[i]       = m.next() * bi;
+    }
+  }
+
+  template <typename T>
+  __global__ void __launch_bounds__(256)
+    k_pcg_update(T *__restrict__ x, T *__restrict__ r, T *__restrict__ p, const T *__restrict__ q, const T *__restrict__ table,
+                 uint32_t n3, const double *__restrict__ scalars, size_t n)
+  {
+    __shared__ T tab[kPcgTableMax];
+    PcgTable<T>  m(tab, table, n3);
+    const T      alpha = (T)scalars[0], beta = (T)scalars[1]; // uniform: one scalar load
+    GRID_STRIDE(i, n)
+    {
+      const T pi = p[i];
+      const T ri = r[i] - alpha * q[i];
+      x[i] += alpha * pi;
+      r[i] = ri;
+      p[i] = m.next() * ri + beta * pi;
+    }
+  }
+
+  template <typename T>
+  __global__ void __launch_bounds__(256) k_tile_table(T *__restrict__ v, const T *__restrict__ table, uint32_t n3, size_t n)
+  {
+    __shared__ T tab[kPcgTableMax];
+    PcgTable<T>  m(tab, table, n3);
+    GRID_STRIDE(i, n) v[i] = m.next();
+  }
+
+  __device__ __forceinline__ bool positive_finite(double v) { return v > 0. && v < HUGE_VAL; }
+
+  // quadruples first ... first + count - 1 added by the 256 threads of a workgroup in a fixed order (thread t takes
+  // first + t, first + t + 256, ...; then a tree): the totals in red[0], red[256], red[512], red[768] of thread 0
+  __device__ __forceinline__ void sum_quadruples(const double *__restrict__ partials, uint32_t first, uint32_t count, double *red)
+  {
+    const int tid    = threadIdx.x;
+    double    acc[4] = {0., 0., 0., 0.};
+    for (uint32_t i = tid; i < count; i += 256)
+      for (int j = 0; j < 4; ++j)
+        acc[j] += partials[4 * ((size_t)first + i) + j];
+    for (int j = 0; j < 4; ++j)
+      red[j * 256 + tid] = acc[j];
+    __syncthreads();
+    for (int stride = 128; stride > 0; stride >>= 1)
+      {
+        if (tid < stride)
+          for (int j = 0; j < 4; ++j)
+            red[j * 256 + tid] += red[j * 256 + tid + stride];
+        __syncthreads();
+      }
+  }
+
+  // many block sums (a workgroup of the cell kernel holds 5 cells at p = 4 in fp64: 420 000 quadruples on 128^3 cells,
+  // 0.74 ms for one workgroup): workgroup b adds the quadruples b chunk ... (b + 1) chunk - 1 into out[b]
+  __global__ void __launch_bounds__(256)
+    k_pcg_presum(const double *__restrict__ partials, uint32_t n, uint32_t chunk, double *__restrict__ out)
+  {
+    __shared__ double red[4 * 256];
+    const uint32_t    first = blockIdx.x * chunk;
+    sum_quadruples(partials, first, first < n ? (n - first < chunk ? n - first : chunk) : 0, red);
+    if (threadIdx.x < 4)
+      out[4 * blockIdx.x + threadIdx.x] = red[256 * threadIdx.x];
+  }
+
+  // one workgroup: the block sums in a fixed order, then the scalars of iteration k
+  __global__ void __launch_bounds__(256)
+    k_pcg_scalars(const double *__restrict__ partials, uint32_t n, uint32_t k, double *__restrict__ scalars,
+                  double *__restrict__ rho_hist)
+  {
+    __shared__ double red[4 * 256];
+    sum_quadruples(partials, 0, n, red);
+    if (threadIdx.x != 0)
+      return;
+    const double s0 = red[0], s1 = red[256], s2 = red[512], s3 = red[768];
+    if (k == 0)
+      scalars[2] = -1.;
+    bool   ok    = scalars[2] < 0. && positive_finite(s0) && positive_finite(s1);
+    double alpha = 0., beta = 0., rho_next = 0.;
+    if (ok)
+      {
+        alpha    = s1 / s0;
+        rho_next = s1 - 2. * alpha * s2 + alpha * alpha * s3;
+        ok       = rho_next > -HUGE_VAL && rho_next < HUGE_VAL;
+      }
+    if (ok && rho_next > 0.)
+      {
+        beta            = rho_next / s1;
+        rho_hist[k]     = s1;
+        rho_hist[k + 1] = rho_next;
+      }
+    else if (ok)
+      {
+        // the residual has reached rounding level, where the recurrence cancels: the step is taken (alpha minimises the
+        // error along p whatever comes after), the direction is not renewed -- k + 1 steps in all
+        rho_hist[k]     = s1;
+        rho_hist[k + 1] = 0.;
+        scalars[2]      = (double)(k + 1);
+      }
+    else
+      {
+        alpha = 0.;
+        if (k == 0)
+          rho_hist[0] = s1 >= 0. && s1 < HUGE_VAL ? s1 : 0.;
+        rho_hist[k + 1] = rho_hist[k];
+        if (scalars[2] < 0.)
+          scalars[2] = (double)k;
+      }
+    scalars[0] = alpha;
+    scalars[1] = beta;
+  }
+
+  void launch_pcg_start(hipStream_t s, int number, void *x, void *r, void *p, const void *b, const void *table, uint32_t n3, size_t n)
+  {
+    if (n == 0)
+      return;
+    BY_NUMBER(number, hipLaunchKernelGGL((k_pcg_start<T>), stream_grid(n), dim3(256), 0, s, (T *)x, (T *)r, (T *)p, (const T *)b,
+                                         (const T *)table, n3, n));
+  }
+
+  void launch_pcg_scalars(hipStream_t s, const double *partials, uint32_t n_partials, uint32_t k, double *scalars, double *rho_hist,
+                          double *presums)
+  {
+    if (n_partials > kPcgPresumFrom)
+      {
+        const uint32_t chunk = (n_partials + kPcgPresums - 1) / kPcgPresums;
+        hipLaunchKernelGGL(k_pcg_presum, dim3(kPcgPresums), dim3(256), 0, s, partials, n_partials, chunk, presums);
+        partials   = presums;
+        n_partials = kPcgPresums;
+      }
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(256), 0, s, partials, n_partials, k, scalars, rho_hist);
+  }
+
+  void launch_pcg_update(hipStream_t s, int number, void *x, void *r, void *p, const void *q, const void *table, uint32_t n3,
+                         const double *scalars, size_t n)
+  {
+    if (n == 0)
+      return;
+    BY_NUMBER(number, hipLaunchKernelGGL((k_pcg_update<T>), stream_grid(n), dim3(256), 0, s, (T *)x, (T *)r, (T *)p, (const T *)q,
+                                         (const T *)table, n3, scalars, n));
+  }
+
+  void launch_tile_table(hipStream_t s, int number, void *v, const void *table, uint32_t n3, size_t n)
+  {
+    if (n == 0)
+      return;
+    BY_NUMBER(number, hipLaunchKernelGGL((k_tile_table<T>), stream_grid(n), dim3(256), 0, s, (T *)v, (const T *)table, n3, n));
+  }
 } // namespace mgx
