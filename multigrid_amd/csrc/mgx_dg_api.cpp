@@ -150,7 +150,7 @@ namespace
   int ghosts_pack(mgx_dg_operator_t op, const void *vec)
   {
     hipStream_t    s   = (hipStream_t)mgx_context_stream(op->ctx);
-    const uint32_t n3  = (uint32_t)(op->degree + 1) * (op->degree + 1) * (op->degree + 1);
+    const uint32_t n3  = (uint32_t)dg_cell_entries(op->degree, op->dim);
     const int      nnb = (int)op->nb_rank.size();
     for (int k = 0; k < nnb; ++k)
       {
@@ -166,7 +166,7 @@ namespace
 
   int ghosts_exchange(mgx_dg_operator_t op, void *vec, hipStream_t stream)
   {
-    const uint32_t n3  = (uint32_t)(op->degree + 1) * (op->degree + 1) * (op->degree + 1);
+    const uint32_t n3  = (uint32_t)dg_cell_entries(op->degree, op->dim);
     const size_t   es  = dg_nsz(op->number);
     const int      nnb = (int)op->nb_rank.size();
     std::vector<void *> recv(nnb);
@@ -218,7 +218,7 @@ namespace
     boundary.cell_first = op->interior_is_prefix ? op->n_interior : 0;
     boundary.n_cells    = op->n_boundary;
     if (all.partials) // the block sums of the second launch behind those of the first
-      boundary.partials += 4 * (size_t)cell_grid(op->number, op->degree, op->n_interior);
+      boundary.partials += 4 * (size_t)cell_grid(op->number, op->degree, op->n_interior, op->dim);
     // whatever fails below, the main stream is ordered behind the side stream again before returning:
     // nothing of this application may still be in flight when the caller reuses src / dst
     int status = launch_cells(op, interior);
@@ -539,8 +539,9 @@ int mgx_dg_vmult_with_cg_update(mgx_dg_operator_t op, double alpha, double beta,
                                         "(the 2D cell kernel has no epilogue with the four sums)");
   hipStream_t    s      = (hipStream_t)mgx_context_stream(op->ctx);
   const bool     split  = op->n_ghost > 0 && op->n_interior > 0;
-  const uint32_t blocks = split ? cell_grid(op->number, op->degree, op->n_interior) + cell_grid(op->number, op->degree, op->n_boundary)
-                                : cell_grid(op->number, op->degree, op->n_cells);
+  const uint32_t blocks = split ? cell_grid(op->number, op->degree, op->n_interior, op->dim) +
+                                    cell_grid(op->number, op->degree, op->n_boundary, op->dim)
+                                : cell_grid(op->number, op->degree, op->n_cells, op->dim);
   if (blocks > op->cg_capacity)
     {
       op->mem.release(op->cg_partials);

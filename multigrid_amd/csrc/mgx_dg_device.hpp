@@ -1,13 +1,25 @@
-// mgx_dg_device.hpp -- device code shared by the cell kernels of the DG (symmetric interior penalty) operator in three
-// dimensions (mgx_dg_kernels.hip) and in two (mgx_dg_kernels_2d.hip): the constant block and the argument block of a
-// launch, and the 1D line products (dense on 2-vectors, even-odd, eigenvector basis) that both kernels sweep their cells
-// with.  Nothing here knows the dimension of a cell; what does (the LDS layout, the ownership of lines and face points)
-// stays with the kernel.
+// mgx_dg_device.hpp -- what the cell kernels of the DG (symmetric interior penalty) operator in three dimensions
+// (mgx_dg_kernels.hip) and in two (mgx_dg_kernels_2d.hip) share: the constant block and the argument block of a launch;
+// the launch side (dispatch_cells fills the argument block and selects the instantiation, cell_groups counts the
+// workgroups; each translation unit instantiates them with its own configuration and kernels); the 1D line products
+// (dense on 2-vectors, even-odd, eigenvector basis) that both kernels sweep their cells with; and the block sums of the
+// merged CG iterations (block_sum4_cells).  Nothing here knows the dimension of a cell; what does (the LDS layout, the
+// ownership of lines and face points) stays with the kernel, and so do the mapping from workgroup to cell and the
+// epilogues of the actions: shared versions of those changed the registers, or the choice of fused multiply-adds and
+// with it the last bit of some results, of kernels that sit on a register edge.
 #pragma once
 
 #include "mgx_internal.hpp"
 
 #include "mgx_dg_host.hpp"
+
+namespace mgx::dg
+{
+  // the 2D unit's side of launch_dg_cells and cell_grid (mgx_internal.hpp), which the 3D unit defines: false: no kernel
+  // for this degree, basis or action
+  bool     launch_dg_cells_2d(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
+  uint32_t cell_grid_2d(int number, int p, uint32_t n_cells);
+} // namespace mgx::dg
 
 namespace mgx::dg::device
 {
@@ -78,6 +90,51 @@ namespace mgx::dg::device
     const T          *P1;
     int               plain;
   };
+
+  // ------------------------------------------------------------------------------------------
+  // launch side: each translation unit instantiates these with the configuration and the kernels of its dimension
+
+  // workgroups of a launch over n_cells cells, C the configuration of the kernel (CPW cells per workgroup)
+  template <typename C>
+  constexpr uint32_t cell_groups(uint32_t n_cells)
+  {
+    return (n_cells + C::CPW - 1) / C::CPW;
+  }
+  // ... C = CFG<p, number type>; a degree no kernel is built for: one cell per workgroup
+  template <template <int, typename> class CFG>
+  uint32_t cell_groups(int number, int p, uint32_t n_cells)
+  {
+    uint32_t groups = n_cells;
+    mgx::dispatch_degree(p, [&](auto P) {
+      mgx::dispatch_number(number, [&](auto t) { groups = cell_groups<CFG<decltype(P)::value, decltype(t)>>(n_cells); });
+    });
+    return groups;
+  }
+
+  // The argument block of a launch from what the launches of an operator share and the launch itself, and number type x
+  // degree x basis x action (one of ACTIONS) -> launch_one(P, TYPE, ACTION, args), the first three integral constants.
+  // false: no kernel is built for this combination
+  template <int... ACTIONS, typename F>
+  bool dispatch_cells(const CellOperands &op, const DGLaunch &l, F &&launch_one)
+  {
+    bool launched = false;
+    mgx::dispatch_number(op.number, [&](auto t) {
+      using T = decltype(t);
+      const DGArgs<T> a{(const T *)l.src, (const T *)l.rhs, (T *)l.dst, op.neigh, (const DGConst<T> *)op.consts,
+                        (const T *)(l.action == kPcgSums ? l.lumped : op.inv_diag),
+                        l.cell_list, l.cell_first, l.n_cells, op.n_owned, (T)l.f1, (T)l.f2, l.iteration_index, l.cell_stride,
+                        l.partials, (T *)l.cg, l.idx27, (const T *)l.P1, l.plain};
+      mgx::dispatch_degree(op.degree, [&](auto P) {
+        mgx::dispatch_mode<MGX_DG_HERMITE, MGX_DG_GAUSS_LOBATTO, MGX_DG_GAUSS>(op.basis, [&](auto TYPE) {
+          launched = mgx::dispatch_mode<ACTIONS...>(l.action, [&](auto ACTION) { launch_one(P, TYPE, ACTION, a); });
+        });
+      });
+    });
+    return launched;
+  }
+
+  // ------------------------------------------------------------------------------------------
+  // line products
   template <int N, typename T>
   __device__ __forceinline__ void ld_line(const T *a, int base, int stride, T (&r)[N])
   {

@@ -1,8 +1,9 @@
 // mgx_dg_kernels.hip -- device code of the DG (symmetric interior penalty) Laplace operator on an affine mesh with the
 // merged Chebyshev update: the gfx950 cell kernel with its line products, its constant block and its launch, and the
 // small kernels of the ghost exchange and of the smoother's start vector.  What the host code (mgx_dg_api.cpp) sees of
-// it is the DG section of mgx_internal.hpp; the data format of the device (DGConst, DGArgs) and the line products are
-// mgx_dg_device.hpp, which the cell kernel of two dimensions (mgx_dg_kernels_2d.hip) shares.
+// it is the DG section of mgx_internal.hpp; the data format of the device (DGConst, DGArgs), the launch side
+// (dispatch_cells, cell_groups), the line products and the block sums are mgx_dg_device.hpp, which the cell kernel of
+// two dimensions (mgx_dg_kernels_2d.hip) shares.  launch_dg_cells and cell_grid here hand dim == 2 to that unit.
 //
 // Reference behaviour (not code): common/laplace_operator_dg.h -- LaplaceOperatorCompactCombine
 // :350-2024 (cell-based loop operation_on_cells :1110-1861), JacobiTransformed :2028-2256,
@@ -620,7 +621,9 @@ namespace
       }
     else if constexpr (ACTION == kCgSums)
       {
-        // laplace_operator_dg.h:1827-1838: dst.src, rhs.rhs, dst.rhs, dst.dst over the cells of the launch
+        // laplace_operator_dg.h:1827-1838: dst.src, rhs.rhs, dst.rhs, dst.dst over the cells of the launch.  The reduction is
+        // block_sum4_cells written out: calling it makes the compiler fuse the other product of rhs.rhs in fp64 from p = 4 on
+        // (the last bit of that sum)
         double sum[4] = {0., 0., 0., 0.};
         if (store)
           {
@@ -784,11 +787,11 @@ namespace
     c.hderiv = (T)h.hderiv;
   }
 
-  template <int P, typename T, int TYPE, int ACTION>
+  template <int P, int TYPE, int ACTION, typename T>
   void launch_one(hipStream_t s, const DGArgs<T> &a, bool ghosts)
   {
     using C             = DGCfg<P, T>;
-    const uint32_t grid = (a.n_cells + C::CPW - 1) / C::CPW;
+    const uint32_t grid = cell_groups<C>(a.n_cells);
     if constexpr (TYPE == MGX_DG_HERMITE && ACTION != kJacobi)
       if (ghosts)
         {
@@ -846,24 +849,6 @@ namespace
       }
   }
 
-  // degree x basis x action -> the instantiation; false: none is built for this combination
-  template <typename T>
-  bool launch_cells_t(hipStream_t s, const CellOperands &op, const DGLaunch &l)
-  {
-    const DGArgs<T> a{(const T *)l.src, (const T *)l.rhs, (T *)l.dst, op.neigh, (const DGConst<T> *)op.consts,
-                      (const T *)(l.action == kPcgSums ? l.lumped : op.inv_diag),
-                      l.cell_list, l.cell_first, l.n_cells, op.n_owned, (T)l.f1, (T)l.f2, l.iteration_index, l.cell_stride,
-                      l.partials, (T *)l.cg, l.idx27, (const T *)l.P1, l.plain};
-    bool launched = false;
-    mgx::dispatch_degree(op.degree, [&](auto P) {
-      mgx::dispatch_mode<MGX_DG_HERMITE, MGX_DG_GAUSS_LOBATTO, MGX_DG_GAUSS>(op.basis, [&](auto TYPE) {
-        launched = mgx::dispatch_mode<kVmult, kRestrict, kCgSums, kChebyshev, kResidual, kJacobi, kPcgSums>(l.action, [&](auto ACTION) {
-          launch_one<decltype(P)::value, T, decltype(TYPE)::value, decltype(ACTION)::value>(s, a, op.has_ghosts);
-        });
-      });
-    });
-    return launched;
-  }
 } // namespace
 
 namespace mgx::dg
@@ -872,8 +857,10 @@ namespace mgx::dg
   {
     if (l.n_cells == 0)
       return MGX_OK;
-    const bool launched = op.dim == 2 ? launch_dg_cells_2d(s, op, l)
-                                      : (op.number == MGX_F64 ? launch_cells_t<double>(s, op, l) : launch_cells_t<float>(s, op, l));
+    const bool launched =
+      op.dim == 2 ? launch_dg_cells_2d(s, op, l)
+                  : dispatch_cells<kVmult, kRestrict, kCgSums, kChebyshev, kResidual, kJacobi, kPcgSums>(
+                      op, l, [&](auto P, auto TYPE, auto ACTION, const auto &a) { launch_one<P.value, TYPE.value, ACTION.value>(s, a, op.has_ghosts); });
     if (!launched)
       return mgx::report_error(MGX_ERR_UNSUPPORTED, "DG cell kernel: no kernel for degree " + std::to_string(op.degree) + ", basis " +
                                                       std::to_string(op.basis) + ", action " + std::to_string(l.action));
@@ -883,11 +870,7 @@ namespace mgx::dg
 
   uint32_t cell_grid(int number, int p, uint32_t n_cells, int dim)
   {
-    if (dim == 2)
-      return cell_grid_2d(number, p, n_cells);
-    uint32_t cpw = 1;
-    mgx::dispatch_degree(p, [&](auto P) { mgx::dispatch_number(number, [&](auto t) { cpw = DGCfg<decltype(P)::value, decltype(t)>::CPW; }); });
-    return (n_cells + cpw - 1) / cpw;
+    return dim == 2 ? cell_grid_2d(number, p, n_cells) : cell_groups<DGCfg>(number, p, n_cells);
   }
 
   std::vector<char> const_block(int number, const Host1D &h, const Geometry &g)

@@ -1,7 +1,8 @@
 // mgx_dg_kernels_2d.hip -- the gfx950 cell kernel of the DG (symmetric interior penalty) Laplace operator on an affine
 // mesh of quadrilaterals, with the merged Chebyshev update and the sums of the merged CG iteration: LaplaceOperatorCompactCombine<2,p,Number,type> and
-// JacobiTransformed<2,p,Number,type>.  The line products, the constant block and the argument block are those of the
-// 3D kernel (mgx_dg_device.hpp); this file holds what depends on the dimension.
+// JacobiTransformed<2,p,Number,type>.  The line products, the block sums, the constant block, the argument block and the
+// launch side (dispatch_cells, cell_groups) are those of the 3D kernel (mgx_dg_device.hpp); this file holds what depends
+// on the dimension and is reached through launch_dg_cells / cell_grid of the 3D unit.
 //
 // Reference behaviour (not code): common/laplace_operator_dg.h -- the dim == 2 branches of operation_on_cells
 // (:1147 cell loop, :1359-1457 / :1418 neighbour access, :1568-1577 Dirichlet faces, :1675-1716 cell term),
@@ -423,31 +424,11 @@ namespace
       }
   }
 
-  template <int P, typename T, int TYPE, int ACTION>
+  template <int P, int TYPE, int ACTION, typename T>
   void launch_one_2d(hipStream_t s, const DGArgs<T> &a)
   {
-    using C             = DGCfg2<P, T>;
-    const uint32_t grid = (a.n_cells + C::CPW - 1) / C::CPW;
-    hipLaunchKernelGGL((dg_cell_kernel_2d<P, T, TYPE, ACTION>), dim3(grid), dim3(C::THREADS), 0, s, a);
-  }
-
-  // degree x basis x action -> the instantiation; false: none is built for this combination
-  template <typename T>
-  bool launch_cells_2d_t(hipStream_t s, const CellOperands &op, const DGLaunch &l)
-  {
-    const DGArgs<T> a{(const T *)l.src, (const T *)l.rhs, (T *)l.dst, op.neigh, (const DGConst<T> *)op.consts,
-                      (const T *)(l.action == kPcgSums ? l.lumped : op.inv_diag),
-                      l.cell_list, l.cell_first, l.n_cells, op.n_owned, (T)l.f1, (T)l.f2, l.iteration_index, l.cell_stride,
-                      l.partials, nullptr, nullptr, nullptr, 0};
-    bool launched = false;
-    mgx::dispatch_degree(op.degree, [&](auto P) {
-      mgx::dispatch_mode<MGX_DG_HERMITE, MGX_DG_GAUSS_LOBATTO, MGX_DG_GAUSS>(op.basis, [&](auto TYPE) {
-        launched = mgx::dispatch_mode<kVmult, kChebyshev, kResidual, kJacobi, kPcgSums>(l.action, [&](auto ACTION) {
-          launch_one_2d<decltype(P)::value, T, decltype(TYPE)::value, decltype(ACTION)::value>(s, a);
-        });
-      });
-    });
-    return launched;
+    using C = DGCfg2<P, T>;
+    hipLaunchKernelGGL((dg_cell_kernel_2d<P, T, TYPE, ACTION>), dim3(cell_groups<C>(a.n_cells)), dim3(C::THREADS), 0, s, a);
   }
 } // namespace
 
@@ -455,13 +436,9 @@ namespace mgx::dg
 {
   bool launch_dg_cells_2d(hipStream_t s, const CellOperands &op, const DGLaunch &l)
   {
-    return op.number == MGX_F64 ? launch_cells_2d_t<double>(s, op, l) : launch_cells_2d_t<float>(s, op, l);
+    return dispatch_cells<kVmult, kChebyshev, kResidual, kJacobi, kPcgSums>(
+      op, l, [&](auto P, auto TYPE, auto ACTION, const auto &a) { launch_one_2d<P.value, TYPE.value, ACTION.value>(s, a); });
   }
 
-  uint32_t cell_grid_2d(int number, int p, uint32_t n_cells)
-  {
-    uint32_t cpw = 1;
-    mgx::dispatch_degree(p, [&](auto P) { mgx::dispatch_number(number, [&](auto t) { cpw = DGCfg2<decltype(P)::value, decltype(t)>::CPW; }); });
-    return (n_cells + cpw - 1) / cpw;
-  }
+  uint32_t cell_grid_2d(int number, int p, uint32_t n_cells) { return cell_groups<DGCfg2>(number, p, n_cells); }
 } // namespace mgx::dg

@@ -542,7 +542,7 @@ namespace mgx
   // p1d [2][(p+1)^2] in the number type; identity: children[c][k] == 8 c + k, the table is not read.  dim == 2: a cell
   // and its four children, children [n_coarse][4], identity: children[c][k] == 4 c + k
   void launch_dg_transfer(hipStream_t s, int number, int p, bool prolong, void *dst, const void *src, const uint32_t *children,
-                          uint32_t n_coarse, const void *p1d, bool identity, int dim = 3);
+                          uint32_t n_coarse, const void *p1d, bool identity, int dim);
   // ---- DG cell kernel (mgx_dg_kernels.hip): what it offers the host code of mgx_dg_api.cpp ----
   namespace dg
   {
@@ -595,12 +595,9 @@ namespace mgx
       const void     *lumped   = nullptr;
     };
     // a status of include/mgx.h: MGX_ERR_UNSUPPORTED for a degree, basis or action no kernel is built for
+    // (two dimensions: actions kVmult, kResidual, kChebyshev, kJacobi and kPcgSums)
     int      launch_dg_cells(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
-    uint32_t cell_grid(int number, int p, uint32_t n_cells, int dim = 3); // workgroups of a launch over n_cells cells
-    // the cell kernel of two dimensions (mgx_dg_kernels_2d.hip), reached through the two functions above: actions
-    // kVmult, kResidual, kChebyshev, kJacobi and kPcgSums; false: no kernel for this degree, basis or action
-    bool     launch_dg_cells_2d(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
-    uint32_t cell_grid_2d(int number, int p, uint32_t n_cells);
+    uint32_t cell_grid(int number, int p, uint32_t n_cells, int dim); // workgroups of a launch over n_cells cells
     // the constant block of the cell kernel in the number type, from the host data
     std::vector<char> const_block(int number, const Host1D &h, const Geometry &g);
     // ghost exchange: whole cells / (Hermite-like basis) value and normal derivative on face faces[c] of cells[c]
