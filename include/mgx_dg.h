@@ -154,6 +154,49 @@ int mgx_dg_operator_info(mgx_dg_operator_t op, double *hermite_derivative_on_fac
 int mgx_dg_operator_basis(mgx_dg_operator_t op, double *shape_values, double *quadrature_points,
                           double *quadrature_weights);
 
+/* ---- right-hand side with Dirichlet boundary data and the L2 error, on the device ----
+ * The reference's DG solvers integrate the volume term of the right-hand side only (common/multigrid_solver_dg_plain.h:
+ * 163-185, multigrid_solver_dg.h:243-262) although their solution does not vanish on the boundary.  The face-based form
+ * (laplace_operator_dg_face.h:146-157), a_F(u, v) = int_F (sigma_F u v - d_n u v - u d_n v) on a Dirichlet face F, says what
+ * boundary values g add:  b_i += int_F g (sigma_F phi_i - d_n phi_i).  The operator stays linear (homogeneous mirror
+ * values); the right-hand side carries the data.  3D and 2D, all bases, degrees and number types. */
+
+/* Integer position of every owned cell -- the cell_ijk / cell_ij of mgx_dg_box_neighbours[_2d] -- host [n_cells][dim],
+ * copied; real coordinates are x = origin + J (pos + xi), J the operator's Jacobian, xi in [0,1]^dim (origin[2] is not
+ * read in 2D).  May be called again.  Without it a request that needs coordinates (a sine product) returns
+ * MGX_ERR_INVALID_ARGUMENT. */
+int mgx_dg_operator_set_cell_positions(mgx_dg_operator_t op, const double origin[3], const int32_t *cell_pos);
+
+#define MGX_DG_FN_SINE_PRODUCT 1 /* amplitude prod_d sin(wave[d] x_d + phase[d]), evaluated in the kernel (in double) */
+#define MGX_DG_FN_SAMPLED 2      /* values in the quadrature points, device arrays of doubles */
+#define MGX_DG_FN_NONE 0         /* (internal: what a NULL function stands for) */
+typedef struct
+{
+  int kind; /* MGX_DG_FN_SINE_PRODUCT or MGX_DG_FN_SAMPLED */
+  /* sine product: the number of directions, 0 or 3: three, 2: two; it must be the operator's.  Sampled: not read. */
+  int    dim;
+  double amplitude, wave[3], phase[3];
+  /* sampled, device, cells in the operator's order: cell_values [n_cells][(p+1)^dim], the values in the Gauss points, x
+   * fastest (read where the function is f or u); face_values [n_cells][2 dim][(p+1)^(dim-1)], face 2d+s, the Gauss
+   * points of the face with the lower remaining direction fastest (read where the function is g; only the entries of
+   * Dirichlet faces are).  Whichever is not read may be NULL.  A sampled function needs no cell positions. */
+  const double *cell_values, *face_values;
+} mgx_dg_function;
+
+/* For every owned cell  dst_i = int_K f phi_i + sum over the Dirichlet faces F of K  int_F g (sigma_F phi_i - d_n phi_i)
+ * on the (p+1)-point Gauss rule, sigma_F, the face weight and the normal from the operator's own geometry.  f == NULL:
+ * f = 0; g == NULL: the reference's volume-only vector.  dst (device, the operator's number type) is overwritten; the
+ * arithmetic, function evaluation included, is in double and only the store converts.  One writer per entry, no
+ * atomics: the same bits in every run.  Decomposed operators: owned cells only, the ghost part of dst is left alone;
+ * no communication (a face to another rank is not a Dirichlet face). */
+int mgx_dg_compute_rhs(mgx_dg_operator_t op, const mgx_dg_function *f, const mgx_dg_function *g, void *dst);
+
+/* sums = { sum_K sum_q (u_h(x_q) - u(x_q))^2 JxW_q,  sum_K sum_q JxW_q } over this rank's owned cells, u_h the function
+ * of vec (device, the operator's number type): the two numbers of compute_l2_error (multigrid_solver_dg_plain.h:219-259)
+ * before the sum over the ranks and the square root -- no communication here; the caller adds over the ranks and takes
+ * sqrt(sums[0] / sums[1]).  Block sums in double, added in a fixed order: the same bits in every run. */
+int mgx_dg_compute_l2_error(mgx_dg_operator_t op, const void *vec, const mgx_dg_function *u, double sums[2]);
+
 /* ---- MultigridSolverDG<3,p,Number,double> (common/multigrid_solver_dg.h:55-747): the DG level on top
  * of the FE_Q(p) multigrid hierarchy of the same mesh ---- */
 typedef struct mgx_dg_solver_s *mgx_dg_solver_t;

@@ -1251,6 +1251,36 @@ def dg_box_partition(cells, procs, rank, ordering="z"):
     return dg_partition(loc + r3 * blk, cells, procs, rank)
 
 
+class DGFunction:
+    """A function for DGLaplaceOperator.compute_rhs / compute_l2_error (mgx_dg_function, include/mgx_dg.h)."""
+
+    def __init__(self, desc, keep=()):
+        self.desc, self._keep = desc, keep   # the device vectors of a sampled function live as long as it does
+
+    @classmethod
+    def sine_product(cls, amplitude, wave, phase):
+        """amplitude prod_d sin(wave[d] x_d + phase[d]), evaluated on the device in fp64; len(wave) is the dimension"""
+        wave, phase = np.asarray(wave, dtype=float).ravel(), np.asarray(phase, dtype=float).ravel()
+        assert wave.size == phase.size and wave.size in (2, 3)
+        d = _lib.DGFunctionDesc()
+        d.kind, d.dim, d.amplitude = 1, wave.size, float(amplitude)
+        d.wave[:wave.size], d.phase[:wave.size] = wave.tolist(), phase.tolist()
+        return cls(d)
+
+    @classmethod
+    def sampled(cls, cell_values, face_values=None):
+        """fp64 device vectors: cell_values [n_cells, (p+1)^dim] in the Gauss points (x fastest; read where the function
+        is f or u, may be None otherwise), face_values [n_cells, 2 dim, (p+1)^(dim-1)] in the Gauss points of face 2d+s
+        (read on Dirichlet faces where the function is g)"""
+        for v in (cell_values, face_values):
+            assert v is None or v.number == F64, "sampled values are fp64 device vectors"
+        d = _lib.DGFunctionDesc()
+        d.kind = 2
+        d.cell_values = cell_values.ptr if cell_values is not None else None
+        d.face_values = face_values.ptr if face_values is not None else None
+        return cls(d, (cell_values, face_values))
+
+
 class DGLaplaceOperator:
     """multigrid::LaplaceOperatorCompactCombine<3,p,Number,type> with its JacobiTransformed
     preconditioner (common/laplace_operator_dg.h:350-2256) on an affine mesh; dim=2: <2,p,Number,type> on
@@ -1343,6 +1373,28 @@ class DGLaplaceOperator:
         check(self.lib.mgx_dg_vmult_with_pcg_sums(self.h, r.ptr, q.ptr, p.ptr, sums.ctypes.data_as(_lib.f64p)))
         return sums
 
+    def set_cell_positions(self, origin, cell_pos):
+        """integer position of every owned cell ([n, dim], as dg_box_neighbours gives it): x = origin + J (pos + xi)"""
+        o = np.zeros(3)
+        o[:self.dim] = np.asarray(origin, dtype=float).ravel()
+        pos = np.ascontiguousarray(cell_pos, dtype=np.int32).reshape(-1, self.dim)
+        check(self.lib.mgx_dg_operator_set_cell_positions(self.h, o.ctypes.data_as(_lib.f64p),
+                                                          pos.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def compute_rhs(self, dst, f=None, g=None):
+        """dst_i = int f phi_i + sum over the Dirichlet faces of int g (sigma_F phi_i - d_n phi_i), f and g DGFunctions
+        (None: zero; g=None is the reference's volume-only vector); dst in the operator's number type"""
+        check(self.lib.mgx_dg_compute_rhs(self.h, C.byref(f.desc) if f is not None else None,
+                                          C.byref(g.desc) if g is not None else None, dst.ptr if dst is not None else None))
+
+    def compute_l2_error(self, vec, u):
+        """(sum (u_h - u)^2 JxW, sum JxW) over this rank's owned cells; the L2 error is sqrt of their ratio, each summed
+        over the ranks first"""
+        sums = np.empty(2)
+        check(self.lib.mgx_dg_compute_l2_error(self.h, vec.ptr, C.byref(u.desc) if u is not None else None,
+                                               sums.ctypes.data_as(_lib.f64p)))
+        return sums
+
     def basis_1d(self):
         """(shape values [q, i] in the Gauss points, Gauss points, Gauss weights) on [0, 1]"""
         n = self.degree + 1
@@ -1422,6 +1474,8 @@ class DGMultigridSolver:
         ng, ex = part["n_ghost"], part["exchange"]
         self.matrix_dg = DGLaplaceOperator(ctx, cube.degree, basis, part["neighbours"], jac, vcycle_number, ng, ex, plan_id=1001)
         self.matrix_dg_dp = DGLaplaceOperator(ctx, cube.degree, basis, part["neighbours"], jac, F64, ng, ex, plan_id=1002)
+        # coordinates for compute_rhs / compute_l2_error: the square mesh starts at -0.9, a box at its origin
+        self.matrix_dg_dp.set_cell_positions((cube.box_desc["origin"] if cube.box_desc else -0.9,) * 3, self.cell_ijk)
         d = _lib.DGSolverDesc(self.matrix_dg.h, self.matrix_dg_dp.h, self.cfe.h, degree_pre, gid.ctypes.data_as(_lib.u32p))
         h = C.c_void_p()
         check(self.lib.mgx_dg_solver_create(ctx.h, C.byref(d), C.byref(h)))
@@ -1513,7 +1567,10 @@ class DGPlainMultigridSolver:
     transfers, level 0 solved by its Chebyshev iteration; V-cycle in `vcycle_number`, outer CG in fp64.  A 2-tuple of
     coarse_cells (and a 2 x 2 jacobian0) gives <2,p,Number,double>, the dimension poisson_dg_plain/program.cc:65 runs."""
 
-    def __init__(self, ctx, degree, basis, coarse_cells, jacobian0, n_levels, degree_pre=3, vcycle_number=F32, ordering="z"):
+    def __init__(self, ctx, degree, basis, coarse_cells, jacobian0, n_levels, degree_pre=3, vcycle_number=F32, ordering="z",
+                 origin=None):
+        """origin (default 0): the corner of the box, for the coordinates x = origin + J (pos + xi) that compute_rhs and
+        compute_l2_error of the finest fp64 operator evaluate sine products in"""
         self.ctx, self.lib = ctx, ctx.lib
         self.degree, self.basis, self.n_levels, self.vnumber = degree, basis, n_levels, vcycle_number
         self.dim = dim = len(coarse_cells)
@@ -1532,6 +1589,7 @@ class DGPlainMultigridSolver:
                 self.matrix.append(DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, vcycle_number, dim=dim))
                 if l == n_levels - 1:
                     self.matrix_dg_dp = DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, F64, dim=dim)
+                    self.matrix_dg_dp.set_cell_positions(np.zeros(dim) if origin is None else origin, ijk)
                 if l > 0:
                     self.transfer.append(DGLevelTransfer(ctx, degree, basis, dg_box_children(self.cells[l - 1], ordering, ordering),
                                                          vcycle_number))

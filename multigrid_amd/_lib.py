@@ -62,6 +62,11 @@ class DGOperatorDesc(C.Structure):
                 ("n_ghost_cells", C.c_uint32), ("exchange", C.POINTER(DGExchangeDesc)), ("dim", C.c_int)]
 
 
+class DGFunctionDesc(C.Structure):
+    _fields_ = [("kind", C.c_int), ("dim", C.c_int), ("amplitude", C.c_double), ("wave", C.c_double * 3),
+                ("phase", C.c_double * 3), ("cell_values", vp), ("face_values", vp)]
+
+
 class DGSolverDesc(C.Structure):
     _fields_ = [("matrix_dg", vp), ("matrix_dg_dp", vp), ("cfe", vp), ("degree_pre", C.c_int),
                 ("cell_global_id", u32p)]
@@ -273,6 +278,9 @@ SIGNATURES = {
     "mgx_dg_pcg_solver_history": (C.c_int, [vp, f64p, C.POINTER(C.c_uint)]),
     "mgx_dg_operator_info": (C.c_int, [vp, f64p, f64p, f64p]),
     "mgx_dg_operator_basis": (C.c_int, [vp, f64p, f64p, f64p]),
+    "mgx_dg_operator_set_cell_positions": (C.c_int, [vp, f64p, C.POINTER(C.c_int32)]),
+    "mgx_dg_compute_rhs": (C.c_int, [vp, C.POINTER(DGFunctionDesc), C.POINTER(DGFunctionDesc), vp]),
+    "mgx_dg_compute_l2_error": (C.c_int, [vp, vp, C.POINTER(DGFunctionDesc), f64p]),
     "mgx_dg_solver_create": (C.c_int, [vp, C.POINTER(DGSolverDesc), C.POINTER(vp)]),
     "mgx_dg_solver_destroy": (C.c_int, [vp]),
     "mgx_dg_solver_smoother_info": (C.c_int, [vp, C.POINTER(SmootherInfo)]),

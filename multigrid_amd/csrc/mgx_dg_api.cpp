@@ -1,8 +1,8 @@
 // mgx_dg_api.cpp -- host side of the DG objects of include/mgx_dg.h: the operator (set-up, ghost exchange, the
 // applications of the cell kernel), MultigridSolverDG on top of an FE_Q hierarchy, the DG-to-DG level transfer
 // object and MultigridSolverDGPlain.  No kernel lives here: the cell kernel and its launch are mgx_dg_kernels.hip
-// (DG section of mgx_internal.hpp), the level transfer kernels mgx_dg_transfer.hip, the fp64 numerics of the set-up
-// mgx_dg_host.cpp.
+// (DG section of mgx_internal.hpp), the level transfer kernels mgx_dg_transfer.hip, the kernels of the right-hand side
+// with boundary data and of the L2 error mgx_dg_rhs.hip, the fp64 numerics of the set-up mgx_dg_host.cpp.
 #include "mgx_device_memory.hpp"
 #include "mgx_dg_host.hpp"
 #include "mgx_internal.hpp"
@@ -52,6 +52,12 @@ struct mgx_dg_operator_s
   // block sums of the merged CG iteration (action 2) and their total, allocated at the first use
   double  *cg_partials = nullptr, *cg_sums = nullptr;
   uint32_t cg_capacity = 0;
+  // right-hand side and L2 error (mgx_dg_compute_rhs, mgx_dg_compute_l2_error): the Jacobian as [d * 3 + a], whether a
+  // cell has a Dirichlet face, and the cell positions of mgx_dg_operator_set_cell_positions (device [n_cells][dim])
+  double   jac[9]        = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  bool     has_dirichlet = false;
+  int32_t *cell_pos      = nullptr;
+  double   origin[3]     = {0, 0, 0};
 };
 
 // MultigridSolverDG (common/multigrid_solver_dg.h:55-747): the DG level on top of an FE_Q hierarchy
@@ -228,6 +234,22 @@ namespace
       status = launch_cells(op, boundary, side);
     const int joined = mgx::side_stream_end(op->ctx);
     return status != MGX_OK ? status : joined;
+  }
+
+  // room for the four sums of `blocks` workgroups (cg_partials) and for their total (cg_sums)
+  int reserve_block_sums(mgx_dg_operator_t op, uint32_t blocks)
+  {
+    if (blocks > op->cg_capacity)
+      {
+        op->mem.release(op->cg_partials);
+        op->cg_partials = nullptr;
+        op->cg_capacity = 0;
+        MGX_TRY(op->mem.alloc(&op->cg_partials, 4 * (size_t)blocks));
+        op->cg_capacity = blocks;
+      }
+    if (!op->cg_sums)
+      MGX_TRY(op->mem.alloc(&op->cg_sums, 4));
+    return MGX_OK;
   }
 
   // ---- stages of mgx_dg_operator_create ----
@@ -452,6 +474,11 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
   std::vector<double> table;
   MGX_TRY(build_inverse_diagonal(*op, n3, table));
   MGX_TRY(op->mem.upload(&op->neigh, desc->neighbours, 2 * (size_t)dim * desc->n_cells));
+  for (int d = 0; d < dim; ++d)
+    for (int a = 0; a < dim; ++a)
+      op->jac[d * 3 + a] = desc->jacobian[d * dim + a];
+  op->has_dirichlet = std::find(desc->neighbours, desc->neighbours + 2 * (size_t)dim * desc->n_cells, MGX_DG_BOUNDARY) !=
+                      desc->neighbours + 2 * (size_t)dim * desc->n_cells;
   if (op->n_ghost > 0)
     {
       MGX_TRY(upload_exchange_plan(*op, desc));
@@ -542,16 +569,7 @@ int mgx_dg_vmult_with_cg_update(mgx_dg_operator_t op, double alpha, double beta,
   const uint32_t blocks = split ? cell_grid(op->number, op->degree, op->n_interior, op->dim) +
                                     cell_grid(op->number, op->degree, op->n_boundary, op->dim)
                                 : cell_grid(op->number, op->degree, op->n_cells, op->dim);
-  if (blocks > op->cg_capacity)
-    {
-      op->mem.release(op->cg_partials);
-      op->cg_partials = nullptr;
-      op->cg_capacity = 0;
-      MGX_TRY(op->mem.alloc(&op->cg_partials, 4 * (size_t)blocks));
-      op->cg_capacity = blocks;
-    }
-  if (!op->cg_sums)
-    MGX_TRY(op->mem.alloc(&op->cg_sums, 4));
+  MGX_TRY(reserve_block_sums(op, blocks));
   // laplace_operator_dg.h:871-902: x += alpha p ; p = beta p + q (alpha == 0: p = q) on the owned entries
   mgx::launch_cg_pre(s, op->number, x, p, q, alpha, beta, (size_t)mgx_dg_operator_n_dofs(op));
   // :903 q = A p with the sums of the next iteration
@@ -586,16 +604,7 @@ int mgx_dg_vmult_with_pcg_sums(mgx_dg_operator_t op, const void *r, void *q, con
   const uint32_t blocks = split ? cell_grid(op->number, op->degree, op->n_interior, op->dim) +
                                     cell_grid(op->number, op->degree, op->n_boundary, op->dim)
                                 : cell_grid(op->number, op->degree, op->n_cells, op->dim);
-  if (blocks > op->cg_capacity)
-    {
-      op->mem.release(op->cg_partials);
-      op->cg_partials = nullptr;
-      op->cg_capacity = 0;
-      MGX_TRY(op->mem.alloc(&op->cg_partials, 4 * (size_t)blocks));
-      op->cg_capacity = blocks;
-    }
-  if (!op->cg_sums)
-    MGX_TRY(op->mem.alloc(&op->cg_sums, 4));
+  MGX_TRY(reserve_block_sums(op, blocks));
   // without the overlap of the ghost exchange the cells run in one launch: its blocks are not the split's
   MGX_HIP(hipMemsetAsync(op->cg_partials, 0, sizeof(double) * 4 * (size_t)blocks, s));
   DGLaunch l(kPcgSums, q, r, p);
@@ -637,6 +646,137 @@ int mgx_dg_operator_basis(mgx_dg_operator_t op, double *shape_values, double *qu
     std::copy(op->h.xq.begin(), op->h.xq.begin() + n, quadrature_points);
   if (quadrature_weights)
     std::copy(op->h.wq.begin(), op->h.wq.begin() + n, quadrature_weights);
+  return MGX_OK;
+}
+
+} // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * right-hand side with boundary data, L2 error (kernels: mgx_dg_rhs.hip)
+ * --------------------------------------------------------------------------------------------- */
+namespace
+{
+  DGRhsOperands rhs_operands(mgx_dg_operator_t op)
+  {
+    DGRhsOperands o;
+    o.number = op->number, o.degree = op->degree, o.dim = op->dim;
+    o.neigh = op->neigh, o.consts = op->consts, o.cell_pos = op->cell_pos, o.n_cells = op->n_cells;
+    DGRhsGeometry &g = o.geo;
+    std::copy(op->jac, op->jac + 9, g.jac);
+    std::copy(op->origin, op->origin + 3, g.origin);
+    for (int q = 0; q < kMaxN; ++q)
+      {
+        g.xq[q] = q < op->h.n ? op->h.xq[q] : 0.0;
+        g.wq[q] = q < op->h.n ? op->h.wq[q] : 0.0;
+      }
+    const double *J = op->jac;
+    g.det           = std::fabs(op->dim == 2 ? J[0] * J[4] - J[1] * J[3]
+                                             : J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) +
+                                       J[2] * (J[3] * J[7] - J[4] * J[6]));
+    for (int d = 0; d < 3; ++d)
+      {
+        g.sigma[d] = op->g.sigma[d];
+        g.fw[d]    = op->g.fw[d];
+        for (int a = 0; a < 3; ++a)
+          g.cn[d][a] = op->g.cn[d][a];
+      }
+    return o;
+  }
+
+  // a function of the C ABI as the kernels take it.  role: "f", "g" or "u" -- g reads the face values, the others the
+  // cell values.  NULL: zero.
+  int function_args(mgx_dg_operator_t op, const char *entry, const char *role, const mgx_dg_function *fn, DGFunctionArgs &out)
+  {
+    out = DGFunctionArgs{};
+    if (!fn)
+      return MGX_OK;
+    const std::string who = std::string(entry) + ": function " + role;
+    if (fn->kind == MGX_DG_FN_SINE_PRODUCT)
+      {
+        if (dg_desc_dim(fn->dim) != op->dim)
+          return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + " is a sine product of dim " + std::to_string(fn->dim) + ", the operator has " +
+                                                     std::to_string(op->dim) + " dimensions");
+        if (!op->cell_pos)
+          return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + " is a sine product and needs coordinates: call "
+                                                         "mgx_dg_operator_set_cell_positions first");
+        out.kind      = MGX_DG_FN_SINE_PRODUCT;
+        out.amplitude = fn->amplitude;
+        for (int d = 0; d < op->dim; ++d)
+          {
+            if (!std::isfinite(fn->wave[d]) || !std::isfinite(fn->phase[d]))
+              return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + ": wave and phase must be finite");
+            out.wave[d]  = fn->wave[d];
+            out.phase[d] = fn->phase[d];
+          }
+        return MGX_OK;
+      }
+    if (fn->kind != MGX_DG_FN_SAMPLED)
+      return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + ": kind must be MGX_DG_FN_SINE_PRODUCT or MGX_DG_FN_SAMPLED");
+    const bool on_faces = role[0] == 'g';
+    if (on_faces && !fn->face_values)
+      {
+        if (op->has_dirichlet)
+          return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + " is sampled without face_values, but the mesh has Dirichlet faces");
+        return MGX_OK; // no face reads it: as good as none
+      }
+    if (!on_faces && !fn->cell_values)
+      return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + " is sampled without cell_values");
+    out.kind        = MGX_DG_FN_SAMPLED;
+    out.cell_values = fn->cell_values;
+    out.face_values = fn->face_values;
+    return MGX_OK;
+  }
+} // namespace
+
+extern "C" {
+
+int mgx_dg_operator_set_cell_positions(mgx_dg_operator_t op, const double origin[3], const int32_t *cell_pos)
+{
+  MGX_REQUIRE(op && origin && cell_pos, "mgx_dg_operator_set_cell_positions: null argument");
+  for (int d = 0; d < op->dim; ++d)
+    MGX_REQUIRE(std::isfinite(origin[d]), "mgx_dg_operator_set_cell_positions: origin must be finite");
+  // a launch in flight may still read the old table
+  MGX_HIP(hipStreamSynchronize((hipStream_t)mgx_context_stream(op->ctx)));
+  op->mem.release(op->cell_pos);
+  op->cell_pos = nullptr;
+  MGX_TRY(op->mem.upload(&op->cell_pos, cell_pos, (size_t)op->dim * op->n_cells));
+  for (int d = 0; d < 3; ++d)
+    op->origin[d] = d < op->dim ? origin[d] : 0.0;
+  return MGX_OK;
+}
+
+int mgx_dg_compute_rhs(mgx_dg_operator_t op, const mgx_dg_function *f, const mgx_dg_function *g, void *dst)
+{
+  MGX_REQUIRE(op, "mgx_dg_compute_rhs: null operator");
+  MGX_REQUIRE(dst, "mgx_dg_compute_rhs: dst is null");
+  DGFunctionArgs fa, ga;
+  MGX_TRY(function_args(op, "mgx_dg_compute_rhs", "f", f, fa));
+  MGX_TRY(function_args(op, "mgx_dg_compute_rhs", "g", g, ga));
+  if (!launch_dg_rhs((hipStream_t)mgx_context_stream(op->ctx), rhs_operands(op), fa, ga, dst))
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_compute_rhs: no kernel for this degree and dimension");
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_compute_l2_error(mgx_dg_operator_t op, const void *vec, const mgx_dg_function *u, double sums[2])
+{
+  MGX_REQUIRE(op, "mgx_dg_compute_l2_error: null operator");
+  MGX_REQUIRE(vec && sums, "mgx_dg_compute_l2_error: vec or sums is null");
+  MGX_REQUIRE(u, "mgx_dg_compute_l2_error: the function u is null");
+  DGFunctionArgs ua;
+  MGX_TRY(function_args(op, "mgx_dg_compute_l2_error", "u", u, ua));
+  hipStream_t    s      = (hipStream_t)mgx_context_stream(op->ctx);
+  const uint32_t blocks = rhs_grid(op->degree, op->n_cells, op->dim);
+  MGX_TRY(reserve_block_sums(op, blocks));
+  if (!launch_dg_l2_error(s, rhs_operands(op), ua, vec, op->cg_partials))
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_compute_l2_error: no kernel for this degree and dimension");
+  MGX_HIP(hipGetLastError());
+  mgx::launch_reduce4(s, op->cg_partials, blocks, nullptr, op->cg_sums);
+  double all[4];
+  MGX_HIP(hipMemcpyAsync(all, op->cg_sums, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
+  sums[0] = all[0];
+  sums[1] = all[1];
   return MGX_OK;
 }
 

@@ -608,6 +608,36 @@ namespace mgx
     // v[i] = (global index of i mod 11) - mean over n_cells cells of n3 entries; cell_id: global cell numbers or null
     void launch_start_vector(hipStream_t s, int number, void *v, const uint32_t *cell_id, uint32_t n_cells, uint32_t n3,
                              double mean);
+
+    // ---- right-hand side and L2 error on the device (mgx_dg_rhs.hip) ----
+    // a function as the kernels take it: kind MGX_DG_FN_NONE (zero), _SINE_PRODUCT or _SAMPLED (include/mgx_dg.h)
+    struct DGFunctionArgs
+    {
+      int           kind = 0;
+      double        amplitude = 0, wave[3] = {0, 0, 0}, phase[3] = {0, 0, 0};
+      const double *cell_values = nullptr, *face_values = nullptr;
+    };
+    // the doubles of the operator's host data the kernels compute with: the Jacobian ([d * 3 + a], whatever the
+    // dimension) and the origin of x = origin + J (pos + xi), the Gauss rule, |det J| and the face factors of Geometry
+    struct DGRhsGeometry
+    {
+      double jac[9], origin[3], xq[kMaxN], wq[kMaxN], det, sigma[3], fw[3], cn[3][3];
+    };
+    struct DGRhsOperands
+    {
+      int            number = 0, degree = 0, dim = 3;
+      const int32_t *neigh    = nullptr;
+      const void    *consts   = nullptr; // the constant block of the cell kernel: S, D and the end values b, g
+      const int32_t *cell_pos = nullptr; // device [n_cells][dim]; needed by sine products only
+      uint32_t       n_cells  = 0;       // owned cells
+      DGRhsGeometry  geo;
+    };
+    // dst (number type) = int f phi_i + sum over the Dirichlet faces of int g (sigma_F phi_i - d_n phi_i) on the owned
+    // cells; false: no kernel for this degree or dimension
+    bool launch_dg_rhs(hipStream_t s, const DGRhsOperands &op, const DGFunctionArgs &f, const DGFunctionArgs &g, void *dst);
+    // partials [rhs_grid][4]: block sums {sum (u_h - u)^2 JxW, sum JxW, 0, 0}, to be added by launch_reduce4
+    bool     launch_dg_l2_error(hipStream_t s, const DGRhsOperands &op, const DGFunctionArgs &u, const void *vec, double *partials);
+    uint32_t rhs_grid(int p, uint32_t n_cells, int dim); // workgroups of either launch
   } // namespace dg
   // Ritz values -> Chebyshev interval (PreconditionChebyshev::estimate_eigenvalues): given info.lambda_min / lambda_max,
   // sets degree (degree < 0: Varga's estimate for eps = smoothing_range), delta and theta; returns the lower end a =

@@ -17,7 +17,13 @@ whole boundary: its L2 error falls with h^(p+1) (tests/test_gpu_dg_multigrid.py)
 Prints the reference's lines ("Time solve CG", "matvec time dp/sp ... DoFs/s", "L2 error with ndof = ...") and
 the row of its convergence table (cells dofs mv_outer mv_inner cg_L2error cg_time cg_its cg_reduction,
 program.cc:318-325).  Right-hand side and error norm are evaluated on the host (numpy), as the reference does
-on the CPU; everything timed runs on the GPU."""
+on the CPU; everything timed runs on the GPU.
+
+--boundary data: the right-hand side also carries the boundary values of the chosen solution, b_i += int_F u (sigma_F
+phi_i - d_n phi_i) on every Dirichlet face, so the reference solution converges as well.  Right-hand side and error sums
+are then formed on the device (DGLaplaceOperator.compute_rhs / compute_l2_error; the sums are added over the ranks
+here) and a line "Time compute rhs" is printed as the reference prints it (multigrid_solver_dg.h).  The default,
+homogeneous, is the reference's volume-only vector from the host: nothing it prints changes."""
 import argparse
 import os
 import sys
@@ -51,6 +57,8 @@ def main():
                     help="context option (include/mgx.h mgx_context_set_option), e.g. dg_unmerged_restrict=1")
     ap.add_argument("--solution", choices=["reference", "vanishing"], default="reference",
                     help="reference: prod sin(3 pi x_d) as program.cc:95-100; vanishing: zero on the boundary (convergence check)")
+    ap.add_argument("--boundary", choices=["homogeneous", "data"], default="homogeneous",
+                    help="data: boundary values of the solution in the right-hand side; rhs and error on the device")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn(a.gpus)
@@ -104,21 +112,36 @@ def main():
     nc_own = n_own // (a.degree + 1) ** 3
     say("Number of degrees of freedom: %d (%d cells, FE_DGQHermite(%d) on FE_Q(%d) multigrid, V-cycle in %s, %d GPU%s)"
         % (n, nc, a.degree, a.degree, a.vcycle, world, "" if world == 1 else "s"))
-    S, xq, wq = solver.matrix_dg.basis_1d()
-    h = cube.cell_size(cube.max_level)
-    S3 = np.kron(S, np.kron(S, S))
-    w3 = np.kron(wq, np.kron(wq, wq)) * h ** 3
-    x = quad_points(cube, solver.cell_ijk.astype(float), xq, h)
-    if a.solution == "reference":
-        u = np.prod(np.sin(np.pi * WAVE * x), axis=-1)
-        f = 3 * (np.pi * WAVE) ** 2 * u                      # program.cc:137-141
+    on_device = a.boundary == "data"
+    if on_device:
+        kw = np.pi * WAVE if a.solution == "reference" else np.pi * WAVE / 1.9
+        phase = 0.0 if a.solution == "reference" else 0.9 * kw
+        u_dev = mg.DGFunction.sine_product(1.0, (kw,) * 3, (phase,) * 3)
+        f_dev = mg.DGFunction.sine_product(3 * kw ** 2, (kw,) * 3, (phase,) * 3)
+        b, sol = solver.initialize_dof_vector(), solver.initialize_dof_vector()
+        say("Time setup                    %.3f s" % (time.time() - t0))
+        ctx.sync()
+        t = time.perf_counter()
+        solver.matrix_dg_dp.compute_rhs(b, f_dev, u_dev)
+        ctx.sync()
+        dt = slowest(time.perf_counter() - t)
+        say("Time compute rhs              %.6f s   rhs_norm = %.6e" % (dt, np.sqrt(total(float(np.sum(b.download()[:n_own] ** 2))))))
     else:
-        k = np.pi * WAVE / 1.9
-        u = np.prod(np.sin(k * (x + 0.9)), axis=-1)
-        f = 3 * k ** 2 * u
-    rhs = (f * w3) @ S3                                      # multigrid_solver_dg.h:243-262
-    say("Time setup                    %.3f s   rhs_norm = %.6e" % (time.time() - t0, np.sqrt(total(float(np.sum(rhs ** 2))))))
-    b, sol = solver.initialize_dof_vector(rhs.ravel()), solver.initialize_dof_vector()
+        S, xq, wq = solver.matrix_dg.basis_1d()
+        h = cube.cell_size(cube.max_level)
+        S3 = np.kron(S, np.kron(S, S))
+        w3 = np.kron(wq, np.kron(wq, wq)) * h ** 3
+        x = quad_points(cube, solver.cell_ijk.astype(float), xq, h)
+        if a.solution == "reference":
+            u = np.prod(np.sin(np.pi * WAVE * x), axis=-1)
+            f = 3 * (np.pi * WAVE) ** 2 * u                      # program.cc:137-141
+        else:
+            k = np.pi * WAVE / 1.9
+            u = np.prod(np.sin(k * (x + 0.9)), axis=-1)
+            f = 3 * k ** 2 * u
+        rhs = (f * w3) @ S3                                      # multigrid_solver_dg.h:243-262
+        say("Time setup                    %.3f s   rhs_norm = %.6e" % (time.time() - t0, np.sqrt(total(float(np.sum(rhs ** 2))))))
+        b, sol = solver.initialize_dof_vector(rhs.ravel()), solver.initialize_dof_vector()
     time_cg = 1e10
     for _ in range(4):                                          # program.cc:252-258
         ctx.sync()
@@ -128,8 +151,12 @@ def main():
         dt = slowest(time.perf_counter() - t)
         time_cg = min(time_cg, dt)
         say("Time solve CG                 %.6f s   (%d iterations, reduction %.4e)" % (dt, its, red))
-    uh = sol.download()[:n_own].reshape(nc_own, -1) @ S3.T
-    l2 = np.sqrt(total(float(np.sum(w3 * (uh - u) ** 2))) / (nc * h ** 3))    # multigrid_solver_dg.h:328-367
+    if on_device:
+        sums = solver.matrix_dg_dp.compute_l2_error(sol, u_dev)               # this rank's cells
+        l2 = np.sqrt(total(float(sums[0])) / total(float(sums[1])))
+    else:
+        uh = sol.download()[:n_own].reshape(nc_own, -1) @ S3.T
+        l2 = np.sqrt(total(float(np.sum(w3 * (uh - u) ** 2))) / (nc * h ** 3))    # multigrid_solver_dg.h:328-367
     A_dp, A_sp = solver.matrix_dg_dp, solver.matrix_dg
     best = {}
     for name, A, number in (("dp", A_dp, mg.F64), ("sp", A_sp, vnum)):

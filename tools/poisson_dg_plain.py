@@ -6,6 +6,7 @@ The same problem, printed lines and table row as tools/poisson_dg.py, whose solv
 
     python tools/poisson_dg_plain.py [degree=3] [n_refine=5] [n_pre_smooth=3] [tolerance=1e-9] [--vcycle f32|f64]
                                      [--basis 0|1|2] [--solution reference|vanishing] [--levels] [--dim 2|3]
+                                     [--boundary homogeneous|data]
 
 --dim 2: the dimension the reference's driver is compiled for (poisson_dg_plain/program.cc:65): the square [-0.9, 1]^2,
 rhs dim (3 pi)^2 prod sin(3 pi x_d) (program.cc:140), the same printed lines and table row.
@@ -16,7 +17,13 @@ One line per level gives the smoother's degree, lambda_max and the CG iterations
 solve they time is slower than the solves reported above it.
 
 --solution as in tools/poisson_dg.py: the benchmark's own solution does not vanish on the boundary, `vanishing` does
-and shows the discretisation error (tests/test_gpu_dg_plain.py)."""
+and shows the discretisation error (tests/test_gpu_dg_plain.py).
+
+--boundary data: the right-hand side also carries the boundary values of the chosen solution, b_i += int_F u (sigma_F
+phi_i - d_n phi_i) on every Dirichlet face (DGLaplaceOperator.compute_rhs), so the reference solution converges too;
+right-hand side and error are then formed on the device (compute_rhs, compute_l2_error) and a line "Time compute rhs"
+is printed as the reference prints it (multigrid_solver_dg_plain.h:188).  The default, homogeneous, is the reference's
+volume-only vector from the host: nothing it prints changes."""
 import argparse
 import os
 import sys
@@ -41,13 +48,16 @@ def main():
     ap.add_argument("--solution", choices=["reference", "vanishing"], default="reference")
     ap.add_argument("--levels", action="store_true", help="per-level time table of one more (synchronised) solve")
     ap.add_argument("--dim", type=int, choices=[2, 3], default=3)
+    ap.add_argument("--boundary", choices=["homogeneous", "data"], default="homogeneous",
+                    help="data: boundary values of the solution in the right-hand side; rhs and error on the device")
     a = ap.parse_args()
     vnum = mg.F32 if a.vcycle == "f32" else mg.F64
     t0 = time.time()
     ctx = mg.Context(0)
     n_levels = a.n_refine + 1
     dim = a.dim
-    solver = mg.DGPlainMultigridSolver(ctx, a.degree, a.basis, (1,) * dim, np.eye(dim) * 1.9, n_levels, a.n_pre_smooth, vnum)
+    solver = mg.DGPlainMultigridSolver(ctx, a.degree, a.basis, (1,) * dim, np.eye(dim) * 1.9, n_levels, a.n_pre_smooth, vnum,
+                                       origin=(-0.9,) * dim)
     n = solver.m()
     nc = n // (a.degree + 1) ** dim
     print("Number of degrees of freedom: %d (%d cells, FE_DGQHermite(%d) on every one of %d levels, V-cycle in %s)"
@@ -56,6 +66,8 @@ def main():
         i = solver.smoother_info(l)
         print("level %2d  cells %9d  smoother degree %3d  lambda_max %.6f  cg_its %d"
               % (l, int(np.prod(solver.cells[l])), i["degree"], i["lambda_max"], i["cg_its"]))
+    if a.boundary == "data":
+        return with_boundary_data(a, ctx, solver, t0)
     S, xq, wq = solver.matrix_dg_dp.basis_1d()
     h = 1.9 / 2 ** a.n_refine
     S3, w3 = S, wq                                           # tensor products over the dim directions, x fastest
@@ -85,6 +97,43 @@ def main():
         print("Time solve CG                 %.6f s   (%d iterations, reduction %.4e)" % (dt, its, red))
     uh = sol.download()[:n].reshape(nc, -1) @ S3.T
     l2 = np.sqrt(float(np.sum(w3 * (uh - u) ** 2)) / (nc * h ** dim))
+    report(a, ctx, solver, b, sol, l2, time_cg, its, red)
+
+
+def with_boundary_data(a, ctx, solver, t0):
+    """--boundary data: right-hand side with g = u and the error on the device"""
+    dim, A = a.dim, solver.matrix_dg_dp
+    if a.solution == "reference":
+        k, phase = np.pi * WAVE, 0.0
+    else:
+        k = np.pi * WAVE / 1.9
+        phase = 0.9 * k
+    u = mg.DGFunction.sine_product(1.0, (k,) * dim, (phase,) * dim)
+    f = mg.DGFunction.sine_product(dim * k ** 2, (k,) * dim, (phase,) * dim)
+    b, sol = solver.initialize_dof_vector(), solver.initialize_dof_vector()
+    print("Time setup                    %.3f s" % (time.time() - t0))
+    ctx.sync()
+    t = time.perf_counter()
+    A.compute_rhs(b, f, u)
+    ctx.sync()
+    dt = time.perf_counter() - t
+    print("Time compute rhs              %.6f s   rhs_norm = %.6e" % (dt, ctx.l2_norm(b)))
+    time_cg = 1e10
+    for _ in range(4):
+        ctx.sync()
+        t = time.perf_counter()
+        its, red = solver.solve_cg(b, sol, a.tolerance)
+        ctx.sync()
+        dt = time.perf_counter() - t
+        time_cg = min(time_cg, dt)
+        print("Time solve CG                 %.6f s   (%d iterations, reduction %.4e)" % (dt, its, red))
+    sums = A.compute_l2_error(sol, u)                         # one rank: nothing to add up
+    report(a, ctx, solver, b, sol, float(np.sqrt(sums[0] / sums[1])), time_cg, its, red)
+
+
+def report(a, ctx, solver, b, sol, l2, time_cg, its, red):
+    n, n_levels = solver.m(), a.n_refine + 1
+    nc = n // (a.degree + 1) ** a.dim
     if a.levels:
         solver.enable_timings(True)
         solver.solve_cg(b, sol, a.tolerance)
