@@ -2007,11 +2007,12 @@ int mgx_vmult_with_cg_update(mgx_operator_t op, double alpha, double beta, const
 // Cells of a brick level in launches whose cells share no DoF: brick colour by brick colour (bricks of one launch
 // group share no DoF), inside a brick the cells with the same position m mod 8 in Morton order -- the same child of
 // every parent -- do not touch.  64 lists; plain adds in an order that does not depend on the run.
-static void brick_cell_lists(mgx_operator_t op, std::vector<uint32_t> &lists, std::vector<uint32_t> &list_start)
+// The cells go to the device, into memory of `mem` (the caller's: it outlives the launches), the offsets to `list_start`.
+static int brick_cell_lists(mgx_operator_t op, DeviceArena &mem, std::vector<uint32_t> &list_start, CellLists &out)
 {
-  const BrickData &bd = op->d.bricks;
-  const uint32_t   cb = op->d.n_cells / bd.n_bricks; // cells per brick: 64 or 8
-  lists.clear();
+  const BrickData      &bd = op->d.bricks;
+  const uint32_t        cb = op->d.n_cells / bd.n_bricks; // cells per brick: 64 or 8
+  std::vector<uint32_t> lists;
   list_start.assign(1, 0);
   lists.reserve(op->d.n_cells);
   for (int g = 0; g < bd.n_colours; ++g)
@@ -2022,6 +2023,13 @@ static void brick_cell_lists(mgx_operator_t op, std::vector<uint32_t> &lists, st
             lists.push_back(bd.order[pos] * cb + m);
         list_start.push_back((uint32_t)lists.size());
       }
+  hipStream_t s         = op->ctx->stream;
+  uint32_t   *lists_dev = nullptr;
+  MGX_TRY(mem.alloc(&lists_dev, lists.size() + 1));
+  MGX_HIP(hipMemcpyAsync(lists_dev, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice, s));
+  MGX_HIP(hipStreamSynchronize(s)); // (`lists` is pageable host memory in flight until here)
+  out = CellLists(lists_dev, list_start.data(), (int)list_start.size() - 1);
+  return MGX_OK;
 }
 
 int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const void *rhs_q)
@@ -2042,21 +2050,15 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
       src = zero;
     }
   MGX_HIP(hipMemsetAsync(dst, 0, bytes, s));
-  // assembly without atomics, as for the diagonal (mgx_compute_diagonal)
+  // assembly without atomics, as for the diagonal (mgx_compute_diagonal): brick lists, then the cell colours -- only
+  // where there is no ordered assembly --, then the ordered assembly (or atomics)
+  std::vector<uint32_t> list_start;
+  CellLists             lists;
   if (op->d.bricks.available())
-    {
-      std::vector<uint32_t> lists, list_start;
-      brick_cell_lists(op, lists, list_start);
-      uint32_t *lists_dev = nullptr;
-      MGX_TRY(tmp.alloc(&lists_dev, lists.size() + 1));
-      MGX_HIP(hipMemcpyAsync(lists_dev, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice, s));
-      launch_cell_residual(s, op->d, dst, src, rhs_q, lists_dev, list_start.data(), (int)list_start.size() - 1);
-      MGX_HIP(hipStreamSynchronize(s)); // (`lists` is pageable host memory in flight until here)
-    }
+    MGX_TRY(brick_cell_lists(op, tmp, list_start, lists));
   else if (op->d.cell_order && !op->d.asm_start)
-    launch_cell_residual(s, op->d, dst, src, rhs_q, op->d.cell_order, op->d.cell_colour_start, op->d.n_cell_colours);
-  else
-    launch_cell_residual(s, op->d, dst, src, rhs_q);
+    lists = CellLists(op->d);
+  launch_cell_residual(s, op->d, dst, src, rhs_q, lists);
   MGX_HIP(hipGetLastError());
   return exchange_add(op, dst); // dst.compress(add), laplace_operator.h:843
 }
@@ -2162,18 +2164,17 @@ int mgx_compute_nonlinear_residual(mgx_operator_t op, int law, void *dst, const 
   MGX_TRY(require_coefficient_update(op, law, "mgx_compute_nonlinear_residual"));
   hipStream_t s  = op->ctx->stream;
   const bool  ms = law == MGX_LAW_MINIMAL_SURFACE;
-  // atomic-free assembly as in mgx_compute_residual: colour by colour where the level has cell colours, else ordered
-  if (op->d.asm_start)
-    launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state);
-  else if (op->d.cell_order)
-    {
-      MGX_HIP(hipMemsetAsync(dst, 0, number_size(op->d.number) * op->d.n_dofs, s));
-      launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state, op->d.cell_order, op->d.cell_colour_start,
-                              op->d.n_cell_colours);
-    }
-  else
+  // atomic-free assembly only: the ordered assembly where the level has it, else colour by colour
+  if (!op->d.asm_start && !op->d.cell_order)
     return fail(MGX_ERR_UNSUPPORTED, "mgx_compute_nonlinear_residual: the level has neither cell colours nor the ordered-assembly "
                                      "tables (more than 32 colours): no reproducible assembly");
+  CellLists lists; // none: the ordered assembly, which comes first where the level has it (dst is written)
+  if (!op->d.asm_start) // the cell colours: dst is added to
+    {
+      MGX_HIP(hipMemsetAsync(dst, 0, number_size(op->d.number) * op->d.n_dofs, s));
+      lists = CellLists(op->d);
+    }
+  launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state, lists);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -2203,22 +2204,16 @@ int mgx_compute_diagonal(mgx_operator_t op)
   // The cell contributions are added up without atomics, in an order that does not depend on the run:
   // brick levels colour by colour (bricks of one launch group share no DoF; inside a brick the cells
   // with the same position m mod 8 in Morton order -- the same child of every parent -- do not touch),
-  // cell-coloured levels colour by colour, the others through the ordered assembly.
+  // cell-coloured levels colour by colour, the others through the ordered assembly (or with atomics).
+  DeviceArena lists_mem("mgx_compute_diagonal");
+  lists_mem.drain_before_release(s);
+  std::vector<uint32_t> list_start;
+  CellLists             lists;
   if (op->d.bricks.available())
-    {
-      std::vector<uint32_t> lists, list_start;
-      brick_cell_lists(op, lists, list_start);
-      DeviceArena tmp("mgx_compute_diagonal");
-      uint32_t   *lists_dev = nullptr;
-      MGX_TRY(tmp.alloc(&lists_dev, lists.size() + 1));
-      MGX_HIP(hipMemcpyAsync(lists_dev, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice, s));
-      launch_cell_diagonal(s, op->d, op->d.inv_diag, a1d, m1d, lists_dev, list_start.data(), (int)list_start.size() - 1);
-      MGX_HIP(hipStreamSynchronize(s));
-    }
+    MGX_TRY(brick_cell_lists(op, lists_mem, list_start, lists));
   else if (op->d.cell_order)
-    launch_cell_diagonal(s, op->d, op->d.inv_diag, a1d, m1d, op->d.cell_order, op->d.cell_colour_start, op->d.n_cell_colours);
-  else
-    launch_cell_diagonal(s, op->d, op->d.inv_diag, a1d, m1d);
+    lists = CellLists(op->d);
+  launch_cell_diagonal(s, op->d, op->d.inv_diag, a1d, m1d, lists);
   MGX_TRY(exchange_add(op, op->d.inv_diag)); // Vector::compress(add) of the reference's cell_loop
   // set_constrained_entries_to_one + invert (laplace_operator.h:757-765)
   launch_constrained_set(s, op->d.number, op->d.inv_diag, 1.0, op->d.constrained, op->d.n_constrained);

@@ -281,6 +281,39 @@ namespace mgx
                                 bool with_constraints);
 
   // ---- cell loops (mgx_kernels.hip) ----
+  // The cells of the launches of a per-cell kernel: list k is cells[start[k] .. start[k + 1]), and the cells of one list
+  // share no DoF (plain adds).  cells: device; start: host, n + 1 offsets; n == 0: one launch over all cells.
+  struct CellLists
+  {
+    const uint32_t *cells = nullptr;
+    const uint32_t *start = nullptr;
+    int             n     = 0;
+    CellLists() = default;
+    CellLists(const uint32_t *cells_, const uint32_t *start_, int n_) : cells(cells_), start(start_), n(n_) {}
+    // the operator's cell colours (none: all cells)
+    explicit CellLists(const OperatorData &op) : cells(op.cell_order), start(op.cell_colour_start), n(op.n_cell_colours) {}
+  };
+  // The symmetric tensor [xx,yy,zz,xy,xz,yz] a general kernel applies (PERQ decides which it reads): one per cell and
+  // quadrature point, device [n_cells][6][n^3] in the kernel's number type, or one per mesh; the other is null / zero.
+  struct CellTensor
+  {
+    const void *per_point = nullptr;
+    double      c[6]      = {0, 0, 0, 0, 0, 0};
+    static CellTensor at_points(const void *q)
+    {
+      CellTensor t;
+      t.per_point = q;
+      return t;
+    }
+    static CellTensor per_mesh(const double *m)
+    {
+      CellTensor t;
+      std::copy(m, m + 6, t.c);
+      return t;
+    }
+    // the coefficient of an operator of the general branch
+    static CellTensor of(const OperatorData &op) { return op.coef_q ? at_points(op.coef_q) : per_mesh(op.coef); }
+  };
   // dst += A_cells * src  (MatrixFree::cell_loop(local_apply), laplace_operator.h:527-558)
   // op.asm_start (ordered assembly): dst is WRITTEN (no zeroing by the caller), and dst[d] = tail_src[d] for
   // d >= n_head if tail_src is given; otherwise dst must be zero on entry
@@ -425,6 +458,14 @@ namespace mgx
     else
       f(float());
   }
+  // f(T(), std::integral_constant<int, P>()) for the number type and P = p; false: no kernel is built for this degree
+  template <typename F>
+  static bool dispatch_number_degree(int number, int p, F &&f)
+  {
+    bool found = false;
+    dispatch_number(number, [&](auto t) { found = dispatch_degree(p, [&](auto P) { f(t, P); }); });
+    return found;
+  }
   // workgroups of a persistent launch over `count` bricks: as many as are resident at once (wgs_per_cu on every CU of
   // the operator's device); Tunables::macro_wg_x16 sets the number per CU instead (tuning aid)
   inline uint32_t persistent_grid(const OperatorData &op, int wgs_per_cu, uint32_t count)
@@ -436,16 +477,15 @@ namespace mgx
   // dst += sum over the cells of  S^T [ rhs_q - D^T (K D S (-src)) ], src read through idx27_plain; assembly as in
   // launch_cell_diagonal (lists of cells that share no DoF / ordered assembly / atomics).  dst zeroed by the caller.
   void launch_cell_residual(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *rhs_q,
-                            const uint32_t *lists = nullptr, const uint32_t *list_start = nullptr, int n_lists = 0);
+                            const CellLists &lists);
   // MinimalSurfaceOperator::compute_residual (minimal_surface/program.cc:169-197) on affine cells with the metric
   // M = J^-1 J^-T [xx,yy,zz,xy,xz,yz] and det J: dst = - sum over the cells of grad phi_i . a JxW M grad u, a = 1 or
-  // 1 / sqrt(1 + |grad u|^2); src through idx27_plain, dst through idx27.  n_lists > 0: launches over cell lists that share
-  // no DoF (dst zeroed by the caller); n_lists == 0: the operator's ordered assembly (required then, dst written)
+  // 1 / sqrt(1 + |grad u|^2); src through idx27_plain, dst through idx27.  lists.n > 0: launches over cell lists that share
+  // no DoF (dst zeroed by the caller); lists.n == 0: the operator's ordered assembly (required then, dst written)
   // unit_q / jxw_q (device, number type of op; nullptr: affine cells): per-point geometry of curved cells as in
   // launch_evaluate_coefficient -- the flux of a point is a U g, a = 1 or 1 / sqrt(1 + g . U g / JxW_q)
   void launch_cell_nl_residual(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,
-                               const void *unit_q, const void *jxw_q, void *dst, const void *src, const uint32_t *lists = nullptr,
-                               const uint32_t *list_start = nullptr, int n_lists = 0);
+                               const void *unit_q, const void *jxw_q, void *dst, const void *src, const CellLists &lists);
   // ---- solution-dependent coefficients (mgx_nonlinear.hip) ----
   // MinimalSurfaceOperator::evaluate_coefficient (minimal_surface/program.cc:120-165) on affine cells: op.coef_q =
   // JxW_q M (first_time) or JxW_q (M - (M g)(M g)^T / (1 + s)) / sqrt(1 + s), s = g^T M g, g the reference-space
@@ -489,11 +529,10 @@ namespace mgx
   // quadrature-point form of laplace_operator.h:436-523 (12 sweeps)
   // diag += diagonal of the cell matrices (local_compute_diagonal, laplace_operator.h:770-800)
   // a1d[i] = sum_q w_q (dphi_i(x_q))^2, m1d[i] = sum_q w_q phi_i(x_q)^2 (host arrays, n entries)
-  // lists / list_start / n_lists: device cell lists of launches whose cells share no DoF (plain adds);
-  // n_lists == 0: ordered assembly if op.asm_start, else one launch with atomic adds
-  void launch_cell_diagonal(hipStream_t s, const OperatorData &op, void *diag, const double *a1d,
-                            const double *m1d, const uint32_t *lists = nullptr, const uint32_t *list_start = nullptr,
-                            int n_lists = 0);
+  // lists: launches whose cells share no DoF (plain adds); lists.n == 0: ordered assembly if op.asm_start, else one
+  // launch with atomic adds
+  void launch_cell_diagonal(hipStream_t s, const OperatorData &op, void *diag, const double *a1d, const double *m1d,
+                            const CellLists &lists);
   // transfers
   void launch_prolongate(hipStream_t s, const TransferData &t, void *fine, const void *coarse, bool add,
                          bool with_constraints);

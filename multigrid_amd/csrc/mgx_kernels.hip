@@ -1030,10 +1030,58 @@ namespace mgx
 
   void launch_assemble(hipStream_t s, const OperatorData &op, int mode, void *dst, const void *tail_src, uint32_t n_head)
   {
-    if (op.number == 1)
-      assemble_t<double>(s, op, mode, dst, tail_src, n_head);
-    else
-      assemble_t<float>(s, op, mode, dst, tail_src, n_head);
+    dispatch_number(op.number, [&](auto t) { assemble_t<decltype(t)>(s, op, mode, dst, tail_src, n_head); });
+  }
+
+  // The list loop of the per-cell kernels: launch(list, count, scratch) once per non-empty list of cells that share no
+  // DoF (plain adds); with no lists once over all cells, into the scratch array of the ordered assembly if `ordered`
+  // (the caller assembles), else with atomic adds.  Returns the scratch array the launch wrote, or nullptr.
+  template <typename T, typename F>
+  static T *for_each_cell_list(const OperatorData &op, const CellLists &lists, bool ordered, F &&launch)
+  {
+    T *scratch = (lists.n == 0 && ordered) ? (T *)op.cell_scratch : nullptr;
+    if (lists.n == 0 && op.n_cells > 0)
+      launch((const uint32_t *)nullptr, op.n_cells, scratch);
+    for (int k = 0; k < lists.n; ++k)
+      if (const uint32_t count = lists.start[k + 1] - lists.start[k])
+        launch(lists.cells + lists.start[k], count, scratch);
+    return scratch;
+  }
+
+  // One launch of the general per-cell kernel (cell_loop_general_kernel), in the names of its comment.
+  enum CellForm
+  {
+    kCellApply          = 0, // dst += A src
+    kCellResidual       = 1, // RESID
+    kCellMinimalSurface = 2  // RESID and MINSURF
+  };
+  struct GeneralLaunch
+  {
+    CellForm        form = kCellApply;
+    void           *dst  = nullptr;
+    const void     *src  = nullptr;
+    CellTensor      tensor;               // at points: PERQ
+    const uint32_t *idx_gather = nullptr; // residual forms: the table the source is read through
+    const void     *rhs_q      = nullptr; // kCellResidual (may be null)
+    double          det        = 0.;      // kCellMinimalSurface, one tensor per mesh
+    const void     *jxw_q      = nullptr; // kCellMinimalSurface, tensor at points
+  };
+  // ... over `count` cells: those of `list`, or all; the one place that selects PERQ x (RESID, MINSURF)
+  template <int P, typename T>
+  static void launch_general_cells(hipStream_t s, const OperatorData &op, const GeneralLaunch &g, const uint32_t *list,
+                                   uint32_t count, T *scratch)
+  {
+    using C              = Cfg<P, MGX_GENERAL_WG_THREADS>;
+    const uint32_t    nb = (count + C::CPB - 1) / C::CPB;
+    const CellTensor &t  = g.tensor;
+    dispatch_mode<kCellApply, kCellResidual, kCellMinimalSurface>(g.form, [&](auto FORM) {
+      dispatch_mode<0, 1>(t.per_point != nullptr, [&](auto PERQ) {
+        hipLaunchKernelGGL((cell_loop_general_kernel<P, T, PERQ.value != 0, FORM.value != kCellApply, FORM.value == kCellMinimalSurface>),
+                           dim3(nb), dim3(C::THREADS), 0, s, (T *)g.dst, (const T *)g.src, op.idx27, count,
+                           (const Basis1D<T> *)op.basis, (const T *)t.per_point, (T)t.c[0], (T)t.c[1], (T)t.c[2], (T)t.c[3],
+                           (T)t.c[4], (T)t.c[5], list, scratch, g.idx_gather, (const T *)g.rhs_q, (T)g.det, (const T *)g.jxw_q);
+      });
+    });
   }
 
   // Three ways to add the cell contributions up (op decides): ordered assembly through the scratch
@@ -1048,27 +1096,13 @@ namespace mgx
     T             *scratch = op.asm_start ? (T *)op.cell_scratch : nullptr;
     if (op.coef_q || op.full_tensor)
       {
-        using C = Cfg<P, MGX_GENERAL_WG_THREADS>;
-        const bool coloured = op.cell_order && !scratch;
-        const int  n_launch = coloured ? op.n_cell_colours : 1;
-        for (int k = 0; k < n_launch; ++k)
-          {
-            const uint32_t  first = coloured ? op.cell_colour_start[k] : 0;
-            const uint32_t  count = coloured ? op.cell_colour_start[k + 1] - first : op.n_cells;
-            const uint32_t *list  = coloured ? op.cell_order + first : nullptr;
-            const uint32_t  nbk   = (count + C::CPB - 1) / C::CPB;
-            if (count == 0)
-              continue;
-            if (op.coef_q)
-              hipLaunchKernelGGL((cell_loop_general_kernel<P, T, true>), dim3(nbk), dim3(C::THREADS), 0, s, (T *)dst,
-                                 (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)op.coef_q, (T)0,
-                                 (T)0, (T)0, (T)0, (T)0, (T)0, list, scratch);
-            else
-              hipLaunchKernelGGL((cell_loop_general_kernel<P, T, false>), dim3(nbk), dim3(C::THREADS), 0, s, (T *)dst,
-                                 (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)nullptr,
-                                 (T)op.coef[0], (T)op.coef[1], (T)op.coef[2], (T)op.coef[3], (T)op.coef[4], (T)op.coef[5],
-                                 list, scratch);
-          }
+        GeneralLaunch g;
+        g.dst    = dst;
+        g.src    = src;
+        g.tensor = CellTensor::of(op);
+        // the operator's cell colours only when there is no ordered assembly
+        for_each_cell_list<T>(op, scratch ? CellLists() : CellLists(op), scratch != nullptr,
+                              [&](const uint32_t *list, uint32_t count, T *scr) { launch_general_cells<P, T>(s, op, g, list, count, scr); });
       }
     else
       hipLaunchKernelGGL((cell_loop_kernel<P, T>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst, (const T *)src,
@@ -1217,27 +1251,17 @@ namespace mgx
   {
     if (n_cells == 0)
       return;
-    if (number == 1)
-      {
-        dispatch_degree(p, [&](auto P) { dg_cg_transfer_t<P.value, double>(s, to_dg, dst, src, idx27, n_cells, P1, eight_colours); });
-      }
-    else
-      {
-        dispatch_degree(p, [&](auto P) { dg_cg_transfer_t<P.value, float>(s, to_dg, dst, src, idx27, n_cells, P1, eight_colours); });
-      }
+    dispatch_number_degree(number, p, [&](auto t, auto P) {
+      dg_cg_transfer_t<P.value, decltype(t)>(s, to_dg, dst, src, idx27, n_cells, P1, eight_colours);
+    });
   }
 
   void launch_cell_loop(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *tail_src,
                         uint32_t n_head, const ChebPost *post)
   {
-    if (op.number == 1)
-      {
-        dispatch_degree(op.p, [&](auto P) { cell_loop_t<P.value, double>(s, op, dst, src, tail_src, n_head, post); });
-      }
-    else
-      {
-        dispatch_degree(op.p, [&](auto P) { cell_loop_t<P.value, float>(s, op, dst, src, tail_src, n_head, post); });
-      }
+    dispatch_number_degree(op.number, op.p, [&](auto t, auto P) {
+      cell_loop_t<P.value, decltype(t)>(s, op, dst, src, tail_src, n_head, post);
+    });
   }
 
   // the general operator on its brick schedule (brick_general_kernel): interior DoFs to dst, the bricks' private
@@ -1245,29 +1269,23 @@ namespace mgx
   void launch_general_bricks(hipStream_t s, const OperatorData &op, void *dst, const void *src)
   {
     const BrickData &g = op.gbricks;
-    auto run = [&](auto number) {
+    const CellTensor t = CellTensor::of(op);
+    dispatch_number(op.number, [&](auto number) {
       using T = decltype(number);
-      if (op.coef_q)
-        hipLaunchKernelGGL((brick_general_kernel<4, T, true>), dim3(g.n_bricks), dim3(256), 0, s, (T *)dst, (const T *)src, op.idx27,
-                           g.fr.ent, g.fr.surf_off, g.item_map, g.order_dev, g.n_bricks, (const Basis1D<T> *)op.basis, (const T *)op.coef_q,
-                           (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T *)g.fr.priv, g.fr.n_surf, (uint32_t)((size_t)op.n_dofs * sizeof(T)));
-      else
-        hipLaunchKernelGGL((brick_general_kernel<4, T, false>), dim3(g.n_bricks), dim3(256), 0, s, (T *)dst, (const T *)src, op.idx27,
-                           g.fr.ent, g.fr.surf_off, g.item_map, g.order_dev, g.n_bricks, (const Basis1D<T> *)op.basis, (const T *)nullptr,
-                           (T)op.coef[0], (T)op.coef[1], (T)op.coef[2], (T)op.coef[3], (T)op.coef[4], (T)op.coef[5],
-                           (T *)g.fr.priv, g.fr.n_surf, (uint32_t)((size_t)op.n_dofs * sizeof(T)));
-    };
-    if (op.number == 1)
-      run(double());
-    else
-      run(float());
+      dispatch_mode<0, 1>(t.per_point != nullptr, [&](auto PERQ) {
+        hipLaunchKernelGGL((brick_general_kernel<4, T, PERQ.value != 0>), dim3(g.n_bricks), dim3(256), 0, s, (T *)dst, (const T *)src,
+                           op.idx27, g.fr.ent, g.fr.surf_off, g.item_map, g.order_dev, g.n_bricks, (const Basis1D<T> *)op.basis,
+                           (const T *)t.per_point, (T)t.c[0], (T)t.c[1], (T)t.c[2], (T)t.c[3], (T)t.c[4], (T)t.c[5], (T *)g.fr.priv,
+                           g.fr.n_surf, (uint32_t)((size_t)op.n_dofs * sizeof(T)));
+      });
+    });
   }
 
-  // lists[k] .. lists[k + 1]: device cell lists of n_lists launches whose cells share no DoF (plain
-  // adds); n_lists == 0: ordered assembly if the operator has the tables, else one launch with atomics
+  // lists: launches whose cells share no DoF (plain adds); none: ordered assembly if the operator has the tables, else
+  // one launch with atomics
   template <int P, typename T>
   static void cell_diag_t(hipStream_t s, const OperatorData &op, void *diag, const double *a, const double *m,
-                          const uint32_t *lists, const uint32_t *list_start, int n_lists)
+                          const CellLists &lists)
   {
     constexpr int N = P + 1;
     Diag1D<T>     d1;
@@ -1276,85 +1294,55 @@ namespace mgx
         d1.a[i] = (T)a[i];
         d1.m[i] = (T)m[i];
       }
-    T        *scratch  = (n_lists == 0 && op.asm_start) ? (T *)op.cell_scratch : nullptr;
-    const int n_launch = n_lists > 0 ? n_lists : 1;
-    for (int k = 0; k < n_launch; ++k)
-      {
-        const uint32_t  count = n_lists > 0 ? list_start[k + 1] - list_start[k] : op.n_cells;
-        const uint32_t *list  = n_lists > 0 ? lists + list_start[k] : nullptr;
-        if (count == 0)
-          continue;
-        const uint64_t nthreads = (uint64_t)count * N * N;
-        const uint32_t nb       = (uint32_t)((nthreads + 255) / 256);
-        if (op.coef_q)
-          hipLaunchKernelGGL((cell_diagonal_general_kernel<P, T, true>), dim3(nb), dim3(256), 0, s, (T *)diag, op.idx27, count,
-                             (const Basis1D<T> *)op.basis, (const T *)op.grad_1d, (const T *)op.coef_q, (T)0, (T)0, (T)0,
-                             (T)0, (T)0, (T)0, list, scratch);
-        else if (op.full_tensor)
-          hipLaunchKernelGGL((cell_diagonal_general_kernel<P, T, false>), dim3(nb), dim3(256), 0, s, (T *)diag, op.idx27, count,
-                             (const Basis1D<T> *)op.basis, (const T *)op.grad_1d, (const T *)nullptr, (T)op.coef[0],
-                             (T)op.coef[1], (T)op.coef[2], (T)op.coef[3], (T)op.coef[4], (T)op.coef[5], list, scratch);
-        else
-          hipLaunchKernelGGL((cell_diagonal_kernel<P, T>), dim3(nb), dim3(256), 0, s, (T *)diag, op.idx27, count, d1,
-                             (T)op.coef[0], (T)op.coef[1], (T)op.coef[2], list, scratch);
-      }
+    const CellTensor t = CellTensor::of(op);
+    // no lists: through the scratch array only where the operator has the tables of the ordered assembly, else atomics
+    T *scratch = for_each_cell_list<T>(op, lists, op.asm_start != nullptr, [&](const uint32_t *list, uint32_t count, T *scr) {
+      const uint64_t nthreads = (uint64_t)count * N * N;
+      const uint32_t nb       = (uint32_t)((nthreads + 255) / 256);
+      if (op.coef_q || op.full_tensor)
+        dispatch_mode<0, 1>(t.per_point != nullptr, [&](auto PERQ) {
+          hipLaunchKernelGGL((cell_diagonal_general_kernel<P, T, PERQ.value != 0>), dim3(nb), dim3(256), 0, s, (T *)diag, op.idx27,
+                             count, (const Basis1D<T> *)op.basis, (const T *)op.grad_1d, (const T *)t.per_point, (T)t.c[0],
+                             (T)t.c[1], (T)t.c[2], (T)t.c[3], (T)t.c[4], (T)t.c[5], list, scr);
+        });
+      else
+        hipLaunchKernelGGL((cell_diagonal_kernel<P, T>), dim3(nb), dim3(256), 0, s, (T *)diag, op.idx27, count, d1,
+                           (T)op.coef[0], (T)op.coef[1], (T)op.coef[2], list, scr);
+    });
     if (scratch)
       assemble_t<T>(s, op, 0, diag, nullptr, 0u);
   }
 
   void launch_cell_diagonal(hipStream_t s, const OperatorData &op, void *diag, const double *a, const double *m,
-                            const uint32_t *lists, const uint32_t *list_start, int n_lists)
+                            const CellLists &lists)
   {
-    if (op.number == 1)
-      {
-        dispatch_degree(op.p, [&](auto P) { cell_diag_t<P.value, double>(s, op, diag, a, m, lists, list_start, n_lists); });
-      }
-    else
-      {
-        dispatch_degree(op.p, [&](auto P) { cell_diag_t<P.value, float>(s, op, diag, a, m, lists, list_start, n_lists); });
-      }
+    dispatch_number_degree(op.number, op.p, [&](auto t, auto P) { cell_diag_t<P.value, decltype(t)>(s, op, diag, a, m, lists); });
   }
 
   // compute_residual (cell_loop_general_kernel, RESID) with the assembly variants of the diagonal above
   template <int P, typename T>
   static void cell_residual_t(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *rhs_q,
-                              const uint32_t *lists, const uint32_t *list_start, int n_lists)
+                              const CellLists &lists)
   {
-    using C            = Cfg<P, MGX_GENERAL_WG_THREADS>;
-    T        *scratch  = (n_lists == 0 && op.asm_start) ? (T *)op.cell_scratch : nullptr;
-    const int n_launch = n_lists > 0 ? n_lists : 1;
-    for (int k = 0; k < n_launch; ++k)
-      {
-        const uint32_t  count = n_lists > 0 ? list_start[k + 1] - list_start[k] : op.n_cells;
-        const uint32_t *list  = n_lists > 0 ? lists + list_start[k] : nullptr;
-        if (count == 0)
-          continue;
-        const uint32_t nb = (count + C::CPB - 1) / C::CPB;
-        if (op.coef_q)
-          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst, (const T *)src,
-                             op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)op.coef_q, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0,
-                             list, scratch, op.idx27_plain, (const T *)rhs_q);
-        else
-          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, false, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst,
-                             (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)nullptr, (T)op.coef[0],
-                             (T)op.coef[1], (T)op.coef[2], (T)op.coef[3], (T)op.coef[4], (T)op.coef[5], list, scratch,
-                             op.idx27_plain, (const T *)rhs_q);
-      }
+    GeneralLaunch g;
+    g.form       = kCellResidual;
+    g.dst        = dst;
+    g.src        = src;
+    g.tensor     = CellTensor::of(op);
+    g.idx_gather = op.idx27_plain;
+    g.rhs_q      = rhs_q;
+    // no lists: through the scratch array only where the operator has the tables of the ordered assembly, else atomics
+    T *scratch = for_each_cell_list<T>(op, lists, op.asm_start != nullptr, [&](const uint32_t *list, uint32_t count, T *scr) {
+      launch_general_cells<P, T>(s, op, g, list, count, scr);
+    });
     if (scratch)
       assemble_t<T>(s, op, 0, dst, nullptr, 0u);
   }
 
   void launch_cell_residual(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *rhs_q,
-                            const uint32_t *lists, const uint32_t *list_start, int n_lists)
+                            const CellLists &lists)
   {
-    if (op.number == 1)
-      {
-        dispatch_degree(op.p, [&](auto P) { cell_residual_t<P.value, double>(s, op, dst, src, rhs_q, lists, list_start, n_lists); });
-      }
-    else
-      {
-        dispatch_degree(op.p, [&](auto P) { cell_residual_t<P.value, float>(s, op, dst, src, rhs_q, lists, list_start, n_lists); });
-      }
+    dispatch_number_degree(op.number, op.p, [&](auto t, auto P) { cell_residual_t<P.value, decltype(t)>(s, op, dst, src, rhs_q, lists); });
   }
 
   // MinimalSurfaceOperator::compute_residual (minimal_surface/program.cc:169-197) on affine cells: the residual form of
@@ -1363,53 +1351,40 @@ namespace mgx
   // passes cell lists or the operator has the ordered-assembly tables)
   template <int P, typename T>
   static void cell_nl_residual_t(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *M, double det,
-                                 const void *unit_q, const void *jxw_q, void *dst, const void *src, const uint32_t *lists,
-                                 const uint32_t *list_start, int n_lists)
+                                 const void *unit_q, const void *jxw_q, void *dst, const void *src, const CellLists &lists)
   {
-    using C            = Cfg<P, MGX_GENERAL_WG_THREADS>;
-    T        *scratch  = n_lists == 0 ? (T *)op.cell_scratch : nullptr;
-    const int n_launch = n_lists > 0 ? n_lists : 1;
-    for (int k = 0; k < n_launch; ++k)
+    GeneralLaunch g;
+    g.form       = minimal_surface ? kCellMinimalSurface : kCellResidual;
+    g.dst        = dst;
+    g.src        = src;
+    g.idx_gather = op.idx27_plain;
+    if (unit_q) // curved cells: U at every point (the unit law is the per-point residual form with coef_q = U)
       {
-        const uint32_t  count = n_lists > 0 ? list_start[k + 1] - list_start[k] : op.n_cells;
-        const uint32_t *list  = n_lists > 0 ? lists + list_start[k] : nullptr;
-        if (count == 0)
-          continue;
-        const uint32_t nb = (count + C::CPB - 1) / C::CPB;
-        if (unit_q && minimal_surface) // curved cells
-          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, true, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst,
-                             (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)unit_q, (T)0, (T)0, (T)0, (T)0,
-                             (T)0, (T)0, list, scratch, op.idx27_plain, (const T *)nullptr, (T)0, (const T *)jxw_q);
-        else if (unit_q) // ... unit law: the per-point residual form with coef_q = U
-          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst, (const T *)src,
-                             op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)unit_q, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0,
-                             list, scratch, op.idx27_plain, (const T *)nullptr);
-        else if (minimal_surface)
-          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, false, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst,
-                             (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)nullptr, (T)M[0], (T)M[1],
-                             (T)M[2], (T)M[3], (T)M[4], (T)M[5], list, scratch, op.idx27_plain, (const T *)nullptr, (T)det);
-        else
-          hipLaunchKernelGGL((cell_loop_general_kernel<P, T, false, true>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst,
-                             (const T *)src, op.idx27, count, (const Basis1D<T> *)op.basis, (const T *)nullptr, (T)(det * M[0]),
-                             (T)(det * M[1]), (T)(det * M[2]), (T)(det * M[3]), (T)(det * M[4]), (T)(det * M[5]), list, scratch,
-                             op.idx27_plain, (const T *)nullptr);
+        g.tensor = CellTensor::at_points(unit_q);
+        g.jxw_q  = minimal_surface ? jxw_q : nullptr;
       }
+    else if (minimal_surface) // M and det J: the kernel forms the flux
+      {
+        g.tensor = CellTensor::per_mesh(M);
+        g.det    = det;
+      }
+    else
+      for (int k = 0; k < 6; ++k)
+        g.tensor.c[k] = det * M[k];
+    // no lists: always through the scratch array (the caller has checked that the operator has the tables)
+    T *scratch = for_each_cell_list<T>(op, lists, true, [&](const uint32_t *list, uint32_t count, T *scr) {
+      launch_general_cells<P, T>(s, op, g, list, count, scr);
+    });
     if (scratch)
       assemble_t<T>(s, op, 0, dst, nullptr, 0u);
   }
 
   void launch_cell_nl_residual(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,
-                               const void *unit_q, const void *jxw_q, void *dst, const void *src, const uint32_t *lists,
-                               const uint32_t *list_start, int n_lists)
+                               const void *unit_q, const void *jxw_q, void *dst, const void *src, const CellLists &lists)
   {
-    if (op.number == 1)
-      {
-        dispatch_degree(op.p, [&](auto P) { cell_nl_residual_t<P.value, double>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists, list_start, n_lists); });
-      }
-    else
-      {
-        dispatch_degree(op.p, [&](auto P) { cell_nl_residual_t<P.value, float>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists, list_start, n_lists); });
-      }
+    dispatch_number_degree(op.number, op.p, [&](auto t, auto P) {
+      cell_nl_residual_t<P.value, decltype(t)>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists);
+    });
   }
 
   template <int P, typename T>
@@ -1428,14 +1403,9 @@ namespace mgx
   {
     if (t.patch)
       return launch_prolongate_pipe(s, t, fine, coarse, add, with_constraints);
-    if (t.coarse->number == 1)
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { prolongate_t<P.value, double>(s, t, fine, coarse, add, with_constraints); });
-      }
-    else
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { prolongate_t<P.value, float>(s, t, fine, coarse, add, with_constraints); });
-      }
+    dispatch_number_degree(t.coarse->number, t.coarse->p, [&](auto number, auto P) {
+      prolongate_t<P.value, decltype(number)>(s, t, fine, coarse, add, with_constraints);
+    });
   }
 
   template <int P, typename T>
@@ -1454,13 +1424,8 @@ namespace mgx
   {
     if (t.patch)
       return launch_restrict_add_pipe(s, t, coarse, fine, with_constraints);
-    if (t.coarse->number == 1)
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { restrict_t<P.value, double>(s, t, coarse, fine, with_constraints); });
-      }
-    else
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { restrict_t<P.value, float>(s, t, coarse, fine, with_constraints); });
-      }
+    dispatch_number_degree(t.coarse->number, t.coarse->p, [&](auto number, auto P) {
+      restrict_t<P.value, decltype(number)>(s, t, coarse, fine, with_constraints);
+    });
   }
 } // namespace mgx

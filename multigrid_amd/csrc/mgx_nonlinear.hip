@@ -334,42 +334,34 @@ namespace mgx
   {
     using C           = Cfg<P>;
     const uint32_t nb = (op.n_cells + C::CPB - 1) / C::CPB;
-    if (unit_q) // curved cells
-      {
-        if (minimal_surface)
-          hipLaunchKernelGGL((evaluate_coefficient_kernel<P, T, TO, true, true>), dim3(nb), dim3(C::THREADS), 0, s, (TO *)coef_q,
-                             (const T *)state, op.idx27_plain, op.n_cells, (const Basis1D<T> *)op.basis, (T)0, (T)0, (T)0, (T)0, (T)0,
-                             (T)0, (T)0, (const T *)unit_q, (const T *)jxw_q);
-        else
-          hipLaunchKernelGGL((evaluate_coefficient_kernel<P, T, TO, false, true>), dim3(nb), dim3(C::THREADS), 0, s, (TO *)coef_q,
-                             (const T *)state, op.idx27_plain, op.n_cells, (const Basis1D<T> *)op.basis, (T)0, (T)0, (T)0, (T)0, (T)0,
-                             (T)0, (T)0, (const T *)unit_q, (const T *)jxw_q);
-      }
-    else if (minimal_surface)
-      hipLaunchKernelGGL((evaluate_coefficient_kernel<P, T, TO, true>), dim3(nb), dim3(C::THREADS), 0, s, (TO *)coef_q,
-                         (const T *)state, op.idx27_plain, op.n_cells, (const Basis1D<T> *)op.basis, (T)M[0], (T)M[1], (T)M[2],
-                         (T)M[3], (T)M[4], (T)M[5], (T)det);
-    else
-      hipLaunchKernelGGL((evaluate_coefficient_kernel<P, T, TO, false>), dim3(nb), dim3(C::THREADS), 0, s, (TO *)coef_q,
-                         (const T *)state, op.idx27_plain, op.n_cells, (const Basis1D<T> *)op.basis, (T)M[0], (T)M[1], (T)M[2],
-                         (T)M[3], (T)M[4], (T)M[5], (T)det);
+    // the geometry: U and JxW_q at every point (curved cells; metric and det are not read), or M and det J
+    const bool       curved = unit_q != nullptr;
+    const CellTensor geo    = curved ? CellTensor::at_points(unit_q) : CellTensor::per_mesh(M);
+    dispatch_mode<0, 1>(minimal_surface, [&](auto MINSURF) {
+      dispatch_mode<0, 1>(curved, [&](auto PERQ) {
+        hipLaunchKernelGGL((evaluate_coefficient_kernel<P, T, TO, MINSURF.value != 0, PERQ.value != 0>), dim3(nb), dim3(C::THREADS), 0,
+                           s, (TO *)coef_q, (const T *)state, op.idx27_plain, op.n_cells, (const Basis1D<T> *)op.basis, (T)geo.c[0],
+                           (T)geo.c[1], (T)geo.c[2], (T)geo.c[3], (T)geo.c[4], (T)geo.c[5], (T)(curved ? 0. : det),
+                           (const T *)geo.per_point, (const T *)(curved ? jxw_q : nullptr));
+      });
+    });
   }
 
   void launch_evaluate_coefficient(hipStream_t s, const OperatorData &op, void *coef_q, int coef_number, bool minimal_surface,
                                    const double *metric, double det, const void *unit_q, const void *jxw_q, const void *state)
   {
-    if (op.number == 1 && coef_number == 1)
-      {
-        dispatch_degree(op.p, [&](auto P) { evaluate_coefficient_t<P.value, double, double>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state); });
-      }
-    else if (op.number == 1)
-      {
-        dispatch_degree(op.p, [&](auto P) { evaluate_coefficient_t<P.value, double, float>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state); });
-      }
-    else // (fp32 tables: fp32 tensor)
-      {
-        dispatch_degree(op.p, [&](auto P) { evaluate_coefficient_t<P.value, float, float>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state); });
-      }
+    dispatch_degree(op.p, [&](auto P) {
+      auto run = [&](auto t, auto to) {
+        evaluate_coefficient_t<P.value, decltype(t), decltype(to)>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state);
+      };
+      // (number type of the state and the arithmetic, number type of the tensor)
+      if (op.number == MGX_F64 && coef_number == MGX_F64)
+        run(double(), double());
+      else if (op.number == MGX_F64)
+        run(double(), float());
+      else // (fp32 tables: fp32 tensor)
+        run(float(), float());
+    });
   }
 
   template <int P, typename T>
@@ -384,13 +376,8 @@ namespace mgx
   void launch_interpolate_to_coarse(hipStream_t s, const TransferData &t, const void *r1d, const uint32_t *own_c, void *coarse,
                                     const void *fine)
   {
-    if (t.coarse->number == 1)
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { interpolate_t<P.value, double>(s, t, r1d, own_c, coarse, fine); });
-      }
-    else
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { interpolate_t<P.value, float>(s, t, r1d, own_c, coarse, fine); });
-      }
+    dispatch_number_degree(t.coarse->number, t.coarse->p, [&](auto number, auto P) {
+      interpolate_t<P.value, decltype(number)>(s, t, r1d, own_c, coarse, fine);
+    });
   }
 } // namespace mgx

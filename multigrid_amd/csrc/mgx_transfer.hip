@@ -538,27 +538,17 @@ namespace mgx
   void launch_prolongate_pipe(hipStream_t s, const TransferData &t, void *fine, const void *coarse, bool add,
                               bool with_constraints)
   {
-    if (t.coarse->number == 1)
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { launch_t<P.value, double>(s, t, 0, fine, coarse, nullptr, add, with_constraints); });
-      }
-    else
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { launch_t<P.value, float>(s, t, 0, fine, coarse, nullptr, add, with_constraints); });
-      }
+    dispatch_number_degree(t.coarse->number, t.coarse->p, [&](auto number, auto P) {
+      launch_t<P.value, decltype(number)>(s, t, 0, fine, coarse, nullptr, add, with_constraints);
+    });
   }
 
   void launch_restrict_add_pipe(hipStream_t s, const TransferData &t, void *coarse, const void *fine,
                                 bool with_constraints)
   {
-    if (t.coarse->number == 1)
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { launch_t<P.value, double>(s, t, 1, const_cast<void *>(fine), nullptr, coarse, false, with_constraints); });
-      }
-    else
-      {
-        dispatch_degree(t.coarse->p, [&](auto P) { launch_t<P.value, float>(s, t, 1, const_cast<void *>(fine), nullptr, coarse, false, with_constraints); });
-      }
+    dispatch_number_degree(t.coarse->number, t.coarse->p, [&](auto number, auto P) {
+      launch_t<P.value, decltype(number)>(s, t, 1, const_cast<void *>(fine), nullptr, coarse, false, with_constraints);
+    });
   }
 
 } // namespace mgx
