@@ -27,6 +27,13 @@ extern "C" {
 #define MGX_DG_GAUSS 2         /* FE_DGQArbitraryNodes(QGauss): collocation, no basis change */
 
 #define MGX_DG_BOUNDARY (-1)   /* neighbour entry of a (homogeneous Dirichlet) boundary face */
+/* neighbour entry of a boundary face with the natural (Neumann) condition: the face contributes nothing to the bilinear
+ * form of the face-based SIP formulation (laplace_operator_dg_face.h:66-160, which integrates Dirichlet faces only); its
+ * datum h = d_n u enters the right-hand side as int_F h phi_i (mgx_dg_compute_rhs_mixed).  Every action of the operator
+ * (vmult, residual, the merged Chebyshev and CG forms, block Jacobi), 3D and 2D, every basis, degree and number type,
+ * decomposed or not.  An operator whose faces are all interior or Neumann faces is singular (constants); it can be
+ * created and applied but the solvers below refuse it. */
+#define MGX_DG_NEUMANN (-2)
 
 typedef struct mgx_dg_operator_s *mgx_dg_operator_t;
 
@@ -57,8 +64,8 @@ typedef struct
   int      basis;              /* MGX_DG_* */
   int      number;             /* MGX_F32 (matvec_dg_cheby/program.cc:88) or MGX_F64 */
   uint32_t n_cells;
-  /* [n_cells][6] cell behind face 2d+s (direction d, lower s = 0 / upper s = 1 side) or
-   * MGX_DG_BOUNDARY; replaces start_indices_on_neighbor / dirichlet_faces
+  /* [n_cells][6] cell behind face 2d+s (direction d, lower s = 0 / upper s = 1 side),
+   * MGX_DG_BOUNDARY or MGX_DG_NEUMANN; replaces start_indices_on_neighbor / dirichlet_faces
    * (laplace_operator_dg.h:453-459, 480-560).  Host memory, copied. */
   const int32_t *neighbours;
   /* the one cell Jacobian dx/dxi, row-major [real][reference]; the reference asserts a single
@@ -80,7 +87,10 @@ typedef struct
 /* LaplaceOperatorCompactCombine::reinit (:361-771) + JacobiTransformed::JacobiTransformed
  * (:2031-2038, local_compute_diagonals :2099-2233): 1D basis data, penalty and normal factors,
  * eigenvector basis and the inverse transformed diagonals (one set per combination of Dirichlet
- * faces -- at most 64 -- instead of one per cell). */
+ * faces -- at most 64 -- instead of one per cell; with Neumann faces one set per combination of face kinds that occurs
+ * in the mesh, of 3^6).  Refused with MGX_ERR_UNSUPPORTED if a transformed diagonal is not positive.  An operator with a
+ * cell whose faces are all Neumann faces (a one-cell pure-Neumann mesh) is refused with the same status: the block of
+ * that cell is singular, the constants are in its null space, and block Jacobi cannot invert it. */
 /* desc->dim == 2: the same with the dim == 2 branches (:418 data per face, :749-771 geometry; JacobiTransformed
  * :2162): 16 combinations of Dirichlet faces. */
 int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, mgx_dg_operator_t *op);
@@ -189,7 +199,16 @@ typedef struct
  * arithmetic, function evaluation included, is in double and only the store converts.  One writer per entry, no
  * atomics: the same bits in every run.  Decomposed operators: owned cells only, the ghost part of dst is left alone;
  * no communication (a face to another rank is not a Dirichlet face). */
+/* Neumann faces of the operator are treated as such, with zero flux (mgx_dg_compute_rhs_mixed with h == NULL). */
 int mgx_dg_compute_rhs(mgx_dg_operator_t op, const mgx_dg_function *f, const mgx_dg_function *g, void *dst);
+
+/* The same plus the Neumann term: dst_i += sum over the Neumann faces F of K  int_F h phi_i, h the outward normal
+ * derivative d_n u prescribed on F.  h == NULL: zero flux.  h sampled: face_values ([n_cells][2 dim][(p+1)^(dim-1)], as
+ * for g) holds h in the Gauss points of the faces; only the entries of Neumann faces are read.  h a sine product: the
+ * struct describes a potential u, and the kernel forms h = n . grad u with the outward unit normal of the operator's own
+ * geometry -- on a sheared mesh the flux of a sine product is not one itself.  In double, one writer per entry. */
+int mgx_dg_compute_rhs_mixed(mgx_dg_operator_t op, const mgx_dg_function *f, const mgx_dg_function *g, const mgx_dg_function *h,
+                             void *dst);
 
 /* sums = { sum_K sum_q (u_h(x_q) - u(x_q))^2 JxW_q,  sum_K sum_q JxW_q } over this rank's owned cells, u_h the function
  * of vec (device, the operator's number type): the two numbers of compute_l2_error (multigrid_solver_dg_plain.h:219-259)
@@ -219,7 +238,8 @@ typedef struct
   const uint32_t   *cell_global_id;
 } mgx_dg_solver_desc;
 /* ctor (:58-323), incl. smooth_dg.initialize: eigenvalue estimate with JacobiTransformed.  2D operators are refused
- * with MGX_ERR_UNSUPPORTED: there is no FE_Q hierarchy in two dimensions (include/mgx.h). */
+ * with MGX_ERR_UNSUPPORTED: there is no FE_Q hierarchy in two dimensions (include/mgx.h).  So are operators with Neumann
+ * faces: the FE_Q levels constrain every boundary DoF, their coarse correction would be that of another problem. */
 int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_dg_solver_t *solver);
 int mgx_dg_solver_destroy(mgx_dg_solver_t solver);
 int mgx_dg_solver_smoother_info(mgx_dg_solver_t solver, mgx_smoother_info *info);
@@ -289,7 +309,8 @@ typedef struct
 /* ctor (:58-215): level vectors and smooth[level].initialize -- levels l > 0: range 20, 15 CG iterations; level 0:
  * range 1e-5, degree by Varga's rule, at most m() CG iterations (:204-209).  The dimension is that of the operators
  * (poisson_dg_plain/program.cc:65 runs dimension 2): all operators and transfers must share it, and a level has 2^dim
- * times the cells of the one below. */
+ * times the cells of the one below.  Operators with Neumann faces are accepted (every level should mark the same sides);
+ * a level or matrix_dg_dp without any Dirichlet face is refused with MGX_ERR_UNSUPPORTED: the problem is singular. */
 int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc *desc, mgx_dg_plain_solver_t *solver);
 int mgx_dg_plain_solver_destroy(mgx_dg_plain_solver_t solver);
 int mgx_dg_plain_solver_smoother_info(mgx_dg_plain_solver_t solver, int level, mgx_smoother_info *info);
@@ -341,7 +362,8 @@ typedef struct
   unsigned          check_every;    /* >= 1: with a tolerance, the host looks at the history every so many iterations */
 } mgx_dg_pcg_solver_desc;
 /* solver_dg/program.cc:134-148, 177-178: owns r, p, q, the block sums, the scalars and the history.  Refused with
- * MGX_ERR_UNSUPPORTED (and a reason) if an entry of the preconditioner table is not positive and finite. */
+ * MGX_ERR_UNSUPPORTED (and a reason) if an entry of the preconditioner table is not positive and finite, or if the
+ * operator has no Dirichlet face at all (Neumann faces only: the problem is singular). */
 int mgx_dg_pcg_solver_create(mgx_context_t ctx, const mgx_dg_pcg_solver_desc *desc, mgx_dg_pcg_solver_t *solver);
 int mgx_dg_pcg_solver_destroy(mgx_dg_pcg_solver_t solver);
 /* solver.solve(laplace_operator, output, input, diagonal) (solver_dg/program.cc:222-263): zero start, `solution` is
@@ -379,6 +401,12 @@ int mgx_dg_box_children(const int coarse_cells[3], int coarse_ordering, int fine
  * children[c * 4 + kx + 2 ky] = fine cell at position 2 ij(c) + (kx, ky) */
 int mgx_dg_box_neighbours_2d(const int cells[2], int ordering, int32_t *neighbours, int32_t *cell_ij);
 int mgx_dg_box_children_2d(const int coarse_cells[2], int coarse_ordering, int fine_ordering, uint32_t *children);
+
+/* marks whole sides of a box in a table made by mgx_dg_box_neighbours[_2d] (dim 3 / 2): every boundary entry of face
+ * 2d+s becomes side_kind[2d+s], MGX_DG_BOUNDARY or MGX_DG_NEUMANN.  cells: the box, [dim]; cell_pos: [n_cells][dim], the
+ * positions the table was made with (the owned cells of a rank with their positions in the whole box will do: entries
+ * of rank faces are cells).  The table is checked against the positions first and left alone if it does not fit. */
+int mgx_dg_box_set_sides(int dim, const int *cells, uint32_t n_cells, const int32_t *cell_pos, const int *side_kind, int32_t *neighbours);
 
 #ifdef __cplusplus
 }

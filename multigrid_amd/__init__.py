@@ -1141,6 +1141,7 @@ class MinimalSurfaceProblem:
 # ---------------------------------------------------------------------------------------------
 # DG path (include/mgx_dg.h)
 DG_HERMITE, DG_GAUSS_LOBATTO, DG_GAUSS = 0, 1, 2
+DG_BOUNDARY, DG_NEUMANN = -1, -2   # neighbour entries of a Dirichlet / a Neumann boundary face
 
 
 def dg_cheby_mesh(n_cell_steps):
@@ -1150,10 +1151,27 @@ def dg_cheby_mesh(n_cell_steps):
     return tuple(cells), np.array(jac).reshape(3, 3)
 
 
-def dg_box_neighbours(cells, ordering="z"):
-    """(neighbour table [n, 6], cell positions [n, 3]) of a box of cells, all outer faces Dirichlet; a 2-tuple of
+def dg_box_set_sides(cells, cell_pos, neighbours, neumann_sides):
+    """marks the sides `neumann_sides` (face numbers 2d+s) of the box as Neumann faces, the others as Dirichlet faces,
+    in a neighbour table made with the positions cell_pos (mgx_dg_box_set_sides); returns the table"""
+    dim = len(cells)
+    sides = set(int(f) for f in neumann_sides)
+    assert sides <= set(range(2 * dim)), "sides are face numbers 2d+s"
+    kind = (C.c_int * (2 * dim))(*[DG_NEUMANN if f in sides else DG_BOUNDARY for f in range(2 * dim)])
+    nb = np.ascontiguousarray(neighbours, dtype=np.int32)
+    pos = np.ascontiguousarray(cell_pos, dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    check(_lib.load().mgx_dg_box_set_sides(dim, (C.c_int * dim)(*cells), pos.shape[0], pos.ctypes.data_as(i32p), kind,
+                                           nb.ctypes.data_as(i32p)))
+    return nb
+
+
+def dg_box_neighbours(cells, ordering="z", neumann_sides=()):
+    """(neighbour table [n, 6], cell positions [n, 3]) of a box of cells; the outer faces are Dirichlet faces but for
+    the sides in neumann_sides (face numbers 2d+s), which are Neumann faces; a 2-tuple of
     cells gives the tables of a box of quadrilaterals, [n, 4] and [n, 2]"""
     dim = len(cells)
+    neumann_sides = tuple(neumann_sides)
     c = (C.c_int * dim)(*cells)
     n = int(np.prod(cells))
     nb = np.empty((n, 2 * dim), dtype=np.int32)
@@ -1161,6 +1179,8 @@ def dg_box_neighbours(cells, ordering="z"):
     i32p = C.POINTER(C.c_int32)
     fn = _lib.load().mgx_dg_box_neighbours_2d if dim == 2 else _lib.load().mgx_dg_box_neighbours
     check(fn(C.byref(c), 1 if ordering == "z" else 0, nb.ctypes.data_as(i32p), ijk.ctypes.data_as(i32p)))
+    if neumann_sides:
+        nb = dg_box_set_sides(cells, ijk, nb, neumann_sides)
     return nb, ijk
 
 
@@ -1381,11 +1401,16 @@ class DGLaplaceOperator:
         check(self.lib.mgx_dg_operator_set_cell_positions(self.h, o.ctypes.data_as(_lib.f64p),
                                                           pos.ctypes.data_as(C.POINTER(C.c_int32))))
 
-    def compute_rhs(self, dst, f=None, g=None):
+    def compute_rhs(self, dst, f=None, g=None, h=None):
         """dst_i = int f phi_i + sum over the Dirichlet faces of int g (sigma_F phi_i - d_n phi_i), f and g DGFunctions
-        (None: zero; g=None is the reference's volume-only vector); dst in the operator's number type"""
-        check(self.lib.mgx_dg_compute_rhs(self.h, C.byref(f.desc) if f is not None else None,
-                                          C.byref(g.desc) if g is not None else None, dst.ptr if dst is not None else None))
+        (None: zero; g=None is the reference's volume-only vector); dst in the operator's number type.  h: the flux on
+        the Neumann faces, + sum over them of int h phi_i -- sampled: the outward normal derivative in face_values; a
+        sine product: the potential u of h = n . grad u (mgx_dg_compute_rhs_mixed); None: zero flux"""
+        byref = lambda fn: C.byref(fn.desc) if fn is not None else None
+        if h is None:
+            check(self.lib.mgx_dg_compute_rhs(self.h, byref(f), byref(g), dst.ptr if dst is not None else None))
+        else:
+            check(self.lib.mgx_dg_compute_rhs_mixed(self.h, byref(f), byref(g), byref(h), dst.ptr if dst is not None else None))
 
     def compute_l2_error(self, vec, u):
         """(sum (u_h - u)^2 JxW, sum JxW) over this rank's owned cells; the L2 error is sqrt of their ratio, each summed
@@ -1568,9 +1593,10 @@ class DGPlainMultigridSolver:
     coarse_cells (and a 2 x 2 jacobian0) gives <2,p,Number,double>, the dimension poisson_dg_plain/program.cc:65 runs."""
 
     def __init__(self, ctx, degree, basis, coarse_cells, jacobian0, n_levels, degree_pre=3, vcycle_number=F32, ordering="z",
-                 origin=None):
+                 origin=None, neumann_sides=()):
         """origin (default 0): the corner of the box, for the coordinates x = origin + J (pos + xi) that compute_rhs and
-        compute_l2_error of the finest fp64 operator evaluate sine products in"""
+        compute_l2_error of the finest fp64 operator evaluate sine products in; neumann_sides: the sides of the box
+        (face numbers 2d+s) that are Neumann faces, on every level alike -- at least one side must stay Dirichlet"""
         self.ctx, self.lib = ctx, ctx.lib
         self.degree, self.basis, self.n_levels, self.vnumber = degree, basis, n_levels, vcycle_number
         self.dim = dim = len(coarse_cells)
@@ -1580,7 +1606,7 @@ class DGPlainMultigridSolver:
         try:
             for l in range(n_levels):
                 cells = tuple(int(c) << l for c in coarse_cells)
-                nb, ijk = dg_box_neighbours(cells, ordering)
+                nb, ijk = dg_box_neighbours(cells, ordering, neumann_sides)
                 self.cells.append(cells)
                 self.cell_ijk.append(ijk)
                 i64 = ijk.astype(np.int64)

@@ -280,6 +280,7 @@ SIGNATURES = {
     "mgx_dg_operator_basis": (C.c_int, [vp, f64p, f64p, f64p]),
     "mgx_dg_operator_set_cell_positions": (C.c_int, [vp, f64p, C.POINTER(C.c_int32)]),
     "mgx_dg_compute_rhs": (C.c_int, [vp, C.POINTER(DGFunctionDesc), C.POINTER(DGFunctionDesc), vp]),
+    "mgx_dg_compute_rhs_mixed": (C.c_int, [vp, C.POINTER(DGFunctionDesc), C.POINTER(DGFunctionDesc), C.POINTER(DGFunctionDesc), vp]),
     "mgx_dg_compute_l2_error": (C.c_int, [vp, vp, C.POINTER(DGFunctionDesc), f64p]),
     "mgx_dg_solver_create": (C.c_int, [vp, C.POINTER(DGSolverDesc), C.POINTER(vp)]),
     "mgx_dg_solver_destroy": (C.c_int, [vp]),
@@ -309,6 +310,8 @@ SIGNATURES = {
     "mgx_dg_box_neighbours": (C.c_int, [C.POINTER(C.c_int * 3), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mgx_dg_box_neighbours_2d": (C.c_int, [C.POINTER(C.c_int * 2), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mgx_dg_box_children_2d": (C.c_int, [C.POINTER(C.c_int * 2), C.c_int, C.c_int, u32p]),
+    "mgx_dg_box_set_sides": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int),
+                                       C.POINTER(C.c_int32)]),
 }
 
 _lib = None

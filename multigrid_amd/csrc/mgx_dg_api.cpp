@@ -25,7 +25,7 @@ struct mgx_dg_operator_s
   uint32_t      n_cells = 0;
   int32_t      *neigh   = nullptr; // device [n_cells][2 dim]
   void         *consts  = nullptr; // device DGConst<T>
-  void         *inv_diag = nullptr; // device [4^dim][(p+1)^dim]
+  void         *inv_diag = nullptr; // device [4^dim][(p+1)^dim]; has_neumann: [9^dim][(p+1)^dim] (build_inverse_diagonal)
   // inverse of the lumped mass matrix of a cell (solver_dg/program.cc:134-148): host fp64 and device in the number type,
   // [(p+1)^dim]; an entry is not positive and finite where the lumped mass is not (mgx_dg_pcg_solver_create refuses)
   std::vector<double> lumped_inv_host;
@@ -56,6 +56,7 @@ struct mgx_dg_operator_s
   // cell has a Dirichlet face, and the cell positions of mgx_dg_operator_set_cell_positions (device [n_cells][dim])
   double   jac[9]        = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   bool     has_dirichlet = false;
+  bool     has_neumann   = false; // a face is MGX_DG_NEUMANN: the variant kernels run, the diagonals are coded in base 3
   int32_t *cell_pos      = nullptr;
   double   origin[3]     = {0, 0, 0};
 };
@@ -193,7 +194,7 @@ namespace
 
   int launch_cells(mgx_dg_operator_t op, const DGLaunch &launch, hipStream_t stream = nullptr)
   {
-    const CellOperands o{op->number, op->degree, op->basis, op->neigh, op->consts, op->inv_diag, op->n_cells, op->n_ghost > 0, op->dim};
+    const CellOperands o{op->number, op->degree, op->basis, op->neigh, op->consts, op->inv_diag, op->n_cells, op->n_ghost > 0, op->dim, op->has_neumann};
     return launch_dg_cells(stream ? stream : (hipStream_t)mgx_context_stream(op->ctx), o, launch);
   }
 
@@ -275,9 +276,10 @@ namespace
     if (n_all * n3 >= (1ull << 32))
       return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: more than 2^32 vector entries per rank");
     for (uint64_t i = 0; i < (uint64_t)desc->n_cells * 2 * dim; ++i)
-      if (desc->neighbours[i] != MGX_DG_BOUNDARY && (desc->neighbours[i] < 0 || (uint64_t)desc->neighbours[i] >= n_all))
+      if (desc->neighbours[i] != MGX_DG_BOUNDARY && desc->neighbours[i] != MGX_DG_NEUMANN &&
+          (desc->neighbours[i] < 0 || (uint64_t)desc->neighbours[i] >= n_all))
         return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_operator_create: neighbour entry " + std::to_string(i) +
-                                                   " is neither a cell of the mesh, a ghost cell nor MGX_DG_BOUNDARY");
+                                                   " is neither a cell (of the mesh or a ghost cell), MGX_DG_BOUNDARY nor MGX_DG_NEUMANN");
     if (desc->n_ghost_cells > 0)
       {
         if (!desc->exchange || !mgx::context_has_comm(ctx))
@@ -337,15 +339,57 @@ namespace
   }
 
   // table[cat][(p+1)^dim]: inverse of the transformed diagonal for every combination of Dirichlet faces (host);
-  // 64 combinations of 6 faces, 16 of the 4 faces of a quadrilateral (JacobiTransformed, laplace_operator_dg.h:2162)
-  int build_inverse_diagonal(const mgx_dg_operator_s &op, uint64_t n3, std::vector<double> &table)
+  // 64 combinations of 6 faces, 16 of the 4 faces of a quadrilateral (JacobiTransformed, laplace_operator_dg.h:2162).
+  // An operator with Neumann faces: 3^(2 dim) rows, one per combination of face kinds in base 3 (face_kind_code of the
+  // cell kernels); the rows of the combinations its cells have are built and must be positive, the others stay zero.
+  int build_inverse_diagonal(const mgx_dg_operator_s &op, const int32_t *neighbours, uint64_t n3, std::vector<double> &table)
   {
     std::vector<double> diag;
-    const unsigned      n_cat = 1u << (2 * op.dim);
+    const int           nf = 2 * op.dim;
+    int                 kind[6];
+    if (op.has_neumann)
+      {
+        unsigned n_cat = 1;
+        for (int f = 0; f < nf; ++f)
+          n_cat *= 3u;
+        std::vector<bool> occurs(n_cat, false);
+        for (uint32_t c = 0; c < op.n_cells; ++c)
+          {
+            unsigned code = 0, weight = 1;
+            for (int f = 0; f < nf; ++f, weight *= 3u)
+              code += weight * (unsigned)kind_of_entry(neighbours[(size_t)c * nf + f]);
+            occurs[code] = true;
+          }
+        // A cell whose faces are all Neumann faces (a one-cell pure-Neumann mesh) has a singular block: the constants.
+        // Its transformed diagonal shows that at p = 1 only -- the eigenvector basis does not hold the constant
+        // otherwise -- so the combination itself is refused.
+        if (occurs[n_cat - 1])
+          return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: transformed cell block is not positive definite: every face "
+                                              "of a cell is a Neumann face");
+        table.assign(n_cat * n3, 0.0);
+        for (unsigned cat = 0; cat < n_cat; ++cat)
+          {
+            if (!occurs[cat])
+              continue;
+            for (unsigned f = 0, rest = cat; f < (unsigned)nf; ++f, rest /= 3u)
+              kind[f] = (int)(rest % 3u);
+            transformed_diagonal(op.h, op.g, kind, diag);
+            for (uint64_t i = 0; i < n3; ++i)
+              {
+                if (!(diag[i] > 0))
+                  return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_operator_create: transformed cell block is not positive");
+                table[cat * n3 + i] = 1.0 / diag[i];
+              }
+          }
+        return MGX_OK;
+      }
+    const unsigned      n_cat = 1u << nf;
     table.resize(n_cat * n3);
     for (unsigned cat = 0; cat < n_cat; ++cat)
       {
-        transformed_diagonal(op.h, op.g, cat, diag);
+        for (int f = 0; f < nf; ++f)
+          kind[f] = (cat >> f) & 1u ? kDirichlet : kInterior;
+        transformed_diagonal(op.h, op.g, kind, diag);
         for (uint64_t i = 0; i < n3; ++i)
           {
             if (!(diag[i] > 0))
@@ -471,8 +515,12 @@ int mgx_dg_operator_create(mgx_context_t ctx, const mgx_dg_operator_desc *desc, 
   op->n_ghost = desc->n_ghost_cells;
   op->ghost_stride = desc->basis == MGX_DG_HERMITE ? 2u * (desc->degree + 1) * (desc->degree + 1) : (uint32_t)n3;
   MGX_TRY(build_basis_and_geometry(*op, desc));
+  {
+    const int32_t *end = desc->neighbours + 2 * (size_t)dim * desc->n_cells;
+    op->has_neumann    = std::find(desc->neighbours, end, MGX_DG_NEUMANN) != end;
+  }
   std::vector<double> table;
-  MGX_TRY(build_inverse_diagonal(*op, n3, table));
+  MGX_TRY(build_inverse_diagonal(*op, desc->neighbours, n3, table));
   MGX_TRY(op->mem.upload(&op->neigh, desc->neighbours, 2 * (size_t)dim * desc->n_cells));
   for (int d = 0; d < dim; ++d)
     for (int a = 0; a < dim; ++a)
@@ -661,6 +709,7 @@ namespace
     DGRhsOperands o;
     o.number = op->number, o.degree = op->degree, o.dim = op->dim;
     o.neigh = op->neigh, o.consts = op->consts, o.cell_pos = op->cell_pos, o.n_cells = op->n_cells;
+    o.has_neumann = op->has_neumann;
     DGRhsGeometry &g = o.geo;
     std::copy(op->jac, op->jac + 9, g.jac);
     std::copy(op->origin, op->origin + 3, g.origin);
@@ -680,11 +729,29 @@ namespace
         for (int a = 0; a < 3; ++a)
           g.cn[d][a] = op->g.cn[d][a];
       }
+    // unit normals towards +xi_d: the rows of J^-1, normalised (cofactors of J; the third row and column of a 2D
+    // Jacobian stand for the identity)
+    {
+      double M[9];
+      std::copy(J, J + 9, M);
+      if (op->dim == 2)
+        M[2] = M[5] = M[6] = M[7] = 0., M[8] = 1.;
+      const double cof[3][3] = {{M[4] * M[8] - M[5] * M[7], M[2] * M[7] - M[1] * M[8], M[1] * M[5] - M[2] * M[4]},
+                                {M[5] * M[6] - M[3] * M[8], M[0] * M[8] - M[2] * M[6], M[2] * M[3] - M[0] * M[5]},
+                                {M[3] * M[7] - M[4] * M[6], M[1] * M[6] - M[0] * M[7], M[0] * M[4] - M[1] * M[3]}};
+      const double det = M[0] * cof[0][0] + M[1] * cof[1][0] + M[2] * cof[2][0];
+      for (int d = 0; d < 3; ++d)
+        {
+          const double len = std::sqrt(cof[d][0] * cof[d][0] + cof[d][1] * cof[d][1] + cof[d][2] * cof[d][2]);
+          for (int i = 0; i < 3; ++i)
+            g.normal[d][i] = (det < 0 ? -1.0 : 1.0) * cof[d][i] / len;
+        }
+    }
     return o;
   }
 
-  // a function of the C ABI as the kernels take it.  role: "f", "g" or "u" -- g reads the face values, the others the
-  // cell values.  NULL: zero.
+  // a function of the C ABI as the kernels take it.  role: "f", "g", "h" or "u" -- g reads the face values on the
+  // Dirichlet faces, h on the Neumann faces, the others the cell values.  NULL: zero.
   int function_args(mgx_dg_operator_t op, const char *entry, const char *role, const mgx_dg_function *fn, DGFunctionArgs &out)
   {
     out = DGFunctionArgs{};
@@ -712,11 +779,12 @@ namespace
       }
     if (fn->kind != MGX_DG_FN_SAMPLED)
       return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + ": kind must be MGX_DG_FN_SINE_PRODUCT or MGX_DG_FN_SAMPLED");
-    const bool on_faces = role[0] == 'g';
+    const bool on_faces = role[0] == 'g' || role[0] == 'h';
     if (on_faces && !fn->face_values)
       {
-        if (op->has_dirichlet)
-          return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + " is sampled without face_values, but the mesh has Dirichlet faces");
+        if (role[0] == 'g' ? op->has_dirichlet : op->has_neumann)
+          return dg_fail(MGX_ERR_INVALID_ARGUMENT, who + " is sampled without face_values, but the mesh has " +
+                                                     (role[0] == 'g' ? "Dirichlet" : "Neumann") + " faces");
         return MGX_OK; // no face reads it: as good as none
       }
     if (!on_faces && !fn->cell_values)
@@ -752,8 +820,23 @@ int mgx_dg_compute_rhs(mgx_dg_operator_t op, const mgx_dg_function *f, const mgx
   DGFunctionArgs fa, ga;
   MGX_TRY(function_args(op, "mgx_dg_compute_rhs", "f", f, fa));
   MGX_TRY(function_args(op, "mgx_dg_compute_rhs", "g", g, ga));
-  if (!launch_dg_rhs((hipStream_t)mgx_context_stream(op->ctx), rhs_operands(op), fa, ga, dst))
+  if (!launch_dg_rhs((hipStream_t)mgx_context_stream(op->ctx), rhs_operands(op), fa, ga, DGFunctionArgs{}, dst))
     return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_compute_rhs: no kernel for this degree and dimension");
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_compute_rhs_mixed(mgx_dg_operator_t op, const mgx_dg_function *f, const mgx_dg_function *g, const mgx_dg_function *h,
+                             void *dst)
+{
+  MGX_REQUIRE(op, "mgx_dg_compute_rhs_mixed: null operator");
+  MGX_REQUIRE(dst, "mgx_dg_compute_rhs_mixed: dst is null");
+  DGFunctionArgs fa, ga, ha;
+  MGX_TRY(function_args(op, "mgx_dg_compute_rhs_mixed", "f", f, fa));
+  MGX_TRY(function_args(op, "mgx_dg_compute_rhs_mixed", "g", g, ga));
+  MGX_TRY(function_args(op, "mgx_dg_compute_rhs_mixed", "h", h, ha));
+  if (!launch_dg_rhs((hipStream_t)mgx_context_stream(op->ctx), rhs_operands(op), fa, ga, ha, dst))
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_compute_rhs_mixed: no kernel for this degree and dimension");
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -1037,6 +1120,9 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
   if (A->dim == 2 || Ad->dim == 2) // (before the FE_Q solver is looked at: none can exist for these operators)
     return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: 2D DG operator -- there is no FE_Q hierarchy in two dimensions; "
                                         "use mgx_dg_plain_solver_create");
+  if (A->has_neumann || Ad->has_neumann)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: DG operator with Neumann faces -- the FE_Q levels of the hierarchy "
+                                        "constrain every boundary DoF; use mgx_dg_plain_solver_create");
   MGX_REQUIRE(desc->cfe, "mgx_dg_solver_create: null argument");
   if (Ad->number != MGX_F64 || A->n_cells != Ad->n_cells || A->degree != Ad->degree || A->basis != Ad->basis)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_solver_create: matrix_dg_dp must be the fp64 twin of matrix_dg");
@@ -1373,6 +1459,10 @@ int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc
       if (A->dim != top->dim)
         return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) + "] has dimension " +
                                                    std::to_string(A->dim) + ", the finest level " + std::to_string(top->dim));
+      if (!A->has_dirichlet)
+        return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
+                                              "] has no Dirichlet face: the problem is singular (pure Neumann problems are not "
+                                              "solved)");
       if (l == 0)
         continue;
       mgx_dg_transfer_t T = desc->transfer[l - 1];
@@ -1394,6 +1484,9 @@ int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc
   if (Ad->number != MGX_F64 || Ad->n_cells != top->n_cells || Ad->degree != top->degree || Ad->basis != top->basis || Ad->n_ghost > 0 ||
       Ad->ctx != ctx || Ad->dim != top->dim)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix_dg_dp must be the fp64 twin of the finest matrix");
+  if (!Ad->has_dirichlet)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_plain_solver_create: matrix_dg_dp has no Dirichlet face: the problem is singular "
+                                        "(pure Neumann problems are not solved)");
 
   std::unique_ptr<mgx_dg_plain_solver_s, int (*)(mgx_dg_plain_solver_t)> S(new mgx_dg_plain_solver_s, mgx_dg_plain_solver_destroy);
   S->ctx    = ctx;
@@ -1683,6 +1776,9 @@ int mgx_dg_pcg_solver_create(mgx_context_t ctx, const mgx_dg_pcg_solver_desc *de
   if (A->n_ghost > 0)
     return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_pcg_solver_create: the operator has ghost cells; the lumped-mass PCG runs on one "
                                         "rank (its scalars stay on the device, there is no allreduce)");
+  if (!A->has_dirichlet)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_pcg_solver_create: the operator has no Dirichlet face: the problem is singular (pure "
+                                        "Neumann problems are not solved)");
   for (size_t i = 0; i < A->lumped_inv_host.size(); ++i)
     if (!pcg_positive_finite(A->lumped_inv_host[i]))
       return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_pcg_solver_create: the lumped mass of local index " + std::to_string(i) +

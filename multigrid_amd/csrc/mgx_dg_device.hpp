@@ -19,6 +19,10 @@ namespace mgx::dg
   // for this degree, basis or action
   bool     launch_dg_cells_2d(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
   uint32_t cell_grid_2d(int number, int p, uint32_t n_cells);
+  // the variants for operators with Neumann faces (op.has_neumann), each in a unit of its own built from the source
+  // of the cell kernel of its dimension (MGX_DG_NEUMANN_UNIT); 3D: every action but kRestrict
+  bool launch_dg_cells_neumann(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
+  bool launch_dg_cells_2d_neumann(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
 } // namespace mgx::dg
 
 namespace mgx::dg::device
@@ -90,6 +94,22 @@ namespace mgx::dg::device
     const T          *P1;
     int               plain;
   };
+
+  // Row of the table of inverse diagonals of a cell in an operator with Neumann faces: the kinds of its NF faces
+  // (kind_of_entry: interior, Dirichlet, Neumann) as the digits of a number in base 3, face 0 lowest.  The host builds
+  // the rows that occur in the operator's cells (mgx_dg_api.cpp, build_inverse_diagonal).
+  template <int NF>
+  __host__ __device__ __forceinline__ unsigned face_kind_code(const int (&nb)[NF])
+  {
+    unsigned code = 0, weight = 1;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      {
+        code += weight * (unsigned)kind_of_entry(nb[f]);
+        weight *= 3u;
+      }
+    return code;
+  }
 
   // ------------------------------------------------------------------------------------------
   // launch side: each translation unit instantiates these with the configuration and the kernels of its dimension

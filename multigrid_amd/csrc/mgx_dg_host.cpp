@@ -581,7 +581,7 @@ namespace mgx::dg
 
   namespace
   {
-    void transformed_diagonal_2d(const Host1D &h, const Geometry &g, unsigned cat, std::vector<double> &diag)
+    void transformed_diagonal_2d(const Host1D &h, const Geometry &g, const int *kind, std::vector<double> &diag)
     {
       const int n = h.n;
       diag.assign((size_t)n * n, 0.0);
@@ -593,7 +593,7 @@ namespace mgx::dg
             for (int f = 0; f < 4; ++f)
               {
                 const int    d = f / 2, s = f % 2;
-                const double fbnd = (cat >> f) & 1u ? 1.0 : 0.5;
+                const double fbnd = kind[f] == kDirichlet ? 1.0 : (kind[f] == kNeumann ? 0.0 : 0.5);
                 const double sgn  = s ? 1.0 : -1.0;
                 const double be = h.beta[s][e[d]], ga = h.gamma[s][e[d]];
                 const double vn = g.cn[d][d] * be * ga + g.cn[d][1 - d] * be * be * h.ct[e[1 - d]];
@@ -604,10 +604,10 @@ namespace mgx::dg
     }
   } // namespace
 
-  void transformed_diagonal(const Host1D &h, const Geometry &g, unsigned cat, std::vector<double> &diag)
+  void transformed_diagonal(const Host1D &h, const Geometry &g, const int *kind, std::vector<double> &diag)
   {
     if (g.dim == 2)
-      return transformed_diagonal_2d(h, g, cat, diag);
+      return transformed_diagonal_2d(h, g, kind, diag);
     const int n = h.n;
     diag.assign((size_t)n * n * n, 0.0);
     for (int k = 0; k < n; ++k)
@@ -620,7 +620,7 @@ namespace mgx::dg
             for (int f = 0; f < 6; ++f)
               {
                 const int    d = f / 2, s = f % 2;
-                const double fbnd = (cat >> f) & 1u ? 1.0 : 0.5;
+                const double fbnd = kind[f] == kDirichlet ? 1.0 : (kind[f] == kNeumann ? 0.0 : 0.5);
                 const double sgn  = s ? 1.0 : -1.0;
                 const double be = h.beta[s][e[d]], ga = h.gamma[s][e[d]];
                 double       vn = g.cn[d][d] * be * ga;
@@ -777,6 +777,39 @@ int mgx_dg_box_neighbours_2d(const int cells[2], int ordering, int32_t *neighbou
             p[d] + 1 < cells[d] ? (int32_t)position[order[c] + stride[d]] : MGX_DG_BOUNDARY;
         }
     }
+  return MGX_OK;
+}
+
+int mgx_dg_box_set_sides(int dim, const int *cells, uint32_t n_cells, const int32_t *cell_pos, const int *side_kind,
+                         int32_t *neighbours)
+{
+  if ((dim != 2 && dim != 3) || !cells || !cell_pos || !side_kind || !neighbours)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_box_set_sides: dim must be 2 or 3 and no argument null");
+  for (int d = 0; d < dim; ++d)
+    if (cells[d] < 1)
+      return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_box_set_sides: cells must be positive");
+  for (int f = 0; f < 2 * dim; ++f)
+    if (side_kind[f] != MGX_DG_BOUNDARY && side_kind[f] != MGX_DG_NEUMANN)
+      return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_box_set_sides: a side is MGX_DG_BOUNDARY or MGX_DG_NEUMANN");
+  // checked before anything is written: a table that does not belong to these positions stays as it is
+  for (int pass = 0; pass < 2; ++pass)
+    for (uint32_t c = 0; c < n_cells; ++c)
+      for (int d = 0; d < dim; ++d)
+        {
+          const int32_t p = cell_pos[(size_t)c * dim + d];
+          if (pass == 0 && (p < 0 || p >= cells[d]))
+            return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_box_set_sides: cell position outside the box");
+          for (int s = 0; s < 2; ++s)
+            {
+              int32_t   &entry   = neighbours[((size_t)c * dim + d) * 2 + s];
+              const bool at_side = s == 0 ? p == 0 : p + 1 == cells[d];
+              if (pass == 0 && at_side != (entry < 0))
+                return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_box_set_sides: the neighbour table has a boundary entry "
+                                                                   "inside the box or a cell behind one of its sides");
+              if (pass == 1 && at_side)
+                entry = side_kind[2 * d + s];
+            }
+        }
   return MGX_OK;
 }
 

@@ -49,8 +49,19 @@ namespace mgx::dg
   // unless every entry is finite and the determinant positive
   int build_geometry_2d(const double J[4], int p, Geometry &g, std::string &why);
 
-  // diagonal of T^T A_KK T for one combination of Dirichlet faces (bit f of cat): Kronecker
-  // products of 1D forms in the eigenvector basis, in which the mass matrix is the identity.
-  // g.dim == 2: 16 categories of (p+1)^2 entries (JacobiTransformed, laplace_operator_dg.h:2162)
-  void transformed_diagonal(const Host1D &h, const Geometry &g, unsigned cat, std::vector<double> &diag);
+  // what lies behind a face of a cell, from its neighbour entry: a cell (owned or ghost), a homogeneous Dirichlet
+  // face (MGX_DG_BOUNDARY) or a Neumann face (MGX_DG_NEUMANN), which contributes nothing to the bilinear form
+  enum FaceKind
+  {
+    kInterior  = 0,
+    kDirichlet = 1,
+    kNeumann   = 2
+  };
+  constexpr int kind_of_entry(int32_t entry) { return entry >= 0 ? kInterior : (entry == MGX_DG_NEUMANN ? kNeumann : kDirichlet); }
+
+  // diagonal of T^T A_KK T for one combination of face kinds (kind[f], a FaceKind, of the 2 dim faces): Kronecker
+  // products of 1D forms in the eigenvector basis, in which the mass matrix is the identity.  An interior face gives
+  // half of what a Dirichlet face gives, a Neumann face nothing.
+  // g.dim == 2: (p+1)^2 entries (JacobiTransformed, laplace_operator_dg.h:2162)
+  void transformed_diagonal(const Host1D &h, const Geometry &g, const int *kind, std::vector<double> &diag);
 } // namespace mgx::dg

@@ -33,6 +33,14 @@ namespace
   using namespace mgx::dg::device; // DGConst, DGArgs and the line products, shared with the 2D kernel
   using mgx::kMaxN;
 
+  // This file is compiled twice (Makefile).  The second unit, MGX_DG_NEUMANN_UNIT = 1, holds the variant of the cell
+  // kernel for operators with Neumann faces (neighbour entry MGX_DG_NEUMANN) and nothing else; operators without such
+  // faces run the kernels of the first unit, whose code the variant does not touch.
+#ifndef MGX_DG_NEUMANN_UNIT
+#define MGX_DG_NEUMANN_UNIT 0
+#endif
+  constexpr bool kNeumannUnit = MGX_DG_NEUMANN_UNIT != 0;
+
   template <int P, typename T>
   struct DGCfg
   {
@@ -191,7 +199,9 @@ namespace
   }
 
   // GHOSTS (Hermite-like basis on a decomposed mesh): neighbour entries >= A.n_owned are ghost faces
-  template <int P, typename T, int TYPE, int ACTION, bool GHOSTS = false>
+  // NEUMANN: a negative neighbour entry is MGX_DG_BOUNDARY or MGX_DG_NEUMANN, and the inverse diagonals are indexed by
+  // the kinds of the six faces in base 3 (face_kind_code); without it every negative entry is a Dirichlet face
+  template <int P, typename T, int TYPE, int ACTION, bool GHOSTS, bool NEUMANN>
   __global__ void __launch_bounds__((DGCfg<P, T>::THREADS), (DGCfg<P, T>::MINW)) dg_cell_kernel(const DGArgs<T> A)
   {
     using C         = DGCfg<P, T>;
@@ -239,8 +249,11 @@ namespace
     for (int f = 0; f < 6; ++f)
       {
         nb[f] = A.neigh[(size_t)cell * 6 + f];
-        cat |= (nb[f] < 0 ? 1u : 0u) << f;
+        if constexpr (!NEUMANN)
+          cat |= (nb[f] < 0 ? 1u : 0u) << f;
       }
+    if constexpr (NEUMANN)
+      cat = face_kind_code<6>(nb);
 
     if constexpr (ACTION == kJacobi)
       {
@@ -430,11 +443,17 @@ namespace
             for (int s = 0; s < 2; ++s)
               {
                 const int  f = 2 * d + s;
-                const bool dirichlet = nb[f] < 0;
-                const T    te = dirichlet ? To[f] : E0(s)[fidx];
-                const T    ne = dirichlet ? No[f] : E1(s)[fidx];
+                // NEUMANN: te = -To, ne = -No and no jump -- sum of the traces, sum of the normal derivatives and the
+                // weighted jump are exact zeros and the face gives nothing to the form, on sheared cells too (mirroring
+                // the value alone would leave the tangential part of the mean normal derivative).  Written as selects.
+                const bool dirichlet = NEUMANN ? nb[f] == MGX_DG_BOUNDARY : nb[f] < 0;
+                const bool neumann   = NEUMANN && nb[f] == MGX_DG_NEUMANN;
+                const T    te = dirichlet ? To[f] : (neumann ? -To[f] : E0(s)[fidx]);
+                const T    ne = dirichlet ? No[f] : (neumann ? -No[f] : E1(s)[fidx]);
                 sN[s]         = No[f] + ne;
                 wJ[s]         = wq * (dirichlet ? T(2) * To[f] : To[f] - te);
+                if (neumann)
+                  wJ[s] = T(0);
                 E0(s)[fidx]   = To[f] + te;
                 E1(s)[fidx]   = wJ[s];
               }
@@ -708,6 +727,7 @@ namespace
   }
 
 
+#if !MGX_DG_NEUMANN_UNIT
   template <typename T>
   void fill_const(const Host1D &h, const Geometry &g, DGConst<T> &c)
   {
@@ -786,6 +806,7 @@ namespace
       }
     c.hderiv = (T)h.hderiv;
   }
+#endif
 
   template <int P, int TYPE, int ACTION, typename T>
   void launch_one(hipStream_t s, const DGArgs<T> &a, bool ghosts)
@@ -795,11 +816,13 @@ namespace
     if constexpr (TYPE == MGX_DG_HERMITE && ACTION != kJacobi)
       if (ghosts)
         {
-          hipLaunchKernelGGL((dg_cell_kernel<P, T, TYPE, ACTION, true>), dim3(grid), dim3(C::THREADS), 0, s, a);
+          hipLaunchKernelGGL((dg_cell_kernel<P, T, TYPE, ACTION, true, kNeumannUnit>), dim3(grid), dim3(C::THREADS), 0, s, a);
           return;
         }
-    hipLaunchKernelGGL((dg_cell_kernel<P, T, TYPE, ACTION>), dim3(grid), dim3(C::THREADS), 0, s, a);
+    hipLaunchKernelGGL((dg_cell_kernel<P, T, TYPE, ACTION, false, kNeumannUnit>), dim3(grid), dim3(C::THREADS), 0, s, a);
   }
+
+#if !MGX_DG_NEUMANN_UNIT
 
   template <typename T>
   __global__ void __launch_bounds__(256)
@@ -848,9 +871,21 @@ namespace
         v[i]             = (T)((double)(g % 11u) - mean);
       }
   }
+#endif
 
 } // namespace
 
+#if MGX_DG_NEUMANN_UNIT
+namespace mgx::dg
+{
+  // every action but kRestrict: the solver on the FE_Q hierarchy refuses operators with Neumann faces
+  bool launch_dg_cells_neumann(hipStream_t s, const CellOperands &op, const DGLaunch &l)
+  {
+    return dispatch_cells<kVmult, kCgSums, kChebyshev, kResidual, kJacobi, kPcgSums>(
+      op, l, [&](auto P, auto TYPE, auto ACTION, const auto &a) { launch_one<P.value, TYPE.value, ACTION.value>(s, a, op.has_ghosts); });
+  }
+} // namespace mgx::dg
+#else
 namespace mgx::dg
 {
   int launch_dg_cells(hipStream_t s, const CellOperands &op, const DGLaunch &l)
@@ -858,6 +893,7 @@ namespace mgx::dg
     if (l.n_cells == 0)
       return MGX_OK;
     const bool launched =
+      op.has_neumann ? (op.dim == 2 ? launch_dg_cells_2d_neumann(s, op, l) : launch_dg_cells_neumann(s, op, l)) :
       op.dim == 2 ? launch_dg_cells_2d(s, op, l)
                   : dispatch_cells<kVmult, kRestrict, kCgSums, kChebyshev, kResidual, kJacobi, kPcgSums>(
                       op, l, [&](auto P, auto TYPE, auto ACTION, const auto &a) { launch_one<P.value, TYPE.value, ACTION.value>(s, a, op.has_ghosts); });
@@ -910,3 +946,4 @@ namespace mgx::dg
     });
   }
 } // namespace mgx::dg
+#endif

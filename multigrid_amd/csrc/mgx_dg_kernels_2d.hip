@@ -25,6 +25,13 @@ namespace
   using namespace mgx::dg;
   using namespace mgx::dg::device;
 
+  // compiled twice, as mgx_dg_kernels.hip is: MGX_DG_NEUMANN_UNIT = 1 holds the variant of the cell kernel for operators
+  // with Neumann faces and its launch, nothing else
+#ifndef MGX_DG_NEUMANN_UNIT
+#define MGX_DG_NEUMANN_UNIT 0
+#endif
+  constexpr bool kNeumannUnit = MGX_DG_NEUMANN_UNIT != 0;
+
   template <int P, typename T>
   struct DGCfg2
   {
@@ -76,7 +83,9 @@ namespace
       }
   }
 
-  template <int P, typename T, int TYPE, int ACTION>
+  // NEUMANN: as in the 3D kernel -- a negative neighbour entry is MGX_DG_BOUNDARY or MGX_DG_NEUMANN, the inverse diagonals
+  // are indexed by the kinds of the four faces in base 3
+  template <int P, typename T, int TYPE, int ACTION, bool NEUMANN>
   __global__ void __launch_bounds__((DGCfg2<P, T>::THREADS)) dg_cell_kernel_2d(const DGArgs<T> A)
   {
     using C         = DGCfg2<P, T>;
@@ -111,8 +120,11 @@ namespace
     for (int f = 0; f < 4; ++f)
       {
         nb[f] = A.neigh[(size_t)cell * 4 + f];
-        cat |= (nb[f] < 0 ? 1u : 0u) << f;
+        if constexpr (!NEUMANN)
+          cat |= (nb[f] < 0 ? 1u : 0u) << f;
       }
+    if constexpr (NEUMANN)
+      cat = face_kind_code<4>(nb);
 
     if constexpr (ACTION == kJacobi)
       {
@@ -253,11 +265,15 @@ namespace
             for (int s = 0; s < 2; ++s)
               {
                 const int  f = 2 * d + s;
-                const bool dirichlet = nb[f] < 0;
-                const T    te = dirichlet ? To[f] : E0(s)[a];
-                const T    ne = dirichlet ? No[f] : E1(s)[a];
+                // NEUMANN: te = -To, ne = -No and no jump: the face gives nothing to the form (see the 3D kernel)
+                const bool dirichlet = NEUMANN ? nb[f] == MGX_DG_BOUNDARY : nb[f] < 0;
+                const bool neumann   = NEUMANN && nb[f] == MGX_DG_NEUMANN;
+                const T    te = dirichlet ? To[f] : (neumann ? -To[f] : E0(s)[a]);
+                const T    ne = dirichlet ? No[f] : (neumann ? -No[f] : E1(s)[a]);
                 sN[s]         = No[f] + ne;
                 wJ[s]         = wq * (dirichlet ? T(2) * To[f] : To[f] - te);
+                if (neumann)
+                  wJ[s] = T(0);
                 E0(s)[a]      = To[f] + te;
                 E1(s)[a]      = wJ[s];
               }
@@ -428,12 +444,19 @@ namespace
   void launch_one_2d(hipStream_t s, const DGArgs<T> &a)
   {
     using C = DGCfg2<P, T>;
-    hipLaunchKernelGGL((dg_cell_kernel_2d<P, T, TYPE, ACTION>), dim3(cell_groups<C>(a.n_cells)), dim3(C::THREADS), 0, s, a);
+    hipLaunchKernelGGL((dg_cell_kernel_2d<P, T, TYPE, ACTION, kNeumannUnit>), dim3(cell_groups<C>(a.n_cells)), dim3(C::THREADS), 0, s, a);
   }
 } // namespace
 
 namespace mgx::dg
 {
+#if MGX_DG_NEUMANN_UNIT
+  bool launch_dg_cells_2d_neumann(hipStream_t s, const CellOperands &op, const DGLaunch &l)
+  {
+    return dispatch_cells<kVmult, kChebyshev, kResidual, kJacobi, kPcgSums>(
+      op, l, [&](auto P, auto TYPE, auto ACTION, const auto &a) { launch_one_2d<P.value, TYPE.value, ACTION.value>(s, a); });
+  }
+#else
   bool launch_dg_cells_2d(hipStream_t s, const CellOperands &op, const DGLaunch &l)
   {
     return dispatch_cells<kVmult, kChebyshev, kResidual, kJacobi, kPcgSums>(
@@ -441,4 +464,5 @@ namespace mgx::dg
   }
 
   uint32_t cell_grid_2d(int number, int p, uint32_t n_cells) { return cell_groups<DGCfg2>(number, p, n_cells); }
+#endif
 } // namespace mgx::dg

@@ -21,6 +21,14 @@
 // same way.  A cell reads its Dirichlet faces off the neighbour table: the branch is uniform per cell, every barrier
 // is outside it.  One writer per entry, no atomics: the same bits in every run.
 //
+// Operators with Neumann faces run a variant of the right-hand side kernel (MIXED) that tells the two kinds of boundary
+// entry apart and adds int_F h phi_i on the Neumann faces: V = B, W = 0 with B = w fw[d] h in the face point -- no
+// tangential part, so B never leaves the registers of the point's owner.  h is sampled in the face points, or the
+// normal derivative n . grad u of a sine product u: d_k u = amplitude wave[k] cos(.) prod_{d != k} sin(.), from the
+// sines and cosines the complex products hold anyway, n the outward unit normal of the operator's geometry.  A third
+// function means a third table of the cell-independent factors; the kernels of operators without Neumann faces keep
+// their two.
+//
 // The sine product amplitude prod_d sin(wave[d] x_d + phase[d]) with x = origin + J (pos + xi) is separable in the
 // reference coordinates through the complex exponential: sin(t_d + sum_a wave[d] J[d][a] xi_a) is the imaginary part of
 // e^{i t_d} prod_a e^{i wave[d] J[d][a] xi_a}.  The factors of the second kind do not depend on the cell: dim^2 (p+3)
@@ -38,7 +46,8 @@ namespace
   using namespace mgx::dg;
   using namespace mgx::dg::device;
 
-  template <int P, int DIM>
+  // NFN: functions whose sine-product tables the LDS holds (f and g; the MIXED kernel: and h)
+  template <int P, int DIM, int NFN = 2>
   struct RhsCfg
   {
     static constexpr int N     = P + 1;
@@ -50,10 +59,10 @@ namespace
     static constexpr int PL    = DIM == 3 ? (N * PX) | 1 : 0; // odd plane pitch
     static constexpr int TILE  = DIM == 3 ? N * PL : N * PX;
     static constexpr int NF    = 2 * DIM;
-    static constexpr int BASES = 2 * DIM * 2;                // e^{i t_d} of two functions
+    static constexpr int BASES = 2 * DIM * NFN;              // e^{i t_d} of every function
     static constexpr int CELL  = (TILE + NF * TPC + BASES) | 1;
     static constexpr int TAB1  = DIM * DIM * (N + 2) * 2;    // e^{i wave[d] J[d][a] xi} of one function
-    static constexpr int LDS   = CPW * CELL + 2 * TAB1;
+    static constexpr int LDS   = CPW * CELL + NFN * TAB1;
     static_assert(LDS * (int)sizeof(double) <= 65536, "cells of a workgroup do not fit the LDS");
   };
 
@@ -69,6 +78,13 @@ namespace
     const int32_t    *pos; // [n_cells][dim] or nullptr
     uint32_t          n_cells;
     DGRhsGeometry     geo;
+  };
+
+  // ... of the MIXED right-hand side: and the flux on the Neumann faces, or the potential it derives from
+  template <typename T>
+  struct RhsArgsMixed : RhsArgs<T>
+  {
+    DGFunctionArgs h;
   };
 
   // out[i] = sum_q M[q*N+i] in[q] with a matrix of another number type
@@ -173,17 +189,51 @@ namespace
     return v;
   }
 
+  // the gradient of the sine product in that point: grad[k] = amplitude wave[k] cos(.) prod_{d != k} sin(.)
+  template <int N, int DIM>
+  __device__ __forceinline__ void sine_gradient(const DGFunctionArgs &fn, const double *tab, const double *base, const int (&ix)[DIM],
+                                                double (&grad)[DIM])
+  {
+    double co[DIM], si[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      {
+        double re = base[2 * d], im = base[2 * d + 1];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a)
+          {
+            const double *t  = tab + ((d * DIM + a) * (N + 2) + ix[a]) * 2;
+            const double  r2 = re * t[0] - im * t[1];
+            im               = fma(re, t[1], im * t[0]);
+            re               = r2;
+          }
+        co[d] = re;
+        si[d] = im;
+      }
+#pragma unroll
+    for (int k = 0; k < DIM; ++k)
+      {
+        double v = fn.amplitude * fn.wave[k] * co[k];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          if (d != k)
+            v *= si[d];
+        grad[k] = v;
+      }
+  }
+
   // what both kernels begin with: thread -> cell and lines, the LDS of the cell, the tables of the sine products
-  template <int P, int DIM, typename T>
+  template <int P, int DIM, typename T, int NFN = 2>
   struct CellSetup
   {
-    using C = RhsCfg<P, DIM>;
+    using C = RhsCfg<P, DIM, NFN>;
     int      tid, cw, t, a, b;
     bool     active, store;
     uint32_t cell;
     double  *U, *F, *base, *tab;
 
-    __device__ __forceinline__ CellSetup(const RhsArgs<T> &A, double *lds)
+    template <typename ARGS>
+    __device__ __forceinline__ CellSetup(const ARGS &A, double *lds)
     {
       tid    = threadIdx.x;
       cw     = tid / C::TPC;
@@ -201,6 +251,8 @@ namespace
       tab  = lds + C::CPW * C::CELL;
       sine_table<C::N, DIM>(A.f, A.geo, tab, tid, C::WG);
       sine_table<C::N, DIM>(A.g, A.geo, tab + C::TAB1, tid, C::WG);
+      if constexpr (NFN > 2)
+        sine_table<C::N, DIM>(A.h, A.geo, tab + 2 * C::TAB1, tid, C::WG);
       if (active)
         for (int k = t; k < 2 * DIM; k += C::TPC)
           {
@@ -208,6 +260,10 @@ namespace
             if (fn.kind == MGX_DG_FN_SINE_PRODUCT)
               sine_base<DIM>(fn, A.geo, A.pos + (size_t)cell * DIM, k % DIM, base + (k < DIM ? 0 : 2 * DIM));
           }
+      if constexpr (NFN > 2) // (a loop of its own: a choice between three functions copies the arguments to scratch)
+        if (active && A.h.kind == MGX_DG_FN_SINE_PRODUCT)
+          for (int d = t; d < DIM; d += C::TPC)
+            sine_base<DIM>(A.h, A.geo, A.pos + (size_t)cell * DIM, d, base + 4 * DIM);
       __syncthreads();
     }
     // 1D indices of point q of the thread's line of the last direction
@@ -233,20 +289,34 @@ namespace
     }
   };
 
-  template <int P, int DIM, typename T>
-  __global__ void __launch_bounds__((RhsCfg<P, DIM>::WG)) dg_rhs_kernel(const RhsArgs<T> A)
+  // MIXED: the operator has Neumann faces (see the head of the file)
+  template <int P, int DIM, typename T, bool MIXED>
+  __global__ void __launch_bounds__((RhsCfg<P, DIM>::WG))
+    dg_rhs_kernel(const std::conditional_t<MIXED, RhsArgsMixed<T>, RhsArgs<T>> A)
   {
-    using C         = RhsCfg<P, DIM>;
+    using C         = RhsCfg<P, DIM, MIXED ? 3 : 2>;
     constexpr int N = C::N, TPC = C::TPC, NF = C::NF;
     __shared__ __attribute__((aligned(16))) double lds[C::LDS];
     const DGConst<T> *__restrict__ c = A.c;
-    const CellSetup<P, DIM, T> K(A, lds);
+    const CellSetup<P, DIM, T, MIXED ? 3 : 2> K(A, lds);
     const int a = K.a, b = K.b, t = K.t;
 
-    bool dirichlet[NF];
+    bool dirichlet[NF], neumann[NF];
 #pragma unroll
     for (int f = 0; f < NF; ++f)
-      dirichlet[f] = A.g.kind != MGX_DG_FN_NONE && A.neigh[(size_t)K.cell * NF + f] < 0;
+      {
+        if constexpr (MIXED)
+          {
+            const int32_t entry = A.neigh[(size_t)K.cell * NF + f];
+            dirichlet[f]        = A.g.kind != MGX_DG_FN_NONE && entry == MGX_DG_BOUNDARY;
+            neumann[f]          = A.h.kind != MGX_DG_FN_NONE && entry == MGX_DG_NEUMANN;
+          }
+        else
+          {
+            dirichlet[f] = A.g.kind != MGX_DG_FN_NONE && A.neigh[(size_t)K.cell * NF + f] < 0;
+            neumann[f]   = false;
+          }
+      }
 
     // ---- 1. the line of the last direction: JxW f in its Gauss points; B = w fw g in the thread's face points
     double h[N];
@@ -311,6 +381,28 @@ namespace
             V[f] = 2.0 * A.geo.sigma[d] * B[t] - ns * tang;
             W[f] = -ns * A.geo.cn[d][d] * B[t];
           }
+        if constexpr (MIXED)
+          if (K.active && neumann[f])
+            {
+              // V = B = w fw[d] h, W = 0
+              const int d = f / 2;
+              double    flux;
+              if (A.h.kind == MGX_DG_FN_SINE_PRODUCT)
+                {
+                  int    ix[DIM];
+                  double grad[DIM];
+                  K.face_point(d, f % 2, ix);
+                  sine_gradient<N, DIM>(A.h, K.tab + 2 * C::TAB1, K.base + 4 * DIM, ix, grad);
+                  flux = 0;
+#pragma unroll
+                  for (int k = 0; k < DIM; ++k)
+                    flux = fma(A.geo.normal[d][k], grad[k], flux);
+                  flux = f % 2 ? flux : -flux;
+                }
+              else
+                flux = A.h.face_values[((size_t)K.cell * NF + f) * TPC + t];
+              V[f] = flux * K.face_weight(A.geo) * A.geo.fw[d];
+            }
       }
 
     // ---- 3. the faces of every direction join in the Gauss points, last direction first; the lines of the first
@@ -323,7 +415,7 @@ namespace
           {
             if (d != DIM - 1)
               ld_line<N>(K.U, base, stride, h);
-            if (dirichlet[2 * d] || dirichlet[2 * d + 1])
+            if (dirichlet[2 * d] || dirichlet[2 * d + 1] || neumann[2 * d] || neumann[2 * d + 1])
               {
 #pragma unroll
                 for (int q = 0; q < N; ++q)
@@ -451,12 +543,22 @@ namespace mgx::dg
     return groups;
   }
 
-  bool launch_dg_rhs(hipStream_t s, const DGRhsOperands &op, const DGFunctionArgs &f, const DGFunctionArgs &g, void *dst)
+  bool launch_dg_rhs(hipStream_t s, const DGRhsOperands &op, const DGFunctionArgs &f, const DGFunctionArgs &g,
+                     const DGFunctionArgs &h, void *dst)
   {
     return dispatch_rhs(op, [&](auto P, auto DIM, auto t) {
-      using T = decltype(t);
-      hipLaunchKernelGGL((dg_rhs_kernel<P.value, DIM.value, T>), dim3(rhs_grid(op.degree, op.n_cells, op.dim)),
-                         dim3(RhsCfg<P.value, DIM.value>::WG), 0, s, make_args<T>(op, f, g, nullptr, dst, nullptr));
+      using T               = decltype(t);
+      const dim3       grid = dim3(rhs_grid(op.degree, op.n_cells, op.dim)), block = dim3(RhsCfg<P.value, DIM.value>::WG);
+      const RhsArgs<T> args = make_args<T>(op, f, g, nullptr, dst, nullptr);
+      if (op.has_neumann)
+        {
+          RhsArgsMixed<T> mixed;
+          static_cast<RhsArgs<T> &>(mixed) = args;
+          mixed.h                          = h;
+          hipLaunchKernelGGL((dg_rhs_kernel<P.value, DIM.value, T, true>), grid, block, 0, s, mixed);
+        }
+      else
+        hipLaunchKernelGGL((dg_rhs_kernel<P.value, DIM.value, T, false>), grid, block, 0, s, args);
     });
   }
 

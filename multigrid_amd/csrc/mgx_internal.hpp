@@ -605,10 +605,12 @@ namespace mgx
       int            number = 0, degree = 0, basis = 0;
       const int32_t *neigh    = nullptr;
       const void    *consts   = nullptr;
-      const void    *inv_diag = nullptr; // [4^dim][(p+1)^dim]
+      // [4^dim][(p+1)^dim], row: bit f set for a Dirichlet face; has_neumann: [9^dim][(p+1)^dim], row: face_kind_code
+      const void    *inv_diag = nullptr;
       uint32_t       n_owned  = 0;       // owned cells of the operator: neighbour entries >= n_owned are ghosts
       bool           has_ghosts = false;
       int            dim        = 3;     // 2: quadrilaterals, neigh [n_cells][4] (mgx_dg_kernels_2d.hip)
+      bool           has_neumann = false; // a neighbour entry is MGX_DG_NEUMANN: the variant kernels run
     };
 
     // one launch of the cell kernel; vectors and P1 in the operator's number type
@@ -661,6 +663,7 @@ namespace mgx
     struct DGRhsGeometry
     {
       double jac[9], origin[3], xq[kMaxN], wq[kMaxN], det, sigma[3], fw[3], cn[3][3];
+      double normal[3][3]; // normal[d]: the unit normal towards +xi_d in real coordinates
     };
     struct DGRhsOperands
     {
@@ -669,11 +672,14 @@ namespace mgx
       const void    *consts   = nullptr; // the constant block of the cell kernel: S, D and the end values b, g
       const int32_t *cell_pos = nullptr; // device [n_cells][dim]; needed by sine products only
       uint32_t       n_cells  = 0;       // owned cells
+      bool           has_neumann = false; // a neighbour entry is MGX_DG_NEUMANN: the MIXED kernel runs
       DGRhsGeometry  geo;
     };
-    // dst (number type) = int f phi_i + sum over the Dirichlet faces of int g (sigma_F phi_i - d_n phi_i) on the owned
-    // cells; false: no kernel for this degree or dimension
-    bool launch_dg_rhs(hipStream_t s, const DGRhsOperands &op, const DGFunctionArgs &f, const DGFunctionArgs &g, void *dst);
+    // dst (number type) = int f phi_i + sum over the Dirichlet faces of int g (sigma_F phi_i - d_n phi_i) + sum over
+    // the Neumann faces of int h phi_i on the owned cells (h sampled: the flux in face_values; h a sine product: the
+    // potential u of h = n . grad u); false: no kernel for this degree or dimension
+    bool launch_dg_rhs(hipStream_t s, const DGRhsOperands &op, const DGFunctionArgs &f, const DGFunctionArgs &g,
+                       const DGFunctionArgs &h, void *dst);
     // partials [rhs_grid][4]: block sums {sum (u_h - u)^2 JxW, sum JxW, 0, 0}, to be added by launch_reduce4
     bool     launch_dg_l2_error(hipStream_t s, const DGRhsOperands &op, const DGFunctionArgs &u, const void *vec, double *partials);
     uint32_t rhs_grid(int p, uint32_t n_cells, int dim); // workgroups of either launch

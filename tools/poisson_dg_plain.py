@@ -6,7 +6,7 @@ The same problem, printed lines and table row as tools/poisson_dg.py, whose solv
 
     python tools/poisson_dg_plain.py [degree=3] [n_refine=5] [n_pre_smooth=3] [tolerance=1e-9] [--vcycle f32|f64]
                                      [--basis 0|1|2] [--solution reference|vanishing] [--levels] [--dim 2|3]
-                                     [--boundary homogeneous|data]
+                                     [--boundary homogeneous|data] [--neumann 0,3]
 
 --dim 2: the dimension the reference's driver is compiled for (poisson_dg_plain/program.cc:65): the square [-0.9, 1]^2,
 rhs dim (3 pi)^2 prod sin(3 pi x_d) (program.cc:140), the same printed lines and table row.
@@ -23,7 +23,12 @@ and shows the discretisation error (tests/test_gpu_dg_plain.py).
 phi_i - d_n phi_i) on every Dirichlet face (DGLaplaceOperator.compute_rhs), so the reference solution converges too;
 right-hand side and error are then formed on the device (compute_rhs, compute_l2_error) and a line "Time compute rhs"
 is printed as the reference prints it (multigrid_solver_dg_plain.h:188).  The default, homogeneous, is the reference's
-volume-only vector from the host: nothing it prints changes."""
+volume-only vector from the host: nothing it prints changes.
+
+--neumann 0,3 (with --boundary data, either --dim): the listed sides of the box, face numbers 2d+s (direction d, lower
+s = 0 / upper s = 1), are Neumann faces on every level; the right-hand side carries the exact flux there, h = n . grad u
+of the chosen solution (the potential form of compute_rhs's h), and its boundary values on the other sides.  At least
+one side must stay a Dirichlet side.  One more line names the Neumann sides; without the option nothing changes."""
 import argparse
 import os
 import sys
@@ -50,18 +55,26 @@ def main():
     ap.add_argument("--dim", type=int, choices=[2, 3], default=3)
     ap.add_argument("--boundary", choices=["homogeneous", "data"], default="homogeneous",
                     help="data: boundary values of the solution in the right-hand side; rhs and error on the device")
+    ap.add_argument("--neumann", default="", help="sides 2d+s that are Neumann faces, e.g. 0,3 (needs --boundary data)")
     a = ap.parse_args()
+    a.neumann = tuple(sorted(set(int(f) for f in a.neumann.split(",") if f.strip() != "")))
+    if a.neumann and a.boundary != "data":
+        ap.error("--neumann needs --boundary data: the flux enters the right-hand side on the device")
+    if any(f < 0 or f >= 2 * a.dim for f in a.neumann) or len(a.neumann) == 2 * a.dim:
+        ap.error("--neumann: sides are face numbers 0 .. %d, and one side must stay a Dirichlet side" % (2 * a.dim - 1))
     vnum = mg.F32 if a.vcycle == "f32" else mg.F64
     t0 = time.time()
     ctx = mg.Context(0)
     n_levels = a.n_refine + 1
     dim = a.dim
     solver = mg.DGPlainMultigridSolver(ctx, a.degree, a.basis, (1,) * dim, np.eye(dim) * 1.9, n_levels, a.n_pre_smooth, vnum,
-                                       origin=(-0.9,) * dim)
+                                       origin=(-0.9,) * dim, neumann_sides=a.neumann)
     n = solver.m()
     nc = n // (a.degree + 1) ** dim
     print("Number of degrees of freedom: %d (%d cells, FE_DGQHermite(%d) on every one of %d levels, V-cycle in %s)"
           % (n, nc, a.degree, n_levels, a.vcycle))
+    if a.neumann:
+        print("Neumann sides (2d+s): %s, exact flux in the right-hand side" % ",".join(map(str, a.neumann)))
     for l in range(n_levels):
         i = solver.smoother_info(l)
         print("level %2d  cells %9d  smoother degree %3d  lambda_max %.6f  cg_its %d"
@@ -114,7 +127,7 @@ def with_boundary_data(a, ctx, solver, t0):
     print("Time setup                    %.3f s" % (time.time() - t0))
     ctx.sync()
     t = time.perf_counter()
-    A.compute_rhs(b, f, u)
+    A.compute_rhs(b, f, u, u if a.neumann else None)
     ctx.sync()
     dt = time.perf_counter() - t
     print("Time compute rhs              %.6f s   rhs_norm = %.6e" % (dt, ctx.l2_norm(b)))
