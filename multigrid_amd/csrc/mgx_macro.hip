@@ -317,20 +317,24 @@ namespace mgx
             }
         }
     };
-    T    xs[kKeepX ? IT : 1];
-    auto gather_land = [&]() {
+    // kept across the sweeps for the update: the source value x_i of the item -- kChebInit: the gathered b_i, from
+    // which the write-out forms x_i = x_1 again (cheb_first_iterate) instead of loading b a second time
+    constexpr bool kKeepRhs = keeps_rhs(MODE);
+    T              xs[kKeepX ? IT : 1];
+    auto           gather_land = [&]() {
 #pragma unroll
       for (int it = 0; it < IT; ++it)
         {
-          T v = g[0][it];
+          T       v  = g[0][it];
+          const T bi = g[DTAB ? 0 : NG - 1][it]; // kChebInit: the right-hand side (DTAB: the only operand gathered)
           if (MODE == kChebInit) // x_1 = (1/theta) D^-1 b, never stored
-            v = DTAB ? post.f0 * dv[DTAB ? it : 0] * g[0][it] : post.f0 * g[0][it] * g[NG - 1][it];
+            v = cheb_first_iterate(post.f0, DTAB ? dv[DTAB ? it : 0] : g[0][it], bi);
           if (MODE == kCgUpdate) // p = beta p + q, or p = q in the first step (laplace_operator.h:660-688)
             v = post.f1 == T(0) ? g[NG - 1][it] : post.f2 * g[0][it] + g[NG - 1][it];
           if (live(it))
             U[item_point(mw[it])] = v;
           if (kKeepX)
-            xs[it] = v;
+            xs[it] = kKeepRhs ? bi : v;
         }
     };
 
@@ -659,10 +663,16 @@ namespace mgx
                       T                 res[2];
 #pragma unroll
                       for (int e = 0; e < 2; ++e)
-                        res[e] = (e == 0 || pair)
-                                   ? post_finish<T, MODE>(post, o.pv[e], o.av[e], o.ov[e], DTAB ? dv[DTAB ? v0 + e : 0] : o.bv[e],
-                                                          last, val[j][e], xs[kKeepX ? v0 + e : 0])
-                                   : T(0);
+                        {
+                          const int v    = (e == 0 || pair) ? v0 + e : v0;
+                          // inverse diagonal: per-item table, or loaded with the operands (the value the gather used)
+                          const T   dinv = DTAB ? dv[DTAB ? v : 0] : o.bv[e];
+                          const T   kept = xs[kKeepX ? v : 0]; // x_i; kChebInit: b_i, and x_i = x_1 is formed from it again
+                          const T   xi   = kKeepRhs ? cheb_first_iterate(post.f0, dinv, kept) : kept;
+                          res[e]         = (e == 0 || pair) ? post_finish<T, MODE>(post, o.pv[e], kKeepRhs ? kept : o.av[e], o.ov[e], dinv,
+                                                                                   last, val[j][e], xi)
+                                                            : T(0);
+                        }
                       constexpr int kStAux = (MODE == kPlain || MODE == kResidual) ? kAuxNt : 0;
                       auto          st     = [&](rsrc_t r, uint32_t f) {
                         if (pair)
@@ -863,14 +873,33 @@ namespace mgx
 #endif
 
   // ------------------------------------------------------------------------------------------
-  // Item-ordered table of the inverse diagonal (DTAB).  collect: every brick writes the value of
-  // each of its unconstrained items into the table (all bricks write the same value if the diagonal
-  // is periodic); verify: any item of any brick that differs bitwise from the table raises the flag.
+  // Item-ordered table of the inverse diagonal (DTAB).  collect (one thread per item): the value of the item in the
+  // last brick that has it unconstrained -- a fixed choice: the bricks agree up to the rounding of the assembly only
+  // (see verify), and a table that took whichever brick wrote last differed in the last bits from one set-up to the
+  // next (p = 5, 6 on 8^3 cells: smoother results not reproducible bitwise); verify (one workgroup per brick): any item
+  // of any brick that differs from the table by more than that rounding raises the flag.
   template <typename T, bool VERIFY>
   __global__ void diag_table_kernel(const T *__restrict__ inv_diag, const uint32_t *__restrict__ ent_base,
-                                    const uint32_t *__restrict__ item_map, uint32_t ne, uint32_t npts, T *table,
-                                    uint32_t *flag)
+                                    const uint32_t *__restrict__ item_map, uint32_t ne, uint32_t npts, uint32_t n_bricks,
+                                    T *table, uint32_t *flag)
   {
+    if (!VERIFY)
+      {
+        const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= npts)
+          return;
+        const uint32_t m = item_map[i];
+        for (uint32_t brick = n_bricks; brick-- > 0;)
+          {
+            const uint32_t w = ent_base[(size_t)brick * ne + item_slot(m)];
+            if (w != kInvalid)
+              {
+                table[i] = inv_diag[ent_index(w) + item_offset(m)];
+                break;
+              }
+          }
+        return;
+      }
     const uint32_t brick = blockIdx.x;
     for (uint32_t i = threadIdx.x; i < npts; i += blockDim.x)
       {
@@ -878,20 +907,15 @@ namespace mgx
         if (w == kInvalid)
           continue;
         const T v = inv_diag[ent_index(w) + item_offset(m)];
-        if (!VERIFY)
-          table[i] = v;
-        else
-          {
-            // equal up to the rounding of the assembly: the cell contributions to one diagonal entry
-            // are added in the order the atomics arrive, which differs from brick to brick in the
-            // last bits (a few ulp); anything beyond that means the diagonal is not periodic
-            const T    t   = table[i];
-            const T    tol = (sizeof(T) == 8 ? T(1e-14) : T(2e-6)) * (t < 0 ? -t : t);
-            const T    dvt = v - t;
-            const bool same = (dvt < 0 ? -dvt : dvt) <= tol;
-            if (!same)
-              atomicOr(flag, 1u);
-          }
+        // equal up to the rounding of the assembly: the cell contributions to one diagonal entry
+        // are added in an order that differs from brick to brick, hence the last bits (a few ulp);
+        // anything beyond that means the diagonal is not periodic
+        const T    t   = table[i];
+        const T    tol = (sizeof(T) == 8 ? T(1e-14) : T(2e-6)) * (t < 0 ? -t : t);
+        const T    dvt = v - t;
+        const bool same = (dvt < 0 ? -dvt : dvt) <= tol;
+        if (!same)
+          atomicOr(flag, 1u);
       }
   }
 
@@ -905,10 +929,10 @@ namespace mgx
     using T             = MGX_MACRO_T;
     const BrickData &bd = op.bricks;
     const uint32_t   nb = op.p <= 4 ? 4 : 2, g = nb * op.p + 1, npts = g * g * g, e1 = 2 * nb + 1, ne = e1 * e1 * e1;
-    hipLaunchKernelGGL((diag_table_kernel<T, false>), dim3(bd.n_bricks), dim3(256), 0, s, (const T *)op.inv_diag,
-                       bd.ent_base, item_map, ne, npts, (T *)table, flag_dev);
+    hipLaunchKernelGGL((diag_table_kernel<T, false>), dim3((npts + 255) / 256), dim3(256), 0, s, (const T *)op.inv_diag,
+                       bd.ent_base, item_map, ne, npts, (uint32_t)bd.n_bricks, (T *)table, flag_dev);
     hipLaunchKernelGGL((diag_table_kernel<T, true>), dim3(bd.n_bricks), dim3(256), 0, s, (const T *)op.inv_diag,
-                       bd.ent_base, item_map, ne, npts, (T *)table, flag_dev);
+                       bd.ent_base, item_map, ne, npts, (uint32_t)bd.n_bricks, (T *)table, flag_dev);
   }
 
   // vmult_with_cg_update on a brick-scheduled level of one rank (mgx_api.cpp handles the rest):

@@ -26,8 +26,9 @@
 // Measured: plain 104 -> 95 us per colour launch.  Also measured and not kept (tools/experiments/
 // r04_macro2_wide_early_variants.hip.txt): the gather of the next brick issued before the sweeps (its loads then queue
 // behind the stores of the write-out just before: 99 us); 512-thread workgroups with the sweeps as cell-block tasks
-// (four waves per SIMD: 98 us, the LDS array 63 % busy); the general Chebyshev iteration on this pipeline (143-148
-// against 144 us: its write-out waits for its operands either way).
+// (four waves per SIMD: 98 us, the LDS array 63 % busy); the GENERAL Chebyshev iteration (kCheb) and its two special
+// cases with a stored first iterate on this pipeline (143-148 against 144 us: their write-out waits for b and x_old
+// either way).  The two Chebyshev forms that never store the first iterate do run here -- see macro2_covers().
 // Barriers order LDS traffic only (lds_barrier): global loads stay in flight across them.
 #include "mgx_macro_device.hpp"
 
@@ -268,7 +269,8 @@ namespace mgx
   // Of the Chebyshev forms the two that never store the first iterate (kChebInit, kChebOldInit) run here, with the inverse
   // diagonal taken from the per-item table (uniform meshes; where it has to be streamed they stay on the first
   // pipeline): 119 -> 116 and 133 -> 126 us per colour launch (kChebInit at p <= 4 only; p = 8: 155 against 141 us on
-  // the first pipeline).  The general iteration (kCheb: 144 -> 148 us) and its
+  // the first pipeline).  kChebInit keeps the b it gathered and loads nothing at write-out (keeps_rhs,
+  // mgx_macro_device.hpp).  The general iteration (kCheb: 144 -> 148 us) and its
   // two special cases gain nothing from the earlier partial sums -- their write-out waits for b and x_old either way --
   // and stay on the first pipeline.
   __host__ __device__ constexpr bool macro2_covers(int mode, int p)
@@ -348,18 +350,21 @@ namespace mgx
             g[j] = buf_ld(MODE == kChebInit ? r_a : rsrc, unit_offset(tab[item_slot(mw[j])], mw[j]), T());
         }
     };
-    T    xs[kKeepX ? IT : 1];
-    auto gather_land = [&]() {
+    // kept across the sweeps for the update: the source value x_i of the item -- kChebInit: the gathered b_i, from
+    // which the write-out forms x_i = x_1 again (cheb_first_iterate) instead of loading b a second time
+    constexpr bool kKeepRhs = keeps_rhs(MODE);
+    T              xs[kKeepX ? IT : 1];
+    auto           gather_land = [&]() {
 #pragma unroll
       for (int j = 0; j < IT; ++j)
         {
           T v = g[j];
           if (MODE == kChebInit)
-            v = post.f0 * dv[kKeepX ? j : 0] * g[j];
+            v = cheb_first_iterate(post.f0, dv[kKeepX ? j : 0], g[j]);
           if (live(j))
             U[item_point(mw[j])] = v;
           if (kKeepX)
-            xs[kKeepX ? j : 0] = v;
+            xs[kKeepX ? j : 0] = kKeepRhs ? g[j] : v;
         }
     };
     // partial sums of the surface slots of the current brick (not FIRST: an earlier colour launch left a sum).  The
@@ -462,6 +467,9 @@ namespace mgx
             // ---- write-out of the Chebyshev forms: x_new = x + f2 D^-1 (b - A x) [+ f1 (x - x_old)] where the brick
             //      completes the DoF, the partial sum to the carrier elsewhere.  The operands b (and x_old) are requested
             //      in chunks, one chunk ahead of the stores; the partial sums are in registers already ----
+            //      (kChebInit with the kept b loads no operand and waits for nothing here; it keeps the chunks all the same:
+            //      as one chunk of IT slots, the form of the plain write-out, the fp64 kernel at p = 4 spills 32 B per lane
+            //      at the 256 registers it has, in chunks it spills nothing)
             constexpr int kChunk = MGX_MACRO2_CHUNK < IT ? MGX_MACRO2_CHUNK : IT, NCH = (IT + kChunk - 1) / kChunk;
             struct Ops
             {
@@ -488,7 +496,7 @@ namespace mgx
                   const bool last  = o[k].w != kInvalid && (o[k].w >> 31);
                   o[k].off         = unit_offset(o[k].w, mw[j]);
                   const uint32_t ol = last ? o[k].off : kOob;
-                  o[k].av          = buf_ld(r_a, ol, T());
+                  o[k].av          = kKeepRhs ? T(0) : buf_ld(r_a, ol, T());
                   o[k].ov          = MODE == kCheb ? buf_ld(r_old, ol, T()) : T(0);
                 }
             };
@@ -514,8 +522,10 @@ namespace mgx
                       continue;
                     const Ops &o   = ops[c & 1][k];
                     const bool vld = o.w != kInvalid, last = vld && (o.w >> 31);
-                    const T    res = post_finish<T, MODE>(post, j >= JINT ? pp[j >= JINT ? j - JINT : 0] : T(0), o.av, o.ov,
-                                                          dv[kKeepX ? j : 0], last, val[k], xs[kKeepX ? j : 0]);
+                    const T    kept = xs[kKeepX ? j : 0]; // x_i; kChebInit: b_i, and x_i = x_1 is formed from it again
+                    const T    xi   = kKeepRhs ? cheb_first_iterate(post.f0, dv[kKeepX ? j : 0], kept) : kept;
+                    const T    res  = post_finish<T, MODE>(post, j >= JINT ? pp[j >= JINT ? j - JINT : 0] : T(0),
+                                                           kKeepRhs ? kept : o.av, o.ov, dv[kKeepX ? j : 0], last, val[k], xi);
                     if (j < JINT)
                       buf_st(r_out, o.off, res);
                     else

@@ -384,6 +384,28 @@ namespace mgx
                                           off, 0, 0);
   }
 
+  // A/B builds only (tools/build_variant_of.sh ... -DMGX_CHEB_INIT_REREAD=1), never the production library: the first
+  // Chebyshev iteration from a zero start keeps x_1 across the sweeps and loads the right-hand side a second time at
+  // write-out, as it did before it kept the gathered value.
+#ifndef MGX_CHEB_INIT_REREAD
+#define MGX_CHEB_INIT_REREAD 0
+#endif
+  // kChebInit gathers the right-hand side b to land x_1 = f0 D^-1 b, and needs both b and x_1 again where the brick
+  // completes a DoF.  The gather and the write-out map items to threads alike, so the thread keeps the b it gathered
+  // and forms x_1 from it a second time: 2 accesses per DoF (b in, result out) instead of 3.
+  __host__ __device__ constexpr bool keeps_rhs(int mode) { return mode == kChebInit && !MGX_CHEB_INIT_REREAD; }
+
+  // x_1 = f0 D^-1 b of a zero start: (f0 * d) * b, rounded as a product of its own.  The value landed in the brick
+  // array and the one formed again at write-out both come from here; the empty asm keeps the product out of any
+  // contraction with the arithmetic around either call, so they are the same bits.
+  template <typename T>
+  __device__ __forceinline__ T cheb_first_iterate(T f0, T d, T b)
+  {
+    T x = f0 * d * b;
+    asm("" : "+v"(x));
+    return x;
+  }
+
   template <typename T>
   struct PostRsrc
   {
@@ -424,7 +446,7 @@ namespace mgx
     if (__builtin_amdgcn_ballot_w64(need_partial) != 0)
       ld(R.partial, op, o.pv);
 #endif
-    if (MODE != kPlain)
+    if (MODE != kPlain && !keeps_rhs(MODE)) // (kChebInit: the thread kept the right-hand side it gathered)
       ld(R.a, ol, o.av);
     if (is_cheb_mode(MODE) && !DTAB)
       ld(R.b, ol, o.bv);
