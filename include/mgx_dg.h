@@ -292,6 +292,37 @@ int mgx_dg_transfer_restrict_and_add(mgx_dg_transfer_t transfer, void *coarse_ds
  * p1d[h (p+1)^2 + i (p+1) + j] = coefficient i, in the child's basis on [0,1], of phi_j((x + h) / 2) */
 int mgx_dg_transfer_matrix(mgx_dg_transfer_t transfer, double *p1d);
 
+/* ---- level transfer between two DG spaces of different degree on the same mesh (p-coarsening; no counterpart in the
+ * reference, whose plain DG multigrid coarsens the mesh only).  Same basis kind and the same cells in the same order on
+ * both levels: cell c is the run of (pc+1)^dim entries in the coarse vector and of (pf+1)^dim in the fine one. ---- */
+
+/* The 1D embedding of the space of degree coarse_degree into that of fine_degree, 1 <= coarse_degree < fine_degree <=
+ * MGX_MAX_DEGREE, both in the basis MGX_DG_*: e1d[i (pc+1) + j] = coefficient i, in the basis of degree pf, of the function
+ * j of the basis of degree pc on the same cell ((pf+1)(pc+1) doubles).  Host only, needs neither a context nor a device;
+ * computed in double from the 1D polynomials of the operator (interpolation in the Gauss points of the fine space: the
+ * spaces are nested, any unisolvent set of points gives the same matrix).  coarse_degree >= fine_degree or a null
+ * pointer: MGX_ERR_INVALID_ARGUMENT; a degree outside 1 .. MGX_MAX_DEGREE or an unknown basis: MGX_ERR_UNSUPPORTED. */
+int mgx_dg_degree_embedding(int fine_degree, int coarse_degree, int basis, double *e1d);
+
+typedef struct mgx_dg_degree_transfer_s *mgx_dg_degree_transfer_t;
+typedef struct
+{
+  int      fine_degree, coarse_degree; /* 1 <= coarse_degree < fine_degree <= MGX_MAX_DEGREE */
+  int      basis;                      /* MGX_DG_* */
+  int      number;                     /* MGX_F32 or MGX_F64: the type of the vectors */
+  uint32_t n_cells;                    /* of either level, >= 1 */
+  int      dim;                        /* 0 or 3: three dimensions, 2: two.  Any other value: MGX_ERR_INVALID_ARGUMENT. */
+} mgx_dg_degree_transfer_desc;
+/* uploads mgx_dg_degree_embedding in the number type; refuses what that function refuses, with its status */
+int mgx_dg_degree_transfer_create(mgx_context_t ctx, const mgx_dg_degree_transfer_desc *desc, mgx_dg_degree_transfer_t *transfer);
+int mgx_dg_degree_transfer_destroy(mgx_dg_degree_transfer_t transfer);
+/* fine[c] += (E (x) E (x) E) coarse[c]; dim == 2: (E (x) E), here and below.  The vectors must not alias. */
+int mgx_dg_degree_transfer_prolongate_and_add(mgx_dg_degree_transfer_t transfer, void *fine_dst, const void *coarse_src);
+/* coarse[c] += (E (x) E (x) E)^T fine[c].  One writer per entry in both operations: the same bits in every run. */
+int mgx_dg_degree_transfer_restrict_and_add(mgx_dg_degree_transfer_t transfer, void *coarse_dst, const void *fine_src);
+/* the 1D embedding the object was created with, (pf+1)(pc+1) doubles as mgx_dg_degree_embedding gives them */
+int mgx_dg_degree_transfer_matrix(mgx_dg_degree_transfer_t transfer, double *e1d);
+
 /* ---- MultigridSolverDGPlain<3,p,Number,double> (common/multigrid_solver_dg_plain.h:55-595): the DG-SIP operator on
  * every level of a globally refined mesh, Chebyshev / JacobiTransformed smoothers, DG-to-DG transfers, level 0 solved
  * by its Chebyshev iteration; one rank ---- */
@@ -312,6 +343,30 @@ typedef struct
  * times the cells of the one below.  Operators with Neumann faces are accepted (every level should mark the same sides);
  * a level or matrix_dg_dp without any Dirichlet face is refused with MGX_ERR_UNSUPPORTED: the problem is singular. */
 int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc *desc, mgx_dg_plain_solver_t *solver);
+/* The same solver on a level sequence in which every step is either a mesh refinement (same degree, 2^dim times the
+ * cells) or a degree raise (same cells, coarse degree < fine degree): h- and p-coarsening mixed at will.  The levels
+ * below the finest are rediscretisations, each with the penalty (p+1)^2 of its own degree -- not Galerkin products. */
+typedef struct
+{
+  int                      n_levels;
+  const mgx_dg_operator_t *matrix;       /* [n_levels], V-cycle number type, coarsest first */
+  mgx_dg_operator_t        matrix_dg_dp; /* fp64 twin of matrix[n_levels - 1] */
+  /* [n_levels - 1] each (an array without any entry may be NULL); of transfer[l - 1] and degree_transfer[l - 1]
+   * exactly one is non-NULL: the step from level l - 1 to level l is a mesh refinement or a degree raise */
+  const mgx_dg_transfer_t        *transfer;
+  const mgx_dg_degree_transfer_t *degree_transfer;
+  int                             degree_pre; /* as in mgx_dg_plain_solver_desc, whatever the kind of step */
+  const uint32_t *const          *cell_global_id; /* as in mgx_dg_plain_solver_desc */
+} mgx_dg_hp_solver_desc;
+/* Returns the handle type of mgx_dg_plain_solver_create: every entry point below works on it unchanged, and with
+ * mesh refinements only the solver is the one mgx_dg_plain_solver_create builds.  Smoothers as there (levels 0 < l < L:
+ * degree_pre; level L: max(1, degree_pre - 1); level 0: range 1e-5, Varga's rule).  Refused with
+ * MGX_ERR_INVALID_ARGUMENT and a message that names the level: a step with both or neither transfer; operators that
+ * differ in basis, number type, dimension or context, have ghost cells or no Dirichlet face; a mesh refinement with
+ * unequal degrees, other than 2^dim times the cells, or a transfer of another degree or n_coarse_cells; a degree raise
+ * with unequal cell counts, coarse degree >= fine degree, or a degree transfer whose degrees or n_cells are not those
+ * of its two operators; a matrix_dg_dp that is not the fp64 twin of the last level. */
+int mgx_dg_hp_solver_create(mgx_context_t ctx, const mgx_dg_hp_solver_desc *desc, mgx_dg_plain_solver_t *solver);
 int mgx_dg_plain_solver_destroy(mgx_dg_plain_solver_t solver);
 int mgx_dg_plain_solver_smoother_info(mgx_dg_plain_solver_t solver, int level, mgx_smoother_info *info);
 /* MultigridSolverDGPlain::vmult (:322-334): one V-cycle (:456-496); fp64 device vectors of the finest level */

@@ -1196,6 +1196,14 @@ def dg_box_children(coarse_cells, coarse_ordering="z", fine_ordering="z"):
     return ch
 
 
+def dg_degree_embedding(pf, pc, basis):
+    """E[i, j]: coefficient i, in the basis of degree pf, of the function j of the basis of degree pc < pf on the same
+    cell (mgx_dg_degree_embedding; host only)"""
+    E = np.empty((max(pf, 0) + 1, max(pc, 0) + 1))
+    check(_lib.load().mgx_dg_degree_embedding(pf, pc, basis, E.ctypes.data_as(_lib.f64p)))
+    return E
+
+
 def dg_partition(ijk, cells, procs, rank):
     """Ghost cells and exchange lists of a block decomposition, for the owned cells `ijk` ([n, 3] global
     positions, in the local cell order) of the rank whose block of the process grid they fill.
@@ -1585,6 +1593,38 @@ class DGLevelTransfer:
             self.h = None
 
 
+class DGDegreeTransfer:
+    """Transfer between two DG levels of degrees coarse_degree < fine_degree and the same basis on the same n_cells cells
+    in the same order (include/mgx_dg.h, mgx_dg_degree_transfer_*): p-coarsening.  dim 3 or 2."""
+
+    def __init__(self, ctx, fine_degree, coarse_degree, basis, n_cells, number=F32, dim=3):
+        self.ctx, self.lib, self.h = ctx, ctx.lib, None
+        self.fine_degree, self.coarse_degree, self.basis, self.number, self.dim = fine_degree, coarse_degree, basis, number, dim
+        d = _lib.DGDegreeTransferDesc(fine_degree, coarse_degree, basis, number, n_cells, dim)
+        h = C.c_void_p()
+        check(self.lib.mgx_dg_degree_transfer_create(ctx.h, C.byref(d), C.byref(h)))
+        self.h = h
+
+    def prolongate_and_add(self, fine, coarse):
+        check(self.lib.mgx_dg_degree_transfer_prolongate_and_add(self.h, fine.ptr if fine is not None else None,
+                                                                 coarse.ptr if coarse is not None else None))
+
+    def restrict_and_add(self, coarse, fine):
+        check(self.lib.mgx_dg_degree_transfer_restrict_and_add(self.h, coarse.ptr if coarse is not None else None,
+                                                               fine.ptr if fine is not None else None))
+
+    def matrix(self):
+        """E[i, j] as dg_degree_embedding gives it"""
+        E = np.empty((self.fine_degree + 1, self.coarse_degree + 1))
+        check(self.lib.mgx_dg_degree_transfer_matrix(self.h, E.ctypes.data_as(_lib.f64p)))
+        return E
+
+    def clear(self):
+        if getattr(self, "h", None):
+            self.lib.mgx_dg_degree_transfer_destroy(self.h)
+            self.h = None
+
+
 class DGPlainMultigridSolver:
     """multigrid::MultigridSolverDGPlain<3,p,Number,double> (common/multigrid_solver_dg_plain.h:55-595) on a box of
     coarse_cells refined n_levels - 1 times: the DG-SIP operator on every level (cells 2^l per coarse cell and
@@ -1593,41 +1633,69 @@ class DGPlainMultigridSolver:
     coarse_cells (and a 2 x 2 jacobian0) gives <2,p,Number,double>, the dimension poisson_dg_plain/program.cc:65 runs."""
 
     def __init__(self, ctx, degree, basis, coarse_cells, jacobian0, n_levels, degree_pre=3, vcycle_number=F32, ordering="z",
-                 origin=None, neumann_sides=()):
+                 origin=None, neumann_sides=(), hierarchy=None):
         """origin (default 0): the corner of the box, for the coordinates x = origin + J (pos + xi) that compute_rhs and
         compute_l2_error of the finest fp64 operator evaluate sine products in; neumann_sides: the sides of the box
-        (face numbers 2d+s) that are Neumann faces, on every level alike -- at least one side must stay Dirichlet"""
+        (face numbers 2d+s) that are Neumann faces, on every level alike -- at least one side must stay Dirichlet.
+        hierarchy (default None: every level has `degree`, level l the mesh refined l times, mgx_dg_plain_solver_create):
+        the levels from coarsest to finest as (degree, refinement) pairs, starting on the mesh coarse_cells (refinement
+        0); each step either refines the mesh once (same degree, refinement + 1) or raises the degree (same refinement);
+        the last entry must be (degree, n_levels - 1), and n_levels may be None.  Built by mgx_dg_hp_solver_create;
+        every level is a rediscretisation with its own degree and penalty."""
         self.ctx, self.lib = ctx, ctx.lib
-        self.degree, self.basis, self.n_levels, self.vnumber = degree, basis, n_levels, vcycle_number
         self.dim = dim = len(coarse_cells)
+        if hierarchy is None:
+            levels = [(int(degree), l) for l in range(n_levels)]
+        else:
+            levels = [(int(p), int(r)) for p, r in hierarchy]
+            if not levels or levels[0][1] != 0:
+                raise ValueError("hierarchy: the first level is on the mesh coarse_cells (refinement 0)")
+            for l in range(1, len(levels)):
+                (pc, rc), (pf, rf) = levels[l - 1], levels[l]
+                if not ((pf == pc and rf == rc + 1) or (pf > pc and rf == rc)):
+                    raise ValueError("hierarchy: the step from level %d %r to level %d %r neither refines the mesh once nor "
+                                     "raises the degree" % (l - 1, levels[l - 1], l, levels[l]))
+            if levels[-1][0] != degree or (n_levels is not None and levels[-1][1] != n_levels - 1):
+                raise ValueError("hierarchy: the last level %r must be (degree, n_levels - 1)" % (levels[-1],))
+        self.hierarchy = levels
+        self.degree, self.basis, self.n_levels, self.vnumber = degree, basis, len(levels), vcycle_number
         jac0 = np.asarray(jacobian0, dtype=float).reshape(dim, dim)
         self.cells, self.cell_ijk, self.cell_gid, self.matrix, self.transfer = [], [], [], [], []
         self.matrix_dg_dp = self.h = None
         try:
-            for l in range(n_levels):
-                cells = tuple(int(c) << l for c in coarse_cells)
+            for l, (p, r) in enumerate(levels):
+                cells = tuple(int(c) << r for c in coarse_cells)
                 nb, ijk = dg_box_neighbours(cells, ordering, neumann_sides)
                 self.cells.append(cells)
                 self.cell_ijk.append(ijk)
                 i64 = ijk.astype(np.int64)
                 lex = i64[:, 0] + cells[0] * (i64[:, 1] + (cells[1] * i64[:, 2] if dim == 3 else 0))
                 self.cell_gid.append(np.ascontiguousarray(lex, dtype=np.uint32))
-                self.matrix.append(DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, vcycle_number, dim=dim))
-                if l == n_levels - 1:
-                    self.matrix_dg_dp = DGLaplaceOperator(ctx, degree, basis, nb, jac0 / 2 ** l, F64, dim=dim)
+                self.matrix.append(DGLaplaceOperator(ctx, p, basis, nb, jac0 / 2 ** r, vcycle_number, dim=dim))
+                if l == len(levels) - 1:
+                    self.matrix_dg_dp = DGLaplaceOperator(ctx, p, basis, nb, jac0 / 2 ** r, F64, dim=dim)
                     self.matrix_dg_dp.set_cell_positions(np.zeros(dim) if origin is None else origin, ijk)
-                if l > 0:
-                    self.transfer.append(DGLevelTransfer(ctx, degree, basis, dg_box_children(self.cells[l - 1], ordering, ordering),
+                if l > 0 and levels[l - 1][1] < r:
+                    self.transfer.append(DGLevelTransfer(ctx, p, basis, dg_box_children(self.cells[l - 1], ordering, ordering),
                                                          vcycle_number))
-            d = _lib.DGPlainSolverDesc()
-            d.n_levels = n_levels
-            d.matrix = (_lib.vp * n_levels)(*[m.h for m in self.matrix])
+                elif l > 0:
+                    self.transfer.append(DGDegreeTransfer(ctx, p, levels[l - 1][0], basis, len(ijk), vcycle_number, dim))
+            n = len(levels)
+            d = _lib.DGPlainSolverDesc() if hierarchy is None else _lib.DGHPSolverDesc()
+            d.n_levels = n
+            d.matrix = (_lib.vp * n)(*[m.h for m in self.matrix])
             d.matrix_dg_dp = self.matrix_dg_dp.h
-            d.transfer = (_lib.vp * max(1, n_levels - 1))(*[t.h for t in self.transfer])
             d.degree_pre = degree_pre
-            d.cell_global_id = (_lib.u32p * n_levels)(*[g.ctypes.data_as(_lib.u32p) for g in self.cell_gid])
+            d.cell_global_id = (_lib.u32p * n)(*[g.ctypes.data_as(_lib.u32p) for g in self.cell_gid])
             h = C.c_void_p()
-            check(self.lib.mgx_dg_plain_solver_create(ctx.h, C.byref(d), C.byref(h)))
+            if hierarchy is None:
+                d.transfer = (_lib.vp * max(1, n - 1))(*[t.h for t in self.transfer])
+                check(self.lib.mgx_dg_plain_solver_create(ctx.h, C.byref(d), C.byref(h)))
+            else:
+                d.transfer = (_lib.vp * max(1, n - 1))(*[t.h if isinstance(t, DGLevelTransfer) else None for t in self.transfer])
+                d.degree_transfer = (_lib.vp * max(1, n - 1))(*[t.h if isinstance(t, DGDegreeTransfer) else None
+                                                                for t in self.transfer])
+                check(self.lib.mgx_dg_hp_solver_create(ctx.h, C.byref(d), C.byref(h)))
             self.h = h
         except Exception:
             self.close()

@@ -82,6 +82,16 @@ class DGPlainSolverDesc(C.Structure):
                 ("degree_pre", C.c_int), ("cell_global_id", C.POINTER(u32p))]
 
 
+class DGDegreeTransferDesc(C.Structure):
+    _fields_ = [("fine_degree", C.c_int), ("coarse_degree", C.c_int), ("basis", C.c_int), ("number", C.c_int),
+                ("n_cells", C.c_uint32), ("dim", C.c_int)]
+
+
+class DGHPSolverDesc(C.Structure):
+    _fields_ = [("n_levels", C.c_int), ("matrix", C.POINTER(vp)), ("matrix_dg_dp", vp), ("transfer", C.POINTER(vp)),
+                ("degree_transfer", C.POINTER(vp)), ("degree_pre", C.c_int), ("cell_global_id", C.POINTER(u32p))]
+
+
 class DGPcgSolverDesc(C.Structure):
     _fields_ = [("matrix", vp), ("form", C.c_int), ("max_iterations", C.c_uint), ("tolerance", C.c_double),
                 ("check_every", C.c_uint)]
@@ -295,7 +305,14 @@ SIGNATURES = {
     "mgx_dg_transfer_prolongate_and_add": (C.c_int, [vp, vp, vp]),
     "mgx_dg_transfer_restrict_and_add": (C.c_int, [vp, vp, vp]),
     "mgx_dg_transfer_matrix": (C.c_int, [vp, f64p]),
+    "mgx_dg_degree_embedding": (C.c_int, [C.c_int, C.c_int, C.c_int, f64p]),
+    "mgx_dg_degree_transfer_create": (C.c_int, [vp, C.POINTER(DGDegreeTransferDesc), C.POINTER(vp)]),
+    "mgx_dg_degree_transfer_destroy": (C.c_int, [vp]),
+    "mgx_dg_degree_transfer_prolongate_and_add": (C.c_int, [vp, vp, vp]),
+    "mgx_dg_degree_transfer_restrict_and_add": (C.c_int, [vp, vp, vp]),
+    "mgx_dg_degree_transfer_matrix": (C.c_int, [vp, f64p]),
     "mgx_dg_plain_solver_create": (C.c_int, [vp, C.POINTER(DGPlainSolverDesc), C.POINTER(vp)]),
+    "mgx_dg_hp_solver_create": (C.c_int, [vp, C.POINTER(DGHPSolverDesc), C.POINTER(vp)]),
     "mgx_dg_plain_solver_destroy": (C.c_int, [vp]),
     "mgx_dg_plain_solver_smoother_info": (C.c_int, [vp, C.c_int, C.POINTER(SmootherInfo)]),
     "mgx_dg_plain_solver_vmult": (C.c_int, [vp, vp, vp]),

@@ -1,7 +1,8 @@
 // mgx_dg_api.cpp -- host side of the DG objects of include/mgx_dg.h: the operator (set-up, ghost exchange, the
 // applications of the cell kernel), MultigridSolverDG on top of an FE_Q hierarchy, the DG-to-DG level transfer
-// object and MultigridSolverDGPlain.  No kernel lives here: the cell kernel and its launch are mgx_dg_kernels.hip
-// (DG section of mgx_internal.hpp), the level transfer kernels mgx_dg_transfer.hip, the kernels of the right-hand side
+// objects (between two meshes, between two degrees) and MultigridSolverDGPlain on h-only and mixed h/p level sequences.
+// No kernel lives here: the cell kernel and its launch are mgx_dg_kernels.hip (DG section of mgx_internal.hpp), the
+// level transfer kernels mgx_dg_transfer.hip and mgx_dg_ptransfer.hip, the kernels of the right-hand side
 // with boundary data and of the L2 error mgx_dg_rhs.hip, the fp64 numerics of the set-up mgx_dg_host.cpp.
 #include "mgx_device_memory.hpp"
 #include "mgx_dg_host.hpp"
@@ -97,13 +98,27 @@ struct mgx_dg_transfer_s
   std::vector<double> p1d_host;
 };
 
+// the transfer between two degrees on one mesh (mgx_dg_ptransfer.hip)
+struct mgx_dg_degree_transfer_s
+{
+  mgx_context_t       ctx = nullptr;
+  mgx::DeviceArena    mem{"mgx_dg_degree_transfer"};
+  int                 fine_degree = 0, coarse_degree = 0, basis = 0, number = MGX_F32;
+  int                 dim = 3;
+  uint32_t            n_cells = 0;
+  void               *e1d     = nullptr; // device [(pf+1)][(pc+1)], number type
+  std::vector<double> e1d_host;
+};
+
 // MultigridSolverDGPlain (common/multigrid_solver_dg_plain.h:55-595)
 struct mgx_dg_plain_solver_s
 {
   struct Level
   {
     mgx_dg_operator_t A = nullptr;
-    mgx_dg_transfer_t transfer = nullptr; // from the level below (null on level 0)
+    // from the level below (both null on level 0): a mesh refinement or a degree raise, exactly one of the two
+    mgx_dg_transfer_t        transfer        = nullptr;
+    mgx_dg_degree_transfer_t degree_transfer = nullptr;
     size_t            n = 0;
     mgx_smoother_info info{};
     void             *defect = nullptr, *t = nullptr, *update = nullptr, *old = nullptr; // V-cycle number type
@@ -1334,15 +1349,70 @@ namespace
     {
       PlainTimer timer(S, &L.times[1]);
       MGX_HIP(hipMemsetAsync(C.defect, 0, dg_nsz(S->number) * C.n, s)); // :482
-      MGX_TRY(mgx_dg_transfer_restrict_and_add(L.transfer, C.defect, L.t)); // :483
+      if (L.transfer)
+        MGX_TRY(mgx_dg_transfer_restrict_and_add(L.transfer, C.defect, L.t)); // :483
+      else
+        MGX_TRY(mgx_dg_degree_transfer_restrict_and_add(L.degree_transfer, C.defect, L.t));
     }
     MGX_TRY(plain_v_cycle(S, l - 1));
     {
       PlainTimer timer(S, &L.times[2]);
-      MGX_TRY(mgx_dg_transfer_prolongate_and_add(L.transfer, L.update, C.update)); // :489
+      if (L.transfer)
+        MGX_TRY(mgx_dg_transfer_prolongate_and_add(L.transfer, L.update, C.update)); // :489
+      else
+        MGX_TRY(mgx_dg_degree_transfer_prolongate_and_add(L.degree_transfer, L.update, C.update));
     }
     PlainTimer timer(S, &L.times[5]);
     return dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, true); // :493
+  }
+
+  // the solver object of a checked level sequence: level vectors and smooth[level].initialize.  Between levels l - 1 and
+  // l sits whichever of desc->transfer[l - 1] and desc->degree_transfer[l - 1] is set (either array may be null)
+  int plain_solver_build(mgx_context_t ctx, const mgx_dg_hp_solver_desc *desc, mgx_dg_plain_solver_t *out)
+  {
+    const int         L   = desc->n_levels - 1;
+    mgx_dg_operator_t top = desc->matrix[L];
+    std::unique_ptr<mgx_dg_plain_solver_s, int (*)(mgx_dg_plain_solver_t)> S(new mgx_dg_plain_solver_s, mgx_dg_plain_solver_destroy);
+    S->ctx    = ctx;
+    S->A_dp   = desc->matrix_dg_dp;
+    S->number = top->number;
+    S->level.resize(L + 1);
+    hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
+    for (int l = 0; l <= L; ++l)
+      {
+        mgx_dg_plain_solver_s::Level &lv = S->level[l];
+        lv.A               = desc->matrix[l];
+        lv.transfer        = l > 0 && desc->transfer ? desc->transfer[l - 1] : nullptr;
+        lv.degree_transfer = l > 0 && desc->degree_transfer ? desc->degree_transfer[l - 1] : nullptr;
+        lv.n               = (size_t)mgx_dg_operator_n_dofs(lv.A);
+        for (void **v : {&lv.defect, &lv.t, &lv.update, &lv.old})
+          {
+            MGX_TRY(S->mem.zeros(v, dg_nsz(S->number) * lv.n, s));
+          }
+      }
+    for (double **v : {&S->r, &S->z, &S->d, &S->h})
+      {
+        MGX_TRY(S->mem.zeros(v, S->level[L].n, s));
+      }
+    MGX_TRY(S->mem.alloc(&S->partials, 4 * (size_t)mgx::kDotBlocks));
+    MGX_TRY(S->mem.alloc(&S->sums, 4));
+    // smooth[level].initialize (:192-213)
+    for (int l = 0; l <= L; ++l)
+      {
+        mgx_dg_plain_solver_s::Level &lv  = S->level[l];
+        const uint32_t               *ids = desc->cell_global_id ? desc->cell_global_id[l] : nullptr;
+        if (l > 0)
+          MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect, 15, 20.,
+                                         l < L ? desc->degree_pre : std::max(1, desc->degree_pre - 1), lv.info));
+        else
+          MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect,
+                                         (int)std::min<size_t>(lv.n, 0x7FFFFFFF), 1e-5, -1, lv.info));
+        for (void *v : {lv.defect, lv.t, lv.update, lv.old})
+          MGX_HIP(hipMemsetAsync(v, 0, dg_nsz(S->number) * lv.n, s));
+      }
+    MGX_HIP(hipStreamSynchronize(s));
+    *out = S.release();
+    return MGX_OK;
   }
 } // namespace
 
@@ -1433,6 +1503,155 @@ int mgx_dg_transfer_matrix(mgx_dg_transfer_t T, double *p1d)
   return MGX_OK;
 }
 
+int mgx_dg_degree_transfer_create(mgx_context_t ctx, const mgx_dg_degree_transfer_desc *desc, mgx_dg_degree_transfer_t *out)
+{
+  MGX_REQUIRE(ctx && desc && out, "mgx_dg_degree_transfer_create: null argument");
+  if (desc->number != MGX_F32 && desc->number != MGX_F64)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_degree_transfer_create: number must be MGX_F32 or MGX_F64");
+  if (desc->n_cells == 0 || desc->n_cells >= (1u << 31))
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_degree_transfer_create: n_cells must be in 1 .. 2^31 - 1");
+  const int dim = dg_desc_dim(desc->dim);
+  if (dim < 0)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_degree_transfer_create: dim must be 0 or 3 (three dimensions) or 2");
+  // degrees and basis: checked by the host function, which names what it refuses
+  const int           nf = desc->fine_degree + 1, nc = desc->coarse_degree + 1;
+  std::vector<double> e1d((size_t)(MGX_MAX_DEGREE + 1) * (MGX_MAX_DEGREE + 1));
+  MGX_TRY(mgx_dg_degree_embedding(desc->fine_degree, desc->coarse_degree, desc->basis, e1d.data()));
+  e1d.resize((size_t)nf * nc);
+  std::unique_ptr<mgx_dg_degree_transfer_s, int (*)(mgx_dg_degree_transfer_t)> T(new mgx_dg_degree_transfer_s,
+                                                                                 mgx_dg_degree_transfer_destroy);
+  T->ctx           = ctx;
+  T->dim           = dim;
+  T->fine_degree   = desc->fine_degree;
+  T->coarse_degree = desc->coarse_degree;
+  T->basis         = desc->basis;
+  T->number        = desc->number;
+  T->n_cells       = desc->n_cells;
+  T->e1d_host      = e1d;
+  MGX_TRY(T->mem.upload_as(T->number, &T->e1d, e1d.data(), e1d.size()));
+  *out = T.release();
+  return MGX_OK;
+}
+
+int mgx_dg_degree_transfer_destroy(mgx_dg_degree_transfer_t T)
+{
+  if (!T)
+    return MGX_OK;
+  if (T->ctx)
+    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(T->ctx));
+  delete T;
+  return MGX_OK;
+}
+
+int mgx_dg_degree_transfer_prolongate_and_add(mgx_dg_degree_transfer_t T, void *fine_dst, const void *coarse_src)
+{
+  MGX_REQUIRE(T && fine_dst && coarse_src && fine_dst != coarse_src, "mgx_dg_degree_transfer_prolongate_and_add: null or aliased vectors");
+  if (!mgx::launch_dg_ptransfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->fine_degree, T->coarse_degree, true, fine_dst,
+                                coarse_src, T->n_cells, T->e1d, T->dim))
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_degree_transfer_prolongate_and_add: no kernel for this pair of degrees");
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_degree_transfer_restrict_and_add(mgx_dg_degree_transfer_t T, void *coarse_dst, const void *fine_src)
+{
+  MGX_REQUIRE(T && coarse_dst && fine_src && coarse_dst != fine_src, "mgx_dg_degree_transfer_restrict_and_add: null or aliased vectors");
+  if (!mgx::launch_dg_ptransfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->fine_degree, T->coarse_degree, false, coarse_dst,
+                                fine_src, T->n_cells, T->e1d, T->dim))
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_degree_transfer_restrict_and_add: no kernel for this pair of degrees");
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_dg_degree_transfer_matrix(mgx_dg_degree_transfer_t T, double *e1d)
+{
+  MGX_REQUIRE(T && e1d, "mgx_dg_degree_transfer_matrix: null argument");
+  std::copy(T->e1d_host.begin(), T->e1d_host.end(), e1d);
+  return MGX_OK;
+}
+
+int mgx_dg_hp_solver_create(mgx_context_t ctx, const mgx_dg_hp_solver_desc *desc, mgx_dg_plain_solver_t *out)
+{
+  const std::string name = "mgx_dg_hp_solver_create: ";
+  if (!ctx || !desc || !out || !desc->matrix || !desc->matrix_dg_dp)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "null argument");
+  if (desc->n_levels < 1 || desc->n_levels > 32)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "n_levels must be in 1..32");
+  if (desc->degree_pre < 1)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "degree_pre must be at least 1");
+  const int         L   = desc->n_levels - 1;
+  mgx_dg_operator_t top = desc->matrix[L], Ad = desc->matrix_dg_dp;
+  if (!top)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "matrix[" + std::to_string(L) + "] is null");
+  for (int l = 0; l <= L; ++l)
+    {
+      mgx_dg_operator_t A     = desc->matrix[l];
+      const std::string level = "level " + std::to_string(l) + ": matrix[" + std::to_string(l) + "]";
+      if (!A)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " is null");
+      if (A->ctx != ctx)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " belongs to another context");
+      if (A->n_ghost > 0)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " has ghost cells; the plain DG multigrid runs on one rank");
+      if (A->basis != top->basis || A->number != top->number)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " differs from the finest level in basis or number type");
+      if (A->dim != top->dim)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " has dimension " + std::to_string(A->dim) + ", the finest level " +
+                                                   std::to_string(top->dim));
+      if (!A->has_dirichlet)
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " has no Dirichlet face: the problem is singular (pure Neumann "
+                                                                "problems are not solved)");
+      if (l == 0)
+        continue;
+      mgx_dg_operator_t        C    = desc->matrix[l - 1];
+      mgx_dg_transfer_t        H    = desc->transfer ? desc->transfer[l - 1] : nullptr;
+      mgx_dg_degree_transfer_t P    = desc->degree_transfer ? desc->degree_transfer[l - 1] : nullptr;
+      const std::string        step = "the step from level " + std::to_string(l - 1) + " to level " + std::to_string(l);
+      if ((H != nullptr) == (P != nullptr))
+        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " needs exactly one of transfer[" + std::to_string(l - 1) +
+                                                   "] (a mesh refinement) and degree_transfer[" + std::to_string(l - 1) +
+                                                   "] (a degree raise), it has " + (H ? "both" : "neither"));
+      if (H)
+        {
+          if (H->basis != top->basis || H->number != top->number || H->ctx != ctx || H->dim != top->dim)
+            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + ": the transfer differs from the operators in basis, number type, "
+                                                                   "dimension or context");
+          if (C->degree != A->degree || H->degree != A->degree)
+            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " is a mesh refinement: the levels have degrees " +
+                                                       std::to_string(C->degree) + " and " + std::to_string(A->degree) +
+                                                       ", the transfer " + std::to_string(H->degree) + " (all equal required)");
+          if (H->n_coarse != C->n_cells || ((uint64_t)C->n_cells << top->dim) != A->n_cells)
+            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " is a mesh refinement: level " + std::to_string(l) + " has " +
+                                                       std::to_string(A->n_cells) + " cells, level " + std::to_string(l - 1) + " " +
+                                                       std::to_string(C->n_cells) + " and the transfer " + std::to_string(H->n_coarse) +
+                                                       " coarse cells (" + (top->dim == 2 ? "4" : "8") + " x coarse = fine required)");
+        }
+      else
+        {
+          if (P->basis != top->basis || P->number != top->number || P->ctx != ctx || P->dim != top->dim)
+            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + ": the degree transfer differs from the operators in basis, number "
+                                                                   "type, dimension or context");
+          if (C->n_cells != A->n_cells || P->n_cells != A->n_cells)
+            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " is a degree raise: the levels have " + std::to_string(C->n_cells) +
+                                                       " and " + std::to_string(A->n_cells) + " cells, the degree transfer " +
+                                                       std::to_string(P->n_cells) + " (all equal required)");
+          if (C->degree >= A->degree)
+            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " is a degree raise: the coarse degree " + std::to_string(C->degree) +
+                                                       " must be below the fine degree " + std::to_string(A->degree));
+          if (P->coarse_degree != C->degree || P->fine_degree != A->degree)
+            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + ": the degree transfer is between degrees " +
+                                                       std::to_string(P->coarse_degree) + " and " + std::to_string(P->fine_degree) +
+                                                       ", its operators have " + std::to_string(C->degree) + " and " +
+                                                       std::to_string(A->degree));
+        }
+    }
+  if (Ad->number != MGX_F64 || Ad->n_cells != top->n_cells || Ad->degree != top->degree || Ad->basis != top->basis || Ad->n_ghost > 0 ||
+      Ad->ctx != ctx || Ad->dim != top->dim || !Ad->has_dirichlet)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "matrix_dg_dp must be the fp64 twin of the operator of level " + std::to_string(L) +
+                                               ", the finest");
+  return plain_solver_build(ctx, desc, out);
+}
+
 int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc *desc, mgx_dg_plain_solver_t *out)
 {
   if (!ctx || !desc || !out || !desc->matrix || !desc->matrix_dg_dp || (desc->n_levels > 1 && !desc->transfer))
@@ -1488,46 +1707,8 @@ int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc
     return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_plain_solver_create: matrix_dg_dp has no Dirichlet face: the problem is singular "
                                         "(pure Neumann problems are not solved)");
 
-  std::unique_ptr<mgx_dg_plain_solver_s, int (*)(mgx_dg_plain_solver_t)> S(new mgx_dg_plain_solver_s, mgx_dg_plain_solver_destroy);
-  S->ctx    = ctx;
-  S->A_dp   = Ad;
-  S->number = top->number;
-  S->level.resize(L + 1);
-  hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
-  for (int l = 0; l <= L; ++l)
-    {
-      mgx_dg_plain_solver_s::Level &lv = S->level[l];
-      lv.A        = desc->matrix[l];
-      lv.transfer = l > 0 ? desc->transfer[l - 1] : nullptr;
-      lv.n        = (size_t)mgx_dg_operator_n_dofs(lv.A);
-      for (void **v : {&lv.defect, &lv.t, &lv.update, &lv.old})
-        {
-          MGX_TRY(S->mem.zeros(v, dg_nsz(S->number) * lv.n, s));
-        }
-    }
-  for (double **v : {&S->r, &S->z, &S->d, &S->h})
-    {
-      MGX_TRY(S->mem.zeros(v, S->level[L].n, s));
-    }
-  MGX_TRY(S->mem.alloc(&S->partials, 4 * (size_t)mgx::kDotBlocks));
-  MGX_TRY(S->mem.alloc(&S->sums, 4));
-  // smooth[level].initialize (:192-213)
-  for (int l = 0; l <= L; ++l)
-    {
-      mgx_dg_plain_solver_s::Level &lv  = S->level[l];
-      const uint32_t               *ids = desc->cell_global_id ? desc->cell_global_id[l] : nullptr;
-      if (l > 0)
-        MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect, 15, 20.,
-                                       l < L ? desc->degree_pre : std::max(1, desc->degree_pre - 1), lv.info));
-      else
-        MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect,
-                                       (int)std::min<size_t>(lv.n, 0x7FFFFFFF), 1e-5, -1, lv.info));
-      for (void *v : {lv.defect, lv.t, lv.update, lv.old})
-        MGX_HIP(hipMemsetAsync(v, 0, dg_nsz(S->number) * lv.n, s));
-    }
-  MGX_HIP(hipStreamSynchronize(s));
-  *out = S.release();
-  return MGX_OK;
+  const mgx_dg_hp_solver_desc levels{desc->n_levels, desc->matrix, Ad, desc->transfer, nullptr, desc->degree_pre, desc->cell_global_id};
+  return plain_solver_build(ctx, &levels, out);
 }
 
 int mgx_dg_plain_solver_destroy(mgx_dg_plain_solver_t S)

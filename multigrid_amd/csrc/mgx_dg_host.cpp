@@ -223,6 +223,21 @@ namespace
       }
     return true;
   }
+
+  // the p + 1 functions of the element basis MGX_DG_* on [0,1]; xq: the (p+1)-point Gauss rule (the nodes of
+  // MGX_DG_GAUSS)
+  std::vector<Poly1> element_basis(int p, int basis, const std::vector<double> &xq)
+  {
+    if (basis == MGX_DG_HERMITE)
+      return hermite_like(p);
+    if (basis == MGX_DG_GAUSS)
+      return lagrange(xq);
+    std::vector<double> nodes{0.0};
+    for (double x : jacobi_roots01(p - 1, 1.0))
+      nodes.push_back(x);
+    nodes.push_back(1.0);
+    return lagrange(nodes);
+  }
 } // namespace
 
 namespace mgx::dg
@@ -287,19 +302,7 @@ namespace mgx::dg
     const int n = p + 1;
     h.n         = n;
     gauss01(n, h.xq, h.wq);
-    std::vector<Poly1> fe;
-    if (basis == MGX_DG_HERMITE)
-      fe = hermite_like(p);
-    else if (basis == MGX_DG_GAUSS)
-      fe = lagrange(h.xq);
-    else
-      {
-        std::vector<double> nodes{0.0};
-        for (double x : jacobi_roots01(n - 2, 1.0))
-          nodes.push_back(x);
-        nodes.push_back(1.0);
-        fe = lagrange(nodes);
-      }
+    const std::vector<Poly1> fe  = element_basis(p, basis, h.xq);
     const std::vector<Poly1> col = lagrange(h.xq);
     h.S.assign(n * n, 0);
     h.SD.assign(n * n, 0);
@@ -635,6 +638,43 @@ namespace mgx::dg
 } // namespace mgx::dg
 
 extern "C" {
+
+int mgx_dg_degree_embedding(int fine_degree, int coarse_degree, int basis, double *e1d)
+{
+  if (!e1d)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_degree_embedding: null argument");
+  if (basis < MGX_DG_HERMITE || basis > MGX_DG_GAUSS)
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_dg_degree_embedding: basis must be MGX_DG_HERMITE, _GAUSS_LOBATTO or _GAUSS");
+  if (fine_degree < 1 || fine_degree > MGX_MAX_DEGREE || coarse_degree < 1 || coarse_degree > MGX_MAX_DEGREE)
+    return mgx::report_error(MGX_ERR_UNSUPPORTED,
+                             ("mgx_dg_degree_embedding: degrees must be in 1.." + std::to_string(MGX_MAX_DEGREE)).c_str());
+  if (coarse_degree >= fine_degree)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, ("mgx_dg_degree_embedding: coarse degree " + std::to_string(coarse_degree) +
+                                                        " must be below the fine degree " + std::to_string(fine_degree))
+                                                         .c_str());
+  // sum_i E[i][j] phi^f_i(x_q) = phi^c_j(x_q) in the Gauss points x_q of the fine space, i.e. E = S_f^-1 V (the spaces
+  // are nested: any unisolvent set of points gives the same matrix)
+  const int           nf = fine_degree + 1, nc = coarse_degree + 1;
+  std::vector<double> xf, wf, xc, wc;
+  gauss01(nf, xf, wf);
+  gauss01(nc, xc, wc);
+  const std::vector<Poly1> fine = element_basis(fine_degree, basis, xf), coarse = element_basis(coarse_degree, basis, xc);
+  std::vector<double>      S((size_t)nf * nf), Sinv;
+  for (int q = 0; q < nf; ++q)
+    for (int i = 0; i < nf; ++i)
+      S[q * nf + i] = fine[i].val(xf[q]);
+  if (!invert(nf, S, Sinv))
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_dg_degree_embedding: element basis is not unisolvent in the Gauss points");
+  for (int i = 0; i < nf; ++i)
+    for (int j = 0; j < nc; ++j)
+      {
+        double v = 0;
+        for (int q = 0; q < nf; ++q)
+          v += Sinv[i * nf + q] * coarse[j].val(xf[q]);
+        e1d[i * nc + j] = v;
+      }
+  return MGX_OK;
+}
 
 int mgx_dg_cheby_mesh(int n_cell_steps, int cells[3], double jacobian[9])
 {

@@ -582,6 +582,11 @@ namespace mgx
   // and its four children, children [n_coarse][4], identity: children[c][k] == 4 c + k
   void launch_dg_transfer(hipStream_t s, int number, int p, bool prolong, void *dst, const void *src, const uint32_t *children,
                           uint32_t n_coarse, const void *p1d, bool identity, int dim);
+  // DG <-> DG transfer between two degrees pc < pf on one mesh (mgx_dg_ptransfer.hip): prolong: fine += (E (x) E (x) E)
+  // coarse, else coarse += (E (x) E (x) E)^T fine, cell by cell; e1d [(pf+1)][(pc+1)] in the number type; dim == 2:
+  // E (x) E.  false: no kernel for this pair of degrees
+  bool launch_dg_ptransfer(hipStream_t s, int number, int pf, int pc, bool prolong, void *dst, const void *src, uint32_t n_cells,
+                           const void *e1d, int dim);
   // ---- DG cell kernel (mgx_dg_kernels.hip): what it offers the host code of mgx_dg_api.cpp ----
   namespace dg
   {

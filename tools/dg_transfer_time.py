@@ -3,6 +3,12 @@ warm, against the DG <-> FE_Q transfers of MultigridSolverDG (mgx_dg_prolongate_
 on the same fine cells in the same process, and as a fraction of a streaming ceiling.
 
     python tools/dg_transfer_time.py [degree=4] [n_refine=6] [--number f32|f64] [--repeat 20] [--ceiling 4.9e12] [--dim 2]
+                                     [--degrees PF PC]
+
+--degrees PF PC: the transfer between the degrees PC < PF on one mesh (mgx_dg_degree_transfer_*) next to the h transfer
+of the fine degree PF, in the same process on the same 2^(dim n_refine) fine cells (the positional degree is not read):
+time, bytes per second and time per fine DoF.  Accesses per fine DoF: prolongation 2 + (nc / nf)^dim, restriction
+1 + 2 (nc / nf)^dim, with nf = PF + 1, nc = PC + 1.
 
 --dim 2: the 2D transfers alone, on 4^n_refine fine cells in forest order (there is no FE_Q partner in 2D): 2 1/4
 accesses per fine DoF for the prolongation, 1 1/2 for the restriction.
@@ -39,6 +45,33 @@ def timed(ctx, fn, repeat):
     return min(out), float(np.median(out))
 
 
+def degree_transfer_rows(a, ctx, number, es):
+    """--degrees: the degree transfer and the h transfer of the fine degree on the same fine cells"""
+    (pf, pc), dim = a.degrees, a.dim
+    n_cells = (1 << dim) ** a.n_refine
+    nf, nc = n_cells * (pf + 1) ** dim, n_cells * (pc + 1) ** dim
+    nh = nf >> dim                                            # the h transfer's coarse vector
+    P = mg.DGDegreeTransfer(ctx, pf, pc, mg.DG_HERMITE, n_cells, number, dim)
+    H = mg.DGLevelTransfer(ctx, pf, mg.DG_HERMITE, np.arange(n_cells, dtype=np.uint32).reshape(-1, 1 << dim), number)
+    rng = np.random.default_rng(0)
+    fine, coarse_p, coarse_h = (ctx.vector(n, number, rng.standard_normal(n)) for n in (nf, nc, nh))
+    print("FE_DGQHermite(%d) <-> (%d) in %dD, %d cells, %d fine DoFs, %s" % (pf, pc, dim, n_cells, nf, a.number))
+    rows = [("p %d->%d prolongate_and_add" % (pc, pf), lambda: P.prolongate_and_add(fine, coarse_p), es * (2 * nf + nc)),
+            ("h p=%d prolongate_and_add" % pf, lambda: H.prolongate_and_add(fine, coarse_h), es * (2 * nf + nh)),
+            ("p %d->%d restrict_and_add" % (pf, pc), lambda: P.restrict_and_add(coarse_p, fine), es * (nf + 2 * nc)),
+            ("h p=%d restrict_and_add" % pf, lambda: H.restrict_and_add(coarse_h, fine), es * (nf + 2 * nh))]
+    best = []
+    for name, fn, nbytes in rows:
+        b, med = timed(ctx, fn, a.repeat)
+        best.append(b)
+        print("%-28s best %9.2f us  median %9.2f us  %8.1f GB/s  %5.1f %% of the %.1f TB/s copy ceiling  %.3f ps per fine DoF"
+              % (name, b * 1e6, med * 1e6, nbytes / b * 1e-9, 100 * nbytes / b / a.ceiling, a.ceiling * 1e-12, b / nf * 1e12))
+    print("time per fine DoF, degree transfer / h transfer: prolongation %.3f   restriction %.3f" % (best[0] / best[1], best[2] / best[3]))
+    P.clear()
+    H.clear()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("degree", nargs="?", type=int, default=4)
@@ -47,9 +80,12 @@ def main():
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--ceiling", type=float, default=4.9e12)
     ap.add_argument("--dim", type=int, choices=[2, 3], default=3)
+    ap.add_argument("--degrees", type=int, nargs=2, metavar=("PF", "PC"), help="time the degree transfer PC <-> PF too")
     a = ap.parse_args()
     number, es = (mg.F32, 4) if a.number == "f32" else (mg.F64, 8)
     ctx = mg.Context(0)
+    if a.degrees:
+        return degree_transfer_rows(a, ctx, number, es)
     if a.dim == 2:
         p, n2 = a.degree, (a.degree + 1) ** 2
         n_fine_cells = 4 ** a.n_refine

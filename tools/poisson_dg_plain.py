@@ -6,12 +6,18 @@ The same problem, printed lines and table row as tools/poisson_dg.py, whose solv
 
     python tools/poisson_dg_plain.py [degree=3] [n_refine=5] [n_pre_smooth=3] [tolerance=1e-9] [--vcycle f32|f64]
                                      [--basis 0|1|2] [--solution reference|vanishing] [--levels] [--dim 2|3]
-                                     [--boundary homogeneous|data] [--neumann 0,3]
+                                     [--boundary homogeneous|data] [--neumann 0,3] [--hierarchy h|hp|ph] [--coarse N]
 
 --dim 2: the dimension the reference's driver is compiled for (poisson_dg_plain/program.cc:65): the square [-0.9, 1]^2,
 rhs dim (3 pi)^2 prod sin(3 pi x_d) (program.cc:140), the same printed lines and table row.
 
-One line per level gives the smoother's degree, lambda_max and the CG iterations of its eigenvalue estimate.
+--hierarchy (default h, the reference's: the mesh alone is coarsened, every level has the full degree): hp refines the
+mesh at full degree and bisects the degree (p -> max(1, p // 2) down to 1) on the coarsest mesh; ph bisects the degree
+on the finest mesh and refines the mesh at degree 1.  Every level is a rediscretisation with the penalty of its own
+degree (mgx_dg_hp_solver_create).  --coarse N (default 1): N cells per direction on the coarsest mesh, which for N = 3
+cannot be halved any further -- the case degree coarsening is for.
+
+One line per level gives the degree, the cells and unknowns, the smoother's degree, lambda_max and the CG iterations of its eigenvalue estimate.
 --levels: one more solve with the solver's per-level timers on, and the table of the reference's print_wall_times
 (multigrid_solver_dg_plain.h:264-287).  The timers synchronise the stream around every part: for diagnosis, the
 solve they time is slower than the solves reported above it.
@@ -55,6 +61,9 @@ def main():
     ap.add_argument("--dim", type=int, choices=[2, 3], default=3)
     ap.add_argument("--boundary", choices=["homogeneous", "data"], default="homogeneous",
                     help="data: boundary values of the solution in the right-hand side; rhs and error on the device")
+    ap.add_argument("--hierarchy", choices=["h", "hp", "ph"], default="h",
+                    help="hp: degree bisected on the coarsest mesh; ph: on the finest mesh, the mesh refined at degree 1")
+    ap.add_argument("--coarse", type=int, default=1, help="cells per direction of the coarsest mesh")
     ap.add_argument("--neumann", default="", help="sides 2d+s that are Neumann faces, e.g. 0,3 (needs --boundary data)")
     a = ap.parse_args()
     a.neumann = tuple(sorted(set(int(f) for f in a.neumann.split(",") if f.strip() != "")))
@@ -65,24 +74,31 @@ def main():
     vnum = mg.F32 if a.vcycle == "f32" else mg.F64
     t0 = time.time()
     ctx = mg.Context(0)
-    n_levels = a.n_refine + 1
     dim = a.dim
-    solver = mg.DGPlainMultigridSolver(ctx, a.degree, a.basis, (1,) * dim, np.eye(dim) * 1.9, n_levels, a.n_pre_smooth, vnum,
-                                       origin=(-0.9,) * dim, neumann_sides=a.neumann)
+    degrees = [a.degree]
+    while degrees[0] > 1:
+        degrees.insert(0, max(1, degrees[0] // 2))
+    hierarchy = {"h": None,
+                 "hp": [(p, 0) for p in degrees] + [(a.degree, r) for r in range(1, a.n_refine + 1)],
+                 "ph": [(1, r) for r in range(a.n_refine + 1)] + [(p, a.n_refine) for p in degrees[1:]]}[a.hierarchy]
+    solver = mg.DGPlainMultigridSolver(ctx, a.degree, a.basis, (a.coarse,) * dim, np.eye(dim) * 1.9 / a.coarse, a.n_refine + 1,
+                                       a.n_pre_smooth, vnum, origin=(-0.9,) * dim, neumann_sides=a.neumann, hierarchy=hierarchy)
+    n_levels = solver.n_levels
     n = solver.m()
     nc = n // (a.degree + 1) ** dim
-    print("Number of degrees of freedom: %d (%d cells, FE_DGQHermite(%d) on every one of %d levels, V-cycle in %s)"
-          % (n, nc, a.degree, n_levels, a.vcycle))
+    print("Number of degrees of freedom: %d (%d cells, FE_DGQHermite(%d) on %s %d levels, V-cycle in %s)"
+          % (n, nc, a.degree, "every one of" if hierarchy is None else "the finest of", n_levels, a.vcycle))
     if a.neumann:
         print("Neumann sides (2d+s): %s, exact flux in the right-hand side" % ",".join(map(str, a.neumann)))
     for l in range(n_levels):
         i = solver.smoother_info(l)
-        print("level %2d  cells %9d  smoother degree %3d  lambda_max %.6f  cg_its %d"
-              % (l, int(np.prod(solver.cells[l])), i["degree"], i["lambda_max"], i["cg_its"]))
+        print("level %2d  degree %d  cells %9d  dofs %10d  smoother degree %3d  lambda_max %.6f  cg_its %d"
+              % (l, solver.hierarchy[l][0], int(np.prod(solver.cells[l])), solver.matrix[l].m(), i["degree"], i["lambda_max"],
+                 i["cg_its"]))
     if a.boundary == "data":
         return with_boundary_data(a, ctx, solver, t0)
     S, xq, wq = solver.matrix_dg_dp.basis_1d()
-    h = 1.9 / 2 ** a.n_refine
+    h = 1.9 / a.coarse / 2 ** a.n_refine
     S3, w3 = S, wq                                           # tensor products over the dim directions, x fastest
     for _ in range(dim - 1):
         S3, w3 = np.kron(S, S3), np.kron(wq, w3)
@@ -145,7 +161,7 @@ def with_boundary_data(a, ctx, solver, t0):
 
 
 def report(a, ctx, solver, b, sol, l2, time_cg, its, red):
-    n, n_levels = solver.m(), a.n_refine + 1
+    n, n_levels = solver.m(), solver.n_levels
     nc = n // (a.degree + 1) ** a.dim
     if a.levels:
         solver.enable_timings(True)
