@@ -1,8 +1,8 @@
 // mgx_dg_api.cpp -- host side of the DG objects of include/mgx_dg.h: the operator (set-up, ghost exchange, the
 // applications of the cell kernel), MultigridSolverDG on top of an FE_Q hierarchy, the DG-to-DG level transfer
-// objects (between two meshes, between two degrees) and MultigridSolverDGPlain on h-only and mixed h/p level sequences.
-// No kernel lives here: the cell kernel and its launch are mgx_dg_kernels.hip (DG section of mgx_internal.hpp), the
-// level transfer kernels mgx_dg_transfer.hip and mgx_dg_ptransfer.hip, the kernels of the right-hand side
+// objects (between two meshes, between two degrees: one object behind two handles) and MultigridSolverDGPlain on
+// h-only and mixed h/p level sequences.  No kernel lives here: the cell kernel and its launch are mgx_dg_kernels.hip
+// (DG section of mgx_internal.hpp), the level transfer kernel mgx_dg_transfer.hip, the kernels of the right-hand side
 // with boundary data and of the L2 error mgx_dg_rhs.hip, the fp64 numerics of the set-up mgx_dg_host.cpp.
 #include "mgx_device_memory.hpp"
 #include "mgx_dg_host.hpp"
@@ -84,30 +84,38 @@ struct mgx_dg_solver_s
   double           *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr; // PCG, fp64
 };
 
-// MGTransferMatrixFree between two DG levels (mgx_dg_transfer.hip)
-struct mgx_dg_transfer_s
+// one step of a DG level hierarchy (mgx_dg_transfer.hip).  A mesh step (MGTransferMatrixFree between two DG levels):
+// coarse_degree == fine_degree, a group is a coarse cell with its 2^dim children.  A degree step on one mesh:
+// coarse_degree < fine_degree, a group is a cell, no children
+struct DGLevelStep
 {
+  explicit DGLevelStep(const char *owner)
+    : mem{owner}
+  {}
   mgx_context_t       ctx = nullptr;
-  mgx::DeviceArena    mem{"mgx_dg_transfer"};
-  int                 degree = 0, basis = 0, number = MGX_F32;
-  int                 dim = 3;
-  uint32_t            n_coarse = 0;
-  uint32_t           *children = nullptr; // device [n_coarse][2^dim]
-  bool                identity = false;   // children[c][k] == 2^dim c + k (checked at creation): the table is not read
-  void               *p1d      = nullptr; // device [2][(p+1)^2], number type
-  std::vector<double> p1d_host;
-};
-
-// the transfer between two degrees on one mesh (mgx_dg_ptransfer.hip)
-struct mgx_dg_degree_transfer_s
-{
-  mgx_context_t       ctx = nullptr;
-  mgx::DeviceArena    mem{"mgx_dg_degree_transfer"};
+  mgx::DeviceArena    mem;
   int                 fine_degree = 0, coarse_degree = 0, basis = 0, number = MGX_F32;
   int                 dim = 3;
-  uint32_t            n_cells = 0;
-  void               *e1d     = nullptr; // device [(pf+1)][(pc+1)], number type
-  std::vector<double> e1d_host;
+  uint32_t            n_groups = 0;
+  uint32_t           *children = nullptr; // mesh step: device [n_groups][2^dim]
+  bool                identity = false;   // children[c][k] == 2^dim c + k (checked at creation): the table is not read
+  void               *m1d      = nullptr; // device, number type: [2][(p+1)^2], or [(pf+1)][(pc+1)]
+  std::vector<double> m1d_host;
+};
+
+// the two public handles of a step
+struct mgx_dg_transfer_s : DGLevelStep
+{
+  mgx_dg_transfer_s()
+    : DGLevelStep("mgx_dg_transfer")
+  {}
+};
+
+struct mgx_dg_degree_transfer_s : DGLevelStep
+{
+  mgx_dg_degree_transfer_s()
+    : DGLevelStep("mgx_dg_degree_transfer")
+  {}
 };
 
 // MultigridSolverDGPlain (common/multigrid_solver_dg_plain.h:55-595)
@@ -116,9 +124,7 @@ struct mgx_dg_plain_solver_s
   struct Level
   {
     mgx_dg_operator_t A = nullptr;
-    // from the level below (both null on level 0): a mesh refinement or a degree raise, exactly one of the two
-    mgx_dg_transfer_t        transfer        = nullptr;
-    mgx_dg_degree_transfer_t degree_transfer = nullptr;
+    const DGLevelStep *step = nullptr; // from the level below (null on level 0): a mesh refinement or a degree raise
     size_t            n = 0;
     mgx_smoother_info info{};
     void             *defect = nullptr, *t = nullptr, *update = nullptr, *old = nullptr; // V-cycle number type
@@ -1299,6 +1305,49 @@ int mgx_dg_solver_solve_cg(mgx_dg_solver_t S, double tolerance, const double *rh
  * --------------------------------------------------------------------------------------------- */
 namespace
 {
+  // a step in one direction: fine += P coarse (prolong) or coarse += P^T fine; `entry` names the caller in the messages
+  int step_apply(const DGLevelStep *T, bool prolong, void *dst, const void *src, const char *entry)
+  {
+    if (!T || !dst || !src || dst == src)
+      return dg_fail(MGX_ERR_INVALID_ARGUMENT, std::string(entry) + ": null or aliased vectors");
+    if (!mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->fine_degree, T->coarse_degree, prolong, dst, src,
+                                 T->n_groups, T->m1d, T->dim, T->children, T->identity))
+      return dg_fail(MGX_ERR_UNSUPPORTED, std::string(entry) + ": no kernel for this pair of degrees");
+    MGX_HIP(hipGetLastError());
+    return MGX_OK;
+  }
+
+  // what both kinds of step hold, and the 1D matrix on the device in the number type
+  int step_fill(DGLevelStep &T, mgx_context_t ctx, int dim, int basis, int number, uint32_t n_groups, const std::vector<double> &m1d)
+  {
+    T.ctx      = ctx;
+    T.dim      = dim;
+    T.basis    = basis;
+    T.number   = number;
+    T.n_groups = n_groups;
+    T.m1d_host = m1d;
+    return T.mem.upload_as(number, &T.m1d, m1d.data(), m1d.size());
+  }
+
+  int step_matrix(const DGLevelStep *T, double *m1d, const char *entry)
+  {
+    if (!T || !m1d)
+      return dg_fail(MGX_ERR_INVALID_ARGUMENT, std::string(entry) + ": null argument");
+    std::copy(T->m1d_host.begin(), T->m1d_host.end(), m1d);
+    return MGX_OK;
+  }
+
+  template <typename Step> // the handle's own type: what was created is what is deleted
+  int step_destroy(Step *T)
+  {
+    if (!T)
+      return MGX_OK;
+    if (T->ctx)
+      (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(T->ctx));
+    delete T;
+    return MGX_OK;
+  }
+
   // one part of a V-cycle, timed when the solver's timings are on (print_wall_times of the reference: host timers
   // around synchronised parts -- for diagnosis, the parts no longer overlap their launches)
   struct PlainTimer
@@ -1349,25 +1398,27 @@ namespace
     {
       PlainTimer timer(S, &L.times[1]);
       MGX_HIP(hipMemsetAsync(C.defect, 0, dg_nsz(S->number) * C.n, s)); // :482
-      if (L.transfer)
-        MGX_TRY(mgx_dg_transfer_restrict_and_add(L.transfer, C.defect, L.t)); // :483
-      else
-        MGX_TRY(mgx_dg_degree_transfer_restrict_and_add(L.degree_transfer, C.defect, L.t));
+      MGX_TRY(step_apply(L.step, false, C.defect, L.t, "mgx_dg_plain_solver: restriction")); // :483
     }
     MGX_TRY(plain_v_cycle(S, l - 1));
     {
       PlainTimer timer(S, &L.times[2]);
-      if (L.transfer)
-        MGX_TRY(mgx_dg_transfer_prolongate_and_add(L.transfer, L.update, C.update)); // :489
-      else
-        MGX_TRY(mgx_dg_degree_transfer_prolongate_and_add(L.degree_transfer, L.update, C.update));
+      MGX_TRY(step_apply(L.step, true, L.update, C.update, "mgx_dg_plain_solver: prolongation")); // :489
     }
     PlainTimer timer(S, &L.times[5]);
     return dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, true); // :493
   }
 
-  // the solver object of a checked level sequence: level vectors and smooth[level].initialize.  Between levels l - 1 and
-  // l sits whichever of desc->transfer[l - 1] and desc->degree_transfer[l - 1] is set (either array may be null)
+  // the step from level l - 1 to level l: whichever of desc->transfer[l - 1] and desc->degree_transfer[l - 1] is set
+  // (either array may be null); null if neither is
+  const DGLevelStep *step_of(const mgx_dg_hp_solver_desc *desc, int l)
+  {
+    if (desc->transfer && desc->transfer[l - 1])
+      return desc->transfer[l - 1];
+    return desc->degree_transfer ? desc->degree_transfer[l - 1] : nullptr;
+  }
+
+  // the solver object of a checked level sequence: level vectors and smooth[level].initialize
   int plain_solver_build(mgx_context_t ctx, const mgx_dg_hp_solver_desc *desc, mgx_dg_plain_solver_t *out)
   {
     const int         L   = desc->n_levels - 1;
@@ -1381,10 +1432,9 @@ namespace
     for (int l = 0; l <= L; ++l)
       {
         mgx_dg_plain_solver_s::Level &lv = S->level[l];
-        lv.A               = desc->matrix[l];
-        lv.transfer        = l > 0 && desc->transfer ? desc->transfer[l - 1] : nullptr;
-        lv.degree_transfer = l > 0 && desc->degree_transfer ? desc->degree_transfer[l - 1] : nullptr;
-        lv.n               = (size_t)mgx_dg_operator_n_dofs(lv.A);
+        lv.A    = desc->matrix[l];
+        lv.step = l > 0 ? step_of(desc, l) : nullptr;
+        lv.n    = (size_t)mgx_dg_operator_n_dofs(lv.A);
         for (void **v : {&lv.defect, &lv.t, &lv.update, &lv.old})
           {
             MGX_TRY(S->mem.zeros(v, dg_nsz(S->number) * lv.n, s));
@@ -1413,6 +1463,91 @@ namespace
     MGX_HIP(hipStreamSynchronize(s));
     *out = S.release();
     return MGX_OK;
+  }
+
+  // what both entry points of the plain solver ask of a level sequence: the operators level by level, the step between
+  // two levels, the fp64 twin; then the solver.  degree_raises: mgx_dg_hp_solver_create; without them
+  // (mgx_dg_plain_solver_create) all levels have one degree, every step is a mesh refinement, and a problem without a
+  // Dirichlet face is called unsupported, not an invalid argument
+  int plain_solver_create(const std::string &name, bool degree_raises, mgx_context_t ctx, const mgx_dg_hp_solver_desc *desc,
+                          mgx_dg_plain_solver_t *out)
+  {
+    const auto refuse = [&](const std::string &why) { return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + why); };
+    const auto str    = [](uint64_t v) { return std::to_string(v); };
+    if (!ctx || !out || !desc->matrix || !desc->matrix_dg_dp || (!degree_raises && desc->n_levels > 1 && !desc->transfer))
+      return refuse("null argument");
+    if (desc->n_levels < 1 || desc->n_levels > 32)
+      return refuse("n_levels must be in 1..32");
+    if (desc->degree_pre < 1)
+      return refuse("degree_pre must be at least 1");
+    const int         L   = desc->n_levels - 1;
+    mgx_dg_operator_t top = desc->matrix[L], Ad = desc->matrix_dg_dp;
+    if (!top)
+      return refuse("matrix[" + str(L) + "] is null");
+    const int         singular   = degree_raises ? MGX_ERR_INVALID_ARGUMENT : MGX_ERR_UNSUPPORTED;
+    const std::string no_dirichlet = " has no Dirichlet face: the problem is singular (pure Neumann problems are not solved)";
+    for (int l = 0; l <= L; ++l)
+      {
+        mgx_dg_operator_t A     = desc->matrix[l];
+        const std::string level = "level " + str(l) + ": matrix[" + str(l) + "]";
+        if (!A)
+          return refuse(level + " is null");
+        if (A->ctx != ctx)
+          return refuse(level + " belongs to another context");
+        if (A->n_ghost > 0)
+          return refuse(level + " has ghost cells; the plain DG multigrid runs on one rank");
+        if (A->basis != top->basis || A->number != top->number || (!degree_raises && A->degree != top->degree))
+          return refuse(level + " differs from the finest level in " + (degree_raises ? "" : "degree, ") + "basis or number type");
+        if (A->dim != top->dim)
+          return refuse(level + " has dimension " + str(A->dim) + ", the finest level " + str(top->dim));
+        if (!A->has_dirichlet)
+          return dg_fail(singular, name + level + no_dirichlet);
+        if (l == 0)
+          continue;
+        mgx_dg_operator_t  C = desc->matrix[l - 1];
+        const DGLevelStep *H = desc->transfer ? desc->transfer[l - 1] : nullptr;
+        const DGLevelStep *P = desc->degree_transfer ? desc->degree_transfer[l - 1] : nullptr;
+        const std::string  step = "the step from level " + str(l - 1) + " to level " + str(l), at = "[" + str(l - 1) + "]";
+        if (!degree_raises && !H)
+          return refuse("transfer" + at + " is null");
+        if ((H != nullptr) == (P != nullptr))
+          return refuse(step + " needs exactly one of transfer" + at + " (a mesh refinement) and degree_transfer" + at +
+                        " (a degree raise), it has " + (H ? "both" : "neither"));
+        const DGLevelStep *S     = H ? H : P;
+        const std::string  which = (H ? "transfer" : "degree_transfer") + at;
+        if (S->basis != top->basis || S->number != top->number || S->ctx != ctx)
+          return refuse(step + ": " + which + " differs from the operators in basis, number type or context");
+        if (S->dim != top->dim)
+          return refuse(step + ": " + which + " has dimension " + str(S->dim) + ", the operators " + str(top->dim));
+        if (H)
+          {
+            if (C->degree != A->degree || H->fine_degree != A->degree)
+              return refuse(step + " is a mesh refinement: the levels have degrees " + str(C->degree) + " and " + str(A->degree) +
+                            ", the transfer " + str(H->fine_degree) + " (all equal required)");
+            if (H->n_groups != C->n_cells || ((uint64_t)C->n_cells << top->dim) != A->n_cells)
+              return refuse(step + " is a mesh refinement: level " + str(l) + " has " + str(A->n_cells) + " cells, level " + str(l - 1) +
+                            " " + str(C->n_cells) + " and the transfer " + str(H->n_groups) + " coarse cells (" + str(1 << top->dim) +
+                            " x coarse = fine required)");
+          }
+        else
+          {
+            if (C->n_cells != A->n_cells || P->n_groups != A->n_cells)
+              return refuse(step + " is a degree raise: the levels have " + str(C->n_cells) + " and " + str(A->n_cells) +
+                            " cells, the degree transfer " + str(P->n_groups) + " (all equal required)");
+            if (C->degree >= A->degree)
+              return refuse(step + " is a degree raise: the coarse degree " + str(C->degree) + " must be below the fine degree " +
+                            str(A->degree));
+            if (P->coarse_degree != C->degree || P->fine_degree != A->degree)
+              return refuse(step + ": the degree transfer is between degrees " + str(P->coarse_degree) + " and " + str(P->fine_degree) +
+                            ", its operators have " + str(C->degree) + " and " + str(A->degree));
+          }
+      }
+    if (Ad->number != MGX_F64 || Ad->n_cells != top->n_cells || Ad->degree != top->degree || Ad->basis != top->basis || Ad->n_ghost > 0 ||
+        Ad->ctx != ctx || Ad->dim != top->dim)
+      return refuse("matrix_dg_dp must be the fp64 twin of the operator of level " + str(L) + ", the finest");
+    if (!Ad->has_dirichlet)
+      return dg_fail(singular, name + "matrix_dg_dp" + no_dirichlet);
+    return plain_solver_build(ctx, desc, out);
   }
 } // namespace
 
@@ -1454,52 +1589,11 @@ int mgx_dg_transfer_create(mgx_context_t ctx, const mgx_dg_transfer_desc *desc, 
   if (status != MGX_OK)
     return dg_fail(status, "mgx_dg_transfer_create: " + why);
   std::unique_ptr<mgx_dg_transfer_s, int (*)(mgx_dg_transfer_t)> T(new mgx_dg_transfer_s, mgx_dg_transfer_destroy);
-  T->ctx      = ctx;
-  T->dim      = dim;
-  T->degree   = desc->degree;
-  T->basis    = desc->basis;
-  T->number   = desc->number;
-  T->n_coarse = desc->n_coarse_cells;
-  T->identity = identity;
-  T->p1d_host = h.embed;
+  T->fine_degree = T->coarse_degree = desc->degree;
+  T->identity                       = identity;
   MGX_TRY(T->mem.upload(&T->children, desc->children, n_fine));
-  MGX_TRY(T->mem.upload_as(T->number, &T->p1d, h.embed.data(), h.embed.size()));
+  MGX_TRY(step_fill(*T, ctx, dim, desc->basis, desc->number, desc->n_coarse_cells, h.embed));
   *out = T.release();
-  return MGX_OK;
-}
-
-int mgx_dg_transfer_destroy(mgx_dg_transfer_t T)
-{
-  if (!T)
-    return MGX_OK;
-  if (T->ctx)
-    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(T->ctx));
-  delete T;
-  return MGX_OK;
-}
-
-int mgx_dg_transfer_prolongate_and_add(mgx_dg_transfer_t T, void *fine_dst, const void *coarse_src)
-{
-  MGX_REQUIRE(T && fine_dst && coarse_src && fine_dst != coarse_src, "mgx_dg_transfer_prolongate_and_add: null or aliased vectors");
-  mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->degree, true, fine_dst, coarse_src, T->children,
-                          T->n_coarse, T->p1d, T->identity, T->dim);
-  MGX_HIP(hipGetLastError());
-  return MGX_OK;
-}
-
-int mgx_dg_transfer_restrict_and_add(mgx_dg_transfer_t T, void *coarse_dst, const void *fine_src)
-{
-  MGX_REQUIRE(T && coarse_dst && fine_src && coarse_dst != fine_src, "mgx_dg_transfer_restrict_and_add: null or aliased vectors");
-  mgx::launch_dg_transfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->degree, false, coarse_dst, fine_src, T->children,
-                          T->n_coarse, T->p1d, T->identity, T->dim);
-  MGX_HIP(hipGetLastError());
-  return MGX_OK;
-}
-
-int mgx_dg_transfer_matrix(mgx_dg_transfer_t T, double *p1d)
-{
-  MGX_REQUIRE(T && p1d, "mgx_dg_transfer_matrix: null argument");
-  std::copy(T->p1d_host.begin(), T->p1d_host.end(), p1d);
   return MGX_OK;
 }
 
@@ -1514,201 +1608,58 @@ int mgx_dg_degree_transfer_create(mgx_context_t ctx, const mgx_dg_degree_transfe
   if (dim < 0)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_degree_transfer_create: dim must be 0 or 3 (three dimensions) or 2");
   // degrees and basis: checked by the host function, which names what it refuses
-  const int           nf = desc->fine_degree + 1, nc = desc->coarse_degree + 1;
   std::vector<double> e1d((size_t)(MGX_MAX_DEGREE + 1) * (MGX_MAX_DEGREE + 1));
   MGX_TRY(mgx_dg_degree_embedding(desc->fine_degree, desc->coarse_degree, desc->basis, e1d.data()));
-  e1d.resize((size_t)nf * nc);
+  e1d.resize((size_t)(desc->fine_degree + 1) * (desc->coarse_degree + 1));
   std::unique_ptr<mgx_dg_degree_transfer_s, int (*)(mgx_dg_degree_transfer_t)> T(new mgx_dg_degree_transfer_s,
                                                                                  mgx_dg_degree_transfer_destroy);
-  T->ctx           = ctx;
-  T->dim           = dim;
   T->fine_degree   = desc->fine_degree;
   T->coarse_degree = desc->coarse_degree;
-  T->basis         = desc->basis;
-  T->number        = desc->number;
-  T->n_cells       = desc->n_cells;
-  T->e1d_host      = e1d;
-  MGX_TRY(T->mem.upload_as(T->number, &T->e1d, e1d.data(), e1d.size()));
+  MGX_TRY(step_fill(*T, ctx, dim, desc->basis, desc->number, desc->n_cells, e1d));
   *out = T.release();
   return MGX_OK;
 }
 
-int mgx_dg_degree_transfer_destroy(mgx_dg_degree_transfer_t T)
+int mgx_dg_transfer_destroy(mgx_dg_transfer_t T) { return step_destroy(T); }
+int mgx_dg_degree_transfer_destroy(mgx_dg_degree_transfer_t T) { return step_destroy(T); }
+
+int mgx_dg_transfer_prolongate_and_add(mgx_dg_transfer_t T, void *fine_dst, const void *coarse_src)
 {
-  if (!T)
-    return MGX_OK;
-  if (T->ctx)
-    (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(T->ctx));
-  delete T;
-  return MGX_OK;
+  return step_apply(T, true, fine_dst, coarse_src, "mgx_dg_transfer_prolongate_and_add");
+}
+
+int mgx_dg_transfer_restrict_and_add(mgx_dg_transfer_t T, void *coarse_dst, const void *fine_src)
+{
+  return step_apply(T, false, coarse_dst, fine_src, "mgx_dg_transfer_restrict_and_add");
 }
 
 int mgx_dg_degree_transfer_prolongate_and_add(mgx_dg_degree_transfer_t T, void *fine_dst, const void *coarse_src)
 {
-  MGX_REQUIRE(T && fine_dst && coarse_src && fine_dst != coarse_src, "mgx_dg_degree_transfer_prolongate_and_add: null or aliased vectors");
-  if (!mgx::launch_dg_ptransfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->fine_degree, T->coarse_degree, true, fine_dst,
-                                coarse_src, T->n_cells, T->e1d, T->dim))
-    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_degree_transfer_prolongate_and_add: no kernel for this pair of degrees");
-  MGX_HIP(hipGetLastError());
-  return MGX_OK;
+  return step_apply(T, true, fine_dst, coarse_src, "mgx_dg_degree_transfer_prolongate_and_add");
 }
 
 int mgx_dg_degree_transfer_restrict_and_add(mgx_dg_degree_transfer_t T, void *coarse_dst, const void *fine_src)
 {
-  MGX_REQUIRE(T && coarse_dst && fine_src && coarse_dst != fine_src, "mgx_dg_degree_transfer_restrict_and_add: null or aliased vectors");
-  if (!mgx::launch_dg_ptransfer((hipStream_t)mgx_context_stream(T->ctx), T->number, T->fine_degree, T->coarse_degree, false, coarse_dst,
-                                fine_src, T->n_cells, T->e1d, T->dim))
-    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_degree_transfer_restrict_and_add: no kernel for this pair of degrees");
-  MGX_HIP(hipGetLastError());
-  return MGX_OK;
+  return step_apply(T, false, coarse_dst, fine_src, "mgx_dg_degree_transfer_restrict_and_add");
 }
 
-int mgx_dg_degree_transfer_matrix(mgx_dg_degree_transfer_t T, double *e1d)
-{
-  MGX_REQUIRE(T && e1d, "mgx_dg_degree_transfer_matrix: null argument");
-  std::copy(T->e1d_host.begin(), T->e1d_host.end(), e1d);
-  return MGX_OK;
-}
+int mgx_dg_transfer_matrix(mgx_dg_transfer_t T, double *p1d) { return step_matrix(T, p1d, "mgx_dg_transfer_matrix"); }
+int mgx_dg_degree_transfer_matrix(mgx_dg_degree_transfer_t T, double *e1d) { return step_matrix(T, e1d, "mgx_dg_degree_transfer_matrix"); }
 
 int mgx_dg_hp_solver_create(mgx_context_t ctx, const mgx_dg_hp_solver_desc *desc, mgx_dg_plain_solver_t *out)
 {
-  const std::string name = "mgx_dg_hp_solver_create: ";
-  if (!ctx || !desc || !out || !desc->matrix || !desc->matrix_dg_dp)
-    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "null argument");
-  if (desc->n_levels < 1 || desc->n_levels > 32)
-    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "n_levels must be in 1..32");
-  if (desc->degree_pre < 1)
-    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "degree_pre must be at least 1");
-  const int         L   = desc->n_levels - 1;
-  mgx_dg_operator_t top = desc->matrix[L], Ad = desc->matrix_dg_dp;
-  if (!top)
-    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "matrix[" + std::to_string(L) + "] is null");
-  for (int l = 0; l <= L; ++l)
-    {
-      mgx_dg_operator_t A     = desc->matrix[l];
-      const std::string level = "level " + std::to_string(l) + ": matrix[" + std::to_string(l) + "]";
-      if (!A)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " is null");
-      if (A->ctx != ctx)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " belongs to another context");
-      if (A->n_ghost > 0)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " has ghost cells; the plain DG multigrid runs on one rank");
-      if (A->basis != top->basis || A->number != top->number)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " differs from the finest level in basis or number type");
-      if (A->dim != top->dim)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " has dimension " + std::to_string(A->dim) + ", the finest level " +
-                                                   std::to_string(top->dim));
-      if (!A->has_dirichlet)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + level + " has no Dirichlet face: the problem is singular (pure Neumann "
-                                                                "problems are not solved)");
-      if (l == 0)
-        continue;
-      mgx_dg_operator_t        C    = desc->matrix[l - 1];
-      mgx_dg_transfer_t        H    = desc->transfer ? desc->transfer[l - 1] : nullptr;
-      mgx_dg_degree_transfer_t P    = desc->degree_transfer ? desc->degree_transfer[l - 1] : nullptr;
-      const std::string        step = "the step from level " + std::to_string(l - 1) + " to level " + std::to_string(l);
-      if ((H != nullptr) == (P != nullptr))
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " needs exactly one of transfer[" + std::to_string(l - 1) +
-                                                   "] (a mesh refinement) and degree_transfer[" + std::to_string(l - 1) +
-                                                   "] (a degree raise), it has " + (H ? "both" : "neither"));
-      if (H)
-        {
-          if (H->basis != top->basis || H->number != top->number || H->ctx != ctx || H->dim != top->dim)
-            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + ": the transfer differs from the operators in basis, number type, "
-                                                                   "dimension or context");
-          if (C->degree != A->degree || H->degree != A->degree)
-            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " is a mesh refinement: the levels have degrees " +
-                                                       std::to_string(C->degree) + " and " + std::to_string(A->degree) +
-                                                       ", the transfer " + std::to_string(H->degree) + " (all equal required)");
-          if (H->n_coarse != C->n_cells || ((uint64_t)C->n_cells << top->dim) != A->n_cells)
-            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " is a mesh refinement: level " + std::to_string(l) + " has " +
-                                                       std::to_string(A->n_cells) + " cells, level " + std::to_string(l - 1) + " " +
-                                                       std::to_string(C->n_cells) + " and the transfer " + std::to_string(H->n_coarse) +
-                                                       " coarse cells (" + (top->dim == 2 ? "4" : "8") + " x coarse = fine required)");
-        }
-      else
-        {
-          if (P->basis != top->basis || P->number != top->number || P->ctx != ctx || P->dim != top->dim)
-            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + ": the degree transfer differs from the operators in basis, number "
-                                                                   "type, dimension or context");
-          if (C->n_cells != A->n_cells || P->n_cells != A->n_cells)
-            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " is a degree raise: the levels have " + std::to_string(C->n_cells) +
-                                                       " and " + std::to_string(A->n_cells) + " cells, the degree transfer " +
-                                                       std::to_string(P->n_cells) + " (all equal required)");
-          if (C->degree >= A->degree)
-            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + " is a degree raise: the coarse degree " + std::to_string(C->degree) +
-                                                       " must be below the fine degree " + std::to_string(A->degree));
-          if (P->coarse_degree != C->degree || P->fine_degree != A->degree)
-            return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + step + ": the degree transfer is between degrees " +
-                                                       std::to_string(P->coarse_degree) + " and " + std::to_string(P->fine_degree) +
-                                                       ", its operators have " + std::to_string(C->degree) + " and " +
-                                                       std::to_string(A->degree));
-        }
-    }
-  if (Ad->number != MGX_F64 || Ad->n_cells != top->n_cells || Ad->degree != top->degree || Ad->basis != top->basis || Ad->n_ghost > 0 ||
-      Ad->ctx != ctx || Ad->dim != top->dim || !Ad->has_dirichlet)
-    return dg_fail(MGX_ERR_INVALID_ARGUMENT, name + "matrix_dg_dp must be the fp64 twin of the operator of level " + std::to_string(L) +
-                                               ", the finest");
-  return plain_solver_build(ctx, desc, out);
+  if (!desc)
+    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_hp_solver_create: null argument");
+  return plain_solver_create("mgx_dg_hp_solver_create: ", true, ctx, desc, out);
 }
 
 int mgx_dg_plain_solver_create(mgx_context_t ctx, const mgx_dg_plain_solver_desc *desc, mgx_dg_plain_solver_t *out)
 {
-  if (!ctx || !desc || !out || !desc->matrix || !desc->matrix_dg_dp || (desc->n_levels > 1 && !desc->transfer))
+  if (!desc)
     return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: null argument");
-  if (desc->n_levels < 1 || desc->n_levels > 32)
-    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: n_levels must be in 1..32");
-  if (desc->degree_pre < 1)
-    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: degree_pre must be at least 1");
-  const int         L   = desc->n_levels - 1;
-  mgx_dg_operator_t top = desc->matrix[L], Ad = desc->matrix_dg_dp;
-  for (int l = 0; l <= L; ++l)
-    {
-      mgx_dg_operator_t A = desc->matrix[l];
-      if (!A)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) + "] is null");
-      if (A->ctx != ctx)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: operators of another context");
-      if (A->n_ghost > 0)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
-                                                   "] has ghost cells; the plain DG multigrid runs on one rank");
-      if (A->degree != top->degree || A->basis != top->basis || A->number != top->number)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
-                                                   "] differs from the finest level in degree, basis or number type");
-      if (A->dim != top->dim)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) + "] has dimension " +
-                                                   std::to_string(A->dim) + ", the finest level " + std::to_string(top->dim));
-      if (!A->has_dirichlet)
-        return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_plain_solver_create: matrix[" + std::to_string(l) +
-                                              "] has no Dirichlet face: the problem is singular (pure Neumann problems are not "
-                                              "solved)");
-      if (l == 0)
-        continue;
-      mgx_dg_transfer_t T = desc->transfer[l - 1];
-      if (!T)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) + "] is null");
-      if (T->degree != top->degree || T->basis != top->basis || T->number != top->number || T->ctx != ctx)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) +
-                                                   "] differs from the operators in degree, basis, number type or context");
-      if (T->dim != top->dim)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: transfer[" + std::to_string(l - 1) + "] has dimension " +
-                                                   std::to_string(T->dim) + ", the operators " + std::to_string(top->dim));
-      if (T->n_coarse != desc->matrix[l - 1]->n_cells || ((uint64_t)desc->matrix[l - 1]->n_cells << top->dim) != A->n_cells)
-        return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: level " + std::to_string(l) + " has " +
-                                                   std::to_string(A->n_cells) + " cells, level " + std::to_string(l - 1) + " " +
-                                                   std::to_string(desc->matrix[l - 1]->n_cells) + " and the transfer between them " +
-                                                   std::to_string(T->n_coarse) + " coarse cells (" + (top->dim == 2 ? "4" : "8") +
-                                                   " x coarse = fine required)");
-    }
-  if (Ad->number != MGX_F64 || Ad->n_cells != top->n_cells || Ad->degree != top->degree || Ad->basis != top->basis || Ad->n_ghost > 0 ||
-      Ad->ctx != ctx || Ad->dim != top->dim)
-    return dg_fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dg_plain_solver_create: matrix_dg_dp must be the fp64 twin of the finest matrix");
-  if (!Ad->has_dirichlet)
-    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_plain_solver_create: matrix_dg_dp has no Dirichlet face: the problem is singular "
-                                        "(pure Neumann problems are not solved)");
-
-  const mgx_dg_hp_solver_desc levels{desc->n_levels, desc->matrix, Ad, desc->transfer, nullptr, desc->degree_pre, desc->cell_global_id};
-  return plain_solver_build(ctx, &levels, out);
+  const mgx_dg_hp_solver_desc levels{desc->n_levels, desc->matrix, desc->matrix_dg_dp, desc->transfer, nullptr, desc->degree_pre,
+                                     desc->cell_global_id};
+  return plain_solver_create("mgx_dg_plain_solver_create: ", false, ctx, &levels, out);
 }
 
 int mgx_dg_plain_solver_destroy(mgx_dg_plain_solver_t S)

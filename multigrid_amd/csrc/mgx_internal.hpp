@@ -576,17 +576,15 @@ namespace mgx
   // plain read-modify-writes instead of one with atomics
   void launch_dg_cg_transfer(hipStream_t s, int number, int p, bool to_dg, void *dst, const void *src,
                              const uint32_t *idx27, uint32_t n_cells, const void *P1, bool eight_colours = false);
-  // DG <-> DG transfer between a level and its refinement (mgx_dg_transfer.hip): prolong: fine += P coarse, else
-  // coarse += P^T fine; children [n_coarse][8] names every fine cell exactly once (the caller has checked it);
-  // p1d [2][(p+1)^2] in the number type; identity: children[c][k] == 8 c + k, the table is not read.  dim == 2: a cell
-  // and its four children, children [n_coarse][4], identity: children[c][k] == 4 c + k
-  void launch_dg_transfer(hipStream_t s, int number, int p, bool prolong, void *dst, const void *src, const uint32_t *children,
-                          uint32_t n_coarse, const void *p1d, bool identity, int dim);
-  // DG <-> DG transfer between two degrees pc < pf on one mesh (mgx_dg_ptransfer.hip): prolong: fine += (E (x) E (x) E)
-  // coarse, else coarse += (E (x) E (x) E)^T fine, cell by cell; e1d [(pf+1)][(pc+1)] in the number type; dim == 2:
-  // E (x) E.  false: no kernel for this pair of degrees
-  bool launch_dg_ptransfer(hipStream_t s, int number, int pf, int pc, bool prolong, void *dst, const void *src, uint32_t n_cells,
-                           const void *e1d, int dim);
+  // DG <-> DG transfer over one step of a level hierarchy (mgx_dg_transfer.hip): prolong: fine += P coarse, else
+  // coarse += P^T fine, group by group; dim == 2 or 3.  false: no kernel for this pair of degrees
+  //   coarse_degree == fine_degree = p: a mesh step, a group is a coarse cell and its 2^dim children.  n_groups coarse
+  //   cells; children [n_groups][2^dim] names every fine cell exactly once (the caller has checked it); identity:
+  //   children[c][k] == 2^dim c + k, the table is not read; m1d [2][(p+1)^2] in the number type
+  //   coarse_degree < fine_degree: a degree step on one mesh, a group is a cell.  n_groups cells; m1d [(pf+1)][(pc+1)]
+  //   in the number type; children and identity are not looked at
+  bool launch_dg_transfer(hipStream_t s, int number, int fine_degree, int coarse_degree, bool prolong, void *dst, const void *src,
+                          uint32_t n_groups, const void *m1d, int dim, const uint32_t *children, bool identity);
   // ---- DG cell kernel (mgx_dg_kernels.hip): what it offers the host code of mgx_dg_api.cpp ----
   namespace dg
   {
