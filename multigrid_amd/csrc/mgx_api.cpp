@@ -6,6 +6,7 @@
 #include "mgx_bricks.hpp"
 #include "mgx_device_memory.hpp"
 #include "mgx_internal.hpp"
+#include "mgx_krylov.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types only: the library is bound at run time (dlopen), single-GPU users need no RCCL
@@ -294,20 +295,7 @@ struct mgx_smoother_s
   double            req_range  = 0;
   int               req_degree = 0, req_eig_its = 0;
   // factor of the first step, and factor1 / factor2 of iteration k = 0, 1, ... of the recurrence
-  double first_factor() const { return fourth_kind ? 4. / (3. * info.delta) : 1. / info.theta; }
-  void   next_factors(int k, double &rhok, double &f1, double &f2) const
-  {
-    if (fourth_kind)
-      {
-        f1 = (2. * k + 1.) / (2. * k + 5.);
-        f2 = (8. * k + 12.) / (info.delta * (2. * k + 5.));
-        return;
-      }
-    const double sigma = info.theta / info.delta, rhokp = 1. / (2. * sigma - rhok);
-    f1   = rhokp * rhok;
-    f2   = 2. * rhokp / info.delta;
-    rhok = rhokp;
-  }
+  krylov::ChebyshevFactors factors() const { return krylov::ChebyshevFactors(info, fourth_kind); }
 };
 
 struct mgx_transfer_s
@@ -728,109 +716,98 @@ namespace
       (void)roctx().pop();
   }
 
-  struct Stopwatch
+
+  // the sum the launch before has left: decomposed, duplicated interface DoFs must count once -- dot() with the plan
+  int fused_sum(mgx_operator_t A, const void *a, const void *b, double *out)
   {
-    mgx_solver_t s;
-    int          level, slot;
-    std::chrono::steady_clock::time_point t0;
-    Stopwatch(mgx_solver_t s, int level, int slot)
-      : s(s)
-      , level(level)
-      , slot(slot)
+    return A->ctx->has_comm ? dot(A->ctx, A->d.number, a, b, A->d.n_dofs, out, A->plan.get()) : read_result(A->ctx, out);
+  }
+
+  // The four steps of a CG iteration (mgx_krylov.hpp) on an FE_Q operator with vectors of its number type.  Mixed precision
+  // (r32, z32 set): the fp32 defect is written along with r, the direction reads the fp32 result z32 of the preconditioner
+  template <typename PreconditionDot>
+  struct CGOps
+  {
+    mgx_operator_t  A;
+    void           *x, *r, *z, *d, *h;
+    PreconditionDot precondition_dot;
+    float          *r32 = nullptr;
+    const float    *z32 = nullptr;
+    int direction(double beta, bool first)
     {
-      if (s->ctx->tun.roctx)
-        {
-          // the phases print_wall_times() reports (multigrid_solver.h:348-371), the smoother under the reference's
-          // marker name
-          static const char *const names[6] = {"mg_mv", "restrict", "prolongate", "inhomBC", "mg_vec", "vmult_cheby"};
-          char                     buf[48];
-          std::snprintf(buf, sizeof(buf), "%s_%d", (level == 0 && slot == 0) ? "coarse_solver" : names[slot], level);
-          range_push(s->ctx, buf);
-        }
-      if (s->timing)
-        {
-          (void)hipStreamSynchronize(s->ctx->stream);
-          t0 = std::chrono::steady_clock::now();
-        }
+      hipStream_t s = A->ctx->stream;
+      if (first)
+        launch_copy_cast(s, d, A->d.number, z32 ? (const void *)z32 : z, z32 ? MGX_F32 : A->d.number, A->d.n_dofs);
+      else if (z32)
+        launch_xpby_f64_f32(s, (double *)d, z32, beta, A->d.n_dofs);
+      else
+        launch_xpby(s, A->d.number, d, z, beta, A->d.n_dofs);
+      return MGX_OK;
     }
-    ~Stopwatch()
+    int vmult_dot(double *dh)
     {
-      if (s->timing)
-        {
-          (void)hipStreamSynchronize(s->ctx->stream);
-          s->timings[6 * level + slot] +=
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-      range_pop(s->ctx);
+      MGX_TRY(mgx_vmult(A, h, d));
+      return dot(A->ctx, A->d.number, d, h, A->d.n_dofs, dh, A->plan.get());
+    }
+    int update(double alpha, double *res)
+    {
+      mgx_context_t ctx = A->ctx;
+      if (r32)
+        launch_cg_update_f32copy(ctx->stream, (double *)x, (double *)r, (const double *)d, (const double *)h, alpha, A->d.n_dofs,
+                                 r32, ctx->partial_dev, ctx->result_dev);
+      else
+        launch_cg_update(ctx->stream, A->d.number, x, r, d, h, alpha, A->d.n_dofs, ctx->partial_dev, ctx->result_dev);
+      MGX_TRY(fused_sum(A, r, r, res));
+      *res = std::sqrt(*res);
+      return MGX_OK;
     }
   };
 
-  // extreme eigenvalues of a symmetric tridiagonal matrix (Sturm bisection)
-  int sturm_count(int n, const double *d, const double *e, double x)
-  {
-    int    count = 0;
-    double q     = d[0] - x;
-    if (q < 0)
-      ++count;
-    for (int i = 1; i < n; ++i)
-      {
-        if (q == 0)
-          q = 1e-300;
-        q = d[i] - x - e[i - 1] * e[i - 1] / q;
-        if (q < 0)
-          ++count;
-      }
-    return count;
-  }
-
-  void tridiag_extreme(int n, const double *d, const double *e, double &lo, double &hi)
-  {
-    double gl = d[0], gu = d[0];
-    for (int i = 0; i < n; ++i)
-      {
-        const double r = (i > 0 ? std::fabs(e[i - 1]) : 0) + (i < n - 1 ? std::fabs(e[i]) : 0);
-        gl             = std::min(gl, d[i] - r);
-        gu             = std::max(gu, d[i] + r);
-      }
-    for (int which = 0; which < 2; ++which)
-      {
-        const int k = which == 0 ? 1 : n;
-        double    a = gl, b = gu;
-        for (int it = 0; it < 200; ++it)
-          {
-            const double m = 0.5 * (a + b);
-            if (m == a || m == b)
-              break;
-            if (sturm_count(n, d, e, m) >= k)
-              b = m;
-            else
-              a = m;
-          }
-        (which == 0 ? lo : hi) = 0.5 * (a + b);
-      }
-  }
+  // a timed part of the FE_Q V-cycle, as a range under the name of the phase
+  LevelTimer stopwatch(mgx_solver_t S, int level, int slot) { return LevelTimer(S->ctx, S->timing, &S->timings[6 * level], level, slot, true); }
 } // namespace
 
-void mgx::tridiag_extreme_eigenvalues(int n, const double *d, const double *e, double &lo, double &hi)
+mgx::LevelTimer::LevelTimer(mgx_context_t ctx, bool timed, double *times, int level, int part, bool with_ranges)
+  : ctx(ctx), slot(timed ? times + part : nullptr), ranges(with_ranges && ctx->tun.roctx)
 {
-  tridiag_extreme(n, d, e, lo, hi);
+  if (ranges)
+    {
+      // the phases print_wall_times() reports (multigrid_solver.h:348-371), the smoother under the reference's marker name
+      static const char *const names[6] = {"mg_mv", "restrict", "prolongate", "inhomBC", "mg_vec", "vmult_cheby"};
+      char                     buf[48];
+      std::snprintf(buf, sizeof(buf), "%s_%d", (level == 0 && part == 0) ? "coarse_solver" : names[part], level);
+      range_push(ctx, buf);
+    }
+  if (slot)
+    {
+      (void)hipStreamSynchronize(ctx->stream);
+      t0 = std::chrono::steady_clock::now();
+    }
 }
 
-double mgx::chebyshev_interval(double smoothing_range, int degree, mgx_smoother_info &info)
+mgx::LevelTimer::~LevelTimer()
 {
-  const double a =
-    smoothing_range > 1. ? info.lambda_max / smoothing_range : std::min(0.9 * info.lambda_max, info.lambda_min);
-  if (degree < 0) // numbers::invalid_unsigned_int: Varga's estimate for eps = smoothing_range
+  if (slot)
     {
-      const double actual_range = info.lambda_max / a;
-      const double sigma        = (1. - std::sqrt(1. / actual_range)) / (1. + std::sqrt(1. / actual_range));
-      const double eps          = smoothing_range;
-      degree = 1 + (int)(std::log(1. / eps + std::sqrt(1. / eps / eps - 1.)) / std::log(1. / sigma));
+      (void)hipStreamSynchronize(ctx->stream);
+      *slot += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
-  info.degree = degree;
-  info.delta  = (info.lambda_max - a) * 0.5;
-  info.theta  = (info.lambda_max + a) * 0.5;
-  return a;
+  if (ranges)
+    range_pop(ctx);
+}
+
+int mgx::residual_update_finish(hipStream_t s, int number, const void *cycle_result, double *residual, double *update, double factor,
+                                size_t n_free, size_t n, double *partials, double *sums_dev, double out[2])
+{
+  double sums[4];
+  const uint32_t used = launch_residual_post(s, number, cycle_result, residual, update, factor, n_free, n, partials);
+  launch_reduce4(s, partials, used, nullptr, sums_dev);
+  MGX_HIP(hipGetLastError());
+  MGX_HIP(hipMemcpyAsync(sums, sums_dev, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
+  out[0] = sums[0];
+  out[1] = sums[1];
+  return MGX_OK;
 }
 
 // Point-to-point exchange of packed device buffers with the context's transport (native RCCL group
@@ -2284,9 +2261,8 @@ int mgx_smoother_create(mgx_operator_t op, double smoothing_range, int degree, i
   // estimate_eigenvalues: PCG(D^-1) on v_i = (i mod 11) - mean; Lanczos tridiagonal
   void       *r = nullptr, *z = nullptr, *d = nullptr, *h = sm->tmp, *x = sm->x_old;
   DeviceArena scratch("mgx_smoother_create");
-  MGX_TRY(scratch.alloc(&r, bytes));
-  MGX_TRY(scratch.alloc(&z, bytes));
-  MGX_TRY(scratch.alloc(&d, bytes));
+  for (void **v : {&r, &z, &d})
+    MGX_TRY(scratch.alloc(v, bytes));
   {
     // deal.II: v_i = (global index of i) mod 11 minus the global mean
     double sc[2] = {op->start_sum, op->start_count};
@@ -2294,62 +2270,19 @@ int mgx_smoother_create(mgx_operator_t op, double smoothing_range, int degree, i
     launch_index_mod11(s, num, r, op->global_index_dev, sc[0] / sc[1], n);
   }
   MGX_HIP(hipMemsetAsync(x, 0, bytes, s));
-  std::vector<double> diag, off;
-  double              res = 0, rz = 0, rz_old = 0, alpha = 0, alpha_old = 0, beta = 0;
-  MGX_TRY(dot(ctx, num, r, r, n, &res, op->plan.get()));
-  res    = std::sqrt(res);
-  int it = 0;
+  double res = 0;
+  MGX_TRY(mgx_operator_l2_norm(op, r, &res));
   MGX_TRACE("smoother_create: n=%zu eig_its=%d res0=%g", n, eig_cg_n_iterations, res);
-  while (it < eig_cg_n_iterations && res > 1e-10) // IterationNumberControl(n_its, 1e-10)
-    {
-      ++it;
-      rz_old = rz;
-      launch_jacobi_dot(s, num, z, op->d.inv_diag, r, n, ctx->partial_dev, ctx->result_dev);
-      if (ctx->has_comm)
-        MGX_TRY(dot(ctx, num, r, z, n, &rz, op->plan.get()));
-      else
-        MGX_TRY(read_result(ctx, &rz));
-      if (it > 1)
-        {
-          beta = rz / rz_old;
-          launch_xpby(s, num, d, z, beta, n);
-        }
-      else
-        launch_copy_cast(s, d, num, z, num, n);
-      alpha_old = alpha;
-      MGX_TRY(mgx_vmult(op, h, d));
-      double dh = 0;
-      MGX_TRY(dot(ctx, num, d, h, n, &dh, op->plan.get()));
-      alpha = rz / dh;
-      launch_cg_update(s, num, x, r, d, h, alpha, n, ctx->partial_dev, ctx->result_dev);
-      if (ctx->has_comm)
-        MGX_TRY(dot(ctx, num, r, r, n, &res, op->plan.get())); // duplicated interface DoFs must count once
-      else
-        MGX_TRY(read_result(ctx, &res));
-      res = std::sqrt(res);
-      if (it == 1)
-        diag.push_back(1. / alpha);
-      else
-        {
-          off.push_back(std::sqrt(beta) / alpha_old);
-          diag.push_back(1. / alpha + beta / alpha_old);
-        }
-    }
+  const auto jacobi = [&](double *rz) {
+    launch_jacobi_dot(s, num, z, op->d.inv_diag, r, n, ctx->partial_dev, ctx->result_dev);
+    return fused_sum(op, r, z, rz);
+  };
+  CGOps<decltype(jacobi)> ops{op, x, r, z, d, h, jacobi};
+  mgx_smoother_info      &info = sm->info; // IterationNumberControl(n_its, 1e-10), extreme Ritz values by bisection
+  MGX_TRY(krylov::lanczos_estimate(ops, res, eig_cg_n_iterations, krylov::RitzRule{}, info));
   MGX_HIP(hipStreamSynchronize(s));
-  mgx_smoother_info &info = sm->info;
-  info.cg_iterations      = it;
-  if (diag.empty())
-    info.lambda_min = info.lambda_max = 1.;
-  else
-    {
-      double lo, hi;
-      off.push_back(0.);
-      tridiag_extreme((int)diag.size(), diag.data(), off.data(), lo, hi);
-      info.lambda_min = lo;
-      info.lambda_max = 1.2 * hi; // safety factor
-    }
-  const double a = chebyshev_interval(smoothing_range, degree, info);
-  MGX_TRACE("smoother_create: its=%d lambda=[%g,%g] degree=%d", it, info.lambda_min, info.lambda_max, info.degree);
+  const double a = krylov::chebyshev_interval(smoothing_range, degree, info);
+  MGX_TRACE("smoother_create: its=%d lambda=[%g,%g] degree=%d", info.cg_iterations, info.lambda_min, info.lambda_max, info.degree);
   sm->range_a = a;
   *out        = sm.release();
   return MGX_OK;
@@ -2404,11 +2337,11 @@ static int cheb_loop(mgx_smoother_t sm, void *x, const void *b)
   hipStream_t              s  = op->ctx->stream;
   if (I.degree < 2 || std::fabs(I.delta) < 1e-40)
     return MGX_OK;
-  double rhok = I.delta / I.theta;
+  krylov::ChebyshevFactors F = sm->factors();
   for (int k = 0; k < I.degree - 1; ++k)
     {
       double f1, f2;
-      sm->next_factors(k, rhok, f1, f2);
+      F.next(k, f1, f2);
       if (cheb_in_assembly(op))
         {
           cheb_assembly_iteration(sm, x, b, f1, f2, true);
@@ -2495,14 +2428,14 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
   if (!op->d.bricks.available())
     {
       if (is_step && cheb_in_assembly(op))
-        cheb_assembly_iteration(sm, x, b, 0., sm->first_factor(), false);
+        cheb_assembly_iteration(sm, x, b, 0., sm->factors().first(), false);
       else if (is_step)
         {
           MGX_TRY(mgx_vmult(op, sm->tmp, x));
-          launch_cheb_update(s, num, kUpdateFirst, x, sm->x_old, b, sm->tmp, op->d.inv_diag, 0., sm->first_factor(), n);
+          launch_cheb_update(s, num, kUpdateFirst, x, sm->x_old, b, sm->tmp, op->d.inv_diag, 0., sm->factors().first(), n);
         }
       else
-        launch_cheb_update(s, num, kUpdateStart, x, sm->x_old, b, nullptr, op->d.inv_diag, 0., sm->first_factor(), n);
+        launch_cheb_update(s, num, kUpdateStart, x, sm->x_old, b, nullptr, op->d.inv_diag, 0., sm->factors().first(), n);
       return cheb_loop(sm, x, b);
     }
   const bool three_term = I.degree >= 2 && std::fabs(I.delta) >= 1e-40;
@@ -2513,13 +2446,13 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
       // Zero initial guess: x_1 = (1/theta) D^-1 b is not stored.  The first loop iteration
       // evaluates it while gathering (kChebInit), the second one again as its x_old (kChebOldInit); from the
       // third on both operands are stored iterates.  Targets alternate so that the last is X.
-      const double f0   = sm->first_factor();
-      double       rhok = I.delta / I.theta;
+      const double f0   = sm->factors().first();
+      krylov::ChebyshevFactors F = sm->factors();
       void        *cur = nullptr, *old = nullptr;
       for (int k = 0; k < n_loop; ++k)
         {
           double f1, f2;
-          sm->next_factors(k, rhok, f1, f2);
+          F.next(k, f1, f2);
           void *out = ((n_loop - 1 - k) % 2 == 0) ? X : Y;
           MGX_TRY(cheb_fused_iteration(sm, k == 0 ? kChebInit : (k == 1 ? kChebOldInit : kCheb), cur, old, out, b, f1, f2, f0));
           old = cur;
@@ -2531,12 +2464,12 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
     {
       // x_1 = (1/theta) D^-1 b goes where an alternation over {X,Y} ends in X
       void *cur = (n_loop % 2 == 0) ? X : Y, *old = nullptr;
-      launch_cheb_init(s, num, cur, b, op->d.inv_diag, sm->first_factor(), n);
-      double rhok = I.delta / I.theta;
+      launch_cheb_init(s, num, cur, b, op->d.inv_diag, sm->factors().first(), n);
+      krylov::ChebyshevFactors F = sm->factors();
       for (int k = 0; k < n_loop; ++k)
         {
           double f1, f2;
-          sm->next_factors(k, rhok, f1, f2);
+          F.next(k, f1, f2);
           void *out = (cur == X) ? Y : X;
           MGX_TRY(cheb_fused_iteration(sm, k == 0 ? kChebZeroOld : kCheb, cur, old, out, b, f1, f2)); // k = 0: x_0 = 0
           old = cur;
@@ -2549,7 +2482,7 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
   if (T % 2 == 1 && T >= 3 && !sm->x_old2)
     MGX_TRY(sm->mem.alloc(&sm->x_old2, number_size(num) * n));
   void  *Z = sm->x_old2, *cur = X, *old = nullptr;
-  double rhok = I.delta / I.theta;
+  krylov::ChebyshevFactors F = sm->factors();
   for (int k = 1; k <= T; ++k)
     {
       void *out;
@@ -2560,12 +2493,12 @@ static int smoother_apply(mgx_smoother_t sm, void *x, const void *b, bool is_ste
       else
         out = k == 1 ? Y : (k == 2 ? Z : (k == 3 ? X : ((cur == X) ? Y : X)));
       if (k == 1)
-        MGX_TRY(cheb_fused_iteration(sm, prolong_blocks ? kChebFirstProlong : kChebFirst, cur, nullptr, out, b, 0., sm->first_factor(), 0.,
+        MGX_TRY(cheb_fused_iteration(sm, prolong_blocks ? kChebFirstProlong : kChebFirst, cur, nullptr, out, b, 0., sm->factors().first(), 0.,
                                      prolong_coarse, prolong_blocks, prolong_tr));
       else
         {
           double f1, f2;
-          sm->next_factors(k - 2, rhok, f1, f2);
+          F.next(k - 2, f1, f2);
           MGX_TRY(cheb_fused_iteration(sm, kCheb, cur, old, out, b, f1, f2));
         }
       old = cur;
@@ -3537,7 +3470,7 @@ static int agglomerated_cycle(mgx_solver_t S, int my_n_cycles)
   hipStream_t   s = ctx->stream, sg = G->ctx->stream;
   const int     num = S->vnumber;
   const size_t  ng = G->matrix[Lg]->d.n_dofs, nl = S->matrix[L]->d.n_dofs;
-  Stopwatch     sw(S, L, 5);
+  LevelTimer sw = stopwatch(S, L, 5);
   MGX_HIP(hipMemsetAsync(G->defect[Lg], 0, number_size(num) * ng, s));
   launch_scatter_map(s, num, G->defect[Lg], S->defect[L], S->agg_map, S->agg_owned, (uint32_t)nl);
   if (ctx->use_rccl)
@@ -3687,7 +3620,7 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
   hipStream_t s = S->ctx->stream;
   if (level == 0)
     {
-      Stopwatch sw(S, 0, 0);
+      LevelTimer sw = stopwatch(S, 0, 0);
       S->timings[1] += 1;
       return smoother_apply(S->smooth[0], S->solution_update[0], S->defect[0], false); // :647 (MGCoarseFromSmoother :72-91)
     }
@@ -3695,7 +3628,7 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
   for (int c = 0; c < my_n_cycles; ++c)
     {
       {
-        Stopwatch sw(S, level, 5);
+        LevelTimer sw = stopwatch(S, level, 5);
         if (c == 0) // :656-659
           MGX_TRY(smoother_apply(S->smooth[level], S->solution_update[level], S->defect[level], false));
         else
@@ -3707,7 +3640,7 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
         {
           // residual and restriction in one pass of the cell loop: t only carries the partial sums
           // of brick-surface DoFs between the colour launches, the residual is never stored
-          Stopwatch           sw(S, level, 0);
+          LevelTimer sw = stopwatch(S, level, 0);
           mgx_operator_t      A = S->matrix[level];
           const TransferData &T = S->transfer[level]->d;
           // scratch form: the bricks store their restricted values block by block (one launch for the level), the
@@ -3744,11 +3677,11 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
       else
         {
           {
-            Stopwatch sw(S, level, 0);
+            LevelTimer sw = stopwatch(S, level, 0);
             MGX_TRY(mgx_vmult_residual(S->matrix[level], S->defect[level], S->solution_update[level], S->t[level])); // :663
           }
           {
-            Stopwatch sw(S, level, 1);
+            LevelTimer sw = stopwatch(S, level, 1);
             MGX_HIP(hipMemsetAsync(S->defect[level - 1], 0, number_size(S->vnumber) * nc, s));         // :667
             MGX_TRY(mgx_restrict_and_add(S->transfer[level], S->defect[level - 1], S->t[level], 1)); // :668
           }
@@ -3758,19 +3691,19 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
       // its own: the first post-smoothing iteration forms x + P x_coarse while it gathers x
       if (!fused_prolong_blocker(S->transfer[level], S->ctx->tun, S->smooth[level]->info.degree))
         {
-          Stopwatch sw(S, level, 5);
+          LevelTimer sw = stopwatch(S, level, 5);
           MGX_TRY(smoother_apply(S->smooth[level], S->solution_update[level], S->defect[level], true,
                                  S->solution_update[level - 1], S->transfer[level]->d.coarse_blocks, &S->transfer[level]->d));
         }
       else
         {
           {
-            Stopwatch sw(S, level, 2);
+            LevelTimer sw = stopwatch(S, level, 2);
             MGX_TRY(mgx_prolongate(S->transfer[level], S->solution_update[level], S->solution_update[level - 1], 1,
                                    1)); // :674
           }
           {
-            Stopwatch sw(S, level, 5);
+            LevelTimer sw = stopwatch(S, level, 5);
             MGX_TRY(smoother_apply(S->smooth[level], S->solution_update[level], S->defect[level], true)); // :678
           }
         }
@@ -3825,7 +3758,7 @@ int mgx_solver_solve_hooked(mgx_solver_t S, int do_analyze, double *reduction_ra
   else
   {
     // coarse solver invoked twice (multigrid_solver.h:397-402)
-    Stopwatch    sw(S, 0, 0);
+    LevelTimer sw = stopwatch(S, 0, 0);
     const size_t n0 = S->matrix[0]->d.n_dofs;
     launch_copy_cast(s, S->defect[0], S->vnumber, S->rhs[0], MGX_F64, n0);
     MGX_TRY(smoother_apply(S->smooth[0], S->t[0], S->defect[0], false));
@@ -3837,11 +3770,11 @@ int mgx_solver_solve_hooked(mgx_solver_t S, int do_analyze, double *reduction_ra
     {
       const size_t n = S->matrix[level]->d.n_dofs;
       {
-        Stopwatch sw(S, level, 3);
+        LevelTimer sw = stopwatch(S, level, 3);
         set_bc(S, level - 1, S->solution[level - 1], false); // :408-409
       }
       {
-        Stopwatch sw(S, level, 2);
+        LevelTimer sw = stopwatch(S, level, 2);
         MGX_TRY(mgx_prolongate(S->transfer_dp[level], S->solution[level], S->solution[level - 1], 0, 0)); // :415
       }
       double init_residual = 1.;
@@ -3852,11 +3785,11 @@ int mgx_solver_solve_hooked(mgx_solver_t S, int do_analyze, double *reduction_ra
         }
       set_bc(S, level, S->solution[level], true); // :427-428
       {
-        Stopwatch sw(S, level, 0);
+        LevelTimer sw = stopwatch(S, level, 0);
         MGX_TRY(mgx_vmult_residual(S->matrix_dp[level], S->rhs[level], S->solution[level], S->residual[level])); // :432
       }
       {
-        Stopwatch sw(S, level, 4);
+        LevelTimer sw = stopwatch(S, level, 4);
         launch_copy_cast(s, S->defect[level], S->vnumber, S->residual[level], MGX_F64, n); // :437
       }
       if (do_analyze)
@@ -3867,7 +3800,7 @@ int mgx_solver_solve_hooked(mgx_solver_t S, int do_analyze, double *reduction_ra
         }
       MGX_TRY(v_cycle(S, level, S->n_cycles)); // :451
       {
-        Stopwatch sw(S, level, 4);
+        LevelTimer sw = stopwatch(S, level, 4);
         launch_add_cast(s, S->solution[level], MGX_F64, S->solution_update[level], S->vnumber, n); // :456
       }
       if (do_analyze)
@@ -3932,59 +3865,24 @@ static int solve_cg_control(mgx_solver_t S, unsigned int max_iterations, double 
   launch_copy_cast(s, r, MGX_F64, S->rhs[lmax], MGX_F64, n);
   double res0 = 0;
   MGX_TRY(mgx_operator_l2_norm(A, r, &res0));
-  double       res = res0, rz = 0, rz_old = 0;
-  unsigned int it  = 0;
-  S->cg_history.assign(1, res0);
   // Mixed precision on one rank: the precision casts around the V-cycle (:503, :507) are folded into the CG
   // kernels next to them (mgx_vector.hip): the residual update writes the fp32 defect, the r.z product and the
   // direction update read the fp32 result of the cycle.  The values are those the two copies would produce.
   const bool mixed = S->vnumber == MGX_F32 && !ctx->has_comm;
-  float     *r32 = (float *)S->defect[lmax];
   if (mixed)
-    launch_copy_cast(s, r32, MGX_F32, r, MGX_F64, n);
-  while (res > abs_tol && res > reduction * res0 && it < max_iterations)
-    {
-      ++it;
-      rz_old = rz;
-      if (mixed)
-        {
-          MGX_TRY(v_cycle(S, lmax, 1)); // :505
-          const float *z32 = (const float *)S->solution_update[lmax];
-          launch_dot_f64_f32(s, r, z32, n, ctx->partial_dev, ctx->result_dev);
-          MGX_TRY(read_result(ctx, &rz));
-          if (it > 1)
-            launch_xpby_f64_f32(s, d, z32, rz / rz_old, n);
-          else
-            launch_copy_cast(s, d, MGX_F64, z32, MGX_F32, n);
-        }
-      else
-        {
-          MGX_TRY(mgx_solver_vmult(S, z, r));
-          MGX_TRY(dot(ctx, MGX_F64, r, z, n, &rz, A->plan.get()));
-          if (it > 1)
-            launch_xpby(s, MGX_F64, d, z, rz / rz_old, n);
-          else
-            launch_copy_cast(s, d, MGX_F64, z, MGX_F64, n);
-        }
-      MGX_TRY(mgx_vmult(A, h, d));
-      double dh = 0;
-      MGX_TRY(dot(ctx, MGX_F64, d, h, n, &dh, A->plan.get()));
-      if (mixed)
-        launch_cg_update_f32copy(s, x, r, d, h, rz / dh, n, r32, ctx->partial_dev, ctx->result_dev);
-      else
-      launch_cg_update(s, MGX_F64, x, r, d, h, rz / dh, n, ctx->partial_dev, ctx->result_dev);
-      if (ctx->has_comm)
-        MGX_TRY(dot(ctx, MGX_F64, r, r, n, &res, A->plan.get()));
-      else
-        MGX_TRY(read_result(ctx, &res));
-      res = std::sqrt(res);
-      S->cg_history.push_back(res);
-    }
-  if (iterations)
-    *iterations = it;
-  if (reduction_rate)
-    *reduction_rate = it > 0 ? std::pow(res / res0, 1. / it) : 1.; // :491-492
-  if (it >= max_iterations)
+    launch_copy_cast(s, S->defect[lmax], MGX_F32, r, MGX_F64, n);
+  const float *z32 = mixed ? (const float *)S->solution_update[lmax] : nullptr;
+  const auto   v_cycle_dot = [&](double *rz) {
+    MGX_TRY(mixed ? v_cycle(S, lmax, 1) : mgx_solver_vmult(S, z, r)); // :505
+    if (!mixed)
+      return dot(ctx, MGX_F64, r, z, n, rz, A->plan.get());
+    launch_dot_f64_f32(s, r, z32, n, ctx->partial_dev, ctx->result_dev);
+    return read_result(ctx, rz);
+  };
+  CGOps<decltype(v_cycle_dot)> ops{A, x, r, z, d, h, v_cycle_dot, mixed ? (float *)S->defect[lmax] : nullptr, z32};
+  krylov::SolveResult R;
+  MGX_TRY(krylov::solve(ops, res0, max_iterations, abs_tol, reduction, &S->cg_history, R, iterations, reduction_rate));
+  if (R.iterations >= max_iterations || R.above_tolerance) // (above: a step that broke down ended the iteration)
     return fail(MGX_ERR_NOT_CONVERGED, not_converged);
   return MGX_OK;
 }
@@ -4007,10 +3905,10 @@ int mgx_solver_solve_cg_control(mgx_solver_t S, unsigned int max_iterations, dou
                           "mgx_solver_solve_cg_control: no convergence within max_iterations");
 }
 
-/* MultigridSolver::vmult_with_residual_update (multigrid_solver.h:516-619); out3 (may be NULL)
- * additionally receives residual.residual after the update */
-static int residual_update(mgx_solver_t S, double *residual, double *update, double factor, double out[2], double *rr)
+/* MultigridSolver::vmult_with_residual_update (multigrid_solver.h:516-619) */
+int mgx_solver_vmult_with_residual_update(mgx_solver_t S, double *residual, double *update, double factor, double out[2])
 {
+  MGX_REQUIRE(S && residual && update && out && residual != update, "mgx_solver_vmult_with_residual_update: bad argument");
   const int      lmax = S->n_levels - 1;
   mgx_operator_t A    = S->matrix[lmax];
   mgx_context_t  ctx  = S->ctx;
@@ -4026,26 +3924,10 @@ static int residual_update(mgx_solver_t S, double *residual, double *update, dou
       MGX_TRY(A->mem.alloc(&A->cg_partials, 4 * (size_t)(1u << 16)));
       MGX_TRY(A->mem.alloc(&A->cg_result, 4));
     }
-  const size_t n_free = n - A->d.n_constrained;
   launch_residual_pre(s, S->vnumber, S->defect[lmax], residual, update, factor, n); // :527-534
   MGX_TRY(v_cycle(S, lmax, 1));                                                      // :538
-  const uint32_t used =
-    launch_residual_post(s, S->vnumber, S->solution_update[lmax], residual, update, factor, n_free, n, A->cg_partials);
-  launch_reduce4(s, A->cg_partials, used, nullptr, A->cg_result);
-  double h[4];
-  MGX_HIP(hipMemcpyAsync(h, A->cg_result, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  MGX_HIP(hipStreamSynchronize(s));
-  out[0] = h[0];
-  out[1] = h[1];
-  if (rr)
-    *rr = h[2];
-  return MGX_OK;
-}
-
-int mgx_solver_vmult_with_residual_update(mgx_solver_t S, double *residual, double *update, double factor, double out[2])
-{
-  MGX_REQUIRE(S && residual && update && out && residual != update, "mgx_solver_vmult_with_residual_update: bad argument");
-  return residual_update(S, residual, update, factor, out, nullptr);
+  return residual_update_finish(s, S->vnumber, S->solution_update[lmax], residual, update, factor, n - A->d.n_constrained, n,
+                                A->cg_partials, A->cg_result, out);
 }
 
 /* PCG with the matrix-vector product merged with the vector updates (mgx_vmult_with_cg_update):

@@ -7,9 +7,9 @@
 #include "mgx_device_memory.hpp"
 #include "mgx_dg_host.hpp"
 #include "mgx_internal.hpp"
+#include "mgx_krylov.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <memory>
 #include <string>
@@ -62,28 +62,6 @@ struct mgx_dg_operator_s
   double   origin[3]     = {0, 0, 0};
 };
 
-// MultigridSolverDG (common/multigrid_solver_dg.h:55-747): the DG level on top of an FE_Q hierarchy
-struct mgx_dg_solver_s
-{
-  mgx_context_t     ctx = nullptr;
-  mgx::DeviceArena  mem{"mgx_dg_solver"};
-  mgx_dg_operator_t A = nullptr, A_dp = nullptr;
-  mgx_solver_t      cfe = nullptr;
-  int               degree = 0, number = MGX_F32;
-  size_t            n = 0;      // owned DoFs
-  size_t            n_vec = 0;  // entries of a vector: owned cells, then ghost cells
-  mgx_operator_t    fe = nullptr; // finest FE_Q operator (interface sum of the restricted defect)
-  bool              decomposed = false;
-  mgx_smoother_info info{};
-  void             *defect = nullptr, *t = nullptr, *update = nullptr, *old = nullptr; // V-cycle number type
-  void             *P1 = nullptr;                                                      // device, V-cycle number type
-  const uint32_t   *idx27 = nullptr;
-  uint32_t          n_cells = 0, n_cg = 0;
-  bool              cg_eight_colours = false; // cells c, c + 8, ... of the FE_Q level share no DoF
-  void             *cg_defect = nullptr, *cg_update = nullptr; // the FE_Q solver's finest-level vectors
-  double           *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr; // PCG, fp64
-};
-
 // one step of a DG level hierarchy (mgx_dg_transfer.hip).  A mesh step (MGTransferMatrixFree between two DG levels):
 // coarse_degree == fine_degree, a group is a coarse cell with its 2^dim children.  A degree step on one mesh:
 // coarse_degree < fine_degree, a group is a cell, no children
@@ -101,6 +79,37 @@ struct DGLevelStep
   bool                identity = false;   // children[c][k] == 2^dim c + k (checked at creation): the table is not read
   void               *m1d      = nullptr; // device, number type: [2][(p+1)^2], or [(pf+1)][(pc+1)]
   std::vector<double> m1d_host;
+};
+
+// a DG level of either multigrid solver: operator, smoother and the vectors of the V-cycle
+struct DGLevel
+{
+  mgx_dg_operator_t  A = nullptr;
+  const DGLevelStep *step = nullptr; // plain solver: from the level below (null on level 0), a mesh refinement or a degree raise
+  size_t             n = 0;          // owned DoFs
+  size_t             n_vec = 0;      // entries of a vector: owned cells, then the ghost cells of a decomposed mesh
+  mgx_smoother_info  info{};
+  void              *defect = nullptr, *t = nullptr, *update = nullptr, *old = nullptr; // V-cycle number type
+  double            *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr;             // finest level: the outer CG, fp64
+  double             times[6] = {0, 0, 0, 0, 0, 0};                                     // timings[level] of the reference
+};
+
+// MultigridSolverDG (common/multigrid_solver_dg.h:55-747): the DG level on top of an FE_Q hierarchy
+struct mgx_dg_solver_s
+{
+  mgx_context_t     ctx = nullptr;
+  mgx::DeviceArena  mem{"mgx_dg_solver"};
+  DGLevel           level;
+  mgx_dg_operator_t A_dp = nullptr;
+  mgx_solver_t      cfe = nullptr;
+  int               degree = 0, number = MGX_F32;
+  mgx_operator_t    fe = nullptr; // finest FE_Q operator (interface sum of the restricted defect)
+  bool              decomposed = false;
+  void             *P1 = nullptr; // device, V-cycle number type
+  const uint32_t   *idx27 = nullptr;
+  uint32_t          n_cells = 0, n_cg = 0;
+  bool              cg_eight_colours = false; // cells c, c + 8, ... of the FE_Q level share no DoF
+  void             *cg_defect = nullptr, *cg_update = nullptr; // the FE_Q solver's finest-level vectors
 };
 
 // the two public handles of a step
@@ -121,23 +130,13 @@ struct mgx_dg_degree_transfer_s : DGLevelStep
 // MultigridSolverDGPlain (common/multigrid_solver_dg_plain.h:55-595)
 struct mgx_dg_plain_solver_s
 {
-  struct Level
-  {
-    mgx_dg_operator_t A = nullptr;
-    const DGLevelStep *step = nullptr; // from the level below (null on level 0): a mesh refinement or a degree raise
-    size_t            n = 0;
-    mgx_smoother_info info{};
-    void             *defect = nullptr, *t = nullptr, *update = nullptr, *old = nullptr; // V-cycle number type
-    double            times[6] = {0, 0, 0, 0, 0, 0};                                     // timings[level] of the reference
-  };
-  mgx_context_t      ctx = nullptr;
-  mgx::DeviceArena   mem{"mgx_dg_plain_solver"};
-  std::vector<Level> level;
-  mgx_dg_operator_t  A_dp = nullptr;
-  int                number = MGX_F32;
-  double            *r = nullptr, *z = nullptr, *d = nullptr, *h = nullptr; // PCG, fp64
-  double            *partials = nullptr, *sums = nullptr;                   // vmult_with_residual_update
-  bool               timed = false;
+  mgx_context_t        ctx = nullptr;
+  mgx::DeviceArena     mem{"mgx_dg_plain_solver"};
+  std::vector<DGLevel> level;
+  mgx_dg_operator_t    A_dp = nullptr;
+  int                  number = MGX_F32;
+  double              *partials = nullptr, *sums = nullptr; // vmult_with_residual_update
+  bool                 timed = false;
 };
 
 // conjugate gradients on the DG operator alone, preconditioned by the inverse lumped mass (solver_dg/program.cc:134-148,
@@ -892,11 +891,6 @@ int mgx_dg_compute_l2_error(mgx_dg_operator_t op, const void *vec, const mgx_dg_
 namespace
 {
   // over the first n (owned) entries
-  int dg_dot(mgx_context_t ctx, size_t n, int number, const void *x, const void *y, double *out)
-  {
-    return mgx::dot_owned_prefix(ctx, number, x, y, n, out);
-  }
-
   int dg_norm(mgx_context_t ctx, size_t n, int number, const void *x, double *out)
   {
     MGX_TRY(mgx::dot_owned_prefix(ctx, number, x, x, n, out));
@@ -904,95 +898,89 @@ namespace
     return MGX_OK;
   }
 
-  // SolverCG with ReductionControl(100, 1e-16, tolerance) and zero start on the fp64 operator A_dp, as both multigrid
-  // solvers run it: n owned entries, solution_bytes cleared in the solution, r / z / d / h four fp64 vectors of the
-  // solver, precondition(z, r): z = M^-1 r; `name` heads the message when the iteration does not converge
+  // The four steps of a CG iteration (mgx_krylov.hpp) on a DG operator, over its n owned entries: x (null: none), r, z,
+  // d, h vectors of A's number type, precondition(z, r): z = M^-1 r
   template <typename Preconditioner>
-  int dg_pcg(mgx_context_t ctx, mgx_dg_operator_t A_dp, size_t n, size_t solution_bytes, double *r, double *z, double *d, double *h,
-             Preconditioner precondition, double tolerance, const double *rhs, double *solution, unsigned *iterations,
-             double *reduction_rate, const char *name)
+  struct DGCGOps
   {
-    hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
-    MGX_HIP(hipMemsetAsync(solution, 0, solution_bytes, s));
-    MGX_TRY(mgx_copy_cast(ctx, r, MGX_F64, rhs, MGX_F64, n));
-    double res0 = 0, res = 0, rz = 0, rz_old = 0;
-    MGX_TRY(dg_norm(ctx, n, MGX_F64, r, &res0));
-    res         = res0;
-    unsigned it = 0;
-    while (res > std::max(1e-16, tolerance * res0) && it < 100)
-      {
-        ++it;
-        MGX_TRY(precondition(z, r));
-        rz_old = rz;
-        MGX_TRY(dg_dot(ctx, n, MGX_F64, r, z, &rz));
-        if (it > 1)
-          MGX_TRY(mgx_sadd(ctx, MGX_F64, d, rz / rz_old, 1.0, z, n));
-        else
-          MGX_TRY(mgx_copy_cast(ctx, d, MGX_F64, z, MGX_F64, n));
-        MGX_TRY(mgx_dg_vmult(A_dp, h, d));
-        double dh = 0;
-        MGX_TRY(dg_dot(ctx, n, MGX_F64, d, h, &dh));
-        const double alpha = rz / dh;
-        MGX_TRY(mgx_sadd(ctx, MGX_F64, solution, 1.0, alpha, d, n));
-        MGX_TRY(mgx_sadd(ctx, MGX_F64, r, 1.0, -alpha, h, n));
-        MGX_TRY(dg_norm(ctx, n, MGX_F64, r, &res));
-      }
-    if (iterations)
-      *iterations = it;
-    if (reduction_rate)
-      *reduction_rate = it ? std::pow(res / res0, 1.0 / it) : 1.0;
-    return res > std::max(1e-16, tolerance * res0) ? dg_fail(MGX_ERR_NOT_CONVERGED, std::string(name) + ": 100 iterations") : MGX_OK;
+    mgx_context_t     ctx;
+    mgx_dg_operator_t A;
+    size_t            n;
+    void             *x, *r, *z, *d, *h;
+    Preconditioner    precondition;
+    int precondition_dot(double *rz)
+    {
+      MGX_TRY(precondition(z, r));
+      return mgx::dot_owned_prefix(ctx, A->number, r, z, n, rz);
+    }
+    int direction(double beta, bool first) { return first ? mgx_copy_cast(ctx, d, A->number, z, A->number, n) : mgx_sadd(ctx, A->number, d, beta, 1.0, z, n); }
+    int vmult_dot(double *dh)
+    {
+      MGX_TRY(mgx_dg_vmult(A, h, d));
+      return mgx::dot_owned_prefix(ctx, A->number, d, h, n, dh);
+    }
+    int update(double alpha, double *res)
+    {
+      if (x)
+        MGX_TRY(mgx_sadd(ctx, A->number, x, 1.0, alpha, d, n));
+      MGX_TRY(mgx_sadd(ctx, A->number, r, 1.0, -alpha, h, n));
+      return dg_norm(ctx, n, A->number, r, res);
+    }
+  };
+
+  // SolverCG with ReductionControl(100, 1e-16, tolerance) and zero start on the fp64 operator A_dp, on the fp64 vectors of a
+  // solver's finest level v; precondition(z, r): z = M^-1 r; `name` heads the message when the residual stays above the tolerance
+  template <typename Preconditioner>
+  int dg_solve_cg(mgx_context_t ctx, mgx_dg_operator_t A_dp, const DGLevel &v, Preconditioner precondition, double tolerance,
+                  const double *rhs, double *solution, unsigned *iterations, double *reduction_rate, const char *name)
+  {
+    MGX_HIP(hipMemsetAsync(solution, 0, 8 * v.n_vec, (hipStream_t)mgx_context_stream(ctx)));
+    MGX_TRY(mgx_copy_cast(ctx, v.r, MGX_F64, rhs, MGX_F64, v.n));
+    double res0 = 0;
+    MGX_TRY(dg_norm(ctx, v.n, MGX_F64, v.r, &res0));
+    DGCGOps<Preconditioner>  ops{ctx, A_dp, v.n, solution, v.r, v.z, v.d, v.h, precondition};
+    mgx::krylov::SolveResult R;
+    MGX_TRY(mgx::krylov::solve(ops, res0, 100, 1e-16, tolerance, nullptr, R, iterations, reduction_rate));
+    return R.above_tolerance ? dg_fail(MGX_ERR_NOT_CONVERGED, std::string(name) + ": 100 iterations") : MGX_OK;
   }
 
   // PreconditionChebyshev<LaplaceOperatorCompactCombine, Vector, JacobiTransformed>: vmult (zero start) and
   // step, through the merged operation (deal.II hands iteration index 0 / 1, then k + 1 / k + 2)
   // (update and old trade places with every step, as the reference swaps its two vectors)
-  int dg_smoother_apply(mgx_dg_operator_t A, const mgx_smoother_info &I, const void *defect, void *&update, void *&old,
-                        bool is_step)
+  int dg_smoother_apply(DGLevel &L, bool is_step)
   {
-    int index;
-    if (!is_step)
-      {
-        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, 0, 0., 1. / I.theta, update, old));
-        index = 1;
-      }
-    else
-      {
-        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, 1, 0., 1. / I.theta, update, old));
-        std::swap(update, old);
-        index = 2;
-      }
+    const mgx_smoother_info      &I = L.info;
+    mgx::krylov::ChebyshevFactors F(I);
+    int                           index = is_step ? 2 : 1;
+    MGX_TRY(mgx_dg_vmult_with_chebyshev_update(L.A, L.defect, is_step ? 1 : 0, 0., F.first(), L.update, L.old));
+    if (is_step)
+      std::swap(L.update, L.old);
     if (I.degree < 2 || std::fabs(I.delta) < 1e-40)
       return MGX_OK;
-    double rhok = I.delta / I.theta;
-    const double sigma = I.theta / I.delta;
     for (int k = 0; k < I.degree - 1; ++k, ++index)
       {
-        const double rhokp = 1. / (2. * sigma - rhok);
-        const double f1 = rhokp * rhok, f2 = 2. * rhokp / I.delta;
-        rhok = rhokp;
-        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(A, defect, (unsigned)index, f1, f2, update, old));
-        std::swap(update, old);
+        double f1, f2;
+        F.next(k, f1, f2);
+        MGX_TRY(mgx_dg_vmult_with_chebyshev_update(L.A, L.defect, (unsigned)index, f1, f2, L.update, L.old));
+        std::swap(L.update, L.old);
       }
     return MGX_OK;
   }
 
-  int dg_smoother_apply(mgx_dg_solver_t S, bool is_step) { return dg_smoother_apply(S->A, S->info, S->defect, S->update, S->old, is_step); }
-
   // PreconditionChebyshev::initialize -> estimate_eigenvalues for a DG operator with JacobiTransformed
   // (multigrid_solver_dg.h:293-303, multigrid_solver_dg_plain.h:192-213): at most max_its iterations of CG
-  // preconditioned with JacobiTransformed on v_i = (global index of i mod 11) - mean, stopped at a residual of 1e-10;
-  // lambda_max = 1.2 x the largest Ritz value.  smoothing_range > 1: [lambda_max / range, lambda_max]; otherwise
-  // [min(0.9 lambda_max, lambda_min), lambda_max].  degree < 0 (numbers::invalid_unsigned_int): Varga's estimate of the
-  // degree that reduces the error by smoothing_range.  r, z, d, h: four vectors of the operator, overwritten;
-  // cell_global_id: host, may be null.  A step whose d.A d or r.z is not a positive finite number ends the estimate
-  // with the Ritz values collected so far (fp32 on a level that CG has already solved to rounding).
-  int dg_smoother_initialize(mgx_context_t ctx, mgx_dg_operator_t A, const uint32_t *cell_global_id, void *r, void *z, void *d,
-                             void *h, int max_its, double smoothing_range, int degree, mgx_smoother_info &I)
+  // preconditioned with JacobiTransformed on v_i = (global index of i mod 11) - mean, as mgx_krylov.hpp runs them
+  // (lanczos_estimate with the dense solver up to 64 rows; chebyshev_interval for smoothing_range and degree).  The
+  // level's own vectors carry the iteration -- they are free until the first cycle -- and are zero again afterwards;
+  // cell_global_id: host, may be null.
+  int dg_smoother_initialize(mgx_context_t ctx, DGLevel &L, const uint32_t *cell_global_id, int max_its, double smoothing_range,
+                             int degree)
   {
-    hipStream_t  s      = (hipStream_t)mgx_context_stream(ctx);
-    const size_t n      = (size_t)mgx_dg_operator_n_dofs(A);
-    const int    number = A->number;
+    mgx_dg_operator_t A      = L.A;
+    void             *r      = L.t;
+    hipStream_t       s      = (hipStream_t)mgx_context_stream(ctx);
+    const size_t      n      = L.n;
+    const int         number = A->number;
     double       ng     = (double)n; // global number of DoFs
     MGX_TRY(mgx::allreduce_sum(ctx, &ng, 1));
     const uint64_t ngl  = (uint64_t)(ng + 0.5);
@@ -1006,72 +994,38 @@ namespace
       launch_start_vector(s, number, r, cell_id, A->n_cells, (uint32_t)(n / A->n_cells), mean);
       MGX_HIP(hipStreamSynchronize(s));
     }
-    std::vector<double> diag, off;
-    double              res = 0, rz = 0, rz_old = 0, alpha = 0, alpha_old = 0, beta = 0;
+    double res = 0;
     MGX_TRY(dg_norm(ctx, n, number, r, &res));
-    int it = 0;
-    while (it < max_its && res > 1e-10)
-      {
-        rz_old = rz;
-        MGX_TRY(mgx_dg_jacobi_vmult(A, z, r));
-        MGX_TRY(dg_dot(ctx, n, number, r, z, &rz));
-        if (!(rz > 0.) || !std::isfinite(rz))
-          break;
-        ++it;
-        if (it > 1)
-          {
-            beta = rz / rz_old;
-            MGX_TRY(mgx_sadd(ctx, number, d, beta, 1.0, z, n));
-          }
-        else
-          MGX_TRY(mgx_copy_cast(ctx, d, number, z, number, n));
-        MGX_TRY(mgx_dg_vmult(A, h, d));
-        double dh = 0;
-        MGX_TRY(dg_dot(ctx, n, number, d, h, &dh));
-        if (!(dh > 0.) || !std::isfinite(dh))
-          {
-            --it;
-            break;
-          }
-        alpha_old = alpha;
-        alpha     = rz / dh;
-        MGX_TRY(mgx_sadd(ctx, number, r, 1.0, -alpha, h, n));
-        MGX_TRY(dg_norm(ctx, n, number, r, &res));
-        if (it == 1)
-          diag.push_back(1. / alpha);
-        else
-          {
-            off.push_back(std::sqrt(beta) / alpha_old);
-            diag.push_back(1. / alpha + beta / alpha_old);
-          }
-      }
-    I.cg_iterations = it;
-    if (diag.empty())
-      I.lambda_min = I.lambda_max = 1.;
-    else if (diag.size() <= 64)
-      {
-        const int           m = (int)diag.size();
-        std::vector<double> Tm((size_t)m * m, 0.0), lam, V;
-        for (int i = 0; i < m; ++i)
-          {
-            Tm[i * m + i] = diag[i];
-            if (i + 1 < m)
-              Tm[i * m + i + 1] = Tm[(i + 1) * m + i] = off[i];
-          }
-        sym_eig(m, Tm, lam, V);
-        I.lambda_min = lam.front();
-        I.lambda_max = 1.2 * lam.back();
-      }
-    else // (the Jacobi sweeps above cost m^3 each: bisection on the tridiagonal matrix for a long Lanczos run)
-      {
-        double lo = 0, hi = 0;
-        off.push_back(0.);
-        mgx::tridiag_extreme_eigenvalues((int)diag.size(), diag.data(), off.data(), lo, hi);
-        I.lambda_min = lo;
-        I.lambda_max = 1.2 * hi;
-      }
-    mgx::chebyshev_interval(smoothing_range, degree, I);
+    const auto jacobi = [A](void *z, const void *r) { return mgx_dg_jacobi_vmult(A, z, r); };
+    DGCGOps<decltype(jacobi)> ops{ctx, A, n, nullptr, r, L.update, L.old, L.defect, jacobi};
+    MGX_TRY(mgx::krylov::lanczos_estimate(ops, res, max_its, mgx::krylov::RitzRule{sym_eig}, L.info));
+    mgx::krylov::chebyshev_interval(smoothing_range, degree, L.info);
+    for (void *v : {L.defect, L.t, L.update, L.old})
+      MGX_HIP(hipMemsetAsync(v, 0, dg_nsz(number) * L.n_vec, s));
     return MGX_OK;
+  }
+
+  // operator, lengths and the zeroed vectors of a level; finest: those of the outer CG too
+  int dg_level_allocate(mgx::DeviceArena &mem, DGLevel &L, mgx_dg_operator_t A, bool finest, hipStream_t s)
+  {
+    L.A     = A;
+    L.n     = (size_t)mgx_dg_operator_n_dofs(A);
+    L.n_vec = (size_t)mgx_dg_operator_vector_size(A);
+    for (void **v : {&L.defect, &L.t, &L.update, &L.old})
+      MGX_TRY(mem.zeros(v, dg_nsz(A->number) * L.n_vec, s));
+    if (finest)
+      for (double **v : {&L.r, &L.z, &L.d, &L.h})
+        MGX_TRY(mem.zeros(v, L.n_vec, s));
+    return MGX_OK;
+  }
+
+  // vmult of a solver (multigrid_solver_dg.h:433-436, _dg_plain.h:327-331): cast the source in, one cycle, cast the update out
+  template <typename Cycle>
+  int dg_level_vmult(mgx_context_t ctx, DGLevel &top, Cycle cycle, double *dst, const double *src)
+  {
+    MGX_TRY(mgx_copy_cast(ctx, top.defect, top.A->number, src, MGX_F64, top.n));
+    MGX_TRY(cycle());
+    return mgx_copy_cast(ctx, dst, MGX_F64, top.update, top.A->number, top.n);
   }
 
   // vmult_residual_and_restrict_to_cg (laplace_operator_dg.h:853-861, action 1 :1798-1819): cg = sum over the cells of
@@ -1080,7 +1034,7 @@ namespace
   int dg_residual_and_restrict(mgx_dg_solver_t S, void *cg, const void *rhs, const void *lhs)
   {
     hipStream_t       s  = (hipStream_t)mgx_context_stream(S->ctx);
-    mgx_dg_operator_t op = S->A;
+    mgx_dg_operator_t op = S->level.A;
     MGX_HIP(hipMemsetAsync(cg, 0, dg_nsz(S->number) * S->n_cg, s));
     if (op->n_ghost > 0)
       MGX_TRY(update_ghosts(op, const_cast<void *>(lhs)));
@@ -1111,24 +1065,25 @@ namespace
   int dg_v_cycle(mgx_dg_solver_t S)
   {
     hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
-    MGX_TRY(dg_smoother_apply(S, false));
+    DGLevel    &L = S->level;
+    MGX_TRY(dg_smoother_apply(L, false));
     // vmult_residual_and_restrict_to_cg (:616-618)
     if (!mgx::context_tunables(S->ctx).dg_unmerged_restrict)
-      MGX_TRY(dg_residual_and_restrict(S, S->cg_defect, S->defect, S->update));
+      MGX_TRY(dg_residual_and_restrict(S, S->cg_defect, L.defect, L.update));
     else
       {
-        MGX_TRY(mgx_dg_vmult_residual(S->A, S->t, S->defect, S->update));
+        MGX_TRY(mgx_dg_vmult_residual(L.A, L.t, L.defect, L.update));
         MGX_HIP(hipMemsetAsync(S->cg_defect, 0, dg_nsz(S->number) * S->n_cg, s));
-        mgx::launch_dg_cg_transfer(s, S->number, S->degree, false, S->cg_defect, S->t, S->idx27, S->n_cells, S->P1,
+        mgx::launch_dg_cg_transfer(s, S->number, S->degree, false, S->cg_defect, L.t, S->idx27, S->n_cells, S->P1,
                                    S->cg_eight_colours);
         if (S->decomposed) // FE_Q DoFs on a rank interface collect the contributions of all sharers
           MGX_TRY(mgx_exchange_add(S->fe, S->cg_defect));
       }
     MGX_TRY(mgx_solver_v_cycle(S->cfe)); // :622
     // prolongate_add_cg_to_dg (:625; laplace_operator_dg.h:1863-1894)
-    mgx::launch_dg_cg_transfer(s, S->number, S->degree, true, S->update, S->cg_update, S->idx27, S->n_cells, S->P1);
+    mgx::launch_dg_cg_transfer(s, S->number, S->degree, true, L.update, S->cg_update, S->idx27, S->n_cells, S->P1);
     MGX_HIP(hipGetLastError());
-    return dg_smoother_apply(S, true); // :629
+    return dg_smoother_apply(L, true); // :629
   }
 } // namespace
 
@@ -1161,13 +1116,10 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
                                              "operator's cells, degree and number type");
   std::unique_ptr<mgx_dg_solver_s, int (*)(mgx_dg_solver_t)> S(new mgx_dg_solver_s, mgx_dg_solver_destroy);
   S->ctx = ctx;
-  S->A = A;
   S->A_dp = Ad;
   S->cfe = desc->cfe;
   S->degree = A->degree;
   S->number = A->number;
-  S->n = (size_t)mgx_dg_operator_n_dofs(A);
-  S->n_vec = (size_t)mgx_dg_operator_vector_size(A);
   S->fe = fe;
   S->decomposed = A->n_ghost > 0;
   if (A->n_ghost != Ad->n_ghost)
@@ -1196,16 +1148,8 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
           }
     S->cg_eight_colours = ok && nc < 0x80000000u;
   }
-  hipStream_t  s  = (hipStream_t)mgx_context_stream(ctx);
-  const size_t vb = dg_nsz(S->number) * S->n_vec;
-  for (void **v : {&S->defect, &S->t, &S->update, &S->old})
-    {
-      MGX_TRY(S->mem.zeros(v, vb, s));
-    }
-  for (double **v : {&S->r, &S->z, &S->d, &S->h})
-    {
-      MGX_TRY(S->mem.zeros(v, S->n_vec, s));
-    }
+  hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
+  MGX_TRY(dg_level_allocate(S->mem, S->level, A, true, s));
   {
     const int n1 = S->degree + 1;
     MGX_TRY(S->mem.upload_as(S->number, &S->P1, A->h.P1.data(), (size_t)n1 * n1));
@@ -1227,14 +1171,8 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
   // smooth_dg.initialize (multigrid_solver_dg.h:293-303): eigenvalue estimate by 15 iterations of
   // CG preconditioned with JacobiTransformed on v_i = (i mod 11) - mean, lambda_max = 1.2 x the
   // largest Ritz value, range 20
-  {
-    // (the level vectors are free until the first cycle)
-    MGX_TRY(dg_smoother_initialize(ctx, A, desc->cell_global_id, S->t, S->update, S->old, S->defect, 15, 20., desc->degree_pre,
-                                   S->info));
-    for (void *v : {S->defect, S->t, S->update, S->old})
-      MGX_HIP(hipMemsetAsync(v, 0, vb, s));
-    MGX_HIP(hipStreamSynchronize(s));
-  }
+  MGX_TRY(dg_smoother_initialize(ctx, S->level, desc->cell_global_id, 15, 20., desc->degree_pre));
+  MGX_HIP(hipStreamSynchronize(s));
   *out = S.release();
   return MGX_OK;
 }
@@ -1252,7 +1190,7 @@ int mgx_dg_solver_destroy(mgx_dg_solver_t S)
 int mgx_dg_solver_smoother_info(mgx_dg_solver_t S, mgx_smoother_info *info)
 {
   MGX_REQUIRE(S && info, "mgx_dg_solver_smoother_info: null argument");
-  *info = S->info;
+  *info = S->level.info;
   return MGX_OK;
 }
 
@@ -1284,9 +1222,7 @@ int mgx_dg_prolongate_add_cg_to_dg(mgx_dg_solver_t S, void *dg_dst, const void *
 int mgx_dg_solver_vmult(mgx_dg_solver_t S, double *dst, const double *src)
 {
   MGX_REQUIRE(S && dst && src, "mgx_dg_solver_vmult: null argument");
-  MGX_TRY(mgx_copy_cast(S->ctx, S->defect, S->number, src, MGX_F64, S->n)); // multigrid_solver_dg.h:433
-  MGX_TRY(dg_v_cycle(S));
-  return mgx_copy_cast(S->ctx, dst, MGX_F64, S->update, S->number, S->n);       // :436
+  return dg_level_vmult(S->ctx, S->level, [S] { return dg_v_cycle(S); }, dst, src);
 }
 
 int mgx_dg_solver_solve_cg(mgx_dg_solver_t S, double tolerance, const double *rhs, double *solution,
@@ -1294,8 +1230,9 @@ int mgx_dg_solver_solve_cg(mgx_dg_solver_t S, double tolerance, const double *rh
 {
   MGX_REQUIRE(S && rhs && solution, "mgx_dg_solver_solve_cg: null argument");
   // preconditioner = one DG V-cycle (multigrid_solver_dg.h:410-424)
-  return dg_pcg(S->ctx, S->A_dp, S->n, 8 * S->n_vec, S->r, S->z, S->d, S->h, [S](double *z, const double *r) { return mgx_dg_solver_vmult(S, z, r); },
-                tolerance, rhs, solution, iterations, reduction_rate, "mgx_dg_solver_solve_cg");
+  const auto v_cycle = [S](void *z, const void *r) { return mgx_dg_solver_vmult(S, (double *)z, (const double *)r); };
+  return dg_solve_cg(S->ctx, S->A_dp, S->level, v_cycle, tolerance, rhs, solution, iterations, reduction_rate,
+                     "mgx_dg_solver_solve_cg");
 }
 
 } // extern "C"
@@ -1348,65 +1285,38 @@ namespace
     return MGX_OK;
   }
 
-  // one part of a V-cycle, timed when the solver's timings are on (print_wall_times of the reference: host timers
-  // around synchronised parts -- for diagnosis, the parts no longer overlap their launches)
-  struct PlainTimer
-  {
-    mgx_dg_plain_solver_t S;
-    double               *slot;
-    std::chrono::steady_clock::time_point t0;
-    PlainTimer(mgx_dg_plain_solver_t solver, double *where)
-      : S(solver)
-      , slot(where)
-    {
-      if (S->timed)
-        {
-          (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
-          t0 = std::chrono::steady_clock::now();
-        }
-    }
-    ~PlainTimer()
-    {
-      if (S->timed)
-        {
-          (void)hipStreamSynchronize((hipStream_t)mgx_context_stream(S->ctx));
-          *slot += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-    }
-  };
-
   // v_cycle(level, 1) (multigrid_solver_dg_plain.h:456-496): defect[level] in, update[level] out
   int plain_v_cycle(mgx_dg_plain_solver_t S, int l)
   {
-    hipStream_t                   s = (hipStream_t)mgx_context_stream(S->ctx);
-    mgx_dg_plain_solver_s::Level &L = S->level[l];
+    hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
+    DGLevel    &L = S->level[l];
     if (l == 0) // coarse = the level-0 smoother's vmult (:462)
       {
-        PlainTimer timer(S, &L.times[0]);
+        mgx::LevelTimer timer(S->ctx, S->timed, L.times, l, 0);
         L.times[1] += 1;
-        return dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, false);
+        return dg_smoother_apply(L, false);
       }
-    mgx_dg_plain_solver_s::Level &C = S->level[l - 1];
+    DGLevel &C = S->level[l - 1];
     {
-      PlainTimer timer(S, &L.times[5]);
-      MGX_TRY(dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, false)); // :472
+      mgx::LevelTimer timer(S->ctx, S->timed, L.times, l, 5);
+      MGX_TRY(dg_smoother_apply(L, false)); // :472
     }
     {
-      PlainTimer timer(S, &L.times[0]);
+      mgx::LevelTimer timer(S->ctx, S->timed, L.times, l, 0);
       MGX_TRY(mgx_dg_vmult_residual(L.A, L.t, L.defect, L.update)); // :478
     }
     {
-      PlainTimer timer(S, &L.times[1]);
+      mgx::LevelTimer timer(S->ctx, S->timed, L.times, l, 1);
       MGX_HIP(hipMemsetAsync(C.defect, 0, dg_nsz(S->number) * C.n, s)); // :482
       MGX_TRY(step_apply(L.step, false, C.defect, L.t, "mgx_dg_plain_solver: restriction")); // :483
     }
     MGX_TRY(plain_v_cycle(S, l - 1));
     {
-      PlainTimer timer(S, &L.times[2]);
+      mgx::LevelTimer timer(S->ctx, S->timed, L.times, l, 2);
       MGX_TRY(step_apply(L.step, true, L.update, C.update, "mgx_dg_plain_solver: prolongation")); // :489
     }
-    PlainTimer timer(S, &L.times[5]);
-    return dg_smoother_apply(L.A, L.info, L.defect, L.update, L.old, true); // :493
+    mgx::LevelTimer timer(S->ctx, S->timed, L.times, l, 5);
+    return dg_smoother_apply(L, true); // :493
   }
 
   // the step from level l - 1 to level l: whichever of desc->transfer[l - 1] and desc->degree_transfer[l - 1] is set
@@ -1431,34 +1341,20 @@ namespace
     hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
     for (int l = 0; l <= L; ++l)
       {
-        mgx_dg_plain_solver_s::Level &lv = S->level[l];
-        lv.A    = desc->matrix[l];
-        lv.step = l > 0 ? step_of(desc, l) : nullptr;
-        lv.n    = (size_t)mgx_dg_operator_n_dofs(lv.A);
-        for (void **v : {&lv.defect, &lv.t, &lv.update, &lv.old})
-          {
-            MGX_TRY(S->mem.zeros(v, dg_nsz(S->number) * lv.n, s));
-          }
-      }
-    for (double **v : {&S->r, &S->z, &S->d, &S->h})
-      {
-        MGX_TRY(S->mem.zeros(v, S->level[L].n, s));
+        MGX_TRY(dg_level_allocate(S->mem, S->level[l], desc->matrix[l], l == L, s));
+        S->level[l].step = l > 0 ? step_of(desc, l) : nullptr;
       }
     MGX_TRY(S->mem.alloc(&S->partials, 4 * (size_t)mgx::kDotBlocks));
     MGX_TRY(S->mem.alloc(&S->sums, 4));
     // smooth[level].initialize (:192-213)
     for (int l = 0; l <= L; ++l)
       {
-        mgx_dg_plain_solver_s::Level &lv  = S->level[l];
-        const uint32_t               *ids = desc->cell_global_id ? desc->cell_global_id[l] : nullptr;
+        DGLevel        &lv  = S->level[l];
+        const uint32_t *ids = desc->cell_global_id ? desc->cell_global_id[l] : nullptr;
         if (l > 0)
-          MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect, 15, 20.,
-                                         l < L ? desc->degree_pre : std::max(1, desc->degree_pre - 1), lv.info));
+          MGX_TRY(dg_smoother_initialize(ctx, lv, ids, 15, 20., l < L ? desc->degree_pre : std::max(1, desc->degree_pre - 1)));
         else
-          MGX_TRY(dg_smoother_initialize(ctx, lv.A, ids, lv.t, lv.update, lv.old, lv.defect,
-                                         (int)std::min<size_t>(lv.n, 0x7FFFFFFF), 1e-5, -1, lv.info));
-        for (void *v : {lv.defect, lv.t, lv.update, lv.old})
-          MGX_HIP(hipMemsetAsync(v, 0, dg_nsz(S->number) * lv.n, s));
+          MGX_TRY(dg_smoother_initialize(ctx, lv, ids, (int)std::min<size_t>(lv.n, 0x7FFFFFFF), 1e-5, -1));
       }
     MGX_HIP(hipStreamSynchronize(s));
     *out = S.release();
@@ -1683,10 +1579,7 @@ int mgx_dg_plain_solver_smoother_info(mgx_dg_plain_solver_t S, int level, mgx_sm
 int mgx_dg_plain_solver_vmult(mgx_dg_plain_solver_t S, double *dst, const double *src)
 {
   MGX_REQUIRE(S && dst && src, "mgx_dg_plain_solver_vmult: null argument");
-  mgx_dg_plain_solver_s::Level &top = S->level.back();
-  MGX_TRY(mgx_copy_cast(S->ctx, top.defect, S->number, src, MGX_F64, top.n)); // multigrid_solver_dg_plain.h:327
-  MGX_TRY(plain_v_cycle(S, (int)S->level.size() - 1));
-  return mgx_copy_cast(S->ctx, dst, MGX_F64, top.update, S->number, top.n);   // :331
+  return dg_level_vmult(S->ctx, S->level.back(), [S] { return plain_v_cycle(S, (int)S->level.size() - 1); }, dst, src);
 }
 
 int mgx_dg_plain_solver_solve_cg(mgx_dg_plain_solver_t S, double tolerance, const double *rhs, double *solution,
@@ -1694,29 +1587,21 @@ int mgx_dg_plain_solver_solve_cg(mgx_dg_plain_solver_t S, double tolerance, cons
 {
   MGX_REQUIRE(S && rhs && solution, "mgx_dg_plain_solver_solve_cg: null argument");
   // preconditioner = one V-cycle (multigrid_solver_dg_plain.h:303-317)
-  const size_t n = S->level.back().n;
-  return dg_pcg(S->ctx, S->A_dp, n, 8 * n, S->r, S->z, S->d, S->h, [S](double *z, const double *r) { return mgx_dg_plain_solver_vmult(S, z, r); },
-                tolerance, rhs, solution, iterations, reduction_rate, "mgx_dg_plain_solver_solve_cg");
+  const auto v_cycle = [S](void *z, const void *r) { return mgx_dg_plain_solver_vmult(S, (double *)z, (const double *)r); };
+  return dg_solve_cg(S->ctx, S->A_dp, S->level.back(), v_cycle, tolerance, rhs, solution, iterations, reduction_rate,
+                     "mgx_dg_plain_solver_solve_cg");
 }
 
 int mgx_dg_plain_solver_vmult_with_residual_update(mgx_dg_plain_solver_t S, double *residual, double *update, double factor,
                                                    double sums[2])
 {
   MGX_REQUIRE(S && residual && update && sums && residual != update, "mgx_dg_plain_solver_vmult_with_residual_update: null or aliased argument");
-  hipStream_t                   s   = (hipStream_t)mgx_context_stream(S->ctx);
-  mgx_dg_plain_solver_s::Level &top = S->level.back();
+  hipStream_t s   = (hipStream_t)mgx_context_stream(S->ctx);
+  DGLevel    &top = S->level.back();
   mgx::launch_residual_pre(s, S->number, top.defect, residual, update, factor, top.n); // :353-358
   MGX_TRY(plain_v_cycle(S, (int)S->level.size() - 1));                                 // :362
   // :365-413 (no constrained rows in DG: every entry takes the V-cycle's value); block sums added in a fixed order
-  const uint32_t used = mgx::launch_residual_post(s, S->number, top.update, residual, update, factor, top.n, top.n, S->partials);
-  mgx::launch_reduce4(s, S->partials, used, nullptr, S->sums);
-  MGX_HIP(hipGetLastError());
-  double h[4];
-  MGX_HIP(hipMemcpyAsync(h, S->sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  MGX_HIP(hipStreamSynchronize(s));
-  sums[0] = h[0];
-  sums[1] = h[1];
-  return MGX_OK;
+  return mgx::residual_update_finish(s, S->number, top.update, residual, update, factor, top.n, top.n, S->partials, S->sums, sums);
 }
 
 int mgx_dg_plain_solver_enable_timings(mgx_dg_plain_solver_t S, int on)
@@ -1741,13 +1626,13 @@ int mgx_dg_plain_solver_get_timings(mgx_dg_plain_solver_t S, double *times)
 int mgx_dg_plain_solver_do_matvec(mgx_dg_plain_solver_t S)
 {
   MGX_REQUIRE(S, "mgx_dg_plain_solver_do_matvec: null solver");
-  return mgx_dg_vmult(S->A_dp, S->h, S->d); // matrix_dg_dp.vmult(residual, solution), :435
+  return mgx_dg_vmult(S->A_dp, S->level.back().h, S->level.back().d); // matrix_dg_dp.vmult(residual, solution), :435
 }
 
 int mgx_dg_plain_solver_do_matvec_smoother(mgx_dg_plain_solver_t S)
 {
   MGX_REQUIRE(S, "mgx_dg_plain_solver_do_matvec_smoother: null solver");
-  mgx_dg_plain_solver_s::Level &top = S->level.back();
+  DGLevel &top = S->level.back();
   return mgx_dg_vmult(top.A, top.t, top.defect); // matrix[maxlevel].vmult, :444
 }
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -237,9 +238,23 @@ namespace mgx
   int  dot_owned_prefix(struct ::mgx_context_s *ctx, int number, const void *x, const void *y, size_t n, double *out);
   bool context_has_comm(struct ::mgx_context_s *ctx);
   const Tunables &context_tunables(struct ::mgx_context_s *ctx);
-  // smallest and largest eigenvalue of the symmetric tridiagonal matrix (diagonal d[n], off-diagonal e[n], e[n-1]
-  // unused), by bisection -- the Lanczos matrix of an eigenvalue estimate
-  void tridiag_extreme_eigenvalues(int n, const double *d, const double *e, double &lo, double &hi);
+  // One part of a V-cycle of a multigrid solver, timed into times[part] of its level when `timed` (print_wall_times of
+  // the reference: host timers around synchronised parts -- for diagnosis, the parts no longer overlap their launches);
+  // ranges: a roctx range named after the part and the level around it, where the context's options ask for ranges
+  struct LevelTimer
+  {
+    struct ::mgx_context_s               *ctx;
+    double                               *slot; // null: not timed
+    bool                                  ranges;
+    std::chrono::steady_clock::time_point t0;
+    LevelTimer(struct ::mgx_context_s *ctx, bool timed, double *times, int level, int part, bool with_ranges = false);
+    ~LevelTimer();
+    LevelTimer(const LevelTimer &) = delete;
+  };
+  // the part of vmult_with_residual_update after the V-cycle (multigrid_solver.h:543-619): the post kernel on the cycle's
+  // result, the block sums added in a fixed order, and the first two of the four sums on the host
+  int residual_update_finish(hipStream_t s, int number, const void *cycle_result, double *residual, double *update, double factor,
+                             size_t n_free, size_t n, double *partials, double *sums_dev, double out[2]);
 
   // records the message mgx_last_error() returns on the calling thread; returns `code` (used by the
   // translation units that implement parts of the C ABI outside mgx_api.cpp)
@@ -687,10 +702,6 @@ namespace mgx
     bool     launch_dg_l2_error(hipStream_t s, const DGRhsOperands &op, const DGFunctionArgs &u, const void *vec, double *partials);
     uint32_t rhs_grid(int p, uint32_t n_cells, int dim); // workgroups of either launch
   } // namespace dg
-  // Ritz values -> Chebyshev interval (PreconditionChebyshev::estimate_eigenvalues): given info.lambda_min / lambda_max,
-  // sets degree (degree < 0: Varga's estimate for eps = smoothing_range), delta and theta; returns the lower end a =
-  // lambda_max / smoothing_range (smoothing_range > 1) or min(0.9 lambda_max, lambda_min)
-  double chebyshev_interval(double smoothing_range, int degree, mgx_smoother_info &info);
   void launch_zero_head_copy_tail(hipStream_t s, int number, void *dst, const void *src, uint32_t n_head, uint32_t n);
   void launch_scatter_map(hipStream_t s, int number, void *dst, const void *src, const uint32_t *map,
                           const uint8_t *mask, uint32_t n);
