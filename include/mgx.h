@@ -48,10 +48,10 @@ extern "C" {
 #define MGX_MAX_DEGREE 9              /* poisson_cube/program.cc:69 */
 
 typedef struct mgx_context_s  *mgx_context_t;
-typedef struct mgx_operator_s *mgx_operator_t;  /* LaplaceOperator<3,p,number> of one level */
+typedef struct mgx_operator_s *mgx_operator_t;  /* LaplaceOperator<dim,p,number> of one level, dim = 3 or 2 */
 typedef struct mgx_smoother_s *mgx_smoother_t;  /* PreconditionChebyshev<LaplaceOperator,...> */
 typedef struct mgx_transfer_s *mgx_transfer_t;  /* one level pair of MGTransferMatrixFree */
-typedef struct mgx_solver_s   *mgx_solver_t;    /* MultigridSolver<3,p,Number,double> */
+typedef struct mgx_solver_s   *mgx_solver_t;    /* MultigridSolver<dim,p,Number,double> */
 
 const char *mgx_last_error(void);
 const char *mgx_version(void);
@@ -249,6 +249,26 @@ typedef struct
    * transposes).  Host pointer, copied (in the operator's number type).  When given, coef[] is
    * ignored. */
   const double *coef_q;
+  /* Dimension of the mesh: 0 or 3 -- hexahedra, everything above as written; 2 -- quadrilaterals (one rank, per-cell
+   * kernels only); anything else: MGX_ERR_INVALID_ARGUMENT.  With dim == 2 the fields above mean the same one dimension
+   * down:
+   *   idx27, idx27_plain  9 entries per cell, idx[9*cell + 3*cy+cx] = first DoF of that entity (the rule of
+   *                       vector_access_reduced.h with two codes): a vertex 1 DoF, the interior of an x-line (cx = 1,
+   *                       cy = 0 or 2) and of a y-line (cx = 0 or 2, cy = 1) p-1 contiguous DoFs, the quad interior
+   *                       (p-1)^2 DoFs with x fastest
+   *   coef[0..2]          [xx, yy, xy]; a nonzero xy selects the full-tensor form.  coef[3..5] are not read
+   *   coef_q              coef_q[(cell*3 + c)*(p+1)^2 + q], c over [xx, yy, xy], q = qy (p+1) + qx
+   *   brick_colour        ignored (no brick schedule in two dimensions)
+   *   exchange            must be NULL: several ranks are refused with MGX_ERR_UNSUPPORTED, as is a context with a
+   *                       communicator
+   * shape_values, colloc_grad, qweights, constrained and global_index are what they are in three dimensions.  A
+   * two-dimensional level adds its cells up through the ordered assembly or, beyond 2^26 local values or from
+   * "cell_colour_min" cells on, colour by colour (four colours on a structured mesh): never with atomics, every result is
+   * bitwise reproducible.  Refused on such an operator with MGX_ERR_UNSUPPORTED: mgx_compute_residual,
+   * mgx_solver_compute_rhs, the solution-dependent coefficients (mgx_operator_enable_coefficient_update[_q],
+   * mgx_evaluate_coefficient, mgx_compute_nonlinear_residual, mgx_interpolate_to_coarse, mgx_solver_update_coefficient),
+   * mgx_solver_set_agglomeration and mgx_dg_solver_create over such a hierarchy. */
+  int dim;
 } mgx_operator_desc;
 
 /* LaplaceOperator::initialize + evaluate_coefficient (laplace_operator.h:184-220, 357-432) */
@@ -373,6 +393,11 @@ typedef struct
    * restriction uses owner weights instead: a shared fine DoF is restricted, with weight 1, by the
    * one parent (of the lowest rank that holds it) owning its entity.  Same R = P^T. */
   const uint8_t *weight_shift;
+  /* Two dimensions (the dimension is that of the two operators, which must agree): children[4*parent + c] with
+   * c = x + 2y, weight_shift[9*parent + e] (NULL: from the local tables).  The embedding is applied in its dense form,
+   * correct whether it is symmetric or not; prolongation: every fine entry written by one designated parent, restriction:
+   * parents colour by colour with plain adds -- no atomics.  Multiplicities that are no powers of two (three or five
+   * cells around a vertex) are refused with MGX_ERR_UNSUPPORTED. */
 } mgx_transfer_desc;
 int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_transfer_desc *desc,
                         mgx_transfer_t *transfer);
@@ -434,7 +459,7 @@ int mgx_solver_reset_smoother(mgx_solver_t solver, int level, double smoothing_r
 int mgx_solver_update_coefficient(mgx_solver_t solver, int law, const double *state_fine);
 int mgx_solver_n_levels(mgx_solver_t solver);
 int mgx_solver_get_operator(mgx_solver_t solver, int level, int fp64, mgx_operator_t *op);
-/* device pointer to an operator's compressed index table [n_cells][27] and its sizes */
+/* device pointer to an operator's compressed index table [n_cells][27] ([n_cells][9] in two dimensions) and its sizes */
 int mgx_operator_device_indices(mgx_operator_t op, const uint32_t **idx27, uint32_t *n_cells, uint32_t *n_dofs,
                                 int *degree);
 /* polynomial type of the smoothers above the coarsest level (which keeps the first kind with the

@@ -1,0 +1,92 @@
+/*
+ * mgx_square.h -- host-side discretisation provider for poisson_cube with dimension = 2: what deal.II's
+ * Triangulation<2> / DoFHandler<2> / MatrixFree<2> / FE_Q<2> would hand to LaplaceOperator<2,p,number> and
+ * MultigridSolver<2,p,...>.  The two-dimensional counterpart of mgx_cube.h, one rank only; it feeds the descriptors
+ * of mgx.h with dim = 2.
+ *
+ *   mesh            a box of roots[0] x roots[1] square coarse cells of size h0 from (origin, origin), refined
+ *                   n_refine times: level l has roots[d] 2^l cells per direction
+ *   cell order      coarse cells lexicographic (x fastest), Morton order inside a coarse cell: the children of cell
+ *                   c are 4c .. 4c+3 with child = x + 2y
+ *   DoF numbering   first touch, entity by entity in cell order (contiguous per entity, x fastest inside the quad
+ *                   interior: the contract of the 9-entry compressed index table), Dirichlet DoFs last
+ *   problem         u = sin(3 pi x) sin(3 pi y), f = 2 (3 pi)^2 u, coefficient 1, Dirichlet values on all four sides
+ *                   (poisson_cube/program.cc with dimension = 2)
+ *   jacobian        optional constant 2 x 2 matrix A of an affine map x = (origin, origin) + A X of the whole box
+ *                   (sheared or anisotropic box): the cells of level l have the Jacobian h_l A, the operator the one
+ *                   tensor det(A) (A^T A)^-1 = [xx, yy, xy] per mesh -- the full-tensor form when xy != 0 -- and u, f
+ *                   are those of the physical coordinates
+ */
+#ifndef MGX_SQUARE_H
+#define MGX_SQUARE_H
+
+#include "mgx.h"
+#include "mgx_cube.h" /* mgx_cube_solver: the hierarchy objects of a solver */
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct mgx_square_s *mgx_square_t;
+
+typedef struct
+{
+  int           degree, n_refine;
+  int           roots[2];
+  double        origin, h0;
+  const double *jacobian; /* 2 x 2 row-major, NULL: identity */
+} mgx_square_box_desc;
+
+/* the square [-0.9, 1]^2 of poisson_cube with n_subdiv coarse cells per direction */
+int mgx_square_create(int degree, int n_subdiv, int n_refine, mgx_square_t *square);
+int mgx_square_create_box(const mgx_square_box_desc *desc, mgx_square_t *square);
+int mgx_square_destroy(mgx_square_t square);
+
+int      mgx_square_n_levels(mgx_square_t square);
+int      mgx_square_degree(mgx_square_t square);
+uint32_t mgx_square_n_cells(mgx_square_t square, int level);
+uint32_t mgx_square_n_dofs(mgx_square_t square, int level);
+uint32_t mgx_square_n_constrained(mgx_square_t square, int level);
+void     mgx_square_cells_per_dim2(mgx_square_t square, int level, uint32_t cells[2]);
+double   mgx_square_cell_size(mgx_square_t square, int level);
+
+/* tables (host memory owned by the square) */
+const uint32_t *mgx_square_idx9(mgx_square_t square, int level);       /* [n_cells][9], constrained entities invalid */
+const uint32_t *mgx_square_idx9_plain(mgx_square_t square, int level); /* [n_cells][9] */
+const uint32_t *mgx_square_constrained(mgx_square_t square, int level);
+const uint32_t *mgx_square_children(mgx_square_t square, int level);     /* level >= 1: [n_cells(level-1)][4] */
+const uint8_t  *mgx_square_weight_shift(mgx_square_t square, int level); /* level >= 1: [n_cells(level-1)][9] */
+const uint32_t *mgx_square_cell_coords(mgx_square_t square, int level);  /* [n_cells][2] */
+/* dof -> lexicographic grid id gy Gx + gx, G_d = N_d p + 1 */
+const uint32_t *mgx_square_dof_grid(mgx_square_t square, int level);
+const double   *mgx_square_shape_values(mgx_square_t square);
+const double   *mgx_square_colloc_grad(mgx_square_t square);
+const double   *mgx_square_qweights(mgx_square_t square);
+const double   *mgx_square_qpoints(mgx_square_t square);
+const double   *mgx_square_gll(mgx_square_t square);
+const double   *mgx_square_prolong_1d(mgx_square_t square);
+
+/* rhs = int f phi - int grad u_bc . K grad phi, assembled on the host at the first call; boundary values */
+const double   *mgx_square_rhs(mgx_square_t square, int level);
+uint32_t        mgx_square_bc_count(mgx_square_t square, int level);
+const uint32_t *mgx_square_bc_index(mgx_square_t square, int level);
+const double   *mgx_square_bc_value(mgx_square_t square, int level);
+/* L2 error of a host copy of solution[level] (boundary values inserted), with the Gauss rule of the operator */
+double mgx_square_l2_error(mgx_square_t square, int level, const double *solution_host);
+/* the generator of mgx_cube_seeded_vector, keyed by the grid id */
+int mgx_square_seeded_vector(mgx_square_t square, int level, uint64_t seed, double *out_host);
+
+/* fills desc for LaplaceOperator<2,p,number> on `level` (dim = 2; pointers stay owned by the square) */
+int mgx_square_operator_desc(mgx_square_t square, int level, int number, mgx_operator_desc *desc);
+/* the per-(cell, q) tensor equivalent to the descriptor's coef: out[n_cells][3][(p+1)^2] = coef[c] w_qx w_qy */
+int mgx_square_coef_q(mgx_square_t square, int level, double *out);
+/* everything MultigridSolver's constructor builds, on the device (mgx_cube_solver_create in two dimensions);
+ * per_point != 0: the level operators in the per-(cell, q) form with mgx_square_coef_q.  Released with
+ * mgx_cube_solver_destroy. */
+int mgx_square_solver_create(mgx_context_t ctx, mgx_square_t square, int vcycle_number, int degree_pre, int n_cycles,
+                             int per_point, mgx_cube_solver *out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

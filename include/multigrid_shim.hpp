@@ -242,6 +242,7 @@ namespace multigrid
       ctx_ = &ctx;
       mgx_operator_desc d;
       check(mgx_cube_operator_desc(disc.handle(), (int)level, number_id<number>::value, &d));
+      d.dim = 3; // (the shim is LaplaceOperator<3,p,number>)
       check(mgx_operator_create(ctx.handle(), &d, &h_));
       owned_ = true;
       desc_  = d; // (the tables stay owned by the discretisation)
@@ -304,6 +305,7 @@ namespace multigrid
       if (!owned_)
         throw MgxError(MGX_ERR_UNSUPPORTED, "evaluate_coefficient: operator is borrowed from a solver");
       mgx_operator_desc d = desc_;
+      d.dim               = 3;
       if (!merged_coefficient.empty())
         {
           if (merged_coefficient.size() != (std::size_t)d.n_cells * 6 * (fe_degree + 1) * (fe_degree + 1) * (fe_degree + 1))

@@ -625,6 +625,124 @@ class Cube:
         return (-0.9 if self.box_desc is None else self.box_desc["origin"]) + X
 
 
+class Square:
+    """Host-side discretisation of poisson_cube with dimension = 2 (include/mgx_square.h): what deal.II supplies for
+    LaplaceOperator<2,p,number> and MultigridSolver<2,p,...>.  One rank.  Method names are Cube's where they apply."""
+
+    size, rank, shell, box_desc, level_offset = 1, 0, None, None, 0
+
+    def __init__(self, degree, n_subdiv=1, n_refine=3, box=None, origin=-0.9, h0=None, jacobian=None):
+        """box=None: the square [-0.9,1]^2 with n_subdiv coarse cells per direction.  box=(sx,sy): a box of sx x sy
+        square coarse cells of size h0 from (origin, origin).  jacobian: constant 2 x 2 matrix of an affine map of the
+        whole box (a sheared or anisotropic box: the operator's one tensor [xx,yy,xy], the full-tensor form)."""
+        self.lib = _lib.load()
+        h = C.c_void_p()
+        if box is None:
+            box, h0 = (n_subdiv, n_subdiv), 1.9 / n_subdiv
+        self._jac = None if jacobian is None else np.ascontiguousarray(jacobian, dtype=np.float64).reshape(2, 2)
+        d = _lib.SquareBoxDesc(degree, n_refine, (C.c_int * 2)(*box), origin, 1.9 if h0 is None else h0,
+                               None if self._jac is None else self._jac.ctypes.data_as(_lib.f64p))
+        check(self.lib.mgx_square_create_box(C.byref(d), C.byref(h)))
+        self.h = h
+        self.degree = degree
+        self.n_levels = self.lib.mgx_square_n_levels(h)
+        self.max_level = self.n_levels - 1
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mgx_square_destroy(self.h)
+            self.h = None
+
+    def n_cells(self, l):
+        return self.lib.mgx_square_n_cells(self.h, l)
+
+    def n_dofs(self, l):
+        return self.lib.mgx_square_n_dofs(self.h, l)
+
+    def n_constrained(self, l):
+        return self.lib.mgx_square_n_constrained(self.h, l)
+
+    def cells_per_dim2(self, l):
+        a = (C.c_uint32 * 2)()
+        self.lib.mgx_square_cells_per_dim2(self.h, l, C.byref(a))
+        return tuple(a)
+
+    def cell_size(self, l):
+        return self.lib.mgx_square_cell_size(self.h, l)
+
+    _arr = Cube._arr
+
+    def idx9(self, l):
+        return self._arr("mgx_square_idx9", (self.n_cells(l), 9), l)
+
+    def idx9_plain(self, l):
+        return self._arr("mgx_square_idx9_plain", (self.n_cells(l), 9), l)
+
+    def constrained(self, l):
+        return self._arr("mgx_square_constrained", (self.n_constrained(l),), l)
+
+    def children(self, l):
+        return self._arr("mgx_square_children", (self.n_cells(l - 1), 4), l)
+
+    def weight_shift(self, l):
+        return self._arr("mgx_square_weight_shift", (self.n_cells(l - 1), 9), l)
+
+    def cell_coords(self, l):
+        return self._arr("mgx_square_cell_coords", (self.n_cells(l), 2), l)
+
+    def dof_grid(self, l):
+        return self._arr("mgx_square_dof_grid", (self.n_dofs(l),), l)
+
+    def shape_values(self):
+        n = self.degree + 1
+        return self._arr("mgx_square_shape_values", (n, n))
+
+    def colloc_grad(self):
+        n = self.degree + 1
+        return self._arr("mgx_square_colloc_grad", (n, n))
+
+    def qweights(self):
+        return self._arr("mgx_square_qweights", (self.degree + 1,))
+
+    def qpoints(self):
+        return self._arr("mgx_square_qpoints", (self.degree + 1,))
+
+    def gll(self):
+        return self._arr("mgx_square_gll", (self.degree + 1,))
+
+    def prolong_1d(self):
+        n = self.degree + 1
+        return self._arr("mgx_square_prolong_1d", (2 * n - 1, n))
+
+    def rhs(self, l):
+        return self._arr("mgx_square_rhs", (self.n_dofs(l),), l)
+
+    def bc(self, l):
+        n = self.lib.mgx_square_bc_count(self.h, l)
+        return self._arr("mgx_square_bc_index", (n,), l), self._arr("mgx_square_bc_value", (n,), l)
+
+    def l2_error(self, l, solution):
+        s = np.ascontiguousarray(solution, dtype=np.float64)
+        assert s.size == self.n_dofs(l)
+        return self.lib.mgx_square_l2_error(self.h, l, s.ctypes.data_as(_lib.f64p))
+
+    def seeded_vector(self, l, seed=42):
+        out = np.empty(self.n_dofs(l))
+        check(self.lib.mgx_square_seeded_vector(self.h, l, seed, out.ctypes.data_as(_lib.f64p)))
+        return out
+
+    def operator_desc(self, l, number=F64):
+        d = _lib.OperatorDesc()
+        check(self.lib.mgx_square_operator_desc(self.h, l, number, C.byref(d)))
+        return d
+
+    def coef_q(self, l):
+        """[n_cells, 3, (p+1)^2] the per-(cell, q) tensor equivalent to the one tensor of operator_desc (weight folded in)"""
+        out = np.empty((self.n_cells(l), 3, (self.degree + 1) ** 2))
+        check(self.lib.mgx_square_coef_q(self.h, l, out.ctypes.data_as(_lib.f64p)))
+        return out
+
+
 def _cell_dofs(idx27, p):
     """[n_cells, (p+1)^3] DoF of every node of every cell (x fastest) from a compressed index table without constrained
     entries (the addressing of read_dof_values_compressed, vector_access_reduced.h:153-229)"""
@@ -663,7 +781,10 @@ class LaplaceOperator:
         d = cube.operator_desc(level, number)
         if coef_q is not None:
             coef_q = np.ascontiguousarray(coef_q, dtype=np.float64)
-            assert coef_q.size == cube.n_cells(level) * 6 * (cube.degree + 1) ** 3
+            if isinstance(cube, Square):
+                assert coef_q.size == cube.n_cells(level) * 3 * (cube.degree + 1) ** 2
+            else:
+                assert coef_q.size == cube.n_cells(level) * 6 * (cube.degree + 1) ** 3
             d.coef_q = coef_q.ctypes.data_as(_lib.f64p)  # (copied by mgx_operator_create)
         return cls(ctx, d)
 
@@ -828,7 +949,8 @@ class MultigridSolver:
     `vcycle_number` is the template parameter Number (program.cc:76: float; BASELINE: double)."""
 
     def __init__(self, ctx, cube, degree_pre=3, degree_post=3, n_cycles=1, vcycle_number=F64, comm=None,
-                 polynomial="first_kind", agglomerate=True, device_rhs=False, general=False, jacobian=None, coef_q=None):
+                 polynomial="first_kind", agglomerate=True, device_rhs=False, general=False, jacobian=None, coef_q=None,
+                 per_point=False):
         """device_rhs: the right-hand sides are assembled on the GPU (mgx_solver_compute_rhs) instead of on the host.
         general: the hierarchy in the general branch of the operator for solution-dependent coefficients
         (mgx_cube_solver_create_general: one rank; zero right-hand sides, homogeneous boundary values), on a Cartesian
@@ -843,6 +965,22 @@ class MultigridSolver:
         self.vnumber = vcycle_number
         self.comm = comm
         self.s = _lib.CubeSolver()
+        self.coarse = None
+        if isinstance(cube, Square):
+            # MultigridSolver<2,p,...>: one rank, right-hand sides from the host; per_point: the operators in the
+            # per-(cell, q) form with the tensor of Square.coef_q
+            if comm is not None or agglomerate is not True or device_rhs or general or jacobian is not None or coef_q is not None:
+                raise ValueError("MultigridSolver on a Square: one rank, host right-hand sides, no general hierarchy "
+                                 "(comm, agglomerate, device_rhs, general, jacobian, coef_q are not accepted)")
+            self.jacobian = None
+            check(self.lib.mgx_square_solver_create(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles, int(bool(per_point)),
+                                                    C.byref(self.s)))
+            self.n_levels = self.s.n_levels
+            self.max_level = self.n_levels - 1
+            self.h = C.c_void_p(self.s.solver)
+            if polynomial != "first_kind":
+                check(self.lib.mgx_solver_set_polynomial_type(self.h, Chebyshev.POLYNOMIAL[polynomial]))
+            return
         if cube.size > 1:
             if comm is None:
                 raise ValueError("a decomposed cube needs a Communicator")

@@ -1,4 +1,4 @@
-"""ctypes declarations for libmgx.so (include/mgx.h, include/mgx_cube.h, include/mgx_dg.h).
+"""ctypes declarations for libmgx.so (include/mgx.h, include/mgx_cube.h, include/mgx_square.h, include/mgx_dg.h).
 
 The library is built in-tree by `__graft_entry__.build()` / `make -C multigrid_amd/csrc`.
 There is no CPU fallback: a missing library raises, and so does a missing HIP device at
@@ -43,12 +43,17 @@ class CubeBoxDesc(C.Structure):
                 ("geometry", C.c_int), ("problem", C.c_int)]
 
 
+class SquareBoxDesc(C.Structure):
+    _fields_ = [("degree", C.c_int), ("n_refine", C.c_int), ("roots", C.c_int * 2), ("origin", C.c_double),
+                ("h0", C.c_double), ("jacobian", C.POINTER(C.c_double))]
+
+
 class OperatorDesc(C.Structure):
     _fields_ = [("degree", C.c_int), ("number", C.c_int), ("n_cells", C.c_uint32), ("n_dofs", C.c_uint32),
                 ("idx27", u32p), ("idx27_plain", u32p), ("constrained", u32p), ("n_constrained", C.c_uint32),
                 ("coef", C.c_double * 6), ("shape_values", f64p), ("colloc_grad", f64p), ("qweights", f64p),
                 ("brick_colour", C.POINTER(C.c_uint8)), ("global_index", u32p),
-                ("exchange", C.POINTER(ExchangeDesc)), ("coef_q", f64p)]
+                ("exchange", C.POINTER(ExchangeDesc)), ("coef_q", f64p), ("dim", C.c_int)]
 
 
 class DGExchangeDesc(C.Structure):
@@ -269,6 +274,39 @@ SIGNATURES = {
     "mgx_cube_solver_create_general": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f64p, C.POINTER(f64p),
                                                  C.POINTER(CubeSolver)]),
     "mgx_cube_affine_metric": (C.c_int, [vp, C.c_int, f64p, f64p, f64p]),
+    # include/mgx_square.h
+    "mgx_square_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "mgx_square_create_box": (C.c_int, [C.POINTER(SquareBoxDesc), C.POINTER(vp)]),
+    "mgx_square_destroy": (C.c_int, [vp]),
+    "mgx_square_n_levels": (C.c_int, [vp]),
+    "mgx_square_degree": (C.c_int, [vp]),
+    "mgx_square_n_cells": (C.c_uint32, [vp, C.c_int]),
+    "mgx_square_n_dofs": (C.c_uint32, [vp, C.c_int]),
+    "mgx_square_n_constrained": (C.c_uint32, [vp, C.c_int]),
+    "mgx_square_cells_per_dim2": (None, [vp, C.c_int, C.POINTER(C.c_uint32 * 2)]),
+    "mgx_square_cell_size": (C.c_double, [vp, C.c_int]),
+    "mgx_square_idx9": (u32p, [vp, C.c_int]),
+    "mgx_square_idx9_plain": (u32p, [vp, C.c_int]),
+    "mgx_square_constrained": (u32p, [vp, C.c_int]),
+    "mgx_square_children": (u32p, [vp, C.c_int]),
+    "mgx_square_weight_shift": (C.POINTER(C.c_uint8), [vp, C.c_int]),
+    "mgx_square_cell_coords": (u32p, [vp, C.c_int]),
+    "mgx_square_dof_grid": (u32p, [vp, C.c_int]),
+    "mgx_square_shape_values": (f64p, [vp]),
+    "mgx_square_colloc_grad": (f64p, [vp]),
+    "mgx_square_qweights": (f64p, [vp]),
+    "mgx_square_qpoints": (f64p, [vp]),
+    "mgx_square_gll": (f64p, [vp]),
+    "mgx_square_prolong_1d": (f64p, [vp]),
+    "mgx_square_rhs": (f64p, [vp, C.c_int]),
+    "mgx_square_bc_count": (C.c_uint32, [vp, C.c_int]),
+    "mgx_square_bc_index": (u32p, [vp, C.c_int]),
+    "mgx_square_bc_value": (f64p, [vp, C.c_int]),
+    "mgx_square_l2_error": (C.c_double, [vp, C.c_int, f64p]),
+    "mgx_square_seeded_vector": (C.c_int, [vp, C.c_int, C.c_uint64, f64p]),
+    "mgx_square_operator_desc": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(OperatorDesc)]),
+    "mgx_square_coef_q": (C.c_int, [vp, C.c_int, f64p]),
+    "mgx_square_solver_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CubeSolver)]),
     # include/mgx_dg.h
     "mgx_dg_operator_create": (C.c_int, [vp, C.POINTER(DGOperatorDesc), C.POINTER(vp)]),
     "mgx_dg_operator_destroy": (C.c_int, [vp]),

@@ -856,6 +856,7 @@ int mgx::side_stream_end(mgx_context_t ctx)
 }
 
 int mgx::allreduce_sum(mgx_context_t ctx, double *values, int count) { return comm_allreduce(ctx, values, count); }
+int mgx::operator_dim(mgx_operator_t op) { return op->d.dim; }
 
 // x.y over the first n entries of two vectors whose leading part is owned by this rank without
 // duplicates (DG vectors: owned cells, then ghost cells), summed over the ranks
@@ -1209,6 +1210,21 @@ namespace
   {
     return (e % 3 == 1 ? p - 1 : 1) * ((e / 3) % 3 == 1 ? p - 1 : 1) * (e / 9 == 1 ? p - 1 : 1);
   }
+  // what depends on the dimension of a level (mgx_operator_desc::dim): entities per cell (e = cy 3 + cx in two
+  // dimensions, where entity_size holds as it stands), the entity that is the cell's interior, local values per cell,
+  // entries of the symmetric coefficient tensor
+  inline int    desc_dim(const mgx_operator_desc *desc) { return desc->dim == 2 ? 2 : 3; }
+  inline int    n_entities(int dim) { return dim == 2 ? 9 : 27; }
+  inline int    interior_entity(int dim) { return dim == 2 ? 4 : 13; }
+  inline size_t n_local_values(int dim, int p) { return dim == 2 ? (size_t)(p + 1) * (p + 1) : (size_t)(p + 1) * (p + 1) * (p + 1); }
+  inline int    n_tensor_entries(int dim) { return dim == 2 ? 3 : 6; }
+  // the entry points that exist in three dimensions only
+  inline int refuse_2d(const mgx::OperatorData &d, const char *who, const char *why)
+  {
+    if (d.dim != 2)
+      return MGX_OK;
+    return fail(MGX_ERR_UNSUPPORTED, std::string(who) + ": not on a two-dimensional operator (" + why + ")");
+  }
 
   // G = D S: derivative of the nodal basis at the quadrature points, G[q n + i], accumulated in R
   template <typename R>
@@ -1235,8 +1251,14 @@ namespace
     MGX_REQUIRE(desc->idx27 && desc->shape_values && desc->colloc_grad && desc->qweights,
                 "mgx_operator_create: missing table");
     MGX_REQUIRE(desc->n_constrained == 0 || desc->constrained, "mgx_operator_create: missing constrained list");
+    MGX_REQUIRE(desc->dim == 0 || desc->dim == 2 || desc->dim == 3, "mgx_operator_create: dim must be 2 or 3 (0: 3)");
+    if (desc->dim == 2 && desc->exchange)
+      return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_create: a two-dimensional operator with an exchange plan (one rank only)");
+    if (desc->dim == 2 && ctx->has_comm)
+      return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_create: a two-dimensional operator on a context with a communicator (one rank only)");
     const int    p         = desc->degree;
-    const size_t n_entries = 27 * (size_t)desc->n_cells;
+    const int    ne        = n_entities(desc_dim(desc));
+    const size_t n_entries = ne * (size_t)desc->n_cells;
     for (int pass = 0; pass < 2; ++pass)
       {
         const uint32_t *tab = pass == 0 ? desc->idx27 : desc->idx27_plain;
@@ -1247,14 +1269,17 @@ namespace
             const uint32_t b = tab[i];
             if (b == MGX_INVALID_INDEX)
               continue;
-            if ((uint64_t)b + (uint32_t)entity_size((int)(i % 27), p) > desc->n_dofs)
+            if ((uint64_t)b + (uint32_t)entity_size((int)(i % ne), p) > desc->n_dofs)
               return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: compressed index out of range");
           }
       }
     for (uint32_t i = 0; i < desc->n_constrained; ++i)
       if (desc->constrained[i] >= desc->n_dofs)
         return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_operator_create: constrained index out of range");
-    if (!desc->coef_q)
+    if (!desc->coef_q && desc->dim == 2) // [xx, yy, xy]
+      MGX_REQUIRE(desc->coef[0] > 0 && desc->coef[0] * desc->coef[1] - desc->coef[2] * desc->coef[2] > 0,
+                  "mgx_operator_create: the coefficient tensor is not positive definite");
+    else if (!desc->coef_q)
       {
         // the one coefficient tensor of an affine mesh (xx yy zz xy xz yz) must be positive definite
         const double *c  = desc->coef;
@@ -1357,7 +1382,8 @@ namespace
     nodal_gradient(op, G.data());
     MGX_TRY(op.mem.upload_as(d.number, &d.grad_1d, G.data(), G.size()));
     if (desc->coef_q)
-      MGX_TRY(op.mem.upload_as(d.number, &d.coef_q, desc->coef_q, (size_t)desc->n_cells * 6 * n * n * n));
+      MGX_TRY(op.mem.upload_as(d.number, &d.coef_q, desc->coef_q,
+                               (size_t)desc->n_cells * n_tensor_entries(d.dim) * n_local_values(d.dim, d.p)));
     return MGX_OK;
   }
 
@@ -1374,12 +1400,13 @@ namespace
     uint32_t              count[33] = {0};
     int                   n_colours = 0;
     // the entities whose first DoF is a key: all that carry DoFs but the cell's interior
-    auto is_key = [p](const uint32_t *ix, int e) { return e != 13 && entity_size(e, p) != 0 && ix[e] != MGX_INVALID_INDEX; };
+    const int ne = n_entities(d.dim), inside = interior_entity(d.dim);
+    auto is_key = [p, inside](const uint32_t *ix, int e) { return e != inside && entity_size(e, p) != 0 && ix[e] != MGX_INVALID_INDEX; };
     for (uint32_t c = 0; c < desc->n_cells; ++c)
       {
-        const uint32_t *ix   = desc->idx27 + 27 * (size_t)c;
+        const uint32_t *ix   = desc->idx27 + ne * (size_t)c;
         uint32_t        mask = 0;
-        for (int e = 0; e < 27; ++e)
+        for (int e = 0; e < ne; ++e)
           if (is_key(ix, e))
             mask |= used[ix[e]];
         int col = 0;
@@ -1390,7 +1417,7 @@ namespace
         colour[c] = (uint8_t)col;
         ++count[col];
         n_colours = std::max(n_colours, col + 1);
-        for (int e = 0; e < 27; ++e)
+        for (int e = 0; e < ne; ++e)
           if (is_key(ix, e))
             used[ix[e]] |= 1u << col;
       }
@@ -1404,7 +1431,7 @@ namespace
       order[fill[colour[c]]++] = c;
     d.n_cell_colours = n_colours;
     MGX_TRY(op.mem.upload(&d.cell_order, order));
-    MGX_TRACE("operator_create: general branch, %u cells in %d colours", desc->n_cells, n_colours);
+    MGX_TRACE("operator_create: %u cells in %d colours", desc->n_cells, n_colours);
     return MGX_OK;
   }
 
@@ -1559,18 +1586,20 @@ namespace
   {
     OperatorData &d = op.d;
     const int     p = d.p, n = p + 1;
-    const size_t  n3 = (size_t)n * n * n, n_local = n3 * desc->n_cells;
+    const size_t  n3 = n_local_values(d.dim, p), n_local = n3 * desc->n_cells;
     if (d.bricks.available() || d.cell_order || n_local > kAssemblyMaxEntries)
       return MGX_OK;
     std::vector<uint32_t> start((size_t)desc->n_dofs + 1, 0), pos;
+    // (two dimensions: the one plane k = 0 of a table with 9 entries per cell -- code and offset of k are zero)
+    const int nk = d.dim == 2 ? 1 : n, ne = n_entities(d.dim);
     auto for_each_local = [&](auto &&f) {
       for (uint32_t c = 0; c < desc->n_cells; ++c)
         {
-          const uint32_t *ix = desc->idx27 + 27 * (size_t)c;
-          for (int k = 0; k < n; ++k)
+          const uint32_t *ix = desc->idx27 + ne * (size_t)c;
+          for (int k = 0; k < nk; ++k)
             for (int j = 0; j < n; ++j)
               {
-                const int       cz = k == 0 ? 0 : (k == p ? 2 : 1), oz = cz == 1 ? k - 1 : 0;
+                const int       cz = (k == 0 || nk == 1) ? 0 : (k == p ? 2 : 1), oz = cz == 1 ? k - 1 : 0;
                 const int       cy = j == 0 ? 0 : (j == p ? 2 : 1), oy = cy == 1 ? j - 1 : 0;
                 const uint32_t *e  = ix + 3 * (3 * cz + cy);
                 const uint32_t  off = (uint32_t)((cy == 1 ? p - 1 : 1) * oz + oy);
@@ -1767,8 +1796,10 @@ int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_op
   op->constrained_last = constrained_are_last(desc);
   const Tunables &tun  = ctx->tun;
   const int       p = desc->degree, n = p + 1;
-  const size_t    n_entries = 27 * (size_t)desc->n_cells;
+  const int       dim = desc_dim(desc);
+  const size_t    n_entries = n_entities(dim) * (size_t)desc->n_cells;
   OperatorData   &d  = op->d;
+  d.dim            = dim;
   d.p              = p;
   d.number         = desc->number;
   d.n_cells        = desc->n_cells;
@@ -1779,7 +1810,7 @@ int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_op
   std::memcpy(op->S, desc->shape_values, sizeof(double) * n * n);
   std::memcpy(op->D, desc->colloc_grad, sizeof(double) * n * n);
   std::memcpy(op->w, desc->qweights, sizeof(double) * n);
-  d.full_tensor      = !desc->coef_q && (desc->coef[3] != 0. || desc->coef[4] != 0. || desc->coef[5] != 0.);
+  d.full_tensor      = !desc->coef_q && (dim == 2 ? desc->coef[2] != 0. : (desc->coef[3] != 0. || desc->coef[4] != 0. || desc->coef[5] != 0.));
   const bool general = d.full_tensor || desc->coef_q; // quadrature-point operation with the full tensor
   d.separable        = !tun.general_kernel && !general;
   d.cells_form       = tun.cells_form;
@@ -1796,14 +1827,22 @@ int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_op
   MGX_TRY(op->mem.alloc(&d.inv_diag, number_size(d.number) * d.n_dofs));
   if (general)
     MGX_TRY(upload_general_tables(*op, desc));
-  if (general && (desc->n_cells >= tun.cell_colour_min || (size_t)n * n * n * desc->n_cells > kAssemblyMaxEntries))
-    MGX_TRY(colour_cells(*op, desc));
+  // (two dimensions: every form, the separable one too -- a level without the ordered assembly runs colour by colour,
+  // never with atomics)
+  if ((general || dim == 2) &&
+      (desc->n_cells >= tun.cell_colour_min || n_local_values(dim, p) * desc->n_cells > kAssemblyMaxEntries))
+    {
+      MGX_TRY(colour_cells(*op, desc));
+      if (dim == 2 && !d.cell_order)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_create: a two-dimensional level that needs more than 32 cell colours "
+                                         "(and is too large for, or was told not to use, the ordered assembly)");
+    }
   // (builds without the cell-by-cell cross-check kernels schedule bricks only where the macro-element
   // kernel runs: separable operator, vector below the 4 GB of a buffer descriptor)
   const bool macro_covers = d.separable && (uint64_t)desc->n_dofs * number_size(d.number) < 0xFFFFFFF0ull;
-  if (!tun.no_bricks && !general && (MGX_CELLS_FORM ? (p <= 4 || d.separable) : macro_covers))
+  if (dim == 3 && !tun.no_bricks && !general && (MGX_CELLS_FORM ? (p <= 4 || d.separable) : macro_covers))
     MGX_TRY(build_brick_schedule(*op, desc, tun));
-  if (general && p == 4 && !desc->exchange && !tun.no_bricks && !tun.no_general_bricks && desc->n_dofs < 0x3FFFFFFFu &&
+  if (dim == 3 && general && p == 4 && !desc->exchange && !tun.no_bricks && !tun.no_general_bricks && desc->n_dofs < 0x3FFFFFFFu &&
       (uint64_t)desc->n_dofs * number_size(d.number) < 0xFFFFFFF0ull &&
       desc->n_cells / 64 >= tun.general_brick_min)
     MGX_TRY(build_general_brick_schedule(*op, desc));
@@ -2013,6 +2052,7 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
 {
   MGX_REQUIRE(op && dst, "mgx_compute_residual: null argument");
   MGX_REQUIRE(dst != src, "mgx_compute_residual: dst and src must not alias");
+  MGX_TRY(refuse_2d(op->d, "mgx_compute_residual", "right-hand sides of a two-dimensional problem are assembled on the host"));
   // (the boundary values are gathered through the table that also names the constrained DoFs)
   MGX_REQUIRE(op->d.idx27_plain, "mgx_compute_residual: the operator was created without idx27_plain");
   hipStream_t  s     = op->ctx->stream;
@@ -2046,6 +2086,7 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
 int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metric[6], double det_jacobian)
 {
   MGX_REQUIRE(op && metric, "mgx_operator_enable_coefficient_update: null argument");
+  MGX_TRY(refuse_2d(op->d, "mgx_operator_enable_coefficient_update", "no solution-dependent coefficients in two dimensions"));
   if (!op->d.coef_q)
     return fail(MGX_ERR_UNSUPPORTED,
                 "mgx_operator_enable_coefficient_update: the operator has no per-point coefficient (separable or "
@@ -2072,6 +2113,7 @@ int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metri
 int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *unit_q, const double *jxw_q)
 {
   MGX_REQUIRE(op && unit_q && jxw_q, "mgx_operator_enable_coefficient_update_q: null argument");
+  MGX_TRY(refuse_2d(op->d, "mgx_operator_enable_coefficient_update_q", "no solution-dependent coefficients in two dimensions"));
   if (!op->d.coef_q)
     return fail(MGX_ERR_UNSUPPORTED,
                 "mgx_operator_enable_coefficient_update_q: the operator has no per-point coefficient (separable or "
@@ -2115,6 +2157,7 @@ static int require_coefficient_update(mgx_operator_t op, int law, const char *wh
 int mgx_evaluate_coefficient(mgx_operator_t op, int law, const void *state)
 {
   MGX_REQUIRE(op && state, "mgx_evaluate_coefficient: null argument");
+  MGX_TRY(refuse_2d(op->d, "mgx_evaluate_coefficient", "no solution-dependent coefficients in two dimensions"));
   MGX_TRY(require_coefficient_update(op, law, "mgx_evaluate_coefficient"));
   launch_evaluate_coefficient(op->ctx->stream, op->d, op->d.coef_q, op->d.number, law == MGX_LAW_MINIMAL_SURFACE, op->metric,
                               op->det_jacobian, op->unit_q, op->jxw_q, state);
@@ -2128,9 +2171,8 @@ int mgx_operator_get_coefficient(mgx_operator_t op, const void **dptr, size_t *n
   MGX_REQUIRE(op && dptr && n, "mgx_operator_get_coefficient: null argument");
   if (!op->d.coef_q)
     return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_get_coefficient: the operator has no per-point coefficient");
-  const size_t np = (size_t)op->d.p + 1;
-  *dptr           = op->d.coef_q;
-  *n              = (size_t)op->d.n_cells * 6 * np * np * np;
+  *dptr = op->d.coef_q;
+  *n    = (size_t)op->d.n_cells * n_tensor_entries(op->d.dim) * n_local_values(op->d.dim, op->d.p);
   return MGX_OK;
 }
 
@@ -2138,6 +2180,7 @@ int mgx_compute_nonlinear_residual(mgx_operator_t op, int law, void *dst, const 
 {
   MGX_REQUIRE(op && dst && state, "mgx_compute_nonlinear_residual: null argument");
   MGX_REQUIRE(dst != state, "mgx_compute_nonlinear_residual: dst and state must not alias");
+  MGX_TRY(refuse_2d(op->d, "mgx_compute_nonlinear_residual", "no solution-dependent coefficients in two dimensions"));
   MGX_TRY(require_coefficient_update(op, law, "mgx_compute_nonlinear_residual"));
   hipStream_t s  = op->ctx->stream;
   const bool  ms = law == MGX_LAW_MINIMAL_SURFACE;
@@ -3108,6 +3151,115 @@ namespace
     else
       MGX_TRACE("transfer_create: fused prolongation yes (with a smoother of degree >= 1)");
   }
+  // Two dimensions (mgx_kernels_2d.hip): children in fours, weights and ownership over the 9 entities of a cell, the
+  // parents coloured for the restriction.  No patch table, no fused forms: the dense kernels serve every embedding.
+  int transfer_create_2d(mgx_operator_t coarse, mgx_operator_t fine, const mgx_transfer_desc *desc, mgx_transfer_t *out)
+  {
+    MGX_REQUIRE((uint64_t)coarse->d.n_cells * 4 == fine->d.n_cells,
+                "mgx_transfer_create: fine level must have 4 children per coarse cell (uniform refinement)");
+    const int      p    = coarse->d.p;
+    const uint32_t npar = coarse->d.n_cells, nfine = fine->d.n_cells;
+    {
+      // every fine cell is the child of exactly one parent: the prolongation writes every fine entry once
+      std::vector<uint8_t> seen(nfine, 0);
+      for (size_t i = 0; i < 4 * (size_t)npar; ++i)
+        {
+          if (desc->children[i] >= nfine)
+            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: child index out of range");
+          if (seen[desc->children[i]]++)
+            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: the children table names a fine cell twice");
+        }
+    }
+    std::unique_ptr<mgx_transfer_s, int (*)(mgx_transfer_t)> tr(new mgx_transfer_s, mgx_transfer_destroy);
+    tr->coarse   = coarse;
+    tr->fine     = fine;
+    tr->d.coarse = &coarse->d;
+    tr->d.fine   = &fine->d;
+    tr->d.n_cus  = context_cus(coarse->ctx);
+    MGX_TRY(tr->mem.upload(&tr->d.children, desc->children, 4 * (size_t)npar));
+    std::vector<uint32_t> idxf(9 * (size_t)nfine), idxc(9 * (size_t)npar);
+    MGX_HIP(hipMemcpy(idxf.data(), fine->d.idx27_plain, sizeof(uint32_t) * idxf.size(), hipMemcpyDeviceToHost));
+    MGX_HIP(hipMemcpy(idxc.data(), coarse->d.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
+    // weights 1 / multiplicity per patch entity e = cb 3 + ca, counted at a child vertex that lies in the entity (low
+    // side: child 0's low vertex, inside: the mid line = child 0's high vertex, high side: child 1's high vertex)
+    auto rep = [&](uint32_t pc, int e) {
+      const int      ca = e % 3, cb = e / 3;
+      const uint32_t fc = desc->children[4 * (size_t)pc + ((ca == 2) | ((cb == 2) << 1))];
+      return idxf[9 * (size_t)fc + 3 * (cb ? 2 : 0) + (ca ? 2 : 0)];
+    };
+    std::vector<uint8_t> cnt(fine->d.n_dofs, 0), shift(9 * (size_t)npar, 0);
+    for (uint32_t pc = 0; pc < npar; ++pc)
+      for (int e = 0; e < 9; ++e)
+        cnt[rep(pc, e)]++;
+    for (uint32_t pc = 0; pc < npar; ++pc)
+      for (int e = 0; e < 9; ++e)
+        {
+          const uint8_t c = cnt[rep(pc, e)];
+          if (c != 1 && c != 2 && c != 4)
+            return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: fine DoF multiplicities other than 1/2/4 (three or five "
+                                             "cells around a vertex) in two dimensions");
+          shift[9 * (size_t)pc + e] = c == 1 ? 0 : (c == 2 ? 1 : 2);
+        }
+    if (desc->weight_shift)
+      for (size_t i = 0; i < shift.size(); ++i)
+        {
+          if (desc->weight_shift[i] != shift[i]) // (one rank: the local count is the whole count)
+            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: inconsistent weight_shift");
+        }
+    MGX_TRY(tr->mem.upload(&tr->d.weight_shift, shift));
+    // ownership of the fine entities: the first cell in cell order that contains one writes it
+    std::vector<uint32_t> own(nfine, 0u);
+    {
+      std::vector<uint8_t> seen(fine->d.n_dofs, 0);
+      for (uint32_t c = 0; c < nfine; ++c)
+        for (int e = 0; e < 9; ++e)
+          if (entity_size(e, p) != 0 && !seen[idxf[9 * (size_t)c + e]])
+            {
+              seen[idxf[9 * (size_t)c + e]] = 1;
+              own[c] |= 1u << e;
+            }
+    }
+    MGX_TRY(tr->mem.upload(&tr->d.own27, own));
+    // greedy colouring of the parents over the unconstrained table (it holds for the constrained one as well)
+    {
+      std::vector<uint32_t> used(coarse->d.n_dofs, 0u), count(33, 0u), order(npar);
+      std::vector<uint8_t>  colour(npar, 0);
+      int                   n_colours = 0;
+      for (uint32_t c = 0; c < npar; ++c)
+        {
+          const uint32_t *ix   = &idxc[9 * (size_t)c];
+          uint32_t        mask = 0;
+          for (int e = 0; e < 9; ++e)
+            if (e != 4 && entity_size(e, p) != 0)
+              mask |= used[ix[e]];
+          int col = 0;
+          while (col < 32 && (mask >> col) & 1u)
+            ++col;
+          if (col == 32)
+            return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: the coarse cells need more than 32 colours");
+          colour[c] = (uint8_t)col;
+          ++count[col];
+          n_colours = std::max(n_colours, col + 1);
+          for (int e = 0; e < 9; ++e)
+            if (e != 4 && entity_size(e, p) != 0)
+              used[ix[e]] |= 1u << col;
+        }
+      tr->d.n_parent_colours = n_colours;
+      for (int k = 0; k < n_colours; ++k)
+        tr->d.parent_colour_start[k + 1] = tr->d.parent_colour_start[k] + count[k];
+      std::vector<uint32_t> fill(tr->d.parent_colour_start, tr->d.parent_colour_start + 33);
+      for (uint32_t c = 0; c < npar; ++c)
+        order[fill[colour[c]]++] = c;
+      MGX_TRY(tr->mem.upload(&tr->d.parent_order, order));
+      MGX_TRACE("transfer_create: two dimensions, %u parents in %d colours", npar, n_colours);
+    }
+    // the dense embedding into the basis block of the coarse operator (the transfer kernels read that one)
+    MGX_TRY(tr->mem.copy_as(coarse->d.number,
+                            (char *)coarse->d.basis + (coarse->d.number == MGX_F64 ? offsetof(Basis1D<double>, P1) : offsetof(Basis1D<float>, P1)),
+                            desc->prolong_1d, (size_t)(2 * p + 1) * (p + 1)));
+    *out = tr.release();
+    return MGX_OK;
+  }
 } // namespace
 
 extern "C" {
@@ -3121,6 +3273,9 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
               "mgx_transfer_create: level operators differ in degree or number type");
   MGX_REQUIRE(coarse->d.idx27_plain && fine->d.idx27_plain,
               "mgx_transfer_create: operators were created without idx27_plain");
+  MGX_REQUIRE(coarse->d.dim == fine->d.dim, "mgx_transfer_create: level operators of different dimensions");
+  if (coarse->d.dim == 2)
+    return transfer_create_2d(coarse, fine, desc, out);
   MGX_REQUIRE((uint64_t)coarse->d.n_cells * 8 == fine->d.n_cells,
               "mgx_transfer_create: fine level must have 8 children per coarse cell (uniform refinement)");
   const uint32_t npar = coarse->d.n_cells;
@@ -3258,6 +3413,7 @@ int mgx_interpolate_to_coarse(mgx_transfer_t tr, void *coarse, const void *fine)
 {
   MGX_REQUIRE(tr && coarse && fine, "mgx_interpolate_to_coarse: null argument");
   mgx_operator_t cop = tr->coarse, fop = tr->fine;
+  MGX_TRY(refuse_2d(cop->d, "mgx_interpolate_to_coarse", "no solution-dependent coefficients in two dimensions"));
   if (cop->plan || fop->plan || cop->ctx->has_comm)
     return fail(MGX_ERR_UNSUPPORTED, "mgx_interpolate_to_coarse: not on a decomposed mesh (single rank only)");
   MGX_REQUIRE(cop->d.idx27_plain && fop->d.idx27_plain, "mgx_interpolate_to_coarse: the level operators need idx27_plain");
@@ -3357,6 +3513,10 @@ int mgx_solver_create(mgx_context_t ctx, const mgx_solver_desc *desc, mgx_solver
       MGX_REQUIRE(desc->matrix_dp[l]->d.number == MGX_F64, "mgx_solver_create: matrix_dp must be fp64");
       MGX_REQUIRE(desc->matrix[l]->d.number == S->vnumber, "mgx_solver_create: mixed V-cycle number types");
       MGX_REQUIRE(desc->matrix[l]->d.n_dofs == desc->matrix_dp[l]->d.n_dofs, "mgx_solver_create: level size mismatch");
+      MGX_REQUIRE(desc->matrix[l]->d.dim == desc->matrix[0]->d.dim && desc->matrix_dp[l]->d.dim == desc->matrix[0]->d.dim,
+                  "mgx_solver_create: level operators of different dimensions");
+      if (desc->matrix[l]->d.dim == 2 && ctx->has_comm)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_solver_create: a two-dimensional hierarchy on a context with a communicator (one rank only)");
       S->matrix.push_back(desc->matrix[l]);
       S->matrix_dp.push_back(desc->matrix_dp[l]);
       if (l > 0)
@@ -3536,6 +3696,8 @@ int mgx_solver_set_agglomeration(mgx_solver_t S, int level, mgx_solver_t coarse,
 {
   MGX_REQUIRE(S && coarse && local_to_global && owned, "mgx_solver_set_agglomeration: null argument");
   MGX_REQUIRE(S->agg_solver == nullptr, "mgx_solver_set_agglomeration: already set");
+  MGX_TRY(refuse_2d(S->matrix[0]->d, "mgx_solver_set_agglomeration", "one rank only"));
+  MGX_TRY(refuse_2d(coarse->matrix[0]->d, "mgx_solver_set_agglomeration", "one rank only"));
   // (a hierarchy that lacks the coarsest levels of the whole mesh may consist of its finest level alone: the seam is then
   // that level, the only one that exists on both sides)
   MGX_REQUIRE(level >= 0 && (level < S->n_levels - 1 || (level == S->n_levels - 1 && coarse->n_levels > level + 1)),
@@ -3714,6 +3876,8 @@ static int v_cycle_eager(mgx_solver_t S, int level, int my_n_cycles)
 int mgx_solver_compute_rhs(mgx_solver_t S, int level, const double *rhs_q)
 {
   MGX_REQUIRE(S && level >= 0 && level < S->n_levels, "mgx_solver_compute_rhs: bad argument");
+  MGX_TRY(refuse_2d(S->matrix_dp[level]->d, "mgx_solver_compute_rhs",
+                    "right-hand sides of a two-dimensional problem are assembled on the host"));
   // the boundary values in a vector of their own (the level's solution vector is the caller's)
   mgx_operator_t A = S->matrix_dp[level];
   DeviceArena    tmp("mgx_solver_compute_rhs");
@@ -4070,6 +4234,7 @@ int mgx_solver_reset_smoother(mgx_solver_t S, int level, double smoothing_range,
 int mgx_solver_update_coefficient(mgx_solver_t S, int law, const double *state_fine)
 {
   MGX_REQUIRE(S && state_fine, "mgx_solver_update_coefficient: null argument");
+  MGX_TRY(refuse_2d(S->matrix[0]->d, "mgx_solver_update_coefficient", "no solution-dependent coefficients in two dimensions"));
   if (S->ctx->has_comm)
     return fail(MGX_ERR_UNSUPPORTED, "mgx_solver_update_coefficient: not on a context with a communicator (single rank only)");
   if (S->agg_solver)

@@ -1200,6 +1200,7 @@ int mgx_cube_operator_desc(mgx_cube_t c, int l, int number, mgx_operator_desc *d
   d->brick_colour = L.brick_colour.empty() ? nullptr : L.brick_colour.data();
   d->global_index = L.dof_grid.data();
   d->exchange     = nullptr; // decomposed meshes: see mgx_cube_exchange_desc
+  d->dim          = 3;
   return MGX_OK;
 }
 

@@ -1107,6 +1107,9 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
   const int      lmax = mgx_solver_n_levels(desc->cfe) - 1;
   mgx_operator_t fe   = nullptr;
   MGX_TRY(mgx_solver_get_operator(desc->cfe, lmax, 0, &fe));
+  if (mgx::operator_dim(fe) == 2)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: the FE_Q hierarchy is two-dimensional -- a DG level on top of an "
+                                        "FE_Q hierarchy is not built in two dimensions; use mgx_dg_plain_solver_create");
   const uint32_t *idx27 = nullptr;
   uint32_t        nc = 0, ncg = 0;
   int             p = 0;

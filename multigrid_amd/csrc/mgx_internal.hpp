@@ -147,6 +147,10 @@ namespace mgx
   {
     int       p        = 0;
     int       number   = 1; // MGX_F64
+    // 3: hexahedra.  2: quadrilaterals (mgx_kernels_2d.hip) -- idx27 / idx27_plain hold 9 entries per cell, coef is
+    // [xx,yy,xy], coef_q [n_cells][3][n^2], cell_scratch and asm_pos count n^2 local values per cell, and there is no
+    // brick schedule: ordered assembly or cell colours, for the separable form too
+    int       dim      = 3;
     uint32_t  n_cells  = 0;
     uint32_t  n_dofs   = 0;
     uint32_t  n_constrained = 0;
@@ -220,6 +224,12 @@ namespace mgx
     mutable uint32_t    pipe_grid[4] = {0, 0, 0, 0}; // persistent grid of prolongate(add), prolongate, restrict x2
     bool                owner_weights = false;   // restriction: weight 1 for the parent that owns a fine entity, 0 for the others (multi-block meshes)
     bool                coarse_coloured = false; // coarse cells c and c' with c % 8 == c' % 8 share no DoF
+    // two dimensions (mgx_kernels_2d.hip): children [n_coarse_cells*4], weight_shift [n_coarse_cells*9], own27 the
+    // ownership bits of the 9 entities of a fine cell; the restriction runs over the parents colour by colour
+    // (parents of one colour share no DoF: plain adds): parent_order [n_coarse_cells] sorted by colour
+    uint32_t           *parent_order = nullptr;
+    int                 n_parent_colours = 0;
+    uint32_t            parent_colour_start[33] = {0};
     uint32_t            n_cus = 256;
     uint32_t            colour_min = 16384; // Tunables::restrict_colour_min
   };
@@ -237,6 +247,7 @@ namespace mgx
   int  allreduce_sum(struct ::mgx_context_s *ctx, double *values, int count);
   int  dot_owned_prefix(struct ::mgx_context_s *ctx, int number, const void *x, const void *y, size_t n, double *out);
   bool context_has_comm(struct ::mgx_context_s *ctx);
+  int  operator_dim(struct ::mgx_operator_s *op); // 3 or 2 (mgx_operator_desc::dim)
   const Tunables &context_tunables(struct ::mgx_context_s *ctx);
   // One part of a V-cycle of a multigrid solver, timed into times[part] of its level when `timed` (print_wall_times of
   // the reference: host timers around synchronised parts -- for diagnosis, the parts no longer overlap their launches);
@@ -349,6 +360,8 @@ namespace mgx
   void launch_general_bricks(hipStream_t s, const OperatorData &op, void *dst, const void *src);
   // mode 0: dst = ordered sums of op.cell_scratch (tail as above), mode 1: dst += them
   void launch_assemble(hipStream_t s, const OperatorData &op, int mode, void *dst, const void *tail_src, uint32_t n_head);
+  // the same assembly with the Chebyshev update as its post-operation (ChebPost): x is the iterate, updated in place
+  void launch_assemble_cheb(hipStream_t s, const OperatorData &op, void *x, uint32_t n_head, const ChebPost &post);
   // ---- brick loop (mgx_macro.hip, mgx_macro2.hip; cross-check builds: mgx_brick.hip) ----
   // fused post-operations (what the reference passes as operation_after_loop).  The values are public: they are the
   // form numbers of mgx_profile_read
@@ -553,6 +566,15 @@ namespace mgx
                          bool with_constraints);
   void launch_restrict_add(hipStream_t s, const TransferData &t, void *coarse, const void *fine,
                            bool with_constraints);
+  // ---- quadrilaterals (mgx_kernels_2d.hip): what the four launchers above hand over to when op.dim == 2 ----
+  // the cell loop with launch_cell_loop's arguments; the cells are added up by the ordered assembly (op.asm_start: dst
+  // is written) or colour by colour with plain adds (op.cell_order: dst zeroed by the caller) -- never atomics
+  void launch_cell_loop_2d(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *tail_src,
+                           uint32_t n_head, const ChebPost *post);
+  void launch_cell_diagonal_2d(hipStream_t s, const OperatorData &op, void *diag, const double *a1d, const double *m1d);
+  void launch_prolongate_2d(hipStream_t s, const TransferData &t, void *fine, const void *coarse, bool add,
+                            bool with_constraints);
+  void launch_restrict_add_2d(hipStream_t s, const TransferData &t, void *coarse, const void *fine, bool with_constraints);
 
   // ---- vector kernels (mgx_vector.hip) ----
   void launch_copy_cast(hipStream_t s, void *dst, int dn, const void *src, int sn, size_t n);

@@ -1033,6 +1033,25 @@ namespace mgx
     dispatch_number(op.number, [&](auto t) { assemble_t<decltype(t)>(s, op, mode, dst, tail_src, n_head); });
   }
 
+  template <typename T>
+  static void assemble_cheb_t(hipStream_t s, const OperatorData &op, void *x, uint32_t n_head, const ChebPost &post)
+  {
+    const uint32_t nba = (op.n_dofs + 255) / 256;
+    if (post.three_term)
+      hipLaunchKernelGGL((assemble_cheb_kernel<T, true>), dim3(nba), dim3(256), 0, s, (T *)x, (const T *)op.cell_scratch, op.asm_start,
+                         op.asm_pos, op.n_dofs, n_head, (T *)post.x_old, (const T *)post.b, (const T *)post.dinv, (T)post.f1,
+                         (T)post.f2);
+    else
+      hipLaunchKernelGGL((assemble_cheb_kernel<T, false>), dim3(nba), dim3(256), 0, s, (T *)x, (const T *)op.cell_scratch, op.asm_start,
+                         op.asm_pos, op.n_dofs, n_head, (T *)post.x_old, (const T *)post.b, (const T *)post.dinv, (T)post.f1,
+                         (T)post.f2);
+  }
+
+  void launch_assemble_cheb(hipStream_t s, const OperatorData &op, void *x, uint32_t n_head, const ChebPost &post)
+  {
+    dispatch_number(op.number, [&](auto t) { assemble_cheb_t<decltype(t)>(s, op, x, n_head, post); });
+  }
+
   // The list loop of the per-cell kernels: launch(list, count, scratch) once per non-empty list of cells that share no
   // DoF (plain adds); with no lists once over all cells, into the scratch array of the ordered assembly if `ordered`
   // (the caller assembles), else with atomic adds.  Returns the scratch array the launch wrote, or nullptr.
@@ -1109,17 +1128,7 @@ namespace mgx
                          op.idx27, op.n_cells, (const Basis1D<T> *)op.basis, (T)op.coef[0], (T)op.coef[1],
                          (T)op.coef[2], scratch);
     if (scratch && post)
-      {
-        const uint32_t nba = (op.n_dofs + 255) / 256;
-        if (post->three_term)
-          hipLaunchKernelGGL((assemble_cheb_kernel<T, true>), dim3(nba), dim3(256), 0, s, (T *)dst, (const T *)scratch, op.asm_start,
-                             op.asm_pos, op.n_dofs, n_head, (T *)post->x_old, (const T *)post->b, (const T *)post->dinv,
-                             (T)post->f1, (T)post->f2);
-        else
-          hipLaunchKernelGGL((assemble_cheb_kernel<T, false>), dim3(nba), dim3(256), 0, s, (T *)dst, (const T *)scratch, op.asm_start,
-                             op.asm_pos, op.n_dofs, n_head, (T *)post->x_old, (const T *)post->b, (const T *)post->dinv,
-                             (T)post->f1, (T)post->f2);
-      }
+      assemble_cheb_t<T>(s, op, dst, n_head, *post);
     else if (scratch)
       assemble_t<T>(s, op, 0, dst, tail_src, n_head);
   }
@@ -1259,6 +1268,8 @@ namespace mgx
   void launch_cell_loop(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *tail_src,
                         uint32_t n_head, const ChebPost *post)
   {
+    if (op.dim == 2)
+      return launch_cell_loop_2d(s, op, dst, src, tail_src, n_head, post);
     dispatch_number_degree(op.number, op.p, [&](auto t, auto P) {
       cell_loop_t<P.value, decltype(t)>(s, op, dst, src, tail_src, n_head, post);
     });
@@ -1316,6 +1327,8 @@ namespace mgx
   void launch_cell_diagonal(hipStream_t s, const OperatorData &op, void *diag, const double *a, const double *m,
                             const CellLists &lists)
   {
+    if (op.dim == 2) // (its lists are the operator's own cell colours)
+      return launch_cell_diagonal_2d(s, op, diag, a, m);
     dispatch_number_degree(op.number, op.p, [&](auto t, auto P) { cell_diag_t<P.value, decltype(t)>(s, op, diag, a, m, lists); });
   }
 
@@ -1401,6 +1414,8 @@ namespace mgx
   void launch_prolongate(hipStream_t s, const TransferData &t, void *fine, const void *coarse, bool add,
                          bool with_constraints)
   {
+    if (t.coarse->dim == 2)
+      return launch_prolongate_2d(s, t, fine, coarse, add, with_constraints);
     if (t.patch)
       return launch_prolongate_pipe(s, t, fine, coarse, add, with_constraints);
     dispatch_number_degree(t.coarse->number, t.coarse->p, [&](auto number, auto P) {
@@ -1422,6 +1437,8 @@ namespace mgx
   void launch_restrict_add(hipStream_t s, const TransferData &t, void *coarse, const void *fine,
                            bool with_constraints)
   {
+    if (t.coarse->dim == 2)
+      return launch_restrict_add_2d(s, t, coarse, fine, with_constraints);
     if (t.patch)
       return launch_restrict_add_pipe(s, t, coarse, fine, with_constraints);
     dispatch_number_degree(t.coarse->number, t.coarse->p, [&](auto number, auto P) {

@@ -1,0 +1,517 @@
+// mgx_square.cpp -- host-side structured discretisation on quadrilaterals (see include/mgx_square.h): the
+// two-dimensional counterpart of mgx_cube.cpp, one rank.  Pure host code; the device work is behind mgx.h.  The 1D
+// element data (Gauss-Lobatto nodes, Gauss rule, shape values, collocation derivative, embedding) are those of
+// mgx_cube.cpp, taken from a one-cell cube of the same degree.
+#include "../../include/mgx_square.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace mgx
+{
+  int report_error(int code, const char *message); // mgx_api.cpp
+}
+
+namespace
+{
+  constexpr double kPi = 3.14159265358979323846264338327950288;
+
+  struct Level
+  {
+    uint32_t              N[2] = {0, 0}; // cells per direction
+    uint32_t              n_cells = 0, n_dofs = 0;
+    double                h = 0;
+    std::vector<uint32_t> idx9, idx9_plain, constrained, children, coords, dof_grid;
+    std::vector<uint8_t>  weight_shift;
+    std::vector<double>   bc_value, rhs;
+  };
+} // namespace
+
+struct mgx_square_s
+{
+  int                p = 0, roots[2] = {1, 1};
+  double             origin = -0.9, h0 = 1.9;
+  double             A[4] = {1, 0, 0, 1}, detA = 1, coef[3] = {1, 1, 0};
+  mgx_cube_t         element = nullptr; // a one-cell cube: the owner of the 1D arrays
+  const double      *S = nullptr, *D = nullptr, *gw = nullptr, *gq = nullptr, *gll = nullptr, *P1 = nullptr;
+  std::vector<Level> levels;
+
+  void   map(double X, double Y, double &x, double &y) const
+  {
+    x = origin + A[0] * X + A[1] * Y;
+    y = origin + A[2] * X + A[3] * Y;
+  }
+  static double u(double x, double y) { return std::sin(3 * kPi * x) * std::sin(3 * kPi * y); }
+  static double f(double x, double y) { return 2 * (3 * kPi) * (3 * kPi) * u(x, y); }
+};
+
+namespace
+{
+  inline int code(int a, int p) { return a == 0 ? 0 : (a == p ? 2 : 1); }
+  inline int entity_size(int e, int p) { return (e % 3 == 1 ? p - 1 : 1) * (e / 3 == 1 ? p - 1 : 1); }
+  // DoF of node (i, j) of a cell through its 9 entries (the addressing of read_dof_values_compressed in two dimensions)
+  inline uint32_t local_dof(const uint32_t *ix, int p, int i, int j)
+  {
+    const int      cx = code(i, p), cy = code(j, p);
+    const uint32_t b  = ix[3 * cy + cx];
+    if (b == MGX_INVALID_INDEX)
+      return b;
+    return b + (uint32_t)((cy == 1 ? j - 1 : 0) * (cx == 1 ? p - 1 : 1) + (cx == 1 ? i - 1 : 0));
+  }
+  inline uint32_t compact_bits(uint32_t m) // the even bits of m
+  {
+    uint32_t r = 0;
+    for (int b = 0; b < 16; ++b)
+      r |= ((m >> (2 * b)) & 1u) << b;
+    return r;
+  }
+
+  void build_level(const mgx_square_s &Q, Level &L, int level)
+  {
+    const int p = Q.p;
+    L.N[0]      = (uint32_t)Q.roots[0] << level;
+    L.N[1]      = (uint32_t)Q.roots[1] << level;
+    L.n_cells   = L.N[0] * L.N[1];
+    L.h         = Q.h0 / (double)(1u << level);
+    L.coords.resize(2 * (size_t)L.n_cells);
+    const uint32_t per_root = 1u << (2 * level);
+    for (uint32_t c = 0; c < L.n_cells; ++c)
+      {
+        const uint32_t root = c >> (2 * level), m = c & (per_root - 1);
+        L.coords[2 * (size_t)c]     = ((root % (uint32_t)Q.roots[0]) << level) | compact_bits(m);
+        L.coords[2 * (size_t)c + 1] = ((root / (uint32_t)Q.roots[0]) << level) | compact_bits(m >> 1);
+      }
+    // entities on the lattice (2 Nx + 1) x (2 Ny + 1): key (2 cx + ex, 2 cy + ey); first touch in cell order, the
+    // entities on the boundary (all four sides Dirichlet) after all others
+    const uint32_t        Ex = 2 * L.N[0] + 1, Ey = 2 * L.N[1] + 1;
+    std::vector<uint32_t> base((size_t)Ex * Ey, MGX_INVALID_INDEX);
+    auto key = [&](uint32_t c, int e) { return (size_t)(2 * L.coords[2 * (size_t)c + 1] + e / 3) * Ex + 2 * L.coords[2 * (size_t)c] + e % 3; };
+    auto on_boundary = [&](size_t k) { return k % Ex == 0 || k % Ex == Ex - 1 || k / Ex == 0 || k / Ex == Ey - 1; };
+    uint32_t counter = 0;
+    for (int pass = 0; pass < 2; ++pass)
+      {
+        for (uint32_t c = 0; c < L.n_cells; ++c)
+          for (int e = 0; e < 9; ++e)
+            {
+              const size_t k = key(c, e);
+              if (base[k] != MGX_INVALID_INDEX || on_boundary(k) != (pass == 1))
+                continue;
+              base[k] = counter;
+              if (pass == 1)
+                for (int d = 0; d < entity_size(e, p); ++d)
+                  L.constrained.push_back(counter + (uint32_t)d);
+              counter += (uint32_t)entity_size(e, p);
+            }
+      }
+    L.n_dofs = counter;
+    L.idx9.resize(9 * (size_t)L.n_cells);
+    L.idx9_plain.resize(9 * (size_t)L.n_cells);
+    for (uint32_t c = 0; c < L.n_cells; ++c)
+      for (int e = 0; e < 9; ++e)
+        {
+          const size_t k                  = key(c, e);
+          L.idx9_plain[9 * (size_t)c + e] = base[k];
+          L.idx9[9 * (size_t)c + e]       = on_boundary(k) ? MGX_INVALID_INDEX : base[k];
+        }
+    const uint32_t Gx = L.N[0] * (uint32_t)p + 1;
+    L.dof_grid.resize(L.n_dofs);
+    for (uint32_t c = 0; c < L.n_cells; ++c)
+      for (int j = 0; j <= p; ++j)
+        for (int i = 0; i <= p; ++i)
+          L.dof_grid[local_dof(&L.idx9_plain[9 * (size_t)c], p, i, j)] =
+            (L.coords[2 * (size_t)c + 1] * (uint32_t)p + (uint32_t)j) * Gx + L.coords[2 * (size_t)c] * (uint32_t)p + (uint32_t)i;
+    // boundary values at the nodes
+    L.bc_value.resize(L.constrained.size());
+    for (size_t i = 0; i < L.constrained.size(); ++i)
+      {
+        const uint32_t g  = L.dof_grid[L.constrained[i]], gx = g % Gx, gy = g / Gx;
+        const uint32_t cx = std::min(gx / (uint32_t)p, L.N[0] - 1), cy = std::min(gy / (uint32_t)p, L.N[1] - 1);
+        double         x, y;
+        Q.map(L.h * (cx + Q.gll[gx - cx * p]), L.h * (cy + Q.gll[gy - cy * p]), x, y);
+        L.bc_value[i] = mgx_square_s::u(x, y);
+      }
+    if (level > 0)
+      {
+        // the children of cell c are 4c .. 4c+3 (Morton order); multiplicity of the patch entities: a patch side is
+        // shared with the neighbouring parent if there is one
+        const uint32_t npar = L.n_cells / 4, Nx = L.N[0] / 2, Ny = L.N[1] / 2;
+        L.children.resize(4 * (size_t)npar);
+        L.weight_shift.resize(9 * (size_t)npar);
+        for (uint32_t pc = 0; pc < npar; ++pc)
+          {
+            for (int ch = 0; ch < 4; ++ch)
+              L.children[4 * (size_t)pc + ch] = 4 * pc + (uint32_t)ch;
+            const uint32_t px = L.coords[2 * (size_t)(4 * pc)] / 2, py = L.coords[2 * (size_t)(4 * pc) + 1] / 2;
+            for (int e = 0; e < 9; ++e)
+              {
+                const int ca = e % 3, cb = e / 3;
+                const int sx = (ca == 0 && px > 0) || (ca == 2 && px + 1 < Nx), sy = (cb == 0 && py > 0) || (cb == 2 && py + 1 < Ny);
+                L.weight_shift[9 * (size_t)pc + e] = (uint8_t)(sx + sy);
+              }
+          }
+      }
+  }
+
+  // the cell matrix of the operator (the same on every cell and level: det(J) J^-1 J^-T does not depend on h in two
+  // dimensions): K[a][b] = sum_q w_q grad phi_a . C grad phi_b, a = j n + i
+  std::vector<double> cell_matrix(const mgx_square_s &Q)
+  {
+    const int           p = Q.p, n = p + 1, n2 = n * n;
+    std::vector<double> G((size_t)n * n), gx((size_t)n2 * n2), gy((size_t)n2 * n2), K((size_t)n2 * n2, 0.);
+    for (int q = 0; q < n; ++q)
+      for (int i = 0; i < n; ++i)
+        {
+          double g = 0;
+          for (int r = 0; r < n; ++r)
+            g += Q.D[q * n + r] * Q.S[r * n + i];
+          G[q * n + i] = g;
+        }
+    for (int qy = 0; qy < n; ++qy)
+      for (int qx = 0; qx < n; ++qx)
+        for (int j = 0; j < n; ++j)
+          for (int i = 0; i < n; ++i)
+            {
+              gx[(size_t)(qy * n + qx) * n2 + j * n + i] = G[qx * n + i] * Q.S[qy * n + j];
+              gy[(size_t)(qy * n + qx) * n2 + j * n + i] = Q.S[qx * n + i] * G[qy * n + j];
+            }
+    for (int q = 0; q < n2; ++q)
+      {
+        const double w = Q.gw[q % n] * Q.gw[q / n], t0 = Q.coef[0] * w, t1 = Q.coef[1] * w, t2 = Q.coef[2] * w;
+        const double *dx = &gx[(size_t)q * n2], *dy = &gy[(size_t)q * n2];
+        for (int a = 0; a < n2; ++a)
+          {
+            const double fa = t0 * dx[a] + t2 * dy[a], fb = t2 * dx[a] + t1 * dy[a];
+            for (int b = 0; b < n2; ++b)
+              K[(size_t)a * n2 + b] += fa * dx[b] + fb * dy[b];
+          }
+      }
+    return K;
+  }
+
+  // rhs = int f phi - int grad u_bc . C grad phi (multigrid_solver.h:225-261), rows of constrained DoFs zero
+  void build_rhs(const mgx_square_s &Q, Level &L)
+  {
+    const int                 p = Q.p, n = p + 1, n2 = n * n;
+    const std::vector<double> K = cell_matrix(Q);
+    std::vector<double>       ubc(L.n_dofs, 0.), ul(n2), F(n2);
+    for (size_t i = 0; i < L.constrained.size(); ++i)
+      ubc[L.constrained[i]] = L.bc_value[i];
+    L.rhs.assign(L.n_dofs, 0.);
+    const double jxw = L.h * L.h * Q.detA;
+    for (uint32_t c = 0; c < L.n_cells; ++c)
+      {
+        const uint32_t *ixp = &L.idx9_plain[9 * (size_t)c], *ix = &L.idx9[9 * (size_t)c];
+        std::fill(F.begin(), F.end(), 0.);
+        for (int qy = 0; qy < n; ++qy)
+          for (int qx = 0; qx < n; ++qx)
+            {
+              double x, y;
+              Q.map(L.h * (L.coords[2 * (size_t)c] + Q.gq[qx]), L.h * (L.coords[2 * (size_t)c + 1] + Q.gq[qy]), x, y);
+              const double fq = mgx_square_s::f(x, y) * Q.gw[qx] * Q.gw[qy] * jxw;
+              for (int j = 0; j < n; ++j)
+                for (int i = 0; i < n; ++i)
+                  F[j * n + i] += fq * Q.S[qx * n + i] * Q.S[qy * n + j];
+            }
+        bool any = false;
+        for (int j = 0; j < n; ++j)
+          for (int i = 0; i < n; ++i)
+            {
+              ul[j * n + i] = ubc[local_dof(ixp, p, i, j)];
+              any           = any || ul[j * n + i] != 0.;
+            }
+        for (int j = 0; j < n; ++j)
+          for (int i = 0; i < n; ++i)
+            {
+              const uint32_t d = local_dof(ix, p, i, j);
+              if (d == MGX_INVALID_INDEX)
+                continue;
+              double v = F[j * n + i];
+              if (any)
+                for (int b = 0; b < n2; ++b)
+                  v -= K[(size_t)(j * n + i) * n2 + b] * ul[b];
+              L.rhs[d] += v;
+            }
+      }
+  }
+
+  bool valid(mgx_square_t q, int l) { return q && l >= 0 && l < (int)q->levels.size(); }
+} // namespace
+
+extern "C" {
+
+int mgx_square_create_box(const mgx_square_box_desc *bd, mgx_square_t *out)
+{
+  if (!bd || !out || bd->degree < 1 || bd->degree > MGX_MAX_DEGREE || bd->n_refine < 0 || bd->n_refine > 14 || bd->roots[0] < 1 ||
+      bd->roots[1] < 1 || !(bd->h0 > 0))
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_box: bad argument");
+  if (((uint64_t)bd->roots[0] << bd->n_refine) * ((uint64_t)bd->roots[1] << bd->n_refine) * (uint64_t)(bd->degree * bd->degree) >= 0xFFFFFFF0ull)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_box: the finest level does not fit 32-bit indices");
+  mgx_square_s *Q = new mgx_square_s;
+  Q->p            = bd->degree;
+  Q->roots[0]     = bd->roots[0];
+  Q->roots[1]     = bd->roots[1];
+  Q->origin       = bd->origin;
+  Q->h0           = bd->h0;
+  if (bd->jacobian)
+    std::copy(bd->jacobian, bd->jacobian + 4, Q->A);
+  Q->detA = Q->A[0] * Q->A[3] - Q->A[1] * Q->A[2];
+  if (!(Q->detA > 0) || mgx_cube_create_numbered(bd->degree, 1, 0, MGX_CUBE_NUMBERING_CELL, &Q->element) != MGX_OK)
+    {
+      delete Q;
+      return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_box: the jacobian must have a positive determinant");
+    }
+  // det(J) J^-1 J^-T = det(A) (A^T A)^-1
+  const double g00 = Q->A[0] * Q->A[0] + Q->A[2] * Q->A[2], g11 = Q->A[1] * Q->A[1] + Q->A[3] * Q->A[3],
+               g01 = Q->A[0] * Q->A[1] + Q->A[2] * Q->A[3], dg = g00 * g11 - g01 * g01;
+  Q->coef[0] = Q->detA * g11 / dg;
+  Q->coef[1] = Q->detA * g00 / dg;
+  Q->coef[2] = g01 == 0. ? 0. : -Q->detA * g01 / dg;
+  Q->S       = mgx_cube_shape_values(Q->element);
+  Q->D       = mgx_cube_colloc_grad(Q->element);
+  Q->gw      = mgx_cube_qweights(Q->element);
+  Q->gq      = mgx_cube_qpoints(Q->element);
+  Q->gll     = mgx_cube_gll(Q->element);
+  Q->P1      = mgx_cube_prolong_1d(Q->element);
+  Q->levels.resize((size_t)bd->n_refine + 1);
+  for (int l = 0; l <= bd->n_refine; ++l)
+    build_level(*Q, Q->levels[l], l);
+  *out = Q;
+  return MGX_OK;
+}
+
+int mgx_square_create(int degree, int n_subdiv, int n_refine, mgx_square_t *out)
+{
+  if (n_subdiv < 1)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create: bad argument");
+  mgx_square_box_desc bd;
+  bd.degree   = degree;
+  bd.n_refine = n_refine;
+  bd.roots[0] = bd.roots[1] = n_subdiv;
+  bd.origin   = -0.9;
+  bd.h0       = 1.9 / n_subdiv;
+  bd.jacobian = nullptr;
+  return mgx_square_create_box(&bd, out);
+}
+
+int mgx_square_destroy(mgx_square_t q)
+{
+  if (q)
+    mgx_cube_destroy(q->element);
+  delete q;
+  return MGX_OK;
+}
+
+int      mgx_square_n_levels(mgx_square_t q) { return (int)q->levels.size(); }
+int      mgx_square_degree(mgx_square_t q) { return q->p; }
+uint32_t mgx_square_n_cells(mgx_square_t q, int l) { return q->levels[l].n_cells; }
+uint32_t mgx_square_n_dofs(mgx_square_t q, int l) { return q->levels[l].n_dofs; }
+uint32_t mgx_square_n_constrained(mgx_square_t q, int l) { return (uint32_t)q->levels[l].constrained.size(); }
+void     mgx_square_cells_per_dim2(mgx_square_t q, int l, uint32_t cells[2])
+{
+  cells[0] = q->levels[l].N[0];
+  cells[1] = q->levels[l].N[1];
+}
+double          mgx_square_cell_size(mgx_square_t q, int l) { return q->levels[l].h; }
+const uint32_t *mgx_square_idx9(mgx_square_t q, int l) { return q->levels[l].idx9.data(); }
+const uint32_t *mgx_square_idx9_plain(mgx_square_t q, int l) { return q->levels[l].idx9_plain.data(); }
+const uint32_t *mgx_square_constrained(mgx_square_t q, int l) { return q->levels[l].constrained.data(); }
+const uint32_t *mgx_square_children(mgx_square_t q, int l) { return l > 0 ? q->levels[l].children.data() : nullptr; }
+const uint8_t  *mgx_square_weight_shift(mgx_square_t q, int l) { return l > 0 ? q->levels[l].weight_shift.data() : nullptr; }
+const uint32_t *mgx_square_cell_coords(mgx_square_t q, int l) { return q->levels[l].coords.data(); }
+const uint32_t *mgx_square_dof_grid(mgx_square_t q, int l) { return q->levels[l].dof_grid.data(); }
+const double   *mgx_square_shape_values(mgx_square_t q) { return q->S; }
+const double   *mgx_square_colloc_grad(mgx_square_t q) { return q->D; }
+const double   *mgx_square_qweights(mgx_square_t q) { return q->gw; }
+const double   *mgx_square_qpoints(mgx_square_t q) { return q->gq; }
+const double   *mgx_square_gll(mgx_square_t q) { return q->gll; }
+const double   *mgx_square_prolong_1d(mgx_square_t q) { return q->P1; }
+
+const double *mgx_square_rhs(mgx_square_t q, int l)
+{
+  Level &L = q->levels[l];
+  if (L.rhs.empty())
+    build_rhs(*q, L);
+  return L.rhs.data();
+}
+uint32_t        mgx_square_bc_count(mgx_square_t q, int l) { return (uint32_t)q->levels[l].constrained.size(); }
+const uint32_t *mgx_square_bc_index(mgx_square_t q, int l) { return q->levels[l].constrained.data(); }
+const double   *mgx_square_bc_value(mgx_square_t q, int l) { return q->levels[l].bc_value.data(); }
+
+double mgx_square_l2_error(mgx_square_t q, int l, const double *sol)
+{
+  const Level        &L = q->levels[l];
+  const int           p = q->p, n = p + 1;
+  std::vector<double> ul((size_t)n * n), t((size_t)n * n);
+  const double        jxw = L.h * L.h * q->detA;
+  double              err = 0, vol = 0;
+  for (uint32_t c = 0; c < L.n_cells; ++c)
+    {
+      const uint32_t *ix = &L.idx9_plain[9 * (size_t)c];
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i)
+          ul[j * n + i] = sol[local_dof(ix, p, i, j)];
+      for (int j = 0; j < n; ++j) // along x
+        for (int qx = 0; qx < n; ++qx)
+          {
+            double s = 0;
+            for (int i = 0; i < n; ++i)
+              s += q->S[qx * n + i] * ul[j * n + i];
+            t[j * n + qx] = s;
+          }
+      for (int qy = 0; qy < n; ++qy)
+        for (int qx = 0; qx < n; ++qx)
+          {
+            double s = 0, x, y;
+            for (int j = 0; j < n; ++j)
+              s += q->S[qy * n + j] * t[j * n + qx];
+            q->map(L.h * (L.coords[2 * (size_t)c] + q->gq[qx]), L.h * (L.coords[2 * (size_t)c + 1] + q->gq[qy]), x, y);
+            const double w = q->gw[qx] * q->gw[qy] * jxw, d = s - mgx_square_s::u(x, y);
+            err += d * d * w;
+            vol += w;
+          }
+    }
+  return std::sqrt(err / vol);
+}
+
+int mgx_square_seeded_vector(mgx_square_t q, int l, uint64_t seed, double *out)
+{
+  if (!valid(q, l) || !out)
+    return MGX_ERR_INVALID_ARGUMENT;
+  const Level &L = q->levels[l];
+  for (uint32_t i = 0; i < L.n_dofs; ++i)
+    {
+      uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)L.dof_grid[i] + 1);
+      z          = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z          = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      z ^= z >> 31;
+      out[i] = (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+    }
+  return MGX_OK;
+}
+
+int mgx_square_operator_desc(mgx_square_t q, int l, int number, mgx_operator_desc *d)
+{
+  if (!valid(q, l) || !d)
+    return MGX_ERR_INVALID_ARGUMENT;
+  const Level &L = q->levels[l];
+  std::memset(d, 0, sizeof(*d));
+  d->degree        = q->p;
+  d->number        = number;
+  d->n_cells       = L.n_cells;
+  d->n_dofs        = L.n_dofs;
+  d->idx27         = L.idx9.data();
+  d->idx27_plain   = L.idx9_plain.data();
+  d->constrained   = L.constrained.data();
+  d->n_constrained = (uint32_t)L.constrained.size();
+  d->coef[0]       = q->coef[0];
+  d->coef[1]       = q->coef[1];
+  d->coef[2]       = q->coef[2];
+  d->shape_values  = q->S;
+  d->colloc_grad   = q->D;
+  d->qweights      = q->gw;
+  d->global_index  = L.dof_grid.data();
+  d->dim           = 2;
+  return MGX_OK;
+}
+
+int mgx_square_coef_q(mgx_square_t q, int l, double *out)
+{
+  if (!valid(q, l) || !out)
+    return MGX_ERR_INVALID_ARGUMENT;
+  const int    n  = q->p + 1;
+  const size_t n2 = (size_t)n * n;
+  for (size_t c = 0; c < q->levels[l].n_cells; ++c)
+    for (int k = 0; k < 3; ++k)
+      for (size_t p = 0; p < n2; ++p)
+        out[(c * 3 + k) * n2 + p] = q->coef[k] * q->gw[p % n] * q->gw[p / n];
+  return MGX_OK;
+}
+
+int mgx_square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int degree_pre, int n_cycles, int per_point,
+                             mgx_cube_solver *out)
+{
+  if (!ctx || !q || !out || (vnumber != MGX_F32 && vnumber != MGX_F64))
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_solver_create: bad argument");
+  const int nl = (int)q->levels.size();
+  std::memset(out, 0, sizeof(*out));
+  out->n_levels    = nl;
+  out->matrix      = new mgx_operator_t[nl]();
+  out->matrix_dp   = new mgx_operator_t[nl]();
+  out->transfer    = new mgx_transfer_t[nl]();
+  out->transfer_dp = new mgx_transfer_t[nl]();
+  int status       = MGX_OK;
+  for (int l = 0; l < nl && status == MGX_OK; ++l)
+    {
+      mgx_operator_desc   d;
+      std::vector<double> cq;
+      mgx_square_operator_desc(q, l, MGX_F64, &d);
+      if (per_point)
+        {
+          cq.resize((size_t)d.n_cells * 3 * (q->p + 1) * (q->p + 1));
+          mgx_square_coef_q(q, l, cq.data());
+          d.coef_q = cq.data();
+        }
+      status = mgx_operator_create(ctx, &d, &out->matrix_dp[l]);
+      if (status != MGX_OK)
+        break;
+      if (vnumber == MGX_F64)
+        out->matrix[l] = out->matrix_dp[l];
+      else
+        {
+          d.number = MGX_F32;
+          status   = mgx_operator_create(ctx, &d, &out->matrix[l]);
+        }
+    }
+  for (int l = 1; l < nl && status == MGX_OK; ++l)
+    {
+      mgx_transfer_desc t;
+      t.children     = q->levels[l].children.data();
+      t.prolong_1d   = q->P1;
+      t.weight_shift = q->levels[l].weight_shift.data();
+      status         = mgx_transfer_create(out->matrix_dp[l - 1], out->matrix_dp[l], &t, &out->transfer_dp[l]);
+      if (status != MGX_OK)
+        break;
+      if (vnumber == MGX_F64)
+        out->transfer[l] = out->transfer_dp[l];
+      else
+        status = mgx_transfer_create(out->matrix[l - 1], out->matrix[l], &t, &out->transfer[l]);
+    }
+  if (status == MGX_OK)
+    {
+      std::vector<const double *>   rhs(nl), bcv(nl);
+      std::vector<const uint32_t *> bci(nl);
+      std::vector<uint32_t>         bcn(nl);
+      for (int l = 0; l < nl; ++l)
+        {
+          rhs[l] = mgx_square_rhs(q, l);
+          bci[l] = q->levels[l].constrained.data();
+          bcv[l] = q->levels[l].bc_value.data();
+          bcn[l] = (uint32_t)q->levels[l].constrained.size();
+        }
+      mgx_solver_desc sd;
+      sd.n_levels    = nl;
+      sd.degree_pre  = degree_pre;
+      sd.n_cycles    = n_cycles;
+      sd.matrix      = out->matrix;
+      sd.matrix_dp   = out->matrix_dp;
+      sd.transfer    = out->transfer;
+      sd.transfer_dp = out->transfer_dp;
+      sd.rhs         = rhs.data();
+      sd.bc_index    = bci.data();
+      sd.bc_value    = bcv.data();
+      sd.bc_count    = bcn.data();
+      status         = mgx_solver_create(ctx, &sd, &out->solver);
+    }
+  if (status != MGX_OK)
+    {
+      const std::string keep = mgx_last_error(); // the destroy calls below must not hide the cause
+      mgx_cube_solver_destroy(out);
+      mgx::report_error(status, keep.c_str());
+    }
+  return status;
+}
+
+} // extern "C"
