@@ -265,9 +265,10 @@ typedef struct
    * two-dimensional level adds its cells up through the ordered assembly or, beyond 2^26 local values or from
    * "cell_colour_min" cells on, colour by colour (four colours on a structured mesh): never with atomics, every result is
    * bitwise reproducible.  Refused on such an operator with MGX_ERR_UNSUPPORTED: mgx_compute_residual,
-   * mgx_solver_compute_rhs, the solution-dependent coefficients (mgx_operator_enable_coefficient_update[_q],
-   * mgx_evaluate_coefficient, mgx_compute_nonlinear_residual, mgx_interpolate_to_coarse, mgx_solver_update_coefficient),
-   * mgx_solver_set_agglomeration and mgx_dg_solver_create over such a hierarchy. */
+   * mgx_solver_compute_rhs, mgx_solver_set_agglomeration and mgx_dg_solver_create over such a hierarchy.  The
+   * solution-dependent coefficients take their geometry through mgx_operator_enable_coefficient_update[_q]_2d (the 3D
+   * pair is refused); mgx_evaluate_coefficient, mgx_compute_nonlinear_residual, mgx_interpolate_to_coarse and
+   * mgx_solver_update_coefficient are refused with MGX_ERR_UNSUPPORTED until the operators were enabled. */
   int dim;
 } mgx_operator_desc;
 
@@ -334,6 +335,16 @@ int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metri
  * coefficient: MGX_ERR_UNSUPPORTED.  Either enable call replaces what the other set; the entry points below mean the
  * same with both. */
 int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *unit_q, const double *jxw_q);
+/* The two calls above for an operator on quadrilaterals (mgx_operator_desc::dim == 2; the program's own dimension,
+ * minimal_surface/program.cc:73): what MinimalSurfaceOperator<2,...> reads from MatrixFree<2>'s mapping info, :144-152.
+ * metric = M as [xx, yy, xy]; unit_q[cell][3][(p+1)^2] = JxW_q J^-1 J^-T as [xx, yy, xy] (layout of
+ * mgx_operator_desc::coef_q in two dimensions) and jxw_q[cell][(p+1)^2].  Same laws, checks and replacement rules as in
+ * three dimensions.  The arrays of the 3D calls have another shape, so each pair refuses an operator of the other
+ * dimension with MGX_ERR_UNSUPPORTED.  After either call mgx_evaluate_coefficient, mgx_compute_nonlinear_residual,
+ * mgx_interpolate_to_coarse (coarse operator enabled) and mgx_solver_update_coefficient (every level enabled) accept the
+ * 2D objects; before it they return MGX_ERR_UNSUPPORTED. */
+int mgx_operator_enable_coefficient_update_2d(mgx_operator_t op, const double metric[3], double det_jacobian);
+int mgx_operator_enable_coefficient_update_q_2d(mgx_operator_t op, const double *unit_q, const double *jxw_q);
 /* MinimalSurfaceOperator::evaluate_coefficient(first_time, solution) :120-165: rewrites the operator's coef_q on the
  * device from `state` (device vector of the operator's number type, boundary values in place, read through
  * idx27_plain).  The inverse diagonal becomes stale: mgx_compute_diagonal before it is used again (a smoother created

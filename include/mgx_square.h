@@ -40,6 +40,16 @@ typedef struct
 /* the square [-0.9, 1]^2 of poisson_cube with n_subdiv coarse cells per direction */
 int mgx_square_create(int degree, int n_subdiv, int n_refine, mgx_square_t *square);
 int mgx_square_create_box(const mgx_square_box_desc *desc, mgx_square_t *square);
+/* A mesh with curved cells (what a Triangulation<2> with a PolarManifold and MappingQ(p) hands to MatrixFree<2>): the
+ * box of desc, normalised to the unit square (X, Y), is mapped to the quarter annulus r = 0.5 + 0.5 X, theta = (pi/2) Y,
+ * (x, y) = r (cos theta, sin theta).  Every cell of every level places its (p+1)^2 Gauss-Lobatto nodes by the exact
+ * map -- the isoparametric degree p, the rule of the 3D shell sector.  desc->jacobian must be NULL and desc->origin is
+ * not read.  mgx_square_operator_desc hands out the per-point unit-law tensor (mgx_square_unit_q) as coef_q.  The
+ * Poisson problem of the box does not exist here: mgx_square_rhs, mgx_square_bc_index / _value and
+ * mgx_square_solver_create are refused (NULL / MGX_ERR_UNSUPPORTED), mgx_square_bc_count is 0, mgx_square_l2_error is
+ * NaN; the hierarchy is that of mgx_square_solver_create_general. */
+#define MGX_SQUARE_GEOMETRY_ANNULUS_SECTOR 1
+int mgx_square_create_mapped(const mgx_square_box_desc *desc, int geometry, mgx_square_t *square);
 int mgx_square_destroy(mgx_square_t square);
 
 int      mgx_square_n_levels(mgx_square_t square);
@@ -85,6 +95,29 @@ int mgx_square_coef_q(mgx_square_t square, int level, double *out);
  * mgx_cube_solver_destroy. */
 int mgx_square_solver_create(mgx_context_t ctx, mgx_square_t square, int vcycle_number, int degree_pre, int n_cycles,
                              int per_point, mgx_cube_solver *out);
+
+/* ---- geometry for the solution-dependent coefficients (minimal_surface/program.cc with dimension = 2) ---- */
+/* affine cells of level `level` of a box: metric = J^-1 J^-T as [xx, yy, xy] and det J with J = h_level A (A the
+ * box's jacobian) -- the arguments of mgx_operator_enable_coefficient_update_2d.  Refused on a mapped square. */
+int mgx_square_affine_metric(mgx_square_t square, int level, double metric[3], double *det_jacobian);
+/* out[n_dofs][2]: physical coordinates of the Gauss-Lobatto node of every DoF (where the boundary function of
+ * LaplaceProblem<2>::interpolate_boundary_values is evaluated) */
+int mgx_square_dof_coordinates(mgx_square_t square, int level, double *out);
+/* out[n_cells][(p+1)^2][2]: the nodes of every cell, x fastest */
+int mgx_square_cell_nodes(mgx_square_t square, int level, double *out);
+/* the per-point geometry from the cell nodes (isoparametric): out[n_cells][3][(p+1)^2] = JxW_q J^-1 J^-T as
+ * [xx, yy, xy] and out[n_cells][(p+1)^2] = JxW_q -- the arguments of mgx_operator_enable_coefficient_update_q_2d.  On a
+ * box they equal the affine geometry up to rounding. */
+int mgx_square_unit_q(mgx_square_t square, int level, double *out);
+int mgx_square_jxw_q(mgx_square_t square, int level, double *out);
+/* mgx_cube_solver_create_general in two dimensions: the hierarchy of LaplaceProblem<2>::solve for a solution-dependent
+ * coefficient (minimal_surface/program.cc:425-488).  Operators in the per-point form with coef_q_per_level[l]
+ * ([n_cells][3][(p+1)^2]; NULL or a NULL entry: the unit-law tensor), zero right-hand sides, homogeneous boundary
+ * values, every level enabled (a box: mgx_operator_enable_coefficient_update_2d on the operators of both precisions; a
+ * mapped square: mgx_operator_enable_coefficient_update_q_2d on the fp64 operators, an fp32 V-cycle operator receives the
+ * rounded fp64 tensor).  One rank.  Released with mgx_cube_solver_destroy. */
+int mgx_square_solver_create_general(mgx_context_t ctx, mgx_square_t square, int vcycle_number, int degree_pre, int n_cycles,
+                                     const double *const *coef_q_per_level, mgx_cube_solver *out);
 
 #ifdef __cplusplus
 }

@@ -631,10 +631,14 @@ class Square:
 
     size, rank, shell, box_desc, level_offset = 1, 0, None, None, 0
 
-    def __init__(self, degree, n_subdiv=1, n_refine=3, box=None, origin=-0.9, h0=None, jacobian=None):
+    MAPPED = {"annulus_sector": 1}  # MGX_SQUARE_GEOMETRY_*
+
+    def __init__(self, degree, n_subdiv=1, n_refine=3, box=None, origin=-0.9, h0=None, jacobian=None, mapped=None):
         """box=None: the square [-0.9,1]^2 with n_subdiv coarse cells per direction.  box=(sx,sy): a box of sx x sy
         square coarse cells of size h0 from (origin, origin).  jacobian: constant 2 x 2 matrix of an affine map of the
-        whole box (a sheared or anisotropic box: the operator's one tensor [xx,yy,xy], the full-tensor form)."""
+        whole box (a sheared or anisotropic box: the operator's one tensor [xx,yy,xy], the full-tensor form).
+        mapped="annulus_sector": curved cells on every level (mgx_square_create_mapped): the box as the quarter annulus
+        0.5 <= r <= 1; the operator's coefficient is the per-point unit-law tensor, there is no Poisson problem."""
         self.lib = _lib.load()
         h = C.c_void_p()
         if box is None:
@@ -642,7 +646,11 @@ class Square:
         self._jac = None if jacobian is None else np.ascontiguousarray(jacobian, dtype=np.float64).reshape(2, 2)
         d = _lib.SquareBoxDesc(degree, n_refine, (C.c_int * 2)(*box), origin, 1.9 if h0 is None else h0,
                                None if self._jac is None else self._jac.ctypes.data_as(_lib.f64p))
-        check(self.lib.mgx_square_create_box(C.byref(d), C.byref(h)))
+        self.mapped = mapped
+        if mapped is None:
+            check(self.lib.mgx_square_create_box(C.byref(d), C.byref(h)))
+        else:
+            check(self.lib.mgx_square_create_mapped(C.byref(d), self.MAPPED[mapped], C.byref(h)))
         self.h = h
         self.degree = degree
         self.n_levels = self.lib.mgx_square_n_levels(h)
@@ -714,14 +722,21 @@ class Square:
         n = self.degree + 1
         return self._arr("mgx_square_prolong_1d", (2 * n - 1, n))
 
+    def _poisson_problem(self):
+        if self.mapped is not None:
+            raise ValueError("a mapped Square has no Poisson problem (rhs, bc, l2_error)")
+
     def rhs(self, l):
+        self._poisson_problem()
         return self._arr("mgx_square_rhs", (self.n_dofs(l),), l)
 
     def bc(self, l):
+        self._poisson_problem()
         n = self.lib.mgx_square_bc_count(self.h, l)
         return self._arr("mgx_square_bc_index", (n,), l), self._arr("mgx_square_bc_value", (n,), l)
 
     def l2_error(self, l, solution):
+        self._poisson_problem()
         s = np.ascontiguousarray(solution, dtype=np.float64)
         assert s.size == self.n_dofs(l)
         return self.lib.mgx_square_l2_error(self.h, l, s.ctypes.data_as(_lib.f64p))
@@ -741,6 +756,39 @@ class Square:
         out = np.empty((self.n_cells(l), 3, (self.degree + 1) ** 2))
         check(self.lib.mgx_square_coef_q(self.h, l, out.ctypes.data_as(_lib.f64p)))
         return out
+
+    # ---- geometry for the solution-dependent coefficients (mgx_square_solver_create_general) ----
+    def _filled(self, fn, shape, l):
+        out = np.empty(shape)
+        check(getattr(self.lib, fn)(self.h, l, out.ctypes.data_as(_lib.f64p)))
+        return out
+
+    def affine_metric(self, l):
+        """(M = J^-1 J^-T as [xx,yy,xy], det J) of the cells of level l of a box, J = h_l A with the box's jacobian A"""
+        m, det = np.zeros(3), C.c_double()
+        check(self.lib.mgx_square_affine_metric(self.h, l, m.ctypes.data_as(_lib.f64p), C.byref(det)))
+        return m, det.value
+
+    def unit_law_coefficient(self, l):
+        """[n_cells, 3, (p+1)^2] merged coefficient of the unit law (LAW_UNIT): JxW_q M on a box, the per-point tensor of
+        a mapped square"""
+        return self.coef_q(l)
+
+    def dof_coordinates(self, l):
+        """[n_dofs, 2] physical coordinates of the Gauss-Lobatto node of every DoF of level l"""
+        return self._filled("mgx_square_dof_coordinates", (self.n_dofs(l), 2), l)
+
+    def cell_nodes(self, l):
+        """[n_cells, (p+1)^2, 2] the nodes of every cell, x fastest"""
+        return self._filled("mgx_square_cell_nodes", (self.n_cells(l), (self.degree + 1) ** 2, 2), l)
+
+    def unit_q(self, l):
+        """[n_cells, 3, (p+1)^2] JxW_q J^-1 J^-T of the isoparametric cells as [xx,yy,xy]"""
+        return self._filled("mgx_square_unit_q", (self.n_cells(l), 3, (self.degree + 1) ** 2), l)
+
+    def jxw_q(self, l):
+        """[n_cells, (p+1)^2] JxW_q of the isoparametric cells"""
+        return self._filled("mgx_square_jxw_q", (self.n_cells(l), (self.degree + 1) ** 2), l)
 
 
 def _cell_dofs(idx27, p):
@@ -823,6 +871,9 @@ class LaplaceOperator:
     def enable_coefficient_update(self, metric, det_jacobian):
         """affine geometry of the level: M = J^-1 J^-T as [xx,yy,zz,xy,xz,yz] and det J (Cube.affine_metric)"""
         m = np.ascontiguousarray(metric, dtype=np.float64)
+        if m.size == 3:  # a 2D operator: [xx,yy,xy] (Square.affine_metric)
+            check(self.lib.mgx_operator_enable_coefficient_update_2d(self.h, m.ctypes.data_as(_lib.f64p), float(det_jacobian)))
+            return
         assert m.size == 6
         check(self.lib.mgx_operator_enable_coefficient_update(self.h, m.ctypes.data_as(_lib.f64p), float(det_jacobian)))
 
@@ -833,6 +884,11 @@ class LaplaceOperator:
         w = np.ascontiguousarray(jxw_q, dtype=np.float64)
         p, n = C.c_void_p(), C.c_size_t()
         check(self.lib.mgx_operator_get_coefficient(self.h, C.byref(p), C.byref(n)))  # (refuses an operator without coef_q)
+        if 3 * w.size == n.value:  # a 2D operator (three tensor entries per point): Square.unit_q, Square.jxw_q
+            assert u.size == n.value
+            check(self.lib.mgx_operator_enable_coefficient_update_q_2d(self.h, u.ctypes.data_as(_lib.f64p),
+                                                                       w.ctypes.data_as(_lib.f64p)))
+            return
         assert u.size == n.value and 6 * w.size == n.value
         check(self.lib.mgx_operator_enable_coefficient_update_q(self.h, u.ctypes.data_as(_lib.f64p),
                                                                 w.ctypes.data_as(_lib.f64p)))
@@ -847,7 +903,8 @@ class LaplaceOperator:
         check(self.lib.mgx_compute_nonlinear_residual(self.h, int(law), dst.ptr, state.ptr))
 
     def get_coefficient(self):
-        """the operator's merged coefficient on the device, [n_cells * 6 * (p+1)^3] entries of its number type"""
+        """the operator's merged coefficient on the device, [n_cells * 6 * (p+1)^3] entries of its number type
+        ([n_cells * 3 * (p+1)^2] in two dimensions)"""
         p, n = C.c_void_p(), C.c_size_t()
         check(self.lib.mgx_operator_get_coefficient(self.h, C.byref(p), C.byref(n)))
         return DeviceVector(self.ctx, n.value, self.number, ptr=p)
@@ -956,7 +1013,9 @@ class MultigridSolver:
         (mgx_cube_solver_create_general: one rank; zero right-hand sides, homogeneous boundary values), on a Cartesian
         cube / box with the constant matrix `jacobian` of an affine map of the box (None: identity), or on a mapped cube
         with problem "cube" (sheared, shell_sector, shell=6|12; per-point geometry, jacobian None); per level, the
-        merged coefficient coef_q[l] ([n_cells, 6, (p+1)^3]; None: the unit-law tensor).
+        merged coefficient coef_q[l] ([n_cells, 6, (p+1)^3]; None: the unit-law tensor).  On a Square
+        (mgx_square_solver_create_general): the geometry is the square's own jacobian or map, coef_q[l] is
+        [n_cells, 3, (p+1)^2].
         polynomial: Chebyshev polynomial type of the level smoothers: "first_kind" is what
         MultigridSolver<dim,p,Number,Number2> sets (multigrid_solver.h:277-278), "fourth_kind" what
         the Number == Number2 specialisation sets (:951-952)"""
@@ -969,12 +1028,22 @@ class MultigridSolver:
         if isinstance(cube, Square):
             # MultigridSolver<2,p,...>: one rank, right-hand sides from the host; per_point: the operators in the
             # per-(cell, q) form with the tensor of Square.coef_q
-            if comm is not None or agglomerate is not True or device_rhs or general or jacobian is not None or coef_q is not None:
-                raise ValueError("MultigridSolver on a Square: one rank, host right-hand sides, no general hierarchy "
-                                 "(comm, agglomerate, device_rhs, general, jacobian, coef_q are not accepted)")
+            # general: mgx_square_solver_create_general (the geometry is the square's own: its jacobian or its map)
+            if comm is not None or agglomerate is not True or device_rhs or jacobian is not None or \
+                    (coef_q is not None and not general):
+                raise ValueError("MultigridSolver on a Square: one rank, host right-hand sides "
+                                 "(comm, agglomerate, device_rhs, jacobian are not accepted; coef_q with general only)")
             self.jacobian = None
-            check(self.lib.mgx_square_solver_create(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles, int(bool(per_point)),
-                                                    C.byref(self.s)))
+            if general:
+                cq = None
+                if coef_q is not None:
+                    keep = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in coef_q]
+                    cq = (_lib.f64p * len(keep))(*[None if a is None else a.ctypes.data_as(_lib.f64p) for a in keep])
+                check(self.lib.mgx_square_solver_create_general(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles, cq,
+                                                                C.byref(self.s)))
+            else:
+                check(self.lib.mgx_square_solver_create(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles,
+                                                        int(bool(per_point)), C.byref(self.s)))
             self.n_levels = self.s.n_levels
             self.max_level = self.n_levels - 1
             self.h = C.c_void_p(self.s.solver)
@@ -1195,7 +1264,8 @@ LAW_UNIT, LAW_MINIMAL_SURFACE = 0, 1
 
 class MinimalSurfaceProblem:
     """LaplaceProblem<dim> of minimal_surface/program.cc in 3D on the Cartesian cube / box or a mapped cube (curved cells,
-    boundary function at the mapped node coordinates): -div(grad u / sqrt(1 + |grad u|^2))
+    boundary function at the mapped node coordinates), or in 2D on a Square (box, sheared box or mapped; boundary
+    function of [n, 2] coordinates): -div(grad u / sqrt(1 + |grad u|^2))
     = 0 with Dirichlet values, Newton's method with a V-cycle-preconditioned CG per step and the reference's
     step-halving line search.  Vectors, norms and updates stay on the device; scalars cross to the host.
 
@@ -1212,7 +1282,12 @@ class MinimalSurfaceProblem:
         # interpolate_boundary_values(): zero in the interior, the boundary function on the Dirichlet DoFs
         u = np.zeros(n)
         c = cube.constrained(l)
-        u[c] = boundary(cube.dof_coordinates(l, jacobian)[c])
+        if isinstance(cube, Square):  # dimension = 2 (:73): coordinates [n, 2]; the geometry is the square's own
+            if jacobian is not None:
+                raise ValueError("MinimalSurfaceProblem on a Square: the jacobian belongs to the Square")
+            u[c] = boundary(cube.dof_coordinates(l)[c])
+        else:
+            u[c] = boundary(cube.dof_coordinates(l, jacobian)[c])
         self.solution = ctx.vector(n, F64, u)
         self.tentative = ctx.vector(n, F64)
         self.system_rhs = self.solver.get_vector(l, "rhs")

@@ -307,6 +307,16 @@ SIGNATURES = {
     "mgx_square_operator_desc": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(OperatorDesc)]),
     "mgx_square_coef_q": (C.c_int, [vp, C.c_int, f64p]),
     "mgx_square_solver_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CubeSolver)]),
+    # solution-dependent coefficient in two dimensions
+    "mgx_operator_enable_coefficient_update_2d": (C.c_int, [vp, f64p, C.c_double]),
+    "mgx_operator_enable_coefficient_update_q_2d": (C.c_int, [vp, f64p, f64p]),
+    "mgx_square_create_mapped": (C.c_int, [C.POINTER(SquareBoxDesc), C.c_int, C.POINTER(vp)]),
+    "mgx_square_affine_metric": (C.c_int, [vp, C.c_int, f64p, f64p]),
+    "mgx_square_dof_coordinates": (C.c_int, [vp, C.c_int, f64p]),
+    "mgx_square_cell_nodes": (C.c_int, [vp, C.c_int, f64p]),
+    "mgx_square_unit_q": (C.c_int, [vp, C.c_int, f64p]),
+    "mgx_square_jxw_q": (C.c_int, [vp, C.c_int, f64p]),
+    "mgx_square_solver_create_general": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(f64p), C.POINTER(CubeSolver)]),
     # include/mgx_dg.h
     "mgx_dg_operator_create": (C.c_int, [vp, C.POINTER(DGOperatorDesc), C.POINTER(vp)]),
     "mgx_dg_operator_destroy": (C.c_int, [vp]),

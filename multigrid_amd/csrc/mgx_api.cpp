@@ -2083,56 +2083,47 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
 /* ------------------------------------------------------------------------------------------
  * Solution-dependent coefficient of the general branch (MinimalSurfaceOperator, minimal_surface/program.cc:103-200)
  * ------------------------------------------------------------------------------------------ */
-int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metric[6], double det_jacobian)
+// the operator of a solution-dependent coefficient has a per-point tensor
+static int require_coef_q(mgx_operator_t op, const char *who)
 {
-  MGX_REQUIRE(op && metric, "mgx_operator_enable_coefficient_update: null argument");
-  MGX_TRY(refuse_2d(op->d, "mgx_operator_enable_coefficient_update", "no solution-dependent coefficients in two dimensions"));
-  if (!op->d.coef_q)
-    return fail(MGX_ERR_UNSUPPORTED,
-                "mgx_operator_enable_coefficient_update: the operator has no per-point coefficient (separable or "
-                "one-tensor-per-mesh branch); create it with mgx_operator_desc::coef_q set, e.g. to the unit-law tensor "
-                "JxW_q J^-1 J^-T");
-  // M = J^-1 J^-T is symmetric positive definite (leading minors), det J > 0
-  const double m0 = metric[0], m1 = metric[1], m2 = metric[2], m3 = metric[3], m4 = metric[4], m5 = metric[5];
-  const double det_m = m0 * (m1 * m2 - m5 * m5) - m3 * (m3 * m2 - m5 * m4) + m4 * (m3 * m5 - m1 * m4);
-  MGX_REQUIRE(det_jacobian > 0. && m0 > 0. && m0 * m1 - m3 * m3 > 0. && det_m > 0.,
-              "mgx_operator_enable_coefficient_update: the metric must be positive definite and det J > 0");
-  if (op->unit_q) // replaces a per-point geometry, which a kernel in flight may read
+  if (op->d.coef_q)
+    return MGX_OK;
+  return fail(MGX_ERR_UNSUPPORTED, std::string(who) + ": the operator has no per-point coefficient (separable or "
+                                     "one-tensor-per-mesh branch); create it with mgx_operator_desc::coef_q set, e.g. to the "
+                                     "unit-law tensor JxW_q J^-1 J^-T");
+}
+
+// an affine geometry replaces a per-point one, which a kernel in flight may read
+static int release_point_geometry(mgx_operator_t op)
+{
+  if (op->unit_q)
     {
       MGX_HIP(hipStreamSynchronize(op->ctx->stream));
       op->mem.release(op->unit_q);
       op->mem.release(op->jxw_q);
       op->unit_q = op->jxw_q = nullptr;
     }
-  std::copy(metric, metric + 6, op->metric);
-  op->det_jacobian = det_jacobian;
-  op->coef_update  = true;
   return MGX_OK;
 }
 
-int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *unit_q, const double *jxw_q)
+// per-point geometry: unit_q [n_cells][n_tensor][n_q] = JxW_q J^-1 J^-T with a positive diagonal, jxw_q [n_cells][n_q] > 0
+static int set_point_geometry(mgx_operator_t op, const double *unit_q, const double *jxw_q, const char *who)
 {
-  MGX_REQUIRE(op && unit_q && jxw_q, "mgx_operator_enable_coefficient_update_q: null argument");
-  MGX_TRY(refuse_2d(op->d, "mgx_operator_enable_coefficient_update_q", "no solution-dependent coefficients in two dimensions"));
-  if (!op->d.coef_q)
-    return fail(MGX_ERR_UNSUPPORTED,
-                "mgx_operator_enable_coefficient_update_q: the operator has no per-point coefficient (separable or "
-                "one-tensor-per-mesh branch); create it with mgx_operator_desc::coef_q set, e.g. to the unit-law tensor "
-                "JxW_q J^-1 J^-T");
-  const size_t n3 = (size_t)(op->d.p + 1) * (op->d.p + 1) * (op->d.p + 1), nc = op->d.n_cells;
+  const size_t nq = n_local_values(op->d.dim, op->d.p), nc = op->d.n_cells, nt = (size_t)n_tensor_entries(op->d.dim);
+  const size_t nd = (size_t)op->d.dim; // the diagonal entries come first: [xx,yy,zz,...] / [xx,yy,xy]
   bool         ok = true;
   for (size_t c = 0; c < nc && ok; ++c)
-    for (size_t q = 0; q < n3 && ok; ++q)
+    for (size_t q = 0; q < nq && ok; ++q)
       {
-        const double *u = unit_q + c * 6 * n3 + q;
-        ok              = jxw_q[c * n3 + q] > 0. && u[0] > 0. && u[n3] > 0. && u[2 * n3] > 0.; // (false for NaN)
+        ok = jxw_q[c * nq + q] > 0.; // (false for NaN)
+        for (size_t k = 0; k < nd && ok; ++k)
+          ok = unit_q[(c * nt + k) * nq + q] > 0.;
       }
-  MGX_REQUIRE(ok, "mgx_operator_enable_coefficient_update_q: JxW_q and the diagonal of JxW_q J^-1 J^-T must be positive at every "
-                  "quadrature point");
+  MGX_REQUIRE(ok, std::string(who) + ": JxW_q and the diagonal of JxW_q J^-1 J^-T must be positive at every quadrature point");
   // (a failed upload leaves the new arrays to the operator's arena and the present geometry in place)
   void *u_dev = nullptr, *w_dev = nullptr;
-  MGX_TRY(op->mem.upload_as(op->d.number, &u_dev, unit_q, nc * 6 * n3));
-  MGX_TRY(op->mem.upload_as(op->d.number, &w_dev, jxw_q, nc * n3));
+  MGX_TRY(op->mem.upload_as(op->d.number, &u_dev, unit_q, nc * nt * nq));
+  MGX_TRY(op->mem.upload_as(op->d.number, &w_dev, jxw_q, nc * nq));
   MGX_HIP(hipStreamSynchronize(op->ctx->stream)); // a kernel in flight may read the geometry this call replaces
   op->mem.release(op->unit_q);
   op->mem.release(op->jxw_q);
@@ -2142,12 +2133,76 @@ int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *un
   return MGX_OK;
 }
 
+/* MinimalSurfaceOperator<2,...>::initialize (minimal_surface/program.cc:112-117 with dimension = 2, :73): the mapping data
+ * evaluate_coefficient and compute_residual read, for affine cells */
+int mgx_operator_enable_coefficient_update_2d(mgx_operator_t op, const double metric[3], double det_jacobian)
+{
+  MGX_REQUIRE(op && metric, "mgx_operator_enable_coefficient_update_2d: null argument");
+  if (op->d.dim != 2)
+    return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_enable_coefficient_update_2d: not on a three-dimensional operator (call "
+                                     "mgx_operator_enable_coefficient_update)");
+  MGX_TRY(require_coef_q(op, "mgx_operator_enable_coefficient_update_2d"));
+  // M = J^-1 J^-T [xx, yy, xy] is symmetric positive definite, det J > 0
+  MGX_REQUIRE(det_jacobian > 0. && metric[0] > 0. && metric[0] * metric[1] - metric[2] * metric[2] > 0.,
+              "mgx_operator_enable_coefficient_update_2d: the metric must be positive definite and det J > 0");
+  MGX_TRY(release_point_geometry(op));
+  std::fill(op->metric, op->metric + 6, 0.);
+  std::copy(metric, metric + 3, op->metric);
+  op->det_jacobian = det_jacobian;
+  op->coef_update  = true;
+  return MGX_OK;
+}
+
+/* the same for curved cells: the per-point mapping data of MatrixFree<2> (minimal_surface/program.cc:125-131, inverse_jacobian
+ * and JxW of every quadrature point) */
+int mgx_operator_enable_coefficient_update_q_2d(mgx_operator_t op, const double *unit_q, const double *jxw_q)
+{
+  MGX_REQUIRE(op && unit_q && jxw_q, "mgx_operator_enable_coefficient_update_q_2d: null argument");
+  if (op->d.dim != 2)
+    return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_enable_coefficient_update_q_2d: not on a three-dimensional operator (call "
+                                     "mgx_operator_enable_coefficient_update_q)");
+  MGX_TRY(require_coef_q(op, "mgx_operator_enable_coefficient_update_q_2d"));
+  return set_point_geometry(op, unit_q, jxw_q, "mgx_operator_enable_coefficient_update_q_2d");
+}
+
+int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metric[6], double det_jacobian)
+{
+  MGX_REQUIRE(op && metric, "mgx_operator_enable_coefficient_update: null argument");
+  MGX_TRY(refuse_2d(op->d, "mgx_operator_enable_coefficient_update",
+                    "the arrays of this call are three-dimensional: call mgx_operator_enable_coefficient_update_2d"));
+  MGX_TRY(require_coef_q(op, "mgx_operator_enable_coefficient_update"));
+  // M = J^-1 J^-T is symmetric positive definite (leading minors), det J > 0
+  const double m0 = metric[0], m1 = metric[1], m2 = metric[2], m3 = metric[3], m4 = metric[4], m5 = metric[5];
+  const double det_m = m0 * (m1 * m2 - m5 * m5) - m3 * (m3 * m2 - m5 * m4) + m4 * (m3 * m5 - m1 * m4);
+  MGX_REQUIRE(det_jacobian > 0. && m0 > 0. && m0 * m1 - m3 * m3 > 0. && det_m > 0.,
+              "mgx_operator_enable_coefficient_update: the metric must be positive definite and det J > 0");
+  MGX_TRY(release_point_geometry(op));
+  std::copy(metric, metric + 6, op->metric);
+  op->det_jacobian = det_jacobian;
+  op->coef_update  = true;
+  return MGX_OK;
+}
+
+int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *unit_q, const double *jxw_q)
+{
+  MGX_REQUIRE(op && unit_q && jxw_q, "mgx_operator_enable_coefficient_update_q: null argument");
+  MGX_TRY(refuse_2d(op->d, "mgx_operator_enable_coefficient_update_q",
+                    "the arrays of this call are three-dimensional: call mgx_operator_enable_coefficient_update_q_2d"));
+  MGX_TRY(require_coef_q(op, "mgx_operator_enable_coefficient_update_q"));
+  return set_point_geometry(op, unit_q, jxw_q, "mgx_operator_enable_coefficient_update_q");
+}
+
 static int require_coefficient_update(mgx_operator_t op, int law, const char *who)
 {
   const std::string w(who);
   MGX_REQUIRE(law == MGX_LAW_UNIT || law == MGX_LAW_MINIMAL_SURFACE, w + ": unknown law");
   if (op->ctx->has_comm || op->plan)
     return fail(MGX_ERR_UNSUPPORTED, w + ": not on a decomposed mesh (single rank only)");
+  // (a two-dimensional operator that was not enabled: the refusal every 2D operator met before the _2d calls existed)
+  if (op->d.dim == 2 && !op->coef_update)
+    return fail(MGX_ERR_UNSUPPORTED, w + ": not on a two-dimensional operator without a geometry: call "
+                                         "mgx_operator_enable_coefficient_update_2d (affine cells) or "
+                                         "mgx_operator_enable_coefficient_update_q_2d (curved cells) first");
   MGX_REQUIRE(op->coef_update, w + ": call mgx_operator_enable_coefficient_update (affine geometry of the level) or "
                                    "mgx_operator_enable_coefficient_update_q (curved cells) first");
   MGX_REQUIRE(op->d.idx27_plain, w + ": the operator was created without idx27_plain (the state is read with its boundary values)");
@@ -2157,10 +2212,10 @@ static int require_coefficient_update(mgx_operator_t op, int law, const char *wh
 int mgx_evaluate_coefficient(mgx_operator_t op, int law, const void *state)
 {
   MGX_REQUIRE(op && state, "mgx_evaluate_coefficient: null argument");
-  MGX_TRY(refuse_2d(op->d, "mgx_evaluate_coefficient", "no solution-dependent coefficients in two dimensions"));
   MGX_TRY(require_coefficient_update(op, law, "mgx_evaluate_coefficient"));
-  launch_evaluate_coefficient(op->ctx->stream, op->d, op->d.coef_q, op->d.number, law == MGX_LAW_MINIMAL_SURFACE, op->metric,
-                              op->det_jacobian, op->unit_q, op->jxw_q, state);
+  (op->d.dim == 2 ? launch_evaluate_coefficient_2d : launch_evaluate_coefficient)(
+    op->ctx->stream, op->d, op->d.coef_q, op->d.number, law == MGX_LAW_MINIMAL_SURFACE, op->metric, op->det_jacobian, op->unit_q,
+    op->jxw_q, state);
   MGX_HIP(hipGetLastError());
   op->has_diag = false; // the inverse diagonal belongs to the previous coefficient
   return MGX_OK;
@@ -2180,7 +2235,6 @@ int mgx_compute_nonlinear_residual(mgx_operator_t op, int law, void *dst, const 
 {
   MGX_REQUIRE(op && dst && state, "mgx_compute_nonlinear_residual: null argument");
   MGX_REQUIRE(dst != state, "mgx_compute_nonlinear_residual: dst and state must not alias");
-  MGX_TRY(refuse_2d(op->d, "mgx_compute_nonlinear_residual", "no solution-dependent coefficients in two dimensions"));
   MGX_TRY(require_coefficient_update(op, law, "mgx_compute_nonlinear_residual"));
   hipStream_t s  = op->ctx->stream;
   const bool  ms = law == MGX_LAW_MINIMAL_SURFACE;
@@ -2194,7 +2248,10 @@ int mgx_compute_nonlinear_residual(mgx_operator_t op, int law, void *dst, const 
       MGX_HIP(hipMemsetAsync(dst, 0, number_size(op->d.number) * op->d.n_dofs, s));
       lists = CellLists(op->d);
     }
-  launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state, lists);
+  if (op->d.dim == 2)
+    launch_cell_nl_residual_2d(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state);
+  else
+    launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state, lists);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -3413,7 +3470,11 @@ int mgx_interpolate_to_coarse(mgx_transfer_t tr, void *coarse, const void *fine)
 {
   MGX_REQUIRE(tr && coarse && fine, "mgx_interpolate_to_coarse: null argument");
   mgx_operator_t cop = tr->coarse, fop = tr->fine;
-  MGX_TRY(refuse_2d(cop->d, "mgx_interpolate_to_coarse", "no solution-dependent coefficients in two dimensions"));
+  const int dim = cop->d.dim, ne = n_entities(dim);
+  if (dim == 2 && !cop->coef_update)
+    return fail(MGX_ERR_UNSUPPORTED, "mgx_interpolate_to_coarse: not on a two-dimensional transfer whose coarse operator has no "
+                                     "geometry: call mgx_operator_enable_coefficient_update_2d or _q_2d on the level operators "
+                                     "first (mgx_square_solver_create_general does)");
   if (cop->plan || fop->plan || cop->ctx->has_comm)
     return fail(MGX_ERR_UNSUPPORTED, "mgx_interpolate_to_coarse: not on a decomposed mesh (single rank only)");
   MGX_REQUIRE(cop->d.idx27_plain && fop->d.idx27_plain, "mgx_interpolate_to_coarse: the level operators need idx27_plain");
@@ -3423,15 +3484,16 @@ int mgx_interpolate_to_coarse(mgx_transfer_t tr, void *coarse, const void *fine)
     {
       // (the Gauss-Lobatto nodes mgx_operator_desc::shape_values is defined on)
       const std::vector<double> r = interpolation_matrix_1d(p);
-      std::vector<uint32_t>     idxc((size_t)cop->d.n_cells * 27), own(cop->d.n_cells, 0u);
+      // (two dimensions: 9 entities per cell, e = 3 cy + cx, the low 9 bits of the mask)
+      std::vector<uint32_t>     idxc((size_t)cop->d.n_cells * ne), own(cop->d.n_cells, 0u);
       MGX_HIP(hipMemcpy(idxc.data(), cop->d.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
       std::vector<uint8_t> seen(cop->d.n_dofs, 0);
       for (uint32_t c = 0; c < cop->d.n_cells; ++c)
-        for (int e = 0; e < 27; ++e)
+        for (int e = 0; e < ne; ++e)
           {
             if (entity_size(e, p) == 0)
               continue;
-            const uint32_t base = idxc[27 * (size_t)c + e];
+            const uint32_t base = idxc[(size_t)ne * c + e];
             MGX_REQUIRE(base < cop->d.n_dofs, "mgx_interpolate_to_coarse: index table out of range");
             if (!seen[base])
               {
@@ -3442,7 +3504,7 @@ int mgx_interpolate_to_coarse(mgx_transfer_t tr, void *coarse, const void *fine)
       MGX_TRY(tr->mem.upload(&tr->own_coarse, own));
       MGX_TRY(tr->mem.upload_as(cop->d.number, &tr->interp_1d, r.data(), r.size())); // (last: it marks the tables as built)
     }
-  launch_interpolate_to_coarse(s, tr->d, tr->interp_1d, tr->own_coarse, coarse, fine);
+  (dim == 2 ? launch_interpolate_to_coarse_2d : launch_interpolate_to_coarse)(s, tr->d, tr->interp_1d, tr->own_coarse, coarse, fine);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -4234,7 +4296,6 @@ int mgx_solver_reset_smoother(mgx_solver_t S, int level, double smoothing_range,
 int mgx_solver_update_coefficient(mgx_solver_t S, int law, const double *state_fine)
 {
   MGX_REQUIRE(S && state_fine, "mgx_solver_update_coefficient: null argument");
-  MGX_TRY(refuse_2d(S->matrix[0]->d, "mgx_solver_update_coefficient", "no solution-dependent coefficients in two dimensions"));
   if (S->ctx->has_comm)
     return fail(MGX_ERR_UNSUPPORTED, "mgx_solver_update_coefficient: not on a context with a communicator (single rank only)");
   if (S->agg_solver)
@@ -4277,8 +4338,8 @@ int mgx_solver_update_coefficient(mgx_solver_t S, int law, const double *state_f
           // the two precisions would no longer be the same operator up to storage.)
           mgx_operator_t A = S->matrix_dp[l], V = S->matrix[l];
           MGX_REQUIRE(V->d.n_cells == A->d.n_cells && V->d.p == A->d.p, "mgx_solver_update_coefficient: level operators differ");
-          launch_evaluate_coefficient(s, A->d, V->d.coef_q, V->d.number, law == MGX_LAW_MINIMAL_SURFACE, A->metric,
-                                      A->det_jacobian, A->unit_q, A->jxw_q, state);
+          (A->d.dim == 2 ? launch_evaluate_coefficient_2d : launch_evaluate_coefficient)(
+            s, A->d, V->d.coef_q, V->d.number, law == MGX_LAW_MINIMAL_SURFACE, A->metric, A->det_jacobian, A->unit_q, A->jxw_q, state);
           MGX_HIP(hipGetLastError());
           V->has_diag = false;
         }

@@ -575,6 +575,17 @@ namespace mgx
   void launch_prolongate_2d(hipStream_t s, const TransferData &t, void *fine, const void *coarse, bool add,
                             bool with_constraints);
   void launch_restrict_add_2d(hipStream_t s, const TransferData &t, void *coarse, const void *fine, bool with_constraints);
+  // ---- solution-dependent coefficients on quadrilaterals (mgx_nonlinear_2d.hip) ----
+  // launch_evaluate_coefficient, launch_cell_nl_residual and launch_interpolate_to_coarse for op.dim == 2: metric is
+  // [xx,yy,xy], coef_q and unit_q are [n_cells][3][n^2], jxw_q is [n_cells][n^2], own_c holds 9 bits per coarse cell.
+  // The residual adds the cells up as launch_cell_loop_2d does: the ordered assembly where the level has the tables (dst
+  // is written), else colour by colour (dst zeroed by the caller); the caller has checked that one of the two exists.
+  void launch_evaluate_coefficient_2d(hipStream_t s, const OperatorData &op, void *coef_q, int coef_number, bool minimal_surface,
+                                      const double *metric, double det, const void *unit_q, const void *jxw_q, const void *state);
+  void launch_cell_nl_residual_2d(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,
+                                  const void *unit_q, const void *jxw_q, void *dst, const void *state);
+  void launch_interpolate_to_coarse_2d(hipStream_t s, const TransferData &t, const void *r1d, const uint32_t *own_c, void *coarse,
+                                       const void *fine);
 
   // ---- vector kernels (mgx_vector.hip) ----
   void launch_copy_cast(hipStream_t s, void *dst, int dn, const void *src, int sn, size_t n);

@@ -27,6 +27,7 @@ namespace
     std::vector<uint32_t> idx9, idx9_plain, constrained, children, coords, dof_grid;
     std::vector<uint8_t>  weight_shift;
     std::vector<double>   bc_value, rhs;
+    std::vector<double>   unit_q, jxw_q; // mapped square: [n_cells][3][n^2], [n_cells][n^2]
   };
 } // namespace
 
@@ -35,6 +36,7 @@ struct mgx_square_s
   int                p = 0, roots[2] = {1, 1};
   double             origin = -0.9, h0 = 1.9;
   double             A[4] = {1, 0, 0, 1}, detA = 1, coef[3] = {1, 1, 0};
+  int                geometry = 0; // 0: the box; MGX_SQUARE_GEOMETRY_ANNULUS_SECTOR
   mgx_cube_t         element = nullptr; // a one-cell cube: the owner of the 1D arrays
   const double      *S = nullptr, *D = nullptr, *gw = nullptr, *gq = nullptr, *gll = nullptr, *P1 = nullptr;
   std::vector<Level> levels;
@@ -43,6 +45,15 @@ struct mgx_square_s
   {
     x = origin + A[0] * X + A[1] * Y;
     y = origin + A[2] * X + A[3] * Y;
+  }
+  // physical position of the point (X, Y) of the box (coordinates from its lower corner)
+  void   point(double X, double Y, double &x, double &y) const
+  {
+    if (geometry == 0)
+      return map(X, Y, x, y);
+    const double r = 0.5 + 0.5 * X / (roots[0] * h0), theta = 0.5 * 3.14159265358979323846264338327950288 * Y / (roots[1] * h0);
+    x = r * std::cos(theta);
+    y = r * std::sin(theta);
   }
   static double u(double x, double y) { return std::sin(3 * kPi * x) * std::sin(3 * kPi * y); }
   static double f(double x, double y) { return 2 * (3 * kPi) * (3 * kPi) * u(x, y); }
@@ -123,9 +134,9 @@ namespace
         for (int i = 0; i <= p; ++i)
           L.dof_grid[local_dof(&L.idx9_plain[9 * (size_t)c], p, i, j)] =
             (L.coords[2 * (size_t)c + 1] * (uint32_t)p + (uint32_t)j) * Gx + L.coords[2 * (size_t)c] * (uint32_t)p + (uint32_t)i;
-    // boundary values at the nodes
-    L.bc_value.resize(L.constrained.size());
-    for (size_t i = 0; i < L.constrained.size(); ++i)
+    // boundary values at the nodes (the Poisson problem of the box; a mapped square has none)
+    L.bc_value.resize(Q.geometry == 0 ? L.constrained.size() : 0);
+    for (size_t i = 0; i < L.bc_value.size(); ++i)
       {
         const uint32_t g  = L.dof_grid[L.constrained[i]], gx = g % Gx, gy = g / Gx;
         const uint32_t cx = std::min(gx / (uint32_t)p, L.N[0] - 1), cy = std::min(gy / (uint32_t)p, L.N[1] - 1);
@@ -238,11 +249,85 @@ namespace
   }
 
   bool valid(mgx_square_t q, int l) { return q && l >= 0 && l < (int)q->levels.size(); }
+
+  // the (p+1)^2 Gauss-Lobatto nodes of cell c, x fastest: xy[2 (j n + i)], placed by the exact map
+  void cell_nodes(const mgx_square_s &Q, const Level &L, uint32_t c, double *xy)
+  {
+    const int n = Q.p + 1;
+    for (int j = 0; j < n; ++j)
+      for (int i = 0; i < n; ++i)
+        Q.point(L.h * (L.coords[2 * (size_t)c] + Q.gll[i]), L.h * (L.coords[2 * (size_t)c + 1] + Q.gll[j]), xy[2 * (j * n + i)],
+                xy[2 * (j * n + i) + 1]);
+  }
+
+  // Per-point geometry of the isoparametric cells: with J the Jacobian of the degree-p interpolant of the cell nodes at a
+  // Gauss point, G = J^T J = [[a, b], [b, c]] and det J = sqrt(a c - b^2):  JxW J^-1 J^-T = (w / det J) [c, a, -b].
+  // unit [n_cells][3][n^2] and jxw [n_cells][n^2]; false: a cell with det J <= 0
+  bool point_geometry(const mgx_square_s &Q, const Level &L, double *unit, double *jxw)
+  {
+    const int           p = Q.p, n = p + 1, n2 = n * n;
+    std::vector<double> G((size_t)n * n), xy(2 * (size_t)n2);
+    for (int q = 0; q < n; ++q)
+      for (int i = 0; i < n; ++i)
+        {
+          double g = 0;
+          for (int r = 0; r < n; ++r)
+            g += Q.D[q * n + r] * Q.S[r * n + i];
+          G[q * n + i] = g;
+        }
+    for (uint32_t cell = 0; cell < L.n_cells; ++cell)
+      {
+        cell_nodes(Q, L, cell, xy.data());
+        for (int qy = 0; qy < n; ++qy)
+          for (int qx = 0; qx < n; ++qx)
+            {
+              double xa = 0, xb = 0, ya = 0, yb = 0; // d(x, y) / d(xi, eta)
+              for (int j = 0; j < n; ++j)
+                for (int i = 0; i < n; ++i)
+                  {
+                    const double da = G[qx * n + i] * Q.S[qy * n + j], db = Q.S[qx * n + i] * G[qy * n + j];
+                    xa += da * xy[2 * (j * n + i)];
+                    xb += db * xy[2 * (j * n + i)];
+                    ya += da * xy[2 * (j * n + i) + 1];
+                    yb += db * xy[2 * (j * n + i) + 1];
+                  }
+              const double det = xa * yb - xb * ya;
+              if (!(det > 0.))
+                return false;
+              const double w = Q.gw[qx] * Q.gw[qy], a = xa * xa + ya * ya, b = xa * xb + ya * yb, c = xb * xb + yb * yb;
+              const size_t q = (size_t)qy * n + qx;
+              if (unit)
+                {
+                  double *u = unit + (size_t)cell * 3 * n2 + q;
+                  u[0] = w * c / det, u[n2] = w * a / det, u[2 * n2] = -w * b / det;
+                }
+              if (jxw)
+                jxw[(size_t)cell * n2 + q] = w * det;
+            }
+      }
+    return true;
+  }
 } // namespace
+
+static int square_create(const mgx_square_box_desc *bd, int geometry, mgx_square_t *out);
 
 extern "C" {
 
-int mgx_square_create_box(const mgx_square_box_desc *bd, mgx_square_t *out)
+int mgx_square_create_box(const mgx_square_box_desc *bd, mgx_square_t *out) { return square_create(bd, 0, out); }
+
+int mgx_square_create_mapped(const mgx_square_box_desc *bd, int geometry, mgx_square_t *out)
+{
+  if (geometry != MGX_SQUARE_GEOMETRY_ANNULUS_SECTOR)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_mapped: unknown geometry");
+  if (bd && bd->jacobian)
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_square_create_mapped: a jacobian on a mapped square (its geometry is that "
+                                                  "of its own map; jacobian must be NULL)");
+  return square_create(bd, geometry, out);
+}
+
+} // extern "C"
+
+static int square_create(const mgx_square_box_desc *bd, int geometry, mgx_square_t *out)
 {
   if (!bd || !out || bd->degree < 1 || bd->degree > MGX_MAX_DEGREE || bd->n_refine < 0 || bd->n_refine > 14 || bd->roots[0] < 1 ||
       bd->roots[1] < 1 || !(bd->h0 > 0))
@@ -275,12 +360,29 @@ int mgx_square_create_box(const mgx_square_box_desc *bd, mgx_square_t *out)
   Q->gq      = mgx_cube_qpoints(Q->element);
   Q->gll     = mgx_cube_gll(Q->element);
   Q->P1      = mgx_cube_prolong_1d(Q->element);
+  Q->geometry = geometry;
   Q->levels.resize((size_t)bd->n_refine + 1);
   for (int l = 0; l <= bd->n_refine; ++l)
-    build_level(*Q, Q->levels[l], l);
+    {
+      Level &L = Q->levels[l];
+      build_level(*Q, L, l);
+      if (geometry != 0) // curved cells: the unit-law tensor is the operator's coefficient
+        {
+          const size_t n2 = (size_t)(Q->p + 1) * (Q->p + 1);
+          L.unit_q.resize((size_t)L.n_cells * 3 * n2);
+          L.jxw_q.resize((size_t)L.n_cells * n2);
+          if (!point_geometry(*Q, L, L.unit_q.data(), L.jxw_q.data()))
+            {
+              mgx_square_destroy(Q);
+              return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_mapped: a cell with det J <= 0");
+            }
+        }
+    }
   *out = Q;
   return MGX_OK;
 }
+
+extern "C" {
 
 int mgx_square_create(int degree, int n_subdiv, int n_refine, mgx_square_t *out)
 {
@@ -329,19 +431,38 @@ const double   *mgx_square_qpoints(mgx_square_t q) { return q->gq; }
 const double   *mgx_square_gll(mgx_square_t q) { return q->gll; }
 const double   *mgx_square_prolong_1d(mgx_square_t q) { return q->P1; }
 
+// the Poisson problem exists on the box only
+static bool refuse_mapped(mgx_square_t q, const char *who)
+{
+  if (q->geometry == 0)
+    return false;
+  mgx::report_error(MGX_ERR_UNSUPPORTED, (std::string(who) + ": not on a mapped square (no Poisson problem there)").c_str());
+  return true;
+}
+
 const double *mgx_square_rhs(mgx_square_t q, int l)
 {
+  if (refuse_mapped(q, "mgx_square_rhs"))
+    return nullptr;
   Level &L = q->levels[l];
   if (L.rhs.empty())
     build_rhs(*q, L);
   return L.rhs.data();
 }
-uint32_t        mgx_square_bc_count(mgx_square_t q, int l) { return (uint32_t)q->levels[l].constrained.size(); }
-const uint32_t *mgx_square_bc_index(mgx_square_t q, int l) { return q->levels[l].constrained.data(); }
-const double   *mgx_square_bc_value(mgx_square_t q, int l) { return q->levels[l].bc_value.data(); }
+uint32_t        mgx_square_bc_count(mgx_square_t q, int l) { return q->geometry == 0 ? (uint32_t)q->levels[l].constrained.size() : 0u; }
+const uint32_t *mgx_square_bc_index(mgx_square_t q, int l)
+{
+  return refuse_mapped(q, "mgx_square_bc_index") ? nullptr : q->levels[l].constrained.data();
+}
+const double *mgx_square_bc_value(mgx_square_t q, int l)
+{
+  return refuse_mapped(q, "mgx_square_bc_value") ? nullptr : q->levels[l].bc_value.data();
+}
 
 double mgx_square_l2_error(mgx_square_t q, int l, const double *sol)
 {
+  if (refuse_mapped(q, "mgx_square_l2_error"))
+    return std::nan("");
   const Level        &L = q->levels[l];
   const int           p = q->p, n = p + 1;
   std::vector<double> ul((size_t)n * n), t((size_t)n * n);
@@ -414,6 +535,77 @@ int mgx_square_operator_desc(mgx_square_t q, int l, int number, mgx_operator_des
   d->qweights      = q->gw;
   d->global_index  = L.dof_grid.data();
   d->dim           = 2;
+  if (q->geometry != 0) // curved cells: JxW_q J^-1 J^-T of every point (coef is not read then)
+    d->coef_q = L.unit_q.data();
+  return MGX_OK;
+}
+
+int mgx_square_affine_metric(mgx_square_t q, int l, double metric[3], double *det_jacobian)
+{
+  if (!valid(q, l) || !metric || !det_jacobian)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_affine_metric: bad argument");
+  if (q->geometry != 0)
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_square_affine_metric: not on a mapped square (curved cells: "
+                                                  "mgx_square_unit_q, mgx_square_jxw_q)");
+  // J = h A:  J^-1 J^-T = (A^T A)^-1 / h^2 = coef / (det(A) h^2)
+  const double h = q->levels[l].h, s = 1. / (q->detA * h * h);
+  metric[0] = q->coef[0] * s, metric[1] = q->coef[1] * s, metric[2] = q->coef[2] * s;
+  *det_jacobian = q->detA * h * h;
+  return MGX_OK;
+}
+
+int mgx_square_cell_nodes(mgx_square_t q, int l, double *out)
+{
+  if (!valid(q, l) || !out)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_cell_nodes: bad argument");
+  const size_t n2 = (size_t)(q->p + 1) * (q->p + 1);
+  for (uint32_t c = 0; c < q->levels[l].n_cells; ++c)
+    cell_nodes(*q, q->levels[l], c, out + 2 * n2 * c);
+  return MGX_OK;
+}
+
+int mgx_square_dof_coordinates(mgx_square_t q, int l, double *out)
+{
+  if (!valid(q, l) || !out)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_dof_coordinates: bad argument");
+  const Level        &L = q->levels[l];
+  const int           p = q->p, n = p + 1;
+  std::vector<double> xy(2 * (size_t)n * n);
+  for (uint32_t c = 0; c < L.n_cells; ++c)
+    {
+      cell_nodes(*q, L, c, xy.data());
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i)
+          {
+            const uint32_t d = local_dof(&L.idx9_plain[9 * (size_t)c], p, i, j);
+            out[2 * (size_t)d]     = xy[2 * (j * n + i)];
+            out[2 * (size_t)d + 1] = xy[2 * (j * n + i) + 1];
+          }
+    }
+  return MGX_OK;
+}
+
+int mgx_square_unit_q(mgx_square_t q, int l, double *out)
+{
+  if (!valid(q, l) || !out)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_unit_q: bad argument");
+  const Level &L = q->levels[l];
+  if (!L.unit_q.empty())
+    std::copy(L.unit_q.begin(), L.unit_q.end(), out);
+  else if (!point_geometry(*q, L, out, nullptr))
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_unit_q: a cell with det J <= 0");
+  return MGX_OK;
+}
+
+int mgx_square_jxw_q(mgx_square_t q, int l, double *out)
+{
+  if (!valid(q, l) || !out)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_jxw_q: bad argument");
+  const Level &L = q->levels[l];
+  if (!L.jxw_q.empty())
+    std::copy(L.jxw_q.begin(), L.jxw_q.end(), out);
+  else if (!point_geometry(*q, L, nullptr, out))
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_jxw_q: a cell with det J <= 0");
   return MGX_OK;
 }
 
@@ -423,6 +615,8 @@ int mgx_square_coef_q(mgx_square_t q, int l, double *out)
     return MGX_ERR_INVALID_ARGUMENT;
   const int    n  = q->p + 1;
   const size_t n2 = (size_t)n * n;
+  if (q->geometry != 0) // (the descriptor's coefficient is this tensor already)
+    return mgx_square_unit_q(q, l, out);
   for (size_t c = 0; c < q->levels[l].n_cells; ++c)
     for (int k = 0; k < 3; ++k)
       for (size_t p = 0; p < n2; ++p)
@@ -430,11 +624,34 @@ int mgx_square_coef_q(mgx_square_t q, int l, double *out)
   return MGX_OK;
 }
 
+// general: the hierarchy of mgx_square_solver_create_general with the tensors coef_q[l] (nullptr: the unit law)
+static int square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int degree_pre, int n_cycles, int per_point,
+                                bool general, const double *const *coef_q, mgx_cube_solver *out);
+
 int mgx_square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int degree_pre, int n_cycles, int per_point,
                              mgx_cube_solver *out)
 {
   if (!ctx || !q || !out || (vnumber != MGX_F32 && vnumber != MGX_F64))
     return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_solver_create: bad argument");
+  if (q->geometry != 0)
+    return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_square_solver_create: not on a mapped square (no Poisson problem there; "
+                                                  "mgx_square_solver_create_general)");
+  return square_solver_create(ctx, q, vnumber, degree_pre, n_cycles, per_point, false, nullptr, out);
+}
+
+int mgx_square_solver_create_general(mgx_context_t ctx, mgx_square_t q, int vnumber, int degree_pre, int n_cycles,
+                                     const double *const *coef_q, mgx_cube_solver *out)
+{
+  if (!ctx || !q || !out || (vnumber != MGX_F32 && vnumber != MGX_F64))
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_solver_create_general: bad argument");
+  return square_solver_create(ctx, q, vnumber, degree_pre, n_cycles, 1, true, coef_q, out);
+}
+
+} // extern "C"
+
+static int square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int degree_pre, int n_cycles, int per_point,
+                                bool general, const double *const *coef_q, mgx_cube_solver *out)
+{
   const int nl = (int)q->levels.size();
   std::memset(out, 0, sizeof(*out));
   out->n_levels    = nl;
@@ -448,7 +665,9 @@ int mgx_square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int
       mgx_operator_desc   d;
       std::vector<double> cq;
       mgx_square_operator_desc(q, l, MGX_F64, &d);
-      if (per_point)
+      if (general && coef_q && coef_q[l])
+        d.coef_q = coef_q[l];
+      else if (per_point && !d.coef_q) // (a mapped square: the descriptor carries its per-point tensor)
         {
           cq.resize((size_t)d.n_cells * 3 * (q->p + 1) * (q->p + 1));
           mgx_square_coef_q(q, l, cq.data());
@@ -463,6 +682,18 @@ int mgx_square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int
         {
           d.number = MGX_F32;
           status   = mgx_operator_create(ctx, &d, &out->matrix[l]);
+        }
+      // the geometry of the level.  Curved cells: kept once, in fp64 with matrix_dp[l]; mgx_solver_update_coefficient
+      // writes the tensor of an fp32 V-cycle operator from it
+      if (general && status == MGX_OK && q->geometry != 0)
+        status = mgx_operator_enable_coefficient_update_q_2d(out->matrix_dp[l], q->levels[l].unit_q.data(), q->levels[l].jxw_q.data());
+      else if (general && status == MGX_OK)
+        {
+          double metric[3], det;
+          mgx_square_affine_metric(q, l, metric, &det);
+          status = mgx_operator_enable_coefficient_update_2d(out->matrix_dp[l], metric, det);
+          if (status == MGX_OK && out->matrix[l] != out->matrix_dp[l])
+            status = mgx_operator_enable_coefficient_update_2d(out->matrix[l], metric, det);
         }
     }
   for (int l = 1; l < nl && status == MGX_OK; ++l)
@@ -484,12 +715,15 @@ int mgx_square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int
       std::vector<const double *>   rhs(nl), bcv(nl);
       std::vector<const uint32_t *> bci(nl);
       std::vector<uint32_t>         bcn(nl);
+      // (general hierarchy: the Newton update has a zero right-hand side until the caller writes one, and homogeneous
+      // boundary values)
+      std::vector<double> zero(general ? q->levels[nl - 1].n_dofs : 0, 0.);
       for (int l = 0; l < nl; ++l)
         {
-          rhs[l] = mgx_square_rhs(q, l);
+          rhs[l] = general ? zero.data() : mgx_square_rhs(q, l);
           bci[l] = q->levels[l].constrained.data();
           bcv[l] = q->levels[l].bc_value.data();
-          bcn[l] = (uint32_t)q->levels[l].constrained.size();
+          bcn[l] = general ? 0u : (uint32_t)q->levels[l].constrained.size();
         }
       mgx_solver_desc sd;
       sd.n_levels    = nl;
@@ -513,5 +747,3 @@ int mgx_square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int
     }
   return status;
 }
-
-} // extern "C"

@@ -8,8 +8,12 @@ Prints the reference's lines: "Residual norm: ... in ... steps to ...", "Computi
 --geometry: the same on a mapped mesh with curved cells (per-point geometry): the sheared box, one equiangular sector of
 the shell (a box of one coarse cell, n_refine times refined) or the whole hyper_shell(0, 0.5, 1, 6 | 12).
 
+--dim 2: the program as shipped (dimension = 2, :73) on the square [-0.9, 1]^2, the sheared square or the quarter annulus
+with curved cells (--geometry square|sheared|annulus_sector).
+
 Usage: python tools/minimal_surface.py [degree] [n_refine] [--amplitude A] [--vcycle f32|f64] [--tolerance T]
-                                       [--geometry cube|sheared|shell_sector|shell6|shell12]"""
+                                       [--geometry cube|sheared|shell_sector|shell6|shell12]
+                                       [--dim 2 [--geometry square|sheared|annulus_sector]]"""
 import argparse
 import os
 import sys
@@ -29,18 +33,33 @@ def main():
     ap.add_argument("--vcycle", choices=["f32", "f64"], default="f32", help="number type of the V-cycle (level_number)")
     ap.add_argument("--tolerance", type=float, default=1e-12, help="stop when the residual norm is below (:660)")
     ap.add_argument("--max-steps", type=int, default=100, help="n_inner_iterations (:620)")
-    ap.add_argument("--geometry", choices=["cube", "sheared", "shell_sector", "shell6", "shell12"], default="cube")
+    ap.add_argument("--geometry", choices=["cube", "sheared", "shell_sector", "shell6", "shell12", "square", "annulus_sector"],
+                    default=None)
+    ap.add_argument("--dim", type=int, choices=[2, 3], default=3, help="2: the program's own dimension (:73), on a Square")
     args = ap.parse_args()
+    if args.geometry is None:
+        args.geometry = "cube" if args.dim == 3 else "square"
+    allowed = ("square", "sheared", "annulus_sector") if args.dim == 2 else ("cube", "sheared", "shell_sector", "shell6", "shell12")
+    if args.geometry not in allowed:
+        ap.error("--dim %d takes --geometry %s" % (args.dim, " | ".join(allowed)))
 
     ctx = mg.Context(0)
-    if args.geometry == "cube":
+    if args.dim == 2:
+        if args.geometry == "annulus_sector":
+            cube = mg.Square(args.degree, 1, args.n_refine, mapped="annulus_sector")
+        else:
+            cube = mg.Square(args.degree, 1, args.n_refine, jacobian=[[1.0, 0.35], [0.15, 0.8]] if args.geometry == "sheared" else None)
+    elif args.geometry == "cube":
         cube = mg.Cube(args.degree, 1, args.n_refine)
     elif args.geometry in ("sheared", "shell_sector"):
         cube = mg.Cube(args.degree, n_refine=args.n_refine, box=(1, 1, 1), origin=-0.9, h0=1.9, geometry=args.geometry)
     else:
         cube = mg.Cube(args.degree, n_refine=args.n_refine, shell=int(args.geometry[5:]), problem="cube")
-    print("Testing FE_Q<3>(%d)" % args.degree)
-    if args.geometry == "cube":
+    print("Testing FE_Q<%d>(%d)" % (args.dim, args.degree))
+    if args.dim == 2:
+        print("Number of degrees of freedom: %d (%s, %d x %d cells, %d levels)"
+              % ((cube.n_dofs(cube.max_level), args.geometry) + cube.cells_per_dim2(cube.max_level) + (cube.n_levels,)), flush=True)
+    elif args.geometry == "cube":
         print("Number of degrees of freedom: %d (%d^3 cells, %d levels)"
               % (cube.n_dofs(cube.max_level), cube.cells_per_dim(cube.max_level), cube.n_levels), flush=True)
     else:
