@@ -265,7 +265,8 @@ typedef struct
    * two-dimensional level adds its cells up through the ordered assembly or, beyond 2^26 local values or from
    * "cell_colour_min" cells on, colour by colour (four colours on a structured mesh): never with atomics, every result is
    * bitwise reproducible.  Refused on such an operator with MGX_ERR_UNSUPPORTED: mgx_compute_residual,
-   * mgx_solver_compute_rhs, mgx_solver_set_agglomeration and mgx_dg_solver_create over such a hierarchy.  The
+   * mgx_solver_compute_rhs, mgx_solver_set_agglomeration, and mgx_dg_solver_create with 3D DG operators over such a
+   * hierarchy (2D DG operators over it are MultigridSolverDG in two dimensions, include/mgx_dg.h).  The
    * solution-dependent coefficients take their geometry through mgx_operator_enable_coefficient_update[_q]_2d (the 3D
    * pair is refused); mgx_evaluate_coefficient, mgx_compute_nonlinear_residual, mgx_interpolate_to_coarse and
    * mgx_solver_update_coefficient are refused with MGX_ERR_UNSUPPORTED until the operators were enabled. */

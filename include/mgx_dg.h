@@ -216,8 +216,11 @@ int mgx_dg_compute_rhs_mixed(mgx_dg_operator_t op, const mgx_dg_function *f, con
  * sqrt(sums[0] / sums[1]).  Block sums in double, added in a fixed order: the same bits in every run. */
 int mgx_dg_compute_l2_error(mgx_dg_operator_t op, const void *vec, const mgx_dg_function *u, double sums[2]);
 
-/* ---- MultigridSolverDG<3,p,Number,double> (common/multigrid_solver_dg.h:55-747): the DG level on top
- * of the FE_Q(p) multigrid hierarchy of the same mesh ---- */
+/* ---- MultigridSolverDG<dim,p,Number,double> (common/multigrid_solver_dg.h:55-747): the DG level on top
+ * of the FE_Q(p) multigrid hierarchy of the same mesh.  Every mgx_dg_solver_* and the three transfer entry points
+ * below serve dim = 3 (one or several ranks) and dim = 2 (one rank: 2D DG operators over the FE_Q solver of an
+ * mgx_square).  In 2D every result is bitwise reproducible: the DG -> FE_Q restriction, stand-alone or inside the cell
+ * kernel, adds without atomics in launches over cells that share no FE_Q DoF. ---- */
 typedef struct mgx_dg_solver_s *mgx_dg_solver_t;
 typedef struct
 {
@@ -237,9 +240,11 @@ typedef struct
    * entries), cfe is the decomposed FE_Q solver of the same partition, not agglomerated. */
   const uint32_t   *cell_global_id;
 } mgx_dg_solver_desc;
-/* ctor (:58-323), incl. smooth_dg.initialize: eigenvalue estimate with JacobiTransformed.  2D operators are refused
- * with MGX_ERR_UNSUPPORTED: there is no FE_Q hierarchy in two dimensions (include/mgx.h).  So are operators with Neumann
- * faces: the FE_Q levels constrain every boundary DoF, their coarse correction would be that of another problem. */
+/* ctor (:58-323), incl. smooth_dg.initialize: eigenvalue estimate with JacobiTransformed.  Refused with
+ * MGX_ERR_UNSUPPORTED: 2D operators with cfe == NULL; DG operators and an FE_Q hierarchy of different dimensions;
+ * operators with Neumann faces (the FE_Q levels constrain every boundary DoF, their coarse correction would be that of
+ * another problem); in 2D, cells whose restriction would need more than 32 launches (cells c, c + 4, ... of an
+ * mgx_square share no DoF: 4 launches; any other cell order is coloured here).  A refused call leaves nothing behind. */
 int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_dg_solver_t *solver);
 int mgx_dg_solver_destroy(mgx_dg_solver_t solver);
 int mgx_dg_solver_smoother_info(mgx_dg_solver_t solver, mgx_smoother_info *info);

@@ -647,6 +647,7 @@ class Square:
         d = _lib.SquareBoxDesc(degree, n_refine, (C.c_int * 2)(*box), origin, 1.9 if h0 is None else h0,
                                None if self._jac is None else self._jac.ctypes.data_as(_lib.f64p))
         self.mapped = mapped
+        self.origin = origin
         if mapped is None:
             check(self.lib.mgx_square_create_box(C.byref(d), C.byref(h)))
         else:
@@ -1701,12 +1702,18 @@ class DGMultigridSolver:
     """multigrid::MultigridSolverDG<3,p,Number,double> (common/multigrid_solver_dg.h:55-747) on the
     Cartesian meshes of the Cube provider: a DG level (operator, block-Jacobi Chebyshev smoother) on
     top of the FE_Q(p) hierarchy of the same mesh, V-cycle in `vcycle_number`, outer CG in fp64.
-    The DG cells are the cells of the cube's finest level in the provider's order."""
+    The DG cells are the cells of the cube's finest level in the provider's order.
+    A Square in place of the cube gives MultigridSolverDG<2,...> (poisson_dg/program.cc with dimension = 2) on one rank:
+    cell_ijk then has two columns."""
 
     def __init__(self, ctx, cube, basis=DG_HERMITE, degree_pre=3, vcycle_number=F32, comm=None):
         """comm: Communicator of a decomposed cube (box form): the DG cells get ghost cells, the FE_Q
         hierarchy is the decomposed one (not agglomerated: its smoothers are re-configured)"""
         self.ctx, self.cube, self.lib = ctx, cube, ctx.lib
+        self.h = self.cfe = self.matrix_dg = self.matrix_dg_dp = None
+        if isinstance(cube, Square):
+            self._init_square(ctx, cube, basis, degree_pre, vcycle_number, comm)
+            return
         l = cube.max_level
         local, whole = (np.array(v, dtype=np.int64) for v in cube.cells_per_dim3(l))
         procs = whole // local
@@ -1725,6 +1732,42 @@ class DGMultigridSolver:
         d = _lib.DGSolverDesc(self.matrix_dg.h, self.matrix_dg_dp.h, self.cfe.h, degree_pre, gid.ctypes.data_as(_lib.u32p))
         h = C.c_void_p()
         check(self.lib.mgx_dg_solver_create(ctx.h, C.byref(d), C.byref(h)))
+        self.h = h
+        self.vnumber = vcycle_number
+        self.cell_gid = gid
+
+    def _init_square(self, ctx, sq, basis, degree_pre, vcycle_number, comm):
+        """the Cartesian box of a Square, one rank: neighbours and global cell ids (i + nx j, the layout the start vector
+        of the eigenvalue estimate is defined in) from the provider's cell positions"""
+        if comm is not None:
+            raise ValueError("DGMultigridSolver on a Square: one rank (comm is not accepted)")
+        if sq.mapped is not None or sq._jac is not None:
+            raise ValueError("DGMultigridSolver on a Square: the Cartesian box only (no jacobian, not mapped)")
+        l = sq.max_level
+        nx, ny = sq.cells_per_dim2(l)
+        ij = sq.cell_coords(l).astype(np.int64)
+        pos = np.empty((ny, nx), dtype=np.int64)
+        pos[ij[:, 1], ij[:, 0]] = np.arange(len(ij))
+        nb = np.full((len(ij), 4), DG_BOUNDARY, dtype=np.int32)
+        for f, (d, s) in enumerate(((0, -1), (0, 1), (1, -1), (1, 1))):   # face 2d+s
+            q = ij.copy()
+            q[:, d] += s
+            ok = (q[:, d] >= 0) & (q[:, d] < (nx, ny)[d])
+            nb[ok, f] = pos[q[ok, 1], q[ok, 0]]
+        self.neighbours, self.cell_ijk = nb, ij.astype(np.int32)
+        gid = (ij[:, 0] + nx * ij[:, 1]).astype(np.uint32)
+        jac = np.eye(2) * sq.cell_size(l)
+        try:
+            self.cfe = MultigridSolver(ctx, sq, degree_pre, degree_pre, 1, vcycle_number)
+            self.matrix_dg = DGLaplaceOperator(ctx, sq.degree, basis, nb, jac, vcycle_number, dim=2)
+            self.matrix_dg_dp = DGLaplaceOperator(ctx, sq.degree, basis, nb, jac, F64, dim=2)
+            self.matrix_dg_dp.set_cell_positions((sq.origin, sq.origin), self.cell_ijk)
+            d = _lib.DGSolverDesc(self.matrix_dg.h, self.matrix_dg_dp.h, self.cfe.h, degree_pre, gid.ctypes.data_as(_lib.u32p))
+            h = C.c_void_p()
+            check(self.lib.mgx_dg_solver_create(ctx.h, C.byref(d), C.byref(h)))
+        except Exception:
+            self.close()
+            raise
         self.h = h
         self.vnumber = vcycle_number
         self.cell_gid = gid
@@ -1766,9 +1809,11 @@ class DGMultigridSolver:
         if getattr(self, "h", None):
             self.lib.mgx_dg_solver_destroy(self.h)
             self.h = None
-            self.matrix_dg.clear()
-            self.matrix_dg_dp.clear()
-            self.cfe.close()
+        for part in ("matrix_dg", "matrix_dg_dp", "cfe"):   # (a constructor that failed half-way leaves some of them)
+            obj = getattr(self, part, None)
+            if obj is not None:
+                obj.clear() if part != "cfe" else obj.close()
+                setattr(self, part, None)
 
 
 class DGLevelTransfer:

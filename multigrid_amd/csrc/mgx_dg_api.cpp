@@ -110,6 +110,22 @@ struct mgx_dg_solver_s
   uint32_t          n_cells = 0, n_cg = 0;
   bool              cg_eight_colours = false; // cells c, c + 8, ... of the FE_Q level share no DoF
   void             *cg_defect = nullptr, *cg_update = nullptr; // the FE_Q solver's finest-level vectors
+  // Two dimensions (dim == 2: quadrilaterals, idx27 is the 9-entry table): the restriction never uses atomics.  Cells c,
+  // c + 4, ... share no DoF (cg_four_colours, checked), or the cells are coloured here: colour k is
+  // cg_order[cg_colour_start[k] .. cg_colour_start[k + 1])
+  int                   dim = 3;
+  bool                  cg_four_colours = false;
+  uint32_t             *cg_order = nullptr; // device
+  std::vector<uint32_t> cg_colour_start;    // empty: no lists
+  // the launches of a restriction: 3D stride 8 or one launch (atomics); 2D stride 4 or the colour lists
+  mgx::DisjointCells restriction_launches() const
+  {
+    mgx::DisjointCells d;
+    d.stride = cg_eight_colours ? 8u : (cg_four_colours ? 4u : 1u);
+    if (!cg_colour_start.empty())
+      d.lists = mgx::CellLists(cg_order, cg_colour_start.data(), (int)cg_colour_start.size() - 1);
+    return d;
+  }
 };
 
 // the two public handles of a step
@@ -1030,7 +1046,8 @@ namespace
 
   // vmult_residual_and_restrict_to_cg (laplace_operator_dg.h:853-861, action 1 :1798-1819): cg = sum over the cells of
   // P^T (rhs - A lhs), inside the cell kernel.  Cells c, c + 8, ... share no FE_Q DoF when the mesh is in forest order:
-  // eight launches with plain adds (the sum is then the same in every run); one launch with atomics otherwise.
+  // eight launches with plain adds (the sum is then the same in every run); one launch with atomics otherwise.  Two
+  // dimensions: four launches (cells c, c + 4, ...), or one per colour of the solver's own colouring; never atomics.
   int dg_residual_and_restrict(mgx_dg_solver_t S, void *cg, const void *rhs, const void *lhs)
   {
     hipStream_t       s  = (hipStream_t)mgx_context_stream(S->ctx);
@@ -1043,16 +1060,27 @@ namespace
     l.idx27   = S->idx27;
     l.P1      = S->P1;
     l.n_cells = op->n_cells;
-    if (!S->cg_eight_colours)
+    const mgx::DisjointCells launches = S->restriction_launches();
+    if (launches.lists.n > 0)
+      {
+        l.plain = 1;
+        for (int k = 0; k < launches.lists.n; ++k)
+          {
+            l.cell_list = launches.lists.cells + launches.lists.start[k];
+            l.n_cells   = launches.lists.start[k + 1] - launches.lists.start[k]; // of this launch: the length of its list
+            MGX_TRY(launch_cells(op, l));
+          }
+      }
+    else if (launches.stride == 1)
       MGX_TRY(launch_cells(op, l));
     else
       {
         l.plain       = 1;
-        l.cell_stride = 8;
-        for (uint32_t k = 0; k < 8 && k < op->n_cells; ++k)
+        l.cell_stride = launches.stride;
+        for (uint32_t k = 0; k < launches.stride && k < op->n_cells; ++k)
           {
             l.cell_first = k;
-            l.n_cells    = (op->n_cells - k + 7) / 8;
+            l.n_cells    = (op->n_cells - k + launches.stride - 1) / launches.stride;
             MGX_TRY(launch_cells(op, l));
           }
       }
@@ -1074,14 +1102,14 @@ namespace
       {
         MGX_TRY(mgx_dg_vmult_residual(L.A, L.t, L.defect, L.update));
         MGX_HIP(hipMemsetAsync(S->cg_defect, 0, dg_nsz(S->number) * S->n_cg, s));
-        mgx::launch_dg_cg_transfer(s, S->number, S->degree, false, S->cg_defect, L.t, S->idx27, S->n_cells, S->P1,
-                                   S->cg_eight_colours);
+        mgx::launch_dg_cg_transfer(s, S->number, S->degree, S->dim, false, S->cg_defect, L.t, S->idx27, S->n_cells, S->P1,
+                                   S->restriction_launches());
         if (S->decomposed) // FE_Q DoFs on a rank interface collect the contributions of all sharers
           MGX_TRY(mgx_exchange_add(S->fe, S->cg_defect));
       }
     MGX_TRY(mgx_solver_v_cycle(S->cfe)); // :622
     // prolongate_add_cg_to_dg (:625; laplace_operator_dg.h:1863-1894)
-    mgx::launch_dg_cg_transfer(s, S->number, S->degree, true, L.update, S->cg_update, S->idx27, S->n_cells, S->P1);
+    mgx::launch_dg_cg_transfer(s, S->number, S->degree, S->dim, true, L.update, S->cg_update, S->idx27, S->n_cells, S->P1);
     MGX_HIP(hipGetLastError());
     return dg_smoother_apply(L, true); // :629
   }
@@ -1093,9 +1121,12 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
 {
   MGX_REQUIRE(ctx && desc && out && desc->matrix_dg && desc->matrix_dg_dp, "mgx_dg_solver_create: null argument");
   mgx_dg_operator_t A = desc->matrix_dg, Ad = desc->matrix_dg_dp;
-  if (A->dim == 2 || Ad->dim == 2) // (before the FE_Q solver is looked at: none can exist for these operators)
-    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: 2D DG operator -- there is no FE_Q hierarchy in two dimensions; "
-                                        "use mgx_dg_plain_solver_create");
+  if ((A->dim == 2 || Ad->dim == 2) && !desc->cfe) // (before the null check of cfe: a refusal, not an invalid argument)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: 2D DG operators, but the descriptor names no FE_Q hierarchy in two "
+                                        "dimensions (cfe: a solver made from an mgx_square); without one use "
+                                        "mgx_dg_plain_solver_create");
+  if (A->dim != Ad->dim)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: matrix_dg and matrix_dg_dp differ in their dimension");
   if (A->has_neumann || Ad->has_neumann)
     return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: DG operator with Neumann faces -- the FE_Q levels of the hierarchy "
                                         "constrain every boundary DoF; use mgx_dg_plain_solver_create");
@@ -1107,9 +1138,11 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
   const int      lmax = mgx_solver_n_levels(desc->cfe) - 1;
   mgx_operator_t fe   = nullptr;
   MGX_TRY(mgx_solver_get_operator(desc->cfe, lmax, 0, &fe));
-  if (mgx::operator_dim(fe) == 2)
-    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: the FE_Q hierarchy is two-dimensional -- a DG level on top of an "
-                                        "FE_Q hierarchy is not built in two dimensions; use mgx_dg_plain_solver_create");
+  const int dim = A->dim == 2 ? 2 : 3;
+  if (mgx::operator_dim(fe) != dim) // (before cells and degree are compared: they cannot agree)
+    return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: the DG operators are " + std::to_string(dim) + "D, the FE_Q hierarchy is " +
+                                          std::to_string(mgx::operator_dim(fe)) + "D -- a DG level sits on the FE_Q hierarchy of its own mesh");
+  const int       ne    = dim == 2 ? 9 : 27; // entries of a cell in the compressed index table
   const uint32_t *idx27 = nullptr;
   uint32_t        nc = 0, ncg = 0;
   int             p = 0;
@@ -1130,26 +1163,71 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
   S->idx27 = idx27;
   S->n_cells = nc;
   S->n_cg = ncg;
+  S->dim = dim;
   {
-    // forest order (the same child of every parent in one class): checked, not assumed
-    std::vector<uint32_t> h27(27 * (size_t)nc), stamp(ncg, 0xFFFFFFFFu);
+    // forest order (the same child of every parent in one class: 8 classes of cells c, c + 8, ... in three dimensions,
+    // 4 in two): checked, not assumed
+    const uint32_t        classes = dim == 2 ? 4u : 8u;
+    std::vector<uint32_t> h27(ne * (size_t)nc), stamp(ncg, 0xFFFFFFFFu);
     MGX_HIP(hipMemcpy(h27.data(), idx27, sizeof(uint32_t) * h27.size(), hipMemcpyDeviceToHost));
-    bool ok = nc >= 64;
-    for (uint32_t k = 0; k < 8 && ok; ++k)
-      for (uint32_t c = k; c < nc && ok; c += 8)
-        for (int e = 0; e < 27 && ok; ++e)
+    // an entity's first DoF identifies it; p = 1: the entry of an entity without DoFs (inside a line, quad or hex) is
+    // no address
+    const auto key = [&](uint32_t c, int e) {
+      const uint32_t v = h27[ne * (size_t)c + e];
+      if (S->degree == 1 && (e % 3 == 1 || (e / 3) % 3 == 1 || e / 9 == 1))
+        return 0xFFFFFFFFu;
+      return v < ncg ? v : 0xFFFFFFFFu;
+    };
+    bool ok = nc >= classes * classes;
+    for (uint32_t k = 0; k < classes && ok; ++k)
+      for (uint32_t c = k; c < nc && ok; c += classes)
+        for (int e = 0; e < ne && ok; ++e)
           {
-            const uint32_t v = h27[27 * (size_t)c + e];
-            if (v == 0xFFFFFFFFu || v >= ncg)
+            const uint32_t v = key(c, e);
+            if (v == 0xFFFFFFFFu)
               continue;
-            if (S->degree == 1 && (e % 3 == 1 || (e / 3) % 3 == 1 || e / 9 == 1)) // entity without DoFs
-              continue;
-            // an entity's first DoF identifies it; stamp = class * nc + cell would overflow: class and cell apart
-            const uint32_t mark = k * 0x10000000u + (c >> 3);
+            // stamp = class * nc + cell would overflow: class and cell apart
+            const uint32_t mark = k * 0x10000000u + c / classes;
             ok                  = stamp[v] == 0xFFFFFFFFu || (stamp[v] >> 28) != k || stamp[v] == mark;
             stamp[v]            = mark;
           }
-    S->cg_eight_colours = ok && nc < 0x80000000u;
+    ok = ok && nc / classes < 0x10000000u;
+    (dim == 2 ? S->cg_four_colours : S->cg_eight_colours) = ok;
+    if (dim == 2 && !ok)
+      {
+        // fewer than 16 cells or another cell order: greedy colours over the cells in their order, as colour_cells of
+        // the FE_Q operator (mgx_api.cpp) finds them; two cells conflict when they share an entity with DoFs.  There
+        // is no launch with atomics to fall back to in two dimensions.
+        std::vector<uint32_t> used(ncg, 0u), colour(nc, 0u), count(33, 0u);
+        uint32_t              n_colours = 0;
+        for (uint32_t c = 0; c < nc; ++c)
+          {
+            uint32_t mask = 0;
+            for (int e = 0; e < ne; ++e)
+              if (const uint32_t v = key(c, e); v != 0xFFFFFFFFu)
+                mask |= used[v];
+            uint32_t col = 0;
+            while (col < 32 && ((mask >> col) & 1u))
+              ++col;
+            if (col == 32)
+              return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: the cells of the FE_Q level need more than 32 colours for a "
+                                                  "DG -> FE_Q restriction without atomics");
+            colour[c] = col;
+            ++count[col];
+            n_colours = std::max(n_colours, col + 1);
+            for (int e = 0; e < ne; ++e)
+              if (const uint32_t v = key(c, e); v != 0xFFFFFFFFu)
+                used[v] |= 1u << col;
+          }
+        std::vector<uint32_t> order(nc), fill(n_colours + 1, 0u);
+        for (uint32_t k = 0; k < n_colours; ++k)
+          fill[k + 1] = fill[k] + count[k];
+        S->cg_colour_start = fill;
+        for (uint32_t c = 0; c < nc; ++c)
+          order[fill[colour[c]]++] = c;
+        if (nc > 0)
+          MGX_TRY(S->mem.upload(&S->cg_order, order));
+      }
   }
   hipStream_t s = (hipStream_t)mgx_context_stream(ctx);
   MGX_TRY(dg_level_allocate(S->mem, S->level, A, true, s));
@@ -1202,7 +1280,8 @@ int mgx_dg_restrict_to_cg(mgx_dg_solver_t S, void *cg_dst, const void *dg_src)
   MGX_REQUIRE(S && cg_dst && dg_src, "mgx_dg_restrict_to_cg: null argument");
   hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
   MGX_HIP(hipMemsetAsync(cg_dst, 0, dg_nsz(S->number) * S->n_cg, s));
-  mgx::launch_dg_cg_transfer(s, S->number, S->degree, false, cg_dst, dg_src, S->idx27, S->n_cells, S->P1, S->cg_eight_colours);
+  mgx::launch_dg_cg_transfer(s, S->number, S->degree, S->dim, false, cg_dst, dg_src, S->idx27, S->n_cells, S->P1,
+                             S->restriction_launches());
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -1217,7 +1296,7 @@ int mgx_dg_prolongate_add_cg_to_dg(mgx_dg_solver_t S, void *dg_dst, const void *
 {
   MGX_REQUIRE(S && dg_dst && cg_src, "mgx_dg_prolongate_add_cg_to_dg: null argument");
   hipStream_t s = (hipStream_t)mgx_context_stream(S->ctx);
-  mgx::launch_dg_cg_transfer(s, S->number, S->degree, true, dg_dst, cg_src, S->idx27, S->n_cells, S->P1);
+  mgx::launch_dg_cg_transfer(s, S->number, S->degree, S->dim, true, dg_dst, cg_src, S->idx27, S->n_cells, S->P1);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }

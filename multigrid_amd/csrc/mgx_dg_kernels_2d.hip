@@ -17,7 +17,8 @@
 // have an odd pitch, the per-cell stride is congruent to p+1 modulo the 32 banks.  Neighbour data is read straight
 // from the source vector: two nodes per face point for the Hermite-like basis, a contracted line otherwise.  The
 // inverse diagonal of the block-Jacobi preconditioner is a table of 16 x (p+1)^2 values (one set per combination of
-// Dirichlet faces).  No atomics; every entry has one writer: the same bits in every run.
+// Dirichlet faces).  No atomics; every entry has one writer: the same bits in every run.  (Action kRestrict adds the
+// residual into an FE_Q vector, where cells share entries: its launches cover cells that share none, one after the other.)
 #include "mgx_dg_device.hpp"
 
 namespace
@@ -81,6 +82,71 @@ namespace
         ld_line<N>(U, a * PX, 1, q);
         mul_Et<N>(c, q, r);
       }
+  }
+
+  // One direction of the transposed embedding of FE_Q(p) in the DG space (laplace_operator_dg.h:1803,
+  // local_basis_transformer->apply<true>): out[m] = sum_i P1[i][m] in[i], summed in the order of the stand-alone transfer
+  // (dg_cg_transfer_kernel_2d).  An unrolled product keeps all of P1 in scalar registers, 2 n^2 of them in double: more
+  // than a wave has from p = 8 on (profiles/feq_2d_code_static.txt).  Those instantiations (rolled_P1) take the line from
+  // LDS value by value in a loop that is not unrolled, with one row of P1 in scalar registers at a time.
+  template <int P, typename T>
+  constexpr bool rolled_P1()
+  {
+    return sizeof(T) == 8 && P >= 8;
+  }
+  template <int N, typename T>
+  __device__ __forceinline__ void mul_P1t(const T *__restrict__ P1, const T (&in)[N], T (&out)[N])
+  {
+#pragma unroll
+    for (int m = 0; m < N; ++m)
+      {
+        T s = P1[m] * in[0];
+#pragma unroll
+        for (int i = 1; i < N; ++i)
+          s = fma(P1[i * N + m], in[i], s);
+        out[m] = s;
+      }
+  }
+  template <int N, typename T>
+  __device__ __forceinline__ void mul_P1t_rolled(const T *__restrict__ P1, const T *line, int stride, T (&out)[N])
+  {
+#pragma unroll
+    for (int m = 0; m < N; ++m)
+      out[m] = T(0);
+#pragma unroll 1
+    for (int i = 0; i < N; ++i)
+      {
+        const T x = line[i * stride];
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+          out[m] = fma(P1[i * N + m], x, out[m]);
+      }
+  }
+
+  // r[0 .. p] of the y-line i of an FE_Q cell added into the vector through the cell's nine entries ix of the compressed
+  // index table (first DoF of every vertex / line / quad entity, [3 cy + cx]; constrained: 0xFFFFFFFF).  Plain
+  // read-modify-writes: the cells of a launch share no FE_Q DoF.  For one j the lanes of a cell touch consecutive DoFs of
+  // the quad interior and of the bottom and top lines.  p = 1: the entries of the entities without DoFs are not read.
+  template <int P, typename T>
+  __device__ __forceinline__ void add_fe_q_column_2d(T *__restrict__ dst, const uint32_t *__restrict__ ix, int i, const T (&r)[P + 1])
+  {
+    const int      cx = i == 0 ? 0 : (i == P ? 2 : 1);
+    const uint32_t ox = cx == 1 ? (uint32_t)(i - 1) : 0u;
+    const uint32_t b0 = ix[cx], b2 = ix[6 + cx];
+    if (b0 != 0xFFFFFFFFu)
+      dst[b0 + ox] += r[0];
+    if constexpr (P > 1)
+      {
+        const uint32_t b1 = ix[3 + cx];
+        if (b1 != 0xFFFFFFFFu)
+          {
+#pragma unroll
+            for (int j = 1; j < P; ++j)
+              dst[b1 + (cx == 1 ? (uint32_t)((j - 1) * (P - 1)) + ox : (uint32_t)(j - 1))] += r[j];
+          }
+      }
+    if (b2 != 0xFFFFFFFFu)
+      dst[b2 + ox] += r[P];
   }
 
   // NEUMANN: as in the 3D kernel -- a negative neighbour entry is MGX_DG_BOUNDARY or MGX_DG_NEUMANN, the inverse diagonals
@@ -392,6 +458,41 @@ namespace
               A.dst[lbase + i] = A.rhs[lbase + i] - y[i];
           }
       }
+    else if constexpr (ACTION == kRestrict)
+      {
+        // laplace_operator_dg.h:1798-1819: the residual, taken to the FE_Q basis of the cell by P1^T along x (this
+        // thread's x-line) and along y (its y-line), added into A.cg through the 9-entry table A.idx27.  The x-line goes
+        // back to the row of U this thread has just read and nobody else has: no barrier in front of the store.
+        constexpr bool ROLLED = rolled_P1<P, T>();
+        T              q[N];
+        if (active)
+          {
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+              y[i] = A.rhs[lbase + i] - y[i];
+            if constexpr (ROLLED)
+              {
+                st_line<N>(U, a * PX, 1, y);
+                mul_P1t_rolled<N, T>(A.P1, U + a * PX, 1, q);
+              }
+            else
+              mul_P1t<N, T>(A.P1, y, q);
+            st_line<N>(U, a * PX, 1, q);
+          }
+        __syncthreads();
+        if (active)
+          {
+            if constexpr (ROLLED)
+              mul_P1t_rolled<N, T>(A.P1, U + a, PX, q);
+            else
+              {
+                ld_line<N>(U, a, PX, y);
+                mul_P1t<N, T>(A.P1, y, q);
+              }
+          }
+        if (store)
+          add_fe_q_column_2d<P, T>(A.cg, A.idx27 + 9u * (size_t)cell, a, q);
+      }
     else if constexpr (ACTION == kPcgSums)
       {
         // the product stored and the four sums of the merged CG iteration, weighted by the inverse lumped mass m of the
@@ -457,9 +558,10 @@ namespace mgx::dg
       op, l, [&](auto P, auto TYPE, auto ACTION, const auto &a) { launch_one_2d<P.value, TYPE.value, ACTION.value>(s, a); });
   }
 #else
+  // kRestrict in this unit only: the solver on the FE_Q hierarchy refuses operators with Neumann faces
   bool launch_dg_cells_2d(hipStream_t s, const CellOperands &op, const DGLaunch &l)
   {
-    return dispatch_cells<kVmult, kChebyshev, kResidual, kJacobi, kPcgSums>(
+    return dispatch_cells<kVmult, kRestrict, kChebyshev, kResidual, kJacobi, kPcgSums>(
       op, l, [&](auto P, auto TYPE, auto ACTION, const auto &a) { launch_one_2d<P.value, TYPE.value, ACTION.value>(s, a); });
   }
 

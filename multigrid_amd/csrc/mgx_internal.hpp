@@ -619,11 +619,22 @@ namespace mgx
                                const void *ax = nullptr, const void *old = nullptr, double f0 = 0.);
   // interface exchange helpers
   void launch_pack(hipStream_t s, int number, void *buf, const void *v, const uint32_t *list, uint32_t count);
-  // DG <-> FE_Q transfer on one mesh (mgx_kernels.hip): to_dg: dg += P cg, else cg += P^T dg
-  // eight_colours (restriction only): cells c and c' with c % 8 == c' % 8 share no DoF -- eight launches with
-  // plain read-modify-writes instead of one with atomics
-  void launch_dg_cg_transfer(hipStream_t s, int number, int p, bool to_dg, void *dst, const void *src,
-                             const uint32_t *idx27, uint32_t n_cells, const void *P1, bool eight_colours = false);
+  // Launches of a sum over cells in which no two cells share an FE_Q DoF (plain read-modify-writes): the classes of cells
+  // k, k + stride, ... (forest order: the same child of every parent; 8 in three dimensions, 4 in two), or, where the
+  // caller coloured the cells itself, the lists of `lists`.  stride 1 and no list: one launch over all cells.
+  struct DisjointCells
+  {
+    uint32_t  stride = 1;
+    CellLists lists;
+  };
+  // DG <-> FE_Q transfer on one mesh of dimension dim: to_dg: dg += P cg, else cg += P^T dg (the restriction), launch by
+  // launch of `launches`.  Three dimensions (mgx_kernels.hip): stride 8, or one launch with atomics.  Two
+  // (mgx_kernels_2d.hip, through the 9-entry table): stride 4 or lists -- there is no atomic route, the caller has
+  // checked that the cells of a launch share no DoF.
+  void launch_dg_cg_transfer(hipStream_t s, int number, int p, int dim, bool to_dg, void *dst, const void *src,
+                             const uint32_t *idx27, uint32_t n_cells, const void *P1, const DisjointCells &launches = DisjointCells());
+  void launch_dg_cg_transfer_2d(hipStream_t s, int number, int p, bool to_dg, void *dst, const void *src, const uint32_t *idx9,
+                                uint32_t n_cells, const void *P1, const DisjointCells &launches);
   // DG <-> DG transfer over one step of a level hierarchy (mgx_dg_transfer.hip): prolong: fine += P coarse, else
   // coarse += P^T fine, group by group; dim == 2 or 3.  false: no kernel for this pair of degrees
   //   coarse_degree == fine_degree = p: a mesh step, a group is a coarse cell and its 2^dim children.  n_groups coarse
@@ -687,7 +698,8 @@ namespace mgx
       const void     *lumped   = nullptr;
     };
     // a status of include/mgx.h: MGX_ERR_UNSUPPORTED for a degree, basis or action no kernel is built for
-    // (two dimensions: actions kVmult, kResidual, kChebyshev, kJacobi and kPcgSums)
+    // (two dimensions: every action but kCgSums; kRestrict there adds without atomics whatever `plain` says -- the
+    // cells of a launch must share no FE_Q DoF -- and idx27 is the 9-entry table)
     int      launch_dg_cells(hipStream_t s, const CellOperands &op, const DGLaunch &launch);
     uint32_t cell_grid(int number, int p, uint32_t n_cells, int dim); // workgroups of a launch over n_cells cells
     // the constant block of the cell kernel in the number type, from the host data

@@ -1255,13 +1255,15 @@ namespace mgx
       }
   }
 
-  void launch_dg_cg_transfer(hipStream_t s, int number, int p, bool to_dg, void *dst, const void *src,
-                             const uint32_t *idx27, uint32_t n_cells, const void *P1, bool eight_colours)
+  void launch_dg_cg_transfer(hipStream_t s, int number, int p, int dim, bool to_dg, void *dst, const void *src,
+                             const uint32_t *idx27, uint32_t n_cells, const void *P1, const DisjointCells &launches)
   {
     if (n_cells == 0)
       return;
+    if (dim == 2)
+      return launch_dg_cg_transfer_2d(s, number, p, to_dg, dst, src, idx27, n_cells, P1, launches);
     dispatch_number_degree(number, p, [&](auto t, auto P) {
-      dg_cg_transfer_t<P.value, decltype(t)>(s, to_dg, dst, src, idx27, n_cells, P1, eight_colours);
+      dg_cg_transfer_t<P.value, decltype(t)>(s, to_dg, dst, src, idx27, n_cells, P1, launches.stride == 8);
     });
   }
 

@@ -429,6 +429,89 @@ namespace mgx
   }
 
   // ------------------------------------------------------------------------------------------
+  // Transfer between the DG space and the FE_Q space of the same mesh and degree, cell by cell: dg_cg_transfer_kernel of
+  // mgx_kernels.hip one dimension down (laplace_operator_dg.h:1798-1819 residual -> FE_Q, :1863-1894 FE_Q -> DG).  The
+  // DG vector holds (p+1)^2 contiguous values per cell, cells in the order of the index table; P1 [n][n] takes the
+  // values in the Gauss-Lobatto nodes to the coefficients of the DG basis.
+  // TO_DG: dg[cell] += (P1 x P1) c[cell]   else: cg += (P1 x P1)^T dg[cell], constrained rows skipped.
+  // The cells of a launch are cell_list[i] or cell_first + cell_stride * i, i < n_cells; those of a restriction share no
+  // FE_Q DoF (the caller's launches see to it): plain read-modify-writes, no atomics.
+  // Thread t of a cell: the x-product on the x-line t, one transposition through the cell's tile, the y-product on the
+  // y-line t.  The FE_Q side goes through the tile (gather_cell_2d / scatter_add_cell_2d); the DG side is read by
+  // x-lines and written by y-lines, so the lanes of a cell touch consecutive words.
+  // ------------------------------------------------------------------------------------------
+  template <int P, typename T, bool TO_DG>
+  __global__ void __launch_bounds__(Cfg2<P>::THREADS)
+    dg_cg_transfer_kernel_2d(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *__restrict__ idx9, uint32_t n_cells,
+                             const T *__restrict__ P1, const uint32_t *__restrict__ cell_list, uint32_t cell_first,
+                             uint32_t cell_stride)
+  {
+    using C               = Cfg2<P>;
+    constexpr int  N      = C::N, LN = C::LN, N2 = C::N2;
+    constexpr bool ROLLED = rolled_products<P, T>();
+    __shared__ T   U[C::CPB * C::CELL_LDS];
+
+    const int      tid    = threadIdx.x;
+    const int      lc     = tid / N;
+    const int      t      = tid - lc * N;
+    const uint32_t pos    = blockIdx.x * C::CPB + lc;
+    const bool     active = (lc < C::CPB) && (pos < n_cells);
+    // (inactive threads name no cell: they only meet the barriers)
+    const uint32_t cell = !active ? 0u : (cell_list ? cell_list[pos] : cell_first + cell_stride * pos);
+    T             *Uc   = U + (lc < C::CPB ? lc : 0) * C::CELL_LDS;
+    const int      row = t * LN, col = t;
+    T              r[N], q[N];
+
+    if constexpr (TO_DG)
+      {
+        if (active)
+          gather_cell_2d<P, T>(src, idx9 + 9u * (size_t)cell, t, Uc);
+        __syncthreads();
+        if (active) // along x
+          {
+            lds_product<N, T, false, ROLLED>(P1, Uc + row, 1, q);
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+              Uc[row + i] = q[i];
+          }
+        __syncthreads();
+        if (active) // along y; entry (j, t) of the cell
+          {
+            lds_product<N, T, false, ROLLED>(P1, Uc + col, LN, q);
+            T *d = dst + (size_t)cell * N2 + (size_t)t;
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+              d[j * N] += q[j];
+          }
+      }
+    else
+      {
+        if (active) // along x
+          {
+            const T *s = src + (size_t)cell * N2 + (size_t)(t * N);
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+              r[i] = s[i];
+            reg_product<N, T, true, ROLLED>(P1, r, Uc + row, 1, q);
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+              Uc[row + i] = q[i];
+          }
+        __syncthreads();
+        if (active) // along y
+          {
+            lds_product<N, T, true, ROLLED>(P1, Uc + col, LN, q);
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+              Uc[col + j * LN] = q[j];
+          }
+        __syncthreads();
+        if (active)
+          scatter_add_cell_2d<P, T>(dst, idx9 + 9u * (size_t)cell, t, Uc);
+      }
+  }
+
+  // ------------------------------------------------------------------------------------------
   // launchers
   // ------------------------------------------------------------------------------------------
   static int cell_form(const OperatorData &op)
@@ -529,6 +612,30 @@ namespace mgx
           hipLaunchKernelGGL((restrict_2d_kernel<P.value, T>), dim3(count), dim3(TCfg2<P.value>::THREADS), 0, s, (T *)coarse,
                              (const T *)fine, idx_c, f.idx27_plain, t.children, t.weight_shift,
                              t.parent_order + t.parent_colour_start[k], count, (const Basis1D<T> *)c.basis);
+    });
+  }
+
+  // the restriction launch by launch: the lists of `launches`, else its classes of cells k, k + stride, ...
+  void launch_dg_cg_transfer_2d(hipStream_t s, int number, int p, bool to_dg, void *dst, const void *src, const uint32_t *idx9,
+                                uint32_t n_cells, const void *P1, const DisjointCells &launches)
+  {
+    dispatch_number_degree(number, p, [&](auto number_type, auto P) {
+      using T = decltype(number_type);
+      using C = Cfg2<P.value>;
+      const auto launch = [&](auto TO_DG, const uint32_t *list, uint32_t first, uint32_t stride, uint32_t count) {
+        if (count > 0)
+          hipLaunchKernelGGL((dg_cg_transfer_kernel_2d<P.value, T, TO_DG.value>), dim3((count + C::CPB - 1) / C::CPB),
+                             dim3(C::THREADS), 0, s, (T *)dst, (const T *)src, idx9, count, (const T *)P1, list, first, stride);
+      };
+      const CellLists &lists = launches.lists;
+      if (to_dg)
+        launch(std::true_type(), nullptr, 0u, 1u, n_cells);
+      else if (lists.n > 0)
+        for (int k = 0; k < lists.n; ++k)
+          launch(std::false_type(), lists.cells + lists.start[k], 0u, 1u, lists.start[k + 1] - lists.start[k]);
+      else
+        for (uint32_t k = 0; k < launches.stride && k < n_cells; ++k)
+          launch(std::false_type(), nullptr, k, launches.stride, (n_cells - k + launches.stride - 1) / launches.stride);
     });
   }
 } // namespace mgx

@@ -2,7 +2,10 @@
 [-0.9, 1]^3, rhs 3 (3 pi)^2 prod sin(3 pi x_d), V-cycle-preconditioned CG with the DG level on top of the
 FE_Q(p) multigrid (fp32 V-cycle inside the fp64 outer iteration, program.cc:72-73).
 
-    python tools/poisson_dg.py [degree=3] [n_refine=5] [n_pre_smooth=3] [tolerance=1e-9] [--vcycle f32|f64] [--gpus N]
+    python tools/poisson_dg.py [degree=3] [n_refine=5] [n_pre_smooth=3] [tolerance=1e-9] [--vcycle f32|f64] [--gpus N] [--dim 2]
+
+--dim 2: the program with dimension = 2 -- the square [-0.9, 1]^2, rhs 2 (3 pi)^2 prod sin(3 pi x_d), the same lines and
+table row; one GPU.
 
 --gpus N: the cube is block-split over N ranks (2x1x1 / 2x2x1 / 2x2x2 coarse cells of the mesh with n_subdiv = 2,
 refined n_refine - 1 times: the same cells as on one GPU), one process per GPU, started by this script or by
@@ -38,10 +41,18 @@ WAVE = 3.0
 
 
 def quad_points(cube, ijk, xq, h):
-    """[cell, q = (k, j, i), 3] coordinates of the Gauss points"""
-    n = xq.size
-    ref = np.stack(np.meshgrid(xq, xq, xq, indexing="ij"), axis=-1)[..., ::-1].reshape(-1, 3)  # (k, j, i) order
+    """[cell, q = (k, j, i), dim] coordinates of the Gauss points; dim = the columns of ijk"""
+    dim = ijk.shape[1]
+    ref = np.stack(np.meshgrid(*([xq] * dim), indexing="ij"), axis=-1)[..., ::-1].reshape(-1, dim)  # (k, j, i) order
     return -0.9 + h * (ijk[:, None, :] + ref[None, :, :])
+
+
+def kron_power(a, dim):
+    """a x a (x a)"""
+    out = a
+    for _ in range(dim - 1):
+        out = np.kron(a, out)
+    return out
 
 
 def main():
@@ -53,6 +64,8 @@ def main():
     ap.add_argument("--vcycle", choices=["f32", "f64"], default="f32")
     ap.add_argument("--basis", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--dim", type=int, choices=[2, 3], default=3,
+                    help="2: the program with dimension = 2, on the square [-0.9, 1]^2 (one GPU)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="context option (include/mgx.h mgx_context_set_option), e.g. dg_unmerged_restrict=1")
     ap.add_argument("--solution", choices=["reference", "vanishing"], default="reference",
@@ -60,6 +73,9 @@ def main():
     ap.add_argument("--boundary", choices=["homogeneous", "data"], default="homogeneous",
                     help="data: boundary values of the solution in the right-hand side; rhs and error on the device")
     a = ap.parse_args()
+    dim = a.dim
+    if dim == 2 and a.gpus > 1:
+        raise SystemExit("poisson_dg.py: --dim 2 runs on one GPU (the 2D solver is not decomposed); drop --gpus %d" % a.gpus)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn(a.gpus)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -103,21 +119,23 @@ def main():
             mg.check(ctx.lib.mgx_context_use_rccl(ctx.h, 1))
         cube = mg.Cube(a.degree, n_refine=a.n_refine - 1, box=(2, 2, 2), procs=mg.process_grid(world), rank=rank,
                        origin=-0.9, h0=0.95)
+    elif dim == 2:
+        cube = mg.Square(a.degree, 1, a.n_refine)
     else:
         cube = mg.Cube(a.degree, 1, a.n_refine)
     solver = mg.DGMultigridSolver(ctx, cube, a.basis, a.n_pre_smooth, vnum, comm=comm)
     n_own = solver.m()
     n = int(round(total(n_own)))
-    nc = n // (a.degree + 1) ** 3
-    nc_own = n_own // (a.degree + 1) ** 3
+    nc = n // (a.degree + 1) ** dim
+    nc_own = n_own // (a.degree + 1) ** dim
     say("Number of degrees of freedom: %d (%d cells, FE_DGQHermite(%d) on FE_Q(%d) multigrid, V-cycle in %s, %d GPU%s)"
         % (n, nc, a.degree, a.degree, a.vcycle, world, "" if world == 1 else "s"))
     on_device = a.boundary == "data"
     if on_device:
         kw = np.pi * WAVE if a.solution == "reference" else np.pi * WAVE / 1.9
         phase = 0.0 if a.solution == "reference" else 0.9 * kw
-        u_dev = mg.DGFunction.sine_product(1.0, (kw,) * 3, (phase,) * 3)
-        f_dev = mg.DGFunction.sine_product(3 * kw ** 2, (kw,) * 3, (phase,) * 3)
+        u_dev = mg.DGFunction.sine_product(1.0, (kw,) * dim, (phase,) * dim)
+        f_dev = mg.DGFunction.sine_product(dim * kw ** 2, (kw,) * dim, (phase,) * dim)
         b, sol = solver.initialize_dof_vector(), solver.initialize_dof_vector()
         say("Time setup                    %.3f s" % (time.time() - t0))
         ctx.sync()
@@ -129,16 +147,16 @@ def main():
     else:
         S, xq, wq = solver.matrix_dg.basis_1d()
         h = cube.cell_size(cube.max_level)
-        S3 = np.kron(S, np.kron(S, S))
-        w3 = np.kron(wq, np.kron(wq, wq)) * h ** 3
+        S3 = kron_power(S, dim)
+        w3 = kron_power(wq, dim) * h ** dim
         x = quad_points(cube, solver.cell_ijk.astype(float), xq, h)
         if a.solution == "reference":
             u = np.prod(np.sin(np.pi * WAVE * x), axis=-1)
-            f = 3 * (np.pi * WAVE) ** 2 * u                      # program.cc:137-141
+            f = dim * (np.pi * WAVE) ** 2 * u                    # program.cc:137-141
         else:
             k = np.pi * WAVE / 1.9
             u = np.prod(np.sin(k * (x + 0.9)), axis=-1)
-            f = 3 * k ** 2 * u
+            f = dim * k ** 2 * u
         rhs = (f * w3) @ S3                                      # multigrid_solver_dg.h:243-262
         say("Time setup                    %.3f s   rhs_norm = %.6e" % (time.time() - t0, np.sqrt(total(float(np.sum(rhs ** 2))))))
         b, sol = solver.initialize_dof_vector(rhs.ravel()), solver.initialize_dof_vector()
@@ -156,7 +174,7 @@ def main():
         l2 = np.sqrt(total(float(sums[0])) / total(float(sums[1])))
     else:
         uh = sol.download()[:n_own].reshape(nc_own, -1) @ S3.T
-        l2 = np.sqrt(total(float(np.sum(w3 * (uh - u) ** 2))) / (nc * h ** 3))    # multigrid_solver_dg.h:328-367
+        l2 = np.sqrt(total(float(np.sum(w3 * (uh - u) ** 2))) / (nc * h ** dim))  # multigrid_solver_dg.h:328-367
     A_dp, A_sp = solver.matrix_dg_dp, solver.matrix_dg
     best = {}
     for name, A, number in (("dp", A_dp, mg.F64), ("sp", A_sp, vnum)):
