@@ -5,6 +5,7 @@
 #include "../../include/mgx.h"
 #include "mgx_bricks.hpp"
 #include "mgx_device_memory.hpp"
+#include "mgx_index_tables.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_krylov.hpp"
 
@@ -1204,20 +1205,10 @@ namespace
 {
   constexpr size_t kAssemblyMaxEntries = (size_t)1 << 26; // ordered assembly up to this many local values per level
 
-  // DoFs on mesh entity e of a cell of degree p: e = (cz 3 + cy) 3 + cx with the codes 0 low side, 1 inside, 2 high
-  // side per direction (vertex 1, line p - 1, face (p - 1)^2, interior (p - 1)^3)
-  inline int entity_size(int e, int p)
-  {
-    return (e % 3 == 1 ? p - 1 : 1) * ((e / 3) % 3 == 1 ? p - 1 : 1) * (e / 9 == 1 ? p - 1 : 1);
-  }
-  // what depends on the dimension of a level (mgx_operator_desc::dim): entities per cell (e = cy 3 + cx in two
-  // dimensions, where entity_size holds as it stands), the entity that is the cell's interior, local values per cell,
-  // entries of the symmetric coefficient tensor
-  inline int    desc_dim(const mgx_operator_desc *desc) { return desc->dim == 2 ? 2 : 3; }
-  inline int    n_entities(int dim) { return dim == 2 ? 9 : 27; }
-  inline int    interior_entity(int dim) { return dim == 2 ? 4 : 13; }
-  inline size_t n_local_values(int dim, int p) { return dim == 2 ? (size_t)(p + 1) * (p + 1) : (size_t)(p + 1) * (p + 1) * (p + 1); }
-  inline int    n_tensor_entries(int dim) { return dim == 2 ? 3 : 6; }
+  // what depends on the dimension of a level (mgx_operator_desc::dim) beyond mgx_index_tables.hpp: entries of the
+  // symmetric coefficient tensor
+  inline int desc_dim(const mgx_operator_desc *desc) { return desc->dim == 2 ? 2 : 3; }
+  inline int n_tensor_entries(int dim) { return dim == 2 ? 3 : 6; }
   // the entry points that exist in three dimensions only
   inline int refuse_2d(const mgx::OperatorData &d, const char *who, const char *why)
   {
@@ -1393,45 +1384,11 @@ namespace
   // keep the single launch with atomics.
   int colour_cells(mgx_operator_s &op, const mgx_operator_desc *desc)
   {
-    OperatorData         &d = op.d;
-    const int             p = d.p;
-    std::vector<uint32_t> used(desc->n_dofs, 0u);
-    std::vector<uint8_t>  colour(desc->n_cells, 0);
-    uint32_t              count[33] = {0};
-    int                   n_colours = 0;
-    // the entities whose first DoF is a key: all that carry DoFs but the cell's interior
-    const int ne = n_entities(d.dim), inside = interior_entity(d.dim);
-    auto is_key = [p, inside](const uint32_t *ix, int e) { return e != inside && entity_size(e, p) != 0 && ix[e] != MGX_INVALID_INDEX; };
-    for (uint32_t c = 0; c < desc->n_cells; ++c)
-      {
-        const uint32_t *ix   = desc->idx27 + ne * (size_t)c;
-        uint32_t        mask = 0;
-        for (int e = 0; e < ne; ++e)
-          if (is_key(ix, e))
-            mask |= used[ix[e]];
-        int col = 0;
-        while (col < 32 && (mask >> col) & 1u)
-          ++col;
-        if (col == 32)
-          return MGX_OK;
-        colour[c] = (uint8_t)col;
-        ++count[col];
-        n_colours = std::max(n_colours, col + 1);
-        for (int e = 0; e < ne; ++e)
-          if (is_key(ix, e))
-            used[ix[e]] |= 1u << col;
-      }
-    std::vector<uint32_t> order(desc->n_cells), fill(33, 0);
-    d.cell_colour_start[0] = 0;
-    for (int k = 0; k < n_colours; ++k)
-      d.cell_colour_start[k + 1] = d.cell_colour_start[k] + count[k];
-    for (int k = 0; k < n_colours; ++k)
-      fill[k] = d.cell_colour_start[k];
-    for (uint32_t c = 0; c < desc->n_cells; ++c)
-      order[fill[colour[c]]++] = c;
-    d.n_cell_colours = n_colours;
-    MGX_TRY(op.mem.upload(&d.cell_order, order));
-    MGX_TRACE("operator_create: %u cells in %d colours", desc->n_cells, n_colours);
+    const CellColouring colours = colour_cells_greedy(desc->idx27, n_entities(op.d.dim), desc->n_cells, desc->n_dofs, op.d.p);
+    if (colours.more_than_32)
+      return MGX_OK;
+    MGX_TRY(upload_colours(op.mem, op.d.cell_colours, colours));
+    MGX_TRACE("operator_create: %u cells in %d colours", desc->n_cells, colours.n);
     return MGX_OK;
   }
 
@@ -1587,7 +1544,7 @@ namespace
     OperatorData &d = op.d;
     const int     p = d.p, n = p + 1;
     const size_t  n3 = n_local_values(d.dim, p), n_local = n3 * desc->n_cells;
-    if (d.bricks.available() || d.cell_order || n_local > kAssemblyMaxEntries)
+    if (d.bricks.available() || d.cell_colours.order || n_local > kAssemblyMaxEntries)
       return MGX_OK;
     std::vector<uint32_t> start((size_t)desc->n_dofs + 1, 0), pos;
     // (two dimensions: the one plane k = 0 of a table with 9 entries per cell -- code and offset of k are zero)
@@ -1833,7 +1790,7 @@ int mgx_operator_create(mgx_context_t ctx, const mgx_operator_desc *desc, mgx_op
       (desc->n_cells >= tun.cell_colour_min || n_local_values(dim, p) * desc->n_cells > kAssemblyMaxEntries))
     {
       MGX_TRY(colour_cells(*op, desc));
-      if (dim == 2 && !d.cell_order)
+      if (dim == 2 && !d.cell_colours.order)
         return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_create: a two-dimensional level that needs more than 32 cell colours "
                                          "(and is too large for, or was told not to use, the ordered assembly)");
     }
@@ -2073,8 +2030,8 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
   CellLists             lists;
   if (op->d.bricks.available())
     MGX_TRY(brick_cell_lists(op, tmp, list_start, lists));
-  else if (op->d.cell_order && !op->d.asm_start)
-    lists = CellLists(op->d);
+  else if (op->d.cell_colours.order && !op->d.asm_start)
+    lists = op->d.cell_colours.lists();
   launch_cell_residual(s, op->d, dst, src, rhs_q, lists);
   MGX_HIP(hipGetLastError());
   return exchange_add(op, dst); // dst.compress(add), laplace_operator.h:843
@@ -2213,9 +2170,8 @@ int mgx_evaluate_coefficient(mgx_operator_t op, int law, const void *state)
 {
   MGX_REQUIRE(op && state, "mgx_evaluate_coefficient: null argument");
   MGX_TRY(require_coefficient_update(op, law, "mgx_evaluate_coefficient"));
-  (op->d.dim == 2 ? launch_evaluate_coefficient_2d : launch_evaluate_coefficient)(
-    op->ctx->stream, op->d, op->d.coef_q, op->d.number, law == MGX_LAW_MINIMAL_SURFACE, op->metric, op->det_jacobian, op->unit_q,
-    op->jxw_q, state);
+  launch_evaluate_coefficient(op->ctx->stream, op->d, op->d.coef_q, op->d.number, law == MGX_LAW_MINIMAL_SURFACE, op->metric,
+                              op->det_jacobian, op->unit_q, op->jxw_q, state);
   MGX_HIP(hipGetLastError());
   op->has_diag = false; // the inverse diagonal belongs to the previous coefficient
   return MGX_OK;
@@ -2239,19 +2195,16 @@ int mgx_compute_nonlinear_residual(mgx_operator_t op, int law, void *dst, const 
   hipStream_t s  = op->ctx->stream;
   const bool  ms = law == MGX_LAW_MINIMAL_SURFACE;
   // atomic-free assembly only: the ordered assembly where the level has it, else colour by colour
-  if (!op->d.asm_start && !op->d.cell_order)
+  if (!op->d.asm_start && !op->d.cell_colours.order)
     return fail(MGX_ERR_UNSUPPORTED, "mgx_compute_nonlinear_residual: the level has neither cell colours nor the ordered-assembly "
                                      "tables (more than 32 colours): no reproducible assembly");
   CellLists lists; // none: the ordered assembly, which comes first where the level has it (dst is written)
   if (!op->d.asm_start) // the cell colours: dst is added to
     {
       MGX_HIP(hipMemsetAsync(dst, 0, number_size(op->d.number) * op->d.n_dofs, s));
-      lists = CellLists(op->d);
+      lists = op->d.cell_colours.lists();
     }
-  if (op->d.dim == 2)
-    launch_cell_nl_residual_2d(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state);
-  else
-    launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state, lists);
+  launch_cell_nl_residual(s, op->d, ms, op->metric, op->det_jacobian, op->unit_q, op->jxw_q, dst, state, lists);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -2288,8 +2241,8 @@ int mgx_compute_diagonal(mgx_operator_t op)
   CellLists             lists;
   if (op->d.bricks.available())
     MGX_TRY(brick_cell_lists(op, lists_mem, list_start, lists));
-  else if (op->d.cell_order)
-    lists = CellLists(op->d);
+  else if (op->d.cell_colours.order)
+    lists = op->d.cell_colours.lists();
   launch_cell_diagonal(s, op->d, op->d.inv_diag, a1d, m1d, lists);
   MGX_TRY(exchange_add(op, op->d.inv_diag)); // Vector::compress(add) of the reference's cell_loop
   // set_constrained_entries_to_one + invert (laplace_operator.h:757-765)
@@ -2819,84 +2772,70 @@ namespace
   }
 
   // weights 1/multiplicity (multiplicity = number of parent patches sharing a fine DoF), stored
-  // compressed as 3^3 entries per parent like deal.II does on uniform meshes, and the ownership of the fine entities.
+  // compressed as 3^dim entries per parent like deal.II does on uniform meshes, and the ownership of the fine entities.
   // idxf (the fine level's idx27_plain), shift and own are left on the host for build_patch_table.
   int build_weights_and_ownership(mgx_transfer_s &tr, const mgx_transfer_desc *desc, std::vector<uint32_t> &idxf,
                                   std::vector<uint8_t> &shift, std::vector<uint32_t> &own)
   {
     mgx_operator_t coarse = tr.coarse, fine = tr.fine;
-    const int      p    = coarse->d.p;
-    const uint32_t npar = coarse->d.n_cells;
-    idxf.resize(27 * (size_t)fine->d.n_cells);
+    const int      dim = coarse->d.dim, ne = n_entities(dim);
+    idxf.resize(ne * (size_t)fine->d.n_cells);
     MGX_HIP(hipMemcpy(idxf.data(), fine->d.idx27_plain, sizeof(uint32_t) * idxf.size(), hipMemcpyDeviceToHost));
-    std::vector<uint8_t> cnt(fine->d.n_dofs, 0);
-    // representative fine DoF of patch entity e = (ca,cb,cc): a child vertex lying in it (low
-    // patch face: child 0's low vertex; patch interior: the mid plane = child 0's high vertex;
-    // high patch face: child 1's high vertex) -- vertices carry exactly one DoF for every p
-    auto rep = [&](uint32_t pc, int e) {
-      const int      ca = e % 3, cb = (e / 3) % 3, cc = e / 9;
-      const int      ch = (ca == 2) | ((cb == 2) << 1) | ((cc == 2) << 2);
-      const uint32_t fc = desc->children[8 * (size_t)pc + ch];
-      return idxf[27 * (size_t)fc + 9 * (cc ? 2 : 0) + 3 * (cb ? 2 : 0) + (ca ? 2 : 0)];
-    };
-    for (uint32_t pc = 0; pc < npar; ++pc)
-      for (int e = 0; e < 27; ++e)
-        cnt[rep(pc, e)]++;
-    shift.assign(27 * (size_t)npar, 0);
-    // Multiplicities other than 1/2/4/8 (three blocks of a multi-block mesh around an edge): the
-    // restriction then uses OWNER weights -- a shared fine DoF is restricted by the one parent that
-    // owns its entity, with weight 1.  Any weights that add up to one over the parents of a fine
-    // DoF give the same R = P^T (P is interpolatory: a fine DoF on a shared entity only couples to
-    // coarse DoFs on that entity, which all its parents hold); only the summation order differs.
-    bool owner_weights = false;
-    for (uint32_t pc = 0; pc < npar; ++pc)
-      for (int e = 0; e < 27; ++e)
-        {
-          const uint8_t c = cnt[rep(pc, e)];
-          if (c != 1 && c != 2 && c != 4 && c != 8)
-            owner_weights = true;
-          shift[27 * (size_t)pc + e] = c == 1 ? 0 : (c == 2 ? 1 : (c == 4 ? 2 : 3));
-        }
-    // (on a decomposed mesh the local counts miss the parents of other ranks: without the caller's global
-    // weight_shift every rank uses owner weights, which need no count at all)
-    if (coarse->plan && !desc->weight_shift)
-      owner_weights = true;
-    if (owner_weights)
+    PatchShifts counted = patch_multiplicity_shifts(dim, desc->children, idxf.data(), coarse->d.n_cells, fine->d.n_dofs);
+    shift.swap(counted.shift);
+    if (dim == 2) // (one rank: the local count is the whole count; no owner weights in the dense kernels)
       {
-        if (desc->weight_shift)
-          return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: fine DoF multiplicities other than 1/2/4/8 together with "
-                                           "weight_shift");
-        std::fill(shift.begin(), shift.end(), (uint8_t)0);
-        tr.d.owner_weights = true;
+        if (counted.irregular)
+          return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: fine DoF multiplicities other than 1/2/4 (three or five "
+                                           "cells around a vertex) in two dimensions");
+        if (desc->weight_shift && !std::equal(shift.begin(), shift.end(), desc->weight_shift))
+          return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: inconsistent weight_shift");
       }
-    if (desc->weight_shift) // multiplicities that count the parents of other ranks as well
+    else
       {
-        for (size_t i = 0; i < shift.size(); ++i)
+        // Multiplicities other than 1/2/4/8 (three blocks of a multi-block mesh around an edge): the
+        // restriction then uses OWNER weights -- a shared fine DoF is restricted by the one parent that
+        // owns its entity, with weight 1.  Any weights that add up to one over the parents of a fine
+        // DoF give the same R = P^T (P is interpolatory: a fine DoF on a shared entity only couples to
+        // coarse DoFs on that entity, which all its parents hold); only the summation order differs.
+        // (on a decomposed mesh the local counts miss the parents of other ranks: without the caller's global
+        // weight_shift every rank uses owner weights, which need no count at all)
+        if (counted.irregular || (coarse->plan && !desc->weight_shift))
           {
-            if (desc->weight_shift[i] > 3 || desc->weight_shift[i] < shift[i])
-              return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: inconsistent weight_shift");
-            shift[i] = desc->weight_shift[i];
+            if (desc->weight_shift)
+              return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: fine DoF multiplicities other than 1/2/4/8 together with "
+                                               "weight_shift");
+            std::fill(shift.begin(), shift.end(), (uint8_t)0);
+            tr.d.owner_weights = true;
           }
+        if (desc->weight_shift) // multiplicities that count the parents of other ranks as well
+          for (size_t i = 0; i < shift.size(); ++i)
+            {
+              if (desc->weight_shift[i] > 3 || desc->weight_shift[i] < shift[i])
+                return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: inconsistent weight_shift");
+              shift[i] = desc->weight_shift[i];
+            }
       }
     MGX_TRY(tr.mem.upload(&tr.d.weight_shift, shift));
-    // ownership of the fine entities for the atomic-free prolongation: first cell in cell order
-    own.assign(fine->d.n_cells, 0u);
-    {
-      std::vector<uint8_t> seen(fine->d.n_dofs, 0);
-      for (uint32_t c = 0; c < fine->d.n_cells; ++c)
-        for (int e = 0; e < 27; ++e)
-          {
-            if (entity_size(e, p) == 0)
-              continue;
-            const uint32_t base = idxf[27 * (size_t)c + e];
-            if (!seen[base])
-              {
-                seen[base] = 1;
-                own[c] |= 1u << e;
-              }
-          }
-    }
+    // ownership of the fine entities for the atomic-free prolongation: first cell in cell order (the table was checked
+    // when the fine operator was created)
+    own = first_owner_masks(idxf.data(), ne, fine->d.n_cells, fine->d.n_dofs, coarse->d.p);
     return tr.mem.upload(&tr.d.own27, own);
+  }
+
+  // Two dimensions: the restriction runs over the parents colour by colour -- greedy colours over the unconstrained
+  // table (they hold for the constrained one as well)
+  int colour_parents(mgx_transfer_s &tr)
+  {
+    const OperatorData   &c = tr.coarse->d;
+    std::vector<uint32_t> idxc(n_entities(c.dim) * (size_t)c.n_cells);
+    MGX_HIP(hipMemcpy(idxc.data(), c.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
+    const CellColouring colours = colour_cells_greedy(idxc.data(), n_entities(c.dim), c.n_cells, c.n_dofs, c.p);
+    if (colours.more_than_32)
+      return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: the coarse cells need more than 32 colours");
+    MGX_TRY(upload_colours(tr.mem, tr.d.parent_colours, colours));
+    MGX_TRACE("transfer_create: two dimensions, %u parents in %d colours", c.n_cells, colours.n);
+    return MGX_OK;
   }
 
   // patch table of the pipelined kernels (mgx_transfer.hip): the 5^3 mesh entities of the
@@ -2980,7 +2919,6 @@ namespace
         return MGX_OK;
       }
     MGX_TRY(tr.mem.upload(&tr.d.patch, patch));
-    tr.d.n_cus = context_cus(coarse->ctx);
     // colouring of the coarse cells by index mod 8 (the parity colouring of a Morton-ordered
     // mesh): valid if no two cells of one colour share a mesh entity
     if (npar % 8 == 0 && !coarse->ctx->tun.restrict_atomic)
@@ -3045,13 +2983,19 @@ namespace
         for (int a = 0; a <= p; ++a)
           p1eo[(size_t)(2 * p + 1) * nh + a] = P1[a * n + p / 2];
     }
+    // (two dimensions: the dense embedding into the block of the coarse operator, which the transfer kernels read, and
+    // nothing else -- there are no fused forms)
+    const bool quads = tr.coarse->d.dim == 2;
     for (mgx_operator_t o : {tr.coarse, tr.fine})
       {
+        if (quads && o == tr.fine)
+          break;
         const bool   f64 = o->d.number == MGX_F64;
         const size_t at_p1 = f64 ? offsetof(Basis1D<double>, P1) : offsetof(Basis1D<float>, P1);
         const size_t at_eo = f64 ? offsetof(Basis1D<double>, P1eo) : offsetof(Basis1D<float>, P1eo);
         MGX_TRY(tr.mem.copy_as(o->d.number, (char *)o->d.basis + at_p1, desc->prolong_1d, np1));
-        MGX_TRY(tr.mem.copy_as(o->d.number, (char *)o->d.basis + at_eo, p1eo.data(), p1eo.size()));
+        if (!quads)
+          MGX_TRY(tr.mem.copy_as(o->d.number, (char *)o->d.basis + at_eo, p1eo.data(), p1eo.size()));
       }
     return MGX_OK;
   }
@@ -3208,115 +3152,6 @@ namespace
     else
       MGX_TRACE("transfer_create: fused prolongation yes (with a smoother of degree >= 1)");
   }
-  // Two dimensions (mgx_kernels_2d.hip): children in fours, weights and ownership over the 9 entities of a cell, the
-  // parents coloured for the restriction.  No patch table, no fused forms: the dense kernels serve every embedding.
-  int transfer_create_2d(mgx_operator_t coarse, mgx_operator_t fine, const mgx_transfer_desc *desc, mgx_transfer_t *out)
-  {
-    MGX_REQUIRE((uint64_t)coarse->d.n_cells * 4 == fine->d.n_cells,
-                "mgx_transfer_create: fine level must have 4 children per coarse cell (uniform refinement)");
-    const int      p    = coarse->d.p;
-    const uint32_t npar = coarse->d.n_cells, nfine = fine->d.n_cells;
-    {
-      // every fine cell is the child of exactly one parent: the prolongation writes every fine entry once
-      std::vector<uint8_t> seen(nfine, 0);
-      for (size_t i = 0; i < 4 * (size_t)npar; ++i)
-        {
-          if (desc->children[i] >= nfine)
-            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: child index out of range");
-          if (seen[desc->children[i]]++)
-            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: the children table names a fine cell twice");
-        }
-    }
-    std::unique_ptr<mgx_transfer_s, int (*)(mgx_transfer_t)> tr(new mgx_transfer_s, mgx_transfer_destroy);
-    tr->coarse   = coarse;
-    tr->fine     = fine;
-    tr->d.coarse = &coarse->d;
-    tr->d.fine   = &fine->d;
-    tr->d.n_cus  = context_cus(coarse->ctx);
-    MGX_TRY(tr->mem.upload(&tr->d.children, desc->children, 4 * (size_t)npar));
-    std::vector<uint32_t> idxf(9 * (size_t)nfine), idxc(9 * (size_t)npar);
-    MGX_HIP(hipMemcpy(idxf.data(), fine->d.idx27_plain, sizeof(uint32_t) * idxf.size(), hipMemcpyDeviceToHost));
-    MGX_HIP(hipMemcpy(idxc.data(), coarse->d.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
-    // weights 1 / multiplicity per patch entity e = cb 3 + ca, counted at a child vertex that lies in the entity (low
-    // side: child 0's low vertex, inside: the mid line = child 0's high vertex, high side: child 1's high vertex)
-    auto rep = [&](uint32_t pc, int e) {
-      const int      ca = e % 3, cb = e / 3;
-      const uint32_t fc = desc->children[4 * (size_t)pc + ((ca == 2) | ((cb == 2) << 1))];
-      return idxf[9 * (size_t)fc + 3 * (cb ? 2 : 0) + (ca ? 2 : 0)];
-    };
-    std::vector<uint8_t> cnt(fine->d.n_dofs, 0), shift(9 * (size_t)npar, 0);
-    for (uint32_t pc = 0; pc < npar; ++pc)
-      for (int e = 0; e < 9; ++e)
-        cnt[rep(pc, e)]++;
-    for (uint32_t pc = 0; pc < npar; ++pc)
-      for (int e = 0; e < 9; ++e)
-        {
-          const uint8_t c = cnt[rep(pc, e)];
-          if (c != 1 && c != 2 && c != 4)
-            return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: fine DoF multiplicities other than 1/2/4 (three or five "
-                                             "cells around a vertex) in two dimensions");
-          shift[9 * (size_t)pc + e] = c == 1 ? 0 : (c == 2 ? 1 : 2);
-        }
-    if (desc->weight_shift)
-      for (size_t i = 0; i < shift.size(); ++i)
-        {
-          if (desc->weight_shift[i] != shift[i]) // (one rank: the local count is the whole count)
-            return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: inconsistent weight_shift");
-        }
-    MGX_TRY(tr->mem.upload(&tr->d.weight_shift, shift));
-    // ownership of the fine entities: the first cell in cell order that contains one writes it
-    std::vector<uint32_t> own(nfine, 0u);
-    {
-      std::vector<uint8_t> seen(fine->d.n_dofs, 0);
-      for (uint32_t c = 0; c < nfine; ++c)
-        for (int e = 0; e < 9; ++e)
-          if (entity_size(e, p) != 0 && !seen[idxf[9 * (size_t)c + e]])
-            {
-              seen[idxf[9 * (size_t)c + e]] = 1;
-              own[c] |= 1u << e;
-            }
-    }
-    MGX_TRY(tr->mem.upload(&tr->d.own27, own));
-    // greedy colouring of the parents over the unconstrained table (it holds for the constrained one as well)
-    {
-      std::vector<uint32_t> used(coarse->d.n_dofs, 0u), count(33, 0u), order(npar);
-      std::vector<uint8_t>  colour(npar, 0);
-      int                   n_colours = 0;
-      for (uint32_t c = 0; c < npar; ++c)
-        {
-          const uint32_t *ix   = &idxc[9 * (size_t)c];
-          uint32_t        mask = 0;
-          for (int e = 0; e < 9; ++e)
-            if (e != 4 && entity_size(e, p) != 0)
-              mask |= used[ix[e]];
-          int col = 0;
-          while (col < 32 && (mask >> col) & 1u)
-            ++col;
-          if (col == 32)
-            return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: the coarse cells need more than 32 colours");
-          colour[c] = (uint8_t)col;
-          ++count[col];
-          n_colours = std::max(n_colours, col + 1);
-          for (int e = 0; e < 9; ++e)
-            if (e != 4 && entity_size(e, p) != 0)
-              used[ix[e]] |= 1u << col;
-        }
-      tr->d.n_parent_colours = n_colours;
-      for (int k = 0; k < n_colours; ++k)
-        tr->d.parent_colour_start[k + 1] = tr->d.parent_colour_start[k] + count[k];
-      std::vector<uint32_t> fill(tr->d.parent_colour_start, tr->d.parent_colour_start + 33);
-      for (uint32_t c = 0; c < npar; ++c)
-        order[fill[colour[c]]++] = c;
-      MGX_TRY(tr->mem.upload(&tr->d.parent_order, order));
-      MGX_TRACE("transfer_create: two dimensions, %u parents in %d colours", npar, n_colours);
-    }
-    // the dense embedding into the basis block of the coarse operator (the transfer kernels read that one)
-    MGX_TRY(tr->mem.copy_as(coarse->d.number,
-                            (char *)coarse->d.basis + (coarse->d.number == MGX_F64 ? offsetof(Basis1D<double>, P1) : offsetof(Basis1D<float>, P1)),
-                            desc->prolong_1d, (size_t)(2 * p + 1) * (p + 1)));
-    *out = tr.release();
-    return MGX_OK;
-  }
 } // namespace
 
 extern "C" {
@@ -3331,15 +3166,26 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
   MGX_REQUIRE(coarse->d.idx27_plain && fine->d.idx27_plain,
               "mgx_transfer_create: operators were created without idx27_plain");
   MGX_REQUIRE(coarse->d.dim == fine->d.dim, "mgx_transfer_create: level operators of different dimensions");
-  if (coarse->d.dim == 2)
-    return transfer_create_2d(coarse, fine, desc, out);
-  MGX_REQUIRE((uint64_t)coarse->d.n_cells * 8 == fine->d.n_cells,
-              "mgx_transfer_create: fine level must have 8 children per coarse cell (uniform refinement)");
-  const uint32_t npar = coarse->d.n_cells;
-  for (size_t i = 0; i < 8 * (size_t)npar; ++i)
-    if (desc->children[i] >= fine->d.n_cells)
-      return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: child index out of range");
-  MGX_TRACE("transfer_create: parents=%u", npar);
+  // Two dimensions (mgx_kernels_2d.hip): children in fours, weights and ownership over the 9 entities of a cell, the
+  // parents coloured for the restriction.  No patch table, no fused forms: the dense kernels serve every embedding.
+  const bool     quads      = coarse->d.dim == 2;
+  const uint32_t n_children = quads ? 4u : 8u, npar = coarse->d.n_cells, nfine = fine->d.n_cells;
+  MGX_REQUIRE((uint64_t)npar * n_children == nfine,
+              quads ? "mgx_transfer_create: fine level must have 4 children per coarse cell (uniform refinement)"
+                    : "mgx_transfer_create: fine level must have 8 children per coarse cell (uniform refinement)");
+  {
+    // (two dimensions: every fine cell is the child of exactly one parent -- the prolongation writes every fine entry once)
+    std::vector<uint8_t> seen(quads ? nfine : 0u, 0);
+    for (size_t i = 0; i < n_children * (size_t)npar; ++i)
+      {
+        if (desc->children[i] >= nfine)
+          return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: child index out of range");
+        if (quads && seen[desc->children[i]]++)
+          return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: the children table names a fine cell twice");
+      }
+  }
+  if (!quads)
+    MGX_TRACE("transfer_create: parents=%u", npar);
   const bool p1_symmetric = embedding_is_symmetric(desc->prolong_1d, coarse->d.p);
   // failures below return through the destroy function, which frees what the transfer's arena holds by then
   std::unique_ptr<mgx_transfer_s, int (*)(mgx_transfer_t)> tr(new mgx_transfer_s, mgx_transfer_destroy);
@@ -3348,14 +3194,23 @@ int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_tr
   tr->d.coarse = &coarse->d;
   tr->d.colour_min = coarse->ctx->tun.restrict_colour_min;
   tr->d.fine   = &fine->d;
-  MGX_TRY(tr->mem.upload(&tr->d.children, desc->children, 8 * (size_t)npar));
+  tr->d.n_cus  = context_cus(coarse->ctx);
+  MGX_TRY(tr->mem.upload(&tr->d.children, desc->children, n_children * (size_t)npar));
   {
     std::vector<uint32_t> idxf, own; // fine idx27_plain, entity ownership of the fine cells
     std::vector<uint8_t>  shift;
     MGX_TRY(build_weights_and_ownership(*tr, desc, idxf, shift, own));
-    MGX_TRY(build_patch_table(*tr, desc, p1_symmetric, idxf, shift, own));
+    if (!quads)
+      MGX_TRY(build_patch_table(*tr, desc, p1_symmetric, idxf, shift, own));
   }
+  if (quads)
+    MGX_TRY(colour_parents(*tr));
   MGX_TRY(upload_embedding(*tr, desc));
+  if (quads)
+    {
+      *out = tr.release();
+      return MGX_OK;
+    }
   {
     std::vector<uint32_t> tab; // block table of the fused forms
     MGX_TRY(build_fused_blocks(*tr, desc, p1_symmetric, tab));
@@ -3485,26 +3340,15 @@ int mgx_interpolate_to_coarse(mgx_transfer_t tr, void *coarse, const void *fine)
       // (the Gauss-Lobatto nodes mgx_operator_desc::shape_values is defined on)
       const std::vector<double> r = interpolation_matrix_1d(p);
       // (two dimensions: 9 entities per cell, e = 3 cy + cx, the low 9 bits of the mask)
-      std::vector<uint32_t>     idxc((size_t)cop->d.n_cells * ne), own(cop->d.n_cells, 0u);
+      std::vector<uint32_t>     idxc((size_t)cop->d.n_cells * ne);
       MGX_HIP(hipMemcpy(idxc.data(), cop->d.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
-      std::vector<uint8_t> seen(cop->d.n_dofs, 0);
-      for (uint32_t c = 0; c < cop->d.n_cells; ++c)
-        for (int e = 0; e < ne; ++e)
-          {
-            if (entity_size(e, p) == 0)
-              continue;
-            const uint32_t base = idxc[(size_t)ne * c + e];
-            MGX_REQUIRE(base < cop->d.n_dofs, "mgx_interpolate_to_coarse: index table out of range");
-            if (!seen[base])
-              {
-                seen[base] = 1;
-                own[c] |= 1u << e;
-              }
-          }
+      bool                        out_of_range = false;
+      const std::vector<uint32_t> own          = first_owner_masks(idxc.data(), ne, cop->d.n_cells, cop->d.n_dofs, p, &out_of_range);
+      MGX_REQUIRE(!out_of_range, "mgx_interpolate_to_coarse: index table out of range");
       MGX_TRY(tr->mem.upload(&tr->own_coarse, own));
       MGX_TRY(tr->mem.upload_as(cop->d.number, &tr->interp_1d, r.data(), r.size())); // (last: it marks the tables as built)
     }
-  (dim == 2 ? launch_interpolate_to_coarse_2d : launch_interpolate_to_coarse)(s, tr->d, tr->interp_1d, tr->own_coarse, coarse, fine);
+  launch_interpolate_to_coarse(s, tr->d, tr->interp_1d, tr->own_coarse, coarse, fine);
   MGX_HIP(hipGetLastError());
   return MGX_OK;
 }
@@ -4338,8 +4182,8 @@ int mgx_solver_update_coefficient(mgx_solver_t S, int law, const double *state_f
           // the two precisions would no longer be the same operator up to storage.)
           mgx_operator_t A = S->matrix_dp[l], V = S->matrix[l];
           MGX_REQUIRE(V->d.n_cells == A->d.n_cells && V->d.p == A->d.p, "mgx_solver_update_coefficient: level operators differ");
-          (A->d.dim == 2 ? launch_evaluate_coefficient_2d : launch_evaluate_coefficient)(
-            s, A->d, V->d.coef_q, V->d.number, law == MGX_LAW_MINIMAL_SURFACE, A->metric, A->det_jacobian, A->unit_q, A->jxw_q, state);
+          launch_evaluate_coefficient(s, A->d, V->d.coef_q, V->d.number, law == MGX_LAW_MINIMAL_SURFACE, A->metric, A->det_jacobian,
+                                      A->unit_q, A->jxw_q, state);
           MGX_HIP(hipGetLastError());
           V->has_diag = false;
         }

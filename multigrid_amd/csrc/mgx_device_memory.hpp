@@ -3,6 +3,7 @@
 #pragma once
 
 #include "../../include/mgx.h"
+#include "mgx_index_tables.hpp"
 #include "mgx_internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -157,4 +158,13 @@ namespace mgx
     bool                drain_        = false;
     hipStream_t         drain_stream_ = nullptr;
   };
+
+  // a colouring of cells (mgx_index_tables.hpp) as the launchers read it: the order on the device, in the arena of the
+  // object that holds `out`
+  inline int upload_colours(DeviceArena &mem, ColourLists &out, const CellColouring &colours)
+  {
+    out.n = colours.n;
+    std::copy(colours.start, colours.start + 33, out.start);
+    return mem.upload(&out.order, colours.order);
+  }
 } // namespace mgx

@@ -111,19 +111,16 @@ struct mgx_dg_solver_s
   bool              cg_eight_colours = false; // cells c, c + 8, ... of the FE_Q level share no DoF
   void             *cg_defect = nullptr, *cg_update = nullptr; // the FE_Q solver's finest-level vectors
   // Two dimensions (dim == 2: quadrilaterals, idx27 is the 9-entry table): the restriction never uses atomics.  Cells c,
-  // c + 4, ... share no DoF (cg_four_colours, checked), or the cells are coloured here: colour k is
-  // cg_order[cg_colour_start[k] .. cg_colour_start[k + 1])
-  int                   dim = 3;
-  bool                  cg_four_colours = false;
-  uint32_t             *cg_order = nullptr; // device
-  std::vector<uint32_t> cg_colour_start;    // empty: no lists
+  // c + 4, ... share no DoF (cg_four_colours, checked), or the cells are coloured here (cg_colours)
+  int              dim = 3;
+  bool             cg_four_colours = false;
+  mgx::ColourLists cg_colours; // order == nullptr: no lists
   // the launches of a restriction: 3D stride 8 or one launch (atomics); 2D stride 4 or the colour lists
   mgx::DisjointCells restriction_launches() const
   {
     mgx::DisjointCells d;
     d.stride = cg_eight_colours ? 8u : (cg_four_colours ? 4u : 1u);
-    if (!cg_colour_start.empty())
-      d.lists = mgx::CellLists(cg_order, cg_colour_start.data(), (int)cg_colour_start.size() - 1);
+    d.lists  = cg_colours.lists();
     return d;
   }
 };
@@ -1174,9 +1171,7 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
     // no address
     const auto key = [&](uint32_t c, int e) {
       const uint32_t v = h27[ne * (size_t)c + e];
-      if (S->degree == 1 && (e % 3 == 1 || (e / 3) % 3 == 1 || e / 9 == 1))
-        return 0xFFFFFFFFu;
-      return v < ncg ? v : 0xFFFFFFFFu;
+      return mgx::entity_size(e, S->degree) != 0 && v < ncg ? v : 0xFFFFFFFFu;
     };
     bool ok = nc >= classes * classes;
     for (uint32_t k = 0; k < classes && ok; ++k)
@@ -1195,38 +1190,13 @@ int mgx_dg_solver_create(mgx_context_t ctx, const mgx_dg_solver_desc *desc, mgx_
     (dim == 2 ? S->cg_four_colours : S->cg_eight_colours) = ok;
     if (dim == 2 && !ok)
       {
-        // fewer than 16 cells or another cell order: greedy colours over the cells in their order, as colour_cells of
-        // the FE_Q operator (mgx_api.cpp) finds them; two cells conflict when they share an entity with DoFs.  There
-        // is no launch with atomics to fall back to in two dimensions.
-        std::vector<uint32_t> used(ncg, 0u), colour(nc, 0u), count(33, 0u);
-        uint32_t              n_colours = 0;
-        for (uint32_t c = 0; c < nc; ++c)
-          {
-            uint32_t mask = 0;
-            for (int e = 0; e < ne; ++e)
-              if (const uint32_t v = key(c, e); v != 0xFFFFFFFFu)
-                mask |= used[v];
-            uint32_t col = 0;
-            while (col < 32 && ((mask >> col) & 1u))
-              ++col;
-            if (col == 32)
-              return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: the cells of the FE_Q level need more than 32 colours for a "
-                                                  "DG -> FE_Q restriction without atomics");
-            colour[c] = col;
-            ++count[col];
-            n_colours = std::max(n_colours, col + 1);
-            for (int e = 0; e < ne; ++e)
-              if (const uint32_t v = key(c, e); v != 0xFFFFFFFFu)
-                used[v] |= 1u << col;
-          }
-        std::vector<uint32_t> order(nc), fill(n_colours + 1, 0u);
-        for (uint32_t k = 0; k < n_colours; ++k)
-          fill[k + 1] = fill[k] + count[k];
-        S->cg_colour_start = fill;
-        for (uint32_t c = 0; c < nc; ++c)
-          order[fill[colour[c]]++] = c;
-        if (nc > 0)
-          MGX_TRY(S->mem.upload(&S->cg_order, order));
+        // fewer than 16 cells or another cell order: the greedy colours of the FE_Q operator's own cell colouring
+        // (mgx_index_tables.hpp).  There is no launch with atomics to fall back to in two dimensions.
+        const mgx::CellColouring colours = mgx::colour_cells_greedy(h27.data(), ne, nc, ncg, S->degree);
+        if (colours.more_than_32)
+          return dg_fail(MGX_ERR_UNSUPPORTED, "mgx_dg_solver_create: the cells of the FE_Q level need more than 32 colours for a "
+                                              "DG -> FE_Q restriction without atomics");
+        MGX_TRY(mgx::upload_colours(S->mem, S->cg_colours, colours));
       }
   }
   hipStream_t s = (hipStream_t)mgx_context_stream(ctx);

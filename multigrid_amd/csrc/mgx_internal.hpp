@@ -142,6 +142,26 @@ namespace mgx
   constexpr int kBrickEntities = 729;
   constexpr int kMaxColours    = 32;
 
+  // The cells of the launches of a per-cell kernel: list k is cells[start[k] .. start[k + 1]), and the cells of one list
+  // share no DoF (plain adds).  cells: device; start: host, n + 1 offsets; n == 0: one launch over all cells.
+  struct CellLists
+  {
+    const uint32_t *cells = nullptr;
+    const uint32_t *start = nullptr;
+    int             n     = 0;
+    CellLists() = default;
+    CellLists(const uint32_t *cells_, const uint32_t *start_, int n_) : cells(cells_), start(start_), n(n_) {}
+  };
+  // Cells sorted by colour, at most 32 colours (CellColouring of mgx_index_tables.hpp with the order on the device):
+  // colour k is order[start[k] .. start[k + 1]).  order == nullptr: not coloured.
+  struct ColourLists
+  {
+    uint32_t *order     = nullptr; // device [n_cells]
+    int       n         = 0;
+    uint32_t  start[33] = {0};
+    CellLists lists() const { return CellLists(order, start, n); }
+  };
+
   // Device-side view of a LaplaceOperator level (laplace_operator.h:126-163)
   struct OperatorData
   {
@@ -165,9 +185,7 @@ namespace mgx
     void     *grad_1d       = nullptr; // device [n*n], number type: G = D S, nodal derivative at the quadrature points
     // general branch on levels with many cells: cells sorted by colour (cells of one colour share
     // no DoF), one launch per colour without atomics; nullptr: one launch with atomic adds
-    uint32_t *cell_order    = nullptr; // device [n_cells]
-    int       n_cell_colours = 0;
-    uint32_t  cell_colour_start[33] = {0};
+    ColourLists cell_colours;
     // Ordered assembly of the per-cell kernels (levels without a brick schedule and without cell
     // colours): the kernels store each cell's (p+1)^3 local results in cell_scratch and
     // assemble_kernel adds, for every DoF d, the entries asm_pos[asm_start[d] .. asm_start[d+1]) in
@@ -226,10 +244,8 @@ namespace mgx
     bool                coarse_coloured = false; // coarse cells c and c' with c % 8 == c' % 8 share no DoF
     // two dimensions (mgx_kernels_2d.hip): children [n_coarse_cells*4], weight_shift [n_coarse_cells*9], own27 the
     // ownership bits of the 9 entities of a fine cell; the restriction runs over the parents colour by colour
-    // (parents of one colour share no DoF: plain adds): parent_order [n_coarse_cells] sorted by colour
-    uint32_t           *parent_order = nullptr;
-    int                 n_parent_colours = 0;
-    uint32_t            parent_colour_start[33] = {0};
+    // (parents of one colour share no DoF: plain adds)
+    ColourLists         parent_colours;
     uint32_t            n_cus = 256;
     uint32_t            colour_min = 16384; // Tunables::restrict_colour_min
   };
@@ -306,19 +322,21 @@ namespace mgx
   void launch_restrict_add_pipe(hipStream_t s, const TransferData &t, void *coarse, const void *fine,
                                 bool with_constraints);
 
-  // ---- cell loops (mgx_kernels.hip) ----
-  // The cells of the launches of a per-cell kernel: list k is cells[start[k] .. start[k + 1]), and the cells of one list
-  // share no DoF (plain adds).  cells: device; start: host, n + 1 offsets; n == 0: one launch over all cells.
-  struct CellLists
+  // ---- cell loops (mgx_kernels.hip, mgx_kernels_2d.hip, mgx_nonlinear_2d.hip) ----
+  // The list loop of the per-cell kernels: launch(list, count, scratch) once per non-empty list of cells that share no
+  // DoF (plain adds); with no lists once over all cells, into the scratch array of the ordered assembly if `ordered`
+  // (the caller assembles), else with atomic adds.  Returns the scratch array the launch wrote, or nullptr.
+  template <typename T, typename F>
+  static T *for_each_cell_list(const OperatorData &op, const CellLists &lists, bool ordered, F &&launch)
   {
-    const uint32_t *cells = nullptr;
-    const uint32_t *start = nullptr;
-    int             n     = 0;
-    CellLists() = default;
-    CellLists(const uint32_t *cells_, const uint32_t *start_, int n_) : cells(cells_), start(start_), n(n_) {}
-    // the operator's cell colours (none: all cells)
-    explicit CellLists(const OperatorData &op) : cells(op.cell_order), start(op.cell_colour_start), n(op.n_cell_colours) {}
-  };
+    T *scratch = (lists.n == 0 && ordered) ? (T *)op.cell_scratch : nullptr;
+    if (lists.n == 0 && op.n_cells > 0)
+      launch((const uint32_t *)nullptr, op.n_cells, scratch);
+    for (int k = 0; k < lists.n; ++k)
+      if (const uint32_t count = lists.start[k + 1] - lists.start[k])
+        launch(lists.cells + lists.start[k], count, scratch);
+    return scratch;
+  }
   // The symmetric tensor [xx,yy,zz,xy,xz,yz] a general kernel applies (PERQ decides which it reads): one per cell and
   // quadrature point, device [n_cells][6][n^3] in the kernel's number type, or one per mesh; the other is null / zero.
   struct CellTensor
@@ -568,7 +586,7 @@ namespace mgx
                            bool with_constraints);
   // ---- quadrilaterals (mgx_kernels_2d.hip): what the four launchers above hand over to when op.dim == 2 ----
   // the cell loop with launch_cell_loop's arguments; the cells are added up by the ordered assembly (op.asm_start: dst
-  // is written) or colour by colour with plain adds (op.cell_order: dst zeroed by the caller) -- never atomics
+  // is written) or colour by colour with plain adds (op.cell_colours: dst zeroed by the caller) -- never atomics
   void launch_cell_loop_2d(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *tail_src,
                            uint32_t n_head, const ChebPost *post);
   void launch_cell_diagonal_2d(hipStream_t s, const OperatorData &op, void *diag, const double *a1d, const double *m1d);
@@ -576,8 +594,8 @@ namespace mgx
                             bool with_constraints);
   void launch_restrict_add_2d(hipStream_t s, const TransferData &t, void *coarse, const void *fine, bool with_constraints);
   // ---- solution-dependent coefficients on quadrilaterals (mgx_nonlinear_2d.hip) ----
-  // launch_evaluate_coefficient, launch_cell_nl_residual and launch_interpolate_to_coarse for op.dim == 2: metric is
-  // [xx,yy,xy], coef_q and unit_q are [n_cells][3][n^2], jxw_q is [n_cells][n^2], own_c holds 9 bits per coarse cell.
+  // what launch_evaluate_coefficient, launch_cell_nl_residual (whose `lists` are not looked at: the 2D residual derives
+  // them) and launch_interpolate_to_coarse hand over to when op.dim == 2: metric is [xx,yy,xy], coef_q and unit_q are [n_cells][3][n^2], jxw_q is [n_cells][n^2], own_c holds 9 bits per coarse cell.
   // The residual adds the cells up as launch_cell_loop_2d does: the ordered assembly where the level has the tables (dst
   // is written), else colour by colour (dst zeroed by the caller); the caller has checked that one of the two exists.
   void launch_evaluate_coefficient_2d(hipStream_t s, const OperatorData &op, void *coef_q, int coef_number, bool minimal_surface,

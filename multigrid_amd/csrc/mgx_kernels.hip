@@ -1052,21 +1052,6 @@ namespace mgx
     dispatch_number(op.number, [&](auto t) { assemble_cheb_t<decltype(t)>(s, op, x, n_head, post); });
   }
 
-  // The list loop of the per-cell kernels: launch(list, count, scratch) once per non-empty list of cells that share no
-  // DoF (plain adds); with no lists once over all cells, into the scratch array of the ordered assembly if `ordered`
-  // (the caller assembles), else with atomic adds.  Returns the scratch array the launch wrote, or nullptr.
-  template <typename T, typename F>
-  static T *for_each_cell_list(const OperatorData &op, const CellLists &lists, bool ordered, F &&launch)
-  {
-    T *scratch = (lists.n == 0 && ordered) ? (T *)op.cell_scratch : nullptr;
-    if (lists.n == 0 && op.n_cells > 0)
-      launch((const uint32_t *)nullptr, op.n_cells, scratch);
-    for (int k = 0; k < lists.n; ++k)
-      if (const uint32_t count = lists.start[k + 1] - lists.start[k])
-        launch(lists.cells + lists.start[k], count, scratch);
-    return scratch;
-  }
-
   // One launch of the general per-cell kernel (cell_loop_general_kernel), in the names of its comment.
   enum CellForm
   {
@@ -1105,7 +1090,7 @@ namespace mgx
 
   // Three ways to add the cell contributions up (op decides): ordered assembly through the scratch
   // array (op.asm_start; dst is written, not added to), one launch per cell colour with plain
-  // read-modify-writes (op.cell_order), or one launch with atomic adds (fallback).
+  // read-modify-writes (op.cell_colours), or one launch with atomic adds (fallback).
   template <int P, typename T>
   static void cell_loop_t(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *tail_src,
                           uint32_t n_head, const ChebPost *post)
@@ -1120,7 +1105,7 @@ namespace mgx
         g.src    = src;
         g.tensor = CellTensor::of(op);
         // the operator's cell colours only when there is no ordered assembly
-        for_each_cell_list<T>(op, scratch ? CellLists() : CellLists(op), scratch != nullptr,
+        for_each_cell_list<T>(op, scratch ? CellLists() : op.cell_colours.lists(), scratch != nullptr,
                               [&](const uint32_t *list, uint32_t count, T *scr) { launch_general_cells<P, T>(s, op, g, list, count, scr); });
       }
     else
@@ -1397,6 +1382,8 @@ namespace mgx
   void launch_cell_nl_residual(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,
                                const void *unit_q, const void *jxw_q, void *dst, const void *src, const CellLists &lists)
   {
+    if (op.dim == 2) // (its lists are the operator's own cell colours)
+      return launch_cell_nl_residual_2d(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src);
     dispatch_number_degree(op.number, op.p, [&](auto t, auto P) {
       cell_nl_residual_t<P.value, decltype(t)>(s, op, minimal_surface, metric, det, unit_q, jxw_q, dst, src, lists);
     });

@@ -519,27 +519,16 @@ namespace mgx
     return op.coef_q ? kTensorPerPoint : (op.full_tensor ? kTensorPerMesh : kDiagonalCoefficient);
   }
 
-  // launch(list, count, scratch): once over all cells into the scratch array of the ordered assembly where the operator
-  // has one, else once per cell colour
-  template <typename T, typename F>
-  static T *for_each_launch_2d(const OperatorData &op, F &&launch)
-  {
-    T *scratch = op.asm_start ? (T *)op.cell_scratch : nullptr;
-    if (scratch)
-      launch((const uint32_t *)nullptr, op.n_cells, scratch);
-    else
-      for (int k = 0; k < op.n_cell_colours; ++k)
-        if (const uint32_t count = op.cell_colour_start[k + 1] - op.cell_colour_start[k])
-          launch(op.cell_order + op.cell_colour_start[k], count, scratch);
-    return scratch;
-  }
+  // the lists of a launcher: none, once over all cells into the scratch array of the ordered assembly, where the operator
+  // has one; else its cell colours (operator_create has made sure that a level without the tables is coloured)
+  static CellLists cell_lists_2d(const OperatorData &op) { return op.asm_start ? CellLists() : op.cell_colours.lists(); }
 
   template <int P, typename T>
   static void cell_loop_2d_t(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *tail_src,
                              uint32_t n_head, const ChebPost *post)
   {
     using C = Cfg2<P>;
-    T *scratch = for_each_launch_2d<T>(op, [&](const uint32_t *list, uint32_t count, T *scr) {
+    T *scratch = for_each_cell_list<T>(op, cell_lists_2d(op), true, [&](const uint32_t *list, uint32_t count, T *scr) {
       const uint32_t nb = (count + C::CPB - 1) / C::CPB;
       dispatch_mode<kDiagonalCoefficient, kTensorPerMesh, kTensorPerPoint>(cell_form(op), [&](auto FORM) {
         hipLaunchKernelGGL((cell_loop_2d_kernel<P, T, FORM.value>), dim3(nb), dim3(C::THREADS), 0, s, (T *)dst, (const T *)src,
@@ -571,7 +560,7 @@ namespace mgx
         d1.a[i] = (T)a[i];
         d1.m[i] = (T)m[i];
       }
-    T *scratch = for_each_launch_2d<T>(op, [&](const uint32_t *list, uint32_t count, T *scr) {
+    T *scratch = for_each_cell_list<T>(op, cell_lists_2d(op), true, [&](const uint32_t *list, uint32_t count, T *scr) {
       const uint32_t nb = (uint32_t)(((uint64_t)count * N + 255) / 256);
       dispatch_mode<kDiagonalCoefficient, kTensorPerMesh, kTensorPerPoint>(cell_form(op), [&](auto FORM) {
         hipLaunchKernelGGL((cell_diagonal_2d_kernel<P, T, FORM.value>), dim3(nb), dim3(256), 0, s, (T *)diag, op.idx27, count,
@@ -607,11 +596,12 @@ namespace mgx
     const uint32_t     *idx_c = with_constraints ? c.idx27 : c.idx27_plain;
     dispatch_number_degree(c.number, c.p, [&](auto number, auto P) {
       using T = decltype(number);
-      for (int k = 0; k < t.n_parent_colours; ++k)
-        if (const uint32_t count = t.parent_colour_start[k + 1] - t.parent_colour_start[k])
-          hipLaunchKernelGGL((restrict_2d_kernel<P.value, T>), dim3(count), dim3(TCfg2<P.value>::THREADS), 0, s, (T *)coarse,
-                             (const T *)fine, idx_c, f.idx27_plain, t.children, t.weight_shift,
-                             t.parent_order + t.parent_colour_start[k], count, (const Basis1D<T> *)c.basis);
+      // (the parents of a colour share no DoF; a transfer always has the colours: never one launch over all parents)
+      for_each_cell_list<T>(c, t.parent_colours.lists(), false, [&](const uint32_t *list, uint32_t count, T *) {
+        hipLaunchKernelGGL((restrict_2d_kernel<P.value, T>), dim3(count), dim3(TCfg2<P.value>::THREADS), 0, s, (T *)coarse,
+                           (const T *)fine, idx_c, f.idx27_plain, t.children, t.weight_shift, list, count,
+                           (const Basis1D<T> *)c.basis);
+      });
     });
   }
 

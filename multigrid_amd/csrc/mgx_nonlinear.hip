@@ -350,6 +350,8 @@ namespace mgx
   void launch_evaluate_coefficient(hipStream_t s, const OperatorData &op, void *coef_q, int coef_number, bool minimal_surface,
                                    const double *metric, double det, const void *unit_q, const void *jxw_q, const void *state)
   {
+    if (op.dim == 2)
+      return launch_evaluate_coefficient_2d(s, op, coef_q, coef_number, minimal_surface, metric, det, unit_q, jxw_q, state);
     dispatch_degree(op.p, [&](auto P) {
       auto run = [&](auto t, auto to) {
         evaluate_coefficient_t<P.value, decltype(t), decltype(to)>(s, op, coef_q, minimal_surface, metric, det, unit_q, jxw_q, state);
@@ -376,6 +378,8 @@ namespace mgx
   void launch_interpolate_to_coarse(hipStream_t s, const TransferData &t, const void *r1d, const uint32_t *own_c, void *coarse,
                                     const void *fine)
   {
+    if (t.coarse->dim == 2)
+      return launch_interpolate_to_coarse_2d(s, t, r1d, own_c, coarse, fine);
     dispatch_number_degree(t.coarse->number, t.coarse->p, [&](auto number, auto P) {
       interpolate_t<P.value, decltype(number)>(s, t, r1d, own_c, coarse, fine);
     });

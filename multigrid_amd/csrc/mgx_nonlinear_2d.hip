@@ -384,28 +384,20 @@ namespace mgx
     const bool curved = unit_q != nullptr;
     // once over all cells into the scratch array of the ordered assembly where the operator has one (dst is written by
     // the assembly), else once per cell colour (dst zeroed by the caller)
-    T   *scratch = op.asm_start ? (T *)op.cell_scratch : nullptr;
-    auto launch  = [&](const uint32_t *list, uint32_t count) {
+    const CellLists lists = op.asm_start ? CellLists() : op.cell_colours.lists();
+    T *scratch = for_each_cell_list<T>(op, lists, true, [&](const uint32_t *list, uint32_t count, T *scr) {
       const uint32_t nb = (count + C::CPB - 1) / C::CPB;
       dispatch_mode<0, 1>(minimal_surface, [&](auto MINSURF) {
         dispatch_mode<0, 1>(curved, [&](auto PERQ) {
           hipLaunchKernelGGL((nl_residual_2d_kernel<P, T, MINSURF.value != 0, PERQ.value != 0>), dim3(nb), dim3(C::THREADS), 0, s,
                              (T *)dst, (const T *)state, op.idx27, op.idx27_plain, count, (const Basis1D<T> *)op.basis,
                              (T)(curved ? 0. : M[0]), (T)(curved ? 0. : M[1]), (T)(curved ? 0. : M[2]), (T)(curved ? 0. : det),
-                             (const T *)unit_q, (const T *)(curved ? jxw_q : nullptr), list, scratch);
+                             (const T *)unit_q, (const T *)(curved ? jxw_q : nullptr), list, scr);
         });
       });
-    };
+    });
     if (scratch)
-      {
-        if (op.n_cells > 0)
-          launch(nullptr, op.n_cells);
-        launch_assemble(s, op, 0, dst, nullptr, 0u);
-      }
-    else
-      for (int k = 0; k < op.n_cell_colours; ++k)
-        if (const uint32_t count = op.cell_colour_start[k + 1] - op.cell_colour_start[k])
-          launch(op.cell_order + op.cell_colour_start[k], count);
+      launch_assemble(s, op, 0, dst, nullptr, 0u);
   }
 
   void launch_cell_nl_residual_2d(hipStream_t s, const OperatorData &op, bool minimal_surface, const double *metric, double det,

@@ -3,6 +3,7 @@
 // element data (Gauss-Lobatto nodes, Gauss rule, shape values, collocation derivative, embedding) are those of
 // mgx_cube.cpp, taken from a one-cell cube of the same degree.
 #include "../../include/mgx_square.h"
+#include "mgx_index_tables.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -62,7 +63,7 @@ struct mgx_square_s
 namespace
 {
   inline int code(int a, int p) { return a == 0 ? 0 : (a == p ? 2 : 1); }
-  inline int entity_size(int e, int p) { return (e % 3 == 1 ? p - 1 : 1) * (e / 3 == 1 ? p - 1 : 1); }
+  using mgx::entity_size; // (of the 9 entities of a cell, e = cy 3 + cx)
   // DoF of node (i, j) of a cell through its 9 entries (the addressing of read_dof_values_compressed in two dimensions)
   inline uint32_t local_dof(const uint32_t *ix, int p, int i, int j)
   {
