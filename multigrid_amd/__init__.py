@@ -378,8 +378,90 @@ class DeviceVector:
             pass
 
 
-class Cube:
+class _Mesh:
+    """What Cube and Square share: the handle `h` and the accessors whose C names differ in the prefix only
+    (mgx_cube_* / mgx_square_*)."""
+
+    _prefix, _dim = None, 0
+
+    def _c(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._c("destroy")(self.h)
+            self.h = None
+
+    def n_cells(self, l):
+        return self._c("n_cells")(self.h, l)
+
+    def n_dofs(self, l):
+        return self._c("n_dofs")(self.h, l)
+
+    def n_constrained(self, l):
+        return self._c("n_constrained")(self.h, l)
+
+    def cell_size(self, l):
+        return self._c("cell_size")(self.h, l)
+
+    def _arr(self, name, shape, *args):
+        f = self._c(name)
+        p = f(self.h, *args)
+        n = int(np.prod(shape))
+        if n == 0:
+            return np.zeros(shape, dtype=np.dtype(f.restype._type_))
+        return np.ctypeslib.as_array(p, shape=(n,)).reshape(shape).copy()
+
+    def _filled(self, name, shape, l):
+        out = np.empty(shape)
+        check(self._c(name)(self.h, l, out.ctypes.data_as(_lib.f64p)))
+        return out
+
+    def constrained(self, l):
+        return self._arr("constrained", (self.n_constrained(l),), l)
+
+    def cell_coords(self, l):
+        return self._arr("cell_coords", (self.n_cells(l), self._dim), l)
+
+    def dof_grid(self, l):
+        return self._arr("dof_grid", (self.n_dofs(l),), l)
+
+    def shape_values(self):
+        n = self.degree + 1
+        return self._arr("shape_values", (n, n))
+
+    def colloc_grad(self):
+        n = self.degree + 1
+        return self._arr("colloc_grad", (n, n))
+
+    def qweights(self):
+        return self._arr("qweights", (self.degree + 1,))
+
+    def qpoints(self):
+        return self._arr("qpoints", (self.degree + 1,))
+
+    def gll(self):
+        return self._arr("gll", (self.degree + 1,))
+
+    def prolong_1d(self):
+        n = self.degree + 1
+        return self._arr("prolong_1d", (2 * n - 1, n))
+
+    def operator_desc(self, l, number=F64):
+        d = _lib.OperatorDesc()
+        check(self._c("operator_desc")(self.h, l, number, C.byref(d)))
+        return d
+
+    def seeded_vector(self, l, seed=42):
+        out = np.empty(self.n_dofs(l))
+        check(self._c("seeded_vector")(self.h, l, seed, out.ctypes.data_as(_lib.f64p)))
+        return out
+
+
+class Cube(_Mesh):
     """Host-side discretisation of poisson_cube (include/mgx_cube.h): what deal.II supplies."""
+
+    _prefix, _dim = "mgx_cube_", 3
 
     NUMBERING = {"brick": 0, "cell": 1}
     GEOMETRY = {"cartesian": 0, "sheared": 1, "shell_sector": 2}
@@ -436,42 +518,14 @@ class Cube:
         self.n_levels = self.lib.mgx_cube_n_levels(h)
         self.max_level = self.n_levels - 1
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.mgx_cube_destroy(self.h)
-            self.h = None
-
-    def n_cells(self, l):
-        return self.lib.mgx_cube_n_cells(self.h, l)
-
-    def n_dofs(self, l):
-        return self.lib.mgx_cube_n_dofs(self.h, l)
-
-    def n_constrained(self, l):
-        return self.lib.mgx_cube_n_constrained(self.h, l)
-
     def cells_per_dim(self, l):
         return self.lib.mgx_cube_cells_per_dim(self.h, l)
 
-    def cell_size(self, l):
-        return self.lib.mgx_cube_cell_size(self.h, l)
-
-    def _arr(self, fn, shape, *args):
-        f = getattr(self.lib, fn)
-        p = f(self.h, *args)
-        n = int(np.prod(shape))
-        if n == 0:
-            return np.zeros(shape, dtype=np.dtype(f.restype._type_))
-        return np.ctypeslib.as_array(p, shape=(n,)).reshape(shape).copy()
-
     def idx27(self, l):
-        return self._arr("mgx_cube_idx27", (self.n_cells(l), 27), l)
+        return self._arr("idx27", (self.n_cells(l), 27), l)
 
     def idx27_plain(self, l):
-        return self._arr("mgx_cube_idx27_plain", (self.n_cells(l), 27), l)
-
-    def constrained(self, l):
-        return self._arr("mgx_cube_constrained", (self.n_constrained(l),), l)
+        return self._arr("idx27_plain", (self.n_cells(l), 27), l)
 
     def coef_q(self, l):
         """[n_cells, 6, (p+1)^3] merged coefficient of a mapped level (None on the Cartesian cube)"""
@@ -488,13 +542,11 @@ class Cube:
         return np.ctypeslib.as_array(ptr, shape=(self.n_cells(l), (self.degree + 1) ** 3)).copy()
 
     def children(self, l):
-        return self._arr("mgx_cube_children", (self.n_cells(l - 1), 8), l)
+        return self._arr("children", (self.n_cells(l - 1), 8), l)
 
     def cell_nodes(self, l):
         """physical Gauss-Lobatto points of every cell, [n_cells, 3, (p+1)^3] (x fastest)"""
-        out = np.empty((self.n_cells(l), 3, (self.degree + 1) ** 3))
-        check(self.lib.mgx_cube_cell_nodes(self.h, l, out.ctypes.data_as(_lib.f64p)))
-        return out
+        return self._filled("cell_nodes", (self.n_cells(l), 3, (self.degree + 1) ** 3), l)
 
     def entity_multiplicity(self, l):
         """multi-block meshes: cells around each of the 27 entities of every cell, [n_cells, 27]"""
@@ -503,45 +555,16 @@ class Cube:
             return None
         return np.ctypeslib.as_array(ptr, shape=(self.n_cells(l) * 27,)).reshape(-1, 27).copy()
 
-    def cell_coords(self, l):
-        return self._arr("mgx_cube_cell_coords", (self.n_cells(l), 3), l)
-
-    def dof_grid(self, l):
-        return self._arr("mgx_cube_dof_grid", (self.n_dofs(l),), l)
-
-    def shape_values(self):
-        n = self.degree + 1
-        return self._arr("mgx_cube_shape_values", (n, n))
-
-    def colloc_grad(self):
-        n = self.degree + 1
-        return self._arr("mgx_cube_colloc_grad", (n, n))
-
-    def qweights(self):
-        return self._arr("mgx_cube_qweights", (self.degree + 1,))
-
-    def qpoints(self):
-        return self._arr("mgx_cube_qpoints", (self.degree + 1,))
-
-    def gll(self):
-        return self._arr("mgx_cube_gll", (self.degree + 1,))
-
-    def prolong_1d(self):
-        n = self.degree + 1
-        return self._arr("mgx_cube_prolong_1d", (2 * n - 1, n))
-
     def rhs(self, l):
-        return self._arr("mgx_cube_rhs", (self.n_dofs(l),), l)
+        return self._arr("rhs", (self.n_dofs(l),), l)
 
     def rhs_quadrature(self, l):
         """f(x_q) JxW_q, [n_cells, (p+1)^3]: the integrand of the right-hand side (input of compute_residual)"""
-        out = np.empty((self.n_cells(l), (self.degree + 1) ** 3))
-        check(self.lib.mgx_cube_rhs_quadrature(self.h, l, out.ctypes.data_as(_lib.f64p)))
-        return out
+        return self._filled("rhs_quadrature", (self.n_cells(l), (self.degree + 1) ** 3), l)
 
     def bc(self, l):
         n = self.lib.mgx_cube_bc_count(self.h, l)
-        return self._arr("mgx_cube_bc_index", (n,), l), self._arr("mgx_cube_bc_value", (n,), l)
+        return self._arr("bc_index", (n,), l), self._arr("bc_value", (n,), l)
 
     def neighbors(self, l):
         """[(rank, index array)] of the interface exchange on level l (ascending rank)"""
@@ -549,14 +572,14 @@ class Cube:
         for k in range(self.lib.mgx_cube_n_neighbors(self.h, l)):
             n = self.lib.mgx_cube_neighbor_count(self.h, l, k)
             out.append((self.lib.mgx_cube_neighbor_rank(self.h, l, k),
-                        self._arr("mgx_cube_neighbor_index", (n,), l, k)))
+                        self._arr("neighbor_index", (n,), l, k)))
         return out
 
     def shared(self, l):
-        return self._arr("mgx_cube_shared", (self.lib.mgx_cube_n_shared(self.h, l),), l)
+        return self._arr("shared", (self.lib.mgx_cube_n_shared(self.h, l),), l)
 
     def not_owned(self, l):
-        return self._arr("mgx_cube_not_owned", (self.lib.mgx_cube_n_not_owned(self.h, l),), l)
+        return self._arr("not_owned", (self.lib.mgx_cube_n_not_owned(self.h, l),), l)
 
     def cells_per_dim3(self, l):
         a, b = (C.c_uint32 * 3)(), (C.c_uint32 * 3)()
@@ -569,20 +592,10 @@ class Cube:
         self.lib.mgx_cube_l2_error_parts(self.h, l, s.ctypes.data_as(_lib.f64p), C.byref(e), C.byref(v))
         return e.value, v.value
 
-    def operator_desc(self, l, number=F64):
-        d = _lib.OperatorDesc()
-        check(self.lib.mgx_cube_operator_desc(self.h, l, number, C.byref(d)))
-        return d
-
     def l2_error(self, l, solution):
         s = np.ascontiguousarray(solution, dtype=np.float64)
         assert s.size == self.n_dofs(l)
         return self.lib.mgx_cube_l2_error(self.h, l, s.ctypes.data_as(_lib.f64p))
-
-    def seeded_vector(self, l, seed=42):
-        out = np.empty(self.n_dofs(l))
-        check(self.lib.mgx_cube_seeded_vector(self.h, l, seed, out.ctypes.data_as(_lib.f64p)))
-        return out
 
     # ---- affine geometry of the Cartesian cube / box for the general branch (mgx_cube_solver_create_general) ----
     def affine_metric(self, l, jacobian=None):
@@ -625,10 +638,11 @@ class Cube:
         return (-0.9 if self.box_desc is None else self.box_desc["origin"]) + X
 
 
-class Square:
+class Square(_Mesh):
     """Host-side discretisation of poisson_cube with dimension = 2 (include/mgx_square.h): what deal.II supplies for
     LaplaceOperator<2,p,number> and MultigridSolver<2,p,...>.  One rank.  Method names are Cube's where they apply."""
 
+    _prefix, _dim = "mgx_square_", 2
     size, rank, shell, box_desc, level_offset = 1, 0, None, None, 0
 
     MAPPED = {"annulus_sector": 1}  # MGX_SQUARE_GEOMETRY_*
@@ -657,71 +671,22 @@ class Square:
         self.n_levels = self.lib.mgx_square_n_levels(h)
         self.max_level = self.n_levels - 1
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.mgx_square_destroy(self.h)
-            self.h = None
-
-    def n_cells(self, l):
-        return self.lib.mgx_square_n_cells(self.h, l)
-
-    def n_dofs(self, l):
-        return self.lib.mgx_square_n_dofs(self.h, l)
-
-    def n_constrained(self, l):
-        return self.lib.mgx_square_n_constrained(self.h, l)
-
     def cells_per_dim2(self, l):
         a = (C.c_uint32 * 2)()
         self.lib.mgx_square_cells_per_dim2(self.h, l, C.byref(a))
         return tuple(a)
 
-    def cell_size(self, l):
-        return self.lib.mgx_square_cell_size(self.h, l)
-
-    _arr = Cube._arr
-
     def idx9(self, l):
-        return self._arr("mgx_square_idx9", (self.n_cells(l), 9), l)
+        return self._arr("idx9", (self.n_cells(l), 9), l)
 
     def idx9_plain(self, l):
-        return self._arr("mgx_square_idx9_plain", (self.n_cells(l), 9), l)
-
-    def constrained(self, l):
-        return self._arr("mgx_square_constrained", (self.n_constrained(l),), l)
+        return self._arr("idx9_plain", (self.n_cells(l), 9), l)
 
     def children(self, l):
-        return self._arr("mgx_square_children", (self.n_cells(l - 1), 4), l)
+        return self._arr("children", (self.n_cells(l - 1), 4), l)
 
     def weight_shift(self, l):
-        return self._arr("mgx_square_weight_shift", (self.n_cells(l - 1), 9), l)
-
-    def cell_coords(self, l):
-        return self._arr("mgx_square_cell_coords", (self.n_cells(l), 2), l)
-
-    def dof_grid(self, l):
-        return self._arr("mgx_square_dof_grid", (self.n_dofs(l),), l)
-
-    def shape_values(self):
-        n = self.degree + 1
-        return self._arr("mgx_square_shape_values", (n, n))
-
-    def colloc_grad(self):
-        n = self.degree + 1
-        return self._arr("mgx_square_colloc_grad", (n, n))
-
-    def qweights(self):
-        return self._arr("mgx_square_qweights", (self.degree + 1,))
-
-    def qpoints(self):
-        return self._arr("mgx_square_qpoints", (self.degree + 1,))
-
-    def gll(self):
-        return self._arr("mgx_square_gll", (self.degree + 1,))
-
-    def prolong_1d(self):
-        n = self.degree + 1
-        return self._arr("mgx_square_prolong_1d", (2 * n - 1, n))
+        return self._arr("weight_shift", (self.n_cells(l - 1), 9), l)
 
     def _poisson_problem(self):
         if self.mapped is not None:
@@ -729,12 +694,12 @@ class Square:
 
     def rhs(self, l):
         self._poisson_problem()
-        return self._arr("mgx_square_rhs", (self.n_dofs(l),), l)
+        return self._arr("rhs", (self.n_dofs(l),), l)
 
     def bc(self, l):
         self._poisson_problem()
         n = self.lib.mgx_square_bc_count(self.h, l)
-        return self._arr("mgx_square_bc_index", (n,), l), self._arr("mgx_square_bc_value", (n,), l)
+        return self._arr("bc_index", (n,), l), self._arr("bc_value", (n,), l)
 
     def l2_error(self, l, solution):
         self._poisson_problem()
@@ -742,28 +707,11 @@ class Square:
         assert s.size == self.n_dofs(l)
         return self.lib.mgx_square_l2_error(self.h, l, s.ctypes.data_as(_lib.f64p))
 
-    def seeded_vector(self, l, seed=42):
-        out = np.empty(self.n_dofs(l))
-        check(self.lib.mgx_square_seeded_vector(self.h, l, seed, out.ctypes.data_as(_lib.f64p)))
-        return out
-
-    def operator_desc(self, l, number=F64):
-        d = _lib.OperatorDesc()
-        check(self.lib.mgx_square_operator_desc(self.h, l, number, C.byref(d)))
-        return d
-
     def coef_q(self, l):
         """[n_cells, 3, (p+1)^2] the per-(cell, q) tensor equivalent to the one tensor of operator_desc (weight folded in)"""
-        out = np.empty((self.n_cells(l), 3, (self.degree + 1) ** 2))
-        check(self.lib.mgx_square_coef_q(self.h, l, out.ctypes.data_as(_lib.f64p)))
-        return out
+        return self._filled("coef_q", (self.n_cells(l), 3, (self.degree + 1) ** 2), l)
 
     # ---- geometry for the solution-dependent coefficients (mgx_square_solver_create_general) ----
-    def _filled(self, fn, shape, l):
-        out = np.empty(shape)
-        check(getattr(self.lib, fn)(self.h, l, out.ctypes.data_as(_lib.f64p)))
-        return out
-
     def affine_metric(self, l):
         """(M = J^-1 J^-T as [xx,yy,xy], det J) of the cells of level l of a box, J = h_l A with the box's jacobian A"""
         m, det = np.zeros(3), C.c_double()
@@ -777,19 +725,19 @@ class Square:
 
     def dof_coordinates(self, l):
         """[n_dofs, 2] physical coordinates of the Gauss-Lobatto node of every DoF of level l"""
-        return self._filled("mgx_square_dof_coordinates", (self.n_dofs(l), 2), l)
+        return self._filled("dof_coordinates", (self.n_dofs(l), 2), l)
 
     def cell_nodes(self, l):
         """[n_cells, (p+1)^2, 2] the nodes of every cell, x fastest"""
-        return self._filled("mgx_square_cell_nodes", (self.n_cells(l), (self.degree + 1) ** 2, 2), l)
+        return self._filled("cell_nodes", (self.n_cells(l), (self.degree + 1) ** 2, 2), l)
 
     def unit_q(self, l):
         """[n_cells, 3, (p+1)^2] JxW_q J^-1 J^-T of the isoparametric cells as [xx,yy,xy]"""
-        return self._filled("mgx_square_unit_q", (self.n_cells(l), 3, (self.degree + 1) ** 2), l)
+        return self._filled("unit_q", (self.n_cells(l), 3, (self.degree + 1) ** 2), l)
 
     def jxw_q(self, l):
         """[n_cells, (p+1)^2] JxW_q of the isoparametric cells"""
-        return self._filled("mgx_square_jxw_q", (self.n_cells(l), (self.degree + 1) ** 2), l)
+        return self._filled("jxw_q", (self.n_cells(l), (self.degree + 1) ** 2), l)
 
 
 def _cell_dofs(idx27, p):
@@ -869,14 +817,16 @@ class LaplaceOperator:
         check(self.lib.mgx_compute_diagonal(self.h))
 
     # ---- MinimalSurfaceOperator (minimal_surface/program.cc:103-200) ----
+    def _by_dimension(self, name, dim):
+        """the C entry point of a call that exists once per dimension: `name` in three dimensions, `name`_2d in two"""
+        return getattr(self.lib, name + ("_2d" if dim == 2 else ""))
+
     def enable_coefficient_update(self, metric, det_jacobian):
         """affine geometry of the level: M = J^-1 J^-T as [xx,yy,zz,xy,xz,yz] and det J (Cube.affine_metric)"""
         m = np.ascontiguousarray(metric, dtype=np.float64)
-        if m.size == 3:  # a 2D operator: [xx,yy,xy] (Square.affine_metric)
-            check(self.lib.mgx_operator_enable_coefficient_update_2d(self.h, m.ctypes.data_as(_lib.f64p), float(det_jacobian)))
-            return
-        assert m.size == 6
-        check(self.lib.mgx_operator_enable_coefficient_update(self.h, m.ctypes.data_as(_lib.f64p), float(det_jacobian)))
+        assert m.size in (3, 6)  # 3: a 2D operator, [xx,yy,xy] (Square.affine_metric)
+        fn = self._by_dimension("mgx_operator_enable_coefficient_update", 2 if m.size == 3 else 3)
+        check(fn(self.h, m.ctypes.data_as(_lib.f64p), float(det_jacobian)))
 
     def enable_coefficient_update_q(self, unit_q, jxw_q):
         """per-point geometry of a level with curved cells: unit_q [n_cells, 6, (p+1)^3] = JxW_q J^-1 J^-T and jxw_q
@@ -885,14 +835,10 @@ class LaplaceOperator:
         w = np.ascontiguousarray(jxw_q, dtype=np.float64)
         p, n = C.c_void_p(), C.c_size_t()
         check(self.lib.mgx_operator_get_coefficient(self.h, C.byref(p), C.byref(n)))  # (refuses an operator without coef_q)
-        if 3 * w.size == n.value:  # a 2D operator (three tensor entries per point): Square.unit_q, Square.jxw_q
-            assert u.size == n.value
-            check(self.lib.mgx_operator_enable_coefficient_update_q_2d(self.h, u.ctypes.data_as(_lib.f64p),
-                                                                       w.ctypes.data_as(_lib.f64p)))
-            return
-        assert u.size == n.value and 6 * w.size == n.value
-        check(self.lib.mgx_operator_enable_coefficient_update_q(self.h, u.ctypes.data_as(_lib.f64p),
-                                                                w.ctypes.data_as(_lib.f64p)))
+        dim = 2 if 3 * w.size == n.value else 3  # 2: three tensor entries per point (Square.unit_q, Square.jxw_q)
+        assert u.size == n.value and (3, 6)[dim - 2] * w.size == n.value
+        fn = self._by_dimension("mgx_operator_enable_coefficient_update_q", dim)
+        check(fn(self.h, u.ctypes.data_as(_lib.f64p), w.ctypes.data_as(_lib.f64p)))
 
     def evaluate_coefficient(self, law, state):
         """evaluate_coefficient(first_time, solution) :120-165: coef_q from the state (operator's number type, boundary
@@ -1026,50 +972,32 @@ class MultigridSolver:
         self.comm = comm
         self.s = _lib.CubeSolver()
         self.coarse = None
-        if isinstance(cube, Square):
-            # MultigridSolver<2,p,...>: one rank, right-hand sides from the host; per_point: the operators in the
-            # per-(cell, q) form with the tensor of Square.coef_q
-            # general: mgx_square_solver_create_general (the geometry is the square's own: its jacobian or its map)
-            if comm is not None or agglomerate is not True or device_rhs or jacobian is not None or \
-                    (coef_q is not None and not general):
-                raise ValueError("MultigridSolver on a Square: one rank, host right-hand sides "
-                                 "(comm, agglomerate, device_rhs, jacobian are not accepted; coef_q with general only)")
-            self.jacobian = None
-            if general:
-                cq = None
-                if coef_q is not None:
-                    keep = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in coef_q]
-                    cq = (_lib.f64p * len(keep))(*[None if a is None else a.ctypes.data_as(_lib.f64p) for a in keep])
-                check(self.lib.mgx_square_solver_create_general(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles, cq,
-                                                                C.byref(self.s)))
-            else:
-                check(self.lib.mgx_square_solver_create(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles,
-                                                        int(bool(per_point)), C.byref(self.s)))
-            self.n_levels = self.s.n_levels
-            self.max_level = self.n_levels - 1
-            self.h = C.c_void_p(self.s.solver)
-            if polynomial != "first_kind":
-                check(self.lib.mgx_solver_set_polynomial_type(self.h, Chebyshev.POLYNOMIAL[polynomial]))
-            return
-        if cube.size > 1:
-            if comm is None:
-                raise ValueError("a decomposed cube needs a Communicator")
+        square = isinstance(cube, Square)
+        # MultigridSolver<2,p,...>: one rank, right-hand sides from the host; per_point: the operators in the
+        # per-(cell, q) form with the tensor of Square.coef_q
+        # general: mgx_square_solver_create_general (the geometry is the square's own: its jacobian or its map)
+        if square and (comm is not None or agglomerate is not True or device_rhs or jacobian is not None or
+                       (coef_q is not None and not general)):
+            raise ValueError("MultigridSolver on a Square: one rank, host right-hand sides "
+                             "(comm, agglomerate, device_rhs, jacobian are not accepted; coef_q with general only)")
+        if cube.size > 1 and comm is None:
+            raise ValueError("a decomposed cube needs a Communicator")
         self.jacobian = None if jacobian is None else np.ascontiguousarray(jacobian, dtype=np.float64).reshape(3, 3)
+        common = (ctx.h, cube.h, vcycle_number, degree_pre, n_cycles)
         if general:
-            jac = None if self.jacobian is None else self.jacobian.ctypes.data_as(_lib.f64p)
-            cq = None
-            if coef_q is not None:
-                keep = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in coef_q]
-                cq = (_lib.f64p * len(keep))(*[None if a is None else a.ctypes.data_as(_lib.f64p) for a in keep])
-            check(self.lib.mgx_cube_solver_create_general(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles, jac, cq,
-                                                          C.byref(self.s)))
+            keep, cq = self._pointer_array(coef_q)  # noqa: F841 (keep: the arrays live until the call returns)
+            if square:
+                check(self.lib.mgx_square_solver_create_general(*common, cq, C.byref(self.s)))
+            else:
+                jac = None if self.jacobian is None else self.jacobian.ctypes.data_as(_lib.f64p)
+                check(self.lib.mgx_cube_solver_create_general(*common, jac, cq, C.byref(self.s)))
+        elif square:
+            check(self.lib.mgx_square_solver_create(*common, int(bool(per_point)), C.byref(self.s)))
         else:
-            check(self.lib.mgx_cube_solver_create_opt(ctx.h, cube.h, vcycle_number, degree_pre, n_cycles,
-                                                      int(bool(device_rhs)), C.byref(self.s)))
+            check(self.lib.mgx_cube_solver_create_opt(*common, int(bool(device_rhs)), C.byref(self.s)))
         self.n_levels = self.s.n_levels
         self.max_level = self.n_levels - 1
         self.h = C.c_void_p(self.s.solver)
-        self.coarse = None
         if cube.size > 1 and (cube.box_desc is not None or cube.shell is not None) and \
                 ((agglomerate and os.environ.get("MGX_AGGLOMERATE", "1") != "0") or cube.level_offset > 0):
             # the set-up is local; whether to use it is decided by all ranks together (a rank that
@@ -1092,6 +1020,15 @@ class MultigridSolver:
                 prepared[0].close()
         if polynomial != "first_kind":
             check(self.lib.mgx_solver_set_polynomial_type(self.h, Chebyshev.POLYNOMIAL[polynomial]))
+
+    @staticmethod
+    def _pointer_array(coef_q):
+        """the per-level tensors as the C argument `const double *const *` (None: none, an entry None: a null pointer),
+        with the contiguous fp64 arrays the pointers refer to"""
+        if coef_q is None:
+            return None, None
+        keep = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in coef_q]
+        return keep, (_lib.f64p * len(keep))(*[None if a is None else a.ctypes.data_as(_lib.f64p) for a in keep])
 
     def _agglomerate(self, degree, n_cycles, vnumber):
         """Coarse levels of a decomposed hierarchy on every rank as a whole (mgx_solver_set_agglomeration):

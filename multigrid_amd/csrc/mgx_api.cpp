@@ -2066,6 +2066,7 @@ static int release_point_geometry(mgx_operator_t op)
 // per-point geometry: unit_q [n_cells][n_tensor][n_q] = JxW_q J^-1 J^-T with a positive diagonal, jxw_q [n_cells][n_q] > 0
 static int set_point_geometry(mgx_operator_t op, const double *unit_q, const double *jxw_q, const char *who)
 {
+  MGX_TRY(require_coef_q(op, who));
   const size_t nq = n_local_values(op->d.dim, op->d.p), nc = op->d.n_cells, nt = (size_t)n_tensor_entries(op->d.dim);
   const size_t nd = (size_t)op->d.dim; // the diagonal entries come first: [xx,yy,zz,...] / [xx,yy,xy]
   bool         ok = true;
@@ -2090,24 +2091,40 @@ static int set_point_geometry(mgx_operator_t op, const double *unit_q, const dou
   return MGX_OK;
 }
 
+// affine geometry: M = J^-1 J^-T ([xx,yy,zz,xy,xz,yz] / [xx,yy,xy]) is symmetric positive definite (leading minors), det J > 0
+static int set_affine_geometry(mgx_operator_t op, const double *metric, double det_jacobian, const char *who)
+{
+  MGX_TRY(require_coef_q(op, who));
+  double m[6] = {0, 0, 0, 0, 0, 0};
+  std::copy(metric, metric + n_tensor_entries(op->d.dim), m);
+  bool ok = det_jacobian > 0. && m[0] > 0.;
+  if (op->d.dim == 2)
+    ok = ok && m[0] * m[1] - m[2] * m[2] > 0.;
+  else
+    ok = ok && m[0] * m[1] - m[3] * m[3] > 0. &&
+         m[0] * (m[1] * m[2] - m[5] * m[5]) - m[3] * (m[3] * m[2] - m[5] * m[4]) + m[4] * (m[3] * m[5] - m[1] * m[4]) > 0.;
+  MGX_REQUIRE(ok, std::string(who) + ": the metric must be positive definite and det J > 0");
+  MGX_TRY(release_point_geometry(op));
+  std::copy(m, m + 6, op->metric);
+  op->det_jacobian = det_jacobian;
+  op->coef_update  = true;
+  return MGX_OK;
+}
+
+static int refuse_3d(mgx_operator_t op, const char *who, const char *instead)
+{
+  if (op->d.dim == 2)
+    return MGX_OK;
+  return fail(MGX_ERR_UNSUPPORTED, std::string(who) + ": not on a three-dimensional operator (call " + instead + ")");
+}
+
 /* MinimalSurfaceOperator<2,...>::initialize (minimal_surface/program.cc:112-117 with dimension = 2, :73): the mapping data
  * evaluate_coefficient and compute_residual read, for affine cells */
 int mgx_operator_enable_coefficient_update_2d(mgx_operator_t op, const double metric[3], double det_jacobian)
 {
   MGX_REQUIRE(op && metric, "mgx_operator_enable_coefficient_update_2d: null argument");
-  if (op->d.dim != 2)
-    return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_enable_coefficient_update_2d: not on a three-dimensional operator (call "
-                                     "mgx_operator_enable_coefficient_update)");
-  MGX_TRY(require_coef_q(op, "mgx_operator_enable_coefficient_update_2d"));
-  // M = J^-1 J^-T [xx, yy, xy] is symmetric positive definite, det J > 0
-  MGX_REQUIRE(det_jacobian > 0. && metric[0] > 0. && metric[0] * metric[1] - metric[2] * metric[2] > 0.,
-              "mgx_operator_enable_coefficient_update_2d: the metric must be positive definite and det J > 0");
-  MGX_TRY(release_point_geometry(op));
-  std::fill(op->metric, op->metric + 6, 0.);
-  std::copy(metric, metric + 3, op->metric);
-  op->det_jacobian = det_jacobian;
-  op->coef_update  = true;
-  return MGX_OK;
+  MGX_TRY(refuse_3d(op, "mgx_operator_enable_coefficient_update_2d", "mgx_operator_enable_coefficient_update"));
+  return set_affine_geometry(op, metric, det_jacobian, "mgx_operator_enable_coefficient_update_2d");
 }
 
 /* the same for curved cells: the per-point mapping data of MatrixFree<2> (minimal_surface/program.cc:125-131, inverse_jacobian
@@ -2115,10 +2132,7 @@ int mgx_operator_enable_coefficient_update_2d(mgx_operator_t op, const double me
 int mgx_operator_enable_coefficient_update_q_2d(mgx_operator_t op, const double *unit_q, const double *jxw_q)
 {
   MGX_REQUIRE(op && unit_q && jxw_q, "mgx_operator_enable_coefficient_update_q_2d: null argument");
-  if (op->d.dim != 2)
-    return fail(MGX_ERR_UNSUPPORTED, "mgx_operator_enable_coefficient_update_q_2d: not on a three-dimensional operator (call "
-                                     "mgx_operator_enable_coefficient_update_q)");
-  MGX_TRY(require_coef_q(op, "mgx_operator_enable_coefficient_update_q_2d"));
+  MGX_TRY(refuse_3d(op, "mgx_operator_enable_coefficient_update_q_2d", "mgx_operator_enable_coefficient_update_q"));
   return set_point_geometry(op, unit_q, jxw_q, "mgx_operator_enable_coefficient_update_q_2d");
 }
 
@@ -2127,17 +2141,7 @@ int mgx_operator_enable_coefficient_update(mgx_operator_t op, const double metri
   MGX_REQUIRE(op && metric, "mgx_operator_enable_coefficient_update: null argument");
   MGX_TRY(refuse_2d(op->d, "mgx_operator_enable_coefficient_update",
                     "the arrays of this call are three-dimensional: call mgx_operator_enable_coefficient_update_2d"));
-  MGX_TRY(require_coef_q(op, "mgx_operator_enable_coefficient_update"));
-  // M = J^-1 J^-T is symmetric positive definite (leading minors), det J > 0
-  const double m0 = metric[0], m1 = metric[1], m2 = metric[2], m3 = metric[3], m4 = metric[4], m5 = metric[5];
-  const double det_m = m0 * (m1 * m2 - m5 * m5) - m3 * (m3 * m2 - m5 * m4) + m4 * (m3 * m5 - m1 * m4);
-  MGX_REQUIRE(det_jacobian > 0. && m0 > 0. && m0 * m1 - m3 * m3 > 0. && det_m > 0.,
-              "mgx_operator_enable_coefficient_update: the metric must be positive definite and det J > 0");
-  MGX_TRY(release_point_geometry(op));
-  std::copy(metric, metric + 6, op->metric);
-  op->det_jacobian = det_jacobian;
-  op->coef_update  = true;
-  return MGX_OK;
+  return set_affine_geometry(op, metric, det_jacobian, "mgx_operator_enable_coefficient_update");
 }
 
 int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *unit_q, const double *jxw_q)
@@ -2145,7 +2149,6 @@ int mgx_operator_enable_coefficient_update_q(mgx_operator_t op, const double *un
   MGX_REQUIRE(op && unit_q && jxw_q, "mgx_operator_enable_coefficient_update_q: null argument");
   MGX_TRY(refuse_2d(op->d, "mgx_operator_enable_coefficient_update_q",
                     "the arrays of this call are three-dimensional: call mgx_operator_enable_coefficient_update_q_2d"));
-  MGX_TRY(require_coef_q(op, "mgx_operator_enable_coefficient_update_q"));
   return set_point_geometry(op, unit_q, jxw_q, "mgx_operator_enable_coefficient_update_q");
 }
 

@@ -3,6 +3,8 @@
 // MultigridSolver for poisson_cube.  Pure host code (C++17 + OpenMP); the device work is behind
 // mgx.h.
 #include "../../include/mgx_cube.h"
+#include "mgx_element.hpp"
+#include "mgx_hierarchy.hpp"
 
 #include <omp.h>
 #include <sched.h>
@@ -20,19 +22,12 @@
 
 namespace
 {
-  constexpr int    kMaxN = 10;
-  constexpr double kPi   = 3.14159265358979323846264338327950288;
+  constexpr double kPi = 3.14159265358979323846264338327950288;
+}
 
-  // ---- 1D element data: FE_Q(p) on Gauss-Lobatto nodes, QGauss(p+1) ----
-  struct Basis
-  {
-    int    p = 0, n = 0;
-    double gll[kMaxN], gq[kMaxN], gw[kMaxN];
-    double S[kMaxN * kMaxN], D[kMaxN * kMaxN], P1[2 * kMaxN * kMaxN];
-  };
-
-  using ld = long double;
-
+// ---- 1D element data (mgx_element.hpp): the one definition, for both providers ----
+namespace mgx
+{
   void legendre(int n, ld x, ld &P, ld &dP)
   {
     if (n == 0)
@@ -140,6 +135,12 @@ namespace
           }
       }
   }
+} // namespace mgx
+
+namespace
+{
+  using mgx::Basis;
+  using mgx::make_basis;
 
   struct Neighbor
   {
@@ -906,11 +907,6 @@ namespace
   }
 } // namespace
 
-namespace mgx
-{
-  int report_error(int code, const char *message); // mgx_api.cpp: message for mgx_last_error()
-}
-
 extern "C" {
 
 static int create_impl(const mgx_cube_box_desc &bd, mgx_cube_t *out)
@@ -1284,45 +1280,7 @@ int mgx_cube_seeded_vector(mgx_cube_t c, int l, uint64_t seed, double *out)
 {
   if (!c || !out || l < 0 || l >= (int)c->levels.size())
     return MGX_ERR_INVALID_ARGUMENT;
-  const uint32_t *g = mgx_cube_dof_grid(c, l);
-  const uint32_t  n = c->levels[l].n_dofs;
-#pragma omp parallel for schedule(static)
-  for (uint32_t i = 0; i < n; ++i)
-    {
-      uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)g[i] + 1);
-      z          = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-      z          = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-      z ^= z >> 31;
-      out[i] = (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-    }
-  return MGX_OK;
-}
-
-int mgx_cube_solver_destroy(mgx_cube_solver *s)
-{
-  if (!s)
-    return MGX_OK;
-  mgx_solver_destroy(s->solver);
-  // transfers reference their level operators: release them first
-  for (int l = 0; l < s->n_levels; ++l)
-    {
-      if (s->transfer && s->transfer_dp && s->transfer_dp[l] != s->transfer[l])
-        mgx_transfer_destroy(s->transfer_dp[l]);
-      if (s->transfer)
-        mgx_transfer_destroy(s->transfer[l]);
-    }
-  for (int l = 0; l < s->n_levels; ++l)
-    {
-      if (s->matrix && s->matrix_dp && s->matrix_dp[l] != s->matrix[l])
-        mgx_operator_destroy(s->matrix_dp[l]);
-      if (s->matrix)
-        mgx_operator_destroy(s->matrix[l]);
-    }
-  delete[] s->matrix;
-  delete[] s->matrix_dp;
-  delete[] s->transfer;
-  delete[] s->transfer_dp;
-  std::memset(s, 0, sizeof(*s));
+  mgx::seeded_fill(seed, c->levels[l].dof_grid.data(), c->levels[l].n_dofs, out);
   return MGX_OK;
 }
 
@@ -1395,147 +1353,78 @@ static int cube_solver_create(mgx_context_t ctx, mgx_cube_t cube, int vnumber, i
   if (per_point && general->jacobian)
     return mgx::report_error(MGX_ERR_UNSUPPORTED, "mgx_cube_solver_create_general: a jacobian on a mapped cube (the geometry of a "
                                                   "mapped cube is the per-point one of its own map; jacobian must be NULL)");
-  std::memset(out, 0, sizeof(*out));
-  out->n_levels    = nl;
-  out->matrix      = new mgx_operator_t[nl]();
-  out->matrix_dp   = new mgx_operator_t[nl]();
-  out->transfer    = new mgx_transfer_t[nl]();
-  out->transfer_dp = new mgx_transfer_t[nl]();
-  int status       = MGX_OK;
-  for (int l = 0; l < nl && status == MGX_OK; ++l)
-    {
-      mgx_operator_desc d;
-      mgx_cube_operator_desc(cube, l, MGX_F64, &d);
-      // general branch on the Cartesian mesh: the unit-law tensor JxW_q M (or the caller's) as merged coefficient
-      std::vector<double> unit;
-      double              metric[6] = {0, 0, 0, 0, 0, 0}, det = 0;
-      if (per_point) // the provider's JxW_q J^-1 J^-T (mgx_cube_operator_desc set it), or the caller's tensor
-        {
-          if (general->coef_q && general->coef_q[l])
-            d.coef_q = general->coef_q[l];
-        }
-      else if (general)
-        {
-          status = mgx_cube_affine_metric(cube, l, general->jacobian, metric, &det);
-          if (status != MGX_OK)
-            break;
-          if (general->coef_q && general->coef_q[l])
-            d.coef_q = general->coef_q[l];
-          else
-            {
-              const int    n  = cube->p + 1;
-              const size_t n3 = (size_t)n * n * n;
-              unit.resize((size_t)d.n_cells * 6 * n3);
-              for (size_t q = 0; q < n3; ++q)
-                {
-                  const double jxw = cube->basis.gw[q % n] * cube->basis.gw[(q / n) % n] * cube->basis.gw[q / (n * n)] * det;
-                  for (int c = 0; c < 6; ++c)
-                    unit[c * n3 + q] = jxw * metric[c];
-                }
-              for (size_t cell = 1; cell < d.n_cells; ++cell)
-                std::copy(unit.begin(), unit.begin() + 6 * n3, unit.begin() + cell * 6 * n3);
-              d.coef_q = unit.data();
-            }
-        }
-      // decomposed mesh: plan ids 2*level (fp64 operator) and 2*level+1 (V-cycle operator)
-      mgx_exchange_desc ex;
-      const uint32_t   *idx[27];
-      int               ranks[27];
-      uint32_t          counts[27];
-      if (cube->size > 1)
-        {
-          mgx_cube_exchange_desc(cube, l, 2 * l, &ex, idx, ranks, counts);
-          d.exchange = &ex;
-        }
-      status = mgx_operator_create(ctx, &d, &out->matrix_dp[l]);
-      if (status != MGX_OK)
-        break;
-      if (vnumber == MGX_F64)
-        out->matrix[l] = out->matrix_dp[l];
-      else
-        {
-          d.number   = MGX_F32;
-          ex.plan_id = 2 * l + 1;
-          status     = mgx_operator_create(ctx, &d, &out->matrix[l]);
-        }
-      // per_point cells: the geometry is kept once, in fp64 with matrix_dp[l]; mgx_solver_update_coefficient writes the
-      // tensor of an fp32 V-cycle operator from it
-      if (per_point && status == MGX_OK)
-        status = mgx_operator_enable_coefficient_update_q(out->matrix_dp[l], cube->levels[l].coef_q.data(), cube->levels[l].jxw.data());
-      if (general && !per_point && status == MGX_OK)
-        status = mgx_operator_enable_coefficient_update(out->matrix_dp[l], metric, det);
-      if (general && !per_point && status == MGX_OK && out->matrix[l] != out->matrix_dp[l])
-        status = mgx_operator_enable_coefficient_update(out->matrix[l], metric, det);
-    }
-  for (int l = 1; l < nl && status == MGX_OK; ++l)
-    {
-      mgx_transfer_desc t;
-      t.children     = cube->levels[l].children.data();
-      t.prolong_1d   = cube->basis.P1;
-      t.weight_shift = cube->levels[l].weight_shift.empty() ? nullptr : cube->levels[l].weight_shift.data();
-      status       = mgx_transfer_create(out->matrix_dp[l - 1], out->matrix_dp[l], &t, &out->transfer_dp[l]);
-      if (status != MGX_OK)
-        break;
-      if (vnumber == MGX_F64)
-        out->transfer[l] = out->transfer_dp[l];
-      else
-        status = mgx_transfer_create(out->matrix[l - 1], out->matrix[l], &t, &out->transfer[l]);
-    }
-  if (status == MGX_OK)
-    {
-      std::vector<const double *>   rhs(nl), bcv(nl);
-      std::vector<const uint32_t *> bci(nl);
-      std::vector<uint32_t>         bcn(nl);
-      for (int l = 0; l < nl; ++l)
-        {
-          rhs[l] = device_rhs ? nullptr : mgx_cube_rhs(cube, l);
-          bci[l] = cube->levels[l].bc_index.data();
-          bcv[l] = cube->levels[l].bc_value.data();
-          // (general hierarchy: the Newton update has homogeneous boundary values, the right-hand side is the caller's)
-          bcn[l] = general ? 0u : (uint32_t)cube->levels[l].bc_index.size();
-        }
-      mgx_solver_desc sd;
-      sd.n_levels    = nl;
-      sd.degree_pre  = degree_pre;
-      sd.n_cycles    = n_cycles;
-      sd.matrix      = out->matrix;
-      sd.matrix_dp   = out->matrix_dp;
-      sd.transfer    = out->transfer;
-      sd.transfer_dp = out->transfer_dp;
-      sd.rhs         = rhs.data();
-      sd.bc_index    = bci.data();
-      sd.bc_value    = bcv.data();
-      sd.bc_count    = bcn.data();
-      status         = mgx_solver_create(ctx, &sd, &out->solver);
-      // the right-hand sides on the device (laplace_operator.h:804-845): the host only evaluates f JxW at the
-      // quadrature points
-      for (int l = 0; l < nl && status == MGX_OK && device_rhs && !general; ++l)
-        {
-          const size_t        n3 = (size_t)(cube->p + 1) * (cube->p + 1) * (cube->p + 1), count = n3 * cube->levels[l].n_cells;
-          std::vector<double> fq(count);
-          void               *fq_dev = nullptr;
-          status                     = mgx_cube_rhs_quadrature(cube, l, fq.data());
-          if (status == MGX_OK)
-            status = mgx_malloc(ctx, &fq_dev, sizeof(double) * count);
-          if (status == MGX_OK)
-            status = mgx_upload(ctx, fq_dev, fq.data(), sizeof(double) * count);
-          if (status == MGX_OK)
-            status = mgx_solver_compute_rhs(out->solver, l, (const double *)fq_dev);
-          if (fq_dev)
-            {
-              const std::string keep = status != MGX_OK ? mgx_last_error() : "";
-              (void)mgx_sync(ctx);
-              (void)mgx_free(ctx, fq_dev);
-              if (status != MGX_OK)
-                mgx::report_error(status, keep.c_str());
-            }
-        }
-    }
+  // what level l looks like: the unit-law tensor JxW_q M of the Cartesian mesh is built on the spot and lives until the
+  // operators of its level exist
+  const auto describe = [&](int l, mgx::LevelDesc &d) {
+    const Level &L = cube->levels[l];
+    mgx_cube_operator_desc(cube, l, MGX_F64, &d.op);
+    if (general && general->coef_q && general->coef_q[l])
+      d.op.coef_q = general->coef_q[l]; // the caller's tensor
+    if (per_point) // the provider's JxW_q J^-1 J^-T is the geometry (and, unless the caller gave one, the tensor)
+      {
+        d.geometry = mgx::LevelDesc::per_point;
+        d.unit_q   = L.coef_q.data();
+        d.jxw_q    = L.jxw.data();
+      }
+    else if (general)
+      {
+        d.geometry = mgx::LevelDesc::affine;
+        if (const int status = mgx_cube_affine_metric(cube, l, general->jacobian, d.metric, &d.det))
+          return status;
+        if (!(general->coef_q && general->coef_q[l]))
+          {
+            const int    n  = cube->p + 1;
+            const size_t n3 = (size_t)n * n * n;
+            d.scratch.resize((size_t)d.op.n_cells * 6 * n3);
+            for (size_t q = 0; q < n3; ++q)
+              {
+                const double jxw = cube->basis.gw[q % n] * cube->basis.gw[(q / n) % n] * cube->basis.gw[q / (n * n)] * d.det;
+                for (int c = 0; c < 6; ++c)
+                  d.scratch[c * n3 + q] = jxw * d.metric[c];
+              }
+            for (size_t cell = 1; cell < d.op.n_cells; ++cell)
+              std::copy(d.scratch.begin(), d.scratch.begin() + 6 * n3, d.scratch.begin() + cell * 6 * n3);
+            d.op.coef_q = d.scratch.data();
+          }
+      }
+    d.decomposed = cube->size > 1;
+    if (d.decomposed)
+      mgx_cube_exchange_desc(cube, l, 0, &d.exchange, d.neighbor_index, d.neighbor_rank, d.neighbor_count);
+    d.transfer.children     = L.children.data();
+    d.transfer.prolong_1d   = cube->basis.P1;
+    d.transfer.weight_shift = L.weight_shift.empty() ? nullptr : L.weight_shift.data();
+    d.rhs                   = device_rhs ? nullptr : mgx_cube_rhs(cube, l);
+    d.bc_index              = L.bc_index.data();
+    d.bc_value              = L.bc_value.data();
+    // (general hierarchy: the Newton update has homogeneous boundary values, the right-hand side is the caller's)
+    d.bc_count = general ? 0u : (uint32_t)L.bc_index.size();
+    return (int)MGX_OK;
+  };
+  int status = mgx::build_hierarchy(ctx, nl, vnumber, degree_pre, n_cycles, describe, out);
   if (status != MGX_OK)
+    return status;
+  // the right-hand sides on the device (laplace_operator.h:804-845): the host only evaluates f JxW at the
+  // quadrature points
+  for (int l = 0; l < nl && status == MGX_OK && device_rhs && !general; ++l)
     {
-      const std::string keep = mgx_last_error(); // the destroy calls below must not hide the cause
-      mgx_cube_solver_destroy(out);
-      mgx::report_error(status, keep.c_str());
+      const size_t        n3 = (size_t)(cube->p + 1) * (cube->p + 1) * (cube->p + 1), count = n3 * cube->levels[l].n_cells;
+      std::vector<double> fq(count);
+      void               *fq_dev = nullptr;
+      status                     = mgx_cube_rhs_quadrature(cube, l, fq.data());
+      if (status == MGX_OK)
+        status = mgx_malloc(ctx, &fq_dev, sizeof(double) * count);
+      if (status == MGX_OK)
+        status = mgx_upload(ctx, fq_dev, fq.data(), sizeof(double) * count);
+      if (status == MGX_OK)
+        status = mgx_solver_compute_rhs(out->solver, l, (const double *)fq_dev);
+      if (fq_dev)
+        {
+          const std::string keep = status != MGX_OK ? mgx_last_error() : "";
+          (void)mgx_sync(ctx);
+          (void)mgx_free(ctx, fq_dev);
+          if (status != MGX_OK)
+            mgx::report_error(status, keep.c_str());
+        }
     }
-  return status;
+  return status == MGX_OK ? MGX_OK : mgx::abandon_hierarchy(status, out);
 }

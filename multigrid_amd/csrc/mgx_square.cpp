@@ -1,8 +1,10 @@
 // mgx_square.cpp -- host-side structured discretisation on quadrilaterals (see include/mgx_square.h): the
 // two-dimensional counterpart of mgx_cube.cpp, one rank.  Pure host code; the device work is behind mgx.h.  The 1D
 // element data (Gauss-Lobatto nodes, Gauss rule, shape values, collocation derivative, embedding) are those of
-// mgx_cube.cpp, taken from a one-cell cube of the same degree.
+// mgx_cube.cpp (mgx_element.hpp).
 #include "../../include/mgx_square.h"
+#include "mgx_element.hpp"
+#include "mgx_hierarchy.hpp"
 #include "mgx_index_tables.hpp"
 
 #include <algorithm>
@@ -10,11 +12,6 @@
 #include <cstring>
 #include <string>
 #include <vector>
-
-namespace mgx
-{
-  int report_error(int code, const char *message); // mgx_api.cpp
-}
 
 namespace
 {
@@ -38,8 +35,7 @@ struct mgx_square_s
   double             origin = -0.9, h0 = 1.9;
   double             A[4] = {1, 0, 0, 1}, detA = 1, coef[3] = {1, 1, 0};
   int                geometry = 0; // 0: the box; MGX_SQUARE_GEOMETRY_ANNULUS_SECTOR
-  mgx_cube_t         element = nullptr; // a one-cell cube: the owner of the 1D arrays
-  const double      *S = nullptr, *D = nullptr, *gw = nullptr, *gq = nullptr, *gll = nullptr, *P1 = nullptr;
+  mgx::Basis         basis;
   std::vector<Level> levels;
 
   void   map(double X, double Y, double &x, double &y) const
@@ -142,7 +138,7 @@ namespace
         const uint32_t g  = L.dof_grid[L.constrained[i]], gx = g % Gx, gy = g / Gx;
         const uint32_t cx = std::min(gx / (uint32_t)p, L.N[0] - 1), cy = std::min(gy / (uint32_t)p, L.N[1] - 1);
         double         x, y;
-        Q.map(L.h * (cx + Q.gll[gx - cx * p]), L.h * (cy + Q.gll[gy - cy * p]), x, y);
+        Q.map(L.h * (cx + Q.basis.gll[gx - cx * p]), L.h * (cy + Q.basis.gll[gy - cy * p]), x, y);
         L.bc_value[i] = mgx_square_s::u(x, y);
       }
     if (level > 0)
@@ -178,7 +174,7 @@ namespace
         {
           double g = 0;
           for (int r = 0; r < n; ++r)
-            g += Q.D[q * n + r] * Q.S[r * n + i];
+            g += Q.basis.D[q * n + r] * Q.basis.S[r * n + i];
           G[q * n + i] = g;
         }
     for (int qy = 0; qy < n; ++qy)
@@ -186,12 +182,12 @@ namespace
         for (int j = 0; j < n; ++j)
           for (int i = 0; i < n; ++i)
             {
-              gx[(size_t)(qy * n + qx) * n2 + j * n + i] = G[qx * n + i] * Q.S[qy * n + j];
-              gy[(size_t)(qy * n + qx) * n2 + j * n + i] = Q.S[qx * n + i] * G[qy * n + j];
+              gx[(size_t)(qy * n + qx) * n2 + j * n + i] = G[qx * n + i] * Q.basis.S[qy * n + j];
+              gy[(size_t)(qy * n + qx) * n2 + j * n + i] = Q.basis.S[qx * n + i] * G[qy * n + j];
             }
     for (int q = 0; q < n2; ++q)
       {
-        const double w = Q.gw[q % n] * Q.gw[q / n], t0 = Q.coef[0] * w, t1 = Q.coef[1] * w, t2 = Q.coef[2] * w;
+        const double w = Q.basis.gw[q % n] * Q.basis.gw[q / n], t0 = Q.coef[0] * w, t1 = Q.coef[1] * w, t2 = Q.coef[2] * w;
         const double *dx = &gx[(size_t)q * n2], *dy = &gy[(size_t)q * n2];
         for (int a = 0; a < n2; ++a)
           {
@@ -221,11 +217,11 @@ namespace
           for (int qx = 0; qx < n; ++qx)
             {
               double x, y;
-              Q.map(L.h * (L.coords[2 * (size_t)c] + Q.gq[qx]), L.h * (L.coords[2 * (size_t)c + 1] + Q.gq[qy]), x, y);
-              const double fq = mgx_square_s::f(x, y) * Q.gw[qx] * Q.gw[qy] * jxw;
+              Q.map(L.h * (L.coords[2 * (size_t)c] + Q.basis.gq[qx]), L.h * (L.coords[2 * (size_t)c + 1] + Q.basis.gq[qy]), x, y);
+              const double fq = mgx_square_s::f(x, y) * Q.basis.gw[qx] * Q.basis.gw[qy] * jxw;
               for (int j = 0; j < n; ++j)
                 for (int i = 0; i < n; ++i)
-                  F[j * n + i] += fq * Q.S[qx * n + i] * Q.S[qy * n + j];
+                  F[j * n + i] += fq * Q.basis.S[qx * n + i] * Q.basis.S[qy * n + j];
             }
         bool any = false;
         for (int j = 0; j < n; ++j)
@@ -257,7 +253,7 @@ namespace
     const int n = Q.p + 1;
     for (int j = 0; j < n; ++j)
       for (int i = 0; i < n; ++i)
-        Q.point(L.h * (L.coords[2 * (size_t)c] + Q.gll[i]), L.h * (L.coords[2 * (size_t)c + 1] + Q.gll[j]), xy[2 * (j * n + i)],
+        Q.point(L.h * (L.coords[2 * (size_t)c] + Q.basis.gll[i]), L.h * (L.coords[2 * (size_t)c + 1] + Q.basis.gll[j]), xy[2 * (j * n + i)],
                 xy[2 * (j * n + i) + 1]);
   }
 
@@ -273,7 +269,7 @@ namespace
         {
           double g = 0;
           for (int r = 0; r < n; ++r)
-            g += Q.D[q * n + r] * Q.S[r * n + i];
+            g += Q.basis.D[q * n + r] * Q.basis.S[r * n + i];
           G[q * n + i] = g;
         }
     for (uint32_t cell = 0; cell < L.n_cells; ++cell)
@@ -286,7 +282,7 @@ namespace
               for (int j = 0; j < n; ++j)
                 for (int i = 0; i < n; ++i)
                   {
-                    const double da = G[qx * n + i] * Q.S[qy * n + j], db = Q.S[qx * n + i] * G[qy * n + j];
+                    const double da = G[qx * n + i] * Q.basis.S[qy * n + j], db = Q.basis.S[qx * n + i] * G[qy * n + j];
                     xa += da * xy[2 * (j * n + i)];
                     xb += db * xy[2 * (j * n + i)];
                     ya += da * xy[2 * (j * n + i) + 1];
@@ -295,7 +291,7 @@ namespace
               const double det = xa * yb - xb * ya;
               if (!(det > 0.))
                 return false;
-              const double w = Q.gw[qx] * Q.gw[qy], a = xa * xa + ya * ya, b = xa * xb + ya * yb, c = xb * xb + yb * yb;
+              const double w = Q.basis.gw[qx] * Q.basis.gw[qy], a = xa * xa + ya * ya, b = xa * xb + ya * yb, c = xb * xb + yb * yb;
               const size_t q = (size_t)qy * n + qx;
               if (unit)
                 {
@@ -344,7 +340,7 @@ static int square_create(const mgx_square_box_desc *bd, int geometry, mgx_square
   if (bd->jacobian)
     std::copy(bd->jacobian, bd->jacobian + 4, Q->A);
   Q->detA = Q->A[0] * Q->A[3] - Q->A[1] * Q->A[2];
-  if (!(Q->detA > 0) || mgx_cube_create_numbered(bd->degree, 1, 0, MGX_CUBE_NUMBERING_CELL, &Q->element) != MGX_OK)
+  if (!(Q->detA > 0))
     {
       delete Q;
       return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_box: the jacobian must have a positive determinant");
@@ -355,12 +351,7 @@ static int square_create(const mgx_square_box_desc *bd, int geometry, mgx_square
   Q->coef[0] = Q->detA * g11 / dg;
   Q->coef[1] = Q->detA * g00 / dg;
   Q->coef[2] = g01 == 0. ? 0. : -Q->detA * g01 / dg;
-  Q->S       = mgx_cube_shape_values(Q->element);
-  Q->D       = mgx_cube_colloc_grad(Q->element);
-  Q->gw      = mgx_cube_qweights(Q->element);
-  Q->gq      = mgx_cube_qpoints(Q->element);
-  Q->gll     = mgx_cube_gll(Q->element);
-  Q->P1      = mgx_cube_prolong_1d(Q->element);
+  mgx::make_basis(Q->basis, Q->p);
   Q->geometry = geometry;
   Q->levels.resize((size_t)bd->n_refine + 1);
   for (int l = 0; l <= bd->n_refine; ++l)
@@ -401,8 +392,6 @@ int mgx_square_create(int degree, int n_subdiv, int n_refine, mgx_square_t *out)
 
 int mgx_square_destroy(mgx_square_t q)
 {
-  if (q)
-    mgx_cube_destroy(q->element);
   delete q;
   return MGX_OK;
 }
@@ -425,12 +414,12 @@ const uint32_t *mgx_square_children(mgx_square_t q, int l) { return l > 0 ? q->l
 const uint8_t  *mgx_square_weight_shift(mgx_square_t q, int l) { return l > 0 ? q->levels[l].weight_shift.data() : nullptr; }
 const uint32_t *mgx_square_cell_coords(mgx_square_t q, int l) { return q->levels[l].coords.data(); }
 const uint32_t *mgx_square_dof_grid(mgx_square_t q, int l) { return q->levels[l].dof_grid.data(); }
-const double   *mgx_square_shape_values(mgx_square_t q) { return q->S; }
-const double   *mgx_square_colloc_grad(mgx_square_t q) { return q->D; }
-const double   *mgx_square_qweights(mgx_square_t q) { return q->gw; }
-const double   *mgx_square_qpoints(mgx_square_t q) { return q->gq; }
-const double   *mgx_square_gll(mgx_square_t q) { return q->gll; }
-const double   *mgx_square_prolong_1d(mgx_square_t q) { return q->P1; }
+const double   *mgx_square_shape_values(mgx_square_t q) { return q->basis.S; }
+const double   *mgx_square_colloc_grad(mgx_square_t q) { return q->basis.D; }
+const double   *mgx_square_qweights(mgx_square_t q) { return q->basis.gw; }
+const double   *mgx_square_qpoints(mgx_square_t q) { return q->basis.gq; }
+const double   *mgx_square_gll(mgx_square_t q) { return q->basis.gll; }
+const double   *mgx_square_prolong_1d(mgx_square_t q) { return q->basis.P1; }
 
 // the Poisson problem exists on the box only
 static bool refuse_mapped(mgx_square_t q, const char *who)
@@ -480,7 +469,7 @@ double mgx_square_l2_error(mgx_square_t q, int l, const double *sol)
           {
             double s = 0;
             for (int i = 0; i < n; ++i)
-              s += q->S[qx * n + i] * ul[j * n + i];
+              s += q->basis.S[qx * n + i] * ul[j * n + i];
             t[j * n + qx] = s;
           }
       for (int qy = 0; qy < n; ++qy)
@@ -488,9 +477,9 @@ double mgx_square_l2_error(mgx_square_t q, int l, const double *sol)
           {
             double s = 0, x, y;
             for (int j = 0; j < n; ++j)
-              s += q->S[qy * n + j] * t[j * n + qx];
-            q->map(L.h * (L.coords[2 * (size_t)c] + q->gq[qx]), L.h * (L.coords[2 * (size_t)c + 1] + q->gq[qy]), x, y);
-            const double w = q->gw[qx] * q->gw[qy] * jxw, d = s - mgx_square_s::u(x, y);
+              s += q->basis.S[qy * n + j] * t[j * n + qx];
+            q->map(L.h * (L.coords[2 * (size_t)c] + q->basis.gq[qx]), L.h * (L.coords[2 * (size_t)c + 1] + q->basis.gq[qy]), x, y);
+            const double w = q->basis.gw[qx] * q->basis.gw[qy] * jxw, d = s - mgx_square_s::u(x, y);
             err += d * d * w;
             vol += w;
           }
@@ -502,15 +491,7 @@ int mgx_square_seeded_vector(mgx_square_t q, int l, uint64_t seed, double *out)
 {
   if (!valid(q, l) || !out)
     return MGX_ERR_INVALID_ARGUMENT;
-  const Level &L = q->levels[l];
-  for (uint32_t i = 0; i < L.n_dofs; ++i)
-    {
-      uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)L.dof_grid[i] + 1);
-      z          = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-      z          = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-      z ^= z >> 31;
-      out[i] = (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-    }
+  mgx::seeded_fill(seed, q->levels[l].dof_grid.data(), q->levels[l].n_dofs, out);
   return MGX_OK;
 }
 
@@ -531,9 +512,9 @@ int mgx_square_operator_desc(mgx_square_t q, int l, int number, mgx_operator_des
   d->coef[0]       = q->coef[0];
   d->coef[1]       = q->coef[1];
   d->coef[2]       = q->coef[2];
-  d->shape_values  = q->S;
-  d->colloc_grad   = q->D;
-  d->qweights      = q->gw;
+  d->shape_values  = q->basis.S;
+  d->colloc_grad   = q->basis.D;
+  d->qweights      = q->basis.gw;
   d->global_index  = L.dof_grid.data();
   d->dim           = 2;
   if (q->geometry != 0) // curved cells: JxW_q J^-1 J^-T of every point (coef is not read then)
@@ -621,7 +602,7 @@ int mgx_square_coef_q(mgx_square_t q, int l, double *out)
   for (size_t c = 0; c < q->levels[l].n_cells; ++c)
     for (int k = 0; k < 3; ++k)
       for (size_t p = 0; p < n2; ++p)
-        out[(c * 3 + k) * n2 + p] = q->coef[k] * q->gw[p % n] * q->gw[p / n];
+        out[(c * 3 + k) * n2 + p] = q->coef[k] * q->basis.gw[p % n] * q->basis.gw[p / n];
   return MGX_OK;
 }
 
@@ -653,98 +634,39 @@ int mgx_square_solver_create_general(mgx_context_t ctx, mgx_square_t q, int vnum
 static int square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int degree_pre, int n_cycles, int per_point,
                                 bool general, const double *const *coef_q, mgx_cube_solver *out)
 {
-  const int nl = (int)q->levels.size();
-  std::memset(out, 0, sizeof(*out));
-  out->n_levels    = nl;
-  out->matrix      = new mgx_operator_t[nl]();
-  out->matrix_dp   = new mgx_operator_t[nl]();
-  out->transfer    = new mgx_transfer_t[nl]();
-  out->transfer_dp = new mgx_transfer_t[nl]();
-  int status       = MGX_OK;
-  for (int l = 0; l < nl && status == MGX_OK; ++l)
-    {
-      mgx_operator_desc   d;
-      std::vector<double> cq;
-      mgx_square_operator_desc(q, l, MGX_F64, &d);
-      if (general && coef_q && coef_q[l])
-        d.coef_q = coef_q[l];
-      else if (per_point && !d.coef_q) // (a mapped square: the descriptor carries its per-point tensor)
-        {
-          cq.resize((size_t)d.n_cells * 3 * (q->p + 1) * (q->p + 1));
-          mgx_square_coef_q(q, l, cq.data());
-          d.coef_q = cq.data();
-        }
-      status = mgx_operator_create(ctx, &d, &out->matrix_dp[l]);
-      if (status != MGX_OK)
-        break;
-      if (vnumber == MGX_F64)
-        out->matrix[l] = out->matrix_dp[l];
-      else
-        {
-          d.number = MGX_F32;
-          status   = mgx_operator_create(ctx, &d, &out->matrix[l]);
-        }
-      // the geometry of the level.  Curved cells: kept once, in fp64 with matrix_dp[l]; mgx_solver_update_coefficient
-      // writes the tensor of an fp32 V-cycle operator from it
-      if (general && status == MGX_OK && q->geometry != 0)
-        status = mgx_operator_enable_coefficient_update_q_2d(out->matrix_dp[l], q->levels[l].unit_q.data(), q->levels[l].jxw_q.data());
-      else if (general && status == MGX_OK)
-        {
-          double metric[3], det;
-          mgx_square_affine_metric(q, l, metric, &det);
-          status = mgx_operator_enable_coefficient_update_2d(out->matrix_dp[l], metric, det);
-          if (status == MGX_OK && out->matrix[l] != out->matrix_dp[l])
-            status = mgx_operator_enable_coefficient_update_2d(out->matrix[l], metric, det);
-        }
-    }
-  for (int l = 1; l < nl && status == MGX_OK; ++l)
-    {
-      mgx_transfer_desc t;
-      t.children     = q->levels[l].children.data();
-      t.prolong_1d   = q->P1;
-      t.weight_shift = q->levels[l].weight_shift.data();
-      status         = mgx_transfer_create(out->matrix_dp[l - 1], out->matrix_dp[l], &t, &out->transfer_dp[l]);
-      if (status != MGX_OK)
-        break;
-      if (vnumber == MGX_F64)
-        out->transfer[l] = out->transfer_dp[l];
-      else
-        status = mgx_transfer_create(out->matrix[l - 1], out->matrix[l], &t, &out->transfer[l]);
-    }
-  if (status == MGX_OK)
-    {
-      std::vector<const double *>   rhs(nl), bcv(nl);
-      std::vector<const uint32_t *> bci(nl);
-      std::vector<uint32_t>         bcn(nl);
-      // (general hierarchy: the Newton update has a zero right-hand side until the caller writes one, and homogeneous
-      // boundary values)
-      std::vector<double> zero(general ? q->levels[nl - 1].n_dofs : 0, 0.);
-      for (int l = 0; l < nl; ++l)
-        {
-          rhs[l] = general ? zero.data() : mgx_square_rhs(q, l);
-          bci[l] = q->levels[l].constrained.data();
-          bcv[l] = q->levels[l].bc_value.data();
-          bcn[l] = general ? 0u : (uint32_t)q->levels[l].constrained.size();
-        }
-      mgx_solver_desc sd;
-      sd.n_levels    = nl;
-      sd.degree_pre  = degree_pre;
-      sd.n_cycles    = n_cycles;
-      sd.matrix      = out->matrix;
-      sd.matrix_dp   = out->matrix_dp;
-      sd.transfer    = out->transfer;
-      sd.transfer_dp = out->transfer_dp;
-      sd.rhs         = rhs.data();
-      sd.bc_index    = bci.data();
-      sd.bc_value    = bcv.data();
-      sd.bc_count    = bcn.data();
-      status         = mgx_solver_create(ctx, &sd, &out->solver);
-    }
-  if (status != MGX_OK)
-    {
-      const std::string keep = mgx_last_error(); // the destroy calls below must not hide the cause
-      mgx_cube_solver_destroy(out);
-      mgx::report_error(status, keep.c_str());
-    }
-  return status;
+  // (general hierarchy: the Newton update has a zero right-hand side until the caller writes one, and homogeneous
+  // boundary values)
+  const std::vector<double> zero(general ? q->levels.back().n_dofs : 0, 0.);
+  const auto describe = [&](int l, mgx::LevelDesc &d) {
+    const Level &L = q->levels[l];
+    mgx_square_operator_desc(q, l, MGX_F64, &d.op);
+    if (general && coef_q && coef_q[l])
+      d.op.coef_q = coef_q[l];
+    else if (per_point && !d.op.coef_q) // (a mapped square: the descriptor carries its per-point tensor)
+      {
+        d.scratch.resize((size_t)d.op.n_cells * 3 * (q->p + 1) * (q->p + 1));
+        mgx_square_coef_q(q, l, d.scratch.data());
+        d.op.coef_q = d.scratch.data();
+      }
+    if (general && q->geometry != 0) // curved cells
+      {
+        d.geometry = mgx::LevelDesc::per_point;
+        d.unit_q   = L.unit_q.data();
+        d.jxw_q    = L.jxw_q.data();
+      }
+    else if (general)
+      {
+        d.geometry = mgx::LevelDesc::affine;
+        mgx_square_affine_metric(q, l, d.metric, &d.det);
+      }
+    d.transfer.children     = L.children.data();
+    d.transfer.prolong_1d   = q->basis.P1;
+    d.transfer.weight_shift = L.weight_shift.data();
+    d.rhs                   = general ? zero.data() : mgx_square_rhs(q, l);
+    d.bc_index              = L.constrained.data();
+    d.bc_value              = L.bc_value.data();
+    d.bc_count              = general ? 0u : (uint32_t)L.constrained.size();
+    return (int)MGX_OK;
+  };
+  return mgx::build_hierarchy(ctx, (int)q->levels.size(), vnumber, degree_pre, n_cycles, describe, out);
 }
