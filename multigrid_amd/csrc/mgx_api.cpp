@@ -8,6 +8,7 @@
 #include "mgx_index_tables.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_krylov.hpp"
+#include "mgx_transfer_tables.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types only: the library is bound at run time (dlopen), single-GPU users need no RCCL
@@ -1542,45 +1543,14 @@ namespace
   int build_ordered_assembly(mgx_operator_s &op, const mgx_operator_desc *desc)
   {
     OperatorData &d = op.d;
-    const int     p = d.p, n = p + 1;
-    const size_t  n3 = n_local_values(d.dim, p), n_local = n3 * desc->n_cells;
+    const size_t  n_local = n_local_values(d.dim, d.p) * desc->n_cells;
     if (d.bricks.available() || d.cell_colours.order || n_local > kAssemblyMaxEntries)
       return MGX_OK;
-    std::vector<uint32_t> start((size_t)desc->n_dofs + 1, 0), pos;
-    // (two dimensions: the one plane k = 0 of a table with 9 entries per cell -- code and offset of k are zero)
-    const int nk = d.dim == 2 ? 1 : n, ne = n_entities(d.dim);
-    auto for_each_local = [&](auto &&f) {
-      for (uint32_t c = 0; c < desc->n_cells; ++c)
-        {
-          const uint32_t *ix = desc->idx27 + ne * (size_t)c;
-          for (int k = 0; k < nk; ++k)
-            for (int j = 0; j < n; ++j)
-              {
-                const int       cz = (k == 0 || nk == 1) ? 0 : (k == p ? 2 : 1), oz = cz == 1 ? k - 1 : 0;
-                const int       cy = j == 0 ? 0 : (j == p ? 2 : 1), oy = cy == 1 ? j - 1 : 0;
-                const uint32_t *e  = ix + 3 * (3 * cz + cy);
-                const uint32_t  off = (uint32_t)((cy == 1 ? p - 1 : 1) * oz + oy);
-                const uint32_t  l0  = (uint32_t)(c * n3 + (size_t)(k * n + j) * n);
-                if (e[0] != MGX_INVALID_INDEX)
-                  f(e[0] + off, l0);
-                if (e[1] != MGX_INVALID_INDEX)
-                  for (int i = 1; i < p; ++i)
-                    f(e[1] + off * (uint32_t)(p - 1) + (uint32_t)(i - 1), l0 + (uint32_t)i);
-                if (e[2] != MGX_INVALID_INDEX)
-                  f(e[2] + off, l0 + (uint32_t)p);
-              }
-        }
-    };
-    for_each_local([&](uint32_t dof, uint32_t) { ++start[dof + 1]; });
-    for (size_t i = 0; i < desc->n_dofs; ++i)
-      start[i + 1] += start[i];
-    pos.resize(start.back() + 1);
-    std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-    for_each_local([&](uint32_t dof, uint32_t l) { pos[fill[dof]++] = l; });
-    MGX_TRY(op.mem.upload(&d.asm_start, start));
-    MGX_TRY(op.mem.upload(&d.asm_pos, pos));
+    const IndexRows a = ordered_assembly(desc->idx27, d.dim, desc->n_cells, desc->n_dofs, d.p);
+    MGX_TRY(op.mem.upload(&d.asm_start, a.start));
+    MGX_TRY(op.mem.upload(&d.asm_pos, a.pos));
     MGX_TRY(op.mem.alloc(&d.cell_scratch, number_size(d.number) * n_local));
-    MGX_TRACE("operator_create: ordered assembly of the per-cell kernel (%zu contributions)", pos.size() - 1);
+    MGX_TRACE("operator_create: ordered assembly of the per-cell kernel (%zu contributions)", a.pos.size() - 1);
     return MGX_OK;
   }
 
@@ -1977,25 +1947,16 @@ int mgx_vmult_with_cg_update(mgx_operator_t op, double alpha, double beta, const
   return MGX_OK;
 }
 
-// Cells of a brick level in launches whose cells share no DoF: brick colour by brick colour (bricks of one launch
-// group share no DoF), inside a brick the cells with the same position m mod 8 in Morton order -- the same child of
-// every parent -- do not touch.  64 lists; plain adds in an order that does not depend on the run.
+// Cells of a brick level in launches whose cells share no DoF (mgx::brick_cell_lists: 64 lists); plain adds in an order
+// that does not depend on the run.
 // The cells go to the device, into memory of `mem` (the caller's: it outlives the launches), the offsets to `list_start`.
-static int brick_cell_lists(mgx_operator_t op, DeviceArena &mem, std::vector<uint32_t> &list_start, CellLists &out)
+static int upload_brick_cell_lists(mgx_operator_t op, DeviceArena &mem, std::vector<uint32_t> &list_start, CellLists &out)
 {
-  const BrickData      &bd = op->d.bricks;
-  const uint32_t        cb = op->d.n_cells / bd.n_bricks; // cells per brick: 64 or 8
-  std::vector<uint32_t> lists;
-  list_start.assign(1, 0);
-  lists.reserve(op->d.n_cells);
-  for (int g = 0; g < bd.n_colours; ++g)
-    for (uint32_t q = 0; q < 8; ++q)
-      {
-        for (uint32_t pos = bd.colour_start[g]; pos < bd.colour_start[g + 1]; ++pos)
-          for (uint32_t m = q; m < cb; m += 8)
-            lists.push_back(bd.order[pos] * cb + m);
-        list_start.push_back((uint32_t)lists.size());
-      }
+  const BrickData &bd = op->d.bricks;
+  // (cells per brick: 64 or 8)
+  IndexRows built = brick_cell_lists(bd.order.data(), bd.colour_start, bd.n_colours, op->d.n_cells / bd.n_bricks);
+  const std::vector<uint32_t> &lists = built.pos;
+  list_start.swap(built.start);
   hipStream_t s         = op->ctx->stream;
   uint32_t   *lists_dev = nullptr;
   MGX_TRY(mem.alloc(&lists_dev, lists.size() + 1));
@@ -2029,7 +1990,7 @@ int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const vo
   std::vector<uint32_t> list_start;
   CellLists             lists;
   if (op->d.bricks.available())
-    MGX_TRY(brick_cell_lists(op, tmp, list_start, lists));
+    MGX_TRY(upload_brick_cell_lists(op, tmp, list_start, lists));
   else if (op->d.cell_colours.order && !op->d.asm_start)
     lists = op->d.cell_colours.lists();
   launch_cell_residual(s, op->d, dst, src, rhs_q, lists);
@@ -2243,7 +2204,7 @@ int mgx_compute_diagonal(mgx_operator_t op)
   std::vector<uint32_t> list_start;
   CellLists             lists;
   if (op->d.bricks.available())
-    MGX_TRY(brick_cell_lists(op, lists_mem, list_start, lists));
+    MGX_TRY(upload_brick_cell_lists(op, lists_mem, list_start, lists));
   else if (op->d.cell_colours.order)
     lists = op->d.cell_colours.lists();
   launch_cell_diagonal(s, op->d, op->d.inv_diag, a1d, m1d, lists);
@@ -2587,125 +2548,33 @@ int mgx_smoother_step(mgx_smoother_t sm, void *x, const void *b)
 static int build_interface_transfer(mgx_transfer_s *tr, const mgx_transfer_desc *desc, const std::vector<uint32_t> &idxc)
 {
   mgx_operator_t      fine = tr->fine, coarse = tr->coarse;
-  const int           p = fine->d.p, n = p + 1;
-  const uint32_t      npar = coarse->d.n_cells, nsh = fine->plan->n_shared;
+  const uint32_t      nsh = fine->plan->n_shared;
   const ExchangePlan &pl = *fine->plan;
-  std::vector<uint32_t> shared(nsh), pos(fine->d.n_dofs, kInvalid);
+  std::vector<uint32_t> shared(nsh);
   if (nsh)
     MGX_HIP(hipMemcpy(shared.data(), pl.shared_dev, sizeof(uint32_t) * nsh, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < nsh; ++i)
-    pos[shared[i]] = i;
-  std::vector<uint8_t> foreign(nsh, 0), done(nsh, 0);
-  for (uint32_t d : pl.not_owned_host)
-    if (pos[d] != kInvalid)
-      foreign[pos[d]] = 1;
   std::vector<uint32_t> idxf(27 * (size_t)fine->d.n_cells);
   MGX_HIP(hipMemcpy(idxf.data(), fine->d.idx27, sizeof(uint32_t) * idxf.size(), hipMemcpyDeviceToHost));
-  auto dof_of = [p](const uint32_t *ind, int ix, int iy, int iz) {
-    const int      i[3] = {ix, iy, iz};
-    int            code[3], off[3], len[3];
-    for (int d = 0; d < 3; ++d)
-      {
-        code[d] = i[d] == 0 ? 0 : (i[d] == p ? 2 : 1);
-        off[d]  = code[d] == 1 ? i[d] - 1 : 0;
-        len[d]  = code[d] == 1 ? p - 1 : 1;
-      }
-    const uint32_t base = ind[(code[2] * 3 + code[1]) * 3 + code[0]];
-    return base == kInvalid ? kInvalid : base + (uint32_t)((off[2] * len[1] + off[1]) * len[0] + off[0]);
-  };
-  struct Entry
-  {
-    uint32_t si, cdof;
-    double   w;
-  };
-  std::vector<Entry> ent;
-  for (uint32_t pc = 0; pc < npar; ++pc)
-    for (int ch = 0; ch < 8; ++ch)
-      {
-        const uint32_t *indf = &idxf[27 * (size_t)desc->children[8 * (size_t)pc + ch]];
-        bool            any = false;
-        for (int e = 0; e < 27 && !any; ++e)
-          any = indf[e] != kInvalid && indf[e] < fine->d.n_dofs && pos[indf[e]] != kInvalid && entity_size(e, p) != 0;
-        if (!any)
-          continue;
-        for (int iz = 0; iz < n; ++iz)
-          for (int iy = 0; iy < n; ++iy)
-            for (int ix = 0; ix < n; ++ix)
-              {
-                const uint32_t d = dof_of(indf, ix, iy, iz);
-                if (d == kInvalid || pos[d] == kInvalid || done[pos[d]])
-                  continue;
-                const uint32_t si = pos[d];
-                done[si]          = 1;
-                const int F[3]    = {(ch & 1) * p + ix, ((ch >> 1) & 1) * p + iy, ((ch >> 2) & 1) * p + iz};
-                for (int az = 0; az < n; ++az)
-                  for (int ay = 0; ay < n; ++ay)
-                    for (int ax = 0; ax < n; ++ax)
-                      {
-                        const double w = desc->prolong_1d[F[0] * n + ax] * desc->prolong_1d[F[1] * n + ay] *
-                                         desc->prolong_1d[F[2] * n + az];
-                        if (std::fabs(w) < 1e-14)
-                          continue;
-                        const uint32_t c = dof_of(&idxc[27 * (size_t)pc], ax, ay, az);
-                        if (c != kInvalid)
-                          ent.push_back({si, c, w});
-                      }
-              }
-      }
-  for (uint32_t i = 0; i < nsh; ++i)
-    if (!done[i])
-      return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: a shared DoF of the fine level lies in no cell");
+  const InterfaceRows rows =
+    interface_rows(desc->children, idxf.data(), idxc.data(), coarse->d.n_cells, fine->d.n_dofs, shared.data(), nsh,
+                   pl.not_owned_host.data(), pl.not_owned_host.size(), desc->prolong_1d, fine->d.p);
+  if (rows.uncovered)
+    return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: a shared DoF of the fine level lies in no cell");
   // (an empty list still gets one entry)
   auto upload_w = [&](const std::vector<double> &w, void **dev) {
     return tr->mem.upload_as(fine->d.number, dev, w.data(), w.size(), w.empty() ? 1 : 0);
   };
   auto upload_u = [&](const std::vector<uint32_t> &v, uint32_t **dev) { return tr->mem.upload(dev, v, v.empty() ? 1 : 0); };
-  // prolongation: rows in the order of the shared list
-  {
-    std::stable_sort(ent.begin(), ent.end(), [](const Entry &a, const Entry &b) { return a.si < b.si; });
-    std::vector<uint32_t> start(nsh + 1, 0), cd(ent.size());
-    std::vector<double>   w(ent.size());
-    for (const Entry &e : ent)
-      start[e.si + 1]++;
-    for (uint32_t i = 0; i < nsh; ++i)
-      start[i + 1] += start[i];
-    for (size_t k = 0; k < ent.size(); ++k)
-      {
-        cd[k] = ent[k].cdof;
-        w[k]  = ent[k].w;
-      }
-    MGX_TRY(upload_u(start, &tr->d.ifp_start));
-    MGX_TRY(upload_u(cd, &tr->d.ifp_cdof));
-    MGX_TRY(upload_w(w, &tr->d.ifp_w));
-    tr->d.n_ifp = nsh;
-  }
-  // restriction: rows by coarse DoF, only the fine DoFs this rank owns (the coarse sums are added over the ranks)
-  {
-    std::vector<Entry> own;
-    for (const Entry &e : ent)
-      if (!foreign[e.si])
-        own.push_back(e);
-    std::stable_sort(own.begin(), own.end(), [](const Entry &a, const Entry &b) { return a.cdof < b.cdof; });
-    std::vector<uint32_t> cdof, start, fd(own.size());
-    std::vector<double>   w(own.size());
-    for (size_t k = 0; k < own.size(); ++k)
-      {
-        if (k == 0 || own[k].cdof != own[k - 1].cdof)
-          {
-            cdof.push_back(own[k].cdof);
-            start.push_back((uint32_t)k);
-          }
-        fd[k] = shared[own[k].si];
-        w[k]  = own[k].w;
-      }
-    start.push_back((uint32_t)own.size());
-    MGX_TRY(upload_u(cdof, &tr->d.ifr_cdof));
-    MGX_TRY(upload_u(start, &tr->d.ifr_start));
-    MGX_TRY(upload_u(fd, &tr->d.ifr_fdof));
-    MGX_TRY(upload_w(w, &tr->d.ifr_w));
-    tr->d.n_ifr = (uint32_t)cdof.size();
-  }
-  MGX_TRACE("transfer_create: interface rows: %u shared fine DoFs, %zu entries, %u coarse rows", nsh, ent.size(), tr->d.n_ifr);
+  MGX_TRY(upload_u(rows.p_start, &tr->d.ifp_start));
+  MGX_TRY(upload_u(rows.p_cdof, &tr->d.ifp_cdof));
+  MGX_TRY(upload_w(rows.p_w, &tr->d.ifp_w));
+  tr->d.n_ifp = nsh;
+  MGX_TRY(upload_u(rows.r_cdof, &tr->d.ifr_cdof));
+  MGX_TRY(upload_u(rows.r_start, &tr->d.ifr_start));
+  MGX_TRY(upload_u(rows.r_fdof, &tr->d.ifr_fdof));
+  MGX_TRY(upload_w(rows.r_w, &tr->d.ifr_w));
+  tr->d.n_ifr = (uint32_t)rows.r_cdof.size();
+  MGX_TRACE("transfer_create: interface rows: %u shared fine DoFs, %zu entries, %u coarse rows", nsh, rows.n_entries, tr->d.n_ifr);
   return MGX_OK;
 }
 
@@ -2866,8 +2735,6 @@ namespace
         MGX_TRACE("transfer_create: no patch table, first-version kernels (%u fine DoFs: 29-bit index)", fine->d.n_dofs);
         return MGX_OK;
       }
-    std::vector<uint32_t> patch(125 * (size_t)npar);
-    bool                  consistent = true;
     // owner weights on a decomposed mesh: a fine entity that a lower rank holds as well is restricted
     // there; here it enters with weight 0 (the coarse sums are added over the ranks afterwards)
     std::vector<uint8_t> foreign;
@@ -2877,71 +2744,22 @@ namespace
         for (uint32_t i : fine->plan->not_owned_host)
           foreign[i] = 1;
       }
-#pragma omp parallel for schedule(static)
-    for (uint32_t pc = 0; pc < npar; ++pc)
-      for (int e = 0; e < 125; ++e)
+    {
+      const PatchTable patch = patch_table(desc->children, idxf.data(), own.data(), shift.data(), npar, p, tr.d.owner_weights,
+                                           foreign.empty() ? nullptr : foreign.data());
+      if (!patch.consistent)
         {
-          const int el[3] = {e % 5, (e / 5) % 5, e / 25};
-          int       nopt[3], bit[3][2], code[3][2], cls[3], size = 1;
-          for (int d = 0; d < 3; ++d)
-            {
-              nopt[d]    = el[d] == 2 ? 2 : 1;
-              bit[d][0]  = el[d] > 2;
-              code[d][0] = el[d] - 2 * bit[d][0];
-              bit[d][1]  = 1; // layer 2 seen from child 1: its code 0
-              code[d][1] = 0;
-              cls[d]     = el[d] == 0 ? 0 : (el[d] == 4 ? 2 : 1);
-              size *= (el[d] % 2 == 1) ? p - 1 : 1;
-            }
-          uint32_t base = 0;
-          bool     owned = false, first = true;
-          for (int oz = 0; oz < nopt[2]; ++oz)
-            for (int oy = 0; oy < nopt[1]; ++oy)
-              for (int ox = 0; ox < nopt[0]; ++ox)
-                {
-                  const int      ch = bit[0][ox] | (bit[1][oy] << 1) | (bit[2][oz] << 2);
-                  const int      ce = (code[2][oz] * 3 + code[1][oy]) * 3 + code[0][ox];
-                  const uint32_t fc = desc->children[8 * (size_t)pc + ch];
-                  const uint32_t b  = idxf[27 * (size_t)fc + ce];
-                  if (first)
-                    base = b;
-                  else if (b != base)
-                    consistent = false; // children do not share the entities of the parent's mid planes
-                  first = false;
-                  owned = owned || ((own[fc] >> ce) & 1u);
-                }
-          uint32_t sh = shift[27 * (size_t)pc + (cls[2] * 3 + cls[1]) * 3 + cls[0]];
-          if (tr.d.owner_weights) // the field then says who restricts the entity: 0 = this parent, 1 = another one
-            sh = (owned && size != 0 && (foreign.empty() || !foreign[base])) ? 0u : 1u;
-          patch[125 * (size_t)pc + e] =
-            size == 0 ? 0u : (base | (sh << 29) | ((owned ? 1u : 0u) << 31));
+          MGX_TRACE("transfer_create: no patch table, first-version kernels (children patches inconsistent)");
+          return MGX_OK;
         }
-    if (!consistent)
-      {
-        MGX_TRACE("transfer_create: no patch table, first-version kernels (children patches inconsistent)");
-        return MGX_OK;
-      }
-    MGX_TRY(tr.mem.upload(&tr.d.patch, patch));
-    // colouring of the coarse cells by index mod 8 (the parity colouring of a Morton-ordered
-    // mesh): valid if no two cells of one colour share a mesh entity
+      MGX_TRY(tr.mem.upload(&tr.d.patch, patch.words));
+    }
+    // colouring of the coarse cells by index mod 8
     if (npar % 8 == 0 && !coarse->ctx->tun.restrict_atomic)
       {
         std::vector<uint32_t> idxc(27 * (size_t)npar);
         MGX_HIP(hipMemcpy(idxc.data(), coarse->d.idx27_plain, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
-        std::vector<uint8_t> mask(coarse->d.n_dofs, 0);
-        bool                 ok = true;
-        for (uint32_t c = 0; c < npar && ok; ++c)
-          for (int e = 0; e < 27; ++e)
-            {
-              if (entity_size(e, p) == 0 || e == 13)
-                continue;
-              uint8_t      &m   = mask[idxc[27 * (size_t)c + e]];
-              const uint8_t bit = (uint8_t)(1u << (c & 7u));
-              if (m & bit)
-                ok = false;
-              m |= bit;
-            }
-        tr.d.coarse_coloured = ok;
+        tr.d.coarse_coloured = coloured_by_index_mod_8(idxc.data(), npar, coarse->d.n_dofs, p);
       }
     MGX_TRACE("transfer_create: patch table built, pipelined kernels");
     if (tr.d.coarse_coloured)
@@ -3021,62 +2839,18 @@ namespace
     if (!(fine->d.bricks.available() && fine->d.separable && (!fine->plan == !coarse->plan) && fused_pays &&
           !coarse->ctx->tun.no_fused_restrict && !(fine->plan && coarse->ctx->tun.no_fused_decomposed)))
       return MGX_OK;
-    bool forest = true;
-    for (size_t i = 0; i < 8 * (size_t)npar && forest; ++i)
-      forest = desc->children[i] == (uint32_t)i;
-    const int      PB = p <= 4 ? 2 : 1, CE1 = 2 * PB + 1, CE3 = CE1 * CE1 * CE1;
+    const int      PB = p <= 4 ? 2 : 1;
     const uint32_t nb = fine->d.bricks.n_bricks, ppb = PB * PB * PB; // parents per brick
-    if (!(forest && (uint64_t)nb * ppb == npar && fine->d.bricks.order.size() == nb))
+    if (!(children_in_forest_order(desc->children, 8 * (size_t)npar) && (uint64_t)nb * ppb == npar &&
+          fine->d.bricks.order.size() == nb))
       return MGX_OK;
     std::vector<uint32_t> idxc(27 * (size_t)npar);
     MGX_HIP(hipMemcpy(idxc.data(), coarse->d.idx27, sizeof(uint32_t) * idxc.size(), hipMemcpyDeviceToHost));
     std::vector<uint32_t> idxp(27 * (size_t)npar);
     MGX_HIP(hipMemcpy(idxp.data(), coarse->d.idx27_plain, sizeof(uint32_t) * idxp.size(), hipMemcpyDeviceToHost));
-    tab.resize((size_t)nb * CE3);
-    bool consistent = true;
-    for (uint32_t sb = 0; sb < nb; ++sb)
-      {
-        const uint32_t b = fine->d.bricks.order[sb]; // brick in cell order: parents ppb*b ...
-        for (int e = 0; e < CE3; ++e)
-          {
-            const int el[3] = {e % CE1, (e / CE1) % CE1, e / (CE1 * CE1)};
-            int       nopt[3], bit[3][2], code[3][2];
-            for (int d = 0; d < 3; ++d)
-              {
-                // entity layer el of PB parents in a row: parent el/2 (last layer: the previous
-                // parent's high side); the layer between two parents is seen from both
-                nopt[d]    = (PB == 2 && el[d] == 2) ? 2 : 1;
-                bit[d][0]  = (PB == 2 && el[d] > 2) ? 1 : 0;
-                code[d][0] = el[d] - 2 * bit[d][0];
-                bit[d][1]  = 1;
-                code[d][1] = 0;
-              }
-            uint32_t word = 0, key = 0;
-            bool     first = true;
-            for (int oz = 0; oz < nopt[2]; ++oz)
-              for (int oy = 0; oy < nopt[1]; ++oy)
-                for (int ox = 0; ox < nopt[0]; ++ox)
-                  {
-                    const int      q  = bit[0][ox] | (bit[1][oy] << 1) | (bit[2][oz] << 2);
-                    const int      ce = (code[2][oz] * 3 + code[1][oy]) * 3 + code[0][ox];
-                    const uint32_t pc = ppb * b + (uint32_t)q;
-                    if (first)
-                      {
-                        word = idxc[27 * (size_t)pc + ce];
-                        key  = idxp[27 * (size_t)pc + ce];
-                      }
-                    else if (idxp[27 * (size_t)pc + ce] != key)
-                      consistent = false;
-                    first = false;
-                  }
-            tab[(size_t)sb * CE3 + e] = word;
-          }
-      }
-    if (!consistent)
-      {
-        tab.clear();
-        return MGX_OK;
-      }
+    tab = coarse_block_table(idxc.data(), idxp.data(), fine->d.bricks.order.data(), nb, PB);
+    if (tab.empty()) // two parents of a brick disagree on a shared entity
+      return MGX_OK;
     if (fine->plan)
       MGX_TRY(build_interface_transfer(&tr, desc, idxc));
     return tr.mem.upload(&tr.d.coarse_blocks, tab);
@@ -3088,7 +2862,7 @@ namespace
   {
     mgx_operator_t coarse = tr.coarse, fine = tr.fine;
     const int      p  = coarse->d.p;
-    const int      PB = p <= 4 ? 2 : 1, CE1 = 2 * PB + 1, CE3 = CE1 * CE1 * CE1;
+    const int      PB = p <= 4 ? 2 : 1;
     const uint32_t nb = fine->d.bricks.n_bricks;
     const uint64_t CN = (uint64_t)PB * p + 1, NC = CN * CN * CN;
     // (levels on the reduced-colour schedules only: there a colour launch is as long as a brick's latency chain and
@@ -3097,41 +2871,12 @@ namespace
     if (tab.empty() || !((uint64_t)nb * NC < 0xFFFFFFF0ull && !coarse->ctx->tun.no_restrict_scratch &&
                          nb <= coarse->ctx->tun.free_max_bricks))
       return MGX_OK;
-    auto layer = [p](int a, int &e, int &o, int &len) {
-      const int q = a / p, rr = a - q * p;
-      e           = 2 * q + (rr != 0);
-      o           = rr ? rr - 1 : 0;
-      len         = rr ? p - 1 : 1;
-    };
-    const uint32_t        ncd = coarse->d.n_dofs;
-    std::vector<uint32_t> start(ncd + 1, 0), dof((size_t)nb * NC, kInvalid);
-#pragma omp parallel for schedule(static)
-    for (uint32_t sb = 0; sb < nb; ++sb)
-      for (uint32_t l = 0; l < NC; ++l)
-        {
-          const int x = (int)(l % CN), y = (int)((l / CN) % CN), z = (int)(l / (CN * CN));
-          int       ex, ey, ez, ox, oy, oz, nx, ny, nz;
-          layer(x, ex, ox, nx);
-          layer(y, ey, oy, ny);
-          layer(z, ez, oz, nz);
-          const uint32_t w = tab[(size_t)sb * CE3 + (size_t)((ez * CE1 + ey) * CE1 + ex)];
-          if (w != kInvalid)
-            dof[(size_t)sb * NC + l] = w + (uint32_t)((oz * ny + oy) * nx + ox);
-        }
-    for (uint32_t d : dof)
-      if (d != kInvalid)
-        start[d + 1]++;
-    for (uint32_t d = 0; d < ncd; ++d)
-      start[d + 1] += start[d];
-    std::vector<uint32_t> pos(start[ncd]), fill(start.begin(), start.end() - 1);
-    for (size_t k = 0; k < dof.size(); ++k) // ascending position = ascending brick: the order of the sums
-      if (dof[k] != kInvalid)
-        pos[fill[dof[k]]++] = (uint32_t)k;
+    const IndexRows a = block_assembly(tab.data(), nb, PB, p, coarse->d.n_dofs);
     const size_t scratch_bytes = number_size(fine->d.number) * (size_t)nb * NC;
     MGX_TRY(tr.mem.alloc(&tr.d.coarse_scratch, scratch_bytes));
     MGX_HIP(hipMemset(tr.d.coarse_scratch, 0, scratch_bytes));
-    MGX_TRY(tr.mem.upload(&tr.d.cs_start, start));
-    return tr.mem.upload(&tr.d.cs_pos, pos, pos.empty() ? 1 : 0);
+    MGX_TRY(tr.mem.upload(&tr.d.cs_start, a.start));
+    return tr.mem.upload(&tr.d.cs_pos, a.pos, a.pos.empty() ? 1 : 0);
   }
 
   // which of the fused transfer forms the V-cycle will run on this level pair, and why not

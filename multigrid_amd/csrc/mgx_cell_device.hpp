@@ -54,7 +54,8 @@ namespace mgx
   }
 
   // entity code (0 = low vertex plane, 1 = interior, 2 = high) and offset inside the entity of
-  // the 1D node index j (vector_access_reduced.h:232-247)
+  // the 1D node index j (vector_access_reduced.h:232-247): the device copy of the host's one node rule, mgx::node_entity
+  // (mgx_index_tables.hpp), which the tables these kernels read are built with
   template <int P>
   __device__ __forceinline__ void node_code(int j, int &code, int &offs)
   {

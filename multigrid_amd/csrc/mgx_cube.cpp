@@ -5,6 +5,7 @@
 #include "../../include/mgx_cube.h"
 #include "mgx_element.hpp"
 #include "mgx_hierarchy.hpp"
+#include "mgx_index_tables.hpp"
 
 #include <omp.h>
 #include <sched.h>
@@ -548,55 +549,23 @@ namespace
   // host cell kernels (setup only): lexicographic gather through a 27-entry table
   void gather_cell(int p, const uint32_t *base, const double *src, double *v)
   {
-    const int n = p + 1;
-    for (int k = 0; k < n; ++k)
-      {
-        const int cz = k == 0 ? 0 : (k == p ? 2 : 1), oz = cz == 1 ? k - 1 : 0;
-        for (int j = 0; j < n; ++j)
-          {
-            const int       cy = j == 0 ? 0 : (j == p ? 2 : 1), oy = cy == 1 ? j - 1 : 0;
-            const uint32_t  off = (uint32_t)((cy == 1 ? p - 1 : 1) * oz + oy);
-            const uint32_t *ind = base + 3 * (3 * cz + cy);
-            double         *row = v + (k * n + j) * n;
-            row[0]              = ind[0] == MGX_INVALID_INDEX ? 0. : src[ind[0] + off];
-            for (int i = 0; i < p - 1; ++i)
-              row[1 + i] = ind[1] == MGX_INVALID_INDEX ? 0. : src[ind[1] + off * (uint32_t)(p - 1) + (uint32_t)i];
-            row[p] = ind[2] == MGX_INVALID_INDEX ? 0. : src[ind[2] + off];
-          }
-      }
+    mgx::for_each_cell_dof(base, 3, p, [&](int l, uint32_t dof) { v[l] = dof == MGX_INVALID_INDEX ? 0. : src[dof]; });
   }
 
   template <bool atomic>
   void scatter_cell(int p, const uint32_t *base, double *dst, const double *v)
   {
-    const int n   = p + 1;
-    auto      add = [&](uint32_t idx, double val) {
+    mgx::for_each_cell_dof(base, 3, p, [&](int l, uint32_t dof) {
+      if (dof == MGX_INVALID_INDEX)
+        return;
       if (atomic)
         {
 #pragma omp atomic
-          dst[idx] += val;
+          dst[dof] += v[l];
         }
       else
-        dst[idx] += val;
-    };
-    for (int k = 0; k < n; ++k)
-      {
-        const int cz = k == 0 ? 0 : (k == p ? 2 : 1), oz = cz == 1 ? k - 1 : 0;
-        for (int j = 0; j < n; ++j)
-          {
-            const int       cy = j == 0 ? 0 : (j == p ? 2 : 1), oy = cy == 1 ? j - 1 : 0;
-            const uint32_t  off = (uint32_t)((cy == 1 ? p - 1 : 1) * oz + oy);
-            const uint32_t *ind = base + 3 * (3 * cz + cy);
-            const double   *row = v + (k * n + j) * n;
-            if (ind[0] != MGX_INVALID_INDEX)
-              add(ind[0] + off, row[0]);
-            if (ind[1] != MGX_INVALID_INDEX)
-              for (int i = 0; i < p - 1; ++i)
-                add(ind[1] + off * (uint32_t)(p - 1) + (uint32_t)i, row[1 + i]);
-            if (ind[2] != MGX_INVALID_INDEX)
-              add(ind[2] + off, row[p]);
-          }
-      }
+        dst[dof] += v[l];
+    });
   }
 
   // tensor-product application of a 1D matrix (n x n, row-major, or its transpose) along dir

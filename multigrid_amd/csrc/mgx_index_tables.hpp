@@ -1,7 +1,10 @@
 // mgx_index_tables.hpp -- what the set-up code derives from the compressed index table of an FE_Q level, for hexahedra
-// and quadrilaterals alike: which cell owns an entity, colours of cells that share no DoF, multiplicities of the
-// entities of a children patch.  Host only, standard C++: no HIP, no status plumbing -- the callers (mgx_api.cpp,
-// mgx_dg_api.cpp, the mesh providers) decide what a result means; tests/index_tables_check.cpp runs these on their own.
+// and quadrilaterals alike: which DoF a node of a cell is (the node rule) and how the cells of a row share their entity
+// layers (the row rule), which cell owns an entity, colours of cells that share no DoF, multiplicities of the entities of
+// a children patch.  Host only, standard C++: no HIP, no status plumbing -- the callers (mgx_api.cpp, mgx_dg_api.cpp,
+// the mesh providers, mgx_transfer_tables.hpp) decide what a result means; tests/index_tables_check.cpp, a program of
+// its own built with AddressSanitizer and UBSan, runs all of these, and tests/test_index_tables_host.py checks what it
+// prints against a numpy restatement.
 //
 // A table holds ne = 3^dim entries per cell, the first DoF of mesh entity e = (cz 3 + cy) 3 + cx (two dimensions:
 // cy 3 + cx) with the codes 0 low side, 1 inside, 2 high side per direction.  That first DoF identifies the entity.
@@ -24,6 +27,69 @@ namespace mgx
   inline int    n_entities(int dim) { return dim == 2 ? 9 : 27; }
   inline int    interior_entity(int dim) { return dim == 2 ? 4 : 13; }
   inline size_t n_local_values(int dim, int p) { return dim == 2 ? (size_t)(p + 1) * (p + 1) : (size_t)(p + 1) * (p + 1) * (p + 1); }
+
+  constexpr uint32_t kInvalidIndex = 0xFFFFFFFFu; // entry of a constrained entity (MGX_INVALID_INDEX of mgx.h)
+
+  // THE NODE RULE (read_dof_values_compressed, vector_access_reduced.h:153-247).  Node a of 0..p on a line lies on the
+  // entity with code 0 / 1 / 2 at offset a - 1 (else 0) of its len = p - 1 (else 1) nodes; the DoF of node (i, j, k) of
+  // a cell is the first DoF of its entity + its lexicographic position in the entity.
+  struct NodeEntity
+  {
+    int code, off, len;
+  };
+  inline NodeEntity node_entity(int a, int p)
+  {
+    const int code = a == 0 ? 0 : (a == p ? 2 : 1);
+    return {code, code == 1 ? a - 1 : 0, code == 1 ? p - 1 : 1};
+  }
+  // ... through entry `base` of an entity; holds for any table of first DoFs whose entities are products of lines
+  inline uint32_t entity_dof(uint32_t base, const NodeEntity &x, const NodeEntity &y, const NodeEntity &z)
+  {
+    return base == kInvalidIndex ? base : base + (uint32_t)((z.off * y.len + y.off) * x.len + x.off);
+  }
+  // ... through the 9 or 27 entries ix of a cell; kInvalidIndex where the entity's entry is
+  inline uint32_t cell_dof(const uint32_t *ix, int dim, int p, int i, int j, int k = 0)
+  {
+    const NodeEntity x = node_entity(i, p), y = node_entity(j, p), z = dim == 2 ? NodeEntity{0, 0, 1} : node_entity(k, p);
+    return entity_dof(ix[(z.code * 3 + y.code) * 3 + x.code], x, y, z);
+  }
+  // f(local index, cell_dof) for the (p + 1)^dim nodes of a cell in lexicographic order, line by line
+  template <typename F>
+  inline void for_each_cell_dof(const uint32_t *ix, int dim, int p, F &&f)
+  {
+    const int n = p + 1;
+    for (int k = 0, l = 0; k < (dim == 2 ? 1 : n); ++k)
+      for (int j = 0; j < n; ++j)
+        {
+          const NodeEntity y = node_entity(j, p), z = dim == 2 ? NodeEntity{0, 0, 1} : node_entity(k, p);
+          const uint32_t  *e = ix + 3 * (3 * z.code + y.code);
+          for (int i = 0; i < n; ++i, ++l)
+            {
+              const NodeEntity x = node_entity(i, p);
+              f(l, entity_dof(e[x.code], x, y, z));
+            }
+        }
+  }
+
+  // THE ROW RULE: m cells in a row have 2 m + 1 entity layers and m p + 1 points.  Layer l is seen from cell
+  // (l - 1) / 2 with code l - 2 cell (layer 0: code 0 of cell 0), and an even inner layer from the next cell as well,
+  // with code 0; it carries p - 1 points if odd, else one.
+  struct RowViews
+  {
+    int n, cell[2], code[2];
+  };
+  inline RowViews row_layer_views(int l, int m)
+  {
+    const int cell = l == 0 ? 0 : (l - 1) / 2;
+    return {(l % 2 == 0 && l > 0 && l < 2 * m) ? 2 : 1, {cell, cell + 1}, {l - 2 * cell, 0}};
+  }
+  inline int row_layer_size(int l, int p) { return l % 2 == 1 ? p - 1 : 1; }
+  // point a of the m p + 1: code = its layer, offset and length as for a node
+  inline NodeEntity row_point_layer(int a, int p)
+  {
+    const NodeEntity e = node_entity(a % p, p); // (a % p is never p: codes 0 and 1)
+    return {2 * (a / p) + e.code, e.off, e.len};
+  }
 
   // Bit e of cell c is set iff c is the first cell in cell order that contains entity e, over the entities that carry
   // DoFs at degree p: the one writer of the entity's DoFs.  An entry that is not below n_dofs owns nothing and sets

@@ -58,17 +58,7 @@ struct mgx_square_s
 
 namespace
 {
-  inline int code(int a, int p) { return a == 0 ? 0 : (a == p ? 2 : 1); }
   using mgx::entity_size; // (of the 9 entities of a cell, e = cy 3 + cx)
-  // DoF of node (i, j) of a cell through its 9 entries (the addressing of read_dof_values_compressed in two dimensions)
-  inline uint32_t local_dof(const uint32_t *ix, int p, int i, int j)
-  {
-    const int      cx = code(i, p), cy = code(j, p);
-    const uint32_t b  = ix[3 * cy + cx];
-    if (b == MGX_INVALID_INDEX)
-      return b;
-    return b + (uint32_t)((cy == 1 ? j - 1 : 0) * (cx == 1 ? p - 1 : 1) + (cx == 1 ? i - 1 : 0));
-  }
   inline uint32_t compact_bits(uint32_t m) // the even bits of m
   {
     uint32_t r = 0;
@@ -129,7 +119,7 @@ namespace
     for (uint32_t c = 0; c < L.n_cells; ++c)
       for (int j = 0; j <= p; ++j)
         for (int i = 0; i <= p; ++i)
-          L.dof_grid[local_dof(&L.idx9_plain[9 * (size_t)c], p, i, j)] =
+          L.dof_grid[mgx::cell_dof(&L.idx9_plain[9 * (size_t)c], 2, p, i, j)] =
             (L.coords[2 * (size_t)c + 1] * (uint32_t)p + (uint32_t)j) * Gx + L.coords[2 * (size_t)c] * (uint32_t)p + (uint32_t)i;
     // boundary values at the nodes (the Poisson problem of the box; a mapped square has none)
     L.bc_value.resize(Q.geometry == 0 ? L.constrained.size() : 0);
@@ -227,13 +217,13 @@ namespace
         for (int j = 0; j < n; ++j)
           for (int i = 0; i < n; ++i)
             {
-              ul[j * n + i] = ubc[local_dof(ixp, p, i, j)];
+              ul[j * n + i] = ubc[mgx::cell_dof(ixp, 2, p, i, j)];
               any           = any || ul[j * n + i] != 0.;
             }
         for (int j = 0; j < n; ++j)
           for (int i = 0; i < n; ++i)
             {
-              const uint32_t d = local_dof(ix, p, i, j);
+              const uint32_t d = mgx::cell_dof(ix, 2, p, i, j);
               if (d == MGX_INVALID_INDEX)
                 continue;
               double v = F[j * n + i];
@@ -463,7 +453,7 @@ double mgx_square_l2_error(mgx_square_t q, int l, const double *sol)
       const uint32_t *ix = &L.idx9_plain[9 * (size_t)c];
       for (int j = 0; j < n; ++j)
         for (int i = 0; i < n; ++i)
-          ul[j * n + i] = sol[local_dof(ix, p, i, j)];
+          ul[j * n + i] = sol[mgx::cell_dof(ix, 2, p, i, j)];
       for (int j = 0; j < n; ++j) // along x
         for (int qx = 0; qx < n; ++qx)
           {
@@ -559,7 +549,7 @@ int mgx_square_dof_coordinates(mgx_square_t q, int l, double *out)
       for (int j = 0; j < n; ++j)
         for (int i = 0; i < n; ++i)
           {
-            const uint32_t d = local_dof(&L.idx9_plain[9 * (size_t)c], p, i, j);
+            const uint32_t d = mgx::cell_dof(&L.idx9_plain[9 * (size_t)c], 2, p, i, j);
             out[2 * (size_t)d]     = xy[2 * (j * n + i)];
             out[2 * (size_t)d + 1] = xy[2 * (j * n + i) + 1];
           }
