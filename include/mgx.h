@@ -409,7 +409,9 @@ typedef struct
    * c = x + 2y, weight_shift[9*parent + e] (NULL: from the local tables).  The embedding is applied in its dense form,
    * correct whether it is symmetric or not; prolongation: every fine entry written by one designated parent, restriction:
    * parents colour by colour with plain adds -- no atomics.  Multiplicities that are no powers of two (three or five
-   * cells around a vertex) are refused with MGX_ERR_UNSUPPORTED. */
+   * cells around a vertex): owner weights, derived from the tables -- a fine entity is restricted with weight 1 by the
+   * parent that holds its first owner in cell order, with weight 0 by the others; a weight_shift of the caller's together
+   * with such multiplicities is refused with MGX_ERR_UNSUPPORTED. */
 } mgx_transfer_desc;
 int mgx_transfer_create(mgx_operator_t coarse, mgx_operator_t fine, const mgx_transfer_desc *desc,
                         mgx_transfer_t *transfer);

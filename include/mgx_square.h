@@ -50,6 +50,19 @@ int mgx_square_create_box(const mgx_square_box_desc *desc, mgx_square_t *square)
  * NaN; the hierarchy is that of mgx_square_solver_create_general. */
 #define MGX_SQUARE_GEOMETRY_ANNULUS_SECTOR 1
 int mgx_square_create_mapped(const mgx_square_box_desc *desc, int geometry, mgx_square_t *square);
+/* The unit disc of minimal_surface/program.cc (GridGenerator::hyper_ball in two dimensions, centre 0, radius 1, a
+ * SphericalManifold on the boundary, MappingQGeneric(p)): five coarse cells -- a centre square with the corners
+ * (+-i, +-i), i = 1 - 1/sqrt 2, and four blocks between it and the circle, whose corners there are (+-o, +-o),
+ * o = 1/sqrt 2 -- refined n_refine times; level l has 5 4^l cells, block b holds the cells b 4^l ..., Morton order
+ * inside a block (children of c: 4c .. 4c+3).  Three cells meet at the four corners of the centre square on every
+ * level.  New vertices: the midpoint of an edge (on the circle: of the arc), the transfinite centre of a cell; cell nodes:
+ * linear on straight edges, by angle on the arcs of the boundary, transfinite inside.  Everything of a mapped square
+ * holds (per-point unit-law tensor as coef_q, no Poisson problem, mgx_square_solver_create_general), and further:
+ * mgx_square_weight_shift is NULL (mgx_transfer_create derives owner weights); there is no lattice of cells and no grid
+ * of DoFs -- mgx_square_cells_per_dim2 gives zeros, mgx_square_cell_coords and mgx_square_dof_grid NULL, with the reason
+ * in mgx_last_error(), mgx_square_cell_size is 0 -- and mgx_square_seeded_vector keys its generator by the DoF index. */
+#define MGX_SQUARE_GEOMETRY_BALL 2
+int mgx_square_create_ball(int degree, int n_refine, mgx_square_t *square);
 int mgx_square_destroy(mgx_square_t square);
 
 int      mgx_square_n_levels(mgx_square_t square);
@@ -65,7 +78,7 @@ const uint32_t *mgx_square_idx9(mgx_square_t square, int level);       /* [n_cel
 const uint32_t *mgx_square_idx9_plain(mgx_square_t square, int level); /* [n_cells][9] */
 const uint32_t *mgx_square_constrained(mgx_square_t square, int level);
 const uint32_t *mgx_square_children(mgx_square_t square, int level);     /* level >= 1: [n_cells(level-1)][4] */
-const uint8_t  *mgx_square_weight_shift(mgx_square_t square, int level); /* level >= 1: [n_cells(level-1)][9] */
+const uint8_t  *mgx_square_weight_shift(mgx_square_t square, int level); /* level >= 1: [n_cells(level-1)][9]; the disc: NULL */
 const uint32_t *mgx_square_cell_coords(mgx_square_t square, int level);  /* [n_cells][2] */
 /* dof -> lexicographic grid id gy Gx + gx, G_d = N_d p + 1 */
 const uint32_t *mgx_square_dof_grid(mgx_square_t square, int level);

@@ -645,14 +645,17 @@ class Square(_Mesh):
     _prefix, _dim = "mgx_square_", 2
     size, rank, shell, box_desc, level_offset = 1, 0, None, None, 0
 
-    MAPPED = {"annulus_sector": 1}  # MGX_SQUARE_GEOMETRY_*
+    MAPPED = {"annulus_sector": 1, "ball": 2}  # MGX_SQUARE_GEOMETRY_*
 
     def __init__(self, degree, n_subdiv=1, n_refine=3, box=None, origin=-0.9, h0=None, jacobian=None, mapped=None):
         """box=None: the square [-0.9,1]^2 with n_subdiv coarse cells per direction.  box=(sx,sy): a box of sx x sy
         square coarse cells of size h0 from (origin, origin).  jacobian: constant 2 x 2 matrix of an affine map of the
         whole box (a sheared or anisotropic box: the operator's one tensor [xx,yy,xy], the full-tensor form).
         mapped="annulus_sector": curved cells on every level (mgx_square_create_mapped): the box as the quarter annulus
-        0.5 <= r <= 1; the operator's coefficient is the per-point unit-law tensor, there is no Poisson problem."""
+        0.5 <= r <= 1; the operator's coefficient is the per-point unit-law tensor, there is no Poisson problem.
+        mapped="ball": the unit disc in five blocks (mgx_square_create_ball: degree and n_refine only), everything of a
+        mapped square; it has no lattice of cells and no grid of DoFs: cells_per_dim2, cell_coords, dof_grid and
+        weight_shift raise the provider's error."""
         self.lib = _lib.load()
         h = C.c_void_p()
         if box is None:
@@ -662,7 +665,11 @@ class Square(_Mesh):
                                None if self._jac is None else self._jac.ctypes.data_as(_lib.f64p))
         self.mapped = mapped
         self.origin = origin
-        if mapped is None:
+        if mapped == "ball":
+            if box != (n_subdiv, n_subdiv) or n_subdiv != 1 or jacobian is not None:
+                raise ValueError("Square(mapped=\"ball\"): degree and n_refine only (no box, n_subdiv, jacobian)")
+            check(self.lib.mgx_square_create_ball(degree, n_refine, C.byref(h)))
+        elif mapped is None:
             check(self.lib.mgx_square_create_box(C.byref(d), C.byref(h)))
         else:
             check(self.lib.mgx_square_create_mapped(C.byref(d), self.MAPPED[mapped], C.byref(h)))
@@ -671,10 +678,26 @@ class Square(_Mesh):
         self.n_levels = self.lib.mgx_square_n_levels(h)
         self.max_level = self.n_levels - 1
 
+    def _grid(self, name):
+        """the disc has no grid: the provider's refusal (the C accessor itself returns NULL or zeros)"""
+        if self.mapped == "ball":
+            a = (C.c_uint32 * 2)()
+            self.lib.mgx_square_cells_per_dim2(self.h, 0, C.byref(a))  # (leaves the reason in mgx_last_error)
+            raise _lib.MgxError(-4, "%s: %s" % (name, self.lib.mgx_last_error().decode()))
+
     def cells_per_dim2(self, l):
+        self._grid("cells_per_dim2")
         a = (C.c_uint32 * 2)()
         self.lib.mgx_square_cells_per_dim2(self.h, l, C.byref(a))
         return tuple(a)
+
+    def cell_coords(self, l):
+        self._grid("cell_coords")
+        return super().cell_coords(l)
+
+    def dof_grid(self, l):
+        self._grid("dof_grid")
+        return super().dof_grid(l)
 
     def idx9(self, l):
         return self._arr("idx9", (self.n_cells(l), 9), l)
@@ -686,6 +709,7 @@ class Square(_Mesh):
         return self._arr("children", (self.n_cells(l - 1), 4), l)
 
     def weight_shift(self, l):
+        self._grid("weight_shift")
         return self._arr("weight_shift", (self.n_cells(l - 1), 9), l)
 
     def _poisson_problem(self):

@@ -311,6 +311,7 @@ SIGNATURES = {
     "mgx_operator_enable_coefficient_update_2d": (C.c_int, [vp, f64p, C.c_double]),
     "mgx_operator_enable_coefficient_update_q_2d": (C.c_int, [vp, f64p, f64p]),
     "mgx_square_create_mapped": (C.c_int, [C.POINTER(SquareBoxDesc), C.c_int, C.POINTER(vp)]),
+    "mgx_square_create_ball": (C.c_int, [C.c_int, C.c_int, C.POINTER(vp)]),
     "mgx_square_affine_metric": (C.c_int, [vp, C.c_int, f64p, f64p]),
     "mgx_square_dof_coordinates": (C.c_int, [vp, C.c_int, f64p]),
     "mgx_square_cell_nodes": (C.c_int, [vp, C.c_int, f64p]),

@@ -2655,12 +2655,23 @@ namespace
     MGX_HIP(hipMemcpy(idxf.data(), fine->d.idx27_plain, sizeof(uint32_t) * idxf.size(), hipMemcpyDeviceToHost));
     PatchShifts counted = patch_multiplicity_shifts(dim, desc->children, idxf.data(), coarse->d.n_cells, fine->d.n_dofs);
     shift.swap(counted.shift);
-    if (dim == 2) // (one rank: the local count is the whole count; no owner weights in the dense kernels)
+    if (dim == 2) // (one rank: the local count is the whole count)
       {
+        // three or five cells around a vertex: owner weights as below, one byte per parent entity (patch_owner_weights_2d)
         if (counted.irregular)
-          return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: fine DoF multiplicities other than 1/2/4 (three or five "
-                                           "cells around a vertex) in two dimensions");
-        if (desc->weight_shift && !std::equal(shift.begin(), shift.end(), desc->weight_shift))
+          {
+            if (desc->weight_shift)
+              return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: fine DoF multiplicities other than 1/2/4 together with "
+                                               "weight_shift");
+            own = first_owner_masks(idxf.data(), ne, fine->d.n_cells, fine->d.n_dofs, coarse->d.p);
+            OwnerWeights2D w = patch_owner_weights_2d(desc->children, own.data(), coarse->d.n_cells, coarse->d.p);
+            if (!w.consistent)
+              return fail(MGX_ERR_UNSUPPORTED, "mgx_transfer_create: owner weights need the fine entities of every parent entity "
+                                               "to have their first owner in one parent (children in cell order)");
+            shift.swap(w.weight);
+            tr.d.owner_weights = true;
+          }
+        else if (desc->weight_shift && !std::equal(shift.begin(), shift.end(), desc->weight_shift))
           return fail(MGX_ERR_INVALID_ARGUMENT, "mgx_transfer_create: inconsistent weight_shift");
       }
     else

@@ -4,7 +4,8 @@
 // a children patch.  Host only, standard C++: no HIP, no status plumbing -- the callers (mgx_api.cpp, mgx_dg_api.cpp,
 // the mesh providers, mgx_transfer_tables.hpp) decide what a result means; tests/index_tables_check.cpp, a program of
 // its own built with AddressSanitizer and UBSan, runs all of these, and tests/test_index_tables_host.py checks what it
-// prints against a numpy restatement.
+// prints against a numpy restatement (the owner weights of the 2D restriction: tests/ball_owner_weights_check.cpp, on the
+// tables of the disc).
 //
 // A table holds ne = 3^dim entries per cell, the first DoF of mesh entity e = (cz 3 + cy) 3 + cx (two dimensions:
 // cy 3 + cx) with the codes 0 low side, 1 inside, 2 high side per direction.  That first DoF identifies the entity.
@@ -205,6 +206,50 @@ namespace mgx
           ++s;
         out.irregular |= (1 << s) != c;
         out.shift[i] = (uint8_t)s;
+      }
+    return out;
+  }
+
+  // Owner weights of the restriction in two dimensions, where patch_multiplicity_shifts says irregular (three or five
+  // cells around a vertex): byte[9 parent + e] = 0 (weight 1) if a child of the parent is the first owner (own:
+  // first_owner_masks of the fine level) of the fine entities that lie in entity e of the parent, else kWeightZero2D
+  // (weight 0: the parent that holds the owner restricts them).  The children patch has 5 x 5 fine entities by the row
+  // rule; those in one entity of the parent have the same parents, so one byte per parent entity does.  consistent: the
+  // fine entities (with DoFs at degree p) of every parent entity agree on whether the parent owns them -- the children
+  // of a parent are consecutive in cell order wherever children are 4c .. 4c+3.
+  constexpr uint8_t kWeightZero2D = 0xFF;
+  struct OwnerWeights2D
+  {
+    std::vector<uint8_t> weight;
+    bool                 consistent = true;
+  };
+  inline OwnerWeights2D patch_owner_weights_2d(const uint32_t *children, const uint32_t *own, uint32_t n_parents, int p)
+  {
+    OwnerWeights2D out;
+    out.weight.assign(9 * (size_t)n_parents, kWeightZero2D);
+    for (uint32_t pc = 0; pc < n_parents; ++pc)
+      {
+        int owned[9] = {0}, seen[9] = {0}; // fine entities with DoFs in a parent entity: those owned, all
+        for (int ly = 0; ly < 5; ++ly)
+          for (int lx = 0; lx < 5; ++lx)
+            {
+              if (row_layer_size(lx, p) * row_layer_size(ly, p) == 0)
+                continue;
+              const RowViews x = row_layer_views(lx, 2), y = row_layer_views(ly, 2);
+              bool           o = false;
+              for (int vy = 0; vy < y.n; ++vy)
+                for (int vx = 0; vx < x.n; ++vx)
+                  o = o || ((own[children[4 * (size_t)pc + 2 * y.cell[vy] + x.cell[vx]]] >> (3 * y.code[vy] + x.code[vx])) & 1u);
+              const int e = 3 * node_entity(ly, 4).code + node_entity(lx, 4).code;
+              owned[e] += o;
+              ++seen[e];
+            }
+        for (int e = 0; e < 9; ++e)
+          {
+            out.consistent = out.consistent && (owned[e] == 0 || owned[e] == seen[e]);
+            if (seen[e] == 0 || owned[e] == seen[e]) // (an entity without DoFs: its byte is never read)
+              out.weight[9 * (size_t)pc + e] = 0;
+          }
       }
     return out;
   }

@@ -16,6 +16,7 @@
 //
 // No kernel of this unit uses an atomic: the cells are added up by assemble_kernel / assemble_cheb_kernel in cell order
 // or by launches over cells of one colour, the restriction by launches over parents of one colour.
+#include "mgx_index_tables.hpp" // kWeightZero2D
 #include "mgx_internal.hpp"
 #include "mgx_cell_device_2d.hpp"
 
@@ -284,6 +285,15 @@ namespace mgx
     return a == 0 ? 0 : (a == 2 * P ? 2 : 1);
   }
 
+  // weight of the restriction from a byte of TransferData::weight_shift: 2^-shift for 0, 1, 2 (1 / (1 << shift), as ever),
+  // 0 for kWeightZero2D; the division is not guarded by the comparison, so the compiler selects and does not branch
+  template <typename T>
+  __device__ __forceinline__ T restrict_weight_2d(uint8_t shift)
+  {
+    const T w = T(1) / T(1 << (shift & 3));
+    return shift == kWeightZero2D ? T(0) : w;
+  }
+
   // Every fine DoF is written by exactly one fine cell, the first (in cell order) that contains its entity (own9, from
   // the fine index table), hence by one parent.  The values the parents compute for a shared DoF are bitwise the
   // same (the rows of P1 at coinciding nodes are exact unit vectors).
@@ -365,7 +375,9 @@ namespace mgx
   }
 
   // coarse += P^T (weights .* fine): the launch covers the parents parent_list[0 .. n_parents) of one colour (they share
-  // no coarse DoF), plain read-modify-writes
+  // no coarse DoF), plain read-modify-writes.  wshift [n_parents][9], one byte per entity of the parent: 0, 1, 2 = the
+  // weight 2^-shift of a regular mesh; kWeightZero2D = weight 0, the owner rule of a mesh with three or five cells around
+  // a vertex (another parent restricts the fine DoFs of that entity, with shift 0).
   template <int P, typename T>
   __global__ void __launch_bounds__(TCfg2<P>::THREADS)
     restrict_2d_kernel(T *__restrict__ coarse, const T *__restrict__ fine, const uint32_t *__restrict__ idx_c,
@@ -392,10 +404,15 @@ namespace mgx
         const int      ox = (ch & 1) * P, b = (ch >> 1) * P + j;
         T              r[N];
         gather_line<P, T>(fine, line_index_2d<P>(idx_f, fc, j), r);
+        // (the three weights of the line first, without a branch: the byte loads are in flight together)
         const uint8_t *ws = wshift + 9u * (size_t)pc + 3 * patch_code_2d<P>(b);
+        const T        w0 = restrict_weight_2d<T>(ws[0]), w1 = restrict_weight_2d<T>(ws[1]), w2 = restrict_weight_2d<T>(ws[2]);
 #pragma unroll
         for (int i = 0; i < N; ++i)
-          out[b * M + ox + i] = r[i] * (T(1) / T(1 << ws[patch_code_2d<P>(ox + i)]));
+          {
+            const int c = patch_code_2d<P>(ox + i);
+            out[b * M + ox + i] = r[i] * (c == 0 ? w0 : (c == 2 ? w2 : w1));
+          }
       }
     __syncthreads();
     for (int o = tid; o < N * M; o += nt) // y^T: [j][a]

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 namespace
@@ -26,6 +27,10 @@ namespace
     std::vector<uint8_t>  weight_shift;
     std::vector<double>   bc_value, rhs;
     std::vector<double>   unit_q, jxw_q; // mapped square: [n_cells][3][n^2], [n_cells][n^2]
+    // the disc: the vertices v00, v10, v01, v11 of every cell, the positions of the vertices, which lie on the circle
+    std::vector<uint32_t> cell_vertices;
+    std::vector<double>   vertex_xy;
+    std::vector<uint8_t>  on_circle;
   };
 } // namespace
 
@@ -34,7 +39,7 @@ struct mgx_square_s
   int                p = 0, roots[2] = {1, 1};
   double             origin = -0.9, h0 = 1.9;
   double             A[4] = {1, 0, 0, 1}, detA = 1, coef[3] = {1, 1, 0};
-  int                geometry = 0; // 0: the box; MGX_SQUARE_GEOMETRY_ANNULUS_SECTOR
+  int                geometry = 0; // 0: the box; MGX_SQUARE_GEOMETRY_ANNULUS_SECTOR, MGX_SQUARE_GEOMETRY_BALL
   mgx::Basis         basis;
   std::vector<Level> levels;
 
@@ -235,12 +240,200 @@ namespace
       }
   }
 
+  // ---- the disc (MGX_SQUARE_GEOMETRY_BALL): five blocks, no lattice ----
+  // Coarse mesh: the vertices C(s, t) = (s i, t i) and O(s, t) = (s o, t o), o = 1 / sqrt 2, i = 1 - o, numbered
+  // C(-1,-1), C(1,-1), C(-1,1), C(1,1), then O likewise; the blocks centre, right, top, left, bottom with right-handed
+  // frames in which every shared edge runs the same way in both of its cells (the index table knows no edge flip).
+  void ball_coarse_level(Level &L)
+  {
+    const double o = std::sqrt(0.5), i = 1. - o;
+    for (int k = 0; k < 8; ++k)
+      {
+        const double r = k < 4 ? i : o;
+        L.vertex_xy.push_back((k & 1) ? r : -r);
+        L.vertex_xy.push_back((k & 2) ? r : -r);
+        L.on_circle.push_back(k >= 4);
+      }
+    static const uint32_t blocks[5][4] = {{0, 1, 2, 3}, {1, 5, 3, 7}, {2, 3, 6, 7}, {0, 2, 4, 6}, {0, 4, 1, 5}};
+    L.cell_vertices.assign(&blocks[0][0], &blocks[0][0] + 20);
+  }
+
+  inline uint64_t vertex_pair(uint32_t a, uint32_t b) { return ((uint64_t)std::min(a, b) << 32) | std::max(a, b); }
+
+  // Refinement: a new vertex on an edge is the straight midpoint, projected to the circle if both ends lie on it (the
+  // midpoint of the arc); the new vertex of a cell is 1/2 (sum of its four edge midpoints) - 1/4 (sum of its four
+  // vertices), the centre of the transfinite interpolation.  The children of cell c are 4c .. 4c+3, child = x + 2y.
+  void ball_refine(const Level &C, Level &L)
+  {
+    L.vertex_xy = C.vertex_xy;
+    L.on_circle = C.on_circle;
+    std::unordered_map<uint64_t, uint32_t> mid;
+    mid.reserve(2 * C.cell_vertices.size());
+    const auto add_vertex = [&](double x, double y, bool circle) {
+      L.vertex_xy.push_back(x);
+      L.vertex_xy.push_back(y);
+      L.on_circle.push_back(circle);
+      return (uint32_t)L.on_circle.size() - 1;
+    };
+    const auto midpoint = [&](uint32_t a, uint32_t b) {
+      const auto at = mid.find(vertex_pair(a, b));
+      if (at != mid.end())
+        return at->second;
+      double     x = 0.5 * (L.vertex_xy[2 * (size_t)a] + L.vertex_xy[2 * (size_t)b]), y = 0.5 * (L.vertex_xy[2 * (size_t)a + 1] + L.vertex_xy[2 * (size_t)b + 1]);
+      const bool circle = L.on_circle[a] && L.on_circle[b];
+      if (circle)
+        {
+          const double r = std::hypot(x, y);
+          x /= r, y /= r;
+        }
+      return mid[vertex_pair(a, b)] = add_vertex(x, y, circle);
+    };
+    const size_t nc = C.cell_vertices.size() / 4;
+    L.cell_vertices.resize(16 * nc);
+    for (size_t c = 0; c < nc; ++c)
+      {
+        const uint32_t *v = &C.cell_vertices[4 * c];
+        const uint32_t  mb = midpoint(v[0], v[1]), mt = midpoint(v[2], v[3]), ml = midpoint(v[0], v[2]), mr = midpoint(v[1], v[3]);
+        double          xy[2];
+        for (int d = 0; d < 2; ++d)
+          {
+            const double *X = L.vertex_xy.data() + d;
+            xy[d] = 0.5 * (X[2 * (size_t)mb] + X[2 * (size_t)mt] + X[2 * (size_t)ml] + X[2 * (size_t)mr]) -
+                    0.25 * (X[2 * (size_t)v[0]] + X[2 * (size_t)v[1]] + X[2 * (size_t)v[2]] + X[2 * (size_t)v[3]]);
+          }
+        const uint32_t ctr         = add_vertex(xy[0], xy[1], false);
+        const uint32_t child[4][4] = {{v[0], mb, ml, ctr}, {mb, v[1], ctr, mr}, {ml, ctr, v[2], mt}, {ctr, mr, mt, v[3]}};
+        std::copy(&child[0][0], &child[0][0] + 16, &L.cell_vertices[16 * c]);
+      }
+  }
+
+  // Tables of a level of the disc from its cells' vertices: an entity is a vertex, an edge (its pair of vertices) or a
+  // cell; first touch in cell order, the entities on the circle (all Dirichlet) after all others, as in build_level.
+  // false: a shared edge runs in opposite directions in its two cells
+  bool build_ball_level(const mgx_square_s &Q, Level &L, int level)
+  {
+    const int p = Q.p;
+    L.n_cells   = (uint32_t)(L.cell_vertices.size() / 4);
+    const uint32_t nv = (uint32_t)L.on_circle.size();
+    // edges in the order of their first touch; entity e of a cell runs from vertex from[e] to vertex to[e]
+    static const int                       from[9] = {0, 0, 1, 0, 0, 1, 2, 2, 3}, to[9] = {0, 1, 1, 2, 0, 3, 2, 3, 3};
+    std::unordered_map<uint64_t, uint32_t> edge;
+    std::vector<uint32_t>                  edge_first; // the vertex an edge starts from
+    std::vector<uint8_t>                   edge_on_circle;
+    std::vector<uint32_t>                  key(9 * (size_t)L.n_cells);
+    edge.reserve(3 * (size_t)L.n_cells);
+    for (uint32_t c = 0; c < L.n_cells; ++c)
+      for (int e = 0; e < 9; ++e)
+        {
+          const uint32_t a = L.cell_vertices[4 * (size_t)c + from[e]], b = L.cell_vertices[4 * (size_t)c + to[e]];
+          if (e == 4)
+            continue;
+          if (a == b)
+            {
+              key[9 * (size_t)c + e] = a;
+              continue;
+            }
+          const auto at = edge.find(vertex_pair(a, b));
+          uint32_t   id;
+          if (at == edge.end())
+            {
+              id = edge[vertex_pair(a, b)] = (uint32_t)edge_first.size();
+              edge_first.push_back(a);
+              edge_on_circle.push_back(L.on_circle[a] && L.on_circle[b]);
+            }
+          else if (edge_first[id = at->second] != a)
+            return false;
+          key[9 * (size_t)c + e] = nv + id;
+        }
+    const uint32_t ned = (uint32_t)edge_first.size();
+    for (uint32_t c = 0; c < L.n_cells; ++c)
+      key[9 * (size_t)c + 4] = nv + ned + c;
+    auto on_boundary = [&](uint32_t k) { return k < nv ? L.on_circle[k] != 0 : (k < nv + ned && edge_on_circle[k - nv] != 0); };
+    std::vector<uint32_t> base((size_t)nv + ned + L.n_cells, MGX_INVALID_INDEX);
+    uint32_t              counter = 0;
+    for (int pass = 0; pass < 2; ++pass)
+      for (uint32_t c = 0; c < L.n_cells; ++c)
+        for (int e = 0; e < 9; ++e)
+          {
+            const uint32_t k = key[9 * (size_t)c + e];
+            if (base[k] != MGX_INVALID_INDEX || on_boundary(k) != (pass == 1))
+              continue;
+            base[k] = counter;
+            if (pass == 1)
+              for (int d = 0; d < entity_size(e, p); ++d)
+                L.constrained.push_back(counter + (uint32_t)d);
+            counter += (uint32_t)entity_size(e, p);
+          }
+    L.n_dofs = counter;
+    L.idx9.resize(9 * (size_t)L.n_cells);
+    L.idx9_plain.resize(9 * (size_t)L.n_cells);
+    for (size_t i = 0; i < key.size(); ++i)
+      {
+        L.idx9_plain[i] = base[key[i]];
+        L.idx9[i]       = on_boundary(key[i]) ? MGX_INVALID_INDEX : base[key[i]];
+      }
+    L.dof_grid.resize(L.n_dofs); // (no grid: the generators are keyed by the DoF index)
+    for (uint32_t d = 0; d < L.n_dofs; ++d)
+      L.dof_grid[d] = d;
+    if (level > 0)
+      {
+        L.children.resize(L.n_cells);
+        for (uint32_t c = 0; c < L.n_cells; ++c)
+          L.children[c] = c;
+      }
+    return true;
+  }
+
+  // Nodes of a cell of the disc (isoparametric degree p): on a straight edge the Gauss-Lobatto nodes are placed linearly,
+  // on an edge of the boundary on the arc at angles linear in the node parameter; the nodes inside by transfinite
+  // interpolation of the four edges, X(s, u) = (1-u) B(s) + u T(s) + (1-s) L(u) + s R(u) - the bilinear map of the
+  // corners -- the bilinear map itself wherever all four edges are straight.
+  void ball_cell_nodes(const mgx_square_s &Q, const Level &L, uint32_t c, double *xy)
+  {
+    const int       p = Q.p, n = p + 1;
+    const uint32_t *v = &L.cell_vertices[4 * (size_t)c];
+    const double   *g = Q.basis.gll;
+    const auto      X = [&](int k, int d) { return L.vertex_xy[2 * (size_t)v[k] + d]; };
+    const auto      edge = [&](int a, int b, int first, int stride) {
+      double      *out = xy + 2 * first;
+      const double xa = X(a, 0), ya = X(a, 1), xb = X(b, 0), yb = X(b, 1);
+      if (L.on_circle[v[a]] && L.on_circle[v[b]])
+        {
+          const double ta = std::atan2(ya, xa);
+          double       dt = std::atan2(yb, xb) - ta;
+          dt -= 2 * kPi * std::round(dt / (2 * kPi));
+          for (int i = 1; i < p; ++i)
+            out[2 * stride * i] = std::cos(ta + g[i] * dt), out[2 * stride * i + 1] = std::sin(ta + g[i] * dt);
+        }
+      else
+        for (int i = 1; i < p; ++i)
+          out[2 * stride * i] = xa + g[i] * (xb - xa), out[2 * stride * i + 1] = ya + g[i] * (yb - ya);
+      out[0] = xa, out[1] = ya;
+      out[2 * stride * p] = xb, out[2 * stride * p + 1] = yb;
+    };
+    edge(0, 1, 0, 1);     // B
+    edge(2, 3, p * n, 1); // T
+    edge(0, 2, 0, n);     // L
+    edge(1, 3, p, n);     // R
+    for (int j = 1; j < p; ++j)
+      for (int i = 1; i < p; ++i)
+        for (int d = 0; d < 2; ++d)
+          {
+            const double s = g[i], u = g[j];
+            xy[2 * (j * n + i) + d] = (1 - u) * xy[2 * i + d] + u * xy[2 * (p * n + i) + d] + (1 - s) * xy[2 * (j * n) + d] +
+                                      s * xy[2 * (j * n + p) + d] -
+                                      ((1 - s) * (1 - u) * X(0, d) + s * (1 - u) * X(1, d) + (1 - s) * u * X(2, d) + s * u * X(3, d));
+          }
+  }
+
   bool valid(mgx_square_t q, int l) { return q && l >= 0 && l < (int)q->levels.size(); }
 
   // the (p+1)^2 Gauss-Lobatto nodes of cell c, x fastest: xy[2 (j n + i)], placed by the exact map
   void cell_nodes(const mgx_square_s &Q, const Level &L, uint32_t c, double *xy)
   {
     const int n = Q.p + 1;
+    if (Q.geometry == MGX_SQUARE_GEOMETRY_BALL)
+      return ball_cell_nodes(Q, L, c, xy);
     for (int j = 0; j < n; ++j)
       for (int i = 0; i < n; ++i)
         Q.point(L.h * (L.coords[2 * (size_t)c] + Q.basis.gll[i]), L.h * (L.coords[2 * (size_t)c + 1] + Q.basis.gll[j]), xy[2 * (j * n + i)],
@@ -293,6 +486,15 @@ namespace
             }
       }
     return true;
+  }
+
+  // curved cells: the unit-law tensor is the operator's coefficient, kept with JxW on the level
+  bool store_point_geometry(const mgx_square_s &Q, Level &L)
+  {
+    const size_t n2 = (size_t)(Q.p + 1) * (Q.p + 1);
+    L.unit_q.resize((size_t)L.n_cells * 3 * n2);
+    L.jxw_q.resize((size_t)L.n_cells * n2);
+    return point_geometry(Q, L, L.unit_q.data(), L.jxw_q.data());
   }
 } // namespace
 
@@ -348,16 +550,42 @@ static int square_create(const mgx_square_box_desc *bd, int geometry, mgx_square
     {
       Level &L = Q->levels[l];
       build_level(*Q, L, l);
-      if (geometry != 0) // curved cells: the unit-law tensor is the operator's coefficient
+      if (geometry != 0 && !store_point_geometry(*Q, L))
         {
-          const size_t n2 = (size_t)(Q->p + 1) * (Q->p + 1);
-          L.unit_q.resize((size_t)L.n_cells * 3 * n2);
-          L.jxw_q.resize((size_t)L.n_cells * n2);
-          if (!point_geometry(*Q, L, L.unit_q.data(), L.jxw_q.data()))
-            {
-              mgx_square_destroy(Q);
-              return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_mapped: a cell with det J <= 0");
-            }
+          mgx_square_destroy(Q);
+          return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_mapped: a cell with det J <= 0");
+        }
+    }
+  *out = Q;
+  return MGX_OK;
+}
+
+extern "C" int mgx_square_create_ball(int degree, int n_refine, mgx_square_t *out)
+{
+  if (!out || degree < 1 || degree > MGX_MAX_DEGREE || n_refine < 0 || n_refine > 14)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_ball: bad argument");
+  if ((5ull << (2 * n_refine)) * (uint64_t)(degree * degree) >= 0xFFFFFFF0ull)
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_create_ball: the finest level does not fit 32-bit indices");
+  mgx_square_s *Q = new mgx_square_s;
+  Q->p            = degree;
+  Q->roots[0] = Q->roots[1] = 0; // (no lattice)
+  Q->geometry               = MGX_SQUARE_GEOMETRY_BALL;
+  mgx::make_basis(Q->basis, Q->p);
+  Q->levels.resize((size_t)n_refine + 1);
+  for (int l = 0; l <= n_refine; ++l)
+    {
+      Level &L = Q->levels[l];
+      if (l == 0)
+        ball_coarse_level(L);
+      else
+        ball_refine(Q->levels[l - 1], L);
+      const char *why = !build_ball_level(*Q, L, l)   ? "mgx_square_create_ball: a shared edge runs in opposite directions in its cells"
+                        : !store_point_geometry(*Q, L) ? "mgx_square_create_ball: a cell with det J <= 0"
+                                                       : nullptr;
+      if (why)
+        {
+          mgx_square_destroy(Q);
+          return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, why);
         }
     }
   *out = Q;
@@ -391,8 +619,17 @@ int      mgx_square_degree(mgx_square_t q) { return q->p; }
 uint32_t mgx_square_n_cells(mgx_square_t q, int l) { return q->levels[l].n_cells; }
 uint32_t mgx_square_n_dofs(mgx_square_t q, int l) { return q->levels[l].n_dofs; }
 uint32_t mgx_square_n_constrained(mgx_square_t q, int l) { return (uint32_t)q->levels[l].constrained.size(); }
-void     mgx_square_cells_per_dim2(mgx_square_t q, int l, uint32_t cells[2])
+// the disc has no lattice of cells and no grid of DoFs
+static bool refuse_ball(mgx_square_t q, const char *who)
 {
+  if (q->geometry != MGX_SQUARE_GEOMETRY_BALL)
+    return false;
+  mgx::report_error(MGX_ERR_UNSUPPORTED, (std::string(who) + ": not on the disc (five blocks: no lattice of cells, no grid of DoFs)").c_str());
+  return true;
+}
+void mgx_square_cells_per_dim2(mgx_square_t q, int l, uint32_t cells[2])
+{
+  (void)refuse_ball(q, "mgx_square_cells_per_dim2");
   cells[0] = q->levels[l].N[0];
   cells[1] = q->levels[l].N[1];
 }
@@ -401,9 +638,10 @@ const uint32_t *mgx_square_idx9(mgx_square_t q, int l) { return q->levels[l].idx
 const uint32_t *mgx_square_idx9_plain(mgx_square_t q, int l) { return q->levels[l].idx9_plain.data(); }
 const uint32_t *mgx_square_constrained(mgx_square_t q, int l) { return q->levels[l].constrained.data(); }
 const uint32_t *mgx_square_children(mgx_square_t q, int l) { return l > 0 ? q->levels[l].children.data() : nullptr; }
-const uint8_t  *mgx_square_weight_shift(mgx_square_t q, int l) { return l > 0 ? q->levels[l].weight_shift.data() : nullptr; }
-const uint32_t *mgx_square_cell_coords(mgx_square_t q, int l) { return q->levels[l].coords.data(); }
-const uint32_t *mgx_square_dof_grid(mgx_square_t q, int l) { return q->levels[l].dof_grid.data(); }
+// (the disc: NULL -- three cells meet at four of its vertices, the transfer derives owner weights itself)
+const uint8_t  *mgx_square_weight_shift(mgx_square_t q, int l) { return l > 0 && !q->levels[l].weight_shift.empty() ? q->levels[l].weight_shift.data() : nullptr; }
+const uint32_t *mgx_square_cell_coords(mgx_square_t q, int l) { return refuse_ball(q, "mgx_square_cell_coords") ? nullptr : q->levels[l].coords.data(); }
+const uint32_t *mgx_square_dof_grid(mgx_square_t q, int l) { return refuse_ball(q, "mgx_square_dof_grid") ? nullptr : q->levels[l].dof_grid.data(); }
 const double   *mgx_square_shape_values(mgx_square_t q) { return q->basis.S; }
 const double   *mgx_square_colloc_grad(mgx_square_t q) { return q->basis.D; }
 const double   *mgx_square_qweights(mgx_square_t q) { return q->basis.gw; }
@@ -651,7 +889,7 @@ static int square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, 
       }
     d.transfer.children     = L.children.data();
     d.transfer.prolong_1d   = q->basis.P1;
-    d.transfer.weight_shift = L.weight_shift.data();
+    d.transfer.weight_shift = L.weight_shift.empty() ? nullptr : L.weight_shift.data();
     d.rhs                   = general ? zero.data() : mgx_square_rhs(q, l);
     d.bc_index              = L.constrained.data();
     d.bc_value              = L.bc_value.data();

@@ -9,11 +9,12 @@ Prints the reference's lines: "Residual norm: ... in ... steps to ...", "Computi
 the shell (a box of one coarse cell, n_refine times refined) or the whole hyper_shell(0, 0.5, 1, 6 | 12).
 
 --dim 2: the program as shipped (dimension = 2, :73) on the square [-0.9, 1]^2, the sheared square or the quarter annulus
-with curved cells (--geometry square|sheared|annulus_sector).
+with curved cells (--geometry square|sheared|annulus_sector), or on the mesh the program itself uses, the unit disc
+(--geometry ball: hyper_ball with a SphericalManifold on the boundary, :630-634; "4 3" is its first cycle, 320 cells).
 
 Usage: python tools/minimal_surface.py [degree] [n_refine] [--amplitude A] [--vcycle f32|f64] [--tolerance T]
                                        [--geometry cube|sheared|shell_sector|shell6|shell12]
-                                       [--dim 2 [--geometry square|sheared|annulus_sector]]"""
+                                       [--dim 2 [--geometry square|sheared|annulus_sector|ball]]"""
 import argparse
 import os
 import sys
@@ -33,20 +34,20 @@ def main():
     ap.add_argument("--vcycle", choices=["f32", "f64"], default="f32", help="number type of the V-cycle (level_number)")
     ap.add_argument("--tolerance", type=float, default=1e-12, help="stop when the residual norm is below (:660)")
     ap.add_argument("--max-steps", type=int, default=100, help="n_inner_iterations (:620)")
-    ap.add_argument("--geometry", choices=["cube", "sheared", "shell_sector", "shell6", "shell12", "square", "annulus_sector"],
+    ap.add_argument("--geometry", choices=["cube", "sheared", "shell_sector", "shell6", "shell12", "square", "annulus_sector", "ball"],
                     default=None)
     ap.add_argument("--dim", type=int, choices=[2, 3], default=3, help="2: the program's own dimension (:73), on a Square")
     args = ap.parse_args()
     if args.geometry is None:
         args.geometry = "cube" if args.dim == 3 else "square"
-    allowed = ("square", "sheared", "annulus_sector") if args.dim == 2 else ("cube", "sheared", "shell_sector", "shell6", "shell12")
+    allowed = ("square", "sheared", "annulus_sector", "ball") if args.dim == 2 else ("cube", "sheared", "shell_sector", "shell6", "shell12")
     if args.geometry not in allowed:
         ap.error("--dim %d takes --geometry %s" % (args.dim, " | ".join(allowed)))
 
     ctx = mg.Context(0)
     if args.dim == 2:
-        if args.geometry == "annulus_sector":
-            cube = mg.Square(args.degree, 1, args.n_refine, mapped="annulus_sector")
+        if args.geometry in ("annulus_sector", "ball"):
+            cube = mg.Square(args.degree, 1, args.n_refine, mapped=args.geometry)
         else:
             cube = mg.Square(args.degree, 1, args.n_refine, jacobian=[[1.0, 0.35], [0.15, 0.8]] if args.geometry == "sheared" else None)
     elif args.geometry == "cube":
@@ -56,7 +57,7 @@ def main():
     else:
         cube = mg.Cube(args.degree, n_refine=args.n_refine, shell=int(args.geometry[5:]), problem="cube")
     print("Testing FE_Q<%d>(%d)" % (args.dim, args.degree))
-    if args.dim == 2:
+    if args.dim == 2 and args.geometry != "ball":
         print("Number of degrees of freedom: %d (%s, %d x %d cells, %d levels)"
               % ((cube.n_dofs(cube.max_level), args.geometry) + cube.cells_per_dim2(cube.max_level) + (cube.n_levels,)), flush=True)
     elif args.geometry == "cube":
@@ -81,6 +82,7 @@ def main():
              problem.time_coefficient, total))
     print("CG iterations per Newton step: %s" % " ".join(str(h[3]) for h in problem.history))
     first, last = problem.history[0][0], problem.history[-1][2]
+    print("%s: residual norm %.6g -> %.6g in %d Newton steps" % ("Converged" if last < 1e-10 * first else "Not converged", first, last, steps))
     problem.close()
     cube.close()
     ctx.close()
