@@ -264,8 +264,9 @@ typedef struct
    * shape_values, colloc_grad, qweights, constrained and global_index are what they are in three dimensions.  A
    * two-dimensional level adds its cells up through the ordered assembly or, beyond 2^26 local values or from
    * "cell_colour_min" cells on, colour by colour (four colours on a structured mesh): never with atomics, every result is
-   * bitwise reproducible.  Refused on such an operator with MGX_ERR_UNSUPPORTED: mgx_compute_residual,
-   * mgx_solver_compute_rhs, mgx_solver_set_agglomeration, and mgx_dg_solver_create with 3D DG operators over such a
+   * bitwise reproducible.  Refused on such an operator with MGX_ERR_UNSUPPORTED: mgx_compute_residual and
+   * mgx_solver_compute_rhs (their arrays are three-dimensional: mgx_compute_residual_2d, mgx_solver_compute_rhs_2d),
+   * mgx_solver_set_agglomeration, and mgx_dg_solver_create with 3D DG operators over such a
    * hierarchy (2D DG operators over it are MultigridSolverDG in two dimensions, include/mgx_dg.h).  The
    * solution-dependent coefficients take their geometry through mgx_operator_enable_coefficient_update[_q]_2d (the 3D
    * pair is refused); mgx_evaluate_coefficient, mgx_compute_nonlinear_residual, mgx_interpolate_to_coarse and
@@ -284,6 +285,7 @@ int mgx_operator_exchange_buffers(mgx_operator_t op, int k, void **send, void **
  * ascending rank order on every rank => bitwise identical copies): Vector::compress(add) */
 int mgx_exchange_add(mgx_operator_t op, void *vec);
 int mgx_operator_number(mgx_operator_t op);
+int mgx_operator_dim(mgx_operator_t op); /* mgx_operator_desc::dim as the operator reads it: 3 or 2 */
 /* LaplaceOperator::vmult(dst, src) laplace_operator.h:573-601 */
 int mgx_vmult(mgx_operator_t op, void *dst, const void *src);
 /* LaplaceOperator::compute_residual (laplace_operator.h:804-845) on the device:
@@ -294,6 +296,16 @@ int mgx_vmult(mgx_operator_t op, void *dst, const void *src);
  * points lexicographic with x fastest; NULL: f = 0) (:839).  Rows of constrained DoFs stay zero; the result is summed
  * over the rank interfaces (:843).  No atomics: the cells are added up in a fixed order. */
 int mgx_compute_residual(mgx_operator_t op, void *dst, const void *src, const void *rhs_q);
+/* The same on a two-dimensional operator (the 3D name is refused there, this one on a 3D operator): rhs_q is
+ * [n_cells][(p+1)^2], q = qy (p+1) + qx.  The cells are added up through the ordered assembly or the cell colours;
+ * two calls give the same bits.  One rank. */
+int mgx_compute_residual_2d(mgx_operator_t op, void *dst, const void *src, const void *rhs_q);
+/* MultigridSolver::compute_l2_error (multigrid_solver.h:298-343) on a two-dimensional operator, against a function
+ * given at the quadrature points: sums = { sum (u_h - u_q)^2 JxW_q, sum JxW_q } over all cells, the L2 error is
+ * sqrt(sums[0] / sums[1]).  vec (boundary values in place, read through idx27_plain), u_q and jxw_q ([n_cells][(p+1)^2])
+ * are device arrays of the operator's number type; differences, products and sums are fp64, one partial pair per
+ * workgroup added in a fixed order: two calls give the same bits.  Refused on a 3D operator. */
+int mgx_compute_l2_error_2d(mgx_operator_t op, const void *vec, const void *u_q, const void *jxw_q, double sums[2]);
 /* LaplaceOperator::vmult_residual(rhs, lhs, residual) laplace_operator.h:605-634 */
 int mgx_vmult_residual(mgx_operator_t op, const void *rhs, const void *lhs, void *residual);
 /* LaplaceOperator::compute_diagonal() laplace_operator.h:745-800; the inverse diagonal is kept
@@ -444,7 +456,7 @@ typedef struct
   const mgx_transfer_t *transfer;
   const mgx_transfer_t *transfer_dp;
   /* per level: rhs[level] as computed by compute_residual (:261), host fp64, n_dofs entries; rhs or rhs[level] NULL:
-   * the level's right-hand side is assembled on the device afterwards (mgx_solver_compute_rhs) */
+   * the level's right-hand side is assembled on the device afterwards (mgx_solver_compute_rhs[_2d]) */
   const double *const *rhs;
   /* per level: inhomogeneous_bc[level] (:225-253) as index/value lists (host) */
   const uint32_t *const *bc_index;
@@ -483,6 +495,8 @@ int mgx_solver_set_polynomial_type(mgx_solver_t solver, int polynomial_type);
  * mgx_compute_residual of the level's fp64 operator with the solver's boundary values and rhs_q = f(x_q) JxW_q
  * (device, [n_cells][(p+1)^3]; NULL: f = 0) -- into the level's rhs vector (mgx_solver_desc::rhs[level] == NULL) */
 int mgx_solver_compute_rhs(mgx_solver_t solver, int level, const double *rhs_q);
+/* the same for a two-dimensional hierarchy: mgx_compute_residual_2d, rhs_q [n_cells][(p+1)^2] */
+int mgx_solver_compute_rhs_2d(mgx_solver_t solver, int level, const double *rhs_q);
 /* MultigridSolver::solve(do_analyze) :387-476.  trace (may be NULL) receives for every level
  * l >= 1 the residual norms {start, end} at trace[2*l], trace[2*l+1] when do_analyze != 0
  * (the L2 errors printed next to them need the analytic solution and are computed by the

@@ -47,7 +47,8 @@ int mgx_square_create_box(const mgx_square_box_desc *desc, mgx_square_t *square)
  * not read.  mgx_square_operator_desc hands out the per-point unit-law tensor (mgx_square_unit_q) as coef_q.  The
  * Poisson problem of the box does not exist here: mgx_square_rhs, mgx_square_bc_index / _value and
  * mgx_square_solver_create are refused (NULL / MGX_ERR_UNSUPPORTED), mgx_square_bc_count is 0, mgx_square_l2_error is
- * NaN; the hierarchy is that of mgx_square_solver_create_general. */
+ * NaN; the hierarchy is that of mgx_square_solver_create_general.  A linear problem on such a square is stated through
+ * mgx_square_problem (below) and solved by mgx_square_solver_create_problem. */
 #define MGX_SQUARE_GEOMETRY_ANNULUS_SECTOR 1
 int mgx_square_create_mapped(const mgx_square_box_desc *desc, int geometry, mgx_square_t *square);
 /* The unit disc of minimal_surface/program.cc (GridGenerator::hyper_ball in two dimensions, centre 0, radius 1, a
@@ -131,6 +132,36 @@ int mgx_square_jxw_q(mgx_square_t square, int level, double *out);
  * rounded fp64 tensor).  One rank.  Released with mgx_cube_solver_destroy. */
 int mgx_square_solver_create_general(mgx_context_t ctx, mgx_square_t square, int vcycle_number, int degree_pre, int n_cycles,
                                      const double *const *coef_q_per_level, mgx_cube_solver *out);
+
+/* ---- a linear problem -div(a grad u) = f with Dirichlet values on every square: box, sheared box, annulus sector, disc ---- */
+#define MGX_SQUARE_PROBLEM_CUBE  0  /* u = sin(3 pi x) sin(3 pi y), a = 1: the box's own problem */
+#define MGX_SQUARE_PROBLEM_SHELL 1  /* u = sin(2 pi (x+y)), a = 1 + contrast prod_{e<2} cos^2(2 pi x_e + 0.1 e),
+                                       f = -(a lap u + grad a . grad u): poisson_shell/program.cc:97-225, dim = 2 */
+typedef struct
+{
+  int    kind;
+  double contrast; /* the program's 1e6; read by MGX_SQUARE_PROBLEM_SHELL only: finite, >= 0 */
+} mgx_square_problem;
+/* The geometry of a problem, on every square: a cell is the isoparametric interpolant (degree p) of its nodes
+ * (mgx_square_cell_nodes); the quadrature points x_q are that interpolant at the Gauss points, and unit_q / JxW_q
+ * (mgx_square_unit_q, mgx_square_jxw_q) come from its Jacobian.  On a box this is the affine geometry up to rounding.
+ *   coef_q          out[n_cells][3][(p+1)^2] = a(x_q) unit_q (unit_q: mgx_square_coef_q, the operator's own tensor)
+ *   rhs_quadrature  out[n_cells][(p+1)^2]    = f(x_q) JxW_q, the rhs_q of mgx_compute_residual_2d
+ *   solution_q      out[n_cells][(p+1)^2]    = u(x_q), the u_q of mgx_compute_l2_error_2d
+ *   bc_value        out[n_constrained]       = u at the node of every constrained DoF, in the order of mgx_square_constrained
+ * A NULL problem, an unknown kind or a bad contrast: MGX_ERR_INVALID_ARGUMENT. */
+int mgx_square_problem_coef_q(mgx_square_t square, int level, const mgx_square_problem *problem, double *out);
+int mgx_square_problem_rhs_quadrature(mgx_square_t square, int level, const mgx_square_problem *problem, double *out);
+int mgx_square_problem_solution_q(mgx_square_t square, int level, const mgx_square_problem *problem, double *out);
+int mgx_square_problem_bc_value(mgx_square_t square, int level, const mgx_square_problem *problem, double *out);
+/* MultigridSolver<2,p,...> for the problem: the level operators in the per-point form with mgx_square_problem_coef_q (an
+ * fp32 V-cycle operator receives it rounded), the boundary values of the problem, and every level's right-hand side
+ * assembled on the device (mgx_solver_desc::rhs NULL, then mgx_solver_compute_rhs_2d with mgx_square_problem_rhs_quadrature).
+ * One rank.  Released with mgx_cube_solver_destroy.  mgx_square_solver_create, mgx_square_rhs, mgx_square_bc_* and
+ * mgx_square_l2_error are what they were: the box's host-assembled problem, refused on a mapped square.  (deal.II's
+ * two-dimensional hyper_shell, the closed ring, is not built: the curved meshes are the annulus sector and the disc.) */
+int mgx_square_solver_create_problem(mgx_context_t ctx, mgx_square_t square, int vcycle_number, int degree_pre, int n_cycles,
+                                     const mgx_square_problem *problem, mgx_cube_solver *out);
 
 #ifdef __cplusplus
 }

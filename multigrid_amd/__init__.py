@@ -638,6 +638,22 @@ class Cube(_Mesh):
         return (-0.9 if self.box_desc is None else self.box_desc["origin"]) + X
 
 
+class SquareProblem:
+    """A linear problem -div(a grad u) = f with Dirichlet values on a Square (mgx_square_problem): kind "cube" --
+    u = sin(3 pi x) sin(3 pi y), a = 1, the box's own problem -- or "shell" -- u = sin(2 pi (x+y)), a = 1 + contrast
+    prod_e cos^2(2 pi x_e + 0.1 e) (poisson_shell/program.cc with dim = 2; its contrast is 1e6)."""
+
+    KINDS = {"cube": 0, "shell": 1}  # MGX_SQUARE_PROBLEM_*
+
+    def __init__(self, kind="shell", contrast=1e6):
+        self.kind, self.contrast = kind, float(contrast)
+        # (an unknown kind goes to the provider as it is, if it is a number: the provider refuses it)
+        self.c = _lib.SquareProblem(self.KINDS[kind] if kind in self.KINDS else int(kind), self.contrast)
+
+    def __repr__(self):
+        return "SquareProblem(%r, contrast=%g)" % (self.kind, self.contrast)
+
+
 class Square(_Mesh):
     """Host-side discretisation of poisson_cube with dimension = 2 (include/mgx_square.h): what deal.II supplies for
     LaplaceOperator<2,p,number> and MultigridSolver<2,p,...>.  One rank.  Method names are Cube's where they apply."""
@@ -763,6 +779,29 @@ class Square(_Mesh):
         """[n_cells, (p+1)^2] JxW_q of the isoparametric cells"""
         return self._filled("jxw_q", (self.n_cells(l), (self.degree + 1) ** 2), l)
 
+    # ---- a linear problem on any square, curved ones included (SquareProblem; mgx_square_problem_*) ----
+    def _problem(self, name, shape, l, problem):
+        out = np.empty(shape)
+        check(self._c("problem_" + name)(self.h, l, C.byref(problem.c) if problem is not None else None,
+                                         out.ctypes.data_as(_lib.f64p)))
+        return out
+
+    def problem_coef_q(self, l, problem):
+        """[n_cells, 3, (p+1)^2] a(x_q) JxW_q J^-1 J^-T: the operator's tensor for the problem"""
+        return self._problem("coef_q", (self.n_cells(l), 3, (self.degree + 1) ** 2), l, problem)
+
+    def problem_rhs_quadrature(self, l, problem):
+        """[n_cells, (p+1)^2] f(x_q) JxW_q (rhs_q of LaplaceOperator.compute_residual)"""
+        return self._problem("rhs_quadrature", (self.n_cells(l), (self.degree + 1) ** 2), l, problem)
+
+    def problem_solution_q(self, l, problem):
+        """[n_cells, (p+1)^2] u(x_q) (u_q of LaplaceOperator.compute_l2_error)"""
+        return self._problem("solution_q", (self.n_cells(l), (self.degree + 1) ** 2), l, problem)
+
+    def problem_bc_value(self, l, problem):
+        """[n_constrained] u at the node of every constrained DoF, in the order of constrained(l)"""
+        return self._problem("bc_value", (self.n_constrained(l),), l, problem)
+
 
 def _cell_dofs(idx27, p):
     """[n_cells, (p+1)^3] DoF of every node of every cell (x fastest) from a compressed index table without constrained
@@ -833,9 +872,19 @@ class LaplaceOperator:
 
     def compute_residual(self, dst, src=None, rhs_q=None):
         """LaplaceOperator::compute_residual (laplace_operator.h:804-845) on the device: dst = int f phi - A u_bc with the
-        boundary values in the constrained entries of src and rhs_q = f JxW at the quadrature points (device vectors)"""
-        check(self.lib.mgx_compute_residual(self.h, dst.ptr, src.ptr if src is not None else None,
-                                            rhs_q.ptr if rhs_q is not None else None))
+        boundary values in the constrained entries of src and rhs_q = f JxW at the quadrature points (device vectors);
+        on a two-dimensional operator mgx_compute_residual_2d"""
+        fn = self._by_dimension("mgx_compute_residual", self.lib.mgx_operator_dim(self.h))
+        check(fn(self.h, dst.ptr, src.ptr if src is not None else None, rhs_q.ptr if rhs_q is not None else None))
+
+    def compute_l2_error(self, vec, u_q, jxw_q, sums=False):
+        """MultigridSolver::compute_l2_error (multigrid_solver.h:298-343) on the device, two-dimensional operators only
+        (mgx_compute_l2_error_2d): vec with its boundary values in place, u_q = u(x_q) and jxw_q = JxW_q at the quadrature
+        points, device vectors of the operator's number type.  Returns sqrt(sum (u_h - u)^2 JxW / sum JxW), or with
+        sums=True the two sums"""
+        out = np.zeros(2)
+        check(self.lib.mgx_compute_l2_error_2d(self.h, vec.ptr, u_q.ptr, jxw_q.ptr, out.ctypes.data_as(_lib.f64p)))
+        return out if sums else float(np.sqrt(out[0] / out[1]))
 
     def compute_diagonal(self):
         check(self.lib.mgx_compute_diagonal(self.h))
@@ -978,8 +1027,11 @@ class MultigridSolver:
 
     def __init__(self, ctx, cube, degree_pre=3, degree_post=3, n_cycles=1, vcycle_number=F64, comm=None,
                  polynomial="first_kind", agglomerate=True, device_rhs=False, general=False, jacobian=None, coef_q=None,
-                 per_point=False):
-        """device_rhs: the right-hand sides are assembled on the GPU (mgx_solver_compute_rhs) instead of on the host.
+                 per_point=False, problem=None):
+        """problem: a SquareProblem on a Square, curved ones included (mgx_square_solver_create_problem): per-point
+        operators with the problem's tensor, its boundary values, right-hand sides assembled on the device
+        (mgx_solver_compute_rhs_2d); compute_l2_error then runs on the device as well.  Not with general.
+        device_rhs: the right-hand sides are assembled on the GPU (mgx_solver_compute_rhs) instead of on the host.
         general: the hierarchy in the general branch of the operator for solution-dependent coefficients
         (mgx_cube_solver_create_general: one rank; zero right-hand sides, homogeneous boundary values), on a Cartesian
         cube / box with the constant matrix `jacobian` of an affine map of the box (None: identity), or on a mapped cube
@@ -1004,6 +1056,10 @@ class MultigridSolver:
                        (coef_q is not None and not general)):
             raise ValueError("MultigridSolver on a Square: one rank, host right-hand sides "
                              "(comm, agglomerate, device_rhs, jacobian are not accepted; coef_q with general only)")
+        if problem is not None and (not square or general):
+            raise ValueError("MultigridSolver(problem=...): a SquareProblem on a Square, not with general")
+        self.problem = problem
+        self._error_operands = {}
         if cube.size > 1 and comm is None:
             raise ValueError("a decomposed cube needs a Communicator")
         self.jacobian = None if jacobian is None else np.ascontiguousarray(jacobian, dtype=np.float64).reshape(3, 3)
@@ -1015,6 +1071,8 @@ class MultigridSolver:
             else:
                 jac = None if self.jacobian is None else self.jacobian.ctypes.data_as(_lib.f64p)
                 check(self.lib.mgx_cube_solver_create_general(*common, jac, cq, C.byref(self.s)))
+        elif problem is not None:
+            check(self.lib.mgx_square_solver_create_problem(*common, C.byref(problem.c), C.byref(self.s)))
         elif square:
             check(self.lib.mgx_square_solver_create(*common, int(bool(per_point)), C.byref(self.s)))
         else:
@@ -1193,6 +1251,13 @@ class MultigridSolver:
 
     def compute_l2_error(self, level=None):
         level = self.max_level if level is None else level
+        if self.problem is not None:  # on the device, against u(x_q) of the problem (kept per level)
+            if level not in self._error_operands:
+                self._error_operands[level] = tuple(
+                    self.ctx.vector(a.size, F64, data=a.ravel())
+                    for a in (self.cube.problem_solution_q(level, self.problem), self.cube.jxw_q(level)))
+            u_q, jxw_q = self._error_operands[level]
+            return self.matrix_dp(level).compute_l2_error(self.get_solution(level, True), u_q, jxw_q)
         sol = self.get_solution(level, True).download()
         if self.cube.size == 1:
             return self.cube.l2_error(level, sol)
@@ -1208,6 +1273,10 @@ class MultigridSolver:
         return t.reshape(-1, 6)
 
     def close(self):
+        for vectors in getattr(self, "_error_operands", {}).values():
+            for v in vectors:
+                v.free()
+        self._error_operands = {}
         if getattr(self, "h", None):
             self.lib.mgx_cube_solver_destroy(C.byref(self.s))
             self.h = None

@@ -48,6 +48,10 @@ class SquareBoxDesc(C.Structure):
                 ("h0", C.c_double), ("jacobian", C.POINTER(C.c_double))]
 
 
+class SquareProblem(C.Structure):
+    _fields_ = [("kind", C.c_int), ("contrast", C.c_double)]
+
+
 class OperatorDesc(C.Structure):
     _fields_ = [("degree", C.c_int), ("number", C.c_int), ("n_cells", C.c_uint32), ("n_dofs", C.c_uint32),
                 ("idx27", u32p), ("idx27_plain", u32p), ("constrained", u32p), ("n_constrained", C.c_uint32),
@@ -318,6 +322,17 @@ SIGNATURES = {
     "mgx_square_unit_q": (C.c_int, [vp, C.c_int, f64p]),
     "mgx_square_jxw_q": (C.c_int, [vp, C.c_int, f64p]),
     "mgx_square_solver_create_general": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(f64p), C.POINTER(CubeSolver)]),
+    # linear problems in two dimensions: device right-hand side, lifting, L2 error
+    "mgx_operator_dim": (C.c_int, [vp]),
+    "mgx_compute_residual_2d": (C.c_int, [vp, vp, vp, vp]),
+    "mgx_solver_compute_rhs_2d": (C.c_int, [vp, C.c_int, vp]),
+    "mgx_compute_l2_error_2d": (C.c_int, [vp, vp, vp, vp, f64p]),
+    "mgx_square_problem_coef_q": (C.c_int, [vp, C.c_int, C.POINTER(SquareProblem), f64p]),
+    "mgx_square_problem_rhs_quadrature": (C.c_int, [vp, C.c_int, C.POINTER(SquareProblem), f64p]),
+    "mgx_square_problem_solution_q": (C.c_int, [vp, C.c_int, C.POINTER(SquareProblem), f64p]),
+    "mgx_square_problem_bc_value": (C.c_int, [vp, C.c_int, C.POINTER(SquareProblem), f64p]),
+    "mgx_square_solver_create_problem": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(SquareProblem),
+                                                   C.POINTER(CubeSolver)]),
     # include/mgx_dg.h
     "mgx_dg_operator_create": (C.c_int, [vp, C.POINTER(DGOperatorDesc), C.POINTER(vp)]),
     "mgx_dg_operator_destroy": (C.c_int, [vp]),

@@ -1828,6 +1828,7 @@ int mgx_operator_set_profiled(mgx_operator_t op, int profiled)
   return MGX_OK;
 }
 int      mgx_operator_number(mgx_operator_t op) { return op ? op->d.number : -1; }
+int      mgx_operator_dim(mgx_operator_t op) { return op ? op->d.dim : -1; }
 
 int mgx_vmult(mgx_operator_t op, void *dst, const void *src)
 {
@@ -2077,6 +2078,57 @@ static int refuse_3d(mgx_operator_t op, const char *who, const char *instead)
   if (op->d.dim == 2)
     return MGX_OK;
   return fail(MGX_ERR_UNSUPPORTED, std::string(who) + ": not on a three-dimensional operator (call " + instead + ")");
+}
+
+/* LaplaceOperator<2,...>::compute_residual (laplace_operator.h:804-845): mgx_compute_residual with (p+1)^2 points per cell.
+ * The cells are added up as every two-dimensional result is -- the ordered assembly or the cell colours, never atomics. */
+int mgx_compute_residual_2d(mgx_operator_t op, void *dst, const void *src, const void *rhs_q)
+{
+  MGX_REQUIRE(op && dst, "mgx_compute_residual_2d: null argument");
+  MGX_REQUIRE(dst != src, "mgx_compute_residual_2d: dst and src must not alias");
+  MGX_TRY(refuse_3d(op, "mgx_compute_residual_2d", "mgx_compute_residual"));
+  // (the boundary values are gathered through the table that also names the constrained DoFs)
+  MGX_REQUIRE(op->d.idx27_plain, "mgx_compute_residual_2d: the operator was created without idx27_plain");
+  hipStream_t  s     = op->ctx->stream;
+  const size_t bytes = number_size(op->d.number) * op->d.n_dofs;
+  // temporaries of this call, released on every path out of it (after the stream has drained)
+  DeviceArena tmp("mgx_compute_residual_2d");
+  tmp.drain_before_release(s);
+  if (!src) // homogeneous boundary values
+    {
+      void *zero = nullptr;
+      MGX_TRY(tmp.zeros(&zero, bytes, s));
+      src = zero;
+    }
+  if (!op->d.asm_start) // the cell colours add to dst; the ordered assembly writes it
+    MGX_HIP(hipMemsetAsync(dst, 0, bytes, s));
+  launch_cell_residual_2d(s, op->d, dst, src, rhs_q);
+  MGX_HIP(hipGetLastError());
+  return MGX_OK;
+}
+
+/* MultigridSolver<2,...>::compute_l2_error (multigrid_solver.h:298-343) against a function given at the quadrature
+ * points: sums = { sum (u_h - u_q)^2 JxW_q, sum JxW_q }, formed in fp64 in a fixed order */
+int mgx_compute_l2_error_2d(mgx_operator_t op, const void *vec, const void *u_q, const void *jxw_q, double sums[2])
+{
+  MGX_REQUIRE(op && vec && u_q && jxw_q && sums, "mgx_compute_l2_error_2d: null argument");
+  MGX_TRY(refuse_3d(op, "mgx_compute_l2_error_2d", "the host's error evaluation, mgx_cube_l2_error"));
+  MGX_REQUIRE(op->d.idx27_plain, "mgx_compute_l2_error_2d: the operator was created without idx27_plain");
+  hipStream_t    s  = op->ctx->stream;
+  const uint32_t nb = l2_error_grid_2d(op->d.p, op->d.n_cells);
+  DeviceArena    tmp("mgx_compute_l2_error_2d");
+  tmp.drain_before_release(s);
+  double *partials = nullptr, *result = nullptr;
+  MGX_TRY(tmp.alloc(&partials, 4 * (size_t)nb));
+  MGX_TRY(tmp.alloc(&result, 4));
+  launch_l2_error_2d(s, op->d, vec, u_q, jxw_q, partials);
+  launch_reduce4(s, partials, nb, nullptr, result);
+  MGX_HIP(hipGetLastError());
+  double host[4];
+  MGX_HIP(hipMemcpyAsync(host, result, sizeof(host), hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
+  sums[0] = host[0], sums[1] = host[1];
+  return MGX_OK;
 }
 
 /* MinimalSurfaceOperator<2,...>::initialize (minimal_surface/program.cc:112-117 with dimension = 2, :73): the mapping data
@@ -3552,6 +3604,20 @@ int mgx_solver_compute_rhs(mgx_solver_t S, int level, const double *rhs_q)
   const int status = mgx_compute_residual(A, S->rhs[level], u, rhs_q);
   (void)hipStreamSynchronize(S->ctx->stream);
   return status;
+}
+
+int mgx_solver_compute_rhs_2d(mgx_solver_t S, int level, const double *rhs_q)
+{
+  MGX_REQUIRE(S && level >= 0 && level < S->n_levels, "mgx_solver_compute_rhs_2d: bad argument");
+  mgx_operator_t A = S->matrix_dp[level];
+  MGX_TRY(refuse_3d(A, "mgx_solver_compute_rhs_2d", "mgx_solver_compute_rhs"));
+  // the boundary values in a vector of their own (the level's solution vector is the caller's)
+  DeviceArena tmp("mgx_solver_compute_rhs_2d");
+  tmp.drain_before_release(S->ctx->stream);
+  double *u = nullptr;
+  MGX_TRY(tmp.zeros(&u, A->d.n_dofs, S->ctx->stream));
+  set_bc(S, level, u, false);
+  return mgx_compute_residual_2d(A, S->rhs[level], u, rhs_q);
 }
 
 int mgx_solver_solve(mgx_solver_t S, int do_analyze, double *reduction_rate, double *trace)

@@ -21,6 +21,21 @@ namespace mgx
     static constexpr int CELL_LDS = N * LN;
   };
 
+  // the forms of the cell loop (mgx_kernels_2d.hip) and of its residual form (mgx_rhs_2d.hip)
+  enum CellForm2
+  {
+    kDiagonalCoefficient = 0, // coef [xx,yy], weight per point
+    kTensorPerMesh       = 1, // coef [xx,yy,xy] (affine cells), weight per point
+    kTensorPerPoint      = 2  // coef_q [cell][3][n^2], weight folded in
+  };
+  inline int cell_form(const OperatorData &op)
+  {
+    return op.coef_q ? kTensorPerPoint : (op.full_tensor ? kTensorPerMesh : kDiagonalCoefficient);
+  }
+  // the lists of a launcher: none, once over all cells into the scratch array of the ordered assembly, where the operator
+  // has one; else its cell colours (operator_create has made sure that a level without the tables is coloured)
+  inline CellLists cell_lists_2d(const OperatorData &op) { return op.asm_start ? CellLists() : op.cell_colours.lists(); }
+
   // Line products of the cell loop.  An n x n matrix of doubles is 2 n^2 scalar registers when its product with a line is
   // unrolled: at n >= 9 that is more than a wave has (the compiler then parks them in vector registers lane by lane).
   // Those instantiations (ROLLED) take the line from LDS value by value in a loop that is not unrolled and keep only

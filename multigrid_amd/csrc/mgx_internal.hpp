@@ -604,6 +604,16 @@ namespace mgx
                                   const void *unit_q, const void *jxw_q, void *dst, const void *state);
   void launch_interpolate_to_coarse_2d(hipStream_t s, const TransferData &t, const void *r1d, const uint32_t *own_c, void *coarse,
                                        const void *fine);
+  // ---- linear problems on quadrilaterals (mgx_rhs_2d.hip) ----
+  // launch_cell_residual in two dimensions: dst = sum over the cells of S^T [ rhs_q - D^T (C D S src) ], src through
+  // idx27_plain, rows through idx27; rhs_q [n_cells][n^2] in the number type or nullptr.  The cells are added up as
+  // launch_cell_loop_2d does: the ordered assembly (dst is written) or colour by colour (dst zeroed by the caller).
+  void launch_cell_residual_2d(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *rhs_q);
+  // partials [l2_error_grid_2d][4]: block sums {sum (u_h - u_q)^2 JxW_q, sum JxW_q, 0, 0} in fp64, to be added by
+  // launch_reduce4; vec (through idx27_plain), u_q and jxw_q [n_cells][n^2] in the number type
+  void     launch_l2_error_2d(hipStream_t s, const OperatorData &op, const void *vec, const void *u_q, const void *jxw_q,
+                              double *partials);
+  uint32_t l2_error_grid_2d(int p, uint32_t n_cells);
 
   // ---- vector kernels (mgx_vector.hip) ----
   void launch_copy_cast(hipStream_t s, void *dst, int dn, const void *src, int sn, size_t n);

@@ -24,13 +24,6 @@
 
 namespace mgx
 {
-  enum CellForm2
-  {
-    kDiagonalCoefficient = 0, // coef [xx,yy], weight per point
-    kTensorPerMesh       = 1, // coef [xx,yy,xy] (affine cells), weight per point
-    kTensorPerPoint      = 2  // coef_q [cell][3][n^2], weight folded in
-  };
-
   // ------------------------------------------------------------------------------------------
   // Cell loop: local_apply of laplace_operator.h:527-558 with the quadrature-point operation :436-523 in two
   // dimensions.  Thread t of a cell is the row thread of x-line / quadrature row t and the column thread of column t.
@@ -531,15 +524,6 @@ namespace mgx
   // ------------------------------------------------------------------------------------------
   // launchers
   // ------------------------------------------------------------------------------------------
-  static int cell_form(const OperatorData &op)
-  {
-    return op.coef_q ? kTensorPerPoint : (op.full_tensor ? kTensorPerMesh : kDiagonalCoefficient);
-  }
-
-  // the lists of a launcher: none, once over all cells into the scratch array of the ordered assembly, where the operator
-  // has one; else its cell colours (operator_create has made sure that a level without the tables is coloured)
-  static CellLists cell_lists_2d(const OperatorData &op) { return op.asm_start ? CellLists() : op.cell_colours.lists(); }
-
   template <int P, typename T>
   static void cell_loop_2d_t(hipStream_t s, const OperatorData &op, void *dst, const void *src, const void *tail_src,
                              uint32_t n_head, const ChebPost *post)

@@ -496,6 +496,91 @@ namespace
     L.jxw_q.resize((size_t)L.n_cells * n2);
     return point_geometry(Q, L, L.unit_q.data(), L.jxw_q.data());
   }
+
+  // ---- linear problems on every square (mgx_square_problem) ----
+  // The geometry of a problem is that of point_geometry, stated once: a cell is the degree-p interpolant of its nodes
+  // (cell_nodes), x(xi, eta) = sum_ij phi_i(xi) phi_j(eta) X_ij.  Its quadrature points are therefore
+  // x_q = sum_ij S[qx][i] S[qy][j] X_ij, and unit_q / jxw_q come from the Jacobian of the same interpolant.
+  // xq[2 (qy n + qx)] from the nodes xy[2 (j n + i)] of a cell
+  void quadrature_points(const mgx_square_s &Q, const double *xy, double *xq)
+  {
+    const int     n = Q.p + 1;
+    const double *S = Q.basis.S;
+    for (int qy = 0; qy < n; ++qy)
+      for (int qx = 0; qx < n; ++qx)
+        {
+          double x = 0, y = 0;
+          for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i)
+              {
+                const double s = S[qx * n + i] * S[qy * n + j];
+                x += s * xy[2 * (j * n + i)];
+                y += s * xy[2 * (j * n + i) + 1];
+              }
+          xq[2 * (qy * n + qx)] = x, xq[2 * (qy * n + qx) + 1] = y;
+        }
+  }
+
+  // u, a and f = -(a lap u + grad a . grad u) of a problem at a point
+  struct ProblemFunctions
+  {
+    int    kind;
+    double contrast;
+    double u(double x, double y) const
+    {
+      return kind == MGX_SQUARE_PROBLEM_CUBE ? mgx_square_s::u(x, y) : std::sin(2 * kPi * (x + y));
+    }
+    // c_e = cos(2 pi x_e + 0.1 e), e = 0, 1 (poisson_shell/program.cc:157-169 with dim = 2)
+    double a(double x, double y) const
+    {
+      if (kind == MGX_SQUARE_PROBLEM_CUBE)
+        return 1.;
+      const double c0 = std::cos(2 * kPi * x), c1 = std::cos(2 * kPi * y + 0.1);
+      return 1. + contrast * (c0 * c0) * (c1 * c1);
+    }
+    double f(double x, double y) const
+    {
+      if (kind == MGX_SQUARE_PROBLEM_CUBE)
+        return mgx_square_s::f(x, y);
+      const double c0 = std::cos(2 * kPi * x), c1 = std::cos(2 * kPi * y + 0.1);
+      const double s0 = std::sin(2 * kPi * x), s1 = std::sin(2 * kPi * y + 0.1);
+      const double lap = -2 * (2 * kPi) * (2 * kPi) * std::sin(2 * kPi * (x + y)), du = 2 * kPi * std::cos(2 * kPi * (x + y));
+      const double ax = contrast * (-4 * kPi * c0 * s0) * (c1 * c1), ay = contrast * (c0 * c0) * (-4 * kPi * c1 * s1);
+      return -(lap * a(x, y) + (ax + ay) * du);
+    }
+  };
+
+  // the checked arguments of a problem accessor; the status is reported
+  int problem_arguments(mgx_square_t q, int l, const mgx_square_problem *problem, const void *out, const char *who, ProblemFunctions &F)
+  {
+    const auto refuse = [&](const char *why) { return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, (std::string(who) + why).c_str()); };
+    if (!valid(q, l) || !out)
+      return refuse(": bad argument");
+    if (!problem)
+      return refuse(": null problem");
+    if (problem->kind != MGX_SQUARE_PROBLEM_CUBE && problem->kind != MGX_SQUARE_PROBLEM_SHELL)
+      return refuse(": unknown problem kind");
+    if (problem->kind == MGX_SQUARE_PROBLEM_SHELL && !(problem->contrast >= 0. && std::isfinite(problem->contrast)))
+      return refuse(": the contrast must be finite and not negative");
+    F.kind     = problem->kind;
+    F.contrast = problem->contrast;
+    return MGX_OK;
+  }
+
+  // visit(cell, q, x, y) at every quadrature point of the level, cells and points in order
+  template <typename Visit>
+  void for_each_quadrature_point(const mgx_square_s &Q, const Level &L, Visit &&visit)
+  {
+    const size_t        n2 = (size_t)(Q.p + 1) * (Q.p + 1);
+    std::vector<double> xy(2 * n2), xq(2 * n2);
+    for (uint32_t c = 0; c < L.n_cells; ++c)
+      {
+        cell_nodes(Q, L, c, xy.data());
+        quadrature_points(Q, xy.data(), xq.data());
+        for (size_t k = 0; k < n2; ++k)
+          visit(c, k, xq[2 * k], xq[2 * k + 1]);
+      }
+  }
 } // namespace
 
 static int square_create(const mgx_square_box_desc *bd, int geometry, mgx_square_t *out);
@@ -834,6 +919,69 @@ int mgx_square_coef_q(mgx_square_t q, int l, double *out)
   return MGX_OK;
 }
 
+int mgx_square_problem_coef_q(mgx_square_t q, int l, const mgx_square_problem *problem, double *out)
+{
+  ProblemFunctions F;
+  if (const int status = problem_arguments(q, l, problem, out, "mgx_square_problem_coef_q", F); status != MGX_OK)
+    return status;
+  if (const int status = mgx_square_coef_q(q, l, out); status != MGX_OK) // the unit-law tensor of the level's geometry
+    return status;
+  const size_t n2 = (size_t)(q->p + 1) * (q->p + 1);
+  for_each_quadrature_point(*q, q->levels[l], [&](uint32_t c, size_t k, double x, double y) {
+    const double a = F.a(x, y);
+    for (int e = 0; e < 3; ++e)
+      out[((size_t)c * 3 + e) * n2 + k] *= a;
+  });
+  return MGX_OK;
+}
+
+int mgx_square_problem_rhs_quadrature(mgx_square_t q, int l, const mgx_square_problem *problem, double *out)
+{
+  ProblemFunctions F;
+  if (const int status = problem_arguments(q, l, problem, out, "mgx_square_problem_rhs_quadrature", F); status != MGX_OK)
+    return status;
+  if (const int status = mgx_square_jxw_q(q, l, out); status != MGX_OK)
+    return status;
+  const size_t n2 = (size_t)(q->p + 1) * (q->p + 1);
+  for_each_quadrature_point(*q, q->levels[l], [&](uint32_t c, size_t k, double x, double y) { out[(size_t)c * n2 + k] *= F.f(x, y); });
+  return MGX_OK;
+}
+
+int mgx_square_problem_solution_q(mgx_square_t q, int l, const mgx_square_problem *problem, double *out)
+{
+  ProblemFunctions F;
+  if (const int status = problem_arguments(q, l, problem, out, "mgx_square_problem_solution_q", F); status != MGX_OK)
+    return status;
+  const size_t n2 = (size_t)(q->p + 1) * (q->p + 1);
+  for_each_quadrature_point(*q, q->levels[l], [&](uint32_t c, size_t k, double x, double y) { out[(size_t)c * n2 + k] = F.u(x, y); });
+  return MGX_OK;
+}
+
+int mgx_square_problem_bc_value(mgx_square_t q, int l, const mgx_square_problem *problem, double *out)
+{
+  ProblemFunctions F;
+  if (const int status = problem_arguments(q, l, problem, out, "mgx_square_problem_bc_value", F); status != MGX_OK)
+    return status;
+  const Level          &L = q->levels[l];
+  const int             p = q->p, n = p + 1;
+  std::vector<uint32_t> at(L.n_dofs, MGX_INVALID_INDEX); // DoF -> position in the list of constrained DoFs
+  for (size_t i = 0; i < L.constrained.size(); ++i)
+    at[L.constrained[i]] = (uint32_t)i;
+  std::vector<double> xy(2 * (size_t)n * n);
+  for (uint32_t c = 0; c < L.n_cells; ++c)
+    {
+      cell_nodes(*q, L, c, xy.data());
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i)
+          {
+            const uint32_t k = at[mgx::cell_dof(&L.idx9_plain[9 * (size_t)c], 2, p, i, j)];
+            if (k != MGX_INVALID_INDEX)
+              out[k] = F.u(xy[2 * (j * n + i)], xy[2 * (j * n + i) + 1]);
+          }
+    }
+  return MGX_OK;
+}
+
 // general: the hierarchy of mgx_square_solver_create_general with the tensors coef_q[l] (nullptr: the unit law)
 static int square_solver_create(mgx_context_t ctx, mgx_square_t q, int vnumber, int degree_pre, int n_cycles, int per_point,
                                 bool general, const double *const *coef_q, mgx_cube_solver *out);
@@ -855,6 +1003,66 @@ int mgx_square_solver_create_general(mgx_context_t ctx, mgx_square_t q, int vnum
   if (!ctx || !q || !out || (vnumber != MGX_F32 && vnumber != MGX_F64))
     return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_solver_create_general: bad argument");
   return square_solver_create(ctx, q, vnumber, degree_pre, n_cycles, 1, true, coef_q, out);
+}
+
+int mgx_square_solver_create_problem(mgx_context_t ctx, mgx_square_t q, int vnumber, int degree_pre, int n_cycles,
+                                     const mgx_square_problem *problem, mgx_cube_solver *out)
+{
+  if (!ctx || !q || !out || (vnumber != MGX_F32 && vnumber != MGX_F64))
+    return mgx::report_error(MGX_ERR_INVALID_ARGUMENT, "mgx_square_solver_create_problem: bad argument");
+  const int                        nl = (int)q->levels.size();
+  const size_t                     n2 = (size_t)(q->p + 1) * (q->p + 1);
+  std::vector<std::vector<double>> bc_value(nl); // (read by mgx_solver_create, after every level was described)
+  for (int l = 0; l < nl; ++l)
+    {
+      bc_value[l].resize(std::max<size_t>(q->levels[l].constrained.size(), 1));
+      // (checks the problem as well, before anything exists on the device)
+      if (const int status = mgx_square_problem_bc_value(q, l, problem, bc_value[l].data()); status != MGX_OK)
+        return status;
+    }
+  const auto describe = [&](int l, mgx::LevelDesc &d) {
+    const Level &L = q->levels[l];
+    mgx_square_operator_desc(q, l, MGX_F64, &d.op);
+    d.scratch.resize((size_t)L.n_cells * 3 * n2);
+    if (const int status = mgx_square_problem_coef_q(q, l, problem, d.scratch.data()); status != MGX_OK)
+      return status;
+    d.op.coef_q             = d.scratch.data(); // (an fp32 V-cycle operator receives it rounded)
+    d.transfer.children     = L.children.data();
+    d.transfer.prolong_1d   = q->basis.P1;
+    d.transfer.weight_shift = L.weight_shift.empty() ? nullptr : L.weight_shift.data();
+    d.rhs                   = nullptr; // assembled on the device below
+    d.bc_index              = L.constrained.data();
+    d.bc_value              = bc_value[l].data();
+    d.bc_count              = (uint32_t)L.constrained.size();
+    return (int)MGX_OK;
+  };
+  int status = mgx::build_hierarchy(ctx, nl, vnumber, degree_pre, n_cycles, describe, out);
+  if (status != MGX_OK)
+    return status;
+  // the right-hand sides on the device (laplace_operator.h:804-845): the host only evaluates f JxW at the quadrature
+  // points (the loop of mgx_cube_solver_create_opt)
+  for (int l = 0; l < nl && status == MGX_OK; ++l)
+    {
+      const size_t        count = n2 * q->levels[l].n_cells;
+      std::vector<double> fq(count);
+      void               *fq_dev = nullptr;
+      status                     = mgx_square_problem_rhs_quadrature(q, l, problem, fq.data());
+      if (status == MGX_OK)
+        status = mgx_malloc(ctx, &fq_dev, sizeof(double) * count);
+      if (status == MGX_OK)
+        status = mgx_upload(ctx, fq_dev, fq.data(), sizeof(double) * count);
+      if (status == MGX_OK)
+        status = mgx_solver_compute_rhs_2d(out->solver, l, (const double *)fq_dev);
+      if (fq_dev)
+        {
+          const std::string keep = status != MGX_OK ? mgx_last_error() : "";
+          (void)mgx_sync(ctx);
+          (void)mgx_free(ctx, fq_dev);
+          if (status != MGX_OK)
+            mgx::report_error(status, keep.c_str());
+        }
+    }
+  return status == MGX_OK ? MGX_OK : mgx::abandon_hierarchy(status, out);
 }
 
 } // extern "C"
